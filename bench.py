@@ -22,11 +22,18 @@ value     = locus-likelihood evaluations per second (computeLocusDataLikelihood(
             equivalents, counted by the kernels); MCMC iterations/s is reported next to it.
 roofline  = dominant kernel (fused genealogy sweep): algorithmic bytes (96*R*P + 20*N + 8*U + 8 per
             evaluation, counted per evaluation by the kernel) / HIP-event duration, vs 8 TB/s HBM.
-cpu_baseline = the REAL reference (oracle/_ref, OpenMP build).  VALUE: timed on ALL loci of the workload (--cpu-full-loci, default
-            100 000 = the size the metric is quoted on), one start-up, 1 warm-up + 5 iterations (median) at 1 thread and at the
-            best thread count of the thread sweep.  The thread sweep (`thread_sweep`): the first --cpu-loci loci (20 000: a
-            0.7-GB working set, beyond any L3) at 1 / 8 / 16 / 32 / all host threads.  Secondary, labelled: the serial build and
-            the oracle restatement on 5 000 loci.  Rank 0, N = 1 only.  The whole leg stays under five minutes.
+cpu_baseline = (--full only) the REAL reference (oracle/_ref, OpenMP build).  VALUE: timed on ALL loci of the workload
+            (--cpu-full-loci, default 100 000 = the size the metric is quoted on), one start-up, 1 warm-up + 5 iterations
+            (median) at 1 thread and at the best thread count of the thread sweep.  The thread sweep (`thread_sweep`): the first
+            --cpu-loci loci (20 000: a 0.7-GB working set, beyond any L3) at 1 / 8 / 16 / 32 / all host threads.  Secondary,
+            labelled: the serial build and the oracle restatement on 5 000 loci.  Rank 0, N = 1 only.  The whole leg stays
+            under five minutes.
+
+A plain run sets up, runs the pre-roll and the warm-up, times the --steps steps and prints the line; --full adds the CPU
+baseline.  --dump-outputs DIR writes, after the timed steps, what the chain holds after its last step as DIR/<name>.npy
+(float64): the global parameters and log-likelihoods, the cumulative accept counters, every locus's data and genealogy
+log-likelihood and the node ages of a fixed, seeded sample of loci.  The data set and the chain's seed are fixed, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -54,7 +61,10 @@ def build_workload(G, config, L, mut_scale, seed0, cache_dir, begin=0, L_total=N
     """loci [begin, begin + L) of an L_total-locus synthetic data set of the config's shape, generated in
     parallel chunks (chunk c always has seed seed0 + 1000 + c, so a rank's shard is the same data whether it
     is generated alone or as part of the whole set) and cached as .npz"""
-    os.makedirs(cache_dir, exist_ok=True)
+    try:
+        os.makedirs(cache_dir, exist_ok=True)
+    except OSError:
+        pass                    # a tree this user may not write to: the data set is generated, not cached
     L_total = L if L_total is None else L_total
     key = os.path.join(cache_dir, f"synth_c{config}_L{L}_b{begin}_m{mut_scale}_s{seed0}.npz")
     base = G.Pack()
@@ -262,6 +272,82 @@ def build_shard(G, config, L_total, begin, end, mut_scale, seed0, cache_dir):
     return pk
 
 
+DUMP_SAMPLE_LOCI = 1024          # loci whose genealogy (node ages) --dump-outputs writes
+DUMP_SAMPLE_SEED = 20261016
+
+
+def _read_state_dump(path, sample):
+    """(global locus ids, dataLnL, genLnL, {global id: node ages}) of the LOCUS / N lines of a canonical state dump
+    (gph_mcmc_dump_state); node ages only for the global ids in `sample`"""
+    import mmap
+    import re
+    ids, dlnl, glnl, ages = [], [], [], {}
+    node = re.compile(rb"N \S+ \S+ \S+ \S+ (\S+) ")
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+        for m in re.finditer(rb"^LOCUS (\d+) root \S+ dataLnL (\S+) genLnL (\S+) ", mm, re.M):
+            g = int(m.group(1))
+            ids.append(g)
+            dlnl.append(float.fromhex(m.group(2).decode()))
+            glnl.append(float.fromhex(m.group(3).decode()))
+            if g in sample:
+                row, pos = [], mm.find(b"\n", m.end()) + 1
+                if mm[pos:pos + 2] == b"R ":          # the locus's mutation rate (variable rates only)
+                    pos = mm.find(b"\n", pos) + 1
+                while mm[pos:pos + 2] == b"N ":
+                    end = mm.find(b"\n", pos)
+                    row.append(float.fromhex(node.match(mm, pos, end + 1).group(1).decode()))
+                    pos = end + 1
+                ages[g] = row
+    return ids, dlnl, glnl, ages
+
+
+def dump_outputs(s, out_dir, L_total, rank, world, dist):
+    """--dump-outputs: what the chain holds after the last timed step, as float64 arrays in out_dir/<name>.npy.  Every rank
+    writes the canonical state dump of its loci (the dump refreshes the chain's totals: a reduction point, so all ranks
+    take part); rank 0 reads them in rank order and writes the arrays."""
+    os.makedirs(out_dir, exist_ok=True)
+    part = os.path.join(out_dir, f".state.rank{rank}")
+    s.dump_state(part)
+    if dist:
+        dist.barrier()
+    if rank == 0:
+        st = s.state()
+        sample = set(np.random.default_rng(DUMP_SAMPLE_SEED).choice(L_total, min(DUMP_SAMPLE_LOCI, L_total), replace=False).tolist())
+        ids, dlnl, glnl, ages = [], [], [], {}
+        for r in range(world):
+            i, d, g, a = _read_state_dump(os.path.join(out_dir, f".state.rank{r}"), sample)
+            ids += i
+            dlnl += d
+            glnl += g
+            ages.update(a)
+        assert ids == list(range(L_total)), "the state dumps do not hold every locus once, in order"
+        out = {"log_likelihood": [st["logLikelihood"], st["dataLogLikelihood"]], "theta": st["theta"], "pop_age": st["popAge"],
+               "mig_rate": st["migRate"], "accept_counts": s.accept_counts(), "locus_data_lnl": dlnl, "locus_gen_lnl": glnl,
+               "sample_loci": sorted(sample), "sample_node_ages": [ages[g] for g in sorted(sample)]}
+        for name, v in out.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64))
+    if dist:
+        dist.barrier()
+    os.unlink(part)
+
+
+def bring_libraries_up_to_date(G):
+    """build() compiles the libraries; the bench rebuilds stale ones only where this user may write to the package
+    directory and its lock file (G.build() opens g-phocs_amd/.build.lock for writing even when nothing is stale).  In a
+    tree built by another user the libraries are loaded as they are; a missing one is an error of load_library."""
+    pkg = os.path.dirname(os.path.abspath(G.LIB_PATH))
+    lock = os.path.join(pkg, ".build.lock")
+    if os.access(pkg, os.W_OK) and (not os.path.exists(lock) or os.access(lock, os.W_OK)):
+        try:
+            G.build()
+            return
+        except PermissionError as ex:
+            why = str(ex)
+    else:
+        why = f"{pkg} or its build lock is not writable for this user"
+    print(f"bench: libraries not rebuilt ({why}): using them as built", file=sys.stderr)
+
+
 def _free_port():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -347,7 +433,7 @@ def launch_ranks(a):
         import run_hostemu
         run_hostemu.build_hostemu()             # once, before the ranks ask for it
     else:
-        G.build()                               # once, before the ranks race for the build lock
+        bring_libraries_up_to_date(G)           # once, before the ranks race for the build lock
     env = dict(os.environ, WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     procs = []
@@ -418,7 +504,11 @@ def main():
     ap.add_argument("--cpu-iters", type=int, default=5, help="timed iterations per thread count of the CPU baseline (median reported)")
     ap.add_argument("--cpu-small-loci", type=int, default=5000, help="the secondary, cache-friendlier CPU sample")
     ap.add_argument("--cpu-small-iters", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU "
+                    "baseline (minutes of host time)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the chain holds "
+                    "after its last step as DIR/<name>.npy")
     ap.add_argument("--lib", default=None, help="alternative build of the library (A/B measurements)")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "hook", "shm"], help="cross-rank exchange: native RCCL all-gather on "
                     "the engine's stream (default), the torch.distributed hook (a host round trip per reduction), or the "
@@ -452,8 +542,7 @@ def main():
         if a.comm == "rccl":
             a.comm = "shm"
     else:
-        G.build()
-        torch.cuda.set_device(local_rank)
+        bring_libraries_up_to_date(G)
     dev_sync = (lambda: None) if emu else torch.cuda.synchronize
     dist = None
     allreduce = None
@@ -466,7 +555,10 @@ def main():
     if end <= begin:
         print(f"bench: rank {rank} of {world} gets no loci out of {L_total}", file=sys.stderr)
         sys.exit(2)
+    # the data set is generated (forked worker processes on a cold cache) before this process opens the GPU
     pack = build_shard(G, a.config, L_total, begin, end, a.mut_scale, 20261002 + a.config, os.path.join(REPO, "bench_cache"))
+    if not emu:
+        torch.cuda.set_device(local_rank)
     if a.samples_per_log > 0:
         pack.samplesPerLog = a.samples_per_log
     lib = G.load_library(a.lib) if a.lib else G.load_library(dims=(pack.n, pack.K, pack.B))
@@ -693,7 +785,7 @@ def main():
         }
         if emu:
             line["data"] = "synthetic; HOST EMULATION of the engine sources (tests only): not a measurement"
-        if world == 1 and not a.no_cpu_baseline and not emu:
+        if a.full and world == 1 and not a.no_cpu_baseline and not emu:
             try:
                 cb = cpu_baseline_reference(a.config, pack, min(a.cpu_loci, L_total), a.cpu_iters,
                                             min(a.cpu_small_loci, L_total), a.cpu_small_iters,
@@ -707,6 +799,8 @@ def main():
                 line["cpu_baseline"] = cb
             except Exception as ex:  # pragma: no cover
                 line["cpu_baseline"] = {"error": str(ex)}
+    if a.dump_outputs:
+        dump_outputs(s, a.dump_outputs, L_total, rank, world, dist)
     s.close()
     if comm:
         lib.gph_comm_destroy(comm)

@@ -25,10 +25,12 @@ CASES = ["g1", "m3", "a7", "f3", "v8", "w2", "x8", "r5", "j1", "j2", "j3"]   # (
 
 
 def _build():
+    # the host build of the engine sources that gphocs_boundary_emu runs over: needed wherever the binary is, also where it
+    # was built elsewhere and copied along with the tree
+    sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
+    import run_hostemu
+    run_hostemu.build_hostemu()
     if os.path.isdir("/root/reference/src"):
-        sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
-        import run_hostemu
-        run_hostemu.build_hostemu()
         subprocess.run(["make", "-C", ORACLE_DIR, "ref"], check=True, capture_output=True, timeout=900)
         subprocess.run(["make", "-C", ORACLE_DIR, "boundary"], check=True, capture_output=True, timeout=900)
 

@@ -270,21 +270,18 @@ def test_program_prints_the_reference_log(name, tmp_path):
         assert w == g, (i, w, g)
 
 
-def test_reference_sample_control_file_end_to_end(lib, ref_cli, tmp_path):
-    """BASELINE configs[0]: the reference's OWN sample-control-file.ctl (read where it lies under /root/reference; it is
-    not copied into the repo, so this runs in the build container only).  Its sequence file is absent upstream
-    (.MISSING_LARGE_BLOBS), so a small synthetic one with the file's sample names is written here; a secondary control
-    file gives the seed and a short run.  The model, the priors, every phased pattern table and the trace file must equal
-    the real reference's for the same three files."""
+SAMPLE_CTL = "sample-control-file.ctl"      # the reference's own sample control file, unchanged (a data fixture)
+
+
+def _sample_inputs(d):
+    """the three input files of the sample-control-file run in directory d: the control file, a small synthetic sequence
+    file with its sample names (its own is absent upstream: .MISSING_LARGE_BLOBS) and a secondary control file that gives
+    the seed and a short run"""
     import random
-    import subprocess
-    src = "/root/reference/sample-control-file.ctl"
-    if not os.path.exists(src) or ref_cli is None:
-        pytest.skip("the reference tree is absent on this box")
-    shutil.copy(src, tmp_path / "sample.ctl")
+    shutil.copy(os.path.join(GOLDEN, SAMPLE_CTL), os.path.join(d, "sample.ctl"))
     rnd = random.Random(20261002)
     names = ["one", "two", "three", "five"]           # the `samples ... d` entries of the file's four current populations
-    with open(tmp_path / "seqs-sample.txt", "w") as f:
+    with open(os.path.join(d, "seqs-sample.txt"), "w") as f:
         f.write("9\n\n")
         for g in range(9):
             L = 220
@@ -297,11 +294,36 @@ def test_reference_sample_control_file_end_to_end(lib, ref_cli, tmp_path):
                     row.append(b if u < 0.93 else rnd.choice("TCAG") if u < 0.96 else rnd.choice("YRMKSW") if u < 0.995 else "N")
                 f.write(f"{s}\t{''.join(row)}\n")
             f.write("\n")
-    (tmp_path / "short.ctl").write_text("GENERAL-INFO-START\n\trandom-seed 4711\n\tmcmc-iterations 40\n\titerations-per-log 10\n"
-                                        "\tlogs-per-line 2\nGENERAL-INFO-END\n")
+    with open(os.path.join(d, "short.ctl"), "w") as f:
+        f.write("GENERAL-INFO-START\n\trandom-seed 4711\n\tmcmc-iterations 40\n\titerations-per-log 10\n"
+                "\tlogs-per-line 2\nGENERAL-INFO-END\n")
+
+
+def _sample_reference_outputs(ref_cli, d):
+    """the real reference on the sample inputs in d: its pack (sample.gpk) and its trace file (sample.trace); what
+    tests/golden/sample.gpk and sample.trace hold"""
+    import subprocess
     env = dict(os.environ, GPH_REF_CTL2="short.ctl")
-    subprocess.run([ref_cli, "pack", "sample.ctl", "ref.gpk"], cwd=tmp_path, check=True, capture_output=True, timeout=300, env=env)
-    ref = G.Pack.load(str(tmp_path / "ref.gpk"))
+    subprocess.run([ref_cli, "pack", "sample.ctl", "sample.gpk"], cwd=d, check=True, capture_output=True, timeout=300, env=env)
+    subprocess.run([ref_cli, "main", "-n", "1", "sample.ctl", "short.ctl"], cwd=d, check=True, capture_output=True, timeout=600)
+    os.replace(os.path.join(d, "mcmc.log"), os.path.join(d, "sample.trace"))
+
+
+def test_reference_sample_control_file_end_to_end(lib, ref_cli, tmp_path):
+    """BASELINE configs[0]: the reference's OWN sample-control-file.ctl (tests/golden/sample-control-file.ctl).  Its
+    sequence file is absent upstream, so a small synthetic one with the file's sample names is written here; a secondary
+    control file gives the seed and a short run.  The model, the priors, every phased pattern table and the trace file must
+    equal the real reference's for the same three files (tests/golden/sample.gpk, sample.trace; where the reference harness
+    oracle/_ref/gphocs_ref is built, it is run on the same files and must reproduce them byte for byte)."""
+    _sample_inputs(str(tmp_path))
+    if ref_cli is not None:
+        live = tmp_path / "live"
+        live.mkdir()
+        _sample_inputs(str(live))
+        _sample_reference_outputs(ref_cli, str(live))
+        for f in ("sample.gpk", "sample.trace"):
+            assert (live / f).read_bytes() == open(os.path.join(GOLDEN, f), "rb").read(), f
+    ref = G.Pack.load(os.path.join(GOLDEN, "sample.gpk"))
     with _in_dir(tmp_path):
         got = G.Pack.from_control("sample.ctl", lib=lib, secondary="short.ctl")
     assert (got.n, got.Kc, got.K, got.B) == (8, 4, 7, 1) == (ref.n, ref.Kc, ref.K, ref.B)
@@ -311,9 +333,7 @@ def test_reference_sample_control_file_end_to_end(lib, ref_cli, tmp_path):
               "ageStart", "ftTaus", "printFactors", "pattern_offsets", "leafcodes", "numPhases", "counts"):
         assert np.array_equal(np.asarray(getattr(ref, f)), np.asarray(getattr(got, f))), f
     # the whole program: the real binary's trace file (mcmc.log) against gph_run_control_file's
-    subprocess.run([ref_cli, "main", "-n", "1", "sample.ctl", "short.ctl"], cwd=tmp_path, check=True, capture_output=True, timeout=600)
-    want = open(tmp_path / "mcmc.log").read()
-    os.remove(tmp_path / "mcmc.log")
+    want = open(os.path.join(GOLDEN, "sample.trace")).read()
     with _in_dir(tmp_path):
         assert lib.gph_run_control_file(b"sample.ctl", b"short.ctl", 0, 0) == 0
     got_t = open(tmp_path / "mcmc.log").read()

@@ -129,8 +129,8 @@ def test_hip_on_random_models(oracle_cli, name, tmp_path):
 
 def test_fresh_random_models_reference_vs_oracle(oracle_cli, ref_cli, tmp_path):
     """20 models that are NOT committed fixtures (ids 200-219), through the real reference and the oracle"""
-    if ref_cli is None or not os.path.isdir("/root/reference/src"):
-        pytest.skip("oracle/_ref/gphocs_ref not built (the GPU box): the committed fixtures cover this there")
+    if ref_cli is None:
+        pytest.skip("oracle/_ref/gphocs_ref not built: the committed fixtures cover this")
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import random_models as RM
     bad = 0

@@ -20,7 +20,7 @@ n = s["SQ_WAVES"]["sum"]
 print("k_sweep dispatches", nd, "fetch GB %.2f write GB %.2f" % (fetch / 1e9, write / 1e9))
 for c in sorted(s):
     print("%-22s per wave %12.1f" % (c, s[c]["sum"] / n))
-b = json.load(open(f"gpurun_out/bench_{tag}.json"))
+b = json.load(open(f"bench_cache/bench_{tag}.json"))       # the bench.py --full line of tools/profile_round.sh
 build_id = b["config"].get("library_build_id")
 json.dump({"kernel": "k_sweep", "loci": 100000, "hbm_bytes_per_launch": fetch + write, "fetch_bytes": fetch,
            "write_bytes": write, "build": f"{rnd} {tag}, library variant s", "build_id": build_id,

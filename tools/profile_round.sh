@@ -1,7 +1,7 @@
 #!/bin/bash
 # Everything the round's measurement section cites, in one GPU-box call (run through gpurun from the repo root):
 #   bash tools/profile_round.sh <tag>
-#   gpurun_out/bench_<tag>.json          the bench line (with cpu_baseline), default flags = what the driver runs
+#   bench_cache/bench_<tag>.json         the bench line with cpu_baseline (bench.py --full, default sizes)
 #   gpurun_out/kstats_<tag>/             rocprofv3 --kernel-trace --stats of the same command
 #   gpurun_out/pmc_<tag>.json            counter passes (tools/pmc_collect.sh; FETCH_SIZE and WRITE_SIZE in their own passes)
 #   gpurun_out/bench_<tag>_12500.json    the per-GPU share of the 100k-locus set at 8 GPUs, on this one GPU (strong-scaling proxy)
@@ -9,7 +9,8 @@ set -u
 TAG=${1:-run}
 ROOT=$(pwd)
 export TMPDIR=/tmp
-python3 bench.py --steps 20 --warmup 5 > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
+mkdir -p bench_cache
+python3 bench.py --full --steps 20 --warmup 5 > bench_cache/bench_$TAG.json 2> bench_cache/bench_$TAG.err
 echo "bench rc=$?"
 python3 bench.py --steps 20 --warmup 5 --loci 12500 --no-cpu-baseline > gpurun_out/bench_${TAG}_12500.json 2> gpurun_out/bench_${TAG}_12500.err
 echo "bench 12500 rc=$?"
