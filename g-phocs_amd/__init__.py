@@ -284,6 +284,8 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_mcmc_get_chain", "gph_mcmc_set_chain", "gph_mcmc_update_gb", "gph_mcmc_update_locus_rate", "gph_mcmc_update_theta",
     "gph_mcmc_update_mig_rates", "gph_mcmc_update_tau", "gph_mcmc_update_sample_age", "gph_mcmc_mixing",
     "gph_mcmc_synchronize_events", "gph_mcmc_check_all", "gph_mcmc_initialize_genealogies",
+    "gph_engine_locus_summary_enable", "gph_engine_locus_summary_sample", "gph_engine_locus_summary_columns",
+    "gph_engine_locus_summary_fetch", "gph_engine_locus_summary_column_name", "gph_loci_name", "gph_run_control_file_ex",
 ]
 
 
@@ -380,6 +382,15 @@ def _load_library(path):
     lib.gph_comm_on_stream.argtypes = [C.c_void_p]
     lib.gph_comm_attach_shm.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.gph_comm_attach_shm.restype = C.c_void_p
+    lib.gph_engine_locus_summary_enable.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_locus_summary_sample.argtypes = [C.c_void_p]
+    lib.gph_engine_locus_summary_columns.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    lib.gph_engine_locus_summary_fetch.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int32]
+    lib.gph_engine_locus_summary_column_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_locus_summary_column_name.restype = C.c_char_p
+    lib.gph_loci_name.argtypes = [C.c_void_p, C.c_int64]
+    lib.gph_loci_name.restype = C.c_char_p
+    lib.gph_run_control_file_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p]
     return lib
 
 
@@ -548,6 +559,7 @@ class Pack:
                 p.counts = view(cn, Ptot, C.c_int32, np.int32)
                 p.mutRates = view(mr, p.L, C.c_double, np.float64)
                 p.unphased = view(up, p.L, C.c_int32, np.int32)
+                p.locusNames = [lib.gph_loci_name(loci, g).decode() for g in range(p.L)]
             finally:
                 lib.gph_loci_free(loci)
             return p
@@ -559,6 +571,34 @@ class Pack:
         MultiCoreUtils.h:8); returns (begin, end)"""
         per = (self.L + world - 1) // world
         return min(rank * per, self.L), min((rank + 1) * per, self.L)
+
+
+def summary_table(raw, S, pack):
+    """the derived columns of the `-l` summary file from the raw accumulators (README.md): mean = shift + s1 / S,
+    var = (s2 - s1 * s1 / S) / (S - 1) for S > 1 (else 0), sd = sqrt(max(var, 0)), pmig = nonzero / S, mean counts = sum / S.
+    Keys as the file's header: dataLnL, dataLnL_sd, ..., mig_<src>-><tgt>, pmig_<src>-><tgt>, coal_<pop>[, rate, rate_sd]."""
+    t = {"samples": np.full(len(raw["dataLnL.shift"]), S, dtype=np.int64)}
+
+    def moments(q, name):
+        sh, s1, s2 = raw[q + ".shift"], raw[q + ".s1"], raw[q + ".s2"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t[name] = sh + s1 / S
+            var = (s2 - s1 * s1 / S) / (S - 1) if S > 1 else np.zeros_like(sh)
+        t[name + "_sd"] = np.sqrt(np.where(var < 0.0, 0.0, var))
+    moments("dataLnL", "dataLnL")
+    moments("genLnL", "genLnL")
+    moments("tmrca", "tmrca")
+    names = getattr(pack, "popName", None) or [str(k) for k in range(pack.K)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for b in range(pack.B):
+            band = f"{names[int(pack.bandSrc[b])]}->{names[int(pack.bandTgt[b])]}"
+            t["mig_" + band] = raw[f"nmig.{b}"] / S
+            t["pmig_" + band] = raw[f"pmig.{b}"] / S
+        for k in range(pack.K):
+            t["coal_" + names[k]] = raw[f"ncoal.{k}"] / S
+    if "rate.shift" in raw:
+        moments("rate", "rate")
+    return t
 
 
 def _dp(a):
@@ -712,6 +752,30 @@ class Sampler:
         w, c = C.c_int32(), C.c_int32()
         self._chk(self.lib.gph_engine_debug_oob(self.engine, C.byref(w), C.byref(c)), "debug_oob")
         return w.value, c.value
+
+    # ---- per-locus posterior summaries (gph_engine_locus_summary_*): accumulated on the device, one sample per call
+    def enable_locus_summary(self, on=True):
+        self._chk(self.lib.gph_engine_locus_summary_enable(self.engine, int(bool(on))), "locus_summary_enable")
+
+    def sample_locus_summary(self):
+        self._chk(self.lib.gph_engine_locus_summary_sample(self.engine), "locus_summary_sample")
+
+    def locus_summary(self, raw=False, reset=False):
+        """dict of numpy arrays, one entry per local locus in global locus order.  raw=True: the accumulators as the engine
+        keeps them, keyed by their machine names (gph_engine_locus_summary_column_name) + "samples".  raw=False: the columns
+        of the `-l` summary file (README.md), derived from the raw ones with the formulas given there."""
+        nc, ns = C.c_int32(), C.c_int64()
+        self._chk(self.lib.gph_engine_locus_summary_columns(self.engine, C.byref(nc), C.byref(ns)), "locus_summary_columns")
+        nloc = self.end - self.begin
+        out = np.zeros((nloc, max(nc.value, 1)))
+        self._chk(self.lib.gph_engine_locus_summary_fetch(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[1],
+                                                          int(bool(reset))), "locus_summary_fetch")
+        cols = {self.lib.gph_engine_locus_summary_column_name(self.engine, c).decode(): out[:, c].copy() for c in range(nc.value)}
+        S = ns.value
+        if raw:
+            cols["samples"] = np.full(nloc, S, dtype=np.int64)
+            return cols
+        return summary_table(cols, S, self.pack)
 
     def hbm_bytes(self):
         b = C.c_double()

@@ -14,12 +14,14 @@
 #include <stddef.h>
 #include <string.h>
 #include <vector>
+#include <string>
 #include <algorithm>
 #if defined(GPH_HOSTEMU) && defined(GPH_EMU64)
 #define GPH_EMU64_IMPL      /* this translation unit holds the micro-wave scheduler (gph_emu64.h; test builds only) */
 #endif
 #include "gph_kernels.h"
 #include "gph_global.h"
+#include "gph_summary.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
 
@@ -426,6 +428,11 @@ struct gph_engine {
   bool mirror_current = true;  // the host mirror G_h holds what the device-side stages last wrote (false between a queued stage and pull_G)
   bool no_fuse = false;        // GPH_NO_FUSE=1 (tests): every finish as a kernel of its own; read once in gph_engine_create
   gph_counters counters = {0, 0, 0.0, 0};
+  // per-locus summaries (gph_summary.h): [ls_ncol][L] accumulators in slot order, samples since they were last zeroed
+  double *d_ls = nullptr;
+  int32_t ls_ncol = 0;
+  int64_t ls_samples = 0;
+  std::vector<std::string> ls_names;
   double last_ms[16] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[16] = {0}, cls_ms[16] = {0};
@@ -987,6 +994,20 @@ static int run_stage_now(gph_engine *e, int stage, int arg)
   return check_error(e);
 }
 
+// the per-locus summary accumulators back to zero samples (queued on the engine's stream; nothing if summaries are off)
+static int ls_zero(gph_engine *e)
+{
+  e->ls_samples = 0;
+  if (!e->d_ls) return 0;
+  const size_t bytes = sizeof(double) * (size_t)e->ls_ncol * e->L;
+#ifdef GPH_HOSTEMU
+  memset(e->d_ls, 0, bytes);
+#else
+  HIPCHK(hipMemsetAsync(e->d_ls, 0, bytes, e->stream));
+#endif
+  return 0;
+}
+
 // ---------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -1065,7 +1086,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->dev.pages); dev_free(e->dev.shadow); dev_free(e->dev.cond); dev_free((void *)e->dev.cond_off);
   dev_free((void *)e->dev.seq); dev_free((void *)e->dev.seq_off); dev_free((void *)e->dev.orig); dev_free((void *)e->dev.P); dev_free(e->dev.out); dev_free(e->dev.stats); dev_free(e->d_mutRate);
   dev_free(e->d_lrec); dev_free(e->d_lpre); dev_free(e->d_slot_of); dev_free(e->d_lr_result); dev_free(e->d_lr_gscr); dev_free(e->d_ref_page); dev_free(e->d_ref_seq);
-  dev_free(e->d_part); dev_free(e->dev.err);
+  dev_free(e->d_part); dev_free(e->dev.err); dev_free(e->d_ls);
   for (void *p : e->deferred_free) dev_free(p);
   e->deferred_free.clear();
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
@@ -1389,6 +1410,9 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   e->mix_owed = e->fin_owed = e->sync_pending = false;
   if (e->G_h->mix_flag || e->G_h->tau_flag) { e->G_h->mix_flag = 0; e->G_h->tau_flag = 0; e->G_dirty = true; }
   PUSH_IF_DIRTY(e);
+  /* summaries of the old chain do not carry over; the locus-rate columns come and go with `locus-mut-rate VAR` */
+  if (e->d_ls && e->ls_ncol != gph_ls_columns(e->cfg.K, e->cfg.B, e->var_rates)) { int rce = gph_engine_locus_summary_enable(e, 1); if (rce) return rce; }
+  { int rcz = ls_zero(e); if (rcz) return rcz; }
   LAUNCH(e, 3, k_init, e->seedz, (const double *)e->d_mutRate, e->init_predraws);
   int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -2386,6 +2410,93 @@ int gph_engine_dump_loci(gph_engine *e, const char *path, int32_t withCond, int3
   }
   fclose(f);
   return 0;
+}
+
+// ---- per-locus posterior summaries (gph_summary.h)
+int gph_engine_locus_summary_enable(gph_engine *e, int32_t on)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  SETDEV(e);
+  if (e->d_ls) { eng_free(e, e->d_ls); e->d_ls = nullptr; }
+  e->ls_samples = 0;
+  e->ls_ncol = 0;
+  e->ls_names.clear();
+  if (!on) return 0;
+  const int K = e->cfg.K, B = e->cfg.B, var = e->var_rates;
+  const int ncol = gph_ls_columns(K, B, var);
+  if (dev_alloc((void **)&e->d_ls, sizeof(double) * (size_t)ncol * e->L)) { e->d_ls = nullptr; return GPH_EHIP; }
+  e->ls_ncol = ncol;
+  for (const char *q : {"dataLnL", "genLnL", "tmrca"})
+    for (const char *m : {".shift", ".s1", ".s2"}) e->ls_names.push_back(std::string(q) + m);
+  for (int b = 0; b < B; b++) e->ls_names.push_back("nmig." + std::to_string(b));
+  for (int b = 0; b < B; b++) e->ls_names.push_back("pmig." + std::to_string(b));
+  for (int p = 0; p < K; p++) e->ls_names.push_back("ncoal." + std::to_string(p));
+  if (var) for (const char *m : {".shift", ".s1", ".s2"}) e->ls_names.push_back(std::string("rate") + m);
+  return ls_zero(e);
+}
+
+// one sample of the current state, queued on the engine's stream.  A mixing commit still owed to the next sweep kernel
+// changes the pages, so it runs first -- unless the proposal was rejected (the host mirror of the chain state, current
+// after an iteration, says so): then there is nothing to commit, as part_sweep finds too.  A deferred synchronizeEvents
+// pass may stay deferred (it corrects event times only)
+int gph_engine_locus_summary_sample(gph_engine *e)
+{
+  if (!e || !e->initialized || !e->d_ls) return GPH_ESTATE;
+  SETDEV(e);
+  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
+  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
+  const int first = e->ls_samples == 0;
+  const int L = (int)e->L, ncol = e->ls_ncol, var = e->var_rates;
+#ifdef GPH_HOSTEMU
+  for (int j = 0; j < L; j++)
+    locus_summary_slot(e->dev.pages + (size_t)j * e->lay.page_bytes, e->lay, e->d_ls + j, (size_t)L, ncol, first, var);
+  e->cls_launches[13] += 1;
+#else
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  const int tms = tm_begin(e, 13);
+  hipLaunchKernelGGL(k_locus_summary, dim3((unsigned)((L + GPH_LS_THREADS - 1) / GPH_LS_THREADS)), dim3(GPH_LS_THREADS), 0, e->stream,
+                     e->lay, (const char *)e->dev.pages, e->d_ls, L, ncol, first, var);
+  HIPCHK(hipGetLastError());
+  tm_end(e, tms);
+  e->n_launches++;
+  e->last_which = 13;
+  e->cls_launches[13] += 1;
+#endif
+  e->ls_samples++;
+  return 0;
+}
+
+int gph_engine_locus_summary_columns(gph_engine *e, int32_t *ncol, int64_t *samples)
+{
+  if (!e) return GPH_EARG;
+  if (ncol) *ncol = e->ls_ncol;
+  if (samples) *samples = e->ls_samples;
+  return 0;
+}
+
+int gph_engine_locus_summary_fetch(gph_engine *e, double *out, int64_t ld, int32_t reset)
+{
+  if (!e || !out) return GPH_EARG;
+  if (!e->d_ls) return GPH_ESTATE;
+  if (ld < e->ls_ncol) return GPH_EARG;
+  SETDEV(e);
+  const int64_t L = e->L;
+  const int ncol = e->ls_ncol;
+  std::vector<double> acc((size_t)ncol * L);
+  int rc = d2h(e, acc.data(), e->d_ls, sizeof(double) * acc.size());
+  if (rc) return rc;
+  /* slot j holds local locus h_orig[j] */
+  for (int64_t j = 0; j < L; j++) {
+    double *row = out + (size_t)e->h_orig[j] * ld;
+    for (int c = 0; c < ncol; c++) row[c] = acc[(size_t)c * L + j];
+  }
+  return reset ? ls_zero(e) : 0;
+}
+
+const char *gph_engine_locus_summary_column_name(gph_engine *e, int32_t col)
+{
+  if (!e || col < 0 || col >= (int32_t)e->ls_names.size()) return nullptr;
+  return e->ls_names[col].c_str();
 }
 
 } // extern "C"

@@ -1084,6 +1084,12 @@ int gph_loci_read(const gph_control *c, const char *seq_path, int32_t threads, g
 
 void gph_loci_free(gph_loci *l) { delete l; }
 
+const char *gph_loci_name(const gph_loci *l, int64_t g)
+{
+  if (!l || g < 0 || g >= (int64_t)l->names.size()) return nullptr;
+  return l->names[(size_t)g].c_str();
+}
+
 int gph_loci_arrays(const gph_loci *l, int64_t *L, int32_t *n, const int64_t **pattern_offsets, const uint8_t **leafcodes,
                     const uint16_t **numPhases, const int32_t **counts, const double **mutRates, const int32_t **unphased)
 {

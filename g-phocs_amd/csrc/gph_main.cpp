@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -10,6 +10,10 @@
 // the per-locus loops travel by RCCL all-gather on each child's stream (the id of the communicator goes from child
 // 0 to the others through a shared page).  With fewer devices than ranks (tests on a 1-GPU box) the ranks share
 // devices and exchange through that shared page instead -- RCCL refuses two ranks on one GPU.
+//
+// -l FILE: the per-locus posterior summary table (gph_run_control_file_ex).  Under -g N child r writes FILE.part<r>
+// with its own loci; after every child has exited 0 the launcher concatenates the parts in rank order into FILE and
+// removes them (on a failure it only removes them: a run that did not finish leaves no table).
 #include "gphocs_hip.h"
 #include <dlfcn.h>
 #include <libgen.h>
@@ -82,17 +86,19 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
 int main(int argc, char **argv)
 {
   int verbose = 0, device = 0, gpus = 1, i = 1;
+  const char *summary = nullptr;
   for (; i < argc && argv[i][0] == '-'; i++) {
     if (!strcmp(argv[i], "-v") || !strcmp(argv[i], "--verbose")) verbose = 1;
     else if (!strcmp(argv[i], "-d") && i + 1 < argc) device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "-g") && i + 1 < argc) gpus = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "-l") && i + 1 < argc) summary = argv[++i];
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
@@ -105,6 +111,7 @@ int main(int argc, char **argv)
   const std::string dir = dirname(self);
   if (gpus == 1) {
     void *h = load_engine(dir, ctl, ctl2);
+    if (summary) return sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, device, verbose, nullptr, summary) ? 1 : 0;
     return sym<decltype(&gph_run_control_file)>(h, "gph_run_control_file")(ctl, ctl2, device, verbose) ? 1 : 0;
   }
 
@@ -149,7 +156,8 @@ int main(int argc, char **argv)
         comm = create_rccl(mb->id, r, gpus, mydev);
       }
       if (!comm) { fprintf(stderr, "G-PhoCS-hip: rank %d could not join the communicator\n", r); _exit(2); }
-      int rc = sym<decltype(&gph_run_control_file_comm)>(h, "gph_run_control_file_comm")(ctl, ctl2, mydev, verbose, comm);
+      int rc = summary ? sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, mydev, verbose, comm, summary)
+                       : sym<decltype(&gph_run_control_file_comm)>(h, "gph_run_control_file_comm")(ctl, ctl2, mydev, verbose, comm);
       fflush(stdout);
       if (rc == 0) destroy(comm);
       _exit(rc ? 1 : 0);
@@ -176,6 +184,28 @@ int main(int argc, char **argv)
       bad = 1;
       for (int r = 0; r < gpus; r++) if (kids[r] != p) kill(kids[r], SIGTERM);
     }
+  }
+  if (summary) {
+    /* the ranks' parts of the summary table, in rank order */
+    FILE *out = bad ? nullptr : fopen(summary, "w");
+    if (!bad && !out) { perror(summary); bad = 1; }
+    for (int r = 0; r < gpus; r++) {
+      const std::string part = std::string(summary) + ".part" + std::to_string(r);
+      if (out) {
+        FILE *in = fopen(part.c_str(), "r");
+        if (!in) { fprintf(stderr, "G-PhoCS-hip: %s is missing\n", part.c_str()); bad = 1; }
+        else {
+          char buf[1 << 16];
+          size_t nr;
+          while ((nr = fread(buf, 1, sizeof buf, in)) > 0)
+            if (fwrite(buf, 1, nr, out) != nr) { perror(summary); bad = 1; break; }
+          fclose(in);
+        }
+      }
+      unlink(part.c_str());
+    }
+    if (out && fclose(out) != 0) { perror(summary); bad = 1; }
+    if (bad && out) unlink(summary);
   }
   return bad;
 }

@@ -4,6 +4,7 @@
 #include "../../include/gphocs_hip.h"
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,8 +35,49 @@ struct Finetune {
 };
 }   // namespace
 
+// the per-locus summary table (`G-PhoCS-hip -l FILE`) from the raw accumulators of this rank's loci: one row per locus in
+// sequence-file order, every derived value as the header comment of include/gphocs_hip.h and README.md define it
+static int write_locus_summary(const std::string &path, bool header, const gph_control *C, const gph_config &cfg, const gph_loci *LC,
+                               int64_t lb, int64_t nloc, int32_t ncol, int64_t samples, const std::vector<double> &raw, bool var)
+{
+  FILE *f = fopen(path.c_str(), "w");
+  if (!f) { fprintf(stderr, "gphocs_hip: cannot open the locus summary file %s\n", path.c_str()); return GPH_EARG; }
+  const int K = cfg.K, B = cfg.B;
+  if (header) {
+    fprintf(f, "locus\tname\tsamples\tdataLnL\tdataLnL_sd\tgenLnL\tgenLnL_sd\ttmrca\ttmrca_sd");
+    for (int b = 0; b < B; b++) {
+      const char *src = gph_control_pop_name(C, cfg.bandSrc[b]), *tgt = gph_control_pop_name(C, cfg.bandTgt[b]);
+      fprintf(f, "\tmig_%s->%s\tpmig_%s->%s", src, tgt, src, tgt);
+    }
+    for (int p = 0; p < K; p++) fprintf(f, "\tcoal_%s", gph_control_pop_name(C, p));
+    if (var) fprintf(f, "\trate\trate_sd");
+    fprintf(f, "\n");
+  }
+  const double S = (double)samples;
+  auto moments = [&](const double *a) {
+    const double mean = a[0] + a[1] / S;
+    const double v = S > 1 ? (a[2] - a[1] * a[1] / S) / (S - 1) : 0.0;
+    fprintf(f, "\t%.10g\t%.10g", mean, std::sqrt(v < 0.0 ? 0.0 : v));
+  };
+  for (int64_t i = 0; i < nloc; i++) {
+    const double *a = raw.data() + (size_t)i * ncol;
+    const char *nm = gph_loci_name(LC, lb + i);
+    fprintf(f, "%lld\t%s\t%lld", (long long)(lb + i), nm ? nm : "", (long long)samples);
+    moments(a + 0);
+    moments(a + 3);
+    moments(a + 6);
+    for (int b = 0; b < B; b++) fprintf(f, "\t%.10g\t%.10g", a[9 + b] / S, a[9 + B + b] / S);
+    for (int p = 0; p < K; p++) fprintf(f, "\t%.10g", a[9 + 2 * B + p] / S);
+    if (var) moments(a + 9 + 2 * B + K);
+    fprintf(f, "\n");
+  }
+  if (fclose(f) != 0) { fprintf(stderr, "gphocs_hip: writing the locus summary file %s failed\n", path.c_str()); return GPH_EARG; }
+  return GPH_OK;
+}
+
 static int run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
-                            int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user, gph_comm *comm)
+                            int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user, gph_comm *comm,
+                            const char *summary_path = nullptr)
 {
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce && !comm)) return GPH_EARG;
   const bool lead = rank == 0;   /* rank 0 talks and writes the trace file; every rank runs the same chain */
@@ -105,7 +147,6 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
                       world, (long long)L, (long long)per, (long long)((L + per - 1) / per));
     return fail(GPH_EARG, "sharding the loci over the ranks");
   }
-  (void)le;
   cfg.L_total = L;
   cfg.locus_begin = lb;
   cfg.device = device;
@@ -133,6 +174,7 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   if (lead && info.mutRateMode == 2) printf("Reading locus rates from file %s... ", info.rateFile);   /* readRateFile's progress text (GPhoCS.c:514), printed from initializeMCMC upstream */
   int64_t totalCoals = 0;
   if ((rc = gph_mcmc_initialize(M, &totalCoals))) return fail(rc, "gph_mcmc_initialize");
+  if (summary_path && (rc = gph_engine_locus_summary_enable(E, 1))) return fail(rc, "gph_engine_locus_summary_enable");
   std::vector<double> vals(mc.numParameters + 4, 0.0);
   double logL = 0, dataL = 0;
   auto t1 = std::chrono::steady_clock::now();
@@ -207,6 +249,7 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
       for (int i = 0; i < mc.numParameters; i++) fprintf(trace, "%8.5f\t", vals[i] * mc.printFactors[i]);
       fprintf(trace, "\t%.6f\t%.6f\n", logL, dataL);
       fflush(trace);
+      if (summary_path && (rc = gph_engine_locus_summary_sample(E))) return fail(rc, "gph_engine_locus_summary_sample");
     }
     logCount++;
     if ((it + 1) % samplesPerLog == 0) {
@@ -272,19 +315,36 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     if (verbose) printf("(%.2f s, %.3f iterations/s)\n", sec, (info.burnin + info.numSamples) / (sec > 0 ? sec : 1));
   }
   fclose(trace);
+  trace = nullptr;
+  int32_t ls_ncol = 0;
+  int64_t ls_samples = 0;
+  std::vector<double> ls_raw;
+  if (summary_path) {
+    gph_engine_locus_summary_columns(E, &ls_ncol, &ls_samples);
+    ls_raw.resize((size_t)ls_ncol * (le - lb));
+    if ((rc = gph_engine_locus_summary_fetch(E, ls_raw.data(), ls_ncol, 0))) return fail(rc, "gph_engine_locus_summary_fetch");
+  }
   /* a CHECKED build of the library (-DGPH_BOUNDS, tests only) says here whether an index left its array during the run */
   int32_t oob_where = 0, oob_checked = 0;
   (void)gph_engine_debug_oob(E, &oob_where, &oob_checked);
   gph_mcmc_destroy(M);
   gph_engine_destroy(E);
-  gph_loci_free(LC);
-  gph_control_free(C);
   if (oob_checked && oob_where != 0) {
-    fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h; "
-                    "8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
+    fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
+                    "3 gph_summary.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
+    gph_loci_free(LC);
+    gph_control_free(C);
     return GPH_EKERNEL;
   }
-  return GPH_OK;
+  rc = GPH_OK;
+  if (summary_path) {
+    /* one rank: the file itself; several: this rank's part, concatenated in rank order by the caller (rank 0's has the header) */
+    const std::string path = world > 1 ? std::string(summary_path) + ".part" + std::to_string(rank) : std::string(summary_path);
+    rc = write_locus_summary(path, lead, C, cfg, LC, lb, le - lb, ls_ncol, ls_samples, ls_raw, info.mutRateMode == 1);
+  }
+  gph_loci_free(LC);
+  gph_control_free(C);
+  return rc;
 }
 
 extern "C" int gph_run_control_file_ranked(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
@@ -295,10 +355,17 @@ extern "C" int gph_run_control_file_ranked(const char *ctl, const char *ctl2, in
 
 extern "C" int gph_run_control_file_comm(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm)
 {
-  return run_control_file(ctl, ctl2, device, verbose, gph_comm_rank(comm), gph_comm_world(comm), nullptr, nullptr, comm);
+  return gph_run_control_file_ex(ctl, ctl2, device, verbose, comm, nullptr);
+}
+
+extern "C" int gph_run_control_file_ex(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
+                                       const char *locus_summary_path)
+{
+  if (comm) return run_control_file(ctl, ctl2, device, verbose, gph_comm_rank(comm), gph_comm_world(comm), nullptr, nullptr, comm, locus_summary_path);
+  return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr, locus_summary_path);
 }
 
 extern "C" int gph_run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose)
 {
-  return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr);
+  return gph_run_control_file_ex(ctl, ctl2, device, verbose, nullptr, nullptr);
 }

@@ -220,7 +220,7 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
 /* timing of the last launch of a named kernel class, measured with HIP events on the
  * engine's own stream: which = 0 sweep, 1 tau_eval, 2 mix_eval, 3 init, 4 check,
  * 5 tau_finish (commit or revert, by the decision flag), 7 mix_finish, 8 sync, 9 locus-rate scan, 10 locus-rate apply,
- * 11 locus-rate prepare */
+ * 11 locus-rate prepare, 13 locus summary (gph_engine_locus_summary_sample) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -249,6 +249,25 @@ int gph_engine_steplog_enable(gph_engine *e, const int64_t *loci, int32_t n, int
 int gph_engine_steplog_fetch(gph_engine *e, int32_t idx, double *out, int32_t max_records, int32_t *nrec, int32_t reset);
 const char *gph_build_compiler(void);
 const char *gph_runtime_version(void);
+/* per-locus posterior summaries, accumulated on the device (k_locus_summary, csrc/gph_summary.h).  One sample reads, from
+ * every local locus's page, the data and genealogy log-likelihoods, the TMRCA (age of the root node), the locus rate
+ * (`locus-mut-rate VAR` only), the migration count of every band and the coalescence count of every population, and
+ * adds them to fp64 accumulators in HBM.  Moments are kept as shift (the value at the first sample) + sums of d and d^2,
+ * d = x - shift, in sample order; counts as sums, and for every band the number of samples with a migration.
+ *   _enable(on)     allocates and zeroes the accumulators (on = 1) or frees them (on = 0); gph_engine_init_genealogies
+ *                   zeroes them again
+ *   _sample         queues one sample on the engine's stream (no host synchronisation); a mixing commit still owed to
+ *                   the next sweep kernel runs first
+ *   _columns        raw columns per locus and samples taken since the accumulators were last zeroed
+ *   _fetch          out[local locus][ld >= ncol], rows in global locus order (row i = global locus locus_begin + i);
+ *                   reset = 1 zeroes the accumulators afterwards
+ *   _column_name    stable machine name of raw column col ("dataLnL.shift", "dataLnL.s1", "dataLnL.s2", "genLnL.*",
+ *                   "tmrca.*", "nmig.<band>", "pmig.<band>", "ncoal.<pop>", "rate.*"), NULL if out of range */
+int gph_engine_locus_summary_enable(gph_engine *e, int32_t on);
+int gph_engine_locus_summary_sample(gph_engine *e);
+int gph_engine_locus_summary_columns(gph_engine *e, int32_t *ncol, int64_t *samples);
+int gph_engine_locus_summary_fetch(gph_engine *e, double *out, int64_t ld, int32_t reset);
+const char *gph_engine_locus_summary_column_name(gph_engine *e, int32_t col);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -329,6 +348,8 @@ int gph_loci_read(const gph_control *c, const char *seq_path, int32_t threads, g
 void gph_loci_free(gph_loci *l);
 int gph_loci_arrays(const gph_loci *l, int64_t *L, int32_t *n, const int64_t **pattern_offsets, const uint8_t **leafcodes,
                     const uint16_t **numPhases, const int32_t **counts, const double **mutRates, const int32_t **unphased);
+/* name of locus g (0-based, sequence-file order) as the sequence file gives it; NULL if g is out of range */
+const char *gph_loci_name(const gph_loci *l, int64_t g);
 int gph_run_control_file(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device, int32_t verbose);
 /* the same chain over `world` processes, one per GPU: every rank reads the files, holds the contiguous block
  * rank*ceil(L/world) .. of the loci, runs the same host code on the same general RNG stream and combines the
@@ -384,6 +405,12 @@ int gph_mcmc_initialize_genealogies(gph_mcmc *m);
  * its N child processes */
 int gph_run_control_file_comm(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
                               int32_t verbose, gph_comm *comm);
+/* either of the two above (comm NULL = one rank), plus the per-locus summary table (`G-PhoCS-hip -l FILE`): a sample
+ * after every trace line, the table written once after the last iteration and only on success.  One rank writes
+ * locus_summary_path; under a communicator of several ranks rank r writes locus_summary_path.part<r> with its own loci
+ * (rank 0's part holds the header) and the caller concatenates the parts in rank order.  NULL = no table. */
+int gph_run_control_file_ex(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
+                            int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null);
 
 /* ------------------------------------------------------------------------------------
  * post-run summary of a trace file (host only): block means per column, the output of the reference's
