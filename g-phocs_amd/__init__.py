@@ -286,6 +286,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_mcmc_synchronize_events", "gph_mcmc_check_all", "gph_mcmc_initialize_genealogies",
     "gph_engine_locus_summary_enable", "gph_engine_locus_summary_sample", "gph_engine_locus_summary_columns",
     "gph_engine_locus_summary_fetch", "gph_engine_locus_summary_column_name", "gph_loci_name", "gph_run_control_file_ex",
+    "gph_engine_coal_stats_enable", "gph_engine_coal_stats_sample", "gph_engine_coal_stats_shape", "gph_engine_coal_stats_fetch",
+    "gph_engine_coal_stats_column_name", "gph_run_control_file_ex2", "gph_coal_stats_write", "gph_coal_stats_discard",
+    "gph_engine_coal_stats_set_chunk", "gph_coal_stats_combined",
 ]
 
 
@@ -391,6 +394,17 @@ def _load_library(path):
     lib.gph_loci_name.argtypes = [C.c_void_p, C.c_int64]
     lib.gph_loci_name.restype = C.c_char_p
     lib.gph_run_control_file_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p]
+    lib.gph_engine_coal_stats_enable.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_coal_stats_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_coal_stats_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
+    lib.gph_engine_coal_stats_fetch.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_coal_stats_column_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_coal_stats_column_name.restype = C.c_char_p
+    lib.gph_run_control_file_ex2.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32]
+    lib.gph_coal_stats_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_coal_stats_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_engine_coal_stats_set_chunk.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_coal_stats_combined.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     return lib
 
 
@@ -601,6 +615,47 @@ def summary_table(raw, S, pack):
     return t
 
 
+COAL_STATS_FULL = -5     # GPH_EFULL: gph_engine_coal_stats_sample found no free row in the device buffer
+COAL_STATS_FIXED = ("iter", "coalStat", "numCoal", "migStat", "numMig", "genLnL", "dataLnL")
+
+
+def coal_stats_table(rows, n, K, L):
+    """the derived statistics of raw coal-stats rows ([samples][7 + 3 * n(n-1)/2 * K], gph_engine_coal_stats_fetch; several
+    ranks: their rows added in rank order first), L = loci of all ranks.  One dict per sample: the flat columns as
+    printCoalStats prints them (logGenLikelihood = genLnL + dataLnL; logPrior is the caller's) and probCoal = cnt / L,
+    probFirstCoal = first / L, meanCoal = agesum / cnt where cnt > 0 else 0 as symmetric (n, n, K) arrays with a zero
+    diagonal (patch.c:2256-2266)."""
+    iu = np.triu_indices(n, 1)
+    npk = n * (n - 1) // 2 * K
+    out = []
+    for r in np.asarray(rows, dtype=np.float64).reshape(-1, 7 + 3 * npk):
+        cnt, first, agesum = (r[7 + b * npk:7 + (b + 1) * npk].reshape(-1, K) for b in range(3))
+        d = dict(iter=int(r[0]), coalStat=r[1], numCoal=int(r[2]), migStat=r[3], numMig=int(r[4]),
+                 logGenLikelihood=r[5] + r[6], logDataLikelihood=r[6])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            vals = dict(probCoal=cnt / L, probFirstCoal=first / L, meanCoal=np.where(cnt > 0, agesum / cnt, 0.0))
+        for name, v in vals.items():
+            m = np.zeros((n, n, K))
+            m[iu[0], iu[1], :] = v
+            m[iu[1], iu[0], :] = v
+            d[name] = m
+        out.append(d)
+    return out
+
+
+def coal_stats_combined(lib, prefix, ranks):
+    """(samples, row_doubles + 1) array: the records of PREFIX.coal.part<0..ranks-1> added in rank order, logPrior last
+    (gph_coal_stats_combined)"""
+    rows, rd = C.c_int64(), C.c_int32()
+    if lib.gph_coal_stats_combined(str(prefix).encode(), ranks, None, 0, C.byref(rows), C.byref(rd)):
+        raise RuntimeError("gphocs_hip: coal_stats_combined failed")
+    out = np.zeros((rows.value, rd.value))
+    if rows.value and lib.gph_coal_stats_combined(str(prefix).encode(), ranks, out.ctypes.data_as(C.POINTER(C.c_double)), rows.value,
+                                                  C.byref(rows), C.byref(rd)):
+        raise RuntimeError("gphocs_hip: coal_stats_combined failed")
+    return out
+
+
 def _dp(a):
     return np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
 
@@ -776,6 +831,41 @@ class Sampler:
             cols["samples"] = np.full(nloc, S, dtype=np.int64)
             return cols
         return summary_table(cols, S, self.pack)
+
+    # ---- genome-wide coalescent / sample-pair statistics per sample (gph_engine_coal_stats_*): one row per call, on the device
+    def enable_coal_stats(self, capacity, chunk=0):
+        """a device buffer of `capacity` samples; 0 switches the feature off and frees it.  chunk (tests): slots per chunk of
+        the kernel, 0 = the default"""
+        self._chk(self.lib.gph_engine_coal_stats_set_chunk(self.engine, int(chunk)), "coal_stats_set_chunk")
+        self._chk(self.lib.gph_engine_coal_stats_enable(self.engine, int(capacity)), "coal_stats_enable")
+
+    def sample_coal_stats(self, it):
+        """one sample of the current state, labelled iteration `it`; BufferError when the device buffer is full"""
+        rc = self.lib.gph_engine_coal_stats_sample(self.engine, int(it))
+        if rc == COAL_STATS_FULL:
+            raise BufferError("gphocs_hip: the coal-stats buffer is full; fetch with coal_stats() first")
+        self._chk(rc, "coal_stats_sample")
+
+    def coal_stats(self, raw=False):
+        """the samples taken since the last call (the device buffer is emptied).  raw=True: the rows as the engine keeps them,
+        a (samples, row_doubles) array over THIS rank's loci (columns: gph_engine_coal_stats_column_name).  raw=False: a list
+        of dicts, one per sample (coal_stats_table); several ranks must add their raw rows in rank order first."""
+        rd, fill, n, K = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(self.lib.gph_engine_coal_stats_shape(self.engine, C.byref(rd), C.byref(fill), C.byref(n), C.byref(K)), "coal_stats_shape")
+        out = np.zeros((max(fill.value, 1), max(rd.value, 1)))
+        got = C.c_int32()
+        self._chk(self.lib.gph_engine_coal_stats_fetch(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[0], C.byref(got)),
+                  "coal_stats_fetch")
+        out = out[:got.value]
+        if raw:
+            return out
+        L = int(getattr(self.pack, "global_L", None) or self.pack.L)
+        return coal_stats_table(out, n.value, K.value, L)
+
+    def coal_stats_columns(self):
+        rd = C.c_int32()
+        self._chk(self.lib.gph_engine_coal_stats_shape(self.engine, C.byref(rd), None, None, None), "coal_stats_shape")
+        return [self.lib.gph_engine_coal_stats_column_name(self.engine, c).decode() for c in range(rd.value)]
 
     def hbm_bytes(self):
         b = C.c_double()

@@ -22,6 +22,7 @@
 #include "gph_kernels.h"
 #include "gph_global.h"
 #include "gph_summary.h"
+#include "gph_coalstats.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
 
@@ -433,6 +434,12 @@ struct gph_engine {
   int32_t ls_ncol = 0;
   int64_t ls_samples = 0;
   std::vector<std::string> ls_names;
+  // genome-wide coalescent / sample-pair statistics (gph_coalstats.h): per-chunk partial rows, the rows of the samples taken
+  // since the last fetch ([cs_cap][cs_rd]); all null / 0 while the feature is off
+  double *d_cs_part = nullptr, *d_cs_rows = nullptr;
+  int32_t cs_cap = 0, cs_fill = 0, cs_rd = 0, cs_chunk = 0, cs_nchunks = 0, cs_bd = 0;
+  int32_t cs_chunk_next = 0;   // slots per chunk of the next _enable (gph_engine_coal_stats_set_chunk; 0: GPH_CS_CHUNK)
+  std::string cs_name;
   double last_ms[16] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[16] = {0}, cls_ms[16] = {0};
@@ -1086,7 +1093,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->dev.pages); dev_free(e->dev.shadow); dev_free(e->dev.cond); dev_free((void *)e->dev.cond_off);
   dev_free((void *)e->dev.seq); dev_free((void *)e->dev.seq_off); dev_free((void *)e->dev.orig); dev_free((void *)e->dev.P); dev_free(e->dev.out); dev_free(e->dev.stats); dev_free(e->d_mutRate);
   dev_free(e->d_lrec); dev_free(e->d_lpre); dev_free(e->d_slot_of); dev_free(e->d_lr_result); dev_free(e->d_lr_gscr); dev_free(e->d_ref_page); dev_free(e->d_ref_seq);
-  dev_free(e->d_part); dev_free(e->dev.err); dev_free(e->d_ls);
+  dev_free(e->d_part); dev_free(e->dev.err); dev_free(e->d_ls); dev_free(e->d_cs_part); dev_free(e->d_cs_rows);
   for (void *p : e->deferred_free) dev_free(p);
   e->deferred_free.clear();
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
@@ -1413,6 +1420,7 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   /* summaries of the old chain do not carry over; the locus-rate columns come and go with `locus-mut-rate VAR` */
   if (e->d_ls && e->ls_ncol != gph_ls_columns(e->cfg.K, e->cfg.B, e->var_rates)) { int rce = gph_engine_locus_summary_enable(e, 1); if (rce) return rce; }
   { int rcz = ls_zero(e); if (rcz) return rcz; }
+  e->cs_fill = 0;
   LAUNCH(e, 3, k_init, e->seedz, (const double *)e->d_mutRate, e->init_predraws);
   int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -2497,6 +2505,117 @@ const char *gph_engine_locus_summary_column_name(gph_engine *e, int32_t col)
 {
   if (!e || col < 0 || col >= (int32_t)e->ls_names.size()) return nullptr;
   return e->ls_names[col].c_str();
+}
+
+// ---- genome-wide coalescent and sample-pair statistics per sample (gph_coalstats.h)
+int gph_engine_coal_stats_enable(gph_engine *e, int32_t capacity)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity < 0) return GPH_EARG;
+  SETDEV(e);
+  if (e->d_cs_part) { eng_free(e, e->d_cs_part); e->d_cs_part = nullptr; }
+  if (e->d_cs_rows) { eng_free(e, e->d_cs_rows); e->d_cs_rows = nullptr; }
+  e->cs_cap = e->cs_fill = e->cs_rd = e->cs_chunk = e->cs_nchunks = e->cs_bd = 0;
+  if (capacity == 0) return 0;
+  const int n = e->cfg.n, K = e->cfg.K;
+  const int chunk = e->cs_chunk_next > 0 ? e->cs_chunk_next : GPH_CS_CHUNK;
+  const int rd = gph_cs_row_doubles(n, K);
+  const int nchunks = (int)((e->L + chunk - 1) / chunk);
+  if (dev_alloc((void **)&e->d_cs_part, sizeof(double) * (size_t)rd * nchunks)) { e->d_cs_part = nullptr; return GPH_EHIP; }
+  if (dev_alloc((void **)&e->d_cs_rows, sizeof(double) * (size_t)rd * capacity)) {
+    e->d_cs_rows = nullptr;
+    dev_free(e->d_cs_part);
+    e->d_cs_part = nullptr;
+    return GPH_EHIP;
+  }
+  e->cs_cap = capacity; e->cs_rd = rd; e->cs_chunk = chunk; e->cs_nchunks = nchunks; e->cs_bd = gph_cs_block(n, K);
+  return 0;
+}
+
+// tests: the slots per chunk the next _enable uses (0: the default), so that a data set of a few loci runs the fold over
+// several partial rows.  The chunk size is part of the summation order: it changes the last bits of the fp64 sums
+int gph_engine_coal_stats_set_chunk(gph_engine *e, int32_t slots)
+{
+  if (!e || slots < 0) return GPH_EARG;
+  e->cs_chunk_next = slots;
+  return 0;
+}
+
+// one sample of the current state into the next free row, queued on the engine's stream; ordered against a mixing commit
+// still owed to the next sweep kernel exactly as gph_engine_locus_summary_sample orders itself (the node records are page
+// contents; a deferred synchronizeEvents pass corrects event times only and may stay deferred)
+int gph_engine_coal_stats_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->d_cs_rows) return GPH_ESTATE;
+  if (e->cs_fill >= e->cs_cap) return GPH_EFULL;
+  SETDEV(e);
+  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
+  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
+  const int L = (int)e->L, n = e->cfg.n, K = e->cfg.K, B = e->cfg.B, bd = e->cs_bd, rd = e->cs_rd;
+  const int ntiles = (gph_cs_pairs(n) + bd - 1) / bd;
+  double *row = e->d_cs_rows + (size_t)e->cs_fill * rd;
+#ifdef GPH_HOSTEMU
+  (void)B;
+  std::vector<char> lds;
+  for (int ch = 0; ch < e->cs_nchunks; ch++)
+    for (int t = 0; t < ntiles; t++) coal_stats_workgroup(e->lay, (const char *)e->dev.pages, e->d_cs_part, L, e->cs_chunk, bd, ch, t, lds);
+  for (int c = 0; c < rd; c++) gph_cs_fold_column(e->d_cs_part, e->cs_nchunks, rd, c, (double)iteration, row);
+  e->cls_launches[14] += 1;
+#else
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  const int tms = tm_begin(e, 14);
+  hipLaunchKernelGGL(k_coal_stats, dim3((unsigned)e->cs_nchunks, (unsigned)ntiles), dim3((unsigned)bd), gph_cs_lds_bytes(n, K, B, bd), e->stream,
+                     e->lay, (const char *)e->dev.pages, e->d_cs_part, L, e->cs_chunk);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_coal_fold, dim3((unsigned)((rd + GPH_CS_FOLD_THREADS - 1) / GPH_CS_FOLD_THREADS)), dim3(GPH_CS_FOLD_THREADS), 0, e->stream,
+                     (const double *)e->d_cs_part, e->cs_nchunks, rd, (double)iteration, row);
+  HIPCHK(hipGetLastError());
+  tm_end(e, tms);
+  e->n_launches += 2;
+  e->last_which = 14;
+  e->cls_launches[14] += 1;
+#endif
+  e->cs_fill++;
+  return 0;
+}
+
+int gph_engine_coal_stats_shape(gph_engine *e, int32_t *row_doubles, int32_t *filled, int32_t *n, int32_t *K)
+{
+  if (!e) return GPH_EARG;
+  if (row_doubles) *row_doubles = e->cs_rd;
+  if (filled) *filled = e->cs_fill;
+  if (n) *n = e->cfg.n;
+  if (K) *K = e->cfg.K;
+  return 0;
+}
+
+int gph_engine_coal_stats_fetch(gph_engine *e, double *out, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || (!out && max_rows > 0)) return GPH_EARG;
+  if (!e->d_cs_rows) return GPH_ESTATE;
+  if (max_rows < e->cs_fill) return GPH_EARG;
+  SETDEV(e);
+  *rows = e->cs_fill;
+  if (e->cs_fill > 0) {
+    int rc = d2h(e, out, e->d_cs_rows, sizeof(double) * (size_t)e->cs_rd * e->cs_fill);
+    if (rc) return rc;
+  }
+  e->cs_fill = 0;
+  return 0;
+}
+
+const char *gph_engine_coal_stats_column_name(gph_engine *e, int32_t col)
+{
+  static const char *fixed[CS_FIXED] = {"iter", "coalStat", "numCoal", "migStat", "numMig", "genLnL", "dataLnL"};
+  if (!e || col < 0) return nullptr;
+  if (col < CS_FIXED) return fixed[col];
+  const int n = e->cfg.n, K = e->cfg.K, npk = gph_cs_pairs(n) * K;
+  if (K < 1 || col >= CS_FIXED + 3 * npk) return nullptr;
+  const int block = (col - CS_FIXED) / npk, q = (col - CS_FIXED) % npk;
+  int i = 0, p = q / K;
+  while (i < n - 2 && p >= n - 1 - i) { p -= n - 1 - i; i++; }
+  e->cs_name = std::string(block == 0 ? "cnt." : block == 1 ? "first." : "agesum.") + std::to_string(i) + "." + std::to_string(i + 1 + p) + "." + std::to_string(q % K);
+  return e->cs_name.c_str();
 }
 
 } // extern "C"

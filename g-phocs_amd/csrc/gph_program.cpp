@@ -75,9 +75,173 @@ static int write_locus_summary(const std::string &path, bool header, const gph_c
   return GPH_OK;
 }
 
+// ---- coalescent / sample-pair statistics (`G-PhoCS-hip -s PREFIX`): rank r's raw rows travel through the binary file
+// PREFIX.coal.part<r> -- a header (magic, n, K, doubles per row, loci of all ranks, the sample and population names), one
+// record of row_doubles + 1 doubles per sample (the engine's raw row, then logPrior) and, written when the rank closes its
+// part, the number of records: a part without that trailer, or whose size does not match it, is refused
+namespace {
+const char CS_MAGIC[8] = {'G', 'P', 'H', 'C', 'S', '1', '\n', 0};
+std::string cs_part_path(const char *prefix, int r) { return std::string(prefix) + ".coal.part" + std::to_string(r); }
+
+// rows of the device buffer when the caller names none: 64 samples, fewer when a row is large (the widest variant, 200
+// leaves x 39 populations, has rows of 18.6 MB), so that the buffer -- and its host copy -- stay within 256 MB
+int32_t cs_default_rows(int32_t row_doubles)
+{
+  const int64_t fit = ((int64_t)256 << 20) / ((int64_t)row_doubles * 8);
+  return (int32_t)(fit < 1 ? 1 : fit > 64 ? 64 : fit);
+}
+
+// the parts of `ranks` ranks, read sample by sample: next() hands out the ranks' records added in rank order (counts
+// added, sums added rank 0 first; the iteration and logPrior are rank 0's)
+struct CsReader {
+  std::vector<FILE *> f;
+  int32_t n = 0, K = 0, rd = 0;
+  int64_t L = 0, samples = 0;
+  std::vector<std::string> names;     /* n sample names as printed, then K population names */
+  std::vector<double> tmp;
+  ~CsReader() { for (FILE *x : f) if (x) fclose(x); }
+  bool open(const char *prefix, int ranks)
+  {
+    for (int r = 0; r < ranks; r++) {
+      const std::string path = cs_part_path(prefix, r);
+      FILE *x = fopen(path.c_str(), "rb");
+      f.push_back(x);
+      char magic[8];
+      int32_t hdr[3], nbytes = 0;
+      int64_t Lr = 0, count = -1;
+      bool ok = x && fread(magic, 1, 8, x) == 8 && !memcmp(magic, CS_MAGIC, 8) && fread(hdr, 4, 3, x) == 3 && fread(&Lr, 8, 1, x) == 1 &&
+                fread(&nbytes, 4, 1, x) == 1 && nbytes >= 0 && hdr[0] >= 2 && hdr[1] >= 1 && hdr[2] > 0;
+      std::vector<std::string> nm;
+      if (ok) {
+        std::vector<char> buf((size_t)nbytes + 1, 0);
+        ok = fread(buf.data(), 1, (size_t)nbytes, x) == (size_t)nbytes;
+        for (size_t at = 0; ok && at < (size_t)nbytes; at += strlen(buf.data() + at) + 1) nm.push_back(buf.data() + at);
+        ok = ok && (int)nm.size() == hdr[0] + hdr[1];
+      }
+      if (ok) {
+        /* header | count records | count */
+        const long body = ftell(x);
+        ok = body > 0 && fseek(x, -8, SEEK_END) == 0;
+        const long tail = ok ? ftell(x) : 0;
+        ok = ok && fread(&count, 8, 1, x) == 1 && count >= 0 && tail - body == (long)(count * (int64_t)(hdr[2] + 1) * 8) && fseek(x, body, SEEK_SET) == 0;
+      }
+      if (!ok) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); return false; }
+      if (r == 0) { n = hdr[0]; K = hdr[1]; rd = hdr[2]; L = Lr; samples = count; names = nm; }
+      else if (hdr[0] != n || hdr[1] != K || hdr[2] != rd || count != samples) { fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", path.c_str()); return false; }
+    }
+    tmp.resize((size_t)rd + 1);
+    return true;
+  }
+  bool next(std::vector<double> &rec)
+  {
+    rec.resize((size_t)rd + 1);
+    for (size_t r = 0; r < f.size(); r++) {
+      std::vector<double> &into = r == 0 ? rec : tmp;
+      if (fread(into.data(), sizeof(double), into.size(), f[r]) != into.size()) return false;
+      if (r > 0) for (int c = 1; c < rd; c++) rec[c] = rec[c] + tmp[c];
+    }
+    return true;
+  }
+};
+}   // namespace
+
+extern "C" int gph_coal_stats_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  for (int r = 0; r < ranks; r++) remove(cs_part_path(prefix, r).c_str());
+  return GPH_OK;
+}
+
+extern "C" int gph_coal_stats_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles)
+{
+  if (!prefix || ranks < 1 || !rows || !row_doubles) return GPH_EARG;
+  CsReader R;
+  if (!R.open(prefix, ranks)) return GPH_EARG;
+  *rows = R.samples;
+  *row_doubles = R.rd + 1;
+  if (!out) return GPH_OK;
+  if (max_rows < R.samples) return GPH_EARG;
+  std::vector<double> rec;
+  for (int64_t i = 0; i < R.samples; i++) {
+    if (!R.next(rec)) return GPH_EARG;
+    memcpy(out + (size_t)i * rec.size(), rec.data(), sizeof(double) * rec.size());
+  }
+  return GPH_OK;
+}
+
+extern "C" int gph_coal_stats_write(const char *prefix, int32_t ranks)
+{
+  if (!prefix || ranks < 1) return GPH_EARG;
+  static const char *stat[3] = {"probCoal", "probFirstCoal", "meanCoal"};
+  std::vector<std::string> paths;
+  std::vector<FILE *> out;
+  bool ok;
+  {
+    CsReader R;
+    ok = R.open(prefix, ranks);
+    const int n = R.n, K = R.K, rd = R.rd, npk = n * (n - 1) / 2 * K;
+    /* every output file open at once (1 + 3 K of them), so that the parts are read once, sample by sample */
+    if (ok) {
+      paths.push_back(std::string(prefix) + ".coal.tsv");
+      for (int pop = 0; pop < K; pop++)
+        for (int st = 0; st < 3; st++) paths.push_back(std::string(prefix) + "." + R.names[n + pop] + "." + stat[st] + ".tsv");
+      for (const std::string &p : paths) {
+        FILE *x = fopen(p.c_str(), "w");
+        if (!x) { fprintf(stderr, "gphocs_hip: cannot open %s\n", p.c_str()); ok = false; break; }
+        out.push_back(x);
+      }
+    }
+    if (ok) {
+      /* headers: printCoalStats without partitions (GPhoCS.c:924-926) and the node-stats files' (GPhoCS.c:937-981) */
+      fprintf(out[0], "iter\tcoalStat\tnumCoal\tmigStat\tnumMig\tlogPrior\tlogGenLikelihood\tlogDataLikelihood\n");
+      for (int pop = 0; pop < K; pop++)
+        for (int st = 0; st < 3; st++) {
+          FILE *x = out[1 + 3 * pop + st];
+          fprintf(x, "iter");
+          for (int i = 0; i < n; i++)
+            for (int j = 0; j < n; j++) fprintf(x, "\t%s|%s|%s|%s", R.names[i].c_str(), R.names[j].c_str(), R.names[n + pop].c_str(), stat[st]);
+          fprintf(x, "\n");
+        }
+      std::vector<int> pair_of((size_t)n * n, -1);
+      for (int i = 0, p = 0; i < n; i++)
+        for (int j = i + 1; j < n; j++, p++) pair_of[(size_t)i * n + j] = pair_of[(size_t)j * n + i] = p;
+      const double Ld = (double)R.L;
+      std::vector<double> rec;
+      for (int64_t s = 0; s < R.samples && ok; s++) {
+        if (!R.next(rec)) { fprintf(stderr, "gphocs_hip: a part of %s ended early\n", prefix); ok = false; break; }
+        const double *a = rec.data();
+        /* row formats of GPhoCS.c:990-999; all ordered pairs, the diagonal as 0, normalised as patch.c:2256-2266 (GPhoCS.c:1013-1036) */
+        fprintf(out[0], "%7d", (int)a[0]);
+        fprintf(out[0], "\t%8f\t%9d\t%8f\t%9d\t%8f\t%8f\t%8f\n", a[1], (int)a[2], a[3], (int)a[4], a[rd], a[5] + a[6], a[6]);
+        for (int pop = 0; pop < K; pop++)
+          for (int st = 0; st < 3; st++) {
+            FILE *x = out[1 + 3 * pop + st];
+            fprintf(x, "%7d", (int)a[0]);
+            for (int i = 0; i < n; i++)
+              for (int j = 0; j < n; j++) {
+                const int p = pair_of[(size_t)i * n + j];
+                double v = 0.0;
+                if (p >= 0) {
+                  const double cnt = a[7 + p * K + pop], first = a[7 + npk + p * K + pop], agesum = a[7 + 2 * npk + p * K + pop];
+                  v = st == 0 ? cnt / Ld : st == 1 ? first / Ld : cnt > 0 ? agesum / cnt : 0.0;
+                }
+                fprintf(x, "\t%8f", v);
+              }
+            fprintf(x, "\n");
+          }
+      }
+    }
+    for (size_t i = 0; i < out.size(); i++)
+      if ((ferror(out[i]) | fclose(out[i])) != 0) { fprintf(stderr, "gphocs_hip: writing %s failed\n", paths[i].c_str()); ok = false; }
+  }
+  gph_coal_stats_discard(prefix, ranks);
+  if (!ok) for (size_t i = 0; i < out.size(); i++) remove(paths[i].c_str());
+  return ok ? GPH_OK : GPH_EARG;
+}
+
 static int run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
                             int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user, gph_comm *comm,
-                            const char *summary_path = nullptr)
+                            const char *summary_path = nullptr, const char *cs_prefix = nullptr, int32_t cs_capacity = 0)
 {
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce && !comm)) return GPH_EARG;
   const bool lead = rank == 0;   /* rank 0 talks and writes the trace file; every rank runs the same chain */
@@ -90,10 +254,12 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_control_info info;
   char err[512] = "";
   int rc;
-  FILE *trace = nullptr;
+  FILE *trace = nullptr, *cs_part = nullptr;
   auto fail = [&](int code, const char *what) {
     fprintf(stderr, "gphocs_hip: %s failed (status %d)%s%s\n", what, code, err[0] ? ": " : "", err);
     if (trace) fclose(trace);
+    if (cs_part) fclose(cs_part);
+    if (cs_prefix && world == 1) gph_coal_stats_discard(cs_prefix, 1);   /* (several ranks: the caller removes every rank's part) */
     if (M) gph_mcmc_destroy(M);
     if (E) gph_engine_destroy(E);
     if (LC) gph_loci_free(LC);
@@ -175,6 +341,45 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   int64_t totalCoals = 0;
   if ((rc = gph_mcmc_initialize(M, &totalCoals))) return fail(rc, "gph_mcmc_initialize");
   if (summary_path && (rc = gph_engine_locus_summary_enable(E, 1))) return fail(rc, "gph_engine_locus_summary_enable");
+  /* coalescent / sample-pair statistics: the device buffer, this rank's part file and its header */
+  int32_t cs_rd = 0;
+  int64_t cs_written = 0;
+  std::vector<double> cs_rows, cs_prior;
+  std::vector<double> cs_theta(cfg.K), cs_age(cfg.K), cs_mig(cfg.B > 0 ? cfg.B : 1);
+  if (cs_prefix) {
+    if (cs_capacity <= 0) cs_capacity = cs_default_rows(7 + 3 * (cfg.n * (cfg.n - 1) / 2) * cfg.K);
+    if ((rc = gph_engine_coal_stats_enable(E, cs_capacity))) return fail(rc, "gph_engine_coal_stats_enable");
+    gph_engine_coal_stats_shape(E, &cs_rd, nullptr, nullptr, nullptr);
+    cs_rows.resize((size_t)cs_rd * cs_capacity);
+    cs_part = fopen(cs_part_path(cs_prefix, rank).c_str(), "wb");
+    if (!cs_part) { snprintf(err, sizeof err, "Could not open %s", cs_part_path(cs_prefix, rank).c_str()); return fail(GPH_EARG, "opening the coal-stats part file"); }
+    std::string names;
+    for (int s = 0; s < cfg.n; s++) {
+      /* the second haploid of a diploid has no name of its own: the previous sample's, "NA" without one (GPhoCS.c:942-953) */
+      const char *nm = gph_control_sample_name(C, s);
+      if (!nm || !nm[0]) { const char *pv = s > 0 ? gph_control_sample_name(C, s - 1) : nullptr; nm = pv && pv[0] ? pv : "NA"; }
+      names += nm; names.push_back('\0');
+    }
+    for (int p = 0; p < cfg.K; p++) { names += gph_control_pop_name(C, p); names.push_back('\0'); }
+    const int32_t hdr[3] = {cfg.n, cfg.K, cs_rd}, nbytes = (int32_t)names.size();
+    const int64_t Ltot = L;
+    fwrite(CS_MAGIC, 1, 8, cs_part); fwrite(hdr, 4, 3, cs_part); fwrite(&Ltot, 8, 1, cs_part); fwrite(&nbytes, 4, 1, cs_part);
+    fwrite(names.data(), 1, names.size(), cs_part);
+  }
+  /* the filled rows of the device buffer, each with its logPrior, to the part file */
+  auto cs_flush = [&]() -> int {
+    int32_t got = 0;
+    int rcf = gph_engine_coal_stats_fetch(E, cs_rows.data(), cs_capacity, &got);
+    if (rcf) return rcf;
+    if (got != (int32_t)cs_prior.size()) return GPH_ESTATE;
+    for (int32_t i = 0; i < got; i++) {
+      if (fwrite(cs_rows.data() + (size_t)i * cs_rd, sizeof(double), (size_t)cs_rd, cs_part) != (size_t)cs_rd) return GPH_EARG;
+      if (fwrite(&cs_prior[i], sizeof(double), 1, cs_part) != 1) return GPH_EARG;
+    }
+    cs_written += got;
+    cs_prior.clear();
+    return fflush(cs_part) == 0 ? GPH_OK : GPH_EARG;
+  };
   std::vector<double> vals(mc.numParameters + 4, 0.0);
   double logL = 0, dataL = 0;
   auto t1 = std::chrono::steady_clock::now();
@@ -250,6 +455,22 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
       fprintf(trace, "\t%.6f\t%.6f\n", logL, dataL);
       fflush(trace);
       if (summary_path && (rc = gph_engine_locus_summary_sample(E))) return fail(rc, "gph_engine_locus_summary_sample");
+      if (cs_prefix) {
+        if ((rc = gph_engine_coal_stats_sample(E, it))) return fail(rc, "gph_engine_coal_stats_sample");
+        /* logPrior of the parameters this trace line shows: what getLogPrior sums (GPhoCS.c:858-898) -- theta of every population,
+         * tau of every ancestral one, the rate of every band, each under its gamma prior of the control file */
+        gph_mcmc_get_state(M, nullptr, nullptr, cs_theta.data(), cs_age.data(), cs_mig.data());
+        /* log density of a gamma(shape, rate) prior at x: shape ln(rate) - ln Gamma(shape) + (shape - 1) ln x - rate x */
+        auto gamma_lpdf = [](double shape, double rate, double x) {
+          return shape * std::log(rate) - std::lgamma(shape) + (shape - 1.0) * std::log(x) - rate * x;
+        };
+        double lp = 0.0;
+        for (int p = 0; p < cfg.K; p++) lp += gamma_lpdf(mc.thetaAlpha[p], mc.thetaBeta[p], cs_theta[p]);
+        for (int p = cfg.Kc; p < cfg.K; p++) lp += gamma_lpdf(mc.ageAlpha[p], mc.ageBeta[p], cs_age[p]);
+        for (int b = 0; b < cfg.B; b++) lp += gamma_lpdf(mc.mrAlpha[b], mc.mrBeta[b], cs_mig[b]);
+        cs_prior.push_back(lp);
+        if ((int32_t)cs_prior.size() == cs_capacity && (rc = cs_flush())) return fail(rc, "writing the coal-stats part file");
+      }
     }
     logCount++;
     if ((it + 1) % samplesPerLog == 0) {
@@ -316,6 +537,13 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   }
   fclose(trace);
   trace = nullptr;
+  if (cs_prefix) {
+    if ((rc = cs_flush())) return fail(rc, "writing the coal-stats part file");
+    if (fwrite(&cs_written, sizeof cs_written, 1, cs_part) != 1) return fail(GPH_EARG, "writing the coal-stats part file");   /* the trailer: records in this part */
+    const int rcc = fclose(cs_part);
+    cs_part = nullptr;
+    if (rcc != 0) return fail(GPH_EARG, "closing the coal-stats part file");
+  }
   int32_t ls_ncol = 0;
   int64_t ls_samples = 0;
   std::vector<double> ls_raw;
@@ -331,9 +559,10 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_engine_destroy(E);
   if (oob_checked && oob_where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
+                    "3 gph_summary.h, 4 gph_coalstats.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
     gph_loci_free(LC);
     gph_control_free(C);
+    if (cs_prefix && world == 1) gph_coal_stats_discard(cs_prefix, 1);
     return GPH_EKERNEL;
   }
   rc = GPH_OK;
@@ -344,6 +573,11 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   }
   gph_loci_free(LC);
   gph_control_free(C);
+  /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
+  if (cs_prefix && world == 1) {
+    if (rc) gph_coal_stats_discard(cs_prefix, 1);
+    else rc = gph_coal_stats_write(cs_prefix, 1);
+  }
   return rc;
 }
 
@@ -361,8 +595,15 @@ extern "C" int gph_run_control_file_comm(const char *ctl, const char *ctl2, int3
 extern "C" int gph_run_control_file_ex(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
                                        const char *locus_summary_path)
 {
-  if (comm) return run_control_file(ctl, ctl2, device, verbose, gph_comm_rank(comm), gph_comm_world(comm), nullptr, nullptr, comm, locus_summary_path);
-  return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr, locus_summary_path);
+  return gph_run_control_file_ex2(ctl, ctl2, device, verbose, comm, locus_summary_path, nullptr, 0);
+}
+
+extern "C" int gph_run_control_file_ex2(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
+                                        const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity)
+{
+  if (comm) return run_control_file(ctl, ctl2, device, verbose, gph_comm_rank(comm), gph_comm_world(comm), nullptr, nullptr, comm, locus_summary_path,
+                                    coal_stats_prefix, coal_stats_capacity);
+  return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr, locus_summary_path, coal_stats_prefix, coal_stats_capacity);
 }
 
 extern "C" int gph_run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose)

@@ -46,6 +46,7 @@ extern "C" {
 #define GPH_EHIP (-2)      /* HIP runtime failure (no device, OOM, launch error) */
 #define GPH_EKERNEL (-3)   /* a locus reported a fatal consistency error (reference: "Fatal Error NNNN") */
 #define GPH_ESTATE (-4)    /* call out of order */
+#define GPH_EFULL (-5)     /* gph_engine_coal_stats_sample: every row of the device buffer is taken; fetch first */
 
 typedef struct gph_engine gph_engine;
 typedef struct gph_mcmc gph_mcmc;
@@ -220,7 +221,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
 /* timing of the last launch of a named kernel class, measured with HIP events on the
  * engine's own stream: which = 0 sweep, 1 tau_eval, 2 mix_eval, 3 init, 4 check,
  * 5 tau_finish (commit or revert, by the decision flag), 7 mix_finish, 8 sync, 9 locus-rate scan, 10 locus-rate apply,
- * 11 locus-rate prepare, 13 locus summary (gph_engine_locus_summary_sample) */
+ * 11 locus-rate prepare, 13 locus summary (gph_engine_locus_summary_sample), 14 coalescent / sample-pair statistics
+ * (gph_engine_coal_stats_sample: k_coal_stats + k_coal_fold together) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -268,6 +270,41 @@ int gph_engine_locus_summary_sample(gph_engine *e);
 int gph_engine_locus_summary_columns(gph_engine *e, int32_t *ncol, int64_t *samples);
 int gph_engine_locus_summary_fetch(gph_engine *e, double *out, int64_t ld, int32_t reset);
 const char *gph_engine_locus_summary_column_name(gph_engine *e, int32_t col);
+/* genome-wide coalescent statistics and sample-pair statistics of one MCMC sample, computed on the device (k_coal_stats,
+ * k_coal_fold: csrc/gph_coalstats.h).  They replace code the reference carries but never reaches (`coal-stats-file`,
+ * GPhoCS.c:1771 `if (recordCoalStats && 0)`): computeNodeStats (patch.c:2172-2270) over computePairwiseLCAs
+ * (LocusDataLikelihood.c:1685-1830), computeFlatStats (patch.c:2278-2320) over getSortedAges
+ * (LocusDataLikelihood.c:1216-1260), and the numbers printCoalStats prints (GPhoCS.c:911-1040).
+ * A raw row of row_doubles = 7 + 3 * n(n-1)/2 * K doubles, over THIS rank's loci:
+ *   [0] iteration  [1] coalStat  [2] numCoal  [3] migStat  [4] numMig  [5] sum of genealogy log-likelihoods
+ *   [6] sum of data log-likelihoods, then three blocks [pair][population], pairs (i, j), i < j, row-major:
+ *   cnt (loci in which the pair coalesces in the population), first (... and that coalescence is the population's first
+ *   in the locus), agesum (summed age of those coalescences).  Counts are doubles holding integers.
+ * Derived as printCoalStats / computeNodeStats do (patch.c:2256-2266): probCoal = cnt / L, probFirstCoal = first / L,
+ * meanCoal = agesum / cnt where cnt > 0, else 0, with L the loci of all ranks; logGenLikelihood = [5] + [6]
+ * (GPhoCS.c:997 prints dataState.logLikelihood * numLoci, data + genealogy), logDataLikelihood = [6].  logPrior
+ * (getLogPrior, GPhoCS.c:858-898) is a function of the parameters alone and is added by the caller.  Several ranks: the
+ * ranks' raw rows are added in rank order before anything is derived.
+ *   _enable(capacity)  allocates a device buffer of `capacity` rows (capacity 0: frees everything, the feature is off);
+ *                      gph_engine_init_genealogies empties it
+ *   _sample(iteration) queues one sample on the engine's stream (no host synchronisation) into the next free row; a
+ *                      mixing commit still owed to the next sweep kernel runs first.  GPH_EFULL when no row is free:
+ *                      nothing is overwritten
+ *   _shape             doubles per row, rows filled since the last fetch, leaves, populations
+ *   _fetch             copies the filled rows to out[max_rows >= filled][row_doubles], *rows = their number, and
+ *                      empties the buffer
+ *   _column_name       machine name of raw column col: "iter", "coalStat", "numCoal", "migStat", "numMig", "genLnL",
+ *                      "dataLnL", "cnt.<i>.<j>.<pop>", "first.<i>.<j>.<pop>", "agesum.<i>.<j>.<pop>"; NULL if out of
+ *                      range; the string is valid until the next call on this engine */
+int gph_engine_coal_stats_enable(gph_engine *e, int32_t capacity);
+int gph_engine_coal_stats_sample(gph_engine *e, int32_t iteration);
+int gph_engine_coal_stats_shape(gph_engine *e, int32_t *row_doubles, int32_t *filled, int32_t *n, int32_t *K);
+int gph_engine_coal_stats_fetch(gph_engine *e, double *out, int32_t max_rows, int32_t *rows);
+const char *gph_engine_coal_stats_column_name(gph_engine *e, int32_t col);
+/* tests: slots per chunk used by the next _enable (0 = the default, 128).  The chunk size is part of the summation order
+ * of the fp64 sums (csrc/gph_coalstats.h): rows are bitwise reproducible for a given locus count, chunk size and rank
+ * count */
+int gph_engine_coal_stats_set_chunk(gph_engine *e, int32_t slots);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -411,6 +448,24 @@ int gph_run_control_file_comm(const char *ctl_path, const char *secondary_ctl_pa
  * (rank 0's part holds the header) and the caller concatenates the parts in rank order.  NULL = no table. */
 int gph_run_control_file_ex(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null);
+/* the same, plus the coalescent / sample-pair statistics (`G-PhoCS-hip -s PREFIX`; printCoalStats, GPhoCS.c:911-1040): a
+ * sample after every trace line into a device buffer of coal_stats_capacity rows (<= 0: 64, fewer when 64 rows of
+ * 7 + 3 * n(n-1)/2 * K doubles would exceed 256 MB).  Whenever the buffer is
+ * full, and at the end, rank r appends its raw rows (each followed by logPrior) to the binary file
+ * coal_stats_prefix.coal.part<r>.  gph_coal_stats_write(prefix, ranks) then adds the parts in rank order and writes
+ * PREFIX.coal.tsv and, per population, PREFIX.<pop>.probCoal.tsv / .probFirstCoal.tsv / .meanCoal.tsv, and removes the
+ * parts; gph_coal_stats_discard(prefix, ranks) only removes them.  A one-rank run (comm NULL or of one rank) calls
+ * _write itself when it succeeds and _discard when it fails; with several ranks the caller does, after every rank has
+ * returned.  Either way a run that did not finish leaves none of the .tsv files.  NULL prefix = no statistics. */
+int gph_run_control_file_ex2(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
+                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null,
+                             const char *coal_stats_prefix_or_null, int32_t coal_stats_capacity);
+int gph_coal_stats_write(const char *prefix, int32_t ranks);
+/* the records gph_coal_stats_write would print, before it is called: *rows samples of *row_doubles doubles (the raw row
+ * of the ranks' parts added in rank order, then logPrior) into out[max_rows >= *rows]; out NULL: the two counts only.
+ * A part that is missing, damaged or was not closed by its rank (no record count at its end) is an error. */
+int gph_coal_stats_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles);
+int gph_coal_stats_discard(const char *prefix, int32_t ranks);
 
 /* ------------------------------------------------------------------------------------
  * post-run summary of a trace file (host only): block means per column, the output of the reference's
