@@ -289,6 +289,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_coal_stats_enable", "gph_engine_coal_stats_sample", "gph_engine_coal_stats_shape", "gph_engine_coal_stats_fetch",
     "gph_engine_coal_stats_column_name", "gph_run_control_file_ex2", "gph_coal_stats_write", "gph_coal_stats_discard",
     "gph_engine_coal_stats_set_chunk", "gph_coal_stats_combined",
+    "gph_engine_time_slices_enable", "gph_engine_time_slices_sample", "gph_engine_time_slices_shape", "gph_engine_time_slices_fetch",
+    "gph_engine_time_slices_column_name", "gph_engine_time_slices_set_chunk", "gph_run_control_file_ex3", "gph_time_slices_write",
+    "gph_time_slices_combined", "gph_time_slices_discard",
 ]
 
 
@@ -405,6 +408,17 @@ def _load_library(path):
     lib.gph_coal_stats_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_engine_coal_stats_set_chunk.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_coal_stats_combined.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gph_engine_time_slices_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.gph_engine_time_slices_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_time_slices_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 6
+    lib.gph_engine_time_slices_fetch.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_time_slices_column_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_time_slices_column_name.restype = C.c_char_p
+    lib.gph_engine_time_slices_set_chunk.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_run_control_file_ex3.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32]
+    lib.gph_time_slices_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_time_slices_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_time_slices_combined.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     return lib
 
 
@@ -656,6 +670,30 @@ def coal_stats_combined(lib, prefix, ranks):
     return out
 
 
+def time_slices_table(rows, S, K, B):
+    """raw time-slices rows ([samples][1 + 2 S (K + B)], gph_engine_time_slices_fetch; several ranks: added in rank order
+    first) as one dict per sample: iter, numCoal and deltaT as (K, S) arrays, numMig and migT as (B, S) arrays"""
+    out = []
+    for r in np.asarray(rows, dtype=np.float64).reshape(-1, 1 + 2 * S * (K + B)):
+        cells = r[1:].reshape(K + B, S, 2)
+        out.append(dict(iter=int(r[0]), numCoal=cells[:K, :, 0].astype(np.int64), deltaT=cells[:K, :, 1].copy(),
+                        numMig=cells[K:, :, 0].astype(np.int64), migT=cells[K:, :, 1].copy()))
+    return out
+
+
+def time_slices_combined(lib, prefix, ranks):
+    """(samples, row_doubles) array: the records of PREFIX.slices.part<0..ranks-1> added in rank order
+    (gph_time_slices_combined)"""
+    rows, rd = C.c_int64(), C.c_int32()
+    if lib.gph_time_slices_combined(str(prefix).encode(), ranks, None, 0, C.byref(rows), C.byref(rd)):
+        raise RuntimeError("gphocs_hip: time_slices_combined failed")
+    out = np.zeros((rows.value, rd.value))
+    if rows.value and lib.gph_time_slices_combined(str(prefix).encode(), ranks, out.ctypes.data_as(C.POINTER(C.c_double)), rows.value,
+                                                   C.byref(rows), C.byref(rd)):
+        raise RuntimeError("gphocs_hip: time_slices_combined failed")
+    return out
+
+
 def _dp(a):
     return np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
 
@@ -866,6 +904,47 @@ class Sampler:
         rd = C.c_int32()
         self._chk(self.lib.gph_engine_coal_stats_shape(self.engine, C.byref(rd), None, None, None), "coal_stats_shape")
         return [self.lib.gph_engine_coal_stats_column_name(self.engine, c).decode() for c in range(rd.value)]
+
+    # ---- coalescence / migration statistics per time slice (gph_engine_time_slices_*): one row per call, on the device
+    def enable_time_slices(self, slices, capacity, chunk=0):
+        """a device buffer of `capacity` samples of `slices` slices per branch and band; capacity 0 switches the feature off.
+        chunk (tests): slots per chunk of the kernel, 0 = the default.  ValueError for a slice count out of range"""
+        self._chk(self.lib.gph_engine_time_slices_set_chunk(self.engine, int(chunk)), "time_slices_set_chunk")
+        rc = self.lib.gph_engine_time_slices_enable(self.engine, int(slices), int(capacity))
+        if rc == -1 and capacity > 0:
+            raise ValueError(f"gphocs_hip: time_slices_enable refused slices={slices}, capacity={capacity} (GPH_EARG)")
+        self._chk(rc, "time_slices_enable")
+
+    def sample_time_slices(self, it):
+        """one sample of the current state, labelled iteration `it`; BufferError when the device buffer is full"""
+        rc = self.lib.gph_engine_time_slices_sample(self.engine, int(it))
+        if rc == COAL_STATS_FULL:
+            raise BufferError("gphocs_hip: the time-slices buffer is full; fetch with time_slices() first")
+        self._chk(rc, "time_slices_sample")
+
+    def _time_slices_shape(self):
+        v = [C.c_int32() for _ in range(6)]
+        self._chk(self.lib.gph_engine_time_slices_shape(self.engine, *[C.byref(x) for x in v]), "time_slices_shape")
+        return [x.value for x in v]
+
+    def time_slices_staged_bytes(self):
+        """bytes of a page k_time_slices copies into LDS per locus and sample"""
+        return self._time_slices_shape()[5]
+
+    def time_slices(self, raw=True):
+        """the samples taken since the last call (the device buffer is emptied).  raw=True: a (samples, 1 + 2 S (K + B)) array
+        over THIS rank's loci (columns: time_slices_columns()); raw=False: a list of dicts (time_slices_table)"""
+        rd, fill, S, K, B, _ = self._time_slices_shape()
+        out = np.zeros((max(fill, 1), max(rd, 1)))
+        got = C.c_int32()
+        self._chk(self.lib.gph_engine_time_slices_fetch(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[0], C.byref(got)),
+                  "time_slices_fetch")
+        out = out[:got.value]
+        return out if raw else time_slices_table(out, S, K, B)
+
+    def time_slices_columns(self):
+        rd = self._time_slices_shape()[0]
+        return [self.lib.gph_engine_time_slices_column_name(self.engine, c).decode() for c in range(rd)]
 
     def hbm_bytes(self):
         b = C.c_double()

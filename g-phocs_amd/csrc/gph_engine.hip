@@ -23,6 +23,7 @@
 #include "gph_global.h"
 #include "gph_summary.h"
 #include "gph_coalstats.h"
+#include "gph_timeslices.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
 
@@ -440,6 +441,13 @@ struct gph_engine {
   int32_t cs_cap = 0, cs_fill = 0, cs_rd = 0, cs_chunk = 0, cs_nchunks = 0, cs_bd = 0;
   int32_t cs_chunk_next = 0;   // slots per chunk of the next _enable (gph_engine_coal_stats_set_chunk; 0: GPH_CS_CHUNK)
   std::string cs_name;
+  // time-sliced coalescence / migration statistics (gph_timeslices.h): per-chunk partial rows, the rows of the samples taken
+  // since the last fetch ([ts_cap][ts_rd]); all null / 0 while the feature is off
+  double *d_ts_part = nullptr, *d_ts_rows = nullptr;
+  int32_t ts_cap = 0, ts_fill = 0, ts_rd = 0, ts_chunk = 0, ts_nchunks = 0;
+  int32_t ts_chunk_next = 0;   // slots per chunk of the next _enable (gph_engine_time_slices_set_chunk; 0: GPH_TS_CHUNK)
+  GphTsShape ts_shape = {};
+  std::string ts_name;
   double last_ms[16] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[16] = {0}, cls_ms[16] = {0};
@@ -1094,6 +1102,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free((void *)e->dev.seq); dev_free((void *)e->dev.seq_off); dev_free((void *)e->dev.orig); dev_free((void *)e->dev.P); dev_free(e->dev.out); dev_free(e->dev.stats); dev_free(e->d_mutRate);
   dev_free(e->d_lrec); dev_free(e->d_lpre); dev_free(e->d_slot_of); dev_free(e->d_lr_result); dev_free(e->d_lr_gscr); dev_free(e->d_ref_page); dev_free(e->d_ref_seq);
   dev_free(e->d_part); dev_free(e->dev.err); dev_free(e->d_ls); dev_free(e->d_cs_part); dev_free(e->d_cs_rows);
+  dev_free(e->d_ts_part); dev_free(e->d_ts_rows);
   for (void *p : e->deferred_free) dev_free(p);
   e->deferred_free.clear();
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
@@ -1421,6 +1430,7 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   if (e->d_ls && e->ls_ncol != gph_ls_columns(e->cfg.K, e->cfg.B, e->var_rates)) { int rce = gph_engine_locus_summary_enable(e, 1); if (rce) return rce; }
   { int rcz = ls_zero(e); if (rcz) return rcz; }
   e->cs_fill = 0;
+  e->ts_fill = 0;
   LAUNCH(e, 3, k_init, e->seedz, (const double *)e->d_mutRate, e->init_predraws);
   int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -2616,6 +2626,131 @@ const char *gph_engine_coal_stats_column_name(gph_engine *e, int32_t col)
   while (i < n - 2 && p >= n - 1 - i) { p -= n - 1 - i; i++; }
   e->cs_name = std::string(block == 0 ? "cnt." : block == 1 ? "first." : "agesum.") + std::to_string(i) + "." + std::to_string(i + 1 + p) + "." + std::to_string(q % K);
   return e->cs_name.c_str();
+}
+
+// ---- coalescence and migration statistics per time slice, per sample (gph_timeslices.h)
+int gph_engine_time_slices_enable(gph_engine *e, int32_t slices, int32_t capacity)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity < 0) return GPH_EARG;
+  SETDEV(e);
+  if (e->d_ts_part) { eng_free(e, e->d_ts_part); e->d_ts_part = nullptr; }
+  if (e->d_ts_rows) { eng_free(e, e->d_ts_rows); e->d_ts_rows = nullptr; }
+  e->ts_cap = e->ts_fill = e->ts_rd = e->ts_chunk = e->ts_nchunks = 0;
+  e->ts_shape = GphTsShape{};
+  if (capacity == 0) return 0;
+  GphTsShape h;
+  if (gph_ts_shape(e->lay, slices, h)) {
+    fprintf(stderr, "gphocs_hip: time slices: %d slices requested, 1 to %d are supported\n", (int)slices, GPH_TS_MAXS);
+    return GPH_EARG;
+  }
+  if (h.lds_bytes > 65536) {
+    fprintf(stderr, "gphocs_hip: time slices: %d slices need %d bytes of LDS a workgroup, 65536 at most\n", (int)slices, (int)h.lds_bytes);
+    return GPH_EARG;
+  }
+  const int chunk = e->ts_chunk_next > 0 ? e->ts_chunk_next : GPH_TS_CHUNK;
+  const int rd = gph_ts_row_doubles(e->cfg.K, e->cfg.B, slices);
+  const int nchunks = (int)((e->L + chunk - 1) / chunk);
+  if (dev_alloc((void **)&e->d_ts_part, sizeof(double) * (size_t)rd * nchunks)) { e->d_ts_part = nullptr; return GPH_EHIP; }
+  if (dev_alloc((void **)&e->d_ts_rows, sizeof(double) * (size_t)rd * capacity)) {
+    e->d_ts_rows = nullptr;
+    dev_free(e->d_ts_part);
+    e->d_ts_part = nullptr;
+    return GPH_EHIP;
+  }
+  /* (every cell of a partial row is written by its chunk's workgroups, the root's zero slices included) */
+  e->ts_cap = capacity; e->ts_rd = rd; e->ts_chunk = chunk; e->ts_nchunks = nchunks; e->ts_shape = h;
+  return 0;
+}
+
+// tests: the slots per chunk the next _enable uses (0: the default).  The chunk size is part of the summation order
+int gph_engine_time_slices_set_chunk(gph_engine *e, int32_t slots)
+{
+  if (!e || slots < 0) return GPH_EARG;
+  e->ts_chunk_next = slots;
+  return 0;
+}
+
+// one sample of the current state into the next free row, queued on the engine's stream.  The walkers read event times
+// and the model in the chain state, so more has to be settled first than for gph_engine_coal_stats_sample (node records
+// only): a host-side change of the chain state is pushed, the commit / revert of a decided tau or sample-age proposal
+// still owed to the next evaluate kernel runs (k_tau_finish: one more launch; never owed after a whole
+// gph_engine_iteration_, only between the parts of a stepwise caller), and, as there, the commit of an accepted mixing
+// proposal owed to the next sweep kernel (k_mix_finish).  A deferred synchronizeEvents pass STAYS
+// deferred: the walkers apply its arithmetic to the event times they read (vsync, gph_timeslices.h), so the row is that of
+// the chain as the pass will leave it
+int gph_engine_time_slices_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->d_ts_rows) return GPH_ESTATE;
+  if (e->ts_fill >= e->ts_cap) return GPH_EFULL;
+  SETDEV(e);
+  PUSH_IF_DIRTY(e);
+  { int rcw = finish_owed(e); if (rcw) return rcw; }
+  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
+  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
+  const int L = (int)e->L, rd = e->ts_rd, vsync = e->sync_pending ? 1 : 0;
+  const GphTsShape &h = e->ts_shape;
+  double *row = e->d_ts_rows + (size_t)e->ts_fill * rd;
+#ifdef GPH_HOSTEMU
+  std::vector<char> lds;
+  for (int ch = 0; ch < e->ts_nchunks; ch++)
+    for (int t = 0; t < h.ntiles; t++) time_slices_workgroup(e->lay, h, e->G_h, (const char *)e->dev.pages, e->d_ts_part, L, e->ts_chunk, rd, vsync, ch, t, lds);
+  for (int c = 0; c < rd; c++) gph_ts_fold_column(e->d_ts_part, e->ts_nchunks, rd, c, (double)iteration, row);
+  e->cls_launches[15] += 1;
+#else
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  const int tms = tm_begin(e, 15);
+  hipLaunchKernelGGL(k_time_slices, dim3((unsigned)e->ts_nchunks, (unsigned)h.ntiles), dim3((unsigned)h.bd), (size_t)h.lds_bytes, e->stream,
+                     e->lay, h, (const GphGlobal *)e->G_d, (const char *)e->dev.pages, e->d_ts_part, L, e->ts_chunk, rd, vsync);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_time_slices_fold, dim3((unsigned)((rd + GPH_TS_FOLD_THREADS - 1) / GPH_TS_FOLD_THREADS)), dim3(GPH_TS_FOLD_THREADS), 0, e->stream,
+                     (const double *)e->d_ts_part, e->ts_nchunks, rd, (double)iteration, row);
+  HIPCHK(hipGetLastError());
+  tm_end(e, tms);
+  e->n_launches += 2;
+  e->last_which = 15;
+  e->cls_launches[15] += 1;
+#endif
+  e->ts_fill++;
+  return 0;
+}
+
+int gph_engine_time_slices_shape(gph_engine *e, int32_t *row_doubles, int32_t *filled, int32_t *slices, int32_t *K, int32_t *B,
+                                 int32_t *staged_bytes_per_locus)
+{
+  if (!e) return GPH_EARG;
+  if (row_doubles) *row_doubles = e->ts_rd;
+  if (filled) *filled = e->ts_fill;
+  if (slices) *slices = e->ts_shape.S;
+  if (staged_bytes_per_locus) *staged_bytes_per_locus = e->ts_shape.img.bytes;
+  if (K) *K = e->cfg.K;
+  if (B) *B = e->cfg.B;
+  return 0;
+}
+
+int gph_engine_time_slices_fetch(gph_engine *e, double *out, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || (!out && max_rows > 0)) return GPH_EARG;
+  if (!e->d_ts_rows) return GPH_ESTATE;
+  if (max_rows < e->ts_fill) return GPH_EARG;
+  SETDEV(e);
+  *rows = e->ts_fill;
+  if (e->ts_fill > 0) {
+    int rc = d2h(e, out, e->d_ts_rows, sizeof(double) * (size_t)e->ts_rd * e->ts_fill);
+    if (rc) return rc;
+  }
+  e->ts_fill = 0;
+  return 0;
+}
+
+const char *gph_engine_time_slices_column_name(gph_engine *e, int32_t col)
+{
+  if (!e || col < 0 || col >= e->ts_rd) return nullptr;
+  if (col == 0) return "iter";
+  const int S = e->ts_shape.S, K = e->cfg.K, q = (col - 1) / 2, W = q / S, k = q % S + 1, second = (col - 1) & 1;
+  const char *what = W < K ? (second ? "deltaT." : "numCoal.") : (second ? "migT." : "numMig.");
+  e->ts_name = std::string(what) + std::to_string(W < K ? W : W - K) + "." + std::to_string(k);
+  return e->ts_name.c_str();
 }
 
 } // extern "C"

@@ -2736,6 +2736,8 @@ GPH_DEV void replace_mig_nodes(int node)
 }
 
 // synchronizeEvents, patch.c:3548-3633
+// (gph_ts_walk, gph_timeslices.h, applies the SAME arithmetic to the event times it reads while this pass is deferred -- the
+// `vsync` block there must stay bit-identical to the loop body below: a change here is mirrored there)
 GPH_DEV int synchronize_events()
 {
   int i, pop, ev, id, res = 1;

@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N]] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -20,6 +20,10 @@
 // PREFIX.coal.part<r> (--coal-stats-rows N: rows of the device buffer between two flushes, default 64); after every child
 // has exited 0 the launcher has the library add the parts in rank order and write the files (gph_coal_stats_write); on a
 // failure the parts are removed and no file is written.
+//
+// --time-slices S (with -s PREFIX only): additionally PREFIX.slices.tsv, the coalescence / migration statistics of every
+// sample per time slice (gph_run_control_file_ex3); the ranks' PREFIX.slices.part<r> are handled like the coal-stats parts
+// (gph_time_slices_write / _discard).
 #include "gphocs_hip.h"
 #include <dlfcn.h>
 #include <libgen.h>
@@ -92,7 +96,7 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N]] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
@@ -100,7 +104,7 @@ int main(int argc, char **argv)
 {
   int verbose = 0, device = 0, gpus = 1, i = 1;
   const char *summary = nullptr, *coal = nullptr;
-  int coal_rows = 0;
+  int coal_rows = 0, slices = 0;
   for (; i < argc && argv[i][0] == '-'; i++) {
     if (!strcmp(argv[i], "-v") || !strcmp(argv[i], "--verbose")) verbose = 1;
     else if (!strcmp(argv[i], "-d") && i + 1 < argc) device = atoi(argv[++i]);
@@ -108,10 +112,12 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "-l") && i + 1 < argc) summary = argv[++i];
     else if (!strcmp(argv[i], "-s") && i + 1 < argc) coal = argv[++i];
     else if (!strcmp(argv[i], "--coal-stats-rows") && i + 1 < argc) coal_rows = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--time-slices") && i + 1 < argc) { slices = atoi(argv[++i]); if (slices < 1) return usage(argv[0]); }
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
   if (i >= argc || gpus < 1 || gpus > 64) return usage(argv[0]);
+  if (slices && !coal) { fprintf(stderr, "%s: --time-slices needs -s PREFIX\n", argv[0]); return usage(argv[0]); }
   const char *ctl = argv[i], *ctl2 = i + 1 < argc ? argv[i + 1] : nullptr;
   char self[PATH_MAX];
   ssize_t k = readlink("/proc/self/exe", self, sizeof self - 1);
@@ -120,6 +126,7 @@ int main(int argc, char **argv)
   const std::string dir = dirname(self);
   if (gpus == 1) {
     void *h = load_engine(dir, ctl, ctl2);
+    if (slices) return sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices) ? 1 : 0;
     if (coal) return sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows) ? 1 : 0;
     if (summary) return sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, device, verbose, nullptr, summary) ? 1 : 0;
     return sym<decltype(&gph_run_control_file)>(h, "gph_run_control_file")(ctl, ctl2, device, verbose) ? 1 : 0;
@@ -166,7 +173,8 @@ int main(int argc, char **argv)
         comm = create_rccl(mb->id, r, gpus, mydev);
       }
       if (!comm) { fprintf(stderr, "G-PhoCS-hip: rank %d could not join the communicator\n", r); _exit(2); }
-      int rc = coal ? sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows) :
+      int rc = slices ? sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices) :
+               coal ? sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows) :
                summary ? sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, mydev, verbose, comm, summary)
                        : sym<decltype(&gph_run_control_file_comm)>(h, "gph_run_control_file_comm")(ctl, ctl2, mydev, verbose, comm);
       fflush(stdout);
@@ -221,8 +229,11 @@ int main(int argc, char **argv)
   if (coal) {
     /* the ranks' raw rows, added in rank order by the library that wrote them (the launcher itself has not touched a GPU) */
     void *h = load_engine(dir, ctl, ctl2);
+    /* (the slices file first; should the coal-stats files fail after it, _discard removes it again) */
+    if (slices && !bad && sym<decltype(&gph_time_slices_write)>(h, "gph_time_slices_write")(coal, gpus)) bad = 1;
     if (bad) sym<decltype(&gph_coal_stats_discard)>(h, "gph_coal_stats_discard")(coal, gpus);
     else if (sym<decltype(&gph_coal_stats_write)>(h, "gph_coal_stats_write")(coal, gpus)) bad = 1;
+    if (slices && bad) sym<decltype(&gph_time_slices_discard)>(h, "gph_time_slices_discard")(coal, gpus);
   }
   return bad;
 }

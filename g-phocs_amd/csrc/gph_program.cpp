@@ -11,6 +11,7 @@
 #include <ctime>
 #include <string>
 #include <vector>
+#include <unistd.h>
 
 namespace {
 // one step of the find-finetunes search for one step size (GPhoCS.c:1896-2180, the same block per proposal
@@ -239,11 +240,133 @@ extern "C" int gph_coal_stats_write(const char *prefix, int32_t ranks)
   return ok ? GPH_OK : GPH_EARG;
 }
 
+
+// ---- time-sliced statistics (`-s PREFIX --time-slices S`): rank r's raw rows travel through PREFIX.slices.part<r> -- a
+// header (magic, S, K, B, doubles per row, the population names and the bands' "src->tgt" names), one record of
+// row_doubles doubles per sample and, written when the rank closes its part, the number of records
+namespace {
+const char TS_MAGIC[8] = {'G', 'P', 'H', 'T', 'S', '1', '\n', 0};
+std::string ts_part_path(const char *prefix, int r) { return std::string(prefix) + ".slices.part" + std::to_string(r); }
+
+struct TsReader {
+  std::vector<FILE *> f;
+  int32_t S = 0, K = 0, B = 0, rd = 0;
+  int64_t samples = 0;
+  std::vector<std::string> names;     /* K population names, then B band names */
+  std::vector<double> tmp;
+  ~TsReader() { for (FILE *x : f) if (x) fclose(x); }
+  bool open(const char *prefix, int ranks)
+  {
+    for (int r = 0; r < ranks; r++) {
+      const std::string path = ts_part_path(prefix, r);
+      FILE *x = fopen(path.c_str(), "rb");
+      f.push_back(x);
+      char magic[8];
+      int32_t hdr[4], nbytes = 0;
+      int64_t count = -1;
+      bool ok = x && fread(magic, 1, 8, x) == 8 && !memcmp(magic, TS_MAGIC, 8) && fread(hdr, 4, 4, x) == 4 && fread(&nbytes, 4, 1, x) == 1 &&
+                nbytes >= 0 && hdr[0] >= 1 && hdr[1] >= 1 && hdr[2] >= 0 && hdr[3] == 1 + 2 * hdr[0] * (hdr[1] + hdr[2]);
+      std::vector<std::string> nm;
+      if (ok) {
+        std::vector<char> buf((size_t)nbytes + 1, 0);
+        ok = fread(buf.data(), 1, (size_t)nbytes, x) == (size_t)nbytes;
+        for (size_t at = 0; ok && at < (size_t)nbytes; at += strlen(buf.data() + at) + 1) nm.push_back(buf.data() + at);
+        ok = ok && (int)nm.size() == hdr[1] + hdr[2];
+      }
+      if (ok) {
+        const long body = ftell(x);
+        ok = body > 0 && fseek(x, -8, SEEK_END) == 0;
+        const long tail = ok ? ftell(x) : 0;
+        ok = ok && fread(&count, 8, 1, x) == 1 && count >= 0 && tail - body == (long)(count * (int64_t)hdr[3] * 8) && fseek(x, body, SEEK_SET) == 0;
+      }
+      if (!ok) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); return false; }
+      if (r == 0) { S = hdr[0]; K = hdr[1]; B = hdr[2]; rd = hdr[3]; samples = count; names = nm; }
+      else if (hdr[0] != S || hdr[1] != K || hdr[2] != B || count != samples) { fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", path.c_str()); return false; }
+    }
+    tmp.resize((size_t)rd);
+    return true;
+  }
+  /* the ranks' records of the next sample, added in rank order (the iteration is rank 0's) */
+  bool next(std::vector<double> &rec)
+  {
+    rec.resize((size_t)rd);
+    for (size_t r = 0; r < f.size(); r++) {
+      std::vector<double> &into = r == 0 ? rec : tmp;
+      if (fread(into.data(), sizeof(double), into.size(), f[r]) != into.size()) return false;
+      if (r > 0) for (int c = 1; c < rd; c++) rec[c] = rec[c] + tmp[c];
+    }
+    return true;
+  }
+};
+}   // namespace
+
+// the parts, and PREFIX.slices.tsv should it exist already (the run failed after it was written: a failed run leaves none)
+extern "C" int gph_time_slices_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  for (int r = 0; r < ranks; r++) remove(ts_part_path(prefix, r).c_str());
+  unlink((std::string(prefix) + ".slices.tsv").c_str());   /* (a file only: whatever else sits under that name is not ours) */
+  return GPH_OK;
+}
+
+extern "C" int gph_time_slices_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles)
+{
+  if (!prefix || ranks < 1 || !rows || !row_doubles) return GPH_EARG;
+  TsReader R;
+  if (!R.open(prefix, ranks)) return GPH_EARG;
+  *rows = R.samples;
+  *row_doubles = R.rd;
+  if (!out) return GPH_OK;
+  if (max_rows < R.samples) return GPH_EARG;
+  std::vector<double> rec;
+  for (int64_t i = 0; i < R.samples; i++) {
+    if (!R.next(rec)) return GPH_EARG;
+    memcpy(out + (size_t)i * rec.size(), rec.data(), sizeof(double) * rec.size());
+  }
+  return GPH_OK;
+}
+
+extern "C" int gph_time_slices_write(const char *prefix, int32_t ranks)
+{
+  if (!prefix || ranks < 1) return GPH_EARG;
+  const std::string path = std::string(prefix) + ".slices.tsv";
+  FILE *out = nullptr;
+  bool ok;
+  {
+    TsReader R;
+    ok = R.open(prefix, ranks);
+    if (ok && !(out = fopen(path.c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s\n", path.c_str()); ok = false; }
+    if (ok) {
+      /* the partition columns of printCoalStats (GPhoCS.c:927-935), then the bands' */
+      fprintf(out, "iter");
+      for (int q = 0; q < R.K + R.B; q++)
+        for (int k = 1; k <= R.S; k++) {
+          if (q < R.K) fprintf(out, "\tnumCoal_%s:%d\tdeltaT_%s:%d", R.names[q].c_str(), k, R.names[q].c_str(), k);
+          else fprintf(out, "\tnumMig_%s:%d\tmigT_%s:%d", R.names[q].c_str(), k, R.names[q].c_str(), k);
+        }
+      fprintf(out, "\n");
+      std::vector<double> rec;
+      for (int64_t s = 0; s < R.samples && ok; s++) {
+        if (!R.next(rec)) { fprintf(stderr, "gphocs_hip: a part of %s ended early\n", path.c_str()); ok = false; break; }
+        fprintf(out, "%7d", (int)rec[0]);
+        for (int c = 1; c < R.rd; c += 2) fprintf(out, "\t%9d\t%8f", (int)rec[c], rec[c + 1]);   /* GPhoCS.c:1005 */
+        fprintf(out, "\n");
+      }
+    }
+    if (out && (ferror(out) | fclose(out)) != 0) { fprintf(stderr, "gphocs_hip: writing %s failed\n", path.c_str()); ok = false; }
+  }
+  for (int r = 0; r < ranks; r++) remove(ts_part_path(prefix, r).c_str());
+  if (!ok && out) remove(path.c_str());
+  return ok ? GPH_OK : GPH_EARG;
+}
+
 static int run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
                             int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user, gph_comm *comm,
-                            const char *summary_path = nullptr, const char *cs_prefix = nullptr, int32_t cs_capacity = 0)
+                            const char *summary_path = nullptr, const char *cs_prefix = nullptr, int32_t cs_capacity = 0,
+                            int32_t ts_slices = 0)
 {
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce && !comm)) return GPH_EARG;
+  if (ts_slices < 0 || (ts_slices > 0 && !cs_prefix)) { fprintf(stderr, "gphocs_hip: time slices need a coal-stats prefix\n"); return GPH_EARG; }
   const bool lead = rank == 0;   /* rank 0 talks and writes the trace file; every rank runs the same chain */
   gph_control *C = nullptr;
   gph_loci *LC = nullptr;
@@ -254,12 +377,14 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_control_info info;
   char err[512] = "";
   int rc;
-  FILE *trace = nullptr, *cs_part = nullptr;
+  FILE *trace = nullptr, *cs_part = nullptr, *ts_part = nullptr;
   auto fail = [&](int code, const char *what) {
     fprintf(stderr, "gphocs_hip: %s failed (status %d)%s%s\n", what, code, err[0] ? ": " : "", err);
     if (trace) fclose(trace);
     if (cs_part) fclose(cs_part);
+    if (ts_part) fclose(ts_part);
     if (cs_prefix && world == 1) gph_coal_stats_discard(cs_prefix, 1);   /* (several ranks: the caller removes every rank's part) */
+    if (ts_slices && world == 1) gph_time_slices_discard(cs_prefix, 1);
     if (M) gph_mcmc_destroy(M);
     if (E) gph_engine_destroy(E);
     if (LC) gph_loci_free(LC);
@@ -366,6 +491,34 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     fwrite(CS_MAGIC, 1, 8, cs_part); fwrite(hdr, 4, 3, cs_part); fwrite(&Ltot, 8, 1, cs_part); fwrite(&nbytes, 4, 1, cs_part);
     fwrite(names.data(), 1, names.size(), cs_part);
   }
+  /* time-sliced statistics: a device buffer of as many rows, this rank's part file and its header */
+  int32_t ts_rd = 0;
+  int64_t ts_written = 0;
+  std::vector<double> ts_rows;
+  if (ts_slices) {
+    if ((rc = gph_engine_time_slices_enable(E, ts_slices, cs_capacity))) return fail(rc, "gph_engine_time_slices_enable");
+    gph_engine_time_slices_shape(E, &ts_rd, nullptr, nullptr, nullptr, nullptr, nullptr);
+    ts_rows.resize((size_t)ts_rd * cs_capacity);
+    ts_part = fopen(ts_part_path(cs_prefix, rank).c_str(), "wb");
+    if (!ts_part) { snprintf(err, sizeof err, "Could not open %s", ts_part_path(cs_prefix, rank).c_str()); return fail(GPH_EARG, "opening the time-slices part file"); }
+    std::string names;
+    for (int p = 0; p < cfg.K; p++) { names += gph_control_pop_name(C, p); names.push_back('\0'); }
+    for (int b = 0; b < cfg.B; b++) {
+      names += std::string(gph_control_pop_name(C, cfg.bandSrc[b])) + "->" + gph_control_pop_name(C, cfg.bandTgt[b]);
+      names.push_back('\0');
+    }
+    const int32_t hdr[4] = {ts_slices, cfg.K, cfg.B, ts_rd}, nbytes = (int32_t)names.size();
+    fwrite(TS_MAGIC, 1, 8, ts_part); fwrite(hdr, 4, 4, ts_part); fwrite(&nbytes, 4, 1, ts_part);
+    fwrite(names.data(), 1, names.size(), ts_part);
+  }
+  auto ts_flush = [&]() -> int {
+    int32_t got = 0;
+    int rcf = gph_engine_time_slices_fetch(E, ts_rows.data(), cs_capacity, &got);
+    if (rcf) return rcf;
+    if (got > 0 && fwrite(ts_rows.data(), sizeof(double), (size_t)ts_rd * got, ts_part) != (size_t)ts_rd * got) return GPH_EARG;
+    ts_written += got;
+    return fflush(ts_part) == 0 ? GPH_OK : GPH_EARG;
+  };
   /* the filled rows of the device buffer, each with its logPrior, to the part file */
   auto cs_flush = [&]() -> int {
     int32_t got = 0;
@@ -457,6 +610,7 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
       if (summary_path && (rc = gph_engine_locus_summary_sample(E))) return fail(rc, "gph_engine_locus_summary_sample");
       if (cs_prefix) {
         if ((rc = gph_engine_coal_stats_sample(E, it))) return fail(rc, "gph_engine_coal_stats_sample");
+        if (ts_slices && (rc = gph_engine_time_slices_sample(E, it))) return fail(rc, "gph_engine_time_slices_sample");
         /* logPrior of the parameters this trace line shows: what getLogPrior sums (GPhoCS.c:858-898) -- theta of every population,
          * tau of every ancestral one, the rate of every band, each under its gamma prior of the control file */
         gph_mcmc_get_state(M, nullptr, nullptr, cs_theta.data(), cs_age.data(), cs_mig.data());
@@ -469,7 +623,11 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
         for (int p = cfg.Kc; p < cfg.K; p++) lp += gamma_lpdf(mc.ageAlpha[p], mc.ageBeta[p], cs_age[p]);
         for (int b = 0; b < cfg.B; b++) lp += gamma_lpdf(mc.mrAlpha[b], mc.mrBeta[b], cs_mig[b]);
         cs_prior.push_back(lp);
-        if ((int32_t)cs_prior.size() == cs_capacity && (rc = cs_flush())) return fail(rc, "writing the coal-stats part file");
+        if ((int32_t)cs_prior.size() == cs_capacity) {
+          /* (both buffers have cs_capacity rows and fill together) */
+          if ((rc = cs_flush())) return fail(rc, "writing the coal-stats part file");
+          if (ts_slices && (rc = ts_flush())) return fail(rc, "writing the time-slices part file");
+        }
       }
     }
     logCount++;
@@ -544,6 +702,13 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     cs_part = nullptr;
     if (rcc != 0) return fail(GPH_EARG, "closing the coal-stats part file");
   }
+  if (ts_slices) {
+    if ((rc = ts_flush())) return fail(rc, "writing the time-slices part file");
+    if (fwrite(&ts_written, sizeof ts_written, 1, ts_part) != 1) return fail(GPH_EARG, "writing the time-slices part file");
+    const int rcc = fclose(ts_part);
+    ts_part = nullptr;
+    if (rcc != 0) return fail(GPH_EARG, "closing the time-slices part file");
+  }
   int32_t ls_ncol = 0;
   int64_t ls_samples = 0;
   std::vector<double> ls_raw;
@@ -559,10 +724,11 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_engine_destroy(E);
   if (oob_checked && oob_where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
     gph_loci_free(LC);
     gph_control_free(C);
     if (cs_prefix && world == 1) gph_coal_stats_discard(cs_prefix, 1);
+    if (ts_slices && world == 1) gph_time_slices_discard(cs_prefix, 1);
     return GPH_EKERNEL;
   }
   rc = GPH_OK;
@@ -574,9 +740,15 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_loci_free(LC);
   gph_control_free(C);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
+  /* (the slices file first: should the coal-stats files fail after it, one file is removed again, not 1 + 3 K) */
+  if (ts_slices && world == 1) {
+    if (rc) gph_time_slices_discard(cs_prefix, 1);
+    else rc = gph_time_slices_write(cs_prefix, 1);
+  }
   if (cs_prefix && world == 1) {
     if (rc) gph_coal_stats_discard(cs_prefix, 1);
     else rc = gph_coal_stats_write(cs_prefix, 1);
+    if (rc && ts_slices) gph_time_slices_discard(cs_prefix, 1);
   }
   return rc;
 }
@@ -601,9 +773,17 @@ extern "C" int gph_run_control_file_ex(const char *ctl, const char *ctl2, int32_
 extern "C" int gph_run_control_file_ex2(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
                                         const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity)
 {
+  return gph_run_control_file_ex3(ctl, ctl2, device, verbose, comm, locus_summary_path, coal_stats_prefix, coal_stats_capacity, 0);
+}
+
+extern "C" int gph_run_control_file_ex3(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
+                                        const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity,
+                                        int32_t time_slices)
+{
   if (comm) return run_control_file(ctl, ctl2, device, verbose, gph_comm_rank(comm), gph_comm_world(comm), nullptr, nullptr, comm, locus_summary_path,
-                                    coal_stats_prefix, coal_stats_capacity);
-  return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr, locus_summary_path, coal_stats_prefix, coal_stats_capacity);
+                                    coal_stats_prefix, coal_stats_capacity, time_slices);
+  return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr, locus_summary_path, coal_stats_prefix, coal_stats_capacity,
+                          time_slices);
 }
 
 extern "C" int gph_run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose)

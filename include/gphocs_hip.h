@@ -46,7 +46,7 @@ extern "C" {
 #define GPH_EHIP (-2)      /* HIP runtime failure (no device, OOM, launch error) */
 #define GPH_EKERNEL (-3)   /* a locus reported a fatal consistency error (reference: "Fatal Error NNNN") */
 #define GPH_ESTATE (-4)    /* call out of order */
-#define GPH_EFULL (-5)     /* gph_engine_coal_stats_sample: every row of the device buffer is taken; fetch first */
+#define GPH_EFULL (-5)     /* gph_engine_coal_stats_sample / _time_slices_sample: every row of the device buffer is taken; fetch first */
 
 typedef struct gph_engine gph_engine;
 typedef struct gph_mcmc gph_mcmc;
@@ -222,7 +222,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * engine's own stream: which = 0 sweep, 1 tau_eval, 2 mix_eval, 3 init, 4 check,
  * 5 tau_finish (commit or revert, by the decision flag), 7 mix_finish, 8 sync, 9 locus-rate scan, 10 locus-rate apply,
  * 11 locus-rate prepare, 13 locus summary (gph_engine_locus_summary_sample), 14 coalescent / sample-pair statistics
- * (gph_engine_coal_stats_sample: k_coal_stats + k_coal_fold together) */
+ * (gph_engine_coal_stats_sample: k_coal_stats + k_coal_fold together), 15 time-sliced statistics
+ * (gph_engine_time_slices_sample: k_time_slices + k_time_slices_fold together) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -305,6 +306,41 @@ const char *gph_engine_coal_stats_column_name(gph_engine *e, int32_t col);
  * of the fp64 sums (csrc/gph_coalstats.h): rows are bitwise reproducible for a given locus count, chunk size and rank
  * count */
 int gph_engine_coal_stats_set_chunk(gph_engine *e, int32_t slots);
+/* coalescence and migration statistics per TIME SLICE of one MCMC sample, genome-wide, computed on the device
+ * (k_time_slices, k_time_slices_fold: csrc/gph_timeslices.h, where the statistic is defined line by line).  Every
+ * population's branch and every migration band's life is cut into `slices` equal time slices; per slice: the number of
+ * coalescences C and the coalescent exposure D = sum of n(n-1) t (the sufficient statistics of theta within the slice),
+ * the number of migrations N into the band's target through the band and the migration exposure M = sum of n t.  The
+ * population half restates recalcStats_partitioned / computeGenetreeStats_partitioned (patch.c:2357-2694; the columns
+ * numCoal_<pop>:<k> / deltaT_<pop>:<k> of printCoalStats, GPhoCS.c:927-935, 1000-1009), which the reference never reaches;
+ * the migration half is commented out upstream and defined here.  The root population has one slice (its other columns
+ * stay 0, as upstream prints them).  Unlike upstream the last slice takes whatever lies past the last boundary (upstream
+ * drops up to 1e-7 and aborts with Fatal Error 9001 beyond): the slices of a branch add up to the pages' own statistic.
+ * A raw row of row_doubles = 1 + 2 * slices * (K + B) doubles, over THIS rank's loci:
+ *   [0] iteration, then for every population in model order and every slice C, D, then for every band in control-file
+ *   order and every slice N, M.  Counts are doubles holding integers.  Several ranks: the rows are added in rank order.
+ *   _enable(slices, capacity)  a device buffer of `capacity` rows (capacity 0: frees everything, the feature is off);
+ *                      slices outside 1 .. 32 is GPH_EARG (with a message); gph_engine_init_genealogies empties the buffer
+ *   _sample(iteration) queues one sample on the engine's stream (two kernels, no host synchronisation, no exchange) into
+ *                      the next free row; a commit still owed to the next kernel runs first (k_mix_finish after an
+ *                      accepted mixing proposal; k_tau_finish between the parts of a stepwise caller); a deferred synchronizeEvents
+ *                      pass stays deferred (the kernel reads the event times as that pass will leave them).  GPH_EFULL
+ *                      when no row is free: nothing is overwritten
+ *   _shape             doubles per row, rows filled since the last fetch, slices, populations, bands, and the bytes of a
+ *                      page the kernel copies into LDS per locus and sample (any pointer may be NULL)
+ *   _fetch             copies the filled rows to out[max_rows >= filled][row_doubles], *rows = their number, and empties
+ *                      the buffer
+ *   _column_name       machine name of raw column col: "iter", "numCoal.<pop>.<k>", "deltaT.<pop>.<k>", "numMig.<band>.<k>",
+ *                      "migT.<band>.<k>", k = 1 .. slices; NULL if out of range; valid until the next call on this engine
+ *   _set_chunk         tests: slots per chunk used by the next _enable (0 = the default, 128); the chunk size is part of
+ *                      the summation order: rows are bitwise reproducible for a given locus count, chunk size and rank count */
+int gph_engine_time_slices_enable(gph_engine *e, int32_t slices, int32_t capacity);
+int gph_engine_time_slices_sample(gph_engine *e, int32_t iteration);
+int gph_engine_time_slices_shape(gph_engine *e, int32_t *row_doubles, int32_t *filled, int32_t *slices, int32_t *K, int32_t *B,
+                                 int32_t *staged_bytes_per_locus);
+int gph_engine_time_slices_fetch(gph_engine *e, double *out, int32_t max_rows, int32_t *rows);
+const char *gph_engine_time_slices_column_name(gph_engine *e, int32_t col);
+int gph_engine_time_slices_set_chunk(gph_engine *e, int32_t slots);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -466,6 +502,20 @@ int gph_coal_stats_write(const char *prefix, int32_t ranks);
  * A part that is missing, damaged or was not closed by its rank (no record count at its end) is an error. */
 int gph_coal_stats_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles);
 int gph_coal_stats_discard(const char *prefix, int32_t ranks);
+/* the same, plus the time-sliced statistics (`G-PhoCS-hip -s PREFIX --time-slices S`): with time_slices >= 1 (which needs
+ * a coal_stats_prefix: GPH_EARG without one) a sample of gph_engine_time_slices_* is taken wherever a coal-stats sample is,
+ * into a device buffer of as many rows, and rank r appends its raw rows to the binary file PREFIX.slices.part<r>.
+ * gph_time_slices_write(prefix, ranks) adds the parts in rank order, sample by sample, writes PREFIX.slices.tsv -- header
+ * iter, numCoal_<pop>:<k> deltaT_<pop>:<k> (k = 1 .. S, GPhoCS.c:933), numMig_<src>-><tgt>:<k> migT_<src>-><tgt>:<k>; rows
+ * "%7d" then "\t%9d\t%8f" per pair (GPhoCS.c:1005) -- and removes the parts; _discard only removes them; _combined hands
+ * out the added rows (out NULL: the two counts only).  A one-rank run writes or discards itself, as for the coal-stats
+ * files; with several ranks the caller does.  time_slices 0 = gph_run_control_file_ex2. */
+int gph_run_control_file_ex3(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
+                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null,
+                             const char *coal_stats_prefix_or_null, int32_t coal_stats_capacity, int32_t time_slices);
+int gph_time_slices_write(const char *prefix, int32_t ranks);
+int gph_time_slices_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles);
+int gph_time_slices_discard(const char *prefix, int32_t ranks);
 
 /* ------------------------------------------------------------------------------------
  * post-run summary of a trace file (host only): block means per column, the output of the reference's
