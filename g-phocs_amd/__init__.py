@@ -292,6 +292,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_time_slices_enable", "gph_engine_time_slices_sample", "gph_engine_time_slices_shape", "gph_engine_time_slices_fetch",
     "gph_engine_time_slices_column_name", "gph_engine_time_slices_set_chunk", "gph_run_control_file_ex3", "gph_time_slices_write",
     "gph_time_slices_combined", "gph_time_slices_discard",
+    "gph_engine_ancestry_enable", "gph_engine_ancestry_sample", "gph_engine_ancestry_shape", "gph_engine_ancestry_fetch_loci",
+    "gph_engine_ancestry_fetch_rows", "gph_engine_ancestry_column_name", "gph_run_control_file_ex4", "gph_ancestry_write",
+    "gph_ancestry_discard",
 ]
 
 
@@ -419,6 +422,17 @@ def _load_library(path):
     lib.gph_time_slices_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_time_slices_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_time_slices_combined.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gph_engine_ancestry_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
+    lib.gph_engine_ancestry_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_ancestry_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gph_engine_ancestry_fetch_loci.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int32]
+    lib.gph_engine_ancestry_fetch_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_ancestry_column_name.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.gph_engine_ancestry_column_name.restype = C.c_char_p
+    lib.gph_run_control_file_ex4.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32,
+                                             C.c_char_p, C.c_int32]
+    lib.gph_ancestry_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_ancestry_discard.argtypes = [C.c_char_p, C.c_int32]
     return lib
 
 
@@ -694,6 +708,22 @@ def time_slices_combined(lib, prefix, ranks):
     return out
 
 
+def ancestry_table(raw, S, n, B):
+    """the derived columns of PREFIX.loci.tsv from the raw per-locus accumulators (a dict keyed cnt.<b>.<i>, age.<b>.<i>,
+    any.<i>, one array entry per locus) after S samples: pAny (L, n) = any / S, p (L, B, n) = cnt / S, age (L, B, n) =
+    age_sum / cnt where cnt > 0 else 0 (the genealogy's own units), and keep (L, n) = any > 0, the rows the file prints"""
+    L = len(raw["any.0"])
+    anyc = np.stack([raw[f"any.{i}"] for i in range(n)], axis=1)
+    cnt = np.zeros((L, B, n))
+    agesum = np.zeros((L, B, n))
+    for b in range(B):
+        for i in range(n):
+            cnt[:, b, i] = raw[f"cnt.{b}.{i}"]
+            agesum[:, b, i] = raw[f"age.{b}.{i}"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(samples=S, pAny=anyc / S, p=cnt / S, age=np.where(cnt > 0, agesum / cnt, 0.0), keep=anyc > 0)
+
+
 def _dp(a):
     return np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
 
@@ -945,6 +975,53 @@ class Sampler:
     def time_slices_columns(self):
         rd = self._time_slices_shape()[0]
         return [self.lib.gph_engine_time_slices_column_name(self.engine, c).decode() for c in range(rd)]
+
+    # ---- per-locus, per-sample migration ancestry (gph_engine_ancestry_*): accumulated on the device, one sample per call
+    def enable_ancestry(self, capacity, max_bytes=0):
+        """per-locus accumulators and a device buffer of `capacity` per-sample rows; capacity 0 switches the feature off.
+        MemoryError when the accumulators would exceed max_bytes (0: 1 GiB); the sampler stays usable"""
+        rc = self.lib.gph_engine_ancestry_enable(self.engine, int(capacity), int(max_bytes))
+        if rc == COAL_STATS_FULL:
+            raise MemoryError("gphocs_hip: the ancestry accumulators exceed max_bytes (GPH_EFULL)")
+        self._chk(rc, "ancestry_enable")
+
+    def sample_ancestry(self, it):
+        """one sample of the current state, labelled iteration `it`; BufferError when the row buffer is full"""
+        rc = self.lib.gph_engine_ancestry_sample(self.engine, int(it))
+        if rc == COAL_STATS_FULL:
+            raise BufferError("gphocs_hip: the ancestry row buffer is full; fetch with ancestry_rows() first")
+        self._chk(rc, "ancestry_sample")
+
+    def _ancestry_shape(self):
+        nc, ri, ns, held = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+        self._chk(self.lib.gph_engine_ancestry_shape(self.engine, C.byref(nc), C.byref(ri), C.byref(ns), C.byref(held)), "ancestry_shape")
+        return nc.value, ri.value, ns.value, held.value
+
+    def ancestry_loci(self, raw=False, reset=False):
+        """one entry per local locus in global locus order.  raw=True: a dict of the accumulators as the engine keeps them,
+        keyed by their machine names (cnt.<b>.<i>, age.<b>.<i>, any.<i>) + "samples".  raw=False: ancestry_table of them"""
+        nc, _, S, _ = self._ancestry_shape()
+        nloc = self.end - self.begin
+        out = np.zeros((nloc, max(nc, 1)))
+        self._chk(self.lib.gph_engine_ancestry_fetch_loci(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[1],
+                                                          int(bool(reset))), "ancestry_fetch_loci")
+        cols = {self.lib.gph_engine_ancestry_column_name(self.engine, 0, c).decode(): out[:, c].copy() for c in range(nc)}
+        if raw:
+            cols["samples"] = np.full(nloc, S, dtype=np.int64)
+            return cols
+        return ancestry_table(cols, S, self.pack.n, self.pack.B)
+
+    def ancestry_rows(self):
+        """(iterations, rows): the per-sample rows taken since the last call, an int32 (samples, n (B + 1)) array over THIS
+        rank's loci -- any.<i>, then hit.<b>.<i> -- and their iterations; the device buffer is emptied"""
+        _, ri, _, held = self._ancestry_shape()
+        its = np.zeros(max(held, 1), dtype=np.int32)
+        out = np.zeros((max(held, 1), max(ri, 1)), dtype=np.int32)
+        got = C.c_int32()
+        self._chk(self.lib.gph_engine_ancestry_fetch_rows(self.engine, its.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          out.ctypes.data_as(C.POINTER(C.c_int32)), out.shape[1], out.shape[0], C.byref(got)),
+                  "ancestry_fetch_rows")
+        return its[:got.value], out[:got.value, :ri]
 
     def hbm_bytes(self):
         b = C.c_double()

@@ -24,6 +24,7 @@
 #include "gph_summary.h"
 #include "gph_coalstats.h"
 #include "gph_timeslices.h"
+#include "gph_ancestry.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
 
@@ -363,6 +364,7 @@ __global__ void k_debug_math(GphKargs KA, const double *x, const double *y, int 
 #endif
 
 // ---------------------------------------------------------------- engine object
+#define GPH_NCLS 17     // kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 struct gph_engine {
   gph_config cfg;
   std::vector<int32_t> samplesPerPop, popFather, popSon0, popSon1, bandSrc, bandTgt;
@@ -448,9 +450,18 @@ struct gph_engine {
   int32_t ts_chunk_next = 0;   // slots per chunk of the next _enable (gph_engine_time_slices_set_chunk; 0: GPH_TS_CHUNK)
   GphTsShape ts_shape = {};
   std::string ts_name;
-  double last_ms[16] = {0};
+  // per-locus, per-sample migration ancestry (gph_ancestry.h): fp64 accumulators [L][an_ncol] in slot order, the integer rows
+  // of the samples taken since the last fetch ([an_cap][an_ri]) and their iterations; all null / 0 while the feature is off
+  double *d_an_acc = nullptr;
+  uint32_t *d_an_rows = nullptr;
+  int32_t an_cap = 0, an_fill = 0, an_ncol = 0, an_ri = 0;
+  int64_t an_samples = 0;
+  GphAnShape an_shape = {};
+  std::vector<int32_t> an_iters;
+  std::string an_name;
+  double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
-  double cls_launches[16] = {0}, cls_ms[16] = {0};
+  double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
   double cls_evals0[16] = {0}, cls_bytes0[16] = {0}, cls_nodes0[16] = {0};   // offsets of the last reset
   int last_which = 0;
   uint32_t timing_mask = 0xffffffffu;   // classes whose launches are bracketed by HIP events
@@ -1010,6 +1021,18 @@ static int run_stage_now(gph_engine *e, int stage, int arg)
 }
 
 // the per-locus summary accumulators back to zero samples (queued on the engine's stream; nothing if summaries are off)
+static int an_zero(gph_engine *e)
+{
+  e->an_samples = 0;
+  if (!e->d_an_acc) return 0;
+  const size_t bytes = sizeof(double) * (size_t)e->an_ncol * e->L;
+#ifdef GPH_HOSTEMU
+  memset(e->d_an_acc, 0, bytes);
+#else
+  HIPCHK(hipMemsetAsync(e->d_an_acc, 0, bytes, e->stream));
+#endif
+  return 0;
+}
 static int ls_zero(gph_engine *e)
 {
   e->ls_samples = 0;
@@ -1103,6 +1126,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->d_lrec); dev_free(e->d_lpre); dev_free(e->d_slot_of); dev_free(e->d_lr_result); dev_free(e->d_lr_gscr); dev_free(e->d_ref_page); dev_free(e->d_ref_seq);
   dev_free(e->d_part); dev_free(e->dev.err); dev_free(e->d_ls); dev_free(e->d_cs_part); dev_free(e->d_cs_rows);
   dev_free(e->d_ts_part); dev_free(e->d_ts_rows);
+  dev_free(e->d_an_acc); dev_free(e->d_an_rows);
   for (void *p : e->deferred_free) dev_free(p);
   e->deferred_free.clear();
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
@@ -1431,6 +1455,9 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   { int rcz = ls_zero(e); if (rcz) return rcz; }
   e->cs_fill = 0;
   e->ts_fill = 0;
+  e->an_fill = 0;
+  e->an_iters.clear();
+  { int rcz = an_zero(e); if (rcz) return rcz; }
   LAUNCH(e, 3, k_init, e->seedz, (const double *)e->d_mutRate, e->init_predraws);
   int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -1701,7 +1728,7 @@ int gph_engine_get_counters(gph_engine *e, gph_counters *out, int32_t reset)
 
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms)
 {
-  if (!e || !ms || which < 0 || which >= 16) return GPH_EARG;
+  if (!e || !ms || which < 0 || which >= GPH_NCLS) return GPH_EARG;
   *ms = e->last_ms[which];
   return 0;
 }
@@ -1710,8 +1737,13 @@ int64_t gph_engine_num_loci(gph_engine *e) { return e ? e->L : 0; }
 
 int gph_engine_class_stats(gph_engine *e, int32_t which, double *out5, int32_t reset)
 {
-  if (!e || !out5 || which < 0 || which >= 16) return GPH_EARG;
+  if (!e || !out5 || which < 0 || which >= GPH_NCLS) return GPH_EARG;
   const GphGlobal &G = *e->G_h;
+  if (which >= 16) {   /* (classes the chain state keeps no evaluation counters for) */
+    out5[0] = e->cls_launches[which]; out5[1] = e->cls_ms[which]; out5[2] = out5[3] = out5[4] = 0.0;
+    if (reset) e->cls_launches[which] = e->cls_ms[which] = 0;
+    return 0;
+  }
   out5[0] = e->cls_launches[which]; out5[1] = e->cls_ms[which]; out5[2] = G.cls_evals[which] - e->cls_evals0[which];
   out5[3] = G.cls_bytes[which] - e->cls_bytes0[which]; out5[4] = G.cls_nodes[which] - e->cls_nodes0[which];
   if (reset) {
@@ -2751,6 +2783,144 @@ const char *gph_engine_time_slices_column_name(gph_engine *e, int32_t col)
   const char *what = W < K ? (second ? "deltaT." : "numCoal.") : (second ? "migT." : "numMig.");
   e->ts_name = std::string(what) + std::to_string(W < K ? W : W - K) + "." + std::to_string(k);
   return e->ts_name.c_str();
+}
+
+// ---- per-locus, per-sample migration ancestry (gph_ancestry.h)
+int gph_engine_ancestry_enable(gph_engine *e, int32_t capacity_rows, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity_rows < 0) return GPH_EARG;
+  SETDEV(e);
+  if (e->d_an_acc) { eng_free(e, e->d_an_acc); e->d_an_acc = nullptr; }
+  if (e->d_an_rows) { eng_free(e, e->d_an_rows); e->d_an_rows = nullptr; }
+  e->an_cap = e->an_fill = e->an_ncol = e->an_ri = 0;
+  e->an_samples = 0;
+  e->an_iters.clear();
+  e->an_shape = GphAnShape{};
+  if (capacity_rows == 0) return 0;
+  const int n = e->cfg.n, B = e->cfg.B;
+  const int ncol = gph_an_locus_columns(n, B), ri = gph_an_row_ints(n, B);
+  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
+  const int64_t need = (int64_t)e->L * ncol * 8;
+  if (need > limit) {
+    fprintf(stderr, "gphocs_hip: ancestry: the per-locus accumulators need %lld bytes (%lld loci x %d leaves x %d columns x 8), the limit is %lld\n",
+            (long long)need, (long long)e->L, n, 2 * B + 1, (long long)limit);
+    return GPH_EFULL;
+  }
+  if (dev_alloc((void **)&e->d_an_acc, (size_t)need)) { e->d_an_acc = nullptr; return GPH_EHIP; }
+  if (dev_alloc((void **)&e->d_an_rows, sizeof(uint32_t) * (size_t)ri * capacity_rows)) {
+    e->d_an_rows = nullptr;
+    dev_free(e->d_an_acc);
+    e->d_an_acc = nullptr;
+    return GPH_EHIP;
+  }
+  e->an_cap = capacity_rows; e->an_ncol = ncol; e->an_ri = ri;
+  gph_an_shape(e->lay, e->an_shape);
+  return an_zero(e);
+}
+
+// one sample of the current state, queued on the engine's stream; the pages are made current exactly as
+// gph_engine_locus_summary_sample makes them (a mixing commit still owed to the next sweep kernel runs first), and, because
+// the migration ages are read too, the commit / revert of a decided tau or sample-age proposal still owed to the next
+// evaluate kernel (never owed after a whole iteration, only between the parts of a stepwise caller).  A deferred
+// synchronizeEvents pass may stay deferred: it corrects event times only
+int gph_engine_ancestry_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->d_an_rows) return GPH_ESTATE;
+  if (e->an_fill >= e->an_cap) return GPH_EFULL;
+  SETDEV(e);
+  { int rcw = finish_owed(e); if (rcw) return rcw; }
+  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
+  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
+  const int L = (int)e->L;
+  const GphAnShape &h = e->an_shape;
+  const int groups = (L + h.G - 1) / h.G;
+  uint32_t *row = e->d_an_rows + (size_t)e->an_fill * e->an_ri;
+#ifdef GPH_HOSTEMU
+  memset(row, 0, sizeof(uint32_t) * (size_t)e->an_ri);
+  std::vector<char> lds;
+  for (int w = 0; w < groups; w++) ancestry_workgroup(e->lay, h, (const char *)e->dev.pages, e->d_an_acc, row, L, w, lds);
+  e->cls_launches[16] += 1;
+#else
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  const int tms = tm_begin(e, 16);
+  HIPCHK(hipMemsetAsync(row, 0, sizeof(uint32_t) * (size_t)e->an_ri, e->stream));
+  hipLaunchKernelGGL(k_ancestry, dim3((unsigned)groups), dim3((unsigned)h.bd), (size_t)h.lds_bytes, e->stream,
+                     e->lay, h, (const char *)e->dev.pages, e->d_an_acc, row, L);
+  HIPCHK(hipGetLastError());
+  tm_end(e, tms);
+  e->n_launches++;
+  e->last_which = 16;
+  e->cls_launches[16] += 1;
+#endif
+  e->an_iters.push_back(iteration);
+  e->an_fill++;
+  e->an_samples++;
+  return 0;
+}
+
+int gph_engine_ancestry_shape(gph_engine *e, int32_t *locus_columns, int32_t *row_ints, int64_t *samples, int32_t *rows_held)
+{
+  if (!e) return GPH_EARG;
+  if (locus_columns) *locus_columns = e->an_ncol;
+  if (row_ints) *row_ints = e->an_ri;
+  if (samples) *samples = e->an_samples;
+  if (rows_held) *rows_held = e->an_fill;
+  return 0;
+}
+
+int gph_engine_ancestry_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset)
+{
+  if (!e || !out) return GPH_EARG;
+  if (!e->d_an_acc) return GPH_ESTATE;
+  if (ld < e->an_ncol) return GPH_EARG;
+  SETDEV(e);
+  const int64_t L = e->L;
+  const int ncol = e->an_ncol;
+  std::vector<double> acc((size_t)ncol * L);
+  int rc = d2h(e, acc.data(), e->d_an_acc, sizeof(double) * acc.size());
+  if (rc) return rc;
+  /* slot j holds local locus h_orig[j] */
+  for (int64_t j = 0; j < L; j++) memcpy(out + (size_t)e->h_orig[j] * ld, acc.data() + (size_t)j * ncol, sizeof(double) * ncol);
+  return reset ? an_zero(e) : 0;
+}
+
+int gph_engine_ancestry_fetch_rows(gph_engine *e, int32_t *iters, int32_t *out, int64_t ld, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || ((!out || !iters) && max_rows > 0)) return GPH_EARG;
+  if (!e->d_an_rows) return GPH_ESTATE;
+  if (max_rows < e->an_fill || (e->an_fill > 0 && ld < e->an_ri)) return GPH_EARG;
+  SETDEV(e);
+  *rows = e->an_fill;
+  if (e->an_fill > 0) {
+    std::vector<uint32_t> tmp((size_t)e->an_ri * e->an_fill);
+    int rc = d2h(e, tmp.data(), e->d_an_rows, sizeof(uint32_t) * tmp.size());
+    if (rc) return rc;
+    for (int32_t r = 0; r < e->an_fill; r++) {
+      iters[r] = e->an_iters[(size_t)r];
+      memcpy(out + (size_t)r * ld, tmp.data() + (size_t)r * e->an_ri, sizeof(uint32_t) * (size_t)e->an_ri);
+    }
+  }
+  e->an_fill = 0;
+  e->an_iters.clear();
+  return 0;
+}
+
+const char *gph_engine_ancestry_column_name(gph_engine *e, int32_t which, int32_t col)
+{
+  if (!e || col < 0 || e->an_cap == 0) return nullptr;
+  const int n = e->cfg.n, B = e->cfg.B;
+  if (which == 0) {
+    if (col >= e->an_ncol) return nullptr;
+    const int blk = col / n, i = col % n;
+    e->an_name = blk >= 2 * B ? "any." + std::to_string(i)
+                              : std::string(blk < B ? "cnt." : "age.") + std::to_string(blk % (B > 0 ? B : 1)) + "." + std::to_string(i);
+  } else if (which == 1) {
+    if (col >= e->an_ri) return nullptr;
+    const int blk = col / n, i = col % n;
+    e->an_name = blk == 0 ? "any." + std::to_string(i) : "hit." + std::to_string(blk - 1) + "." + std::to_string(i);
+  } else return nullptr;
+  return e->an_name.c_str();
 }
 
 } // extern "C"

@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -24,6 +24,10 @@
 // --time-slices S (with -s PREFIX only): additionally PREFIX.slices.tsv, the coalescence / migration statistics of every
 // sample per time slice (gph_run_control_file_ex3); the ranks' PREFIX.slices.part<r> are handled like the coal-stats parts
 // (gph_time_slices_write / _discard).
+//
+// --ancestry PREFIX: PREFIX.loci.tsv and PREFIX.samples.tsv, which sample's lineage went through which migration band at
+// which locus (gph_run_control_file_ex4); the ranks' PREFIX.ancestry.part<r> become the two files once every child has
+// exited 0 (gph_ancestry_write), and are removed otherwise (gph_ancestry_discard).  Composes with every option above.
 #include "gphocs_hip.h"
 #include <dlfcn.h>
 #include <libgen.h>
@@ -96,14 +100,14 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
 int main(int argc, char **argv)
 {
   int verbose = 0, device = 0, gpus = 1, i = 1;
-  const char *summary = nullptr, *coal = nullptr;
+  const char *summary = nullptr, *coal = nullptr, *ancestry = nullptr;
   int coal_rows = 0, slices = 0;
   for (; i < argc && argv[i][0] == '-'; i++) {
     if (!strcmp(argv[i], "-v") || !strcmp(argv[i], "--verbose")) verbose = 1;
@@ -113,6 +117,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "-s") && i + 1 < argc) coal = argv[++i];
     else if (!strcmp(argv[i], "--coal-stats-rows") && i + 1 < argc) coal_rows = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--time-slices") && i + 1 < argc) { slices = atoi(argv[++i]); if (slices < 1) return usage(argv[0]); }
+    else if (!strcmp(argv[i], "--ancestry") && i + 1 < argc) ancestry = argv[++i];
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
@@ -126,6 +131,7 @@ int main(int argc, char **argv)
   const std::string dir = dirname(self);
   if (gpus == 1) {
     void *h = load_engine(dir, ctl, ctl2);
+    if (ancestry) return sym<decltype(&gph_run_control_file_ex4)>(h, "gph_run_control_file_ex4")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices, ancestry, 0) ? 1 : 0;
     if (slices) return sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices) ? 1 : 0;
     if (coal) return sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows) ? 1 : 0;
     if (summary) return sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, device, verbose, nullptr, summary) ? 1 : 0;
@@ -173,7 +179,8 @@ int main(int argc, char **argv)
         comm = create_rccl(mb->id, r, gpus, mydev);
       }
       if (!comm) { fprintf(stderr, "G-PhoCS-hip: rank %d could not join the communicator\n", r); _exit(2); }
-      int rc = slices ? sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices) :
+      int rc = ancestry ? sym<decltype(&gph_run_control_file_ex4)>(h, "gph_run_control_file_ex4")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices, ancestry, 0) :
+               slices ? sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices) :
                coal ? sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows) :
                summary ? sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, mydev, verbose, comm, summary)
                        : sym<decltype(&gph_run_control_file_comm)>(h, "gph_run_control_file_comm")(ctl, ctl2, mydev, verbose, comm);
@@ -226,6 +233,12 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(summary); bad = 1; }
     if (bad && out) unlink(summary);
   }
+  void *han = nullptr;
+  if (ancestry) {
+    /* the ranks' parts into the two files, by the library that wrote them; first, so that a later failure removes two files */
+    han = load_engine(dir, ctl, ctl2);
+    if (!bad && sym<decltype(&gph_ancestry_write)>(han, "gph_ancestry_write")(ancestry, gpus)) bad = 1;
+  }
   if (coal) {
     /* the ranks' raw rows, added in rank order by the library that wrote them (the launcher itself has not touched a GPU) */
     void *h = load_engine(dir, ctl, ctl2);
@@ -235,5 +248,6 @@ int main(int argc, char **argv)
     else if (sym<decltype(&gph_coal_stats_write)>(h, "gph_coal_stats_write")(coal, gpus)) bad = 1;
     if (slices && bad) sym<decltype(&gph_time_slices_discard)>(h, "gph_time_slices_discard")(coal, gpus);
   }
+  if (ancestry && bad) sym<decltype(&gph_ancestry_discard)>(han, "gph_ancestry_discard")(ancestry, gpus);
   return bad;
 }

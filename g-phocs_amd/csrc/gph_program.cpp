@@ -360,10 +360,135 @@ extern "C" int gph_time_slices_write(const char *prefix, int32_t ranks)
   return ok ? GPH_OK : GPH_EARG;
 }
 
+// ---- migration ancestry (`--ancestry PREFIX`): rank r keeps PREFIX.ancestry.part<r> -- a header (magic, n, B, integers per
+// row, the sample names as printed and the bands' "src->tgt" names), one record of 1 + row_ints 32-bit integers per sample
+// (the iteration, then the engine's row) and, written when the rank closes its part, its rows of the per-locus table as
+// text, the number of records and the number of text bytes: a part without that trailer, or whose size does not match it,
+// is refused
+namespace {
+const char AN_MAGIC[8] = {'G', 'P', 'H', 'A', 'N', '1', '\n', 0};
+std::string an_part_path(const char *prefix, int r) { return std::string(prefix) + ".ancestry.part" + std::to_string(r); }
+
+struct AnReader {
+  std::vector<FILE *> f;
+  std::vector<long> text_at;
+  std::vector<int64_t> text_bytes;
+  int32_t n = 0, B = 0, ri = 0;
+  int64_t samples = 0;
+  std::vector<std::string> names;     /* n sample names, then B band names */
+  std::vector<int32_t> tmp;
+  ~AnReader() { for (FILE *x : f) if (x) fclose(x); }
+  bool open(const char *prefix, int ranks)
+  {
+    for (int r = 0; r < ranks; r++) {
+      const std::string path = an_part_path(prefix, r);
+      FILE *x = fopen(path.c_str(), "rb");
+      f.push_back(x);
+      char magic[8];
+      int32_t hdr[3], nbytes = 0;
+      int64_t tail[2] = {-1, -1};
+      bool ok = x && fread(magic, 1, 8, x) == 8 && !memcmp(magic, AN_MAGIC, 8) && fread(hdr, 4, 3, x) == 3 && fread(&nbytes, 4, 1, x) == 1 &&
+                nbytes >= 0 && hdr[0] >= 1 && hdr[1] >= 0 && hdr[2] == hdr[0] * (hdr[1] + 1);
+      std::vector<std::string> nm;
+      if (ok) {
+        std::vector<char> buf((size_t)nbytes + 1, 0);
+        ok = fread(buf.data(), 1, (size_t)nbytes, x) == (size_t)nbytes;
+        for (size_t at = 0; ok && at < (size_t)nbytes; at += strlen(buf.data() + at) + 1) nm.push_back(buf.data() + at);
+        ok = ok && (int)nm.size() == hdr[0] + hdr[1];
+      }
+      long body = 0;
+      if (ok) {
+        /* header | count records | text | count, text bytes */
+        body = ftell(x);
+        ok = body > 0 && fseek(x, -16, SEEK_END) == 0;
+        const long end = ok ? ftell(x) : 0;
+        ok = ok && fread(tail, 8, 2, x) == 2 && tail[0] >= 0 && tail[1] >= 0 &&
+             end - body == (long)(tail[0] * (int64_t)(hdr[2] + 1) * 4 + tail[1]) && fseek(x, body, SEEK_SET) == 0;
+      }
+      if (!ok) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); return false; }
+      if (r == 0) { n = hdr[0]; B = hdr[1]; ri = hdr[2]; samples = tail[0]; names = nm; }
+      else if (hdr[0] != n || hdr[1] != B || tail[0] != samples) { fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", path.c_str()); return false; }
+      text_at.push_back(body + (long)(tail[0] * (int64_t)(hdr[2] + 1) * 4));
+      text_bytes.push_back(tail[1]);
+    }
+    tmp.resize((size_t)ri + 1);
+    return true;
+  }
+  /* the ranks' records of the next sample, added (the iteration is rank 0's) */
+  bool next(std::vector<int32_t> &rec)
+  {
+    rec.resize((size_t)ri + 1);
+    for (size_t r = 0; r < f.size(); r++) {
+      std::vector<int32_t> &into = r == 0 ? rec : tmp;
+      if (fread(into.data(), 4, into.size(), f[r]) != into.size()) return false;
+      if (r > 0) for (int c = 1; c <= ri; c++) rec[c] += tmp[c];
+    }
+    return true;
+  }
+};
+}   // namespace
+
+// the parts, and the two files should they exist already (the run failed after they were written: a failed run leaves none)
+extern "C" int gph_ancestry_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  for (int r = 0; r < ranks; r++) remove(an_part_path(prefix, r).c_str());
+  unlink((std::string(prefix) + ".loci.tsv").c_str());      /* (files only: whatever else sits under these names is not ours) */
+  unlink((std::string(prefix) + ".samples.tsv").c_str());
+  return GPH_OK;
+}
+
+extern "C" int gph_ancestry_write(const char *prefix, int32_t ranks)
+{
+  if (!prefix || ranks < 1) return GPH_EARG;
+  const std::string paths[2] = {std::string(prefix) + ".loci.tsv", std::string(prefix) + ".samples.tsv"};
+  FILE *out[2] = {nullptr, nullptr};
+  bool ok;
+  {
+    AnReader R;
+    ok = R.open(prefix, ranks);
+    for (int k = 0; k < 2 && ok; k++)
+      if (!(out[k] = fopen(paths[k].c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s\n", paths[k].c_str()); ok = false; }
+    if (ok) {
+      const int n = R.n, B = R.B;
+      fprintf(out[1], "iter");
+      for (int i = 0; i < n; i++) fprintf(out[1], "\tany_%s#%d", R.names[i].c_str(), i);
+      for (int b = 0; b < B; b++)
+        for (int i = 0; i < n; i++) fprintf(out[1], "\t%s|%s#%d", R.names[n + b].c_str(), R.names[i].c_str(), i);
+      fprintf(out[1], "\n");
+      std::vector<int32_t> rec;
+      for (int64_t s = 0; s < R.samples && ok; s++) {
+        if (!R.next(rec)) { fprintf(stderr, "gphocs_hip: a part of %s ended early\n", paths[1].c_str()); ok = false; break; }
+        fprintf(out[1], "%7d", (int)rec[0]);
+        for (int c = 1; c <= R.ri; c++) fprintf(out[1], "\t%9d", (int)rec[c]);
+        fprintf(out[1], "\n");
+      }
+      fprintf(out[0], "locus\tname\tleaf\tsample\tsamples\tpAny");
+      for (int b = 0; b < B; b++) fprintf(out[0], "\tp_%s\tage_%s", R.names[n + b].c_str(), R.names[n + b].c_str());
+      fprintf(out[0], "\n");
+      std::vector<char> buf(1 << 16);
+      for (size_t r = 0; r < R.f.size() && ok; r++) {
+        ok = fseek(R.f[r], R.text_at[r], SEEK_SET) == 0;
+        for (int64_t left = R.text_bytes[r]; left > 0 && ok;) {
+          const size_t want = left < (int64_t)buf.size() ? (size_t)left : buf.size();
+          ok = fread(buf.data(), 1, want, R.f[r]) == want && fwrite(buf.data(), 1, want, out[0]) == want;
+          left -= (int64_t)want;
+        }
+        if (!ok) fprintf(stderr, "gphocs_hip: copying the rows of %s failed\n", an_part_path(prefix, (int)r).c_str());
+      }
+    }
+    for (int k = 0; k < 2; k++)
+      if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s failed\n", paths[k].c_str()); ok = false; }
+  }
+  for (int r = 0; r < ranks; r++) remove(an_part_path(prefix, r).c_str());
+  if (!ok) for (int k = 0; k < 2; k++) if (out[k]) remove(paths[k].c_str());
+  return ok ? GPH_OK : GPH_EARG;
+}
+
 static int run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
                             int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user, gph_comm *comm,
                             const char *summary_path = nullptr, const char *cs_prefix = nullptr, int32_t cs_capacity = 0,
-                            int32_t ts_slices = 0)
+                            int32_t ts_slices = 0, const char *an_prefix = nullptr, int32_t an_capacity = 0)
 {
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce && !comm)) return GPH_EARG;
   if (ts_slices < 0 || (ts_slices > 0 && !cs_prefix)) { fprintf(stderr, "gphocs_hip: time slices need a coal-stats prefix\n"); return GPH_EARG; }
@@ -377,12 +502,14 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_control_info info;
   char err[512] = "";
   int rc;
-  FILE *trace = nullptr, *cs_part = nullptr, *ts_part = nullptr;
+  FILE *trace = nullptr, *cs_part = nullptr, *ts_part = nullptr, *an_part = nullptr;
   auto fail = [&](int code, const char *what) {
     fprintf(stderr, "gphocs_hip: %s failed (status %d)%s%s\n", what, code, err[0] ? ": " : "", err);
     if (trace) fclose(trace);
     if (cs_part) fclose(cs_part);
     if (ts_part) fclose(ts_part);
+    if (an_part) fclose(an_part);
+    if (an_prefix && world == 1) gph_ancestry_discard(an_prefix, 1);
     if (cs_prefix && world == 1) gph_coal_stats_discard(cs_prefix, 1);   /* (several ranks: the caller removes every rank's part) */
     if (ts_slices && world == 1) gph_time_slices_discard(cs_prefix, 1);
     if (M) gph_mcmc_destroy(M);
@@ -511,6 +638,48 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     fwrite(TS_MAGIC, 1, 8, ts_part); fwrite(hdr, 4, 4, ts_part); fwrite(&nbytes, 4, 1, ts_part);
     fwrite(names.data(), 1, names.size(), ts_part);
   }
+  /* migration ancestry: accumulators and a device buffer of an_capacity per-sample rows, this rank's part file and its header */
+  int32_t an_ncol = 0, an_ri = 0;
+  int64_t an_written = 0;
+  std::vector<int32_t> an_rows, an_iters;
+  std::vector<std::string> an_names;
+  if (an_prefix) {
+    if (an_capacity <= 0) an_capacity = 64;
+    if ((rc = gph_engine_ancestry_enable(E, an_capacity, 0))) return fail(rc, "gph_engine_ancestry_enable");
+    gph_engine_ancestry_shape(E, &an_ncol, &an_ri, nullptr, nullptr);
+    an_rows.resize((size_t)an_ri * an_capacity);
+    an_iters.resize((size_t)an_capacity);
+    an_part = fopen(an_part_path(an_prefix, rank).c_str(), "wb");
+    if (!an_part) { snprintf(err, sizeof err, "Could not open %s", an_part_path(an_prefix, rank).c_str()); return fail(GPH_EARG, "opening the ancestry part file"); }
+    std::string names;
+    for (int s = 0; s < cfg.n; s++) {
+      /* the leaf's name as the coal-stats files print it: the second haploid of a diploid takes the previous sample's */
+      const char *nm = gph_control_sample_name(C, s);
+      if (!nm || !nm[0]) { const char *pv = s > 0 ? gph_control_sample_name(C, s - 1) : nullptr; nm = pv && pv[0] ? pv : "NA"; }
+      an_names.push_back(nm);
+      names += nm; names.push_back('\0');
+    }
+    for (int b = 0; b < cfg.B; b++) {
+      names += std::string(gph_control_pop_name(C, cfg.bandSrc[b])) + "->" + gph_control_pop_name(C, cfg.bandTgt[b]);
+      names.push_back('\0');
+    }
+    const int32_t hdr[3] = {cfg.n, cfg.B, an_ri}, nbytes = (int32_t)names.size();
+    fwrite(AN_MAGIC, 1, 8, an_part); fwrite(hdr, 4, 3, an_part); fwrite(&nbytes, 4, 1, an_part);
+    fwrite(names.data(), 1, names.size(), an_part);
+  }
+  int32_t an_held = 0;
+  auto an_flush = [&]() -> int {
+    int32_t got = 0;
+    int rcf = gph_engine_ancestry_fetch_rows(E, an_iters.data(), an_rows.data(), an_ri, an_capacity, &got);
+    if (rcf) return rcf;
+    for (int32_t i = 0; i < got; i++) {
+      if (fwrite(&an_iters[i], 4, 1, an_part) != 1) return GPH_EARG;
+      if (an_ri > 0 && fwrite(an_rows.data() + (size_t)i * an_ri, 4, (size_t)an_ri, an_part) != (size_t)an_ri) return GPH_EARG;
+    }
+    an_written += got;
+    an_held = 0;
+    return fflush(an_part) == 0 ? GPH_OK : GPH_EARG;
+  };
   auto ts_flush = [&]() -> int {
     int32_t got = 0;
     int rcf = gph_engine_time_slices_fetch(E, ts_rows.data(), cs_capacity, &got);
@@ -608,6 +777,10 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
       fprintf(trace, "\t%.6f\t%.6f\n", logL, dataL);
       fflush(trace);
       if (summary_path && (rc = gph_engine_locus_summary_sample(E))) return fail(rc, "gph_engine_locus_summary_sample");
+      if (an_prefix) {
+        if ((rc = gph_engine_ancestry_sample(E, it))) return fail(rc, "gph_engine_ancestry_sample");
+        if (++an_held == an_capacity && (rc = an_flush())) return fail(rc, "writing the ancestry part file");
+      }
       if (cs_prefix) {
         if ((rc = gph_engine_coal_stats_sample(E, it))) return fail(rc, "gph_engine_coal_stats_sample");
         if (ts_slices && (rc = gph_engine_time_slices_sample(E, it))) return fail(rc, "gph_engine_time_slices_sample");
@@ -709,6 +882,37 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     ts_part = nullptr;
     if (rcc != 0) return fail(GPH_EARG, "closing the time-slices part file");
   }
+  if (an_prefix) {
+    if ((rc = an_flush())) return fail(rc, "writing the ancestry part file");
+    /* this rank's rows of the per-locus table, behind its records */
+    int64_t S = 0;
+    gph_engine_ancestry_shape(E, nullptr, nullptr, &S, nullptr);
+    std::vector<double> raw((size_t)an_ncol * (le - lb));
+    if ((rc = gph_engine_ancestry_fetch_loci(E, raw.data(), an_ncol, 0))) return fail(rc, "gph_engine_ancestry_fetch_loci");
+    const long text0 = ftell(an_part);
+    const int n = cfg.n, B = cfg.B;
+    const double Sd = (double)S;
+    for (int64_t g = 0; g < le - lb; g++) {
+      const double *a = raw.data() + (size_t)g * an_ncol;
+      const char *nm = gph_loci_name(LC, lb + g);
+      for (int i = 0; i < n; i++) {
+        const double any = a[2 * B * n + i];
+        if (!(any > 0.0)) continue;
+        fprintf(an_part, "%lld\t%s\t%d\t%s\t%lld\t%.10g", (long long)(lb + g), nm ? nm : "", i, an_names[i].c_str(), (long long)S, any / Sd);
+        for (int b = 0; b < B; b++) {
+          const double c = a[b * n + i], t = a[B * n + b * n + i];
+          fprintf(an_part, "\t%.10g\t%.10g", c / Sd, c > 0.0 ? t / c : 0.0);
+        }
+        fprintf(an_part, "\n");
+      }
+    }
+    const long text1 = ftell(an_part);
+    const int64_t tail[2] = {an_written, (int64_t)(text1 - text0)};
+    if (text0 < 0 || text1 < text0 || fwrite(tail, 8, 2, an_part) != 2) return fail(GPH_EARG, "writing the ancestry part file");
+    const int rcc = ferror(an_part) | fclose(an_part);
+    an_part = nullptr;
+    if (rcc != 0) return fail(GPH_EARG, "closing the ancestry part file");
+  }
   int32_t ls_ncol = 0;
   int64_t ls_samples = 0;
   std::vector<double> ls_raw;
@@ -724,11 +928,12 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_engine_destroy(E);
   if (oob_checked && oob_where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
     gph_loci_free(LC);
     gph_control_free(C);
     if (cs_prefix && world == 1) gph_coal_stats_discard(cs_prefix, 1);
     if (ts_slices && world == 1) gph_time_slices_discard(cs_prefix, 1);
+    if (an_prefix && world == 1) gph_ancestry_discard(an_prefix, 1);
     return GPH_EKERNEL;
   }
   rc = GPH_OK;
@@ -740,7 +945,12 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_loci_free(LC);
   gph_control_free(C);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
-  /* (the slices file first: should the coal-stats files fail after it, one file is removed again, not 1 + 3 K) */
+  /* (the ancestry files first, then the slices file: should a later group fail, two files and one are removed again,
+   * not 1 + 3 K) */
+  if (an_prefix && world == 1) {
+    if (rc) gph_ancestry_discard(an_prefix, 1);
+    else rc = gph_ancestry_write(an_prefix, 1);
+  }
   if (ts_slices && world == 1) {
     if (rc) gph_time_slices_discard(cs_prefix, 1);
     else rc = gph_time_slices_write(cs_prefix, 1);
@@ -750,6 +960,7 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     else rc = gph_coal_stats_write(cs_prefix, 1);
     if (rc && ts_slices) gph_time_slices_discard(cs_prefix, 1);
   }
+  if (rc && an_prefix && world == 1) gph_ancestry_discard(an_prefix, 1);
   return rc;
 }
 
@@ -780,10 +991,17 @@ extern "C" int gph_run_control_file_ex3(const char *ctl, const char *ctl2, int32
                                         const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity,
                                         int32_t time_slices)
 {
+  return gph_run_control_file_ex4(ctl, ctl2, device, verbose, comm, locus_summary_path, coal_stats_prefix, coal_stats_capacity, time_slices, nullptr, 0);
+}
+
+extern "C" int gph_run_control_file_ex4(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
+                                        const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity,
+                                        int32_t time_slices, const char *ancestry_prefix, int32_t ancestry_capacity)
+{
   if (comm) return run_control_file(ctl, ctl2, device, verbose, gph_comm_rank(comm), gph_comm_world(comm), nullptr, nullptr, comm, locus_summary_path,
-                                    coal_stats_prefix, coal_stats_capacity, time_slices);
+                                    coal_stats_prefix, coal_stats_capacity, time_slices, ancestry_prefix, ancestry_capacity);
   return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr, locus_summary_path, coal_stats_prefix, coal_stats_capacity,
-                          time_slices);
+                          time_slices, ancestry_prefix, ancestry_capacity);
 }
 
 extern "C" int gph_run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose)

@@ -46,7 +46,8 @@ extern "C" {
 #define GPH_EHIP (-2)      /* HIP runtime failure (no device, OOM, launch error) */
 #define GPH_EKERNEL (-3)   /* a locus reported a fatal consistency error (reference: "Fatal Error NNNN") */
 #define GPH_ESTATE (-4)    /* call out of order */
-#define GPH_EFULL (-5)     /* gph_engine_coal_stats_sample / _time_slices_sample: every row of the device buffer is taken; fetch first */
+#define GPH_EFULL (-5)     /* gph_engine_coal_stats_sample / _time_slices_sample / _ancestry_sample: every row of the device buffer is taken;
+                            * fetch first.  gph_engine_ancestry_enable: the accumulators would exceed the byte limit */
 
 typedef struct gph_engine gph_engine;
 typedef struct gph_mcmc gph_mcmc;
@@ -223,7 +224,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * 5 tau_finish (commit or revert, by the decision flag), 7 mix_finish, 8 sync, 9 locus-rate scan, 10 locus-rate apply,
  * 11 locus-rate prepare, 13 locus summary (gph_engine_locus_summary_sample), 14 coalescent / sample-pair statistics
  * (gph_engine_coal_stats_sample: k_coal_stats + k_coal_fold together), 15 time-sliced statistics
- * (gph_engine_time_slices_sample: k_time_slices + k_time_slices_fold together) */
+ * (gph_engine_time_slices_sample: k_time_slices + k_time_slices_fold together), 16 migration ancestry
+ * (gph_engine_ancestry_sample: k_ancestry) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -341,6 +343,40 @@ int gph_engine_time_slices_shape(gph_engine *e, int32_t *row_doubles, int32_t *f
 int gph_engine_time_slices_fetch(gph_engine *e, double *out, int32_t max_rows, int32_t *rows);
 const char *gph_engine_time_slices_column_name(gph_engine *e, int32_t col);
 int gph_engine_time_slices_set_chunk(gph_engine *e, int32_t slots);
+/* per-locus, per-sample MIGRATION ANCESTRY accumulated on the device (k_ancestry: csrc/gph_ancestry.h): which sample's
+ * lineage went through which migration band, at which locus.  For one locus at one sample, with n leaves and B bands in
+ * control-file order, take the live migration nodes (the IS_NUM_MIGS entries of `living`; the M line of a state dump prints
+ * mg:branch:band:spop:tpop:sev:tev:age).  The path of leaf i is i, father(i), ..., root; migration node m is on the path
+ * iff its branch is a node of the path.  hit[b][i] = 1 iff some live m on the path of i belongs to band b; first[b][i] =
+ * the smallest age among those (the first one met going back in time); any[i] = 1 iff some hit[b][i] is 1.
+ * Per local locus, over the samples taken: a row of locus_columns = n (2B + 1) doubles, column b n + i: cnt.<b>.<i> += hit;
+ * B n + b n + i: age.<b>.<i> = age.<b>.<i> + first where hit (one plain fp64 addition a sample: rebuilt bit for bit from
+ * state dumps); 2 B n + i: any.<i> += any.  Counts are doubles holding integers.
+ * Per sample, over THIS rank's loci: a row of row_ints = n (B + 1) integers, column i: the loci with any[i] = 1; (1 + b) n
+ * + i: the loci with hit[b][i] = 1.  Several ranks: the per-locus rows concatenate in rank order, the per-sample rows add.
+ *   _enable(capacity_rows, max_bytes)  accumulators (zeroed) and a device buffer of capacity_rows per-sample rows;
+ *                      capacity_rows 0 frees everything, the feature is off.  GPH_EFULL (with a message that names the
+ *                      size) when the accumulators, L_local n (2B + 1) 8 bytes, exceed max_bytes (<= 0: 1 GiB); the
+ *                      engine stays usable.  B = 0: only the any columns exist (all zero).  gph_engine_init_genealogies
+ *                      zeroes the accumulators and empties the buffer
+ *   _sample(iteration) queues one sample on the engine's stream (one kernel, no host synchronisation, no exchange); the
+ *                      pages are made current as for gph_engine_locus_summary_sample (a commit still owed to the next
+ *                      kernel runs first).  A group of loci without a live migration costs one 4-byte read a locus.
+ *                      GPH_EFULL when no per-sample row is free: nothing is overwritten, nothing accumulated
+ *   _shape             doubles per per-locus row, integers per per-sample row, samples accumulated since the accumulators
+ *                      were last zeroed, per-sample rows held (any pointer may be NULL)
+ *   _fetch_loci        out[L_local][ld >= locus_columns] in global locus order (as gph_engine_locus_summary_fetch);
+ *                      reset != 0 zeroes the accumulators and the sample count afterwards
+ *   _fetch_rows        copies the held rows to iters[max_rows >= held] and out[held][ld >= row_ints], *rows = their number,
+ *                      and empties the buffer
+ *   _column_name(which, col)  which 0: a per-locus column, "cnt.<b>.<i>", "age.<b>.<i>", "any.<i>"; which 1: a per-sample
+ *                      column, "any.<i>", "hit.<b>.<i>"; NULL if out of range or off; valid until the next call */
+int gph_engine_ancestry_enable(gph_engine *e, int32_t capacity_rows, int64_t max_bytes);
+int gph_engine_ancestry_sample(gph_engine *e, int32_t iteration);
+int gph_engine_ancestry_shape(gph_engine *e, int32_t *locus_columns, int32_t *row_ints, int64_t *samples, int32_t *rows_held);
+int gph_engine_ancestry_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset);
+int gph_engine_ancestry_fetch_rows(gph_engine *e, int32_t *iters, int32_t *out, int64_t ld, int32_t max_rows, int32_t *rows);
+const char *gph_engine_ancestry_column_name(gph_engine *e, int32_t which, int32_t col);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -516,6 +552,26 @@ int gph_run_control_file_ex3(const char *ctl_path, const char *secondary_ctl_pat
 int gph_time_slices_write(const char *prefix, int32_t ranks);
 int gph_time_slices_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles);
 int gph_time_slices_discard(const char *prefix, int32_t ranks);
+/* the same, plus the migration ancestry (`G-PhoCS-hip --ancestry PREFIX`; needs none of the other options): with an
+ * ancestry_prefix a sample of gph_engine_ancestry_* is taken wherever a trace line is written, into a device buffer of
+ * ancestry_capacity rows (<= 0: 64), and rank r keeps the binary file PREFIX.ancestry.part<r>: its per-sample rows as they
+ * are flushed and, once the last iteration is done, its rows of the per-locus table.
+ * gph_ancestry_write(prefix, ranks) writes, from the parts,
+ *   PREFIX.loci.tsv     header locus name leaf sample samples pAny, then per band p_<src>-><tgt> age_<src>-><tgt>; one row
+ *                       per (locus, leaf) with any.<i> > 0 (all-zero rows are omitted), in sequence-file order, then leaf
+ *                       order; sample = the leaf's name as the header of PREFIX.<pop>.probCoal.tsv names it; pAny = any / S,
+ *                       p = cnt / S, age = age_sum / cnt (0 where cnt = 0) in the genealogy's own units, all "%.10g"; the
+ *                       ranks' rows concatenated in rank order
+ *   PREFIX.samples.tsv  header iter, any_<sample>#<i> per leaf, <src>-><tgt>|<sample>#<i> per band and leaf; rows "%7d" then
+ *                       "\t%9d" per count; the ranks' rows added sample by sample
+ * and removes the parts; _discard removes the parts and both files.  A one-rank run writes or discards itself; with several
+ * ranks the caller does.  A failed run leaves neither parts nor files.  ancestry_prefix NULL = gph_run_control_file_ex3. */
+int gph_run_control_file_ex4(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
+                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null,
+                             const char *coal_stats_prefix_or_null, int32_t coal_stats_capacity, int32_t time_slices,
+                             const char *ancestry_prefix_or_null, int32_t ancestry_capacity);
+int gph_ancestry_write(const char *prefix, int32_t ranks);
+int gph_ancestry_discard(const char *prefix, int32_t ranks);
 
 /* ------------------------------------------------------------------------------------
  * post-run summary of a trace file (host only): block means per column, the output of the reference's
