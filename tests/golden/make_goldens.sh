@@ -88,6 +88,14 @@ gen j3 22 12 300 120 40 --mig-beta 0.00000004
 # randomised model shapes (tools/random_models.py: random binary trees, random legal bands incl. ancestral ends, optional ancient
 # sample): the reference's pack and records of 12 models that run through and 3 on which the reference itself aborts
 python3 $REPO/tools/random_models.py fixtures rnd 2 3 6 17 19 23 24 42 43 55 59 72 34 46 35
+# randomised RUN SETTINGS on those shapes (random_models.py --wide: step sizes over four decades, 0 .. 30 % N, 120 .. 2000 bp, mixing
+# off, CONST / VAR / FIXED rates, haploid samples): 16 models the reference runs to the end, pack and records gzipped; tests/test_run_settings.py says what
+# the set must reach
+python3 $REPO/tools/random_models.py fixtures wide 8 13 20 22 27 28 41 45 48 63 64 67 73 87 88 91 --wide
+# k3: burn-in 13 (iterations -13 .. -1 reach the engine), mcmc-sample-skip 2, a log period (10) that does not divide the burn-in:
+# the real binary's trace file; pack / records / states as for the others (the harness's `run` starts at iteration 0)
+gen k3 3 4 200 24 10 --mig-beta 0.00000004 --burn-in 13 --sample-skip 2
+timeout 900 $REF main -n 1 k3.ctl >/dev/null 2>&1
 
 # kernel-level fixtures: single calls of the reference's per-locus functions after N iterations
 for c in "m4 60" "a7 40" "g2 20" "j1 70" "j2 50"; do set -- $c; timeout 300 $REF unit $1.ctl $2 $1.unit >/dev/null 2>&1; done

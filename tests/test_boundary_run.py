@@ -7,7 +7,7 @@ oracle/integration_binding.c, whose bodies are calls of include/gphocs_hip.h's p
 the reference's per-locus path runs.  The program must write the trace file the unmodified reference binary wrote
 (tests/golden/*.trace) -- migration bands and rubber-band conflicts (m3), estimated sample ages (a7), the reference's
 own find-finetunes search steering the engine's step sizes (f3), `locus-mut-rate VAR` (v8), a secondary control file
-(w2), the engine's hard caps (x8).
+(w2), the engine's hard caps (x8), a burn-in whose iterations carry numbers below zero, with mcmc-sample-skip (k3).
 
 CPU: the binding over the host build of the engine sources (oracle/_ref/gphocs_boundary_emu).  -m gpu: the same
 binding over the gfx950 library (gphocs_boundary_hip): the reference's own driver on the MI355X.
@@ -21,7 +21,7 @@ import pytest
 
 from conftest import GOLDEN, ORACLE_DIR, REPO
 
-CASES = ["g1", "m3", "a7", "f3", "v8", "w2", "x8", "r5", "j1", "j2", "j3"]   # (y9 needs the big-tree build of the engine sources: tests/test_host_logic.py, -m gpu)
+CASES = ["g1", "m3", "a7", "f3", "v8", "w2", "x8", "r5", "j1", "j2", "j3", "k3"]   # (y9 needs the big-tree build of the engine sources: tests/test_host_logic.py, -m gpu)
 
 
 def _build():

@@ -78,7 +78,8 @@ def test_thread_count_does_not_change_the_result(lib):
         assert np.array_equal(getattr(a, f), getattr(b, f))
 
 
-@pytest.mark.parametrize("name", ["g1", "m3", "a7", "f3", "v8", "w2", "r5", "j1", "j2", "j3"])
+@pytest.mark.parametrize("name", ["g1", "m3", "a7", "f3", "v8", "w2", "r5", "j1", "j2", "j3",
+                                  "k3"])    # k3: burn-in 13 (iterations -13 .. -1), mcmc-sample-skip 2, log period 10
 def test_program_writes_the_reference_trace_file(lib, name, tmp_path):
     """same control file + sequence file -> the trace file of the real G-PhoCS binary, byte for byte
     (f3: find-finetunes TRUE -- the step-size search of performMCMC, GPhoCS.c:1896-2180, incl. its acceptance

@@ -30,6 +30,7 @@ CASES = {"g1": 30, "g2": 30, "m3": 120, "m4": 60, "c5": 30, "s3": 40, "a6": 80, 
          "j1": 150,  # (((A,B),(C,D)),E), bands AB->CD, CD->AB, C->AB, E->ABCD
          "j2": 100,  # ((A,(B,C)),((D,E),F)), 8 bands: leaf<->ancestral, ancestral<->ancestral, leaf->leaf, D->BC across the root
          "j3": 120,  # ((A,B),(C,D)) with an ESTIMATED ancient sample in C under the band target CD
+         "k3": 24,   # k3: the pack, records and states of a control file with burn-in 13 / mcmc-sample-skip 2 (test_program_trace_file runs its burn-in)
          "b2": 24}   # b2: 20 migration bands: library variant b (live-band list in LDS, model read from HBM, 384-column reduced rows)
 
 
@@ -365,6 +366,7 @@ def test_native_library_is_the_path(G):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["g1", "m3", "a7", "f3", "v8", "w2", "x8", "y9", "r5", "b2", "n7", "j1", "j2", "j3",
+                                  "k3",     # k3: burn-in 13: iteration numbers below zero on the device, mcmc-sample-skip 2, log period 10
                                   "p6"])    # p6: 2^16 phases of one pattern (a repeated column of 16 hets), 65 554 phased patterns in one locus
 def test_program_trace_file(name, tmp_path):
     """G-PhoCS-hip <control-file> on the MI355X: the trace file of the real G-PhoCS binary for the same

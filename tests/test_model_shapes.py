@@ -50,24 +50,31 @@ def _records_before(path, it):
     return out
 
 
+def _check_oracle(oracle_cli, name, tmp_path, d=RND, meta=META):
+    it = meta[name]["run"]["iters"]
+    tr = tmp_path / "o.rtrace"
+    r = subprocess.run([oracle_cli, "run", os.path.join(d, name + ".gpk"), str(it), str(tr), str(tmp_path / "o.state"), str(it - 1), "0"],
+                       capture_output=True, timeout=600)
+    assert (r.returncode != 0) == meta[name]["reference_aborts"], r.stderr[-300:]
+    assert open(tr).read() == open(os.path.join(d, name + ".rtrace")).read()
+
+
 @pytest.mark.parametrize("name", MODELS)
 def test_oracle_reproduces_the_reference_records(oracle_cli, name, tmp_path):
-    it = META[name]["run"]["iters"]
-    tr = tmp_path / "o.rtrace"
-    r = subprocess.run([oracle_cli, "run", os.path.join(RND, name + ".gpk"), str(it), str(tr), str(tmp_path / "o.state"), str(it - 1), "0"],
-                       capture_output=True, timeout=600)
-    assert (r.returncode != 0) == META[name]["reference_aborts"], r.stderr[-300:]
-    assert open(tr).read() == open(os.path.join(RND, name + ".rtrace")).read()
+    _check_oracle(oracle_cli, name, tmp_path)
 
 
-def _engine_run(G, lib, name, tmp_path, tag):
-    """-> (records file, final state file or None, iteration in which the engine failed or None)"""
-    it = META[name]["run"]["iters"]
+def _engine_run(G, lib, name, tmp_path, tag, d=RND, meta=META, before=None, after=None):
+    """-> (records file, final state file or None, iteration in which the engine failed or None).  d, meta: the fixture
+    directory and its models; before(s): called before initialize; after(s, k): called after iteration k"""
+    it = meta[name]["run"]["iters"]
     tr, st = str(tmp_path / f"{tag}.rtrace"), str(tmp_path / f"{tag}.state")
-    s = G.Sampler(G.Pack.load(os.path.join(RND, name + ".gpk")), lib=lib) if lib is not None else G.Sampler(G.Pack.load(os.path.join(RND, name + ".gpk")))
+    s = G.Sampler(G.Pack.load(os.path.join(d, name + ".gpk")), lib=lib) if lib is not None else G.Sampler(G.Pack.load(os.path.join(d, name + ".gpk")))
     s.set_record_file(tr)
     failed = None
     try:
+        if before is not None:
+            before(s)
         try:
             s.initialize()
         except RuntimeError:
@@ -79,6 +86,8 @@ def _engine_run(G, lib, name, tmp_path, tag):
                 except RuntimeError:
                     failed = k
                     break
+                if after is not None:
+                    after(s, k)
         if failed is None:
             s.dump_state(st, True)
     finally:
@@ -87,12 +96,12 @@ def _engine_run(G, lib, name, tmp_path, tag):
     return tr, (st if failed is None else None), failed
 
 
-def _check_engine(G, lib, oracle_cli, name, tmp_path):
-    it = META[name]["run"]["iters"]
-    tr, st, failed = _engine_run(G, lib, name, tmp_path, "e")
-    ref = os.path.join(RND, name + ".rtrace")
-    if META[name]["reference_aborts"]:
-        last = META[name]["reference_last_iteration"]
+def _check_engine(G, lib, oracle_cli, name, tmp_path, d=RND, meta=META, before=None, after=None, residue=0.0):
+    it = meta[name]["run"]["iters"]
+    tr, st, failed = _engine_run(G, lib, name, tmp_path, "e", d, meta, before, after)
+    ref = os.path.join(d, name + ".rtrace")
+    if meta[name]["reference_aborts"]:
+        last = meta[name]["reference_last_iteration"]
         # the reference dies inside iteration `last` (or right after its records, in the checkAll that follows): the engine in the same one
         assert failed is not None and failed in (last, last + 1), f"engine failed in {failed}, the reference in {last}"
         a, b = _records_before(tr, failed), _records_before(ref, failed)
@@ -104,8 +113,9 @@ def _check_engine(G, lib, oracle_cli, name, tmp_path):
     assert failed is None, f"engine failed in iteration {failed}"
     compare_records(tr, ref)
     ot, os_ = tmp_path / "o.rtrace", tmp_path / "o.state"
-    subprocess.run([oracle_cli, "run", os.path.join(RND, name + ".gpk"), str(it), str(ot), str(os_), str(it - 1), "1"], check=True, timeout=600)
-    compare_states(st, os_)
+    subprocess.run([oracle_cli, "run", os.path.join(d, name + ".gpk"), str(it), str(ot), str(os_), str(it - 1), "1"], check=True, timeout=600)
+    compare_states(st, os_, residue=residue)
+    return tr, st
 
 
 @pytest.mark.parametrize("name", MODELS)
@@ -127,15 +137,13 @@ def test_hip_on_random_models(oracle_cli, name, tmp_path):
     _check_engine(G, None, oracle_cli, name, tmp_path)
 
 
-def test_fresh_random_models_reference_vs_oracle(oracle_cli, ref_cli, tmp_path):
-    """20 models that are NOT committed fixtures (ids 200-219), through the real reference and the oracle"""
-    if ref_cli is None:
-        pytest.skip("oracle/_ref/gphocs_ref not built: the committed fixtures cover this")
+def _fresh_models(oracle_cli, tmp_path, ids, wide=False):
+    """models `ids` through the real reference and the oracle: records, abort or not, final per-locus state"""
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import random_models as RM
     bad = 0
-    for k in range(200, 220):
-        name, cfg, run = RM.generate(k, str(tmp_path))
+    for k in ids:
+        name, cfg, run = RM.generate(k, str(tmp_path), wide)
         rc = RM.reference_run(name, str(tmp_path), run["iters"])
         o = subprocess.run([oracle_cli, "run", name + ".gpk", str(run["iters"]), name + ".o.rtrace", name + ".o.state", str(run["iters"] - 1), "1"],
                            cwd=tmp_path, capture_output=True, timeout=600)
@@ -148,3 +156,10 @@ def test_fresh_random_models_reference_vs_oracle(oracle_cli, ref_cli, tmp_path):
         ok = (o.returncode != 0) == aborted and rd(".rtrace") == rd(".o.rtrace") and (aborted or rd(".state") == rd(".o.state"))
         bad += not ok
     assert bad == 0
+
+
+def test_fresh_random_models_reference_vs_oracle(oracle_cli, ref_cli, tmp_path):
+    """20 models that are NOT committed fixtures (ids 200-219), through the real reference and the oracle"""
+    if ref_cli is None:
+        pytest.skip("oracle/_ref/gphocs_ref not built: the committed fixtures cover this")
+    _fresh_models(oracle_cli, tmp_path, range(200, 220))

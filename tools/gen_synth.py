@@ -6,7 +6,9 @@ reference's unchanged format (AlignmentProcessor.c:468-860).
 Recipe = SURVEY.md section 8(d): per locus, simulate a genealogy under the config's
 population tree at the prior means (theta = alpha/beta, tau = tau-initial, no migration),
 drop JC69 mutations (mu = 1) on a `seqlen`-bp sequence, pair haplotypes into diploids
-(IUPAC het codes Y R M K S W), mask `nmask` of genotypes as N.
+(IUPAC het codes Y R M K S W), mask `nmask` of genotypes as N.  A sample listed under the
+configuration's `haploid` key (global sample indices) is written `sN h` in the control file: one leaf,
+one haplotype row without IUPAC codes.
 
 Configs mirror BASELINE.json `configs` (index 1..5); --loci overrides L so the same
 shapes can be produced at fixture size.
@@ -109,9 +111,43 @@ def ancient_pops(cfg):
     return [] if a is None else list(a) if isinstance(a, (list, tuple)) else [a]
 
 
+def haploid_samples(cfg):
+    return set(int(x) for x in cfg.get("haploid", ()))
+
+
+def ploidies(cfg):
+    """per current population, the ploidy (1 / 2) of each of its samples, in sample order"""
+    hap, out, sid = haploid_samples(cfg), [], 0
+    for k in cfg["pops"]:
+        out.append([1 if sid + j in hap else 2 for j in range(k)])
+        sid += k
+    assert all(0 <= h < sid for h in hap), "haploid: sample indices run over all populations' samples"
+    return out
+
+
+# the step sizes every committed control file was written with (FINETUNE_TEXT: their spelling there); the root's own
+# finetune-tau line is 2.86e-6, every other ancestral population's 8e-7
+FINETUNES = dict(coal_time=0.01, mig_time=0.3, theta=0.04, mig_rate=0.02, tau=0.0000008, mixing=0.003)
+FINETUNE_TEXT = dict(coal_time="0.01", mig_time="0.3", theta="0.04", mig_rate="0.02", tau="0.0000008", mixing="0.003")
+
+
+def _fixed(v):
+    """plain decimal notation (no exponent form), 16 decimals, trailing zeros dropped"""
+    t = f"{v:.16f}".rstrip("0")
+    return t + "0" if t.endswith(".") else t
+
+
 def write_ctl(path, cfg, seqfile, tracefile, loci, seed, iters, samples_per_log, no_mixing=False,
-              start_mig=0, mig_beta=0.00001, var_rates=None, fixed_rates=None):
+              start_mig=0, mig_beta=0.00001, var_rates=None, fixed_rates=None, finetunes=None, burn_in=None, sample_skip=None):
+    """finetunes: {coal_time, mig_time, theta, mig_rate, tau, mixing} -> value; a missing key keeps FINETUNES' value and
+    spelling.  `tau` also scales every ancestral population's own finetune-tau line by tau / FINETUNES["tau"]."""
     cur, anc, taus, children = build_tree(cfg)
+    finetunes = {k: v for k, v in (finetunes or {}).items() if v is not None}
+    assert set(finetunes) <= set(FINETUNES), finetunes
+
+    def ft_text(key):
+        return _fixed(finetunes[key]) if key in finetunes else FINETUNE_TEXT[key]
+    tau_scale = finetunes["tau"] / FINETUNES["tau"] if "tau" in finetunes else None
     out = []
     out.append("GENERAL-INFO-START\n")
     out.append(f"\tseq-file            {seqfile}")
@@ -121,6 +157,10 @@ def write_ctl(path, cfg, seqfile, tracefile, loci, seed, iters, samples_per_log,
     out.append(f"\tnum-loci            {loci}")
     out.append(f"\trandom-seed         {seed}")
     out.append(f"\tmcmc-iterations\t  {iters}")
+    if burn_in is not None:
+        out.append(f"\tburn-in             {burn_in}")
+    if sample_skip is not None:
+        out.append(f"\tmcmc-sample-skip    {sample_skip}")
     out.append(f"\titerations-per-log  {samples_per_log}")
     out.append("\tlogs-per-line       10")
     if start_mig:
@@ -129,12 +169,12 @@ def write_ctl(path, cfg, seqfile, tracefile, loci, seed, iters, samples_per_log,
         out.append("\tno-mixing           1")
     out.append("")
     out.append("\tfind-finetunes\t\tFALSE")
-    out.append("\tfinetune-coal-time\t0.01\t\t")
-    out.append("\tfinetune-mig-time\t0.3\t\t")
-    out.append("\tfinetune-theta\t\t0.04")
-    out.append("\tfinetune-mig-rate\t0.02")
-    out.append("\tfinetune-tau\t\t0.0000008")
-    out.append("\tfinetune-mixing\t\t0.003")
+    out.append(f"\tfinetune-coal-time\t{ft_text('coal_time')}\t\t")
+    out.append(f"\tfinetune-mig-time\t{ft_text('mig_time')}\t\t")
+    out.append(f"\tfinetune-theta\t\t{ft_text('theta')}")
+    out.append(f"\tfinetune-mig-rate\t{ft_text('mig_rate')}")
+    out.append(f"\tfinetune-tau\t\t{ft_text('tau')}")
+    out.append(f"\tfinetune-mixing\t\t{ft_text('mixing')}")
     if var_rates is not None:
         out.append(f"\tfinetune-locus-rate\t{var_rates[1]}")
     out.append("")
@@ -148,10 +188,11 @@ def write_ctl(path, cfg, seqfile, tracefile, loci, seed, iters, samples_per_log,
     out.append("\nGENERAL-INFO-END\n")
     out.append("CURRENT-POPS-START\t\n")
     sid = 0
+    ploidy = ploidies(cfg)
     for i, nm in enumerate(cur):
         out.append("\tPOP-START")
         out.append(f"\t\tname\t\t{nm}")
-        samples = " ".join(f"s{sid + j} d" for j in range(cfg["pops"][i]))
+        samples = " ".join(f"s{sid + j} {'d' if ploidy[i][j] == 2 else 'h'}" for j in range(cfg["pops"][i]))
         sid += cfg["pops"][i]
         out.append(f"\t\tsamples\t\t{samples}")
         if i in ancient_pops(cfg):
@@ -166,7 +207,7 @@ def write_ctl(path, cfg, seqfile, tracefile, loci, seed, iters, samples_per_log,
         out.append(f"\t\ttau-initial\t{taus[i]:.9f}")
         out.append("\t\ttau-beta\t\t20000.0\t")
         ft = 0.0000008 if i < len(anc) - 1 else 0.00000286
-        out.append(f"\t\tfinetune-tau\t\t\t{ft:.8f}")
+        out.append(f"\t\tfinetune-tau\t\t\t{ft:.8f}" if tau_scale is None else f"\t\tfinetune-tau\t\t\t{_fixed(ft * tau_scale)}")
         out.append("\tPOP-END\n")
     out.append("ANCESTRAL-POPS-END\n")
     if cfg["bands"]:
@@ -186,10 +227,11 @@ def write_ctl(path, cfg, seqfile, tracefile, loci, seed, iters, samples_per_log,
 
 def simulate_locus(rng, cfg, taus, theta, seqlen, ancient_age):
     """returns list of haploid sequences (np.uint8 arrays of base indices), leaf order =
-    population order then sample order, two haploids per diploid sample"""
+    population order then sample order, two haploids per diploid sample, one per haploid sample"""
     kc = len(cfg["pops"])
+    ploidy = ploidies(cfg)
     # nodes: list of (age, left, right); leaves first
-    nleaf = 2 * sum(cfg["pops"])
+    nleaf = sum(sum(p) for p in ploidy)
     age = [0.0] * nleaf
     left = [-1] * nleaf
     right = [-1] * nleaf
@@ -197,7 +239,7 @@ def simulate_locus(rng, cfg, taus, theta, seqlen, ancient_age):
     pop_lineages = {}
     cur, anc, _, children = build_tree(cfg)
     for i in range(kc):
-        k = 2 * cfg["pops"][i]
+        k = sum(ploidy[i])
         a0 = ancient_age if i in ancient_pops(cfg) else 0.0
         for j in range(k):
             age[leaf + j] = a0
@@ -257,11 +299,15 @@ def simulate_locus(rng, cfg, taus, theta, seqlen, ancient_age):
     return [seqs[i] for i in range(nleaf)]
 
 
-def genotype_strings(haps, rng, nmask):
-    nd = len(haps) // 2
-    out = []
-    for d in range(nd):
-        a, b = haps[2 * d], haps[2 * d + 1]
+def genotype_strings(haps, rng, nmask, ploidy=None):
+    """one string per sample; ploidy: 1 / 2 per sample in leaf order (default: every sample diploid)"""
+    if ploidy is None:
+        ploidy = [2] * (len(haps) // 2)
+    assert sum(ploidy) == len(haps)
+    out, leaf = [], 0
+    for pl in ploidy:
+        a, b = haps[leaf], haps[leaf + pl - 1]
+        leaf += pl
         chars = np.array(list(BASES))[a].copy()
         het = a != b
         for i in np.nonzero(het)[0]:
@@ -295,6 +341,14 @@ def main():
     ap.add_argument("--fixed-rates", action="store_true",
                     help="locus-mut-rate FIXED <out>.rates: a rate file with one rate per locus, spread over 0.2 .. 5 "
                          "(readRateFile, GPhoCS.c:491-579, normalises them to mean 1)")
+    for key in FINETUNES:
+        ap.add_argument("--finetune-" + key.replace("_", "-"), type=float, default=None,
+                        help=f"finetune-{key.replace('_', '-')} (default {FINETUNE_TEXT[key]})" +
+                             ("; every ancestral population's own finetune-tau line is scaled by the same factor" if key == "tau" else ""))
+    ap.add_argument("--burn-in", type=int, default=None, help="burn-in <N>: N iterations numbered -N .. -1 before the first sample")
+    ap.add_argument("--sample-skip", type=int, default=None, help="mcmc-sample-skip <N>: a trace line every N + 1 iterations")
+    ap.add_argument("--haploid", type=int, nargs="*", default=None, metavar="SAMPLE",
+                    help="samples (indices over all populations, in order) that are haploid: `sN h`, one leaf, one haplotype row")
     ap.add_argument("--out", required=True, help="output prefix: <out>.ctl, <out>.seq")
     a = ap.parse_args()
     if a.model_json:
@@ -310,6 +364,8 @@ def main():
     else:
         assert a.config is not None, "--config or --model-json"
         cfg = CONFIGS[a.config]
+    if a.haploid is not None:
+        cfg = dict(cfg, haploid=a.haploid)
     L = a.loci or cfg["loci"]
     rng = np.random.default_rng(20261002 + a.config)
     cur, anc, taus, _ = build_tree(cfg)
@@ -317,7 +373,8 @@ def main():
     seqfile = os.path.basename(a.out) + ".seq"
     write_ctl(a.out + ".ctl", cfg, seqfile, os.path.basename(a.out) + ".trace", L, a.mcmc_seed,
               a.iters, a.per_log, no_mixing=a.no_mixing, start_mig=a.start_mig, mig_beta=a.mig_beta,
-              var_rates=a.var_rates, fixed_rates=os.path.basename(a.out) + ".rates" if a.fixed_rates else None)
+              var_rates=a.var_rates, fixed_rates=os.path.basename(a.out) + ".rates" if a.fixed_rates else None,
+              finetunes={k: getattr(a, "finetune_" + k) for k in FINETUNES}, burn_in=a.burn_in, sample_skip=a.sample_skip)
     if a.fixed_rates:
         # log-uniform over 0.2 .. 5, mixed layout (several per line, tabs, an exponent form): the reader is fscanf("%lf")
         rr = np.exp(np.random.default_rng(77 + a.config).uniform(np.log(0.2), np.log(5.0), L))
@@ -327,17 +384,18 @@ def main():
                 f.write("\n" if g % 4 == 3 else "\t" if g % 2 else " ")
             f.write("\n")
     nd = sum(cfg["pops"])
+    ploidy = [p for pp in ploidies(cfg) for p in pp]
     with open(a.out + ".seq", "w") as f:
         f.write(f"{L}\n\n")
         for g in range(L):
             haps = simulate_locus(rng, cfg, [t * a.mut_scale for t in taus], theta * a.mut_scale,
                                   a.seqlen, 0.000002 * a.mut_scale)
-            gts = genotype_strings(haps, rng, a.nmask)
+            gts = genotype_strings(haps, rng, a.nmask, ploidy)
             f.write(f"locus{g + 1} {nd} {a.seqlen}\n")
             for d in range(nd):
                 f.write(f"s{d}\t{gts[d]}\n")
             f.write("\n")
-    print(f"wrote {a.out}.ctl {a.out}.seq  L={L} samples={nd} diploid", file=sys.stderr)
+    print(f"wrote {a.out}.ctl {a.out}.seq  L={L} samples={nd} ({ploidy.count(2)} diploid, {ploidy.count(1)} haploid)", file=sys.stderr)
 
 
 if __name__ == "__main__":
