@@ -643,7 +643,8 @@ def summary_table(raw, S, pack):
     return t
 
 
-COAL_STATS_FULL = -5     # GPH_EFULL: gph_engine_coal_stats_sample found no free row in the device buffer
+GPH_EFULL = -5           # a sampler's _sample found no free row in its device buffer (ancestry _enable: over max_bytes)
+COAL_STATS_FULL = GPH_EFULL
 COAL_STATS_FIXED = ("iter", "coalStat", "numCoal", "migStat", "numMig", "genLnL", "dataLnL")
 
 
@@ -671,17 +672,21 @@ def coal_stats_table(rows, n, K, L):
     return out
 
 
+def _combined(fn, prefix, ranks):
+    """(samples, row_doubles) array: the records of the parts of ranks 0..ranks-1 added in rank order"""
+    rows, rd = C.c_int64(), C.c_int32()
+    if fn(str(prefix).encode(), ranks, None, 0, C.byref(rows), C.byref(rd)):
+        raise RuntimeError(f"gphocs_hip: {fn.__name__[4:]} failed")
+    out = np.zeros((rows.value, rd.value))
+    if rows.value and fn(str(prefix).encode(), ranks, out.ctypes.data_as(C.POINTER(C.c_double)), rows.value, C.byref(rows), C.byref(rd)):
+        raise RuntimeError(f"gphocs_hip: {fn.__name__[4:]} failed")
+    return out
+
+
 def coal_stats_combined(lib, prefix, ranks):
     """(samples, row_doubles + 1) array: the records of PREFIX.coal.part<0..ranks-1> added in rank order, logPrior last
     (gph_coal_stats_combined)"""
-    rows, rd = C.c_int64(), C.c_int32()
-    if lib.gph_coal_stats_combined(str(prefix).encode(), ranks, None, 0, C.byref(rows), C.byref(rd)):
-        raise RuntimeError("gphocs_hip: coal_stats_combined failed")
-    out = np.zeros((rows.value, rd.value))
-    if rows.value and lib.gph_coal_stats_combined(str(prefix).encode(), ranks, out.ctypes.data_as(C.POINTER(C.c_double)), rows.value,
-                                                  C.byref(rows), C.byref(rd)):
-        raise RuntimeError("gphocs_hip: coal_stats_combined failed")
-    return out
+    return _combined(lib.gph_coal_stats_combined, prefix, ranks)
 
 
 def time_slices_table(rows, S, K, B):
@@ -698,14 +703,7 @@ def time_slices_table(rows, S, K, B):
 def time_slices_combined(lib, prefix, ranks):
     """(samples, row_doubles) array: the records of PREFIX.slices.part<0..ranks-1> added in rank order
     (gph_time_slices_combined)"""
-    rows, rd = C.c_int64(), C.c_int32()
-    if lib.gph_time_slices_combined(str(prefix).encode(), ranks, None, 0, C.byref(rows), C.byref(rd)):
-        raise RuntimeError("gphocs_hip: time_slices_combined failed")
-    out = np.zeros((rows.value, rd.value))
-    if rows.value and lib.gph_time_slices_combined(str(prefix).encode(), ranks, out.ctypes.data_as(C.POINTER(C.c_double)), rows.value,
-                                                   C.byref(rows), C.byref(rd)):
-        raise RuntimeError("gphocs_hip: time_slices_combined failed")
-    return out
+    return _combined(lib.gph_time_slices_combined, prefix, ranks)
 
 
 def ancestry_table(raw, S, n, B):
@@ -876,6 +874,30 @@ class Sampler:
         self._chk(self.lib.gph_engine_debug_oob(self.engine, C.byref(w), C.byref(c)), "debug_oob")
         return w.value, c.value
 
+    # ---- what the statistics samplers below share
+    def _sample(self, fn, what, full, *args):
+        rc = fn(self.engine, *args)
+        if rc == GPH_EFULL:
+            raise BufferError(f"gphocs_hip: the {what} buffer is full; fetch with {full}() first")
+        self._chk(rc, fn.__name__[11:])
+
+    def _fetch_rows(self, fn, held, width, dtype=np.float64, with_iters=False):
+        """allocate from the shape, fetch, trim: the rows a sampler took since the last call (the device buffer is emptied)"""
+        ct = C.c_double if dtype is np.float64 else C.c_int32
+        out = np.zeros((max(held, 1), max(width, 1)), dtype=dtype)
+        its = np.zeros(max(held, 1), dtype=np.int32)
+        got = C.c_int32()
+        args = (its.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(C.POINTER(ct)), out.shape[1]) if with_iters else \
+            (out.ctypes.data_as(C.POINTER(ct)),)
+        self._chk(fn(self.engine, *args, out.shape[0], C.byref(got)), fn.__name__[11:])
+        return its[:got.value], out[:got.value]
+
+    def _locus_columns(self, fetch, name, ncol, reset):
+        """per-locus columns by name: one array entry per local locus in global locus order"""
+        out = np.zeros((self.end - self.begin, max(ncol, 1)))
+        self._chk(fetch(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[1], int(bool(reset))), fetch.__name__[11:])
+        return {name(c).decode(): out[:, c].copy() for c in range(ncol)}
+
     # ---- per-locus posterior summaries (gph_engine_locus_summary_*): accumulated on the device, one sample per call
     def enable_locus_summary(self, on=True):
         self._chk(self.lib.gph_engine_locus_summary_enable(self.engine, int(bool(on))), "locus_summary_enable")
@@ -889,14 +911,11 @@ class Sampler:
         of the `-l` summary file (README.md), derived from the raw ones with the formulas given there."""
         nc, ns = C.c_int32(), C.c_int64()
         self._chk(self.lib.gph_engine_locus_summary_columns(self.engine, C.byref(nc), C.byref(ns)), "locus_summary_columns")
-        nloc = self.end - self.begin
-        out = np.zeros((nloc, max(nc.value, 1)))
-        self._chk(self.lib.gph_engine_locus_summary_fetch(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[1],
-                                                          int(bool(reset))), "locus_summary_fetch")
-        cols = {self.lib.gph_engine_locus_summary_column_name(self.engine, c).decode(): out[:, c].copy() for c in range(nc.value)}
+        cols = self._locus_columns(self.lib.gph_engine_locus_summary_fetch,
+                                   lambda c: self.lib.gph_engine_locus_summary_column_name(self.engine, c), nc.value, reset)
         S = ns.value
         if raw:
-            cols["samples"] = np.full(nloc, S, dtype=np.int64)
+            cols["samples"] = np.full(self.end - self.begin, S, dtype=np.int64)
             return cols
         return summary_table(cols, S, self.pack)
 
@@ -909,10 +928,7 @@ class Sampler:
 
     def sample_coal_stats(self, it):
         """one sample of the current state, labelled iteration `it`; BufferError when the device buffer is full"""
-        rc = self.lib.gph_engine_coal_stats_sample(self.engine, int(it))
-        if rc == COAL_STATS_FULL:
-            raise BufferError("gphocs_hip: the coal-stats buffer is full; fetch with coal_stats() first")
-        self._chk(rc, "coal_stats_sample")
+        self._sample(self.lib.gph_engine_coal_stats_sample, "coal-stats", "coal_stats", int(it))
 
     def coal_stats(self, raw=False):
         """the samples taken since the last call (the device buffer is emptied).  raw=True: the rows as the engine keeps them,
@@ -920,11 +936,7 @@ class Sampler:
         of dicts, one per sample (coal_stats_table); several ranks must add their raw rows in rank order first."""
         rd, fill, n, K = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(self.lib.gph_engine_coal_stats_shape(self.engine, C.byref(rd), C.byref(fill), C.byref(n), C.byref(K)), "coal_stats_shape")
-        out = np.zeros((max(fill.value, 1), max(rd.value, 1)))
-        got = C.c_int32()
-        self._chk(self.lib.gph_engine_coal_stats_fetch(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[0], C.byref(got)),
-                  "coal_stats_fetch")
-        out = out[:got.value]
+        out = self._fetch_rows(self.lib.gph_engine_coal_stats_fetch, fill.value, rd.value)[1]
         if raw:
             return out
         L = int(getattr(self.pack, "global_L", None) or self.pack.L)
@@ -947,10 +959,7 @@ class Sampler:
 
     def sample_time_slices(self, it):
         """one sample of the current state, labelled iteration `it`; BufferError when the device buffer is full"""
-        rc = self.lib.gph_engine_time_slices_sample(self.engine, int(it))
-        if rc == COAL_STATS_FULL:
-            raise BufferError("gphocs_hip: the time-slices buffer is full; fetch with time_slices() first")
-        self._chk(rc, "time_slices_sample")
+        self._sample(self.lib.gph_engine_time_slices_sample, "time-slices", "time_slices", int(it))
 
     def _time_slices_shape(self):
         v = [C.c_int32() for _ in range(6)]
@@ -965,11 +974,7 @@ class Sampler:
         """the samples taken since the last call (the device buffer is emptied).  raw=True: a (samples, 1 + 2 S (K + B)) array
         over THIS rank's loci (columns: time_slices_columns()); raw=False: a list of dicts (time_slices_table)"""
         rd, fill, S, K, B, _ = self._time_slices_shape()
-        out = np.zeros((max(fill, 1), max(rd, 1)))
-        got = C.c_int32()
-        self._chk(self.lib.gph_engine_time_slices_fetch(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[0], C.byref(got)),
-                  "time_slices_fetch")
-        out = out[:got.value]
+        out = self._fetch_rows(self.lib.gph_engine_time_slices_fetch, fill, rd)[1]
         return out if raw else time_slices_table(out, S, K, B)
 
     def time_slices_columns(self):
@@ -981,16 +986,13 @@ class Sampler:
         """per-locus accumulators and a device buffer of `capacity` per-sample rows; capacity 0 switches the feature off.
         MemoryError when the accumulators would exceed max_bytes (0: 1 GiB); the sampler stays usable"""
         rc = self.lib.gph_engine_ancestry_enable(self.engine, int(capacity), int(max_bytes))
-        if rc == COAL_STATS_FULL:
+        if rc == GPH_EFULL:
             raise MemoryError("gphocs_hip: the ancestry accumulators exceed max_bytes (GPH_EFULL)")
         self._chk(rc, "ancestry_enable")
 
     def sample_ancestry(self, it):
         """one sample of the current state, labelled iteration `it`; BufferError when the row buffer is full"""
-        rc = self.lib.gph_engine_ancestry_sample(self.engine, int(it))
-        if rc == COAL_STATS_FULL:
-            raise BufferError("gphocs_hip: the ancestry row buffer is full; fetch with ancestry_rows() first")
-        self._chk(rc, "ancestry_sample")
+        self._sample(self.lib.gph_engine_ancestry_sample, "ancestry row", "ancestry_rows", int(it))
 
     def _ancestry_shape(self):
         nc, ri, ns, held = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
@@ -1001,13 +1003,10 @@ class Sampler:
         """one entry per local locus in global locus order.  raw=True: a dict of the accumulators as the engine keeps them,
         keyed by their machine names (cnt.<b>.<i>, age.<b>.<i>, any.<i>) + "samples".  raw=False: ancestry_table of them"""
         nc, _, S, _ = self._ancestry_shape()
-        nloc = self.end - self.begin
-        out = np.zeros((nloc, max(nc, 1)))
-        self._chk(self.lib.gph_engine_ancestry_fetch_loci(self.engine, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[1],
-                                                          int(bool(reset))), "ancestry_fetch_loci")
-        cols = {self.lib.gph_engine_ancestry_column_name(self.engine, 0, c).decode(): out[:, c].copy() for c in range(nc)}
+        cols = self._locus_columns(self.lib.gph_engine_ancestry_fetch_loci,
+                                   lambda c: self.lib.gph_engine_ancestry_column_name(self.engine, 0, c), nc, reset)
         if raw:
-            cols["samples"] = np.full(nloc, S, dtype=np.int64)
+            cols["samples"] = np.full(self.end - self.begin, S, dtype=np.int64)
             return cols
         return ancestry_table(cols, S, self.pack.n, self.pack.B)
 
@@ -1015,13 +1014,8 @@ class Sampler:
         """(iterations, rows): the per-sample rows taken since the last call, an int32 (samples, n (B + 1)) array over THIS
         rank's loci -- any.<i>, then hit.<b>.<i> -- and their iterations; the device buffer is emptied"""
         _, ri, _, held = self._ancestry_shape()
-        its = np.zeros(max(held, 1), dtype=np.int32)
-        out = np.zeros((max(held, 1), max(ri, 1)), dtype=np.int32)
-        got = C.c_int32()
-        self._chk(self.lib.gph_engine_ancestry_fetch_rows(self.engine, its.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                          out.ctypes.data_as(C.POINTER(C.c_int32)), out.shape[1], out.shape[0], C.byref(got)),
-                  "ancestry_fetch_rows")
-        return its[:got.value], out[:got.value, :ri]
+        its, out = self._fetch_rows(self.lib.gph_engine_ancestry_fetch_rows, held, ri, np.int32, with_iters=True)
+        return its, out[:, :ri]
 
     def hbm_bytes(self):
         b = C.c_double()

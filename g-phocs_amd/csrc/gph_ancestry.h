@@ -32,7 +32,7 @@
 //
 // The kernel writes no page, draws no random number and touches no chain state.
 #pragma once
-#include "gph_kernels.h"
+#include "gph_sampler.h"
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 6
@@ -40,46 +40,27 @@
 #define GPH_AN_MAXTHREADS 256
 #define GPH_AN_RANGES 3
 
-#ifdef GPH_HOSTEMU
-#define GPH_AN_HD static inline
-#define GPH_AN_FN static inline
-#else
-#define GPH_AN_HD __host__ __device__ inline
-#define GPH_AN_FN __device__ inline
-#endif
-
 static_assert(GPH_MAX_MIGS <= 16, "the path mask of k_ancestry is the high half of a 32-bit word");
 
-// mig_age, mig_i and living of a page, packed: range r = len[r] bytes from page offset src[r] at image offset dst[r] (all
-// multiples of 16); a_*: image offsets of the arrays themselves
-struct GphAnImg {
-  int32_t src[GPH_AN_RANGES], dst[GPH_AN_RANGES], len[GPH_AN_RANGES];
+// mig_age, mig_i and living of a page, packed (gph_sampler.h); a_*: image offsets of the arrays themselves
+struct GphAnImg : GphPackedImg {
   int32_t a_mage, a_migi, a_living;
-  int32_t bytes;
 };
 struct GphAnShape {
   int32_t G, bd, lds_bytes;
   GphAnImg img;
 };
 
-GPH_AN_HD int gph_an_locus_columns(int n, int B) { return n * (2 * B + 1); }
-GPH_AN_HD int gph_an_row_ints(int n, int B) { return n * (B + 1); }
+GPH_SM_HD int gph_an_locus_columns(int n, int B) { return n * (2 * B + 1); }
+GPH_SM_HD int gph_an_row_ints(int n, int B) { return n * (B + 1); }
 
-GPH_AN_HD void gph_an_shape(const GphLayout &y, GphAnShape &h)
+GPH_SM_HD void gph_an_shape(const GphLayout &y, GphAnShape &h)
 {
   const int lo[GPH_AN_RANGES] = {y.o_mig_age, y.o_mig_i, y.o_living};
   const int sz[GPH_AN_RANGES] = {GPH_MAX_MIGS * 8, GPH_MAX_MIGS * MG_COUNT * 2, GPH_MAX_MIGS * 2};
-  int at = 0, a[GPH_AN_RANGES];
-  for (int r = 0; r < GPH_AN_RANGES; r++) {
-    const int s = lo[r] & ~15;
-    int e = (lo[r] + sz[r] + 15) & ~15;
-    if (e > y.page_bytes) e = y.page_bytes;
-    h.img.src[r] = s; h.img.dst[r] = at; h.img.len[r] = e - s;
-    a[r] = at + (lo[r] - s);
-    at += e - s;
-  }
+  int a[GPH_AN_RANGES];
+  gph_pack_ranges(y, lo, sz, GPH_AN_RANGES, h.img, a);
   h.img.a_mage = a[0]; h.img.a_migi = a[1]; h.img.a_living = a[2];
-  h.img.bytes = at;
   const int n = y.n > 0 ? y.n : 1;
   h.G = n < GPH_AN_MAXTHREADS ? GPH_AN_MAXTHREADS / n : 1;
   h.bd = (h.G * n + 63) / 64 * 64;
@@ -92,7 +73,7 @@ struct GphAnLds {
   uint32_t *up;     // [G][N]: father (low half, as int16) | mask of the live migrations on the node's branch << 16
   int32_t *nm;      // [G] live migrations of the locus (0: not staged)
 };
-GPH_AN_FN void gph_an_carve(char *base, int N, const GphAnShape &h, GphAnLds &s)
+GPH_SM_FN void gph_an_carve(char *base, int N, const GphAnShape &h, GphAnLds &s)
 {
   char *p = base;
   s.img = p; p += (size_t)h.G * h.img.bytes;
@@ -101,22 +82,14 @@ GPH_AN_FN void gph_an_carve(char *base, int N, const GphAnShape &h, GphAnLds &s)
 }
 
 // live migrations of the locus in page pg, from the IS_NUM_MIGS word alone
-GPH_AN_FN int gph_an_num_migs(const char *pg, const GphLayout &y)
+GPH_SM_FN int gph_an_num_migs(const char *pg, const GphLayout &y)
 {
   const int nm = ((const int32_t *)(pg + y.o_iscal))[IS_NUM_MIGS];
   return nm < 0 ? 0 : nm > GPH_MAX_MIGS ? GPH_MAX_MIGS : nm;
 }
 
-// 16-byte unit at image offset o -> where it lies in the page
-GPH_AN_FN int gph_an_unit_src(const GphAnImg &m, int o)
-{
-  int r = 0;
-  while (r < GPH_AN_RANGES - 1 && o >= m.dst[r] + m.len[r]) r++;
-  return m.src[r] + (o - m.dst[r]);
-}
-
 // the staged word of a node record (16 bytes, loaded as one unit): its father, no migration yet
-GPH_AN_FN uint32_t gph_an_up_word(const void *rec16)
+GPH_SM_FN uint32_t gph_an_up_word(const void *rec16)
 {
   GphNode r;
   memcpy(&r, rec16, sizeof r);
@@ -124,7 +97,7 @@ GPH_AN_FN uint32_t gph_an_up_word(const void *rec16)
 }
 
 // one lane a locus: bit 16 + k on the branch of the k-th live migration
-GPH_AN_FN void gph_an_mark(const GphAnLds &s, const GphLayout &y, const GphAnShape &h, int g)
+GPH_SM_FN void gph_an_mark(const GphAnLds &s, const GphLayout &y, const GphAnShape &h, int g)
 {
   const char *im = s.img + (size_t)GPH_IX(g, h.G) * h.img.bytes;
   const int16_t *migi = (const int16_t *)(im + h.img.a_migi), *living = (const int16_t *)(im + h.img.a_living);
@@ -146,7 +119,7 @@ GPH_AN_FN void gph_an_mark(const GphAnLds &s, const GphLayout &y, const GphAnSha
 #else
 #define GPH_AN_ROW_ADD(p) ((void)atomicAdd((p), 1u))
 #endif
-GPH_AN_FN void gph_an_leaf(const GphAnLds &s, const GphLayout &y, const GphAnShape &h, int g, int i, double *a, uint32_t *row)
+GPH_SM_FN void gph_an_leaf(const GphAnLds &s, const GphLayout &y, const GphAnShape &h, int g, int i, double *a, uint32_t *row)
 {
   const int n = y.n, N = y.N, B = y.B, ncol = gph_an_locus_columns(n, B), nrow = gph_an_row_ints(n, B);
   uint32_t mask = 0;
@@ -219,7 +192,7 @@ static inline void ancestry_workgroup(const GphLayout &y, const GphAnShape &h, c
   }
   for (int u = 0; u < h.G * upl; u++) {
     const int g = u / upl, o = (u - g * upl) * 16;
-    if (s.nm[g] > 0) memcpy(s.img + (size_t)g * h.img.bytes + o, pages + (size_t)(j0 + g) * y.page_bytes + gph_an_unit_src(h.img, o), 16);
+    if (s.nm[g] > 0) memcpy(s.img + (size_t)g * h.img.bytes + o, pages + (size_t)(j0 + g) * y.page_bytes + gph_pack_unit_src(h.img, o), 16);
   }
   for (int g = 0; g < h.G; g++) if (s.nm[g] > 0) gph_an_mark(s, y, h, g);
   for (int lane = 0; lane < h.G * n; lane++) {
@@ -251,7 +224,7 @@ __global__ void __launch_bounds__(GPH_AN_MAXTHREADS) k_ancestry(GphLayout y, Gph
   for (int u = tid; u < h.G * upl; u += bd) {
     const int g = u / upl, o = (u - g * upl) * 16;
     if (s.nm[GPH_IX(g, h.G)] > 0) {
-      const uint4 val = *(const uint4 *)(pages + (size_t)(j0 + g) * y.page_bytes + gph_an_unit_src(h.img, o));
+      const uint4 val = *(const uint4 *)(pages + (size_t)(j0 + g) * y.page_bytes + gph_pack_unit_src(h.img, o));
       *(uint4 *)(s.img + (size_t)g * h.img.bytes + GPH_IX(o, h.img.bytes)) = val;
     }
   }

@@ -1,4 +1,4 @@
-// gph_coalstats.h -- k_coal_stats + k_coal_fold: the genome-wide coalescent statistics ("coal stats") and sample-pair
+// gph_coalstats.h -- k_coal_stats (+ k_rows_fold, gph_sampler.h): the genome-wide coalescent statistics ("coal stats") and sample-pair
 // statistics ("node stats") of one MCMC sample, computed on the device (include/gphocs_hip.h, gph_engine_coal_stats_*).
 //
 // What is computed restates code the reference carries but never reaches (the call is guarded by
@@ -35,38 +35,30 @@
 // Summation order (what makes a row bitwise reproducible for a given locus count, chunk size and rank count): inside a
 // chunk every accumulator is owned by one lane and grows in slot order; at the end of the chunk the n - 1 flat terms are
 // added by one lane in term order i = 0 .. n-2, and the log-likelihoods were added by one lane in slot order.  The chunk's
-// partial row goes to HBM; k_coal_fold, one lane per column, then adds the partials in chunk order 0, 1, ... into the
+// partial row goes to HBM; k_rows_fold, one lane per column, then adds the partials in chunk order 0, 1, ... into the
 // sample's row.  No atomics, no dependence on how workgroups are scheduled.  Counts are integers held as doubles (exact
 // below 2^53).  Ranks: each rank's row covers its own loci; the rows are added in rank order by whoever combines them
 // (INTEGRATION.md).
 //
 // The kernels write no page, draw no random number and touch no chain state.
 #pragma once
-#include "gph_kernels.h"
+#include "gph_sampler.h"
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 4
 
 // raw row: iteration, the four flat statistics, the two log-likelihood sums, then cnt, first, agesum as [pair][pop]
 enum { CS_ITER = 0, CS_COALSTAT, CS_NUMCOAL, CS_MIGSTAT, CS_NUMMIG, CS_GENLNL, CS_DATALNL, CS_FIXED };
+static_assert(CS_ITER == 0, "gph_fold_column writes the iteration into column 0");
 
 #define GPH_CS_CHUNK 128        // slots per chunk (default)
 #define GPH_CS_LDS_ACC 49152    // LDS bytes of a workgroup's pair accumulators at most
 #define GPH_CS_MAXTHREADS 256
-#define GPH_CS_FOLD_THREADS 256
 
-#ifdef GPH_HOSTEMU
-#define GPH_CS_HD static inline
-#define GPH_CS_FN static inline
-#else
-#define GPH_CS_HD __host__ __device__ inline     /* sizes: the host needs them to allocate and launch */
-#define GPH_CS_FN __device__ inline
-#endif
-
-GPH_CS_HD int gph_cs_pairs(int n) { return n * (n - 1) / 2; }
-GPH_CS_HD int gph_cs_row_doubles(int n, int K) { return CS_FIXED + 3 * gph_cs_pairs(n) * K; }
+GPH_SM_HD int gph_cs_pairs(int n) { return n * (n - 1) / 2; }
+GPH_SM_HD int gph_cs_row_doubles(int n, int K) { return CS_FIXED + 3 * gph_cs_pairs(n) * K; }
 // lanes of a workgroup = pairs of a tile
-GPH_CS_HD int gph_cs_block(int n, int K)
+GPH_SM_HD int gph_cs_block(int n, int K)
 {
   int bd = (gph_cs_pairs(n) + 63) / 64 * 64;
   if (bd > GPH_CS_MAXTHREADS) bd = GPH_CS_MAXTHREADS;
@@ -85,12 +77,12 @@ struct GphCsLds {
   int32_t *isf;         // [N] 1: the node is the first coalescence of its population in the current locus
   int32_t *evt;         // [K + B] coalescence / migration counts summed over the chunk's loci
 };
-GPH_CS_HD size_t gph_cs_lds_bytes(int n, int K, int B, int bd)
+GPH_SM_HD size_t gph_cs_lds_bytes(int n, int K, int B, int bd)
 {
   const int N = 2 * n - 1;
   return (size_t)N * 16 + (size_t)K * bd * 8 + (size_t)(n - 1) * 24 + (size_t)K * bd * 8 + (size_t)N * 4 + (size_t)(K + B) * 4;
 }
-GPH_CS_FN void gph_cs_carve(char *base, int n, int K, int B, int bd, GphCsLds &s)
+GPH_SM_FN void gph_cs_carve(char *base, int n, int K, int B, int bd, GphCsLds &s)
 {
   const int N = 2 * n - 1;
   char *p = base;
@@ -106,7 +98,7 @@ GPH_CS_FN void gph_cs_carve(char *base, int n, int K, int B, int bd, GphCsLds &s
 }
 
 // pair p (row-major over i < j) -> its two leaves
-GPH_CS_FN void gph_cs_pair(int p, int n, int &i, int &j)
+GPH_SM_FN void gph_cs_pair(int p, int n, int &i, int &j)
 {
   int r = 0;
   while (r < n - 2 && p >= n - 1 - r) { p -= n - 1 - r; r++; }
@@ -117,7 +109,7 @@ GPH_CS_FN void gph_cs_pair(int p, int n, int &i, int &j)
 // internal node v of the staged locus: its rank among the internal ages (ties: the lower index first) puts its age into
 // the sorted array, and it is its population's first coalescence when no internal node of that population comes before it
 // (patch.c:2217-2224)
-GPH_CS_FN void gph_cs_rank_first(const GphCsLds &s, int n, int N, int v)
+GPH_SM_FN void gph_cs_rank_first(const GphCsLds &s, int n, int N, int v)
 {
   const double av = s.nd[GPH_IX(v, N)].age;
   const int pv = s.nd[GPH_IX(v, N)].npop;
@@ -135,7 +127,7 @@ GPH_CS_FN void gph_cs_rank_first(const GphCsLds &s, int n, int N, int v)
 // lowest common ancestor of nodes a and b: when one is the other's father, that one is the answer's side and the child
 // climbs (so a zero-length branch cannot send an ancestor past the LCA); otherwise the younger of the two climbs to its
 // father, and with equal ages, where neither is then the other's father, the lower index.  At most 2N steps
-GPH_CS_FN int gph_cs_lca(const GphCsLds &s, int N, int a, int b)
+GPH_SM_FN int gph_cs_lca(const GphCsLds &s, int N, int a, int b)
 {
   for (int guard = 0; a != b && guard < 2 * N; guard++) {
     const GphNode &na = s.nd[GPH_IX(a, N)], &nb = s.nd[GPH_IX(b, N)];
@@ -151,7 +143,7 @@ GPH_CS_FN int gph_cs_lca(const GphCsLds &s, int N, int a, int b)
 }
 
 // the pair owned by `lane` coalesces in node l in the staged locus
-GPH_CS_FN void gph_cs_pair_add(const GphCsLds &s, int N, int K, int bd, int lane, int l)
+GPH_SM_FN void gph_cs_pair_add(const GphCsLds &s, int N, int K, int bd, int lane, int l)
 {
   const GphNode &nl = s.nd[GPH_IX(l, N)];
   const int pop = GPH_IX(nl.npop, K);
@@ -163,7 +155,7 @@ GPH_CS_FN void gph_cs_pair_add(const GphCsLds &s, int N, int K, int bd, int lane
 }
 
 // term i of the flat statistics of the staged locus (patch.c:2307-2311): k = n - i lineages over the i-th interval
-GPH_CS_FN void gph_cs_flat_add(const GphCsLds &s, int n, int i)
+GPH_SM_FN void gph_cs_flat_add(const GphCsLds &s, int n, int i)
 {
   const double dT = i == 0 ? s.sorted[0] : s.sorted[GPH_IX(i, n - 1)] - s.sorted[GPH_IX(i - 1, n - 1)];
   const double k = (double)(n - i);
@@ -173,7 +165,7 @@ GPH_CS_FN void gph_cs_flat_add(const GphCsLds &s, int n, int i)
 }
 
 // the fixed columns of a chunk's partial row, by ONE lane: flat terms in term order, event counts
-GPH_CS_FN void gph_cs_chunk_fixed(const GphCsLds &s, int n, int K, int B, double sgen, double sdata, double *out)
+GPH_SM_FN void gph_cs_chunk_fixed(const GphCsLds &s, int n, int K, int B, double sgen, double sdata, double *out)
 {
   double cs = 0.0, ms = 0.0;
   for (int i = 0; i < n - 1; i++) { ms = ms + s.flat_m[GPH_IX(i, n - 1)]; cs = cs + s.flat_c[GPH_IX(i, n - 1)]; }
@@ -190,7 +182,7 @@ GPH_CS_FN void gph_cs_chunk_fixed(const GphCsLds &s, int n, int K, int B, double
 }
 
 // entry q of a tile's pair accumulators (q = pair-in-tile * K + population) into the chunk's partial row
-GPH_CS_FN void gph_cs_chunk_pair_out(const GphCsLds &s, int n, int K, int bd, int tile, int q, double *out)
+GPH_SM_FN void gph_cs_chunk_pair_out(const GphCsLds &s, int n, int K, int bd, int tile, int q, double *out)
 {
   const int pr = q / K, pop = q - pr * K;
   const int npk = gph_cs_pairs(n) * K;
@@ -199,14 +191,6 @@ GPH_CS_FN void gph_cs_chunk_pair_out(const GphCsLds &s, int n, int K, int bd, in
   out[CS_FIXED + col] = (double)s.cnt[at];
   out[CS_FIXED + npk + col] = (double)s.first[at];
   out[CS_FIXED + 2 * npk + col] = s.agesum[at];
-}
-
-// column c of a sample's row: the chunks' partials in chunk order
-GPH_CS_FN void gph_cs_fold_column(const double *part, int nchunks, int rd, int c, double iteration, double *row)
-{
-  double sum = 0.0;
-  for (int ch = 0; ch < nchunks; ch++) sum = sum + part[(size_t)ch * rd + c];
-  row[c] = c == CS_ITER ? iteration : sum;
 }
 
 #ifdef GPH_HOSTEMU
@@ -286,12 +270,6 @@ __global__ void __launch_bounds__(GPH_CS_MAXTHREADS) k_coal_stats(GphLayout y, c
   double *out = part + (size_t)ch * rd;
   for (int q = tid; q < valid * K; q += bd) gph_cs_chunk_pair_out(s, n, K, bd, tile, q, out);
   if (tile == 0 && tid == 0) gph_cs_chunk_fixed(s, n, K, B, sgen, sdata, out);
-}
-
-__global__ void __launch_bounds__(GPH_CS_FOLD_THREADS) k_coal_fold(const double *part, int nchunks, int rd, double iteration, double *row)
-{
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < rd) gph_cs_fold_column(part, nchunks, rd, c, iteration, row);
 }
 #endif
 

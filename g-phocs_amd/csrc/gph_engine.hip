@@ -365,6 +365,18 @@ __global__ void k_debug_math(GphKargs KA, const double *x, const double *y, int 
 
 // ---------------------------------------------------------------- engine object
 #define GPH_NCLS 17     // kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+// the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
+struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
+  char *d = nullptr;
+  size_t esz = 0;
+  int32_t n = 0, cap = 0, fill = 0;
+};
+struct SmParts {     // one partial row of rd doubles per chunk of `chunk` slots, folded into a sample's row by k_rows_fold
+  double *d_part = nullptr;
+  int32_t rd = 0, chunk = 0, nchunks = 0;
+  int32_t chunk_next = 0;      // slots per chunk of the next alloc (the _set_chunk entry points; 0: the default)
+};
+
 struct gph_engine {
   gph_config cfg;
   std::vector<int32_t> samplesPerPop, popFather, popSon0, popSon1, bandSrc, bandTgt;
@@ -432,33 +444,16 @@ struct gph_engine {
   bool mirror_current = true;  // the host mirror G_h holds what the device-side stages last wrote (false between a queued stage and pull_G)
   bool no_fuse = false;        // GPH_NO_FUSE=1 (tests): every finish as a kernel of its own; read once in gph_engine_create
   gph_counters counters = {0, 0, 0.0, 0};
-  // per-locus summaries (gph_summary.h): [ls_ncol][L] accumulators in slot order, samples since they were last zeroed
-  double *d_ls = nullptr;
-  int32_t ls_ncol = 0;
-  int64_t ls_samples = 0;
-  std::vector<std::string> ls_names;
-  // genome-wide coalescent / sample-pair statistics (gph_coalstats.h): per-chunk partial rows, the rows of the samples taken
-  // since the last fetch ([cs_cap][cs_rd]); all null / 0 while the feature is off
-  double *d_cs_part = nullptr, *d_cs_rows = nullptr;
-  int32_t cs_cap = 0, cs_fill = 0, cs_rd = 0, cs_chunk = 0, cs_nchunks = 0, cs_bd = 0;
-  int32_t cs_chunk_next = 0;   // slots per chunk of the next _enable (gph_engine_coal_stats_set_chunk; 0: GPH_CS_CHUNK)
-  std::string cs_name;
-  // time-sliced coalescence / migration statistics (gph_timeslices.h): per-chunk partial rows, the rows of the samples taken
-  // since the last fetch ([ts_cap][ts_rd]); all null / 0 while the feature is off
-  double *d_ts_part = nullptr, *d_ts_rows = nullptr;
-  int32_t ts_cap = 0, ts_fill = 0, ts_rd = 0, ts_chunk = 0, ts_nchunks = 0;
-  int32_t ts_chunk_next = 0;   // slots per chunk of the next _enable (gph_engine_time_slices_set_chunk; 0: GPH_TS_CHUNK)
-  GphTsShape ts_shape = {};
-  std::string ts_name;
-  // per-locus, per-sample migration ancestry (gph_ancestry.h): fp64 accumulators [L][an_ncol] in slot order, the integer rows
-  // of the samples taken since the last fetch ([an_cap][an_ri]) and their iterations; all null / 0 while the feature is off
-  double *d_an_acc = nullptr;
-  uint32_t *d_an_rows = nullptr;
-  int32_t an_cap = 0, an_fill = 0, an_ncol = 0, an_ri = 0;
-  int64_t an_samples = 0;
-  GphAnShape an_shape = {};
-  std::vector<int32_t> an_iters;
-  std::string an_name;
+  // the statistics samplers; all null / 0 while a feature is off
+  // per-locus summaries (gph_summary.h): [ncol][L] accumulators in slot order, samples since they were last zeroed
+  struct { double *d = nullptr; int32_t ncol = 0; int64_t samples = 0; std::vector<std::string> names; } ls;
+  // genome-wide coalescent / sample-pair statistics (gph_coalstats.h)
+  struct { SmParts part; SmRows rows; int32_t bd = 0; std::string name; } cs;
+  // time-sliced coalescence / migration statistics (gph_timeslices.h)
+  struct { SmParts part; SmRows rows; GphTsShape shape = {}; std::string name; } ts;
+  // per-locus, per-sample migration ancestry (gph_ancestry.h): fp64 accumulators [L][ncol] in slot order, the integer rows
+  // of the samples and their iterations
+  struct { double *d_acc = nullptr; SmRows rows; int32_t ncol = 0; int64_t samples = 0; GphAnShape shape = {}; std::vector<int32_t> iters; std::string name; } an;
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -960,10 +955,6 @@ static int finish_sync(gph_engine *e)
 }
 
 static int run_stage_now(gph_engine *e, int stage, int arg);
-// run a deferred synchronizeEvents pass now (anything but the next genealogy sweep is about to touch the pages).
-// now = the caller is a stepwise entry point that goes on to edit the host mirror of the chain state and push it: the
-// stage that checks the pass (Fatal Error 0075/0076, the class-8 counters) must then have run -- on the host, result
-// checked -- before that, or the push would overwrite what a queued device-side stage wrote
 // the commit of a decided mixing proposal that was left for the next sweep kernel: as a kernel of its own, now (something
 // other than the sweep is about to read or write the pages)
 static int mix_finish_owed(gph_engine *e)
@@ -971,6 +962,10 @@ static int mix_finish_owed(gph_engine *e)
   if (e->mix_owed) { e->mix_owed = false; LAUNCH(e, 7, k_mix_finish, 0); }
   return 0;
 }
+// run a deferred synchronizeEvents pass now (anything but the next genealogy sweep is about to touch the pages).
+// now = the caller is a stepwise entry point that goes on to edit the host mirror of the chain state and push it: the
+// stage that checks the pass (Fatal Error 0075/0076, the class-8 counters) must then have run -- on the host, result
+// checked -- before that, or the push would overwrite what a queued device-side stage wrote
 static int flush_sync(gph_engine *e, bool now)
 {
   { int rcm = mix_finish_owed(e); if (rcm) return rcm; }     /* a mixing commit left for the next sweep kernel goes first */
@@ -1020,28 +1015,15 @@ static int run_stage_now(gph_engine *e, int stage, int arg)
   return check_error(e);
 }
 
-// the per-locus summary accumulators back to zero samples (queued on the engine's stream; nothing if summaries are off)
-static int an_zero(gph_engine *e)
+// accumulators of a sampler on the device back to zero (queued on the engine's stream; nothing while the feature is off)
+static int acc_zero(gph_engine *e, void *p, size_t bytes)
 {
-  e->an_samples = 0;
-  if (!e->d_an_acc) return 0;
-  const size_t bytes = sizeof(double) * (size_t)e->an_ncol * e->L;
+  if (!p) return 0;
 #ifdef GPH_HOSTEMU
-  memset(e->d_an_acc, 0, bytes);
+  (void)e;
+  memset(p, 0, bytes);
 #else
-  HIPCHK(hipMemsetAsync(e->d_an_acc, 0, bytes, e->stream));
-#endif
-  return 0;
-}
-static int ls_zero(gph_engine *e)
-{
-  e->ls_samples = 0;
-  if (!e->d_ls) return 0;
-  const size_t bytes = sizeof(double) * (size_t)e->ls_ncol * e->L;
-#ifdef GPH_HOSTEMU
-  memset(e->d_ls, 0, bytes);
-#else
-  HIPCHK(hipMemsetAsync(e->d_ls, 0, bytes, e->stream));
+  HIPCHK(hipMemsetAsync(p, 0, bytes, e->stream));
 #endif
   return 0;
 }
@@ -1124,9 +1106,9 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->dev.pages); dev_free(e->dev.shadow); dev_free(e->dev.cond); dev_free((void *)e->dev.cond_off);
   dev_free((void *)e->dev.seq); dev_free((void *)e->dev.seq_off); dev_free((void *)e->dev.orig); dev_free((void *)e->dev.P); dev_free(e->dev.out); dev_free(e->dev.stats); dev_free(e->d_mutRate);
   dev_free(e->d_lrec); dev_free(e->d_lpre); dev_free(e->d_slot_of); dev_free(e->d_lr_result); dev_free(e->d_lr_gscr); dev_free(e->d_ref_page); dev_free(e->d_ref_seq);
-  dev_free(e->d_part); dev_free(e->dev.err); dev_free(e->d_ls); dev_free(e->d_cs_part); dev_free(e->d_cs_rows);
-  dev_free(e->d_ts_part); dev_free(e->d_ts_rows);
-  dev_free(e->d_an_acc); dev_free(e->d_an_rows);
+  dev_free(e->d_part); dev_free(e->dev.err);
+  dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
+  dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   for (void *p : e->deferred_free) dev_free(p);
   e->deferred_free.clear();
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
@@ -1451,13 +1433,12 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   if (e->G_h->mix_flag || e->G_h->tau_flag) { e->G_h->mix_flag = 0; e->G_h->tau_flag = 0; e->G_dirty = true; }
   PUSH_IF_DIRTY(e);
   /* summaries of the old chain do not carry over; the locus-rate columns come and go with `locus-mut-rate VAR` */
-  if (e->d_ls && e->ls_ncol != gph_ls_columns(e->cfg.K, e->cfg.B, e->var_rates)) { int rce = gph_engine_locus_summary_enable(e, 1); if (rce) return rce; }
-  { int rcz = ls_zero(e); if (rcz) return rcz; }
-  e->cs_fill = 0;
-  e->ts_fill = 0;
-  e->an_fill = 0;
-  e->an_iters.clear();
-  { int rcz = an_zero(e); if (rcz) return rcz; }
+  if (e->ls.d && e->ls.ncol != gph_ls_columns(e->cfg.K, e->cfg.B, e->var_rates)) { int rce = gph_engine_locus_summary_enable(e, 1); if (rce) return rce; }
+  e->ls.samples = e->an.samples = 0;
+  e->cs.rows.fill = e->ts.rows.fill = e->an.rows.fill = 0;
+  e->an.iters.clear();
+  { int rcz = acc_zero(e, e->ls.d, sizeof(double) * (size_t)e->ls.ncol * e->L); if (rcz) return rcz; }
+  { int rcz = acc_zero(e, e->an.d_acc, sizeof(double) * (size_t)e->an.ncol * e->L); if (rcz) return rcz; }
   LAUNCH(e, 3, k_init, e->seedz, (const double *)e->d_mutRate, e->init_predraws);
   int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -2462,91 +2443,179 @@ int gph_engine_dump_loci(gph_engine *e, const char *path, int32_t withCond, int3
   return 0;
 }
 
+// ---- the statistics samplers: one scaffold (settle, launch bookkeeping, row buffer, chunked partials) under four features
+// A sample reads the current state from the device, so whatever is still owed to it runs first; how much depends on what
+// the sampler's kernels read.  A deferred synchronizeEvents pass STAYS deferred at every level: it corrects event times only
+// (the one sampler that reads them applies the pass's arithmetic itself: vsync, gph_timeslices.h).
+//   SETTLE_PAGES (summary, coal stats: node records and per-page scalars).  The commit of an accepted mixing proposal still
+//     owed to the next sweep kernel changes the pages, so it runs now (k_mix_finish) -- unless the proposal was rejected (the
+//     host mirror of the chain state, current after an iteration, says so): then there is nothing to commit, as part_sweep
+//     finds too.
+//   SETTLE_PAGES_AND_AGES (ancestry: the migration ages too).  First the commit / revert of a decided tau or sample-age
+//     proposal still owed to the next evaluate kernel (k_tau_finish: one more launch; never owed after a whole
+//     gph_engine_iteration_, only between the parts of a stepwise caller).
+//   SETTLE_CHAIN (time slices: event times and the model in the chain state).  Before both, a host-side change of the chain
+//     state is pushed.
+enum { SETTLE_PAGES, SETTLE_PAGES_AND_AGES, SETTLE_CHAIN };
+static int sample_settle(gph_engine *e, int level)
+{
+  if (level == SETTLE_CHAIN) PUSH_IF_DIRTY(e);
+  if (level != SETTLE_PAGES) { int rcw = finish_owed(e); if (rcw) return rcw; }
+  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
+  return mix_finish_owed(e);
+}
+
+// the launch bookkeeping of one sample, k launches of timing class cls queued on the engine's stream between the two:
+// what is pending on the stream goes first, HIP events bracket the launches (tms: their slot).  The host form only counts
+static int sample_begin(gph_engine *e, int cls, int &tms)
+{
+  tms = -1;
+#ifndef GPH_HOSTEMU
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  tms = tm_begin(e, cls);
+#endif
+  (void)e; (void)cls;
+  return 0;
+}
+static void sample_end(gph_engine *e, int cls, int k, int tms)
+{
+#ifndef GPH_HOSTEMU
+  tm_end(e, tms);
+  e->n_launches += k;
+  e->last_which = cls;
+#endif
+  (void)k; (void)tms;
+  e->cls_launches[cls] += 1;
+}
+
+static void rows_free(gph_engine *e, SmRows &b) { eng_free(e, b.d); b = SmRows{}; }
+static int rows_alloc(SmRows &b, size_t esz, int32_t n, int32_t cap)
+{
+  if (dev_alloc((void **)&b.d, esz * (size_t)n * cap)) { b.d = nullptr; return GPH_EHIP; }
+  b.esz = esz; b.n = n; b.cap = cap; b.fill = 0;
+  return 0;
+}
+static void *rows_next(const SmRows &b) { return b.d + b.esz * (size_t)b.n * b.fill; }
+// every row taken since the last fetch into out, contiguous, and the buffer empty again
+static int rows_fetch(gph_engine *e, SmRows &b, void *out, int32_t *rows)
+{
+  *rows = b.fill;
+  if (b.fill > 0) { int rc = d2h(e, out, b.d, b.esz * (size_t)b.n * b.fill); if (rc) return rc; }
+  b.fill = 0;
+  return 0;
+}
+
+static void parts_free(gph_engine *e, SmParts &p) { eng_free(e, p.d_part); p.d_part = nullptr; p.rd = p.chunk = p.nchunks = 0; }
+static int parts_alloc(gph_engine *e, SmParts &p, int32_t rd, int32_t default_chunk)
+{
+  const int chunk = p.chunk_next > 0 ? p.chunk_next : default_chunk;
+  const int nchunks = (int)((e->L + chunk - 1) / chunk);
+  if (dev_alloc((void **)&p.d_part, sizeof(double) * (size_t)rd * nchunks)) { p.d_part = nullptr; return GPH_EHIP; }
+  p.rd = rd; p.chunk = chunk; p.nchunks = nchunks;
+  return 0;
+}
+// the partial rows of a sample into its row, in chunk order (one launch)
+static int parts_fold(gph_engine *e, const SmParts &p, int32_t iteration, double *row)
+{
+#ifdef GPH_HOSTEMU
+  (void)e;
+  for (int c = 0; c < p.rd; c++) gph_fold_column(p.d_part, p.nchunks, p.rd, c, (double)iteration, row);
+#else
+  hipLaunchKernelGGL(k_rows_fold, dim3((unsigned)((p.rd + GPH_FOLD_THREADS - 1) / GPH_FOLD_THREADS)), dim3(GPH_FOLD_THREADS), 0, e->stream,
+                     (const double *)p.d_part, p.nchunks, p.rd, (double)iteration, row);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
+// a chunked sampler's two buffers: partial rows for its L slots, `capacity` rows of rd doubles
+static int chunked_alloc(gph_engine *e, SmParts &p, SmRows &b, int32_t rd, int32_t default_chunk, int32_t capacity)
+{
+  if (parts_alloc(e, p, rd, default_chunk)) return GPH_EHIP;
+  if (rows_alloc(b, sizeof(double), rd, capacity)) { parts_free(e, p); return GPH_EHIP; }
+  return 0;
+}
+// per-locus accumulators [L][ncol] in slot order -> out, row h_orig[j] (the local locus slot j holds) of leading dimension ld
+static int fetch_by_locus(gph_engine *e, const double *d_acc, int ncol, bool column_major, double *out, int64_t ld)
+{
+  const int64_t L = e->L;
+  std::vector<double> acc((size_t)ncol * L);
+  int rc = d2h(e, acc.data(), d_acc, sizeof(double) * acc.size());
+  if (rc) return rc;
+  for (int64_t j = 0; j < L; j++) {
+    double *row = out + (size_t)e->h_orig[j] * ld;
+    for (int c = 0; c < ncol; c++) row[c] = column_major ? acc[(size_t)c * L + j] : acc[(size_t)j * ncol + c];
+  }
+  return 0;
+}
+
 // ---- per-locus posterior summaries (gph_summary.h)
 int gph_engine_locus_summary_enable(gph_engine *e, int32_t on)
 {
   if (!e || !e->loaded) return GPH_ESTATE;
   SETDEV(e);
-  if (e->d_ls) { eng_free(e, e->d_ls); e->d_ls = nullptr; }
-  e->ls_samples = 0;
-  e->ls_ncol = 0;
-  e->ls_names.clear();
+  eng_free(e, e->ls.d);
+  e->ls = {};
   if (!on) return 0;
   const int K = e->cfg.K, B = e->cfg.B, var = e->var_rates;
   const int ncol = gph_ls_columns(K, B, var);
-  if (dev_alloc((void **)&e->d_ls, sizeof(double) * (size_t)ncol * e->L)) { e->d_ls = nullptr; return GPH_EHIP; }
-  e->ls_ncol = ncol;
+  if (dev_alloc((void **)&e->ls.d, sizeof(double) * (size_t)ncol * e->L)) { e->ls.d = nullptr; return GPH_EHIP; }
+  e->ls.ncol = ncol;
   for (const char *q : {"dataLnL", "genLnL", "tmrca"})
-    for (const char *m : {".shift", ".s1", ".s2"}) e->ls_names.push_back(std::string(q) + m);
-  for (int b = 0; b < B; b++) e->ls_names.push_back("nmig." + std::to_string(b));
-  for (int b = 0; b < B; b++) e->ls_names.push_back("pmig." + std::to_string(b));
-  for (int p = 0; p < K; p++) e->ls_names.push_back("ncoal." + std::to_string(p));
-  if (var) for (const char *m : {".shift", ".s1", ".s2"}) e->ls_names.push_back(std::string("rate") + m);
-  return ls_zero(e);
+    for (const char *m : {".shift", ".s1", ".s2"}) e->ls.names.push_back(std::string(q) + m);
+  for (int b = 0; b < B; b++) e->ls.names.push_back("nmig." + std::to_string(b));
+  for (int b = 0; b < B; b++) e->ls.names.push_back("pmig." + std::to_string(b));
+  for (int p = 0; p < K; p++) e->ls.names.push_back("ncoal." + std::to_string(p));
+  if (var) for (const char *m : {".shift", ".s1", ".s2"}) e->ls.names.push_back(std::string("rate") + m);
+  return acc_zero(e, e->ls.d, sizeof(double) * (size_t)ncol * e->L);
 }
 
-// one sample of the current state, queued on the engine's stream.  A mixing commit still owed to the next sweep kernel
-// changes the pages, so it runs first -- unless the proposal was rejected (the host mirror of the chain state, current
-// after an iteration, says so): then there is nothing to commit, as part_sweep finds too.  A deferred synchronizeEvents
-// pass may stay deferred (it corrects event times only)
+// one sample of the current state, queued on the engine's stream
 int gph_engine_locus_summary_sample(gph_engine *e)
 {
-  if (!e || !e->initialized || !e->d_ls) return GPH_ESTATE;
+  if (!e || !e->initialized || !e->ls.d) return GPH_ESTATE;
   SETDEV(e);
-  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
-  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
-  const int first = e->ls_samples == 0;
-  const int L = (int)e->L, ncol = e->ls_ncol, var = e->var_rates;
+  { int rcs = sample_settle(e, SETTLE_PAGES); if (rcs) return rcs; }
+  const int first = e->ls.samples == 0;
+  const int L = (int)e->L, ncol = e->ls.ncol, var = e->var_rates;
+  int tms;
+  { int rcb = sample_begin(e, 13, tms); if (rcb) return rcb; }
 #ifdef GPH_HOSTEMU
   for (int j = 0; j < L; j++)
-    locus_summary_slot(e->dev.pages + (size_t)j * e->lay.page_bytes, e->lay, e->d_ls + j, (size_t)L, ncol, first, var);
-  e->cls_launches[13] += 1;
+    locus_summary_slot(e->dev.pages + (size_t)j * e->lay.page_bytes, e->lay, e->ls.d + j, (size_t)L, ncol, first, var);
 #else
-  { int rcf = flush_pending(e); if (rcf) return rcf; }
-  const int tms = tm_begin(e, 13);
   hipLaunchKernelGGL(k_locus_summary, dim3((unsigned)((L + GPH_LS_THREADS - 1) / GPH_LS_THREADS)), dim3(GPH_LS_THREADS), 0, e->stream,
-                     e->lay, (const char *)e->dev.pages, e->d_ls, L, ncol, first, var);
+                     e->lay, (const char *)e->dev.pages, e->ls.d, L, ncol, first, var);
   HIPCHK(hipGetLastError());
-  tm_end(e, tms);
-  e->n_launches++;
-  e->last_which = 13;
-  e->cls_launches[13] += 1;
 #endif
-  e->ls_samples++;
+  sample_end(e, 13, 1, tms);
+  e->ls.samples++;
   return 0;
 }
 
 int gph_engine_locus_summary_columns(gph_engine *e, int32_t *ncol, int64_t *samples)
 {
   if (!e) return GPH_EARG;
-  if (ncol) *ncol = e->ls_ncol;
-  if (samples) *samples = e->ls_samples;
+  if (ncol) *ncol = e->ls.ncol;
+  if (samples) *samples = e->ls.samples;
   return 0;
 }
 
 int gph_engine_locus_summary_fetch(gph_engine *e, double *out, int64_t ld, int32_t reset)
 {
   if (!e || !out) return GPH_EARG;
-  if (!e->d_ls) return GPH_ESTATE;
-  if (ld < e->ls_ncol) return GPH_EARG;
+  if (!e->ls.d) return GPH_ESTATE;
+  if (ld < e->ls.ncol) return GPH_EARG;
   SETDEV(e);
-  const int64_t L = e->L;
-  const int ncol = e->ls_ncol;
-  std::vector<double> acc((size_t)ncol * L);
-  int rc = d2h(e, acc.data(), e->d_ls, sizeof(double) * acc.size());
-  if (rc) return rc;
-  /* slot j holds local locus h_orig[j] */
-  for (int64_t j = 0; j < L; j++) {
-    double *row = out + (size_t)e->h_orig[j] * ld;
-    for (int c = 0; c < ncol; c++) row[c] = acc[(size_t)c * L + j];
-  }
-  return reset ? ls_zero(e) : 0;
+  int rc = fetch_by_locus(e, e->ls.d, e->ls.ncol, true, out, ld);
+  if (rc || !reset) return rc;
+  e->ls.samples = 0;
+  return acc_zero(e, e->ls.d, sizeof(double) * (size_t)e->ls.ncol * e->L);
 }
 
 const char *gph_engine_locus_summary_column_name(gph_engine *e, int32_t col)
 {
-  if (!e || col < 0 || col >= (int32_t)e->ls_names.size()) return nullptr;
-  return e->ls_names[col].c_str();
+  if (!e || col < 0 || col >= (int32_t)e->ls.names.size()) return nullptr;
+  return e->ls.names[col].c_str();
 }
 
 // ---- genome-wide coalescent and sample-pair statistics per sample (gph_coalstats.h)
@@ -2555,22 +2624,13 @@ int gph_engine_coal_stats_enable(gph_engine *e, int32_t capacity)
   if (!e || !e->loaded) return GPH_ESTATE;
   if (capacity < 0) return GPH_EARG;
   SETDEV(e);
-  if (e->d_cs_part) { eng_free(e, e->d_cs_part); e->d_cs_part = nullptr; }
-  if (e->d_cs_rows) { eng_free(e, e->d_cs_rows); e->d_cs_rows = nullptr; }
-  e->cs_cap = e->cs_fill = e->cs_rd = e->cs_chunk = e->cs_nchunks = e->cs_bd = 0;
+  parts_free(e, e->cs.part);
+  rows_free(e, e->cs.rows);
+  e->cs.bd = 0;
   if (capacity == 0) return 0;
   const int n = e->cfg.n, K = e->cfg.K;
-  const int chunk = e->cs_chunk_next > 0 ? e->cs_chunk_next : GPH_CS_CHUNK;
-  const int rd = gph_cs_row_doubles(n, K);
-  const int nchunks = (int)((e->L + chunk - 1) / chunk);
-  if (dev_alloc((void **)&e->d_cs_part, sizeof(double) * (size_t)rd * nchunks)) { e->d_cs_part = nullptr; return GPH_EHIP; }
-  if (dev_alloc((void **)&e->d_cs_rows, sizeof(double) * (size_t)rd * capacity)) {
-    e->d_cs_rows = nullptr;
-    dev_free(e->d_cs_part);
-    e->d_cs_part = nullptr;
-    return GPH_EHIP;
-  }
-  e->cs_cap = capacity; e->cs_rd = rd; e->cs_chunk = chunk; e->cs_nchunks = nchunks; e->cs_bd = gph_cs_block(n, K);
+  if (chunked_alloc(e, e->cs.part, e->cs.rows, gph_cs_row_doubles(n, K), GPH_CS_CHUNK, capacity)) return GPH_EHIP;
+  e->cs.bd = gph_cs_block(n, K);
   return 0;
 }
 
@@ -2579,53 +2639,43 @@ int gph_engine_coal_stats_enable(gph_engine *e, int32_t capacity)
 int gph_engine_coal_stats_set_chunk(gph_engine *e, int32_t slots)
 {
   if (!e || slots < 0) return GPH_EARG;
-  e->cs_chunk_next = slots;
+  e->cs.part.chunk_next = slots;
   return 0;
 }
 
-// one sample of the current state into the next free row, queued on the engine's stream; ordered against a mixing commit
-// still owed to the next sweep kernel exactly as gph_engine_locus_summary_sample orders itself (the node records are page
-// contents; a deferred synchronizeEvents pass corrects event times only and may stay deferred)
+// one sample of the current state into the next free row, queued on the engine's stream
 int gph_engine_coal_stats_sample(gph_engine *e, int32_t iteration)
 {
-  if (!e || !e->initialized || !e->d_cs_rows) return GPH_ESTATE;
-  if (e->cs_fill >= e->cs_cap) return GPH_EFULL;
+  if (!e || !e->initialized || !e->cs.rows.d) return GPH_ESTATE;
+  if (e->cs.rows.fill >= e->cs.rows.cap) return GPH_EFULL;
   SETDEV(e);
-  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
-  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
-  const int L = (int)e->L, n = e->cfg.n, K = e->cfg.K, B = e->cfg.B, bd = e->cs_bd, rd = e->cs_rd;
+  { int rcs = sample_settle(e, SETTLE_PAGES); if (rcs) return rcs; }
+  const SmParts &p = e->cs.part;
+  const int L = (int)e->L, n = e->cfg.n, K = e->cfg.K, B = e->cfg.B, bd = e->cs.bd;
   const int ntiles = (gph_cs_pairs(n) + bd - 1) / bd;
-  double *row = e->d_cs_rows + (size_t)e->cs_fill * rd;
+  int tms;
+  { int rcb = sample_begin(e, 14, tms); if (rcb) return rcb; }
 #ifdef GPH_HOSTEMU
-  (void)B;
+  (void)K; (void)B;
   std::vector<char> lds;
-  for (int ch = 0; ch < e->cs_nchunks; ch++)
-    for (int t = 0; t < ntiles; t++) coal_stats_workgroup(e->lay, (const char *)e->dev.pages, e->d_cs_part, L, e->cs_chunk, bd, ch, t, lds);
-  for (int c = 0; c < rd; c++) gph_cs_fold_column(e->d_cs_part, e->cs_nchunks, rd, c, (double)iteration, row);
-  e->cls_launches[14] += 1;
+  for (int ch = 0; ch < p.nchunks; ch++)
+    for (int t = 0; t < ntiles; t++) coal_stats_workgroup(e->lay, (const char *)e->dev.pages, p.d_part, L, p.chunk, bd, ch, t, lds);
 #else
-  { int rcf = flush_pending(e); if (rcf) return rcf; }
-  const int tms = tm_begin(e, 14);
-  hipLaunchKernelGGL(k_coal_stats, dim3((unsigned)e->cs_nchunks, (unsigned)ntiles), dim3((unsigned)bd), gph_cs_lds_bytes(n, K, B, bd), e->stream,
-                     e->lay, (const char *)e->dev.pages, e->d_cs_part, L, e->cs_chunk);
+  hipLaunchKernelGGL(k_coal_stats, dim3((unsigned)p.nchunks, (unsigned)ntiles), dim3((unsigned)bd), gph_cs_lds_bytes(n, K, B, bd), e->stream,
+                     e->lay, (const char *)e->dev.pages, p.d_part, L, p.chunk);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_coal_fold, dim3((unsigned)((rd + GPH_CS_FOLD_THREADS - 1) / GPH_CS_FOLD_THREADS)), dim3(GPH_CS_FOLD_THREADS), 0, e->stream,
-                     (const double *)e->d_cs_part, e->cs_nchunks, rd, (double)iteration, row);
-  HIPCHK(hipGetLastError());
-  tm_end(e, tms);
-  e->n_launches += 2;
-  e->last_which = 14;
-  e->cls_launches[14] += 1;
 #endif
-  e->cs_fill++;
+  { int rcf = parts_fold(e, p, iteration, (double *)rows_next(e->cs.rows)); if (rcf) return rcf; }
+  sample_end(e, 14, 2, tms);
+  e->cs.rows.fill++;
   return 0;
 }
 
 int gph_engine_coal_stats_shape(gph_engine *e, int32_t *row_doubles, int32_t *filled, int32_t *n, int32_t *K)
 {
   if (!e) return GPH_EARG;
-  if (row_doubles) *row_doubles = e->cs_rd;
-  if (filled) *filled = e->cs_fill;
+  if (row_doubles) *row_doubles = e->cs.rows.n;
+  if (filled) *filled = e->cs.rows.fill;
   if (n) *n = e->cfg.n;
   if (K) *K = e->cfg.K;
   return 0;
@@ -2634,16 +2684,10 @@ int gph_engine_coal_stats_shape(gph_engine *e, int32_t *row_doubles, int32_t *fi
 int gph_engine_coal_stats_fetch(gph_engine *e, double *out, int32_t max_rows, int32_t *rows)
 {
   if (!e || !rows || max_rows < 0 || (!out && max_rows > 0)) return GPH_EARG;
-  if (!e->d_cs_rows) return GPH_ESTATE;
-  if (max_rows < e->cs_fill) return GPH_EARG;
+  if (!e->cs.rows.d) return GPH_ESTATE;
+  if (max_rows < e->cs.rows.fill) return GPH_EARG;
   SETDEV(e);
-  *rows = e->cs_fill;
-  if (e->cs_fill > 0) {
-    int rc = d2h(e, out, e->d_cs_rows, sizeof(double) * (size_t)e->cs_rd * e->cs_fill);
-    if (rc) return rc;
-  }
-  e->cs_fill = 0;
-  return 0;
+  return rows_fetch(e, e->cs.rows, out, rows);
 }
 
 const char *gph_engine_coal_stats_column_name(gph_engine *e, int32_t col)
@@ -2656,8 +2700,8 @@ const char *gph_engine_coal_stats_column_name(gph_engine *e, int32_t col)
   const int block = (col - CS_FIXED) / npk, q = (col - CS_FIXED) % npk;
   int i = 0, p = q / K;
   while (i < n - 2 && p >= n - 1 - i) { p -= n - 1 - i; i++; }
-  e->cs_name = std::string(block == 0 ? "cnt." : block == 1 ? "first." : "agesum.") + std::to_string(i) + "." + std::to_string(i + 1 + p) + "." + std::to_string(q % K);
-  return e->cs_name.c_str();
+  e->cs.name = std::string(block == 0 ? "cnt." : block == 1 ? "first." : "agesum.") + std::to_string(i) + "." + std::to_string(i + 1 + p) + "." + std::to_string(q % K);
+  return e->cs.name.c_str();
 }
 
 // ---- coalescence and migration statistics per time slice, per sample (gph_timeslices.h)
@@ -2666,10 +2710,9 @@ int gph_engine_time_slices_enable(gph_engine *e, int32_t slices, int32_t capacit
   if (!e || !e->loaded) return GPH_ESTATE;
   if (capacity < 0) return GPH_EARG;
   SETDEV(e);
-  if (e->d_ts_part) { eng_free(e, e->d_ts_part); e->d_ts_part = nullptr; }
-  if (e->d_ts_rows) { eng_free(e, e->d_ts_rows); e->d_ts_rows = nullptr; }
-  e->ts_cap = e->ts_fill = e->ts_rd = e->ts_chunk = e->ts_nchunks = 0;
-  e->ts_shape = GphTsShape{};
+  parts_free(e, e->ts.part);
+  rows_free(e, e->ts.rows);
+  e->ts.shape = GphTsShape{};
   if (capacity == 0) return 0;
   GphTsShape h;
   if (gph_ts_shape(e->lay, slices, h)) {
@@ -2680,18 +2723,9 @@ int gph_engine_time_slices_enable(gph_engine *e, int32_t slices, int32_t capacit
     fprintf(stderr, "gphocs_hip: time slices: %d slices need %d bytes of LDS a workgroup, 65536 at most\n", (int)slices, (int)h.lds_bytes);
     return GPH_EARG;
   }
-  const int chunk = e->ts_chunk_next > 0 ? e->ts_chunk_next : GPH_TS_CHUNK;
-  const int rd = gph_ts_row_doubles(e->cfg.K, e->cfg.B, slices);
-  const int nchunks = (int)((e->L + chunk - 1) / chunk);
-  if (dev_alloc((void **)&e->d_ts_part, sizeof(double) * (size_t)rd * nchunks)) { e->d_ts_part = nullptr; return GPH_EHIP; }
-  if (dev_alloc((void **)&e->d_ts_rows, sizeof(double) * (size_t)rd * capacity)) {
-    e->d_ts_rows = nullptr;
-    dev_free(e->d_ts_part);
-    e->d_ts_part = nullptr;
-    return GPH_EHIP;
-  }
   /* (every cell of a partial row is written by its chunk's workgroups, the root's zero slices included) */
-  e->ts_cap = capacity; e->ts_rd = rd; e->ts_chunk = chunk; e->ts_nchunks = nchunks; e->ts_shape = h;
+  if (chunked_alloc(e, e->ts.part, e->ts.rows, gph_ts_row_doubles(e->cfg.K, e->cfg.B, slices), GPH_TS_CHUNK, capacity)) return GPH_EHIP;
+  e->ts.shape = h;
   return 0;
 }
 
@@ -2699,51 +2733,36 @@ int gph_engine_time_slices_enable(gph_engine *e, int32_t slices, int32_t capacit
 int gph_engine_time_slices_set_chunk(gph_engine *e, int32_t slots)
 {
   if (!e || slots < 0) return GPH_EARG;
-  e->ts_chunk_next = slots;
+  e->ts.part.chunk_next = slots;
   return 0;
 }
 
-// one sample of the current state into the next free row, queued on the engine's stream.  The walkers read event times
-// and the model in the chain state, so more has to be settled first than for gph_engine_coal_stats_sample (node records
-// only): a host-side change of the chain state is pushed, the commit / revert of a decided tau or sample-age proposal
-// still owed to the next evaluate kernel runs (k_tau_finish: one more launch; never owed after a whole
-// gph_engine_iteration_, only between the parts of a stepwise caller), and, as there, the commit of an accepted mixing
-// proposal owed to the next sweep kernel (k_mix_finish).  A deferred synchronizeEvents pass STAYS
-// deferred: the walkers apply its arithmetic to the event times they read (vsync, gph_timeslices.h), so the row is that of
-// the chain as the pass will leave it
+// one sample of the current state into the next free row, queued on the engine's stream.  A deferred synchronizeEvents pass
+// stays deferred: the walkers apply its arithmetic to the event times they read (vsync), so the row is that of the chain as
+// the pass will leave it
 int gph_engine_time_slices_sample(gph_engine *e, int32_t iteration)
 {
-  if (!e || !e->initialized || !e->d_ts_rows) return GPH_ESTATE;
-  if (e->ts_fill >= e->ts_cap) return GPH_EFULL;
+  if (!e || !e->initialized || !e->ts.rows.d) return GPH_ESTATE;
+  if (e->ts.rows.fill >= e->ts.rows.cap) return GPH_EFULL;
   SETDEV(e);
-  PUSH_IF_DIRTY(e);
-  { int rcw = finish_owed(e); if (rcw) return rcw; }
-  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
-  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
-  const int L = (int)e->L, rd = e->ts_rd, vsync = e->sync_pending ? 1 : 0;
-  const GphTsShape &h = e->ts_shape;
-  double *row = e->d_ts_rows + (size_t)e->ts_fill * rd;
+  { int rcs = sample_settle(e, SETTLE_CHAIN); if (rcs) return rcs; }
+  const SmParts &p = e->ts.part;
+  const int L = (int)e->L, vsync = e->sync_pending ? 1 : 0;
+  const GphTsShape &h = e->ts.shape;
+  int tms;
+  { int rcb = sample_begin(e, 15, tms); if (rcb) return rcb; }
 #ifdef GPH_HOSTEMU
   std::vector<char> lds;
-  for (int ch = 0; ch < e->ts_nchunks; ch++)
-    for (int t = 0; t < h.ntiles; t++) time_slices_workgroup(e->lay, h, e->G_h, (const char *)e->dev.pages, e->d_ts_part, L, e->ts_chunk, rd, vsync, ch, t, lds);
-  for (int c = 0; c < rd; c++) gph_ts_fold_column(e->d_ts_part, e->ts_nchunks, rd, c, (double)iteration, row);
-  e->cls_launches[15] += 1;
+  for (int ch = 0; ch < p.nchunks; ch++)
+    for (int t = 0; t < h.ntiles; t++) time_slices_workgroup(e->lay, h, e->G_h, (const char *)e->dev.pages, p.d_part, L, p.chunk, p.rd, vsync, ch, t, lds);
 #else
-  { int rcf = flush_pending(e); if (rcf) return rcf; }
-  const int tms = tm_begin(e, 15);
-  hipLaunchKernelGGL(k_time_slices, dim3((unsigned)e->ts_nchunks, (unsigned)h.ntiles), dim3((unsigned)h.bd), (size_t)h.lds_bytes, e->stream,
-                     e->lay, h, (const GphGlobal *)e->G_d, (const char *)e->dev.pages, e->d_ts_part, L, e->ts_chunk, rd, vsync);
+  hipLaunchKernelGGL(k_time_slices, dim3((unsigned)p.nchunks, (unsigned)h.ntiles), dim3((unsigned)h.bd), (size_t)h.lds_bytes, e->stream,
+                     e->lay, h, (const GphGlobal *)e->G_d, (const char *)e->dev.pages, p.d_part, L, p.chunk, p.rd, vsync);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_time_slices_fold, dim3((unsigned)((rd + GPH_TS_FOLD_THREADS - 1) / GPH_TS_FOLD_THREADS)), dim3(GPH_TS_FOLD_THREADS), 0, e->stream,
-                     (const double *)e->d_ts_part, e->ts_nchunks, rd, (double)iteration, row);
-  HIPCHK(hipGetLastError());
-  tm_end(e, tms);
-  e->n_launches += 2;
-  e->last_which = 15;
-  e->cls_launches[15] += 1;
 #endif
-  e->ts_fill++;
+  { int rcf = parts_fold(e, p, iteration, (double *)rows_next(e->ts.rows)); if (rcf) return rcf; }
+  sample_end(e, 15, 2, tms);
+  e->ts.rows.fill++;
   return 0;
 }
 
@@ -2751,10 +2770,10 @@ int gph_engine_time_slices_shape(gph_engine *e, int32_t *row_doubles, int32_t *f
                                  int32_t *staged_bytes_per_locus)
 {
   if (!e) return GPH_EARG;
-  if (row_doubles) *row_doubles = e->ts_rd;
-  if (filled) *filled = e->ts_fill;
-  if (slices) *slices = e->ts_shape.S;
-  if (staged_bytes_per_locus) *staged_bytes_per_locus = e->ts_shape.img.bytes;
+  if (row_doubles) *row_doubles = e->ts.rows.n;
+  if (filled) *filled = e->ts.rows.fill;
+  if (slices) *slices = e->ts.shape.S;
+  if (staged_bytes_per_locus) *staged_bytes_per_locus = e->ts.shape.img.bytes;
   if (K) *K = e->cfg.K;
   if (B) *B = e->cfg.B;
   return 0;
@@ -2763,26 +2782,20 @@ int gph_engine_time_slices_shape(gph_engine *e, int32_t *row_doubles, int32_t *f
 int gph_engine_time_slices_fetch(gph_engine *e, double *out, int32_t max_rows, int32_t *rows)
 {
   if (!e || !rows || max_rows < 0 || (!out && max_rows > 0)) return GPH_EARG;
-  if (!e->d_ts_rows) return GPH_ESTATE;
-  if (max_rows < e->ts_fill) return GPH_EARG;
+  if (!e->ts.rows.d) return GPH_ESTATE;
+  if (max_rows < e->ts.rows.fill) return GPH_EARG;
   SETDEV(e);
-  *rows = e->ts_fill;
-  if (e->ts_fill > 0) {
-    int rc = d2h(e, out, e->d_ts_rows, sizeof(double) * (size_t)e->ts_rd * e->ts_fill);
-    if (rc) return rc;
-  }
-  e->ts_fill = 0;
-  return 0;
+  return rows_fetch(e, e->ts.rows, out, rows);
 }
 
 const char *gph_engine_time_slices_column_name(gph_engine *e, int32_t col)
 {
-  if (!e || col < 0 || col >= e->ts_rd) return nullptr;
+  if (!e || col < 0 || col >= e->ts.rows.n) return nullptr;
   if (col == 0) return "iter";
-  const int S = e->ts_shape.S, K = e->cfg.K, q = (col - 1) / 2, W = q / S, k = q % S + 1, second = (col - 1) & 1;
+  const int S = e->ts.shape.S, K = e->cfg.K, q = (col - 1) / 2, W = q / S, k = q % S + 1, second = (col - 1) & 1;
   const char *what = W < K ? (second ? "deltaT." : "numCoal.") : (second ? "migT." : "numMig.");
-  e->ts_name = std::string(what) + std::to_string(W < K ? W : W - K) + "." + std::to_string(k);
-  return e->ts_name.c_str();
+  e->ts.name = std::string(what) + std::to_string(W < K ? W : W - K) + "." + std::to_string(k);
+  return e->ts.name.c_str();
 }
 
 // ---- per-locus, per-sample migration ancestry (gph_ancestry.h)
@@ -2791,15 +2804,15 @@ int gph_engine_ancestry_enable(gph_engine *e, int32_t capacity_rows, int64_t max
   if (!e || !e->loaded) return GPH_ESTATE;
   if (capacity_rows < 0) return GPH_EARG;
   SETDEV(e);
-  if (e->d_an_acc) { eng_free(e, e->d_an_acc); e->d_an_acc = nullptr; }
-  if (e->d_an_rows) { eng_free(e, e->d_an_rows); e->d_an_rows = nullptr; }
-  e->an_cap = e->an_fill = e->an_ncol = e->an_ri = 0;
-  e->an_samples = 0;
-  e->an_iters.clear();
-  e->an_shape = GphAnShape{};
+  eng_free(e, e->an.d_acc);
+  e->an.d_acc = nullptr;
+  rows_free(e, e->an.rows);
+  e->an.ncol = 0; e->an.samples = 0;
+  e->an.iters.clear();
+  e->an.shape = GphAnShape{};
   if (capacity_rows == 0) return 0;
   const int n = e->cfg.n, B = e->cfg.B;
-  const int ncol = gph_an_locus_columns(n, B), ri = gph_an_row_ints(n, B);
+  const int ncol = gph_an_locus_columns(n, B);
   const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
   const int64_t need = (int64_t)e->L * ncol * 8;
   if (need > limit) {
@@ -2807,120 +2820,103 @@ int gph_engine_ancestry_enable(gph_engine *e, int32_t capacity_rows, int64_t max
             (long long)need, (long long)e->L, n, 2 * B + 1, (long long)limit);
     return GPH_EFULL;
   }
-  if (dev_alloc((void **)&e->d_an_acc, (size_t)need)) { e->d_an_acc = nullptr; return GPH_EHIP; }
-  if (dev_alloc((void **)&e->d_an_rows, sizeof(uint32_t) * (size_t)ri * capacity_rows)) {
-    e->d_an_rows = nullptr;
-    dev_free(e->d_an_acc);
-    e->d_an_acc = nullptr;
+  if (dev_alloc((void **)&e->an.d_acc, (size_t)need)) { e->an.d_acc = nullptr; return GPH_EHIP; }
+  if (rows_alloc(e->an.rows, sizeof(uint32_t), gph_an_row_ints(n, B), capacity_rows)) {
+    eng_free(e, e->an.d_acc);
+    e->an.d_acc = nullptr;
     return GPH_EHIP;
   }
-  e->an_cap = capacity_rows; e->an_ncol = ncol; e->an_ri = ri;
-  gph_an_shape(e->lay, e->an_shape);
-  return an_zero(e);
+  e->an.ncol = ncol;
+  gph_an_shape(e->lay, e->an.shape);
+  return acc_zero(e, e->an.d_acc, (size_t)need);
 }
 
-// one sample of the current state, queued on the engine's stream; the pages are made current exactly as
-// gph_engine_locus_summary_sample makes them (a mixing commit still owed to the next sweep kernel runs first), and, because
-// the migration ages are read too, the commit / revert of a decided tau or sample-age proposal still owed to the next
-// evaluate kernel (never owed after a whole iteration, only between the parts of a stepwise caller).  A deferred
-// synchronizeEvents pass may stay deferred: it corrects event times only
+// one sample of the current state, queued on the engine's stream
 int gph_engine_ancestry_sample(gph_engine *e, int32_t iteration)
 {
-  if (!e || !e->initialized || !e->d_an_rows) return GPH_ESTATE;
-  if (e->an_fill >= e->an_cap) return GPH_EFULL;
+  if (!e || !e->initialized || !e->an.rows.d) return GPH_ESTATE;
+  if (e->an.rows.fill >= e->an.rows.cap) return GPH_EFULL;
   SETDEV(e);
-  { int rcw = finish_owed(e); if (rcw) return rcw; }
-  if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
-  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
+  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
   const int L = (int)e->L;
-  const GphAnShape &h = e->an_shape;
+  const GphAnShape &h = e->an.shape;
   const int groups = (L + h.G - 1) / h.G;
-  uint32_t *row = e->d_an_rows + (size_t)e->an_fill * e->an_ri;
+  uint32_t *row = (uint32_t *)rows_next(e->an.rows);
+  const size_t row_bytes = sizeof(uint32_t) * (size_t)e->an.rows.n;
+  int tms;
+  { int rcb = sample_begin(e, 16, tms); if (rcb) return rcb; }
 #ifdef GPH_HOSTEMU
-  memset(row, 0, sizeof(uint32_t) * (size_t)e->an_ri);
+  memset(row, 0, row_bytes);
   std::vector<char> lds;
-  for (int w = 0; w < groups; w++) ancestry_workgroup(e->lay, h, (const char *)e->dev.pages, e->d_an_acc, row, L, w, lds);
-  e->cls_launches[16] += 1;
+  for (int w = 0; w < groups; w++) ancestry_workgroup(e->lay, h, (const char *)e->dev.pages, e->an.d_acc, row, L, w, lds);
 #else
-  { int rcf = flush_pending(e); if (rcf) return rcf; }
-  const int tms = tm_begin(e, 16);
-  HIPCHK(hipMemsetAsync(row, 0, sizeof(uint32_t) * (size_t)e->an_ri, e->stream));
+  HIPCHK(hipMemsetAsync(row, 0, row_bytes, e->stream));
   hipLaunchKernelGGL(k_ancestry, dim3((unsigned)groups), dim3((unsigned)h.bd), (size_t)h.lds_bytes, e->stream,
-                     e->lay, h, (const char *)e->dev.pages, e->d_an_acc, row, L);
+                     e->lay, h, (const char *)e->dev.pages, e->an.d_acc, row, L);
   HIPCHK(hipGetLastError());
-  tm_end(e, tms);
-  e->n_launches++;
-  e->last_which = 16;
-  e->cls_launches[16] += 1;
 #endif
-  e->an_iters.push_back(iteration);
-  e->an_fill++;
-  e->an_samples++;
+  sample_end(e, 16, 1, tms);
+  e->an.iters.push_back(iteration);
+  e->an.rows.fill++;
+  e->an.samples++;
   return 0;
 }
 
 int gph_engine_ancestry_shape(gph_engine *e, int32_t *locus_columns, int32_t *row_ints, int64_t *samples, int32_t *rows_held)
 {
   if (!e) return GPH_EARG;
-  if (locus_columns) *locus_columns = e->an_ncol;
-  if (row_ints) *row_ints = e->an_ri;
-  if (samples) *samples = e->an_samples;
-  if (rows_held) *rows_held = e->an_fill;
+  if (locus_columns) *locus_columns = e->an.ncol;
+  if (row_ints) *row_ints = e->an.rows.n;
+  if (samples) *samples = e->an.samples;
+  if (rows_held) *rows_held = e->an.rows.fill;
   return 0;
 }
 
 int gph_engine_ancestry_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset)
 {
   if (!e || !out) return GPH_EARG;
-  if (!e->d_an_acc) return GPH_ESTATE;
-  if (ld < e->an_ncol) return GPH_EARG;
+  if (!e->an.d_acc) return GPH_ESTATE;
+  if (ld < e->an.ncol) return GPH_EARG;
   SETDEV(e);
-  const int64_t L = e->L;
-  const int ncol = e->an_ncol;
-  std::vector<double> acc((size_t)ncol * L);
-  int rc = d2h(e, acc.data(), e->d_an_acc, sizeof(double) * acc.size());
-  if (rc) return rc;
-  /* slot j holds local locus h_orig[j] */
-  for (int64_t j = 0; j < L; j++) memcpy(out + (size_t)e->h_orig[j] * ld, acc.data() + (size_t)j * ncol, sizeof(double) * ncol);
-  return reset ? an_zero(e) : 0;
+  int rc = fetch_by_locus(e, e->an.d_acc, e->an.ncol, false, out, ld);
+  if (rc || !reset) return rc;
+  e->an.samples = 0;
+  return acc_zero(e, e->an.d_acc, sizeof(double) * (size_t)e->an.ncol * e->L);
 }
 
 int gph_engine_ancestry_fetch_rows(gph_engine *e, int32_t *iters, int32_t *out, int64_t ld, int32_t max_rows, int32_t *rows)
 {
   if (!e || !rows || max_rows < 0 || ((!out || !iters) && max_rows > 0)) return GPH_EARG;
-  if (!e->d_an_rows) return GPH_ESTATE;
-  if (max_rows < e->an_fill || (e->an_fill > 0 && ld < e->an_ri)) return GPH_EARG;
+  const SmRows &b = e->an.rows;
+  if (!b.d) return GPH_ESTATE;
+  if (max_rows < b.fill || (b.fill > 0 && ld < b.n)) return GPH_EARG;
   SETDEV(e);
-  *rows = e->an_fill;
-  if (e->an_fill > 0) {
-    std::vector<uint32_t> tmp((size_t)e->an_ri * e->an_fill);
-    int rc = d2h(e, tmp.data(), e->d_an_rows, sizeof(uint32_t) * tmp.size());
-    if (rc) return rc;
-    for (int32_t r = 0; r < e->an_fill; r++) {
-      iters[r] = e->an_iters[(size_t)r];
-      memcpy(out + (size_t)r * ld, tmp.data() + (size_t)r * e->an_ri, sizeof(uint32_t) * (size_t)e->an_ri);
-    }
+  std::vector<uint32_t> tmp((size_t)b.n * b.fill);
+  int rc = rows_fetch(e, e->an.rows, tmp.data(), rows);
+  if (rc) return rc;
+  for (int32_t r = 0; r < *rows; r++) {
+    iters[r] = e->an.iters[(size_t)r];
+    memcpy(out + (size_t)r * ld, tmp.data() + (size_t)r * b.n, sizeof(uint32_t) * (size_t)b.n);
   }
-  e->an_fill = 0;
-  e->an_iters.clear();
+  e->an.iters.clear();
   return 0;
 }
 
 const char *gph_engine_ancestry_column_name(gph_engine *e, int32_t which, int32_t col)
 {
-  if (!e || col < 0 || e->an_cap == 0) return nullptr;
+  if (!e || col < 0 || e->an.rows.cap == 0) return nullptr;
   const int n = e->cfg.n, B = e->cfg.B;
   if (which == 0) {
-    if (col >= e->an_ncol) return nullptr;
+    if (col >= e->an.ncol) return nullptr;
     const int blk = col / n, i = col % n;
-    e->an_name = blk >= 2 * B ? "any." + std::to_string(i)
+    e->an.name = blk >= 2 * B ? "any." + std::to_string(i)
                               : std::string(blk < B ? "cnt." : "age.") + std::to_string(blk % (B > 0 ? B : 1)) + "." + std::to_string(i);
   } else if (which == 1) {
-    if (col >= e->an_ri) return nullptr;
+    if (col >= e->an.rows.n) return nullptr;
     const int blk = col / n, i = col % n;
-    e->an_name = blk == 0 ? "any." + std::to_string(i) : "hit." + std::to_string(blk - 1) + "." + std::to_string(i);
+    e->an.name = blk == 0 ? "any." + std::to_string(i) : "hit." + std::to_string(blk - 1) + "." + std::to_string(i);
   } else return nullptr;
-  return e->an_name.c_str();
+  return e->an.name.c_str();
 }
 
 } // extern "C"

@@ -76,13 +76,35 @@ static int write_locus_summary(const std::string &path, bool header, const gph_c
   return GPH_OK;
 }
 
-// ---- coalescent / sample-pair statistics (`G-PhoCS-hip -s PREFIX`): rank r's raw rows travel through the binary file
-// PREFIX.coal.part<r> -- a header (magic, n, K, doubles per row, loci of all ranks, the sample and population names), one
-// record of row_doubles + 1 doubles per sample (the engine's raw row, then logPrior) and, written when the rank closes its
-// part, the number of records: a part without that trailer, or whose size does not match it, is refused
+// ---- the part files of the statistics samplers.  Rank r's raw rows travel through a binary file PREFIX<suffix><r>: a header
+// (magic, a few 32-bit integers, for coal stats the loci of all ranks as int64, the byte count of the names and the names,
+// NUL-separated), one record per sample and, written when the rank closes its part, a trailer: the number of records (and,
+// for ancestry, the number of bytes of text that sit between the records and the trailer).  A part without that trailer, or
+// whose size does not match it, is refused.
+//   coal stats  PREFIX.coal.part<r>      n, K, doubles per row | L | n sample names as printed, K population names | row, logPrior
+//   time slices PREFIX.slices.part<r>    S, K, B, doubles per row | K population names, B "src->tgt" band names | row
+//   ancestry    PREFIX.ancestry.part<r>  n, B, integers per row | n sample names, B band names | iteration, row (32-bit integers)
 namespace {
-const char CS_MAGIC[8] = {'G', 'P', 'H', 'C', 'S', '1', '\n', 0};
-std::string cs_part_path(const char *prefix, int r) { return std::string(prefix) + ".coal.part" + std::to_string(r); }
+struct PartFormat {
+  char magic[8];
+  const char *suffix;
+  int nh;                               /* header integers */
+  bool (*valid)(const int32_t *h);
+  bool has_L;                           /* an int64 follows them */
+  int (*names)(const int32_t *h);       /* names expected */
+  int (*len)(const int32_t *h);         /* elements per record */
+  int kept;                             /* trailing elements of a record that are rank 0's (coal stats: logPrior), like element 0 */
+  bool text;                            /* trailer: count, text bytes */
+};
+const PartFormat CS_PART = {{'G', 'P', 'H', 'C', 'S', '1', '\n', 0}, ".coal.part", 3, [](const int32_t *h) { return h[0] >= 2 && h[1] >= 1 && h[2] > 0; }, true,
+                            [](const int32_t *h) { return h[0] + h[1]; }, [](const int32_t *h) { return h[2] + 1; }, 1, false};
+const PartFormat TS_PART = {{'G', 'P', 'H', 'T', 'S', '1', '\n', 0}, ".slices.part", 4,
+                            [](const int32_t *h) { return h[0] >= 1 && h[1] >= 1 && h[2] >= 0 && h[3] == 1 + 2 * h[0] * (h[1] + h[2]); }, false,
+                            [](const int32_t *h) { return h[1] + h[2]; }, [](const int32_t *h) { return h[3]; }, 0, false};
+const PartFormat AN_PART = {{'G', 'P', 'H', 'A', 'N', '1', '\n', 0}, ".ancestry.part", 3, [](const int32_t *h) { return h[0] >= 1 && h[1] >= 0 && h[2] == h[0] * (h[1] + 1); }, false,
+                            [](const int32_t *h) { return h[0] + h[1]; }, [](const int32_t *h) { return h[2] + 1; }, 0, true};
+std::string part_path(const PartFormat &F, const char *prefix, int r) { return std::string(prefix) + F.suffix + std::to_string(r); }
+void remove_parts(const PartFormat &F, const char *prefix, int ranks) { for (int r = 0; r < ranks; r++) remove(part_path(F, prefix, r).c_str()); }
 
 // rows of the device buffer when the caller names none: 64 samples, fewer when a row is large (the widest variant, 200
 // leaves x 39 populations, has rows of 18.6 MB), so that the buffer -- and its host copy -- stay within 256 MB
@@ -92,74 +114,77 @@ int32_t cs_default_rows(int32_t row_doubles)
   return (int32_t)(fit < 1 ? 1 : fit > 64 ? 64 : fit);
 }
 
-// the parts of `ranks` ranks, read sample by sample: next() hands out the ranks' records added in rank order (counts
-// added, sums added rank 0 first; the iteration and logPrior are rank 0's)
-struct CsReader {
+// the parts of `ranks` ranks (records of T), read sample by sample: next() hands out the ranks' records added in rank
+// order (counts added, sums added rank 0 first; element 0, the iteration, and the kept tail are rank 0's)
+template <typename T> struct PartReader {
+  const PartFormat &F;
   std::vector<FILE *> f;
-  int32_t n = 0, K = 0, rd = 0;
+  std::vector<long> text_at;
+  std::vector<int64_t> text_bytes;
+  int32_t hdr[4] = {0, 0, 0, 0};
+  int len = 0;
   int64_t L = 0, samples = 0;
-  std::vector<std::string> names;     /* n sample names as printed, then K population names */
-  std::vector<double> tmp;
-  ~CsReader() { for (FILE *x : f) if (x) fclose(x); }
+  std::vector<std::string> names;
+  std::vector<T> tmp;
+  explicit PartReader(const PartFormat &fmt) : F(fmt) {}
+  ~PartReader() { for (FILE *x : f) if (x) fclose(x); }
   bool open(const char *prefix, int ranks)
   {
     for (int r = 0; r < ranks; r++) {
-      const std::string path = cs_part_path(prefix, r);
+      const std::string path = part_path(F, prefix, r);
       FILE *x = fopen(path.c_str(), "rb");
       f.push_back(x);
       char magic[8];
-      int32_t hdr[3], nbytes = 0;
-      int64_t Lr = 0, count = -1;
-      bool ok = x && fread(magic, 1, 8, x) == 8 && !memcmp(magic, CS_MAGIC, 8) && fread(hdr, 4, 3, x) == 3 && fread(&Lr, 8, 1, x) == 1 &&
-                fread(&nbytes, 4, 1, x) == 1 && nbytes >= 0 && hdr[0] >= 2 && hdr[1] >= 1 && hdr[2] > 0;
+      int32_t h[4] = {0, 0, 0, 0}, nbytes = 0;
+      int64_t Lr = 0, tail[2] = {-1, 0};
+      bool ok = x && fread(magic, 1, 8, x) == 8 && !memcmp(magic, F.magic, 8) && fread(h, 4, (size_t)F.nh, x) == (size_t)F.nh &&
+                (!F.has_L || fread(&Lr, 8, 1, x) == 1) && fread(&nbytes, 4, 1, x) == 1 && nbytes >= 0 && F.valid(h);
       std::vector<std::string> nm;
       if (ok) {
         std::vector<char> buf((size_t)nbytes + 1, 0);
         ok = fread(buf.data(), 1, (size_t)nbytes, x) == (size_t)nbytes;
         for (size_t at = 0; ok && at < (size_t)nbytes; at += strlen(buf.data() + at) + 1) nm.push_back(buf.data() + at);
-        ok = ok && (int)nm.size() == hdr[0] + hdr[1];
+        ok = ok && (int)nm.size() == F.names(h);
       }
+      long body = 0;
       if (ok) {
-        /* header | count records | count */
-        const long body = ftell(x);
-        ok = body > 0 && fseek(x, -8, SEEK_END) == 0;
-        const long tail = ok ? ftell(x) : 0;
-        ok = ok && fread(&count, 8, 1, x) == 1 && count >= 0 && tail - body == (long)(count * (int64_t)(hdr[2] + 1) * 8) && fseek(x, body, SEEK_SET) == 0;
+        /* header | count records | [text |] count [, text bytes] */
+        const int tl = F.text ? 2 : 1;
+        body = ftell(x);
+        ok = body > 0 && fseek(x, -8 * tl, SEEK_END) == 0;
+        const long end = ok ? ftell(x) : 0;
+        ok = ok && fread(tail, 8, (size_t)tl, x) == (size_t)tl && tail[0] >= 0 && tail[1] >= 0 &&
+             end - body == (long)(tail[0] * (int64_t)F.len(h) * (int64_t)sizeof(T) + tail[1]) && fseek(x, body, SEEK_SET) == 0;
       }
       if (!ok) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); return false; }
-      if (r == 0) { n = hdr[0]; K = hdr[1]; rd = hdr[2]; L = Lr; samples = count; names = nm; }
-      else if (hdr[0] != n || hdr[1] != K || hdr[2] != rd || count != samples) { fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", path.c_str()); return false; }
+      if (r == 0) { memcpy(hdr, h, sizeof hdr); len = F.len(h); L = Lr; samples = tail[0]; names = nm; }
+      else if (memcmp(hdr, h, sizeof hdr) || tail[0] != samples) { fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", path.c_str()); return false; }
+      text_at.push_back(body + (long)(tail[0] * (int64_t)len * (int64_t)sizeof(T)));
+      text_bytes.push_back(tail[1]);
     }
-    tmp.resize((size_t)rd + 1);
+    tmp.resize((size_t)len);
     return true;
   }
-  bool next(std::vector<double> &rec)
+  bool next(std::vector<T> &rec)
   {
-    rec.resize((size_t)rd + 1);
+    rec.resize((size_t)len);
     for (size_t r = 0; r < f.size(); r++) {
-      std::vector<double> &into = r == 0 ? rec : tmp;
-      if (fread(into.data(), sizeof(double), into.size(), f[r]) != into.size()) return false;
-      if (r > 0) for (int c = 1; c < rd; c++) rec[c] = rec[c] + tmp[c];
+      std::vector<T> &into = r == 0 ? rec : tmp;
+      if (fread(into.data(), sizeof(T), into.size(), f[r]) != into.size()) return false;
+      if (r > 0) for (int c = 1; c < len - F.kept; c++) rec[c] = rec[c] + tmp[c];
     }
     return true;
   }
 };
-}   // namespace
 
-extern "C" int gph_coal_stats_discard(const char *prefix, int32_t ranks)
-{
-  if (!prefix) return GPH_EARG;
-  for (int r = 0; r < ranks; r++) remove(cs_part_path(prefix, r).c_str());
-  return GPH_OK;
-}
-
-extern "C" int gph_coal_stats_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles)
+// every sample's combined record of a part set of doubles into out ([max_rows][*row_doubles]); out == nullptr: the shape only
+int combined(const PartFormat &F, const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles)
 {
   if (!prefix || ranks < 1 || !rows || !row_doubles) return GPH_EARG;
-  CsReader R;
+  PartReader<double> R(F);
   if (!R.open(prefix, ranks)) return GPH_EARG;
   *rows = R.samples;
-  *row_doubles = R.rd + 1;
+  *row_doubles = R.len;
   if (!out) return GPH_OK;
   if (max_rows < R.samples) return GPH_EARG;
   std::vector<double> rec;
@@ -168,6 +193,20 @@ extern "C" int gph_coal_stats_combined(const char *prefix, int32_t ranks, double
     memcpy(out + (size_t)i * rec.size(), rec.data(), sizeof(double) * rec.size());
   }
   return GPH_OK;
+}
+}   // namespace
+
+// ---- coalescent / sample-pair statistics (`G-PhoCS-hip -s PREFIX`)
+extern "C" int gph_coal_stats_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  remove_parts(CS_PART, prefix, ranks);
+  return GPH_OK;
+}
+
+extern "C" int gph_coal_stats_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles)
+{
+  return combined(CS_PART, prefix, ranks, out, max_rows, rows, row_doubles);
 }
 
 extern "C" int gph_coal_stats_write(const char *prefix, int32_t ranks)
@@ -178,9 +217,9 @@ extern "C" int gph_coal_stats_write(const char *prefix, int32_t ranks)
   std::vector<FILE *> out;
   bool ok;
   {
-    CsReader R;
+    PartReader<double> R(CS_PART);
     ok = R.open(prefix, ranks);
-    const int n = R.n, K = R.K, rd = R.rd, npk = n * (n - 1) / 2 * K;
+    const int n = R.hdr[0], K = R.hdr[1], rd = R.hdr[2], npk = n * (n - 1) / 2 * K;
     /* every output file open at once (1 + 3 K of them), so that the parts are read once, sample by sample */
     if (ok) {
       paths.push_back(std::string(prefix) + ".coal.tsv");
@@ -241,89 +280,19 @@ extern "C" int gph_coal_stats_write(const char *prefix, int32_t ranks)
 }
 
 
-// ---- time-sliced statistics (`-s PREFIX --time-slices S`): rank r's raw rows travel through PREFIX.slices.part<r> -- a
-// header (magic, S, K, B, doubles per row, the population names and the bands' "src->tgt" names), one record of
-// row_doubles doubles per sample and, written when the rank closes its part, the number of records
-namespace {
-const char TS_MAGIC[8] = {'G', 'P', 'H', 'T', 'S', '1', '\n', 0};
-std::string ts_part_path(const char *prefix, int r) { return std::string(prefix) + ".slices.part" + std::to_string(r); }
-
-struct TsReader {
-  std::vector<FILE *> f;
-  int32_t S = 0, K = 0, B = 0, rd = 0;
-  int64_t samples = 0;
-  std::vector<std::string> names;     /* K population names, then B band names */
-  std::vector<double> tmp;
-  ~TsReader() { for (FILE *x : f) if (x) fclose(x); }
-  bool open(const char *prefix, int ranks)
-  {
-    for (int r = 0; r < ranks; r++) {
-      const std::string path = ts_part_path(prefix, r);
-      FILE *x = fopen(path.c_str(), "rb");
-      f.push_back(x);
-      char magic[8];
-      int32_t hdr[4], nbytes = 0;
-      int64_t count = -1;
-      bool ok = x && fread(magic, 1, 8, x) == 8 && !memcmp(magic, TS_MAGIC, 8) && fread(hdr, 4, 4, x) == 4 && fread(&nbytes, 4, 1, x) == 1 &&
-                nbytes >= 0 && hdr[0] >= 1 && hdr[1] >= 1 && hdr[2] >= 0 && hdr[3] == 1 + 2 * hdr[0] * (hdr[1] + hdr[2]);
-      std::vector<std::string> nm;
-      if (ok) {
-        std::vector<char> buf((size_t)nbytes + 1, 0);
-        ok = fread(buf.data(), 1, (size_t)nbytes, x) == (size_t)nbytes;
-        for (size_t at = 0; ok && at < (size_t)nbytes; at += strlen(buf.data() + at) + 1) nm.push_back(buf.data() + at);
-        ok = ok && (int)nm.size() == hdr[1] + hdr[2];
-      }
-      if (ok) {
-        const long body = ftell(x);
-        ok = body > 0 && fseek(x, -8, SEEK_END) == 0;
-        const long tail = ok ? ftell(x) : 0;
-        ok = ok && fread(&count, 8, 1, x) == 1 && count >= 0 && tail - body == (long)(count * (int64_t)hdr[3] * 8) && fseek(x, body, SEEK_SET) == 0;
-      }
-      if (!ok) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); return false; }
-      if (r == 0) { S = hdr[0]; K = hdr[1]; B = hdr[2]; rd = hdr[3]; samples = count; names = nm; }
-      else if (hdr[0] != S || hdr[1] != K || hdr[2] != B || count != samples) { fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", path.c_str()); return false; }
-    }
-    tmp.resize((size_t)rd);
-    return true;
-  }
-  /* the ranks' records of the next sample, added in rank order (the iteration is rank 0's) */
-  bool next(std::vector<double> &rec)
-  {
-    rec.resize((size_t)rd);
-    for (size_t r = 0; r < f.size(); r++) {
-      std::vector<double> &into = r == 0 ? rec : tmp;
-      if (fread(into.data(), sizeof(double), into.size(), f[r]) != into.size()) return false;
-      if (r > 0) for (int c = 1; c < rd; c++) rec[c] = rec[c] + tmp[c];
-    }
-    return true;
-  }
-};
-}   // namespace
-
+// ---- time-sliced statistics (`-s PREFIX --time-slices S`)
 // the parts, and PREFIX.slices.tsv should it exist already (the run failed after it was written: a failed run leaves none)
 extern "C" int gph_time_slices_discard(const char *prefix, int32_t ranks)
 {
   if (!prefix) return GPH_EARG;
-  for (int r = 0; r < ranks; r++) remove(ts_part_path(prefix, r).c_str());
+  remove_parts(TS_PART, prefix, ranks);
   unlink((std::string(prefix) + ".slices.tsv").c_str());   /* (a file only: whatever else sits under that name is not ours) */
   return GPH_OK;
 }
 
 extern "C" int gph_time_slices_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles)
 {
-  if (!prefix || ranks < 1 || !rows || !row_doubles) return GPH_EARG;
-  TsReader R;
-  if (!R.open(prefix, ranks)) return GPH_EARG;
-  *rows = R.samples;
-  *row_doubles = R.rd;
-  if (!out) return GPH_OK;
-  if (max_rows < R.samples) return GPH_EARG;
-  std::vector<double> rec;
-  for (int64_t i = 0; i < R.samples; i++) {
-    if (!R.next(rec)) return GPH_EARG;
-    memcpy(out + (size_t)i * rec.size(), rec.data(), sizeof(double) * rec.size());
-  }
-  return GPH_OK;
+  return combined(TS_PART, prefix, ranks, out, max_rows, rows, row_doubles);
 }
 
 extern "C" int gph_time_slices_write(const char *prefix, int32_t ranks)
@@ -333,15 +302,16 @@ extern "C" int gph_time_slices_write(const char *prefix, int32_t ranks)
   FILE *out = nullptr;
   bool ok;
   {
-    TsReader R;
+    PartReader<double> R(TS_PART);
     ok = R.open(prefix, ranks);
+    const int S = R.hdr[0], K = R.hdr[1], B = R.hdr[2];
     if (ok && !(out = fopen(path.c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s\n", path.c_str()); ok = false; }
     if (ok) {
       /* the partition columns of printCoalStats (GPhoCS.c:927-935), then the bands' */
       fprintf(out, "iter");
-      for (int q = 0; q < R.K + R.B; q++)
-        for (int k = 1; k <= R.S; k++) {
-          if (q < R.K) fprintf(out, "\tnumCoal_%s:%d\tdeltaT_%s:%d", R.names[q].c_str(), k, R.names[q].c_str(), k);
+      for (int q = 0; q < K + B; q++)
+        for (int k = 1; k <= S; k++) {
+          if (q < K) fprintf(out, "\tnumCoal_%s:%d\tdeltaT_%s:%d", R.names[q].c_str(), k, R.names[q].c_str(), k);
           else fprintf(out, "\tnumMig_%s:%d\tmigT_%s:%d", R.names[q].c_str(), k, R.names[q].c_str(), k);
         }
       fprintf(out, "\n");
@@ -349,90 +319,23 @@ extern "C" int gph_time_slices_write(const char *prefix, int32_t ranks)
       for (int64_t s = 0; s < R.samples && ok; s++) {
         if (!R.next(rec)) { fprintf(stderr, "gphocs_hip: a part of %s ended early\n", path.c_str()); ok = false; break; }
         fprintf(out, "%7d", (int)rec[0]);
-        for (int c = 1; c < R.rd; c += 2) fprintf(out, "\t%9d\t%8f", (int)rec[c], rec[c + 1]);   /* GPhoCS.c:1005 */
+        for (int c = 1; c < R.len; c += 2) fprintf(out, "\t%9d\t%8f", (int)rec[c], rec[c + 1]);   /* GPhoCS.c:1005 */
         fprintf(out, "\n");
       }
     }
     if (out && (ferror(out) | fclose(out)) != 0) { fprintf(stderr, "gphocs_hip: writing %s failed\n", path.c_str()); ok = false; }
   }
-  for (int r = 0; r < ranks; r++) remove(ts_part_path(prefix, r).c_str());
+  remove_parts(TS_PART, prefix, ranks);
   if (!ok && out) remove(path.c_str());
   return ok ? GPH_OK : GPH_EARG;
 }
 
-// ---- migration ancestry (`--ancestry PREFIX`): rank r keeps PREFIX.ancestry.part<r> -- a header (magic, n, B, integers per
-// row, the sample names as printed and the bands' "src->tgt" names), one record of 1 + row_ints 32-bit integers per sample
-// (the iteration, then the engine's row) and, written when the rank closes its part, its rows of the per-locus table as
-// text, the number of records and the number of text bytes: a part without that trailer, or whose size does not match it,
-// is refused
-namespace {
-const char AN_MAGIC[8] = {'G', 'P', 'H', 'A', 'N', '1', '\n', 0};
-std::string an_part_path(const char *prefix, int r) { return std::string(prefix) + ".ancestry.part" + std::to_string(r); }
-
-struct AnReader {
-  std::vector<FILE *> f;
-  std::vector<long> text_at;
-  std::vector<int64_t> text_bytes;
-  int32_t n = 0, B = 0, ri = 0;
-  int64_t samples = 0;
-  std::vector<std::string> names;     /* n sample names, then B band names */
-  std::vector<int32_t> tmp;
-  ~AnReader() { for (FILE *x : f) if (x) fclose(x); }
-  bool open(const char *prefix, int ranks)
-  {
-    for (int r = 0; r < ranks; r++) {
-      const std::string path = an_part_path(prefix, r);
-      FILE *x = fopen(path.c_str(), "rb");
-      f.push_back(x);
-      char magic[8];
-      int32_t hdr[3], nbytes = 0;
-      int64_t tail[2] = {-1, -1};
-      bool ok = x && fread(magic, 1, 8, x) == 8 && !memcmp(magic, AN_MAGIC, 8) && fread(hdr, 4, 3, x) == 3 && fread(&nbytes, 4, 1, x) == 1 &&
-                nbytes >= 0 && hdr[0] >= 1 && hdr[1] >= 0 && hdr[2] == hdr[0] * (hdr[1] + 1);
-      std::vector<std::string> nm;
-      if (ok) {
-        std::vector<char> buf((size_t)nbytes + 1, 0);
-        ok = fread(buf.data(), 1, (size_t)nbytes, x) == (size_t)nbytes;
-        for (size_t at = 0; ok && at < (size_t)nbytes; at += strlen(buf.data() + at) + 1) nm.push_back(buf.data() + at);
-        ok = ok && (int)nm.size() == hdr[0] + hdr[1];
-      }
-      long body = 0;
-      if (ok) {
-        /* header | count records | text | count, text bytes */
-        body = ftell(x);
-        ok = body > 0 && fseek(x, -16, SEEK_END) == 0;
-        const long end = ok ? ftell(x) : 0;
-        ok = ok && fread(tail, 8, 2, x) == 2 && tail[0] >= 0 && tail[1] >= 0 &&
-             end - body == (long)(tail[0] * (int64_t)(hdr[2] + 1) * 4 + tail[1]) && fseek(x, body, SEEK_SET) == 0;
-      }
-      if (!ok) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); return false; }
-      if (r == 0) { n = hdr[0]; B = hdr[1]; ri = hdr[2]; samples = tail[0]; names = nm; }
-      else if (hdr[0] != n || hdr[1] != B || tail[0] != samples) { fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", path.c_str()); return false; }
-      text_at.push_back(body + (long)(tail[0] * (int64_t)(hdr[2] + 1) * 4));
-      text_bytes.push_back(tail[1]);
-    }
-    tmp.resize((size_t)ri + 1);
-    return true;
-  }
-  /* the ranks' records of the next sample, added (the iteration is rank 0's) */
-  bool next(std::vector<int32_t> &rec)
-  {
-    rec.resize((size_t)ri + 1);
-    for (size_t r = 0; r < f.size(); r++) {
-      std::vector<int32_t> &into = r == 0 ? rec : tmp;
-      if (fread(into.data(), 4, into.size(), f[r]) != into.size()) return false;
-      if (r > 0) for (int c = 1; c <= ri; c++) rec[c] += tmp[c];
-    }
-    return true;
-  }
-};
-}   // namespace
-
+// ---- migration ancestry (`--ancestry PREFIX`): the text behind a part's records is the rank's rows of the per-locus table
 // the parts, and the two files should they exist already (the run failed after they were written: a failed run leaves none)
 extern "C" int gph_ancestry_discard(const char *prefix, int32_t ranks)
 {
   if (!prefix) return GPH_EARG;
-  for (int r = 0; r < ranks; r++) remove(an_part_path(prefix, r).c_str());
+  remove_parts(AN_PART, prefix, ranks);
   unlink((std::string(prefix) + ".loci.tsv").c_str());      /* (files only: whatever else sits under these names is not ours) */
   unlink((std::string(prefix) + ".samples.tsv").c_str());
   return GPH_OK;
@@ -445,12 +348,12 @@ extern "C" int gph_ancestry_write(const char *prefix, int32_t ranks)
   FILE *out[2] = {nullptr, nullptr};
   bool ok;
   {
-    AnReader R;
+    PartReader<int32_t> R(AN_PART);
     ok = R.open(prefix, ranks);
     for (int k = 0; k < 2 && ok; k++)
       if (!(out[k] = fopen(paths[k].c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s\n", paths[k].c_str()); ok = false; }
     if (ok) {
-      const int n = R.n, B = R.B;
+      const int n = R.hdr[0], B = R.hdr[1];
       fprintf(out[1], "iter");
       for (int i = 0; i < n; i++) fprintf(out[1], "\tany_%s#%d", R.names[i].c_str(), i);
       for (int b = 0; b < B; b++)
@@ -460,7 +363,7 @@ extern "C" int gph_ancestry_write(const char *prefix, int32_t ranks)
       for (int64_t s = 0; s < R.samples && ok; s++) {
         if (!R.next(rec)) { fprintf(stderr, "gphocs_hip: a part of %s ended early\n", paths[1].c_str()); ok = false; break; }
         fprintf(out[1], "%7d", (int)rec[0]);
-        for (int c = 1; c <= R.ri; c++) fprintf(out[1], "\t%9d", (int)rec[c]);
+        for (int c = 1; c < R.len; c++) fprintf(out[1], "\t%9d", (int)rec[c]);
         fprintf(out[1], "\n");
       }
       fprintf(out[0], "locus\tname\tleaf\tsample\tsamples\tpAny");
@@ -474,16 +377,72 @@ extern "C" int gph_ancestry_write(const char *prefix, int32_t ranks)
           ok = fread(buf.data(), 1, want, R.f[r]) == want && fwrite(buf.data(), 1, want, out[0]) == want;
           left -= (int64_t)want;
         }
-        if (!ok) fprintf(stderr, "gphocs_hip: copying the rows of %s failed\n", an_part_path(prefix, (int)r).c_str());
+        if (!ok) fprintf(stderr, "gphocs_hip: copying the rows of %s failed\n", part_path(AN_PART, prefix, (int)r).c_str());
       }
     }
     for (int k = 0; k < 2; k++)
       if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s failed\n", paths[k].c_str()); ok = false; }
   }
-  for (int r = 0; r < ranks; r++) remove(an_part_path(prefix, r).c_str());
+  remove_parts(AN_PART, prefix, ranks);
   if (!ok) for (int k = 0; k < 2; k++) if (out[k]) remove(paths[k].c_str());
   return ok ? GPH_OK : GPH_EARG;
 }
+
+// the names a part's header carries, and writing one
+namespace {
+// the leaves' names as the statistics files print them: the second haploid of a diploid has no name of its own and takes
+// the previous sample's, "NA" without one (GPhoCS.c:942-953)
+std::vector<std::string> leaf_names(const gph_control *C, const gph_config &cfg)
+{
+  std::vector<std::string> v;
+  for (int s = 0; s < cfg.n; s++) {
+    const char *nm = gph_control_sample_name(C, s);
+    if (!nm || !nm[0]) { const char *pv = s > 0 ? gph_control_sample_name(C, s - 1) : nullptr; nm = pv && pv[0] ? pv : "NA"; }
+    v.push_back(nm);
+  }
+  return v;
+}
+std::vector<std::string> pop_names(const gph_control *C, const gph_config &cfg)
+{
+  std::vector<std::string> v;
+  for (int p = 0; p < cfg.K; p++) v.push_back(gph_control_pop_name(C, p));
+  return v;
+}
+std::vector<std::string> band_names(const gph_control *C, const gph_config &cfg)
+{
+  std::vector<std::string> v;
+  for (int b = 0; b < cfg.B; b++) v.push_back(std::string(gph_control_pop_name(C, cfg.bandSrc[b])) + "->" + gph_control_pop_name(C, cfg.bandTgt[b]));
+  return v;
+}
+// rank `rank`'s part, open, its header written (L: the int64 of the formats that carry one)
+FILE *open_part(const PartFormat &F, const char *prefix, int rank, const int32_t *hdr, int64_t L, const std::vector<std::string> &a,
+                const std::vector<std::string> &b)
+{
+  FILE *f = fopen(part_path(F, prefix, rank).c_str(), "wb");
+  if (!f) return nullptr;
+  std::string names;
+  for (const std::vector<std::string> *v : {&a, &b})
+    for (const std::string &nm : *v) { names += nm; names.push_back('\0'); }
+  const int32_t nbytes = (int32_t)names.size();
+  fwrite(F.magic, 1, 8, f); fwrite(hdr, 4, (size_t)F.nh, f);
+  if (F.has_L) fwrite(&L, 8, 1, f);
+  fwrite(&nbytes, 4, 1, f);
+  fwrite(names.data(), 1, names.size(), f);
+  return f;
+}
+// `got` fetched rows of n elements of esz bytes behind a part, row i with its extra value of xsz bytes, if any, in front of it
+// (ancestry: the iteration) or behind it (coal stats: logPrior)
+int write_rows(FILE *part, const void *rows, size_t esz, int32_t n, int32_t got, const void *extra, size_t xsz, bool in_front)
+{
+  for (int32_t i = 0; i < got; i++) {
+    const char *x = extra ? (const char *)extra + xsz * i : nullptr;
+    if (x && in_front && fwrite(x, xsz, 1, part) != 1) return GPH_EARG;
+    if (n > 0 && fwrite((const char *)rows + esz * n * i, esz, (size_t)n, part) != (size_t)n) return GPH_EARG;
+    if (x && !in_front && fwrite(x, xsz, 1, part) != 1) return GPH_EARG;
+  }
+  return fflush(part) == 0 ? GPH_OK : GPH_EARG;
+}
+}   // namespace
 
 static int run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
                             int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user, gph_comm *comm,
@@ -503,15 +462,17 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   char err[512] = "";
   int rc;
   FILE *trace = nullptr, *cs_part = nullptr, *ts_part = nullptr, *an_part = nullptr;
+  /* a failed run leaves no statistics file and no part behind (several ranks: the caller removes every rank's part) */
+  auto discard_all = [&]() {
+    if (world != 1) return;
+    if (an_prefix) gph_ancestry_discard(an_prefix, 1);
+    if (cs_prefix) gph_coal_stats_discard(cs_prefix, 1);
+    if (ts_slices) gph_time_slices_discard(cs_prefix, 1);
+  };
   auto fail = [&](int code, const char *what) {
     fprintf(stderr, "gphocs_hip: %s failed (status %d)%s%s\n", what, code, err[0] ? ": " : "", err);
-    if (trace) fclose(trace);
-    if (cs_part) fclose(cs_part);
-    if (ts_part) fclose(ts_part);
-    if (an_part) fclose(an_part);
-    if (an_prefix && world == 1) gph_ancestry_discard(an_prefix, 1);
-    if (cs_prefix && world == 1) gph_coal_stats_discard(cs_prefix, 1);   /* (several ranks: the caller removes every rank's part) */
-    if (ts_slices && world == 1) gph_time_slices_discard(cs_prefix, 1);
+    for (FILE *f : {trace, cs_part, ts_part, an_part}) if (f) fclose(f);
+    discard_all();
     if (M) gph_mcmc_destroy(M);
     if (E) gph_engine_destroy(E);
     if (LC) gph_loci_free(LC);
@@ -603,20 +564,9 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     if ((rc = gph_engine_coal_stats_enable(E, cs_capacity))) return fail(rc, "gph_engine_coal_stats_enable");
     gph_engine_coal_stats_shape(E, &cs_rd, nullptr, nullptr, nullptr);
     cs_rows.resize((size_t)cs_rd * cs_capacity);
-    cs_part = fopen(cs_part_path(cs_prefix, rank).c_str(), "wb");
-    if (!cs_part) { snprintf(err, sizeof err, "Could not open %s", cs_part_path(cs_prefix, rank).c_str()); return fail(GPH_EARG, "opening the coal-stats part file"); }
-    std::string names;
-    for (int s = 0; s < cfg.n; s++) {
-      /* the second haploid of a diploid has no name of its own: the previous sample's, "NA" without one (GPhoCS.c:942-953) */
-      const char *nm = gph_control_sample_name(C, s);
-      if (!nm || !nm[0]) { const char *pv = s > 0 ? gph_control_sample_name(C, s - 1) : nullptr; nm = pv && pv[0] ? pv : "NA"; }
-      names += nm; names.push_back('\0');
-    }
-    for (int p = 0; p < cfg.K; p++) { names += gph_control_pop_name(C, p); names.push_back('\0'); }
-    const int32_t hdr[3] = {cfg.n, cfg.K, cs_rd}, nbytes = (int32_t)names.size();
-    const int64_t Ltot = L;
-    fwrite(CS_MAGIC, 1, 8, cs_part); fwrite(hdr, 4, 3, cs_part); fwrite(&Ltot, 8, 1, cs_part); fwrite(&nbytes, 4, 1, cs_part);
-    fwrite(names.data(), 1, names.size(), cs_part);
+    const int32_t hdr[3] = {cfg.n, cfg.K, cs_rd};
+    cs_part = open_part(CS_PART, cs_prefix, rank, hdr, L, leaf_names(C, cfg), pop_names(C, cfg));
+    if (!cs_part) { snprintf(err, sizeof err, "Could not open %s", part_path(CS_PART, cs_prefix, rank).c_str()); return fail(GPH_EARG, "opening the coal-stats part file"); }
   }
   /* time-sliced statistics: a device buffer of as many rows, this rank's part file and its header */
   int32_t ts_rd = 0;
@@ -626,17 +576,9 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     if ((rc = gph_engine_time_slices_enable(E, ts_slices, cs_capacity))) return fail(rc, "gph_engine_time_slices_enable");
     gph_engine_time_slices_shape(E, &ts_rd, nullptr, nullptr, nullptr, nullptr, nullptr);
     ts_rows.resize((size_t)ts_rd * cs_capacity);
-    ts_part = fopen(ts_part_path(cs_prefix, rank).c_str(), "wb");
-    if (!ts_part) { snprintf(err, sizeof err, "Could not open %s", ts_part_path(cs_prefix, rank).c_str()); return fail(GPH_EARG, "opening the time-slices part file"); }
-    std::string names;
-    for (int p = 0; p < cfg.K; p++) { names += gph_control_pop_name(C, p); names.push_back('\0'); }
-    for (int b = 0; b < cfg.B; b++) {
-      names += std::string(gph_control_pop_name(C, cfg.bandSrc[b])) + "->" + gph_control_pop_name(C, cfg.bandTgt[b]);
-      names.push_back('\0');
-    }
-    const int32_t hdr[4] = {ts_slices, cfg.K, cfg.B, ts_rd}, nbytes = (int32_t)names.size();
-    fwrite(TS_MAGIC, 1, 8, ts_part); fwrite(hdr, 4, 4, ts_part); fwrite(&nbytes, 4, 1, ts_part);
-    fwrite(names.data(), 1, names.size(), ts_part);
+    const int32_t hdr[4] = {ts_slices, cfg.K, cfg.B, ts_rd};
+    ts_part = open_part(TS_PART, cs_prefix, rank, hdr, 0, pop_names(C, cfg), band_names(C, cfg));
+    if (!ts_part) { snprintf(err, sizeof err, "Could not open %s", part_path(TS_PART, cs_prefix, rank).c_str()); return fail(GPH_EARG, "opening the time-slices part file"); }
   }
   /* migration ancestry: accumulators and a device buffer of an_capacity per-sample rows, this rank's part file and its header */
   int32_t an_ncol = 0, an_ri = 0;
@@ -649,58 +591,38 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     gph_engine_ancestry_shape(E, &an_ncol, &an_ri, nullptr, nullptr);
     an_rows.resize((size_t)an_ri * an_capacity);
     an_iters.resize((size_t)an_capacity);
-    an_part = fopen(an_part_path(an_prefix, rank).c_str(), "wb");
-    if (!an_part) { snprintf(err, sizeof err, "Could not open %s", an_part_path(an_prefix, rank).c_str()); return fail(GPH_EARG, "opening the ancestry part file"); }
-    std::string names;
-    for (int s = 0; s < cfg.n; s++) {
-      /* the leaf's name as the coal-stats files print it: the second haploid of a diploid takes the previous sample's */
-      const char *nm = gph_control_sample_name(C, s);
-      if (!nm || !nm[0]) { const char *pv = s > 0 ? gph_control_sample_name(C, s - 1) : nullptr; nm = pv && pv[0] ? pv : "NA"; }
-      an_names.push_back(nm);
-      names += nm; names.push_back('\0');
-    }
-    for (int b = 0; b < cfg.B; b++) {
-      names += std::string(gph_control_pop_name(C, cfg.bandSrc[b])) + "->" + gph_control_pop_name(C, cfg.bandTgt[b]);
-      names.push_back('\0');
-    }
-    const int32_t hdr[3] = {cfg.n, cfg.B, an_ri}, nbytes = (int32_t)names.size();
-    fwrite(AN_MAGIC, 1, 8, an_part); fwrite(hdr, 4, 3, an_part); fwrite(&nbytes, 4, 1, an_part);
-    fwrite(names.data(), 1, names.size(), an_part);
+    an_names = leaf_names(C, cfg);
+    const int32_t hdr[3] = {cfg.n, cfg.B, an_ri};
+    an_part = open_part(AN_PART, an_prefix, rank, hdr, 0, an_names, band_names(C, cfg));
+    if (!an_part) { snprintf(err, sizeof err, "Could not open %s", part_path(AN_PART, an_prefix, rank).c_str()); return fail(GPH_EARG, "opening the ancestry part file"); }
   }
   int32_t an_held = 0;
+  /* the filled rows of a device buffer behind this rank's part: ancestry rows each behind their iteration, coal-stats rows
+   * each in front of their logPrior */
   auto an_flush = [&]() -> int {
     int32_t got = 0;
     int rcf = gph_engine_ancestry_fetch_rows(E, an_iters.data(), an_rows.data(), an_ri, an_capacity, &got);
     if (rcf) return rcf;
-    for (int32_t i = 0; i < got; i++) {
-      if (fwrite(&an_iters[i], 4, 1, an_part) != 1) return GPH_EARG;
-      if (an_ri > 0 && fwrite(an_rows.data() + (size_t)i * an_ri, 4, (size_t)an_ri, an_part) != (size_t)an_ri) return GPH_EARG;
-    }
     an_written += got;
     an_held = 0;
-    return fflush(an_part) == 0 ? GPH_OK : GPH_EARG;
+    return write_rows(an_part, an_rows.data(), 4, an_ri, got, an_iters.data(), 4, true);
   };
   auto ts_flush = [&]() -> int {
     int32_t got = 0;
     int rcf = gph_engine_time_slices_fetch(E, ts_rows.data(), cs_capacity, &got);
     if (rcf) return rcf;
-    if (got > 0 && fwrite(ts_rows.data(), sizeof(double), (size_t)ts_rd * got, ts_part) != (size_t)ts_rd * got) return GPH_EARG;
     ts_written += got;
-    return fflush(ts_part) == 0 ? GPH_OK : GPH_EARG;
+    return write_rows(ts_part, ts_rows.data(), sizeof(double), ts_rd, got, nullptr, 0, false);
   };
-  /* the filled rows of the device buffer, each with its logPrior, to the part file */
   auto cs_flush = [&]() -> int {
     int32_t got = 0;
     int rcf = gph_engine_coal_stats_fetch(E, cs_rows.data(), cs_capacity, &got);
     if (rcf) return rcf;
     if (got != (int32_t)cs_prior.size()) return GPH_ESTATE;
-    for (int32_t i = 0; i < got; i++) {
-      if (fwrite(cs_rows.data() + (size_t)i * cs_rd, sizeof(double), (size_t)cs_rd, cs_part) != (size_t)cs_rd) return GPH_EARG;
-      if (fwrite(&cs_prior[i], sizeof(double), 1, cs_part) != 1) return GPH_EARG;
-    }
+    rcf = write_rows(cs_part, cs_rows.data(), sizeof(double), cs_rd, got, cs_prior.data(), sizeof(double), false);
     cs_written += got;
     cs_prior.clear();
-    return fflush(cs_part) == 0 ? GPH_OK : GPH_EARG;
+    return rcf;
   };
   std::vector<double> vals(mc.numParameters + 4, 0.0);
   double logL = 0, dataL = 0;
@@ -928,12 +850,10 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_engine_destroy(E);
   if (oob_checked && oob_where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
     gph_loci_free(LC);
     gph_control_free(C);
-    if (cs_prefix && world == 1) gph_coal_stats_discard(cs_prefix, 1);
-    if (ts_slices && world == 1) gph_time_slices_discard(cs_prefix, 1);
-    if (an_prefix && world == 1) gph_ancestry_discard(an_prefix, 1);
+    discard_all();
     return GPH_EKERNEL;
   }
   rc = GPH_OK;
@@ -947,20 +867,12 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
   /* (the ancestry files first, then the slices file: should a later group fail, two files and one are removed again,
    * not 1 + 3 K) */
-  if (an_prefix && world == 1) {
-    if (rc) gph_ancestry_discard(an_prefix, 1);
-    else rc = gph_ancestry_write(an_prefix, 1);
+  if (world == 1) {
+    if (!rc && an_prefix) rc = gph_ancestry_write(an_prefix, 1);
+    if (!rc && ts_slices) rc = gph_time_slices_write(cs_prefix, 1);
+    if (!rc && cs_prefix) rc = gph_coal_stats_write(cs_prefix, 1);
+    if (rc) discard_all();
   }
-  if (ts_slices && world == 1) {
-    if (rc) gph_time_slices_discard(cs_prefix, 1);
-    else rc = gph_time_slices_write(cs_prefix, 1);
-  }
-  if (cs_prefix && world == 1) {
-    if (rc) gph_coal_stats_discard(cs_prefix, 1);
-    else rc = gph_coal_stats_write(cs_prefix, 1);
-    if (rc && ts_slices) gph_time_slices_discard(cs_prefix, 1);
-  }
-  if (rc && an_prefix && world == 1) gph_ancestry_discard(an_prefix, 1);
   return rc;
 }
 

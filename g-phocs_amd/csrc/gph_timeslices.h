@@ -1,4 +1,4 @@
-// gph_timeslices.h -- k_time_slices + k_time_slices_fold: the coalescence and migration statistics of one MCMC sample cut
+// gph_timeslices.h -- k_time_slices (+ k_rows_fold, gph_sampler.h): the coalescence and migration statistics of one MCMC sample cut
 // into S equal time slices per population branch and per migration band, genome-wide, computed on the device
 // (include/gphocs_hip.h, gph_engine_time_slices_*).
 //
@@ -43,12 +43,12 @@
 // Summation order (what makes a row bitwise reproducible for a given locus count, chunk size and rank count): a lane's
 // accumulator grows term by term in chain order, locus after locus (the loci g, g + G, g + 2G, ... of the chunk); at the
 // end of the chunk ONE lane per (walker, slice) adds the G copies in the order g = 0, 1, ..., G - 1 into the chunk's
-// partial row; k_time_slices_fold, one lane per column, adds the partial rows in chunk order.  No atomics, nothing
+// partial row; k_rows_fold, one lane per column, adds the partial rows in chunk order.  No atomics, nothing
 // depends on how workgroups are scheduled.  Counts are integers held as doubles.
 //
 // The kernels write no page, draw no random number and touch no chain state.
 #pragma once
-#include "gph_kernels.h"
+#include "gph_sampler.h"
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 5
@@ -58,54 +58,34 @@
 #define GPH_TS_MAXTHREADS 256
 #define GPH_TS_LDS_PREF 40960     // LDS bytes of a workgroup the group size G is grown to
 #define GPH_TS_LDS_MAX 61440      // LDS bytes of a workgroup at most (one locus image + one wavefront of accumulators must fit)
-#define GPH_TS_FOLD_THREADS 256
 #define GPH_TS_RANGES 5
 
-#ifdef GPH_HOSTEMU
-#define GPH_TS_HD static inline
-#define GPH_TS_FN static inline
-#else
-#define GPH_TS_HD __host__ __device__ inline
-#define GPH_TS_FN __device__ inline
-#endif
-
-// the part of a page a walk needs, packed: range r = len[r] bytes from page offset src[r] at image offset dst[r] (all
-// multiples of 16); a_*: image offsets of the arrays themselves
-struct GphTsImg {
-  int32_t src[GPH_TS_RANGES], dst[GPH_TS_RANGES], len[GPH_TS_RANGES];
+// the part of a page a walk needs, packed (gph_sampler.h); a_*: image offsets of the arrays themselves
+struct GphTsImg : GphPackedImg {
   int32_t a_ev, a_nd, a_mage, a_first, a_migi;
-  int32_t bytes;
 };
 struct GphTsShape {
   int32_t S, G, wt, bd, ntiles, lds_bytes;
   GphTsImg img;
 };
 
-GPH_TS_HD int gph_ts_row_doubles(int K, int B, int S) { return 1 + 2 * S * (K + B); }
-GPH_TS_HD int gph_ts_up64(int x) { return (x + 63) / 64 * 64; }
+GPH_SM_HD int gph_ts_row_doubles(int K, int B, int S) { return 1 + 2 * S * (K + B); }
+GPH_SM_HD int gph_ts_up64(int x) { return (x + 63) / 64 * 64; }
 // LDS bytes beside the images and the accumulators: the model tables (4 f64 + 2 i32 arrays), padded
-GPH_TS_HD int gph_ts_model_bytes(int K, int B) { return ((2 * K + 2 * B) * 8 + (K + B) * 4 + 15) / 16 * 16; }
-GPH_TS_HD int gph_ts_lds_bytes(int K, int B, int S, int G, int bd, int img) { return G * img + gph_ts_model_bytes(K, B) + bd * S * 12; }
+GPH_SM_HD int gph_ts_model_bytes(int K, int B) { return ((2 * K + 2 * B) * 8 + (K + B) * 4 + 15) / 16 * 16; }
+GPH_SM_HD int gph_ts_lds_bytes(int K, int B, int S, int G, int bd, int img) { return G * img + gph_ts_model_bytes(K, B) + bd * S * 12; }
 
-GPH_TS_HD void gph_ts_image(const GphLayout &y, GphTsImg &m)
+GPH_SM_HD void gph_ts_image(const GphLayout &y, GphTsImg &m)
 {
   const int lo[GPH_TS_RANGES] = {y.o_ev, y.o_nd, y.o_mig_age, y.o_first, y.o_mig_i};
   const int sz[GPH_TS_RANGES] = {y.E * 16, y.N * 16, GPH_MAX_MIGS * 8, y.K * 2, GPH_MAX_MIGS * MG_COUNT * 2};
-  int at = 0, a[GPH_TS_RANGES];
-  for (int r = 0; r < GPH_TS_RANGES; r++) {
-    const int s = lo[r] & ~15;
-    int e = (lo[r] + sz[r] + 15) & ~15;
-    if (e > y.page_bytes) e = y.page_bytes;
-    m.src[r] = s; m.dst[r] = at; m.len[r] = e - s;
-    a[r] = at + (lo[r] - s);
-    at += e - s;
-  }
+  int a[GPH_TS_RANGES];
+  gph_pack_ranges(y, lo, sz, GPH_TS_RANGES, m, a);
   m.a_ev = a[0]; m.a_nd = a[1]; m.a_mage = a[2]; m.a_first = a[3]; m.a_migi = a[4];
-  m.bytes = at;
 }
 
 // walkers per tile, loci per group, lanes: from K, B, S and the layout alone.  0: fine; 1: S out of range
-GPH_TS_HD int gph_ts_shape(const GphLayout &y, int S, GphTsShape &h)
+GPH_SM_HD int gph_ts_shape(const GphLayout &y, int S, GphTsShape &h)
 {
   if (S < 1 || S > GPH_TS_MAXS) return 1;
   const int K = y.K, B = y.B, W = K + B, per_lane = 12 * S, fixed = gph_ts_model_bytes(K, B);
@@ -130,7 +110,7 @@ struct GphTsLds {
   int32_t *popFather, *bandTgt;                       // [K] [B]
   uint32_t *accC;            // [S][bd]
 };
-GPH_TS_FN void gph_ts_carve(char *base, int K, int B, const GphTsShape &h, GphTsLds &s)
+GPH_SM_FN void gph_ts_carve(char *base, int K, int B, const GphTsShape &h, GphTsLds &s)
 {
   char *p = base;
   s.img = p; p += (size_t)h.G * h.img.bytes;
@@ -145,7 +125,7 @@ GPH_TS_FN void gph_ts_carve(char *base, int K, int B, const GphTsShape &h, GphTs
 }
 
 // entry q of the model tables (q < 2K + 2B: the f64 arrays, then the two i32 arrays) from the chain state
-GPH_TS_FN void gph_ts_load_model(const GphTsLds &s, const GphModel &m, int K, int B, int q)
+GPH_SM_FN void gph_ts_load_model(const GphTsLds &s, const GphModel &m, int K, int B, int q)
 {
   if (q < K) s.popAge[GPH_IX(q, K)] = m.popAge[GPH_IX(q, GPH_MAXK)];
   else if (q < 2 * K) s.sampleAge[GPH_IX(q - K, K)] = m.sampleAge[GPH_IX(q - K, GPH_MAXK)];
@@ -155,16 +135,8 @@ GPH_TS_FN void gph_ts_load_model(const GphTsLds &s, const GphModel &m, int K, in
   else s.bandTgt[GPH_IX(q - 3 * K - 2 * B, B)] = m.bandTgt[GPH_IX(q - 3 * K - 2 * B, GPH_MAXB)];
 }
 
-// 16-byte unit u of a group's images: locus u / upl of the group, image offset 16 (u % upl) -> where it lies in the page
-GPH_TS_FN int gph_ts_unit_src(const GphTsImg &m, int o)
-{
-  int r = 0;
-  while (r < GPH_TS_RANGES - 1 && o >= m.dst[r] + m.len[r]) r++;
-  return m.src[r] + (o - m.dst[r]);
-}
-
 // lane `lane` walks the chain of walker W in the staged image of locus g of the group
-GPH_TS_FN void gph_ts_walk(const GphTsLds &s, const GphLayout &y, const GphTsShape &h, int lane, int g, int W, int vsync)
+GPH_SM_FN void gph_ts_walk(const GphTsLds &s, const GphLayout &y, const GphTsShape &h, int lane, int g, int W, int vsync)
 {
   const int K = y.K, B = y.B, S = h.S, bd = h.bd;
   const char *im = s.img + (size_t)GPH_IX(g, h.G) * h.img.bytes;
@@ -241,7 +213,7 @@ GPH_TS_FN void gph_ts_walk(const GphTsLds &s, const GphLayout &y, const GphTsSha
 }
 
 // cell q = (walker-in-tile, slice) of a tile into the chunk's partial row: the G copies in the order g = 0 .. G - 1
-GPH_TS_FN void gph_ts_chunk_out(const GphTsLds &s, const GphLayout &y, const GphTsShape &h, int tile, int q, double *out)
+GPH_SM_FN void gph_ts_chunk_out(const GphTsLds &s, const GphLayout &y, const GphTsShape &h, int tile, int q, double *out)
 {
   const int S = h.S, w = q / S, sl = q - w * S, W = tile * h.wt + w;
   if (W >= y.K + y.B) return;
@@ -255,14 +227,6 @@ GPH_TS_FN void gph_ts_chunk_out(const GphTsLds &s, const GphLayout &y, const Gph
   const int col = 1 + 2 * GPH_IX(W * S + sl, (y.K + y.B) * S);
   out[col] = (double)c;
   out[col + 1] = d;
-}
-
-// column c of a sample's row: the chunks' partials in chunk order
-GPH_TS_FN void gph_ts_fold_column(const double *part, int nchunks, int rd, int c, double iteration, double *row)
-{
-  double sum = 0.0;
-  for (int ch = 0; ch < nchunks; ch++) sum = sum + part[(size_t)ch * rd + c];
-  row[c] = c == 0 ? iteration : sum;
 }
 
 #ifdef GPH_HOSTEMU
@@ -280,7 +244,7 @@ static inline void time_slices_workgroup(const GphLayout &y, const GphTsShape &h
     const int nl = j1 - jg < h.G ? j1 - jg : h.G;
     for (int u = 0; u < nl * upl; u++) {
       const int loc = u / upl, o = (u - loc * upl) * 16;
-      memcpy(s.img + (size_t)loc * h.img.bytes + o, pages + (size_t)(jg + loc) * y.page_bytes + gph_ts_unit_src(h.img, o), 16);
+      memcpy(s.img + (size_t)loc * h.img.bytes + o, pages + (size_t)(jg + loc) * y.page_bytes + gph_pack_unit_src(h.img, o), 16);
     }
     for (int lane = 0; lane < h.G * h.wt; lane++) {
       const int g = lane / h.wt, Wk = tile * h.wt + (lane - g * h.wt);
@@ -310,7 +274,7 @@ __global__ void __launch_bounds__(GPH_TS_MAXTHREADS) k_time_slices(GphLayout y, 
     __syncthreads();        /* everybody is done with the previous group's images (first pass: with zeroing and the tables) */
     for (int u = tid; u < nl * upl; u += bd) {
       const int loc = u / upl, o = (u - loc * upl) * 16;
-      const uint4 v = *(const uint4 *)(pages + (size_t)(jg + loc) * y.page_bytes + gph_ts_unit_src(h.img, o));
+      const uint4 v = *(const uint4 *)(pages + (size_t)(jg + loc) * y.page_bytes + gph_pack_unit_src(h.img, o));
       *(uint4 *)(s.img + (size_t)GPH_IX(loc, h.G) * h.img.bytes + GPH_IX(o, h.img.bytes)) = v;
     }
     __syncthreads();
@@ -320,12 +284,6 @@ __global__ void __launch_bounds__(GPH_TS_MAXTHREADS) k_time_slices(GphLayout y, 
   double *out = part + (size_t)ch * rd;
   for (int q = tid; q < h.wt * h.S; q += bd) gph_ts_chunk_out(s, y, h, tile, q, out);
   if (tile == 0 && tid == 0) out[0] = 0.0;
-}
-
-__global__ void __launch_bounds__(GPH_TS_FOLD_THREADS) k_time_slices_fold(const double *part, int nchunks, int rd, double iteration, double *row)
-{
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < rd) gph_ts_fold_column(part, nchunks, rd, c, iteration, row);
 }
 #endif
 

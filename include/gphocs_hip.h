@@ -223,8 +223,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * engine's own stream: which = 0 sweep, 1 tau_eval, 2 mix_eval, 3 init, 4 check,
  * 5 tau_finish (commit or revert, by the decision flag), 7 mix_finish, 8 sync, 9 locus-rate scan, 10 locus-rate apply,
  * 11 locus-rate prepare, 13 locus summary (gph_engine_locus_summary_sample), 14 coalescent / sample-pair statistics
- * (gph_engine_coal_stats_sample: k_coal_stats + k_coal_fold together), 15 time-sliced statistics
- * (gph_engine_time_slices_sample: k_time_slices + k_time_slices_fold together), 16 migration ancestry
+ * (gph_engine_coal_stats_sample: k_coal_stats + k_rows_fold together), 15 time-sliced statistics
+ * (gph_engine_time_slices_sample: k_time_slices + k_rows_fold together), 16 migration ancestry
  * (gph_engine_ancestry_sample: k_ancestry) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
@@ -274,7 +274,7 @@ int gph_engine_locus_summary_columns(gph_engine *e, int32_t *ncol, int64_t *samp
 int gph_engine_locus_summary_fetch(gph_engine *e, double *out, int64_t ld, int32_t reset);
 const char *gph_engine_locus_summary_column_name(gph_engine *e, int32_t col);
 /* genome-wide coalescent statistics and sample-pair statistics of one MCMC sample, computed on the device (k_coal_stats,
- * k_coal_fold: csrc/gph_coalstats.h).  They replace code the reference carries but never reaches (`coal-stats-file`,
+ * k_rows_fold: csrc/gph_coalstats.h, gph_sampler.h).  They replace code the reference carries but never reaches (`coal-stats-file`,
  * GPhoCS.c:1771 `if (recordCoalStats && 0)`): computeNodeStats (patch.c:2172-2270) over computePairwiseLCAs
  * (LocusDataLikelihood.c:1685-1830), computeFlatStats (patch.c:2278-2320) over getSortedAges
  * (LocusDataLikelihood.c:1216-1260), and the numbers printCoalStats prints (GPhoCS.c:911-1040).
@@ -309,7 +309,7 @@ const char *gph_engine_coal_stats_column_name(gph_engine *e, int32_t col);
  * count */
 int gph_engine_coal_stats_set_chunk(gph_engine *e, int32_t slots);
 /* coalescence and migration statistics per TIME SLICE of one MCMC sample, genome-wide, computed on the device
- * (k_time_slices, k_time_slices_fold: csrc/gph_timeslices.h, where the statistic is defined line by line).  Every
+ * (k_time_slices, k_rows_fold: csrc/gph_timeslices.h, where the statistic is defined line by line).  Every
  * population's branch and every migration band's life is cut into `slices` equal time slices; per slice: the number of
  * coalescences C and the coalescent exposure D = sum of n(n-1) t (the sufficient statistics of theta within the slice),
  * the number of migrations N into the band's target through the band and the migration exposure M = sum of n t.  The

@@ -1,0 +1,93 @@
+"""Helpers the tests of the statistics samplers share (test_locus_summary.py, test_coal_stats.py, test_time_slices.py,
+test_ancestry.py and their -m gpu twins): the launcher, golden cases copied into a scratch directory, names read from the
+inputs themselves, and the host-emulation build the CPU tests load."""
+import math
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+from conftest import GOLDEN, REPO
+
+sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
+
+EXE = os.path.join(REPO, "g-phocs_amd", "G-PhoCS-hip")
+U = 2.0 ** -53
+
+
+def hostemu_library():
+    """(path, library) of the default host-emulation build; the body of the modules' `hostemu` fixtures"""
+    import run_hostemu
+    import gphocs_amd as G
+    G.build()                       # the launcher executable (g++); the HIP libraries are not loaded here
+    path = run_hostemu.build_hostemu()
+    return path, G.load_library(path)
+
+
+def _fmt(x):
+    return "%.10g" % x
+
+
+def _run(hostemu_path, cwd, args):
+    """the launcher; hostemu_path None: the product libraries (the MI355X)"""
+    env = dict(os.environ, GPHOCS_HIP_LIB=hostemu_path) if hostemu_path else dict(os.environ)
+    r = subprocess.run([EXE] + args, cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return r
+
+
+def _copy_case(name, dst, ctl_text=None):
+    os.makedirs(dst, exist_ok=True)
+    for ext in (".ctl", ".seq"):
+        shutil.copy(os.path.join(GOLDEN, name + ext), dst)
+    if ctl_text is not None:
+        open(os.path.join(dst, name + ".ctl"), "w").write(ctl_text)
+
+
+def _pop_names(ctl_path):
+    """population names in model order (current populations first, then ancestral), from the control file itself"""
+    txt = open(ctl_path).read()
+    cur = re.search(r"CURRENT-POPS-START(.*?)CURRENT-POPS-END", txt, re.S).group(1)
+    anc = re.search(r"ANCESTRAL-POPS-START(.*?)ANCESTRAL-POPS-END", txt, re.S).group(1)
+    return re.findall(r"^\s*name\s+(\S+)", cur, re.M) + re.findall(r"^\s*name\s+(\S+)", anc, re.M)
+
+
+def _locus_names(seq_path):
+    tok = open(seq_path).read().split("\n")
+    names, i = [], 0
+    L = int(tok[0].split()[0])
+    i = 1
+    while len(names) < L:
+        t = tok[i].split()
+        i += 1
+        if len(t) == 3:
+            names.append(t[0])
+            i += int(t[1])
+    return names
+
+
+def _data_lines(trace):
+    return open(trace).read().splitlines()[1:]
+
+
+def within_bound(got, want, T):
+    """relative difference <= (2T + 4) * 2^-53"""
+    if got == want:
+        return True, 0.0
+    rel = abs(got - want) / abs(want) if want != 0.0 else math.inf
+    return rel <= (2 * T + 4) * U, rel
+
+
+def printed_names(sample_names):
+    """the second haploid of a diploid has no name: the previous sample's, NA without one (GPhoCS.c:942-953)"""
+    out = []
+    for i, nm in enumerate(sample_names):
+        if not nm:
+            nm = sample_names[i - 1] if i > 0 and sample_names[i - 1] else "NA"
+        out.append(nm)
+    return out
+
+
+def read_outputs(d, prefix):
+    return {f[len(prefix) + 1:]: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.startswith(prefix + ".")}

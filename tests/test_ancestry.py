@@ -20,12 +20,11 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_records, compare_trace_files
-from test_coal_stats import printed_names, read_outputs
-from test_locus_summary import _copy_case, _data_lines, _locus_names, _pop_names, _run
+from sampler_util import (EXE, _copy_case, _data_lines, _fmt, _locus_names, _pop_names, _run, hostemu_library, printed_names,  # noqa: F401
+                          read_outputs)
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
 
-EXE = os.path.join(REPO, "g-phocs_amd", "G-PhoCS-hip")
 GOLDEN_ITERS = {"m3": 120, "j1": 150, "a7": 100, "x8": 24, "b2": 24, "n7": 12}
 CASES = {"m3": 120, "j1": 80, "a7": 100, "x8": 24, "b2": 24, "n7": 12}      # samples with a state dump each
 BIG = ("b2", "n7")
@@ -34,11 +33,7 @@ FULL = -5               # GPH_EFULL
 
 @pytest.fixture(scope="module")
 def hostemu():
-    import run_hostemu
-    import gphocs_amd as G
-    G.build()                       # the launcher executable (g++); the HIP libraries are not loaded here
-    path = run_hostemu.build_hostemu()
-    return path, G.load_library(path)
+    return hostemu_library()
 
 
 @pytest.fixture(scope="module")
@@ -319,10 +314,6 @@ def test_a_model_without_bands_has_only_the_any_columns(hostemu, tmp_path):
 
 
 # ---------------------------------------------------------------- the program and the launcher
-def _fmt(x):
-    return "%.10g" % x
-
-
 def expected_files(ctl_dir, ctl, lib=None, sampler_lib=None):
     """{file suffix: text} the program must write: the formulas of README.md applied to the raw accumulators and rows of an
     equivalent Sampler run (burn-in first, a sample wherever a trace line is written)"""

@@ -1,6 +1,6 @@
 """Genome-wide coalescent statistics and sample-pair statistics per sample (gph_engine_coal_stats_*, `G-PhoCS-hip -s PREFIX`)
 on the CPU: the host-emulation build of the engine sources runs the per-locus body of k_coal_stats and the fold of
-k_coal_fold over the same pages.
+k_rows_fold over the same pages.
 
 The yardstick is `restate` below: an independent restatement, in plain Python over state dumps taken at every sample (the
 LOCUS / N / S lines), of the reference's computeNodeStats / computeFlatStats (patch.c:2172-2320) -- recursive LCAs over
@@ -32,23 +32,18 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import REL_TOL, compare_records, compare_trace_files
-from test_locus_summary import _copy_case, _data_lines, _pop_names, _run
+from sampler_util import (EXE, U, _copy_case, _data_lines, _pop_names, _run, hostemu_library, printed_names, read_outputs,  # noqa: F401
+                          within_bound)
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
 
-EXE = os.path.join(REPO, "g-phocs_amd", "G-PhoCS-hip")
 GOLDEN_ITERS = {"m3": 120, "a7": 100, "v8": 60, "j1": 150, "g1": 30, "x8": 24, "n7": 12}
-U = 2.0 ** -53
 FIXED = ["iter", "coalStat", "numCoal", "migStat", "numMig", "genLnL", "dataLnL"]
 
 
 @pytest.fixture(scope="module")
 def hostemu():
-    import run_hostemu
-    import gphocs_amd as G
-    G.build()                       # the launcher executable (g++); the HIP libraries are not loaded here
-    path = run_hostemu.build_hostemu()
-    return path, G.load_library(path)
+    return hostemu_library()
 
 
 # ---------------------------------------------------------------- the restatement, from state dumps
@@ -121,14 +116,6 @@ def restate(loci, n, K, B):
         numCoal += sum(d["ncoal"])
         numMig += sum(d["nmig"])
     return dict(cnt=cnt, first=first, agesum=agesum, coalStat=coalStat, migStat=migStat, numCoal=numCoal, numMig=numMig)
-
-
-def within_bound(got, want, T):
-    """relative difference <= (2T + 4) * 2^-53"""
-    if got == want:
-        return True, 0.0
-    rel = abs(got - want) / abs(want) if want != 0.0 else math.inf
-    return rel <= (2 * T + 4) * U, rel
 
 
 def split_row(row, n, K):
@@ -301,16 +288,6 @@ def gamma_lpdf(shape, rate, x):
     return shape * math.log(rate) - math.lgamma(shape) + (shape - 1.0) * math.log(x) - rate * x
 
 
-def printed_names(sample_names):
-    """the second haploid of a diploid has no name: the previous sample's, NA without one (GPhoCS.c:942-953)"""
-    out = []
-    for i, nm in enumerate(sample_names):
-        if not nm:
-            nm = sample_names[i - 1] if i > 0 and sample_names[i - 1] else "NA"
-        out.append(nm)
-    return out
-
-
 def expected_files(ctl_dir, ctl, lib=None, sampler_lib=None):
     """{file suffix: text} the program must write: the documented divisions applied to the raw rows of an equivalent Sampler
     run (burn-in first, a sample wherever a trace line is written), printed with printCoalStats's formats"""
@@ -376,8 +353,6 @@ def format_files(rows, n, K, L, pops, names):
     return files
 
 
-def read_outputs(d, prefix):
-    return {f[len(prefix) + 1:]: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.startswith(prefix + ".")}
 
 
 @pytest.mark.parametrize("name", ["g1", "j1"])

@@ -1,4 +1,4 @@
-"""Coalescent / sample-pair statistics on the MI355X (-m gpu): k_coal_stats and k_coal_fold in the product libraries, on
+"""Coalescent / sample-pair statistics on the MI355X (-m gpu): k_coal_stats and k_rows_fold in the product libraries, on
 every capacity class the goldens reach, held to what tests/test_coal_stats.py holds the host build to -- every sample
 against the restatement over a state dump (integers equal, fp64 sums within the summation bound), two runs bitwise equal,
 the chain's trajectory unchanged by sampling, the program's files, the launcher's ranks -- plus the engine's host
@@ -11,9 +11,9 @@ import os
 import pytest
 
 from conftest import GOLDEN
+from sampler_util import _copy_case, _data_lines, _run, read_outputs
 from test_coal_stats import (GOLDEN_ITERS, check_against_restatement, check_chain_untouched, check_failed_runs_leave_nothing,
-                             check_ranks, expected_files, read_outputs, run_chain)
-from test_locus_summary import _copy_case, _data_lines, _run
+                             check_ranks, expected_files, run_chain)
 
 pytestmark = pytest.mark.gpu
 

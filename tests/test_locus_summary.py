@@ -15,20 +15,16 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_records, compare_trace_files
+from sampler_util import EXE, _copy_case, _data_lines, _fmt, _locus_names, _pop_names, _run, hostemu_library  # noqa: F401
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
 
-EXE = os.path.join(REPO, "g-phocs_amd", "G-PhoCS-hip")
 GOLDEN_ITERS = {"m3": 120, "a7": 100, "v8": 60, "j1": 150, "g1": 30}
 
 
 @pytest.fixture(scope="module")
 def hostemu():
-    import run_hostemu
-    import gphocs_amd as G
-    G.build()                       # the launcher executable (g++); the HIP libraries are not loaded here
-    path = run_hostemu.build_hostemu()
-    return path, G.load_library(path)
+    return hostemu_library()
 
 
 # ---------------------------------------------------------------- the reference computation, from state dumps
@@ -207,10 +203,6 @@ def test_summary_lifecycle(hostemu, tmp_path):
 
 
 # ---------------------------------------------------------------- the program and the launcher
-def _fmt(x):
-    return "%.10g" % x
-
-
 def expected_table(ctl_dir, ctl, names_pop, lib=None, sampler_lib=None):
     """the table the program must write: the formulas of README.md applied to the raw accumulators of an equivalent Sampler
     run (the program's iteration loop: burn-in first, a sample wherever a trace line is written).  lib reads the control
@@ -256,48 +248,6 @@ def expected_table(ctl_dir, ctl, names_pop, lib=None, sampler_lib=None):
             row += mom("rate", g)
         lines.append("\t".join(row))
     return "\n".join(lines) + "\n", S, p
-
-
-def _run(hostemu_path, cwd, args):
-    """the launcher; hostemu_path None: the product libraries (the MI355X)"""
-    env = dict(os.environ, GPHOCS_HIP_LIB=hostemu_path) if hostemu_path else dict(os.environ)
-    r = subprocess.run([EXE] + args, cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
-def _copy_case(name, dst, ctl_text=None):
-    os.makedirs(dst, exist_ok=True)
-    for ext in (".ctl", ".seq"):
-        shutil.copy(os.path.join(GOLDEN, name + ext), dst)
-    if ctl_text is not None:
-        open(os.path.join(dst, name + ".ctl"), "w").write(ctl_text)
-
-
-def _pop_names(ctl_path):
-    """population names in model order (current populations first, then ancestral), from the control file itself"""
-    txt = open(ctl_path).read()
-    cur = re.search(r"CURRENT-POPS-START(.*?)CURRENT-POPS-END", txt, re.S).group(1)
-    anc = re.search(r"ANCESTRAL-POPS-START(.*?)ANCESTRAL-POPS-END", txt, re.S).group(1)
-    return re.findall(r"^\s*name\s+(\S+)", cur, re.M) + re.findall(r"^\s*name\s+(\S+)", anc, re.M)
-
-
-def _locus_names(seq_path):
-    tok = open(seq_path).read().split("\n")
-    names, i = [], 0
-    L = int(tok[0].split()[0])
-    i = 1
-    while len(names) < L:
-        t = tok[i].split()
-        i += 1
-        if len(t) == 3:
-            names.append(t[0])
-            i += int(t[1])
-    return names
-
-
-def _data_lines(trace):
-    return open(trace).read().splitlines()[1:]
 
 
 @pytest.mark.parametrize("name", ["g1", "j1"])

@@ -7,8 +7,8 @@ import os
 import pytest
 
 from conftest import GOLDEN
-from test_locus_summary import (GOLDEN_ITERS, _copy_case, _data_lines, _locus_names, _pop_names, _run, check_against_dumps,
-                                check_trajectory_unchanged, expected_table)
+from sampler_util import _copy_case, _data_lines, _locus_names, _pop_names, _run
+from test_locus_summary import GOLDEN_ITERS, check_against_dumps, check_trajectory_unchanged, expected_table
 
 pytestmark = pytest.mark.gpu
 

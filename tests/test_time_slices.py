@@ -1,5 +1,5 @@
 """Coalescence and migration statistics per time slice (gph_engine_time_slices_*, `G-PhoCS-hip -s PREFIX --time-slices S`)
-on the CPU: the host-emulation build of the engine sources runs the bodies of k_time_slices and k_time_slices_fold over
+on the CPU: the host-emulation build of the engine sources runs the bodies of k_time_slices and k_rows_fold over
 the same pages.
 
 The yardstick is `restate` below: the statistic as csrc/gph_timeslices.h and include/gphocs_hip.h define it, in plain
@@ -28,8 +28,7 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_trace_files
-from test_coal_stats import EXE, read_outputs, within_bound
-from test_locus_summary import _copy_case, _data_lines, _pop_names, _run
+from sampler_util import EXE, _copy_case, _data_lines, _pop_names, _run, hostemu_library, read_outputs, within_bound  # noqa: F401
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
 
@@ -39,11 +38,7 @@ ITERS = {"m3": 30, "a7": 24, "j1": 30, "v8": 24, "g1": 24, "x8": 5, "n7": 3}
 
 @pytest.fixture(scope="module")
 def hostemu():
-    import run_hostemu
-    import gphocs_amd as G
-    G.build()
-    path = run_hostemu.build_hostemu()
-    return path, G.load_library(path)
+    return hostemu_library()
 
 
 # ---------------------------------------------------------------- the restatement, from a state dump

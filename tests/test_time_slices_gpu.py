@@ -1,4 +1,4 @@
-"""Time-sliced coalescence / migration statistics on the MI355X (-m gpu): k_time_slices and k_time_slices_fold in the
+"""Time-sliced coalescence / migration statistics on the MI355X (-m gpu): k_time_slices and k_rows_fold in the
 product libraries, on every capacity class the goldens reach, held to what tests/test_time_slices.py holds the host build
 to -- every sample against the restatement over a state dump (counts equal, fp64 sums within the summation bound), the
 slices adding up to the pages' own statistics, two runs bitwise equal, the chain's trajectory unchanged by sampling, the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the coalescent / sample-pair statistics (k_coal_stats + k_coal_fold, timing class 14) on the benchmark's
+"""Cost of the coalescent / sample-pair statistics (k_coal_stats + k_rows_fold, timing class 14) on the benchmark's
 workloads: BASELINE configs[3] (100 k loci, 16 leaves; --config 4) and configs[4] (200 k loci, 20 leaves; --config 5
 --loci 200000), the synthetic data sets bench.py builds (same generator, seeds and cache), one sample after every iteration.
 
@@ -23,7 +23,7 @@ sys.path.insert(0, REPO)
 import gphocs_amd as G  # noqa: E402
 import bench  # noqa: E402
 
-CS_CLASS = 14     # gph_engine_class_stats / last_kernel_ms class of k_coal_stats + k_coal_fold
+CS_CLASS = 14     # gph_engine_class_stats / last_kernel_ms class of k_coal_stats + k_rows_fold
 
 
 def main():

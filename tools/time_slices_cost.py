@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Cost of the time-sliced statistics (k_time_slices + k_time_slices_fold, timing class 15) on the benchmark's workloads:
+"""Cost of the time-sliced statistics (k_time_slices + k_rows_fold, timing class 15) on the benchmark's workloads:
 BASELINE configs[3] (100 k loci, 16 leaves; --config 4) and configs[4] (200 k loci, 20 leaves; --config 5 --loci 200000),
 the synthetic data sets bench.py builds (same generator, seeds and cache), one sample after every iteration.
 
   python tools/time_slices_cost.py [--config 4] [--loci 100000] [--slices 4] [--steps 50] [--warmup 200] [--blocks 3]
 
 Runs interleaved blocks of `steps` iterations without sampling, with time-slices sampling and with coal-stats sampling
-(the yardstick, k_coal_stats + k_coal_fold, class 14) on one chain and prints one JSON line: the median wall ms per
+(the yardstick, k_coal_stats + k_rows_fold, class 14) on one chain and prints one JSON line: the median wall ms per
 iteration of each kind of block (every iteration ends with its one host synchronisation, so wall time is the device's time
 per iteration), the kernels' time per sample from HIP events, and the bytes the kernel stages per sample -- the page
 ranges of gph_timeslices.h (GphTsImg) times the loci -- with the rate that makes of the kernel time.  `floor_bytes` is the
