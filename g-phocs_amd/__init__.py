@@ -295,6 +295,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_ancestry_enable", "gph_engine_ancestry_sample", "gph_engine_ancestry_shape", "gph_engine_ancestry_fetch_loci",
     "gph_engine_ancestry_fetch_rows", "gph_engine_ancestry_column_name", "gph_run_control_file_ex4", "gph_ancestry_write",
     "gph_ancestry_discard",
+    "gph_engine_gene_trees_enable", "gph_engine_gene_trees_sample", "gph_engine_gene_trees_shape", "gph_engine_gene_trees_selected",
+    "gph_engine_gene_trees_fetch", "gph_run_control_file_ex5", "gph_gene_trees_write", "gph_gene_trees_discard", "gph_gene_trees_decode",
+    "gph_gene_tree_newick",
 ]
 
 
@@ -433,6 +436,19 @@ def _load_library(path):
                                              C.c_char_p, C.c_int32]
     lib.gph_ancestry_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_ancestry_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_engine_gene_trees_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int64]
+    lib.gph_engine_gene_trees_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_gene_trees_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32)]
+    lib.gph_engine_gene_trees_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_gene_trees_fetch.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_run_control_file_ex5.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32,
+                                             C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32]
+    lib.gph_gene_trees_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_gene_trees_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_gene_trees_decode.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32] + [C.c_void_p] * 14
+    lib.gph_gene_tree_newick.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + \
+        [C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     return lib
 
 
@@ -720,6 +736,32 @@ def ancestry_table(raw, S, n, B):
             agesum[:, b, i] = raw[f"age.{b}.{i}"]
     with np.errstate(divide="ignore", invalid="ignore"):
         return dict(samples=S, pAny=anyc / S, p=cnt / S, age=np.where(cnt > 0, agesum / cnt, 0.0), keep=anyc > 0)
+
+
+GT_MAX_MIGS = 10         # GPH_GT_MAX_MIGS
+GT_OFFSETS = 8           # GPH_GT_O_COUNT
+
+
+def gene_tree_newick(lib, age, father, left, right, npop, root, mig_branch, mig_band, mig_age, pop_names, band_names, leaf_labels,
+                     num_migs=None):
+    """one decoded record (the [N] / [10] arrays of Sampler.gene_trees() at one sample and locus) as one line of extended
+    Newick (gph_gene_tree_newick: host only).  pop_names / band_names ("<src>-><tgt>") / leaf_labels: lists of str;
+    num_migs None: the entries of mig_branch that are not -1.  ValueError for a record that is no tree or a refused name"""
+    n = len(leaf_labels)
+    f64 = [np.ascontiguousarray(a, dtype=np.float64) for a in (age, mig_age)]
+    i32 = [np.ascontiguousarray(a, dtype=np.int32) for a in (father, left, right, npop, mig_branch, mig_band)]
+    nm = int(num_migs) if num_migs is not None else int(np.sum(i32[4] >= 0))
+    strs = [(C.c_char_p * max(len(v), 1))(*[x.encode() for x in v]) for v in (pop_names, band_names, leaf_labels)]
+    args = (n, f64[0].ctypes.data, i32[0].ctypes.data, i32[1].ctypes.data, i32[2].ctypes.data, i32[3].ctypes.data, int(root), nm,
+            i32[4].ctypes.data, i32[5].ctypes.data, f64[1].ctypes.data, strs[0], len(pop_names), strs[1], len(band_names), strs[2])
+    ln = C.c_size_t()
+    rc = lib.gph_gene_tree_newick(*args, None, 0, C.byref(ln))
+    if rc == 0:
+        buf = C.create_string_buffer(ln.value + 1)
+        rc = lib.gph_gene_tree_newick(*args, buf, ln.value + 1, C.byref(ln))
+    if rc != 0:
+        raise ValueError(f"gphocs_hip: gene_tree_newick refused the record or a name (status {rc})")
+    return buf.value.decode()
 
 
 def _dp(a):
@@ -1016,6 +1058,60 @@ class Sampler:
         _, ri, _, held = self._ancestry_shape()
         its, out = self._fetch_rows(self.lib.gph_engine_ancestry_fetch_rows, held, ri, np.int32, with_iters=True)
         return its, out[:, :ri]
+
+    # ---- sampled genealogies of selected loci (gph_engine_gene_trees_*): gathered on the device, one row of records per call
+    def enable_gene_trees(self, capacity, loci=None, max_bytes=0):
+        """a device buffer of `capacity` samples of the selected loci (global 0-based indices, strictly increasing; None:
+        all loci of this rank; indices of other ranks' blocks are ignored); capacity 0 switches the feature off.  ValueError
+        for a negative index or a list that is not increasing, MemoryError when the buffer would exceed max_bytes (0: 256 MB)"""
+        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
+        rc = self.lib.gph_engine_gene_trees_enable(self.engine, int(capacity), None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   0 if sel is None else len(sel), int(max_bytes))
+        if rc == GPH_EFULL:
+            raise MemoryError("gphocs_hip: the gene-trees row buffer exceeds max_bytes (GPH_EFULL)")
+        if rc == -1:
+            raise ValueError("gphocs_hip: gene_trees_enable refused the capacity or the selection (GPH_EARG)")
+        self._chk(rc, "gene_trees_enable")
+
+    def sample_gene_trees(self, it):
+        """one sample of the current state, labelled iteration `it`; BufferError when the row buffer is full"""
+        self._sample(self.lib.gph_engine_gene_trees_sample, "gene-trees", "gene_trees", int(it))
+
+    def _gene_trees_shape(self):
+        q, N, rb, held = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+        off = (C.c_int32 * GT_OFFSETS)()
+        self._chk(self.lib.gph_engine_gene_trees_shape(self.engine, C.byref(q), C.byref(N), C.byref(rb), off, C.byref(held)), "gene_trees_shape")
+        return q.value, N.value, rb.value, off, held.value
+
+    def gene_trees(self, raw=False):
+        """the samples taken since the last call (the device buffer is emptied), S samples of this rank's Q selected loci: a
+        dict of iters[S], loci[Q] (global indices), age / father / left / right / npop [S, Q, N], root / num_migs / dataLnL /
+        genLnL [S, Q], and the live migrations in `living` order, mig_branch / mig_band / mig_spop / mig_tpop / mig_age
+        [S, Q, 10] (-1 and age 0 beyond num_migs).  raw=True adds records: the bytes as fetched, uint8 [S, Q, record_bytes]"""
+        Q, N, rb, off, held = self._gene_trees_shape()
+        loci = np.zeros(max(Q, 1), dtype=np.int64)
+        cnt = C.c_int64()
+        self._chk(self.lib.gph_engine_gene_trees_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)),
+                  "gene_trees_selected")
+        buf = np.zeros((max(held, 1), max(Q * rb, 1)), dtype=np.uint8)
+        its = np.zeros(max(held, 1), dtype=np.int32)
+        got = C.c_int32()
+        self._chk(self.lib.gph_engine_gene_trees_fetch(self.engine, its.ctypes.data_as(C.POINTER(C.c_int32)), buf.ctypes.data, buf.shape[0],
+                                                       C.byref(got)), "gene_trees_fetch")
+        S, M = got.value, GT_MAX_MIGS
+        rec = np.ascontiguousarray(buf[:S, :Q * rb]).reshape(S, Q, rb)
+        out = dict(iters=its[:S].copy(), loci=loci[:Q].copy())
+        shapes = dict(age=((S, Q, N), np.float64), father=((S, Q, N), np.int32), left=((S, Q, N), np.int32), right=((S, Q, N), np.int32),
+                      npop=((S, Q, N), np.int32), root=((S, Q), np.int32), num_migs=((S, Q), np.int32), dataLnL=((S, Q), np.float64),
+                      genLnL=((S, Q), np.float64), mig_branch=((S, Q, M), np.int32), mig_band=((S, Q, M), np.int32),
+                      mig_spop=((S, Q, M), np.int32), mig_tpop=((S, Q, M), np.int32), mig_age=((S, Q, M), np.float64))
+        for k, (shp, dt) in shapes.items():
+            out[k] = np.zeros(shp, dtype=dt)
+        if S * Q:
+            self._chk(self.lib.gph_gene_trees_decode(rec.ctypes.data, S * Q, rb, off, N, *[out[k].ctypes.data for k in shapes]), "gene_trees_decode")
+        if raw:
+            out["records"] = rec
+        return out
 
     def hbm_bytes(self):
         b = C.c_double()

@@ -25,6 +25,7 @@
 #include "gph_coalstats.h"
 #include "gph_timeslices.h"
 #include "gph_ancestry.h"
+#include "gph_genetrees.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
 
@@ -364,7 +365,7 @@ __global__ void k_debug_math(GphKargs KA, const double *x, const double *y, int 
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 17     // kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 18     // kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -454,6 +455,9 @@ struct gph_engine {
   // per-locus, per-sample migration ancestry (gph_ancestry.h): fp64 accumulators [L][ncol] in slot order, the integer rows
   // of the samples and their iterations
   struct { double *d_acc = nullptr; SmRows rows; int32_t ncol = 0; int64_t samples = 0; GphAnShape shape = {}; std::vector<int32_t> iters; std::string name; } an;
+  // sampled genealogies of selected loci (gph_genetrees.h): the rows of records, the selected loci of this rank (global indices,
+  // increasing) with their slots in HBM, and the iterations of the rows held
+  struct { SmRows rows; GphGtShape shape = {}; int32_t *d_sel = nullptr; std::vector<int64_t> sel; std::vector<int32_t> iters; } gt;
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -1109,6 +1113,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->d_part); dev_free(e->dev.err);
   dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
+  dev_free(e->gt.rows.d); dev_free(e->gt.d_sel);
   for (void *p : e->deferred_free) dev_free(p);
   e->deferred_free.clear();
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
@@ -1435,8 +1440,9 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   /* summaries of the old chain do not carry over; the locus-rate columns come and go with `locus-mut-rate VAR` */
   if (e->ls.d && e->ls.ncol != gph_ls_columns(e->cfg.K, e->cfg.B, e->var_rates)) { int rce = gph_engine_locus_summary_enable(e, 1); if (rce) return rce; }
   e->ls.samples = e->an.samples = 0;
-  e->cs.rows.fill = e->ts.rows.fill = e->an.rows.fill = 0;
+  e->cs.rows.fill = e->ts.rows.fill = e->an.rows.fill = e->gt.rows.fill = 0;
   e->an.iters.clear();
+  e->gt.iters.clear();
   { int rcz = acc_zero(e, e->ls.d, sizeof(double) * (size_t)e->ls.ncol * e->L); if (rcz) return rcz; }
   { int rcz = acc_zero(e, e->an.d_acc, sizeof(double) * (size_t)e->an.ncol * e->L); if (rcz) return rcz; }
   LAUNCH(e, 3, k_init, e->seedz, (const double *)e->d_mutRate, e->init_predraws);
@@ -2917,6 +2923,117 @@ const char *gph_engine_ancestry_column_name(gph_engine *e, int32_t which, int32_
     e->an.name = blk == 0 ? "any." + std::to_string(i) : "hit." + std::to_string(blk - 1) + "." + std::to_string(i);
   } else return nullptr;
   return e->an.name.c_str();
+}
+
+// ---- sampled genealogies of selected loci (gph_genetrees.h)
+static_assert((int)GT_O_COUNT == (int)GPH_GT_O_COUNT && (int)GT_O_LIVING == (int)GPH_GT_O_LIVING && GPH_MAX_MIGS == GPH_GT_MAX_MIGS && MG_COUNT == 6,
+              "the record layout include/gphocs_hip.h documents");
+int gph_engine_gene_trees_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity_rows < 0 || (loci && nloci < 0)) return GPH_EARG;
+  if (loci)
+    for (int64_t k = 0; k < nloci; k++)
+      if (loci[k] < 0 || (k > 0 && loci[k] <= loci[k - 1])) return GPH_EARG;
+  SETDEV(e);
+  rows_free(e, e->gt.rows);
+  eng_free(e, e->gt.d_sel);
+  e->gt.d_sel = nullptr;
+  e->gt.sel.clear();
+  e->gt.iters.clear();
+  e->gt.shape = GphGtShape{};
+  if (capacity_rows == 0) return 0;
+  const int64_t L = e->L, lb = e->cfg.locus_begin;
+  std::vector<int64_t> sel;
+  if (!loci) for (int64_t g = 0; g < L; g++) sel.push_back(lb + g);
+  else for (int64_t k = 0; k < nloci; k++) if (loci[k] >= lb && loci[k] < lb + L) sel.push_back(loci[k]);
+  GphGtShape h;
+  gph_gt_shape(e->lay, h);
+  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)256 << 20;
+  const int64_t need = (int64_t)capacity_rows * (int64_t)sel.size() * h.img.bytes;
+  if (need > limit) {
+    fprintf(stderr, "gphocs_hip: gene trees: the row buffer needs %lld bytes (%d rows x %lld loci x %d bytes a record), the limit is %lld\n",
+            (long long)need, (int)capacity_rows, (long long)sel.size(), (int)h.img.bytes, (long long)limit);
+    return GPH_EFULL;
+  }
+  /* selected -> slot: slots are sorted by decreasing pattern count, h_orig[j] is the local locus slot j holds */
+  std::vector<int32_t> slot_of((size_t)L), sel_slot(sel.size());
+  for (int64_t j = 0; j < L; j++) slot_of[(size_t)e->h_orig[j]] = (int32_t)j;
+  for (size_t q = 0; q < sel.size(); q++) sel_slot[q] = slot_of[(size_t)(sel[q] - lb)];
+  if (dev_alloc((void **)&e->gt.d_sel, sizeof(int32_t) * sel_slot.size())) { e->gt.d_sel = nullptr; return GPH_EHIP; }
+  if (!sel_slot.empty()) { int rc = h2d(e, e->gt.d_sel, sel_slot.data(), sizeof(int32_t) * sel_slot.size()); if (rc) return rc; }
+  if (rows_alloc(e->gt.rows, (size_t)h.img.bytes, (int32_t)sel.size(), capacity_rows)) {
+    eng_free(e, e->gt.d_sel);
+    e->gt.d_sel = nullptr;
+    return GPH_EHIP;
+  }
+  e->gt.shape = h;
+  e->gt.sel.swap(sel);
+  return 0;
+}
+
+// one sample of the current state, queued on the engine's stream
+int gph_engine_gene_trees_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->gt.rows.d) return GPH_ESTATE;
+  if (e->gt.rows.fill >= e->gt.rows.cap) return GPH_EFULL;
+  SETDEV(e);
+  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
+  const GphGtShape &h = e->gt.shape;
+  const int nsel = e->gt.rows.n, L = (int)e->L;
+  const int groups = (nsel + h.G - 1) / h.G;
+  if (groups > 0) {        /* (a rank without a selected locus launches nothing: a grid of no blocks is no legal launch) */
+    char *row = (char *)rows_next(e->gt.rows);
+    int tms;
+    { int rcb = sample_begin(e, 17, tms); if (rcb) return rcb; }
+#ifdef GPH_HOSTEMU
+    for (int w = 0; w < groups; w++) gene_trees_workgroup(e->lay, h, (const char *)e->dev.pages, e->gt.d_sel, nsel, L, row, w);
+#else
+    hipLaunchKernelGGL(k_gene_trees, dim3((unsigned)groups), dim3(GPH_GT_THREADS), 0, e->stream,
+                       e->lay, h, (const char *)e->dev.pages, (const int32_t *)e->gt.d_sel, nsel, L, row);
+    HIPCHK(hipGetLastError());
+#endif
+    sample_end(e, 17, 1, tms);
+  }
+  e->gt.iters.push_back(iteration);
+  e->gt.rows.fill++;
+  return 0;
+}
+
+int gph_engine_gene_trees_shape(gph_engine *e, int64_t *selected, int32_t *nodes, int32_t *record_bytes, int32_t *offsets, int32_t *rows_held)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->gt.rows.d != nullptr;
+  if (selected) *selected = on ? (int64_t)e->gt.sel.size() : 0;
+  if (nodes) *nodes = on ? e->lay.N : 0;
+  if (record_bytes) *record_bytes = on ? e->gt.shape.img.bytes : 0;
+  if (offsets) for (int k = 0; k < GT_O_COUNT; k++) offsets[k] = on ? e->gt.shape.off[k] : 0;
+  if (rows_held) *rows_held = e->gt.rows.fill;
+  return 0;
+}
+
+int gph_engine_gene_trees_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
+{
+  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
+  if (!e->gt.rows.d) return GPH_ESTATE;
+  *count = (int64_t)e->gt.sel.size();
+  if (max_loci < *count) return out ? GPH_EARG : 0;
+  for (size_t q = 0; q < e->gt.sel.size(); q++) out[q] = e->gt.sel[q];
+  return 0;
+}
+
+int gph_engine_gene_trees_fetch(gph_engine *e, int32_t *iters, void *out, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || (!iters && max_rows > 0)) return GPH_EARG;
+  SmRows &b = e->gt.rows;
+  if (!b.d) return GPH_ESTATE;
+  if (max_rows < b.fill || (!out && b.fill > 0 && b.n > 0)) return GPH_EARG;       /* (rows without records need no `out`) */
+  SETDEV(e);
+  for (int32_t r = 0; r < b.fill; r++) iters[r] = e->gt.iters[(size_t)r];
+  if (b.n == 0) { *rows = b.fill; b.fill = 0; }       /* (rows without records: nothing to copy) */
+  else { int rc = rows_fetch(e, b, out, rows); if (rc) return rc; }
+  e->gt.iters.clear();
+  return 0;
 }
 
 } // extern "C"

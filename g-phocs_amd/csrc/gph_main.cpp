@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -28,6 +28,13 @@
 // --ancestry PREFIX: PREFIX.loci.tsv and PREFIX.samples.tsv, which sample's lineage went through which migration band at
 // which locus (gph_run_control_file_ex4); the ranks' PREFIX.ancestry.part<r> become the two files once every child has
 // exited 0 (gph_ancestry_write), and are removed otherwise (gph_ancestry_discard).  Composes with every option above.
+//
+// --gene-trees PREFIX: PREFIX.trees.tsv, the sampled genealogy of every selected locus at every sample as a line of extended
+// Newick with populations and migration events on the branches (gph_run_control_file_ex5).  --gene-trees-loci SPEC selects
+// loci: a comma list of i, i-j or i-j:step, 0-based in sequence-file order (default all); --gene-trees-rows N: rows of the
+// device buffer between two flushes (default 64, fewer when a row is large).  The ranks' PREFIX.trees.part<r> become the file
+// once every child has exited 0 (gph_gene_trees_write), and are removed otherwise (gph_gene_trees_discard).  Composes with
+// every option above.
 #include "gphocs_hip.h"
 #include <dlfcn.h>
 #include <libgen.h>
@@ -100,15 +107,15 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
 int main(int argc, char **argv)
 {
   int verbose = 0, device = 0, gpus = 1, i = 1;
-  const char *summary = nullptr, *coal = nullptr, *ancestry = nullptr;
-  int coal_rows = 0, slices = 0;
+  const char *summary = nullptr, *coal = nullptr, *ancestry = nullptr, *trees = nullptr, *trees_loci = nullptr;
+  int coal_rows = 0, slices = 0, trees_rows = 0;
   for (; i < argc && argv[i][0] == '-'; i++) {
     if (!strcmp(argv[i], "-v") || !strcmp(argv[i], "--verbose")) verbose = 1;
     else if (!strcmp(argv[i], "-d") && i + 1 < argc) device = atoi(argv[++i]);
@@ -118,11 +125,15 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--coal-stats-rows") && i + 1 < argc) coal_rows = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--time-slices") && i + 1 < argc) { slices = atoi(argv[++i]); if (slices < 1) return usage(argv[0]); }
     else if (!strcmp(argv[i], "--ancestry") && i + 1 < argc) ancestry = argv[++i];
+    else if (!strcmp(argv[i], "--gene-trees") && i + 1 < argc) trees = argv[++i];
+    else if (!strcmp(argv[i], "--gene-trees-loci") && i + 1 < argc) trees_loci = argv[++i];
+    else if (!strcmp(argv[i], "--gene-trees-rows") && i + 1 < argc) { trees_rows = atoi(argv[++i]); if (trees_rows < 1) return usage(argv[0]); }
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
   if (i >= argc || gpus < 1 || gpus > 64) return usage(argv[0]);
   if (slices && !coal) { fprintf(stderr, "%s: --time-slices needs -s PREFIX\n", argv[0]); return usage(argv[0]); }
+  if ((trees_loci || trees_rows) && !trees) { fprintf(stderr, "%s: --gene-trees-loci and --gene-trees-rows need --gene-trees PREFIX\n", argv[0]); return usage(argv[0]); }
   const char *ctl = argv[i], *ctl2 = i + 1 < argc ? argv[i + 1] : nullptr;
   char self[PATH_MAX];
   ssize_t k = readlink("/proc/self/exe", self, sizeof self - 1);
@@ -131,6 +142,7 @@ int main(int argc, char **argv)
   const std::string dir = dirname(self);
   if (gpus == 1) {
     void *h = load_engine(dir, ctl, ctl2);
+    if (trees) return sym<decltype(&gph_run_control_file_ex5)>(h, "gph_run_control_file_ex5")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices, ancestry, 0, trees, trees_loci, trees_rows) ? 1 : 0;
     if (ancestry) return sym<decltype(&gph_run_control_file_ex4)>(h, "gph_run_control_file_ex4")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices, ancestry, 0) ? 1 : 0;
     if (slices) return sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices) ? 1 : 0;
     if (coal) return sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows) ? 1 : 0;
@@ -179,7 +191,8 @@ int main(int argc, char **argv)
         comm = create_rccl(mb->id, r, gpus, mydev);
       }
       if (!comm) { fprintf(stderr, "G-PhoCS-hip: rank %d could not join the communicator\n", r); _exit(2); }
-      int rc = ancestry ? sym<decltype(&gph_run_control_file_ex4)>(h, "gph_run_control_file_ex4")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices, ancestry, 0) :
+      int rc = trees ? sym<decltype(&gph_run_control_file_ex5)>(h, "gph_run_control_file_ex5")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices, ancestry, 0, trees, trees_loci, trees_rows) :
+               ancestry ? sym<decltype(&gph_run_control_file_ex4)>(h, "gph_run_control_file_ex4")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices, ancestry, 0) :
                slices ? sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices) :
                coal ? sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows) :
                summary ? sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, mydev, verbose, comm, summary)
@@ -233,6 +246,12 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(summary); bad = 1; }
     if (bad && out) unlink(summary);
   }
+  void *hgt = nullptr;
+  if (trees) {
+    /* the ranks' parts into PREFIX.trees.tsv, by the library that wrote them; first, so that a later failure removes one file */
+    hgt = load_engine(dir, ctl, ctl2);
+    if (!bad && sym<decltype(&gph_gene_trees_write)>(hgt, "gph_gene_trees_write")(trees, gpus)) bad = 1;
+  }
   void *han = nullptr;
   if (ancestry) {
     /* the ranks' parts into the two files, by the library that wrote them; first, so that a later failure removes two files */
@@ -249,5 +268,6 @@ int main(int argc, char **argv)
     if (slices && bad) sym<decltype(&gph_time_slices_discard)>(h, "gph_time_slices_discard")(coal, gpus);
   }
   if (ancestry && bad) sym<decltype(&gph_ancestry_discard)>(han, "gph_ancestry_discard")(ancestry, gpus);
+  if (trees && bad) sym<decltype(&gph_gene_trees_discard)>(hgt, "gph_gene_trees_discard")(trees, gpus);
   return bad;
 }

@@ -3,12 +3,14 @@
 // file, same trace file.  Everything per-locus runs on the MI355X engine; there is no CPU path.
 #include "../../include/gphocs_hip.h"
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <limits>
 #include <string>
 #include <vector>
 #include <unistd.h>
@@ -388,6 +390,303 @@ extern "C" int gph_ancestry_write(const char *prefix, int32_t ranks)
   return ok ? GPH_OK : GPH_EARG;
 }
 
+// ---- sampled genealogies (`--gene-trees PREFIX`): records as plain arrays, one genealogy as a line of extended Newick, and
+// the ranks' parts into PREFIX.trees.tsv
+namespace {
+// a name that may stand in a tree: no white space, none of the characters extended Newick reserves
+bool gt_name_ok(const char *s)
+{
+  if (!s || !*s) return false;
+  for (; *s; s++) if (isspace((unsigned char)*s) || strchr("()[],:;'=&", *s)) return false;
+  return true;
+}
+std::string gt_len(double d)
+{
+  char buf[40];
+  snprintf(buf, sizeof buf, "%.10g", d);
+  return buf;
+}
+struct GtTree {
+  int n, N;
+  const double *age;
+  const int32_t *father, *left, *right, *npop;
+  int root, nm;
+  const int32_t *mbr, *mband;
+  const double *mage;
+  const char *const *pops; int K;
+  const char *const *bands; int B;
+  const char *const *labels;
+};
+// sub(v) of the grammar in include/gphocs_hip.h, appended to out; false: the record is no tree
+bool gt_sub(const GtTree &t, int v, int depth, std::string &out)
+{
+  if (v < 0 || v >= t.N || depth > t.N) return false;
+  const int p = t.npop[v];
+  if (p < 0 || p >= t.K) return false;
+  std::vector<int> ms;                              /* the live migrations on the branch of v, by age; equal ages in `living` order */
+  if (v != t.root)
+    for (int k = 0; k < t.nm; k++) if (t.mbr[k] == v) ms.push_back(k);
+  std::stable_sort(ms.begin(), ms.end(), [&](int a, int b) { return t.mage[a] < t.mage[b]; });
+  out.append(ms.size(), '(');
+  if (v < t.n) out += t.labels[v];
+  else {
+    out += '(';
+    if (!gt_sub(t, t.left[v], depth + 1, out)) return false;
+    out += ',';
+    if (!gt_sub(t, t.right[v], depth + 1, out)) return false;
+    out += ')';
+  }
+  out += "[&pop=";
+  out += t.pops[p];
+  out += ']';
+  double a = t.age[v];
+  for (int k : ms) {
+    const int b = t.mband[k];
+    if (b < 0 || b >= t.B) return false;
+    out += ':';
+    out += gt_len(t.mage[k] - a);
+    out += ")[&mig=";
+    out += t.bands[b];
+    out += ']';
+    a = t.mage[k];
+  }
+  if (v != t.root) {
+    const int f = t.father[v];
+    if (f < 0 || f >= t.N) return false;
+    out += ':';
+    out += gt_len(t.age[f] - a);
+  }
+  return true;
+}
+int gt_newick(const GtTree &t, std::string &out)
+{
+  for (int p = 0; p < t.K; p++) if (!gt_name_ok(t.pops[p])) { fprintf(stderr, "gphocs_hip: gene trees: the population name '%s' cannot stand in a tree (white space or one of ()[],:;'=&)\n", t.pops[p] ? t.pops[p] : ""); return GPH_EARG; }
+  for (int i = 0; i < t.n; i++) if (!gt_name_ok(t.labels[i])) { fprintf(stderr, "gphocs_hip: gene trees: the leaf label '%s' cannot stand in a tree (white space or one of ()[],:;'=&)\n", t.labels[i] ? t.labels[i] : ""); return GPH_EARG; }
+  for (int b = 0; b < t.B; b++) {
+    const char *nm = t.bands[b], *arrow = nm ? strstr(nm, "->") : nullptr;
+    const bool ok = arrow && gt_name_ok(std::string(nm, arrow).c_str()) && gt_name_ok(arrow + 2);
+    if (!ok) { fprintf(stderr, "gphocs_hip: gene trees: the band name '%s' is not <src>-><tgt> of two names that can stand in a tree\n", nm ? nm : ""); return GPH_EARG; }
+  }
+  out.clear();
+  if (t.n < 1 || t.nm < 0 || !gt_sub(t, t.root, 0, out)) return GPH_EARG;
+  out += ';';
+  return GPH_OK;
+}
+}   // namespace
+
+extern "C" int gph_gene_tree_newick(int32_t n, const double *age, const int32_t *father, const int32_t *left, const int32_t *right,
+                                    const int32_t *npop, int32_t root, int32_t num_migs, const int32_t *mig_branch, const int32_t *mig_band,
+                                    const double *mig_age, const char *const *pop_names, int32_t K, const char *const *band_names, int32_t B,
+                                    const char *const *leaf_labels, char *out, size_t out_cap, size_t *out_len)
+{
+  if (n < 1 || !age || !father || !left || !right || !npop || !pop_names || K < 1 || B < 0 || (B > 0 && !band_names) || !leaf_labels ||
+      num_migs < 0 || (num_migs > 0 && (!mig_branch || !mig_band || !mig_age)))
+    return GPH_EARG;
+  const GtTree t = {n, 2 * n - 1, age, father, left, right, npop, root, num_migs, mig_branch, mig_band, mig_age, pop_names, K, band_names, B, leaf_labels};
+  std::string text;
+  const int rc = gt_newick(t, text);
+  if (rc) return rc;
+  if (out_len) *out_len = text.size();
+  if (!out) return GPH_OK;
+  if (out_cap < text.size() + 1) return 2;
+  memcpy(out, text.c_str(), text.size() + 1);
+  return GPH_OK;
+}
+
+extern "C" int gph_gene_trees_decode(const void *records, int64_t count, int32_t record_bytes, const int32_t *off, int32_t N,
+                                     double *age, int32_t *father, int32_t *left, int32_t *right, int32_t *npop, int32_t *root, int32_t *num_migs,
+                                     double *dataLnL, double *genLnL, int32_t *mig_branch, int32_t *mig_band, int32_t *mig_spop, int32_t *mig_tpop,
+                                     double *mig_age)
+{
+  if (count < 0 || (count > 0 && !records) || !off || N < 1 || record_bytes < 16 * N) return GPH_EARG;
+  const int M = GPH_GT_MAX_MIGS;
+  for (int64_t r = 0; r < count; r++) {
+    const char *rec = (const char *)records + (size_t)r * record_bytes;
+    for (int v = 0; v < N; v++) {
+      const char *nd = rec + off[GPH_GT_O_NODES] + 16 * v;
+      int16_t w[4];
+      memcpy(w, nd + 8, 8);
+      if (age) memcpy(age + (size_t)r * N + v, nd, 8);
+      if (father) father[(size_t)r * N + v] = w[0];
+      if (left) left[(size_t)r * N + v] = w[1];
+      if (right) right[(size_t)r * N + v] = w[2];
+      if (npop) npop[(size_t)r * N + v] = w[3];
+    }
+    int32_t rt, nm;
+    memcpy(&rt, rec + off[GPH_GT_O_ROOT], 4);
+    memcpy(&nm, rec + off[GPH_GT_O_NUM_MIGS], 4);
+    nm = nm < 0 ? 0 : nm > M ? M : nm;
+    if (root) root[r] = rt;
+    if (num_migs) num_migs[r] = nm;
+    if (dataLnL) memcpy(dataLnL + r, rec + off[GPH_GT_O_DATALNL], 8);
+    if (genLnL) memcpy(genLnL + r, rec + off[GPH_GT_O_GENLNL], 8);
+    for (int k = 0; k < M; k++) {
+      int16_t m = -1, f[6] = {-1, -1, -1, -1, -1, -1};
+      double a = 0.0;
+      if (k < nm) memcpy(&m, rec + off[GPH_GT_O_LIVING] + 2 * k, 2);
+      if (m >= 0 && m < M) {
+        memcpy(f, rec + off[GPH_GT_O_MIG_I] + 12 * m, 12);
+        memcpy(&a, rec + off[GPH_GT_O_MIG_AGE] + 8 * m, 8);
+      }
+      const size_t at = (size_t)r * M + k;
+      if (mig_branch) mig_branch[at] = f[0];
+      if (mig_band) mig_band[at] = f[1];
+      if (mig_spop) mig_spop[at] = f[2];
+      if (mig_tpop) mig_tpop[at] = f[3];
+      if (mig_age) mig_age[at] = a;
+    }
+  }
+  return GPH_OK;
+}
+
+// rank r's part PREFIX.trees.part<r>: magic | n, K, B, bytes of a record, the offsets inside one (int32) | selected loci of
+// the rank (int64), their global indices (int64 each) | byte count of the names (int32), the names, NUL-separated: K
+// populations, B bands, n leaf labels, one sequence-file name per selected locus | per sample: iteration (int32), the row |
+// trailer, written when the rank closes its part: the number of samples (int64)
+namespace {
+const char GT_MAGIC[8] = {'G', 'P', 'H', 'G', 'T', '1', '\n', 0};
+const int GT_NH = 4 + GPH_GT_O_COUNT;
+std::string gt_part_path(const char *prefix, int r) { return std::string(prefix) + ".trees.part" + std::to_string(r); }
+struct GtPart {
+  FILE *f = nullptr;
+  int32_t h[GT_NH] = {0};
+  std::vector<int64_t> sel;
+  std::vector<std::string> names;
+  int64_t count = 0;
+  ~GtPart() { if (f) fclose(f); }
+  bool open(const std::string &path)
+  {
+    f = fopen(path.c_str(), "rb");
+    char magic[8];
+    int64_t nsel = -1;
+    int32_t nbytes = -1;
+    bool ok = f && fread(magic, 1, 8, f) == 8 && !memcmp(magic, GT_MAGIC, 8) && fread(h, 4, (size_t)GT_NH, f) == (size_t)GT_NH &&
+              fread(&nsel, 8, 1, f) == 1 && nsel >= 0 && h[0] >= 1 && h[1] >= 1 && h[2] >= 0 && h[3] >= 16 * (2 * h[0] - 1);
+    if (ok && nsel > 0) { sel.resize((size_t)nsel); ok = fread(sel.data(), 8, (size_t)nsel, f) == (size_t)nsel; }
+    ok = ok && fread(&nbytes, 4, 1, f) == 1 && nbytes >= 0;
+    if (ok) {
+      std::vector<char> buf((size_t)nbytes + 1, 0);
+      ok = fread(buf.data(), 1, (size_t)nbytes, f) == (size_t)nbytes;
+      for (size_t at = 0; ok && at < (size_t)nbytes; at += strlen(buf.data() + at) + 1) names.push_back(buf.data() + at);
+      ok = ok && (int64_t)names.size() == (int64_t)h[1] + h[2] + h[0] + nsel;
+    }
+    if (ok) {
+      const long body = ftell(f);
+      ok = body > 0 && fseek(f, -8, SEEK_END) == 0;
+      const long end = ok ? ftell(f) : 0;
+      ok = ok && fread(&count, 8, 1, f) == 1 && count >= 0 && end - body == (long)(count * (4 + nsel * (int64_t)h[3])) && fseek(f, body, SEEK_SET) == 0;
+    }
+    if (!ok) fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str());
+    return ok;
+  }
+};
+}   // namespace
+
+extern "C" int gph_gene_trees_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  for (int r = 0; r < ranks; r++) remove(gt_part_path(prefix, r).c_str());
+  unlink((std::string(prefix) + ".trees.tsv").c_str());     /* (a file only: whatever else sits under that name is not ours) */
+  return GPH_OK;
+}
+
+extern "C" int gph_gene_trees_write(const char *prefix, int32_t ranks)
+{
+  if (!prefix || ranks < 1) return GPH_EARG;
+  const std::string path = std::string(prefix) + ".trees.tsv";
+  FILE *out = nullptr;
+  bool ok = true;
+  {
+    std::vector<GtPart> P((size_t)ranks);
+    for (int r = 0; r < ranks && ok; r++) {
+      ok = P[(size_t)r].open(gt_part_path(prefix, r));
+      if (ok && r > 0 && (memcmp(P[0].h, P[(size_t)r].h, sizeof P[0].h) || P[0].count != P[(size_t)r].count)) {
+        fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", gt_part_path(prefix, r).c_str());
+        ok = false;
+      }
+    }
+    if (ok && !(out = fopen(path.c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s\n", path.c_str()); ok = false; }
+    if (ok) {
+      const int n = P[0].h[0], K = P[0].h[1], B = P[0].h[2], rb = P[0].h[3], N = 2 * n - 1, M = GPH_GT_MAX_MIGS;
+      const int32_t *off = P[0].h + 4;
+      std::vector<const char *> pops, bands, labels;
+      for (int p = 0; p < K; p++) pops.push_back(P[0].names[(size_t)p].c_str());
+      for (int b = 0; b < B; b++) bands.push_back(P[0].names[(size_t)(K + b)].c_str());
+      for (int i = 0; i < n; i++) labels.push_back(P[0].names[(size_t)(K + B + i)].c_str());
+      std::vector<double> age((size_t)N), mage((size_t)M);
+      std::vector<int32_t> fa((size_t)N), le((size_t)N), ri((size_t)N), np((size_t)N), mbr((size_t)M), mband((size_t)M);
+      std::vector<char> row;
+      std::string tree;
+      fprintf(out, "iter\tlocus\tname\tdataLnL\tgenLnL\ttmrca\tnumMigs\ttree\n");
+      for (int64_t s = 0; s < P[0].count && ok; s++) {
+        int32_t it0 = 0;
+        for (int r = 0; r < ranks && ok; r++) {
+          GtPart &p = P[(size_t)r];
+          int32_t it = 0;
+          row.resize(p.sel.size() * (size_t)rb);
+          ok = fread(&it, 4, 1, p.f) == 1 && (row.empty() || fread(row.data(), 1, row.size(), p.f) == row.size());
+          if (r == 0) it0 = it;
+          if (!ok || it != it0) { fprintf(stderr, "gphocs_hip: %s ended early or holds another sample than rank 0's part\n", gt_part_path(prefix, r).c_str()); ok = false; break; }
+          for (size_t q = 0; q < p.sel.size() && ok; q++) {
+            int32_t root = 0, nm = 0;
+            double dl = 0, gl = 0;
+            gph_gene_trees_decode(row.data() + q * (size_t)rb, 1, rb, off, N, age.data(), fa.data(), le.data(), ri.data(), np.data(), &root, &nm,
+                                  &dl, &gl, mbr.data(), mband.data(), nullptr, nullptr, mage.data());
+            const GtTree t = {n, N, age.data(), fa.data(), le.data(), ri.data(), np.data(), root, nm, mbr.data(), mband.data(), mage.data(),
+                              pops.data(), K, bands.data(), B, labels.data()};
+            if (gt_newick(t, tree)) { fprintf(stderr, "gphocs_hip: gene trees: the record of locus %lld at iteration %d is no tree\n", (long long)p.sel[q], (int)it); ok = false; break; }
+            fprintf(out, "%d\t%lld\t%s\t%.10g\t%.10g\t%.10g\t%d\t%s\n", (int)it, (long long)p.sel[q], p.names[(size_t)(K + B + n) + q].c_str(), dl, gl,
+                    age[(size_t)root], (int)nm, tree.c_str());
+          }
+        }
+      }
+    }
+    if (out && (ferror(out) | fclose(out)) != 0) { fprintf(stderr, "gphocs_hip: writing %s failed\n", path.c_str()); ok = false; }
+  }
+  for (int r = 0; r < ranks; r++) remove(gt_part_path(prefix, r).c_str());
+  if (!ok && out) remove(path.c_str());
+  return ok ? GPH_OK : GPH_EARG;
+}
+
+// the selection of `--gene-trees-loci SPEC`: a comma list of i, i-j (both ends included) or i-j:step over 0 .. L - 1, sorted;
+// an index named twice or beyond the loci is refused by name
+static int gt_parse_spec(const char *spec, int64_t L, std::vector<int64_t> &sel, bool &all)
+{
+  sel.clear();
+  all = !spec || !strcmp(spec, "all");
+  if (all) return GPH_OK;
+  const char *p = spec;
+  auto number = [&](int64_t &v) {
+    if (!isdigit((unsigned char)*p)) return false;
+    char *end;
+    const long long x = strtoll(p, &end, 10);
+    if (x < 0 || x > std::numeric_limits<int32_t>::max()) return false;
+    v = x; p = end;
+    return true;
+  };
+  while (true) {
+    int64_t a, b, step = 1;
+    if (!number(a)) break;
+    b = a;
+    if (*p == '-') { p++; if (!number(b) || b < a) break; if (*p == ':') { p++; if (!number(step) || step < 1) break; } }
+    if (a >= L) { fprintf(stderr, "gphocs_hip: --gene-trees-loci: locus %lld is beyond the %lld loci of the sequence file (indices are 0-based)\n", (long long)a, (long long)L); return GPH_EARG; }
+    for (int64_t g = a; g <= b; g += step) {
+      if (g >= L) { fprintf(stderr, "gphocs_hip: --gene-trees-loci: locus %lld is beyond the %lld loci of the sequence file (indices are 0-based)\n", (long long)g, (long long)L); return GPH_EARG; }
+      sel.push_back(g);
+    }
+    if (*p == ',') { p++; continue; }
+    if (*p == 0) {
+      std::sort(sel.begin(), sel.end());
+      for (size_t k = 1; k < sel.size(); k++)
+        if (sel[k] == sel[k - 1]) { fprintf(stderr, "gphocs_hip: --gene-trees-loci: locus %lld is named twice\n", (long long)sel[k]); return GPH_EARG; }
+      return GPH_OK;
+    }
+    break;
+  }
+  fprintf(stderr, "gphocs_hip: --gene-trees-loci: '%s' is not a comma list of i, i-j or i-j:step (0-based indices), nor 'all'\n", spec);
+  return GPH_EARG;
+}
+
 // the names a part's header carries, and writing one
 namespace {
 // the leaves' names as the statistics files print them: the second haploid of a diploid has no name of its own and takes
@@ -447,9 +746,12 @@ int write_rows(FILE *part, const void *rows, size_t esz, int32_t n, int32_t got,
 static int run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
                             int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user, gph_comm *comm,
                             const char *summary_path = nullptr, const char *cs_prefix = nullptr, int32_t cs_capacity = 0,
-                            int32_t ts_slices = 0, const char *an_prefix = nullptr, int32_t an_capacity = 0)
+                            int32_t ts_slices = 0, const char *an_prefix = nullptr, int32_t an_capacity = 0,
+                            const char *gt_prefix = nullptr, const char *gt_spec = nullptr, int32_t gt_capacity = 0)
 {
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce && !comm)) return GPH_EARG;
+  if (!gt_prefix && (gt_spec || gt_capacity != 0)) { fprintf(stderr, "gphocs_hip: a gene-trees selection or row count needs a gene-trees prefix\n"); return GPH_EARG; }
+  if (gt_capacity < 0) return GPH_EARG;
   if (ts_slices < 0 || (ts_slices > 0 && !cs_prefix)) { fprintf(stderr, "gphocs_hip: time slices need a coal-stats prefix\n"); return GPH_EARG; }
   const bool lead = rank == 0;   /* rank 0 talks and writes the trace file; every rank runs the same chain */
   gph_control *C = nullptr;
@@ -461,17 +763,18 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_control_info info;
   char err[512] = "";
   int rc;
-  FILE *trace = nullptr, *cs_part = nullptr, *ts_part = nullptr, *an_part = nullptr;
+  FILE *trace = nullptr, *cs_part = nullptr, *ts_part = nullptr, *an_part = nullptr, *gt_part = nullptr;
   /* a failed run leaves no statistics file and no part behind (several ranks: the caller removes every rank's part) */
   auto discard_all = [&]() {
     if (world != 1) return;
+    if (gt_prefix) gph_gene_trees_discard(gt_prefix, 1);
     if (an_prefix) gph_ancestry_discard(an_prefix, 1);
     if (cs_prefix) gph_coal_stats_discard(cs_prefix, 1);
     if (ts_slices) gph_time_slices_discard(cs_prefix, 1);
   };
   auto fail = [&](int code, const char *what) {
     fprintf(stderr, "gphocs_hip: %s failed (status %d)%s%s\n", what, code, err[0] ? ": " : "", err);
-    for (FILE *f : {trace, cs_part, ts_part, an_part}) if (f) fclose(f);
+    for (FILE *f : {trace, cs_part, ts_part, an_part, gt_part}) if (f) fclose(f);
     discard_all();
     if (M) gph_mcmc_destroy(M);
     if (E) gph_engine_destroy(E);
@@ -484,6 +787,19 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   if ((rc = gph_control_read(ctl, ctl2, &C))) return fail(rc, "reading the control file");
   gph_control_get(C, &cfg, &mc, &info);
   if (lead) printf("Done.\n");
+  if (gt_prefix) {
+    /* the names that will stand in the trees, before anything is computed */
+    for (int p = 0; p < cfg.K; p++)
+      if (!gt_name_ok(gph_control_pop_name(C, p))) {
+        snprintf(err, sizeof err, "the population name '%s' cannot stand in a tree (white space or one of ()[],:;'=&)", gph_control_pop_name(C, p));
+        return fail(GPH_EARG, "--gene-trees");
+      }
+    for (const std::string &nm : leaf_names(C, cfg))
+      if (!gt_name_ok(nm.c_str())) {
+        snprintf(err, sizeof err, "the sample name '%s' cannot stand in a tree (white space or one of ()[],:;'=&)", nm.c_str());
+        return fail(GPH_EARG, "--gene-trees");
+      }
+  }
   if (mc.seed < 0) {
     if (world > 1) return fail(GPH_EARG, "random-seed must be given in the control file when several ranks run one chain");
     mc.seed = abs(2 * (int)time(NULL) + 1);   /* GPhoCS.c:188-191 */
@@ -525,6 +841,21 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     if (lead) fprintf(stderr, "gphocs_hip: %d ranks over %lld loci in blocks of %lld leave the last rank(s) without loci -- use at most %lld ranks\n",
                       world, (long long)L, (long long)per, (long long)((L + per - 1) / per));
     return fail(GPH_EARG, "sharding the loci over the ranks");
+  }
+  std::vector<int64_t> gt_sel;          /* this rank's selected loci (global indices); gt_all: every locus */
+  bool gt_all = true;
+  int64_t gt_widest = 0;                /* selected loci of the rank that holds most: every rank takes the same decisions */
+  if (gt_prefix) {
+    std::vector<int64_t> sel;
+    if ((rc = gt_parse_spec(gt_spec, L, sel, gt_all))) return fail(rc, "--gene-trees-loci");
+    for (int r = 0; r < world; r++) {
+      const int64_t b0 = std::min<int64_t>(r * per, L), b1 = std::min<int64_t>((r + 1) * per, L);
+      int64_t cnt = gt_all ? b1 - b0 : 0;
+      if (!gt_all) for (int64_t g : sel) cnt += g >= b0 && g < b1;
+      gt_widest = std::max(gt_widest, cnt);
+    }
+    if (gt_all) for (int64_t g = lb; g < le; g++) gt_sel.push_back(g);
+    else for (int64_t g : sel) if (g >= lb && g < le) gt_sel.push_back(g);
   }
   cfg.L_total = L;
   cfg.locus_begin = lb;
@@ -597,6 +928,55 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     if (!an_part) { snprintf(err, sizeof err, "Could not open %s", part_path(AN_PART, an_prefix, rank).c_str()); return fail(GPH_EARG, "opening the ancestry part file"); }
   }
   int32_t an_held = 0;
+  /* sampled genealogies: the row buffer for this rank's selected loci, this rank's part file and its header */
+  int32_t gt_rb = 0, gt_held = 0;
+  int64_t gt_written = 0;
+  std::vector<char> gt_rows;
+  std::vector<int32_t> gt_iters;
+  if (gt_prefix) {
+    /* the bytes of a record (the same on every rank) from an empty selection, then the rows that fit */
+    const int64_t none = 0;
+    if ((rc = gph_engine_gene_trees_enable(E, 1, &none, 0, 0))) return fail(rc, "gph_engine_gene_trees_enable");
+    gph_engine_gene_trees_shape(E, nullptr, nullptr, &gt_rb, nullptr, nullptr);
+    const int64_t limit = (int64_t)256 << 20, row_bytes = gt_widest * gt_rb;
+    if (row_bytes > limit) {
+      snprintf(err, sizeof err, "one sample of %lld loci x %d bytes a record is %lld bytes, the limit is %lld: narrow --gene-trees-loci",
+               (long long)gt_widest, (int)gt_rb, (long long)row_bytes, (long long)limit);
+      return fail(GPH_EFULL, "--gene-trees");
+    }
+    const int64_t fit = row_bytes > 0 ? limit / row_bytes : limit;
+    gt_capacity = (int32_t)std::min<int64_t>(gt_capacity > 0 ? gt_capacity : 64, fit);
+    /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
+    if ((rc = gph_engine_gene_trees_enable(E, gt_capacity, gt_sel.empty() ? &none : gt_sel.data(), (int64_t)gt_sel.size(), 0))) return fail(rc, "gph_engine_gene_trees_enable");
+    int32_t offs[GPH_GT_O_COUNT];
+    gph_engine_gene_trees_shape(E, nullptr, nullptr, nullptr, offs, nullptr);
+    gt_rows.resize((size_t)gt_capacity * gt_sel.size() * (size_t)gt_rb);
+    gt_iters.resize((size_t)gt_capacity);
+    gt_part = fopen(gt_part_path(gt_prefix, rank).c_str(), "wb");
+    if (!gt_part) { snprintf(err, sizeof err, "Could not open %s", gt_part_path(gt_prefix, rank).c_str()); return fail(GPH_EARG, "opening the gene-trees part file"); }
+    int32_t hdr[GT_NH] = {cfg.n, cfg.K, cfg.B, gt_rb};
+    memcpy(hdr + 4, offs, sizeof offs);
+    std::string names;
+    for (const std::string &nm : pop_names(C, cfg)) { names += nm; names.push_back('\0'); }
+    for (const std::string &nm : band_names(C, cfg)) { names += nm; names.push_back('\0'); }
+    const std::vector<std::string> leaves = leaf_names(C, cfg);
+    for (int i = 0; i < cfg.n; i++) { names += leaves[(size_t)i] + "." + std::to_string(i); names.push_back('\0'); }
+    for (int64_t g : gt_sel) { const char *nm = gph_loci_name(LC, g); names += nm ? nm : ""; names.push_back('\0'); }
+    const int64_t nsel = (int64_t)gt_sel.size();
+    const int32_t nbytes = (int32_t)names.size();
+    fwrite(GT_MAGIC, 1, 8, gt_part); fwrite(hdr, 4, (size_t)GT_NH, gt_part); fwrite(&nsel, 8, 1, gt_part);
+    if (nsel > 0) fwrite(gt_sel.data(), 8, (size_t)nsel, gt_part);
+    fwrite(&nbytes, 4, 1, gt_part); fwrite(names.data(), 1, names.size(), gt_part);
+  }
+  /* the rows of the buffer behind this rank's part, each behind its iteration: the one host synchronisation of the option */
+  auto gt_flush = [&]() -> int {
+    int32_t got = 0;
+    int rcf = gph_engine_gene_trees_fetch(E, gt_iters.data(), gt_rows.data(), gt_capacity, &got);
+    if (rcf) return rcf;
+    gt_written += got;
+    gt_held = 0;
+    return write_rows(gt_part, gt_rows.data(), (size_t)gt_rb, (int32_t)gt_sel.size(), got, gt_iters.data(), 4, true);
+  };
   /* the filled rows of a device buffer behind this rank's part: ancestry rows each behind their iteration, coal-stats rows
    * each in front of their logPrior */
   auto an_flush = [&]() -> int {
@@ -699,6 +1079,10 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
       fprintf(trace, "\t%.6f\t%.6f\n", logL, dataL);
       fflush(trace);
       if (summary_path && (rc = gph_engine_locus_summary_sample(E))) return fail(rc, "gph_engine_locus_summary_sample");
+      if (gt_prefix) {
+        if ((rc = gph_engine_gene_trees_sample(E, it))) return fail(rc, "gph_engine_gene_trees_sample");
+        if (++gt_held == gt_capacity && (rc = gt_flush())) return fail(rc, "writing the gene-trees part file");
+      }
       if (an_prefix) {
         if ((rc = gph_engine_ancestry_sample(E, it))) return fail(rc, "gph_engine_ancestry_sample");
         if (++an_held == an_capacity && (rc = an_flush())) return fail(rc, "writing the ancestry part file");
@@ -835,6 +1219,13 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     an_part = nullptr;
     if (rcc != 0) return fail(GPH_EARG, "closing the ancestry part file");
   }
+  if (gt_prefix) {
+    if ((rc = gt_flush())) return fail(rc, "writing the gene-trees part file");
+    if (fwrite(&gt_written, sizeof gt_written, 1, gt_part) != 1) return fail(GPH_EARG, "writing the gene-trees part file");   /* the trailer: samples in this part */
+    const int rcc = ferror(gt_part) | fclose(gt_part);
+    gt_part = nullptr;
+    if (rcc != 0) return fail(GPH_EARG, "closing the gene-trees part file");
+  }
   int32_t ls_ncol = 0;
   int64_t ls_samples = 0;
   std::vector<double> ls_raw;
@@ -850,7 +1241,7 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   gph_engine_destroy(E);
   if (oob_checked && oob_where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
     gph_loci_free(LC);
     gph_control_free(C);
     discard_all();
@@ -868,6 +1259,7 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
   /* (the ancestry files first, then the slices file: should a later group fail, two files and one are removed again,
    * not 1 + 3 K) */
   if (world == 1) {
+    if (!rc && gt_prefix) rc = gph_gene_trees_write(gt_prefix, 1);
     if (!rc && an_prefix) rc = gph_ancestry_write(an_prefix, 1);
     if (!rc && ts_slices) rc = gph_time_slices_write(cs_prefix, 1);
     if (!rc && cs_prefix) rc = gph_coal_stats_write(cs_prefix, 1);
@@ -910,10 +1302,20 @@ extern "C" int gph_run_control_file_ex4(const char *ctl, const char *ctl2, int32
                                         const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity,
                                         int32_t time_slices, const char *ancestry_prefix, int32_t ancestry_capacity)
 {
+  return gph_run_control_file_ex5(ctl, ctl2, device, verbose, comm, locus_summary_path, coal_stats_prefix, coal_stats_capacity, time_slices,
+                                  ancestry_prefix, ancestry_capacity, nullptr, nullptr, 0);
+}
+
+extern "C" int gph_run_control_file_ex5(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
+                                        const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity,
+                                        int32_t time_slices, const char *ancestry_prefix, int32_t ancestry_capacity,
+                                        const char *gene_trees_prefix, const char *gene_trees_loci_spec, int32_t gene_trees_capacity)
+{
   if (comm) return run_control_file(ctl, ctl2, device, verbose, gph_comm_rank(comm), gph_comm_world(comm), nullptr, nullptr, comm, locus_summary_path,
-                                    coal_stats_prefix, coal_stats_capacity, time_slices, ancestry_prefix, ancestry_capacity);
+                                    coal_stats_prefix, coal_stats_capacity, time_slices, ancestry_prefix, ancestry_capacity,
+                                    gene_trees_prefix, gene_trees_loci_spec, gene_trees_capacity);
   return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr, locus_summary_path, coal_stats_prefix, coal_stats_capacity,
-                          time_slices, ancestry_prefix, ancestry_capacity);
+                          time_slices, ancestry_prefix, ancestry_capacity, gene_trees_prefix, gene_trees_loci_spec, gene_trees_capacity);
 }
 
 extern "C" int gph_run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose)

@@ -46,8 +46,9 @@ extern "C" {
 #define GPH_EHIP (-2)      /* HIP runtime failure (no device, OOM, launch error) */
 #define GPH_EKERNEL (-3)   /* a locus reported a fatal consistency error (reference: "Fatal Error NNNN") */
 #define GPH_ESTATE (-4)    /* call out of order */
-#define GPH_EFULL (-5)     /* gph_engine_coal_stats_sample / _time_slices_sample / _ancestry_sample: every row of the device buffer is taken;
-                            * fetch first.  gph_engine_ancestry_enable: the accumulators would exceed the byte limit */
+#define GPH_EFULL (-5)     /* gph_engine_coal_stats_sample / _time_slices_sample / _ancestry_sample / _gene_trees_sample: every row of the
+                            * device buffer is taken; fetch first.  gph_engine_ancestry_enable / _gene_trees_enable: the accumulators /
+                            * the row buffer would exceed the byte limit */
 
 typedef struct gph_engine gph_engine;
 typedef struct gph_mcmc gph_mcmc;
@@ -377,6 +378,46 @@ int gph_engine_ancestry_shape(gph_engine *e, int32_t *locus_columns, int32_t *ro
 int gph_engine_ancestry_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset);
 int gph_engine_ancestry_fetch_rows(gph_engine *e, int32_t *iters, int32_t *out, int64_t ld, int32_t max_rows, int32_t *rows);
 const char *gph_engine_ancestry_column_name(gph_engine *e, int32_t which, int32_t col);
+/* SAMPLED GENEALOGIES of selected loci, gathered on the device (k_gene_trees: csrc/gph_genetrees.h).  One RECORD describes
+ * one locus at one sample -- what the LOCUS, N and M lines of a state dump print at the same point of the chain, every field
+ * equal and the ages equal as bit patterns.  With n leaves and N = 2n - 1 nodes it is record_bytes bytes (about 16 N + 300)
+ * copied verbatim from the locus's page, and holds at the offsets _shape hands out (GPH_GT_O_*):
+ *   NODES     N node records of 16 bytes: age (fp64), father, left, right, npop (int16 each)
+ *   ROOT, NUM_MIGS  two int32: the root node and the number of live migrations
+ *   DATALNL, GENLNL two fp64
+ *   MIG_AGE   GPH_GT_MAX_MIGS fp64, by migration node
+ *   MIG_I     GPH_GT_MAX_MIGS x 6 int16, by migration node: branch, band, source population, target population, 2 event ids
+ *   LIVING    GPH_GT_MAX_MIGS int16: the live migration nodes, NUM_MIGS of them, in the order of a state dump's M line
+ * gph_gene_trees_decode (below) turns records into plain arrays.  A SELECTION is a strictly increasing list of global 0-based
+ * locus indices in sequence-file order; a ROW is one sample: the records of the selected loci THIS rank holds, in increasing
+ * locus index (not slot order: the kernel goes through a selected -> slot table).
+ *   _enable(capacity_rows, loci, nloci, max_bytes)  a device buffer of capacity_rows rows for the selection; loci NULL: all
+ *                      loci of the rank.  GPH_ESTATE before gph_engine_load_loci.  GPH_EARG for a negative index or a list
+ *                      that is not strictly increasing; indices outside this rank's block [locus_begin, locus_begin + L_local)
+ *                      are not this rank's and are ignored (a rank may end up with no selected locus).  capacity_rows 0 frees
+ *                      everything, the feature is off.  GPH_EFULL (with a message that names the numbers) when capacity_rows x
+ *                      selected x record_bytes exceeds max_bytes (<= 0: 256 MB); the engine stays usable, the feature is off.
+ *                      gph_engine_init_genealogies empties the buffer
+ *   _sample(iteration) GPH_ESTATE when not enabled or not initialised, GPH_EFULL when no row is free (nothing is overwritten).
+ *                      Otherwise queues one sample on the engine's stream: one kernel (none on a rank without a selected
+ *                      locus, which still counts the sample), no host synchronisation, no exchange.  The pages and the
+ *                      migration ages are made current as for gph_engine_ancestry_sample; a deferred synchronizeEvents pass
+ *                      stays deferred (a record holds no event time)
+ *   _shape             selected loci of this rank, N, bytes of a record, the GPH_GT_O_COUNT offsets inside a record, rows
+ *                      held (any pointer may be NULL; all 0 while the feature is off)
+ *   _selected          out[max_loci >= *count]: the global indices of this rank's selected loci; out NULL with max_loci 0:
+ *                      the count only.  GPH_ESTATE while off
+ *   _fetch             copies the rows taken since the last fetch to iters[max_rows >= held] and out[held][selected x
+ *                      record_bytes], *rows = their number, and empties the buffer (one host synchronisation; out may be
+ *                      NULL on a rank without a selected locus).  GPH_ESTATE while off, GPH_EARG when max_rows is too small */
+#define GPH_GT_MAX_MIGS 10
+enum { GPH_GT_O_NODES = 0, GPH_GT_O_ROOT, GPH_GT_O_NUM_MIGS, GPH_GT_O_DATALNL, GPH_GT_O_GENLNL, GPH_GT_O_MIG_AGE, GPH_GT_O_MIG_I,
+       GPH_GT_O_LIVING, GPH_GT_O_COUNT };
+int gph_engine_gene_trees_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int64_t max_bytes);
+int gph_engine_gene_trees_sample(gph_engine *e, int32_t iteration);
+int gph_engine_gene_trees_shape(gph_engine *e, int64_t *selected, int32_t *nodes, int32_t *record_bytes, int32_t *offsets, int32_t *rows_held);
+int gph_engine_gene_trees_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_gene_trees_fetch(gph_engine *e, int32_t *iters, void *out, int32_t max_rows, int32_t *rows);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -572,6 +613,54 @@ int gph_run_control_file_ex4(const char *ctl_path, const char *secondary_ctl_pat
                              const char *ancestry_prefix_or_null, int32_t ancestry_capacity);
 int gph_ancestry_write(const char *prefix, int32_t ranks);
 int gph_ancestry_discard(const char *prefix, int32_t ranks);
+/* the same, plus the sampled genealogies (`G-PhoCS-hip --gene-trees PREFIX [--gene-trees-loci SPEC] [--gene-trees-rows N]`;
+ * needs none of the other options): with a gene_trees_prefix a sample of gph_engine_gene_trees_* is taken wherever a trace
+ * line is written (never in the burn-in).  gene_trees_loci_spec: NULL or "all", or a comma list of i, i-j (both ends included)
+ * or i-j:step, 0-based indices in sequence-file order; an index named twice or >= the number of loci is refused, with a
+ * message that names it, before the first iteration (GPH_EARG), and so is a population or sample name that holds white
+ * space or one of ()[],:;'=& .  The row buffer holds min(gene_trees_capacity or 64, 256 MB / bytes of a row) rows; a single
+ * row above 256 MB stops the run before the first iteration (GPH_EFULL, with a message).  Whenever the buffer is full, and
+ * at the end, rank r appends its rows to the binary file PREFIX.trees.part<r> (the only host synchronisation the option adds).
+ * gph_gene_trees_write(prefix, ranks) writes, from the parts, PREFIX.trees.tsv:
+ *   header  iter locus name dataLnL genLnL tmrca numMigs tree
+ *   one line per (sample, selected locus), sample order then locus order (the ranks' records of one sample in rank order);
+ *   iter, locus (0-based), numMigs "%d"; name from the sequence file; dataLnL, genLnL, tmrca = age[root] in the genealogy's
+ *   own units "%.10g"; tree: gph_gene_tree_newick with leaf labels <sample>.<i>, <sample> as PREFIX.<pop>.probCoal.tsv
+ *   names leaf i
+ * and removes the parts; _discard removes the parts and the file.  A one-rank run writes or discards itself; with several
+ * ranks the caller does.  A failed run leaves neither parts nor file; a part that is missing, damaged or was not closed by
+ * its rank is an error.  gene_trees_prefix NULL = gph_run_control_file_ex4. */
+int gph_run_control_file_ex5(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
+                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null,
+                             const char *coal_stats_prefix_or_null, int32_t coal_stats_capacity, int32_t time_slices,
+                             const char *ancestry_prefix_or_null, int32_t ancestry_capacity,
+                             const char *gene_trees_prefix_or_null, const char *gene_trees_loci_spec_or_null, int32_t gene_trees_capacity);
+int gph_gene_trees_write(const char *prefix, int32_t ranks);
+int gph_gene_trees_discard(const char *prefix, int32_t ranks);
+/* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
+ * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
+ * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
+ * k < num_migs in `living` order mig_branch / mig_band / mig_spop / mig_tpop / mig_age[r][GPH_GT_MAX_MIGS]; entries
+ * k >= num_migs (and those of a damaged `living` word) are -1 and age 0. */
+int gph_gene_trees_decode(const void *records, int64_t count, int32_t record_bytes, const int32_t *offsets, int32_t nodes,
+                          double *age, int32_t *father, int32_t *left, int32_t *right, int32_t *npop, int32_t *root, int32_t *num_migs,
+                          double *dataLnL, double *genLnL, int32_t *mig_branch, int32_t *mig_band, int32_t *mig_spop, int32_t *mig_tpop,
+                          double *mig_age);
+/* one genealogy as one line of extended Newick (host only: no GPU, no engine).  n leaves, N = 2n - 1 nodes, arrays as
+ * gph_gene_trees_decode fills them; pop_names[K], band_names[B] ("<src>-><tgt>"), leaf_labels[n].
+ *   tree    := sub(root) ";"
+ *   body(v) := label(v) "[&pop=" POP(npop[v]) "]"                                 v a leaf
+ *            | "(" sub(left[v]) "," sub(right[v]) ")" "[&pop=" POP(npop[v]) "]"   v internal
+ * For v != root let m_1 .. m_k be the live migrations on the branch of v sorted by age ascending (equal ages keep `living`
+ * order), a_0 = age[v], a_j = the age of m_j: s_0 = body(v), s_j = "(" s_{j-1} ":" LEN(a_j - a_{j-1}) ")" "[&mig=" BAND "]",
+ * sub(v) = s_k ":" LEN(age[father[v]] - a_k); sub(root) = body(root).  LEN is "%.10g" of the fp64 difference.
+ * Returns 0 with the text in out (NUL-terminated, *out_len = its length; out NULL: the length only), 2 when out_cap is too
+ * small, GPH_EARG for a record that is no tree (an index out of range, a cycle) or a name that holds white space or one of
+ * ()[],:;'=& (with a message). */
+int gph_gene_tree_newick(int32_t n, const double *age, const int32_t *father, const int32_t *left, const int32_t *right,
+                         const int32_t *npop, int32_t root, int32_t num_migs, const int32_t *mig_branch, const int32_t *mig_band,
+                         const double *mig_age, const char *const *pop_names, int32_t K, const char *const *band_names, int32_t B,
+                         const char *const *leaf_labels, char *out, size_t out_cap, size_t *out_len);
 
 /* ------------------------------------------------------------------------------------
  * post-run summary of a trace file (host only): block means per column, the output of the reference's
