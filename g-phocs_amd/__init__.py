@@ -262,6 +262,26 @@ class GphControlInfo(C.Structure):
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32,
                            C.POINTER(C.c_double), C.c_int32)
 
+class GphRunOptions(C.Structure):   # gph_run_options: what each field switches on is said there
+    _fields_ = [("size", C.c_uint32), ("ctl", C.c_char_p), ("ctl2", C.c_char_p), ("device", C.c_int32), ("verbose", C.c_int32),
+                ("comm", C.c_void_p), ("rank", C.c_int32), ("world", C.c_int32), ("allreduce", ALLREDUCE_FN), ("user", C.c_void_p),
+                ("locus_summary_path", C.c_char_p), ("coal_stats_prefix", C.c_char_p), ("coal_stats_rows", C.c_int32),
+                ("time_slices", C.c_int32), ("ancestry_prefix", C.c_char_p), ("ancestry_rows", C.c_int32),
+                ("gene_trees_prefix", C.c_char_p), ("gene_trees_loci", C.c_char_p), ("gene_trees_rows", C.c_int32)]
+
+
+def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
+                     ancestry=None, ancestry_rows=0, gene_trees=None, gene_trees_loci=None, gene_trees_rows=0):
+    """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status"""
+    def b(x):
+        return os.fsencode(x) if x is not None else None
+    o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
+                      locus_summary_path=b(locus_summary), coal_stats_prefix=b(coal_stats), coal_stats_rows=coal_stats_rows,
+                      time_slices=time_slices, ancestry_prefix=b(ancestry), ancestry_rows=ancestry_rows,
+                      gene_trees_prefix=b(gene_trees), gene_trees_loci=b(gene_trees_loci), gene_trees_rows=gene_trees_rows)
+    return lib.gph_run(C.byref(o))
+
+
 EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_create", "gph_engine_destroy", "gph_engine_set_allreduce", "gph_engine_load_loci",
     "gph_engine_set_model", "gph_engine_seed", "gph_engine_init_genealogies",
@@ -285,19 +305,19 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_mcmc_update_mig_rates", "gph_mcmc_update_tau", "gph_mcmc_update_sample_age", "gph_mcmc_mixing",
     "gph_mcmc_synchronize_events", "gph_mcmc_check_all", "gph_mcmc_initialize_genealogies",
     "gph_engine_locus_summary_enable", "gph_engine_locus_summary_sample", "gph_engine_locus_summary_columns",
-    "gph_engine_locus_summary_fetch", "gph_engine_locus_summary_column_name", "gph_loci_name", "gph_run_control_file_ex",
+    "gph_engine_locus_summary_fetch", "gph_engine_locus_summary_column_name", "gph_loci_name",
     "gph_engine_coal_stats_enable", "gph_engine_coal_stats_sample", "gph_engine_coal_stats_shape", "gph_engine_coal_stats_fetch",
-    "gph_engine_coal_stats_column_name", "gph_run_control_file_ex2", "gph_coal_stats_write", "gph_coal_stats_discard",
+    "gph_engine_coal_stats_column_name", "gph_coal_stats_write", "gph_coal_stats_discard",
     "gph_engine_coal_stats_set_chunk", "gph_coal_stats_combined",
     "gph_engine_time_slices_enable", "gph_engine_time_slices_sample", "gph_engine_time_slices_shape", "gph_engine_time_slices_fetch",
-    "gph_engine_time_slices_column_name", "gph_engine_time_slices_set_chunk", "gph_run_control_file_ex3", "gph_time_slices_write",
+    "gph_engine_time_slices_column_name", "gph_engine_time_slices_set_chunk", "gph_time_slices_write",
     "gph_time_slices_combined", "gph_time_slices_discard",
     "gph_engine_ancestry_enable", "gph_engine_ancestry_sample", "gph_engine_ancestry_shape", "gph_engine_ancestry_fetch_loci",
-    "gph_engine_ancestry_fetch_rows", "gph_engine_ancestry_column_name", "gph_run_control_file_ex4", "gph_ancestry_write",
+    "gph_engine_ancestry_fetch_rows", "gph_engine_ancestry_column_name", "gph_ancestry_write",
     "gph_ancestry_discard",
     "gph_engine_gene_trees_enable", "gph_engine_gene_trees_sample", "gph_engine_gene_trees_shape", "gph_engine_gene_trees_selected",
-    "gph_engine_gene_trees_fetch", "gph_run_control_file_ex5", "gph_gene_trees_write", "gph_gene_trees_discard", "gph_gene_trees_decode",
-    "gph_gene_tree_newick",
+    "gph_engine_gene_trees_fetch", "gph_gene_trees_write", "gph_gene_trees_discard", "gph_gene_trees_decode",
+    "gph_gene_tree_newick", "gph_run", "gph_run_finish",
 ]
 
 
@@ -402,14 +422,12 @@ def _load_library(path):
     lib.gph_engine_locus_summary_column_name.restype = C.c_char_p
     lib.gph_loci_name.argtypes = [C.c_void_p, C.c_int64]
     lib.gph_loci_name.restype = C.c_char_p
-    lib.gph_run_control_file_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p]
     lib.gph_engine_coal_stats_enable.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_engine_coal_stats_sample.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_engine_coal_stats_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
     lib.gph_engine_coal_stats_fetch.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32)]
     lib.gph_engine_coal_stats_column_name.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_engine_coal_stats_column_name.restype = C.c_char_p
-    lib.gph_run_control_file_ex2.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32]
     lib.gph_coal_stats_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_coal_stats_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_engine_coal_stats_set_chunk.argtypes = [C.c_void_p, C.c_int32]
@@ -421,7 +439,6 @@ def _load_library(path):
     lib.gph_engine_time_slices_column_name.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_engine_time_slices_column_name.restype = C.c_char_p
     lib.gph_engine_time_slices_set_chunk.argtypes = [C.c_void_p, C.c_int32]
-    lib.gph_run_control_file_ex3.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32]
     lib.gph_time_slices_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_time_slices_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_time_slices_combined.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
@@ -432,8 +449,6 @@ def _load_library(path):
     lib.gph_engine_ancestry_fetch_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
     lib.gph_engine_ancestry_column_name.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.gph_engine_ancestry_column_name.restype = C.c_char_p
-    lib.gph_run_control_file_ex4.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32,
-                                             C.c_char_p, C.c_int32]
     lib.gph_ancestry_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_ancestry_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_engine_gene_trees_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int64]
@@ -442,11 +457,11 @@ def _load_library(path):
                                                 C.POINTER(C.c_int32)]
     lib.gph_engine_gene_trees_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     lib.gph_engine_gene_trees_fetch.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.gph_run_control_file_ex5.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32,
-                                             C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32]
     lib.gph_gene_trees_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_gene_trees_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_gene_trees_decode.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32] + [C.c_void_p] * 14
+    lib.gph_run.argtypes = [C.POINTER(GphRunOptions)]
+    lib.gph_run_finish.argtypes = [C.POINTER(GphRunOptions), C.c_int32, C.c_int32]
     lib.gph_gene_tree_newick.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + \
         [C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     return lib

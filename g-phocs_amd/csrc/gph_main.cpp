@@ -11,30 +11,15 @@
 // 0 to the others through a shared page).  With fewer devices than ranks (tests on a 1-GPU box) the ranks share
 // devices and exchange through that shared page instead -- RCCL refuses two ranks on one GPU.
 //
-// -l FILE: the per-locus posterior summary table (gph_run_control_file_ex).  Under -g N child r writes FILE.part<r>
-// with its own loci; after every child has exited 0 the launcher concatenates the parts in rank order into FILE and
-// removes them (on a failure it only removes them: a run that did not finish leaves no table).
-//
-// -s PREFIX: the coalescent / sample-pair statistics of every sample (gph_run_control_file_ex2): PREFIX.coal.tsv and, per
-// population, PREFIX.<pop>.probCoal.tsv / .probFirstCoal.tsv / .meanCoal.tsv.  Every rank appends its raw rows to
-// PREFIX.coal.part<r> (--coal-stats-rows N: rows of the device buffer between two flushes, default 64); after every child
-// has exited 0 the launcher has the library add the parts in rank order and write the files (gph_coal_stats_write); on a
-// failure the parts are removed and no file is written.
-//
-// --time-slices S (with -s PREFIX only): additionally PREFIX.slices.tsv, the coalescence / migration statistics of every
-// sample per time slice (gph_run_control_file_ex3); the ranks' PREFIX.slices.part<r> are handled like the coal-stats parts
-// (gph_time_slices_write / _discard).
-//
-// --ancestry PREFIX: PREFIX.loci.tsv and PREFIX.samples.tsv, which sample's lineage went through which migration band at
-// which locus (gph_run_control_file_ex4); the ranks' PREFIX.ancestry.part<r> become the two files once every child has
-// exited 0 (gph_ancestry_write), and are removed otherwise (gph_ancestry_discard).  Composes with every option above.
-//
-// --gene-trees PREFIX: PREFIX.trees.tsv, the sampled genealogy of every selected locus at every sample as a line of extended
-// Newick with populations and migration events on the branches (gph_run_control_file_ex5).  --gene-trees-loci SPEC selects
-// loci: a comma list of i, i-j or i-j:step, 0-based in sequence-file order (default all); --gene-trees-rows N: rows of the
-// device buffer between two flushes (default 64, fewer when a row is large).  The ranks' PREFIX.trees.part<r> become the file
-// once every child has exited 0 (gph_gene_trees_write), and are removed otherwise (gph_gene_trees_discard).  Composes with
-// every option above.
+// The outputs (gph_run_options in include/gphocs_hip.h says what each writes): -l FILE, the per-locus posterior summary
+// table; -s PREFIX, the coalescent / sample-pair statistics of every sample (--coal-stats-rows N: rows of the device buffer
+// between two flushes, default 64), with --time-slices S additionally per time slice; --ancestry PREFIX, which sample's
+// lineage went through which migration band at which locus; --gene-trees PREFIX, the sampled genealogy of every selected
+// locus at every sample as a line of extended Newick (--gene-trees-loci SPEC: a comma list of i, i-j or i-j:step, 0-based in
+// sequence-file order, default all; --gene-trees-rows N: rows of the device buffer, default 64, fewer when a row is large).
+// They compose freely.  Under -g N every child leaves parts: of the summary table FILE.part<r>, which the launcher
+// concatenates in rank order into FILE once every child has exited 0; of the others the library's own, which gph_run_finish
+// turns into the files (the launcher itself has not touched a GPU).  A run that did not finish leaves neither parts nor files.
 #include "gphocs_hip.h"
 #include <dlfcn.h>
 #include <libgen.h>
@@ -113,41 +98,38 @@ static int usage(const char *a0)
 
 int main(int argc, char **argv)
 {
-  int verbose = 0, device = 0, gpus = 1, i = 1;
-  const char *summary = nullptr, *coal = nullptr, *ancestry = nullptr, *trees = nullptr, *trees_loci = nullptr;
-  int coal_rows = 0, slices = 0, trees_rows = 0;
+  int gpus = 1, i = 1;
+  gph_run_options o;
+  memset(&o, 0, sizeof o);
+  o.size = sizeof o;
   for (; i < argc && argv[i][0] == '-'; i++) {
-    if (!strcmp(argv[i], "-v") || !strcmp(argv[i], "--verbose")) verbose = 1;
-    else if (!strcmp(argv[i], "-d") && i + 1 < argc) device = atoi(argv[++i]);
+    if (!strcmp(argv[i], "-v") || !strcmp(argv[i], "--verbose")) o.verbose = 1;
+    else if (!strcmp(argv[i], "-d") && i + 1 < argc) o.device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "-g") && i + 1 < argc) gpus = atoi(argv[++i]);
-    else if (!strcmp(argv[i], "-l") && i + 1 < argc) summary = argv[++i];
-    else if (!strcmp(argv[i], "-s") && i + 1 < argc) coal = argv[++i];
-    else if (!strcmp(argv[i], "--coal-stats-rows") && i + 1 < argc) coal_rows = atoi(argv[++i]);
-    else if (!strcmp(argv[i], "--time-slices") && i + 1 < argc) { slices = atoi(argv[++i]); if (slices < 1) return usage(argv[0]); }
-    else if (!strcmp(argv[i], "--ancestry") && i + 1 < argc) ancestry = argv[++i];
-    else if (!strcmp(argv[i], "--gene-trees") && i + 1 < argc) trees = argv[++i];
-    else if (!strcmp(argv[i], "--gene-trees-loci") && i + 1 < argc) trees_loci = argv[++i];
-    else if (!strcmp(argv[i], "--gene-trees-rows") && i + 1 < argc) { trees_rows = atoi(argv[++i]); if (trees_rows < 1) return usage(argv[0]); }
+    else if (!strcmp(argv[i], "-l") && i + 1 < argc) o.locus_summary_path = argv[++i];
+    else if (!strcmp(argv[i], "-s") && i + 1 < argc) o.coal_stats_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--coal-stats-rows") && i + 1 < argc) o.coal_stats_rows = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--time-slices") && i + 1 < argc) { o.time_slices = atoi(argv[++i]); if (o.time_slices < 1) return usage(argv[0]); }
+    else if (!strcmp(argv[i], "--ancestry") && i + 1 < argc) o.ancestry_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--gene-trees") && i + 1 < argc) o.gene_trees_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--gene-trees-loci") && i + 1 < argc) o.gene_trees_loci = argv[++i];
+    else if (!strcmp(argv[i], "--gene-trees-rows") && i + 1 < argc) { o.gene_trees_rows = atoi(argv[++i]); if (o.gene_trees_rows < 1) return usage(argv[0]); }
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
   if (i >= argc || gpus < 1 || gpus > 64) return usage(argv[0]);
-  if (slices && !coal) { fprintf(stderr, "%s: --time-slices needs -s PREFIX\n", argv[0]); return usage(argv[0]); }
-  if ((trees_loci || trees_rows) && !trees) { fprintf(stderr, "%s: --gene-trees-loci and --gene-trees-rows need --gene-trees PREFIX\n", argv[0]); return usage(argv[0]); }
-  const char *ctl = argv[i], *ctl2 = i + 1 < argc ? argv[i + 1] : nullptr;
+  if (o.time_slices && !o.coal_stats_prefix) { fprintf(stderr, "%s: --time-slices needs -s PREFIX\n", argv[0]); return usage(argv[0]); }
+  if ((o.gene_trees_loci || o.gene_trees_rows) && !o.gene_trees_prefix) { fprintf(stderr, "%s: --gene-trees-loci and --gene-trees-rows need --gene-trees PREFIX\n", argv[0]); return usage(argv[0]); }
+  o.ctl = argv[i];
+  o.ctl2 = i + 1 < argc ? argv[i + 1] : nullptr;
   char self[PATH_MAX];
   ssize_t k = readlink("/proc/self/exe", self, sizeof self - 1);
   if (k <= 0) { perror("readlink"); return 2; }
   self[k] = 0;
   const std::string dir = dirname(self);
   if (gpus == 1) {
-    void *h = load_engine(dir, ctl, ctl2);
-    if (trees) return sym<decltype(&gph_run_control_file_ex5)>(h, "gph_run_control_file_ex5")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices, ancestry, 0, trees, trees_loci, trees_rows) ? 1 : 0;
-    if (ancestry) return sym<decltype(&gph_run_control_file_ex4)>(h, "gph_run_control_file_ex4")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices, ancestry, 0) ? 1 : 0;
-    if (slices) return sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows, slices) ? 1 : 0;
-    if (coal) return sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, device, verbose, nullptr, summary, coal, coal_rows) ? 1 : 0;
-    if (summary) return sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, device, verbose, nullptr, summary) ? 1 : 0;
-    return sym<decltype(&gph_run_control_file)>(h, "gph_run_control_file")(ctl, ctl2, device, verbose) ? 1 : 0;
+    void *h = load_engine(dir, o.ctl, o.ctl2);
+    return sym<decltype(&gph_run)>(h, "gph_run")(&o) ? 1 : 0;
   }
 
   // ---- one chain over `gpus` ranks.  Nothing below this line touches a GPU in the parent.
@@ -162,7 +144,7 @@ int main(int argc, char **argv)
     if (p == 0) {
       prctl(PR_SET_PDEATHSIG, SIGTERM);          /* the launcher died (killed -9, say): do not linger in an exchange */
       if (getppid() == 1) _exit(2);
-      void *h = load_engine(dir, ctl, ctl2);
+      void *h = load_engine(dir, o.ctl, o.ctl2);
       Mailbox *mb = (Mailbox *)shared;
       // how many devices are there?  Child 0 asks (the first GPU call of this process tree) and tells the others
       // through the engine library: gph_comm_create_* are the only entry points that need to know
@@ -174,13 +156,13 @@ int main(int argc, char **argv)
       auto ndevices = sym<int (*)()>(h, "gph_device_count");
       const int ndev = ndevices();
       if (ndev < 1) { fprintf(stderr, "G-PhoCS-hip: no HIP device\n"); _exit(2); }
-      const int mydev = device + r < ndev ? device + r : (device + r) % ndev;
-      const bool share = gpus > ndev - device || getenv("GPHOCS_HIP_SHM");   /* ranks would share a device */
+      const int mydev = o.device + r < ndev ? o.device + r : (o.device + r) % ndev;
+      const bool share = gpus > ndev - o.device || getenv("GPHOCS_HIP_SHM");   /* ranks would share a device */
       gph_comm *comm = nullptr;
       if (share) {
         if (shm_bytes(gpus) + 4096 > page) { fprintf(stderr, "G-PhoCS-hip: shared page too small\n"); _exit(2); }
         comm = attach_shm(shared + 4096, r, gpus);
-        if (r == 0 && verbose) printf("%d ranks on %d device(s): host shared-memory exchange (RCCL wants one GPU per rank)\n", gpus, ndev);
+        if (r == 0 && o.verbose) printf("%d ranks on %d device(s): host shared-memory exchange (RCCL wants one GPU per rank)\n", gpus, ndev);
       } else {
         if (r == 0) {
           if (unique_id(mb->id)) _exit(2);
@@ -191,12 +173,9 @@ int main(int argc, char **argv)
         comm = create_rccl(mb->id, r, gpus, mydev);
       }
       if (!comm) { fprintf(stderr, "G-PhoCS-hip: rank %d could not join the communicator\n", r); _exit(2); }
-      int rc = trees ? sym<decltype(&gph_run_control_file_ex5)>(h, "gph_run_control_file_ex5")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices, ancestry, 0, trees, trees_loci, trees_rows) :
-               ancestry ? sym<decltype(&gph_run_control_file_ex4)>(h, "gph_run_control_file_ex4")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices, ancestry, 0) :
-               slices ? sym<decltype(&gph_run_control_file_ex3)>(h, "gph_run_control_file_ex3")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows, slices) :
-               coal ? sym<decltype(&gph_run_control_file_ex2)>(h, "gph_run_control_file_ex2")(ctl, ctl2, mydev, verbose, comm, summary, coal, coal_rows) :
-               summary ? sym<decltype(&gph_run_control_file_ex)>(h, "gph_run_control_file_ex")(ctl, ctl2, mydev, verbose, comm, summary)
-                       : sym<decltype(&gph_run_control_file_comm)>(h, "gph_run_control_file_comm")(ctl, ctl2, mydev, verbose, comm);
+      o.device = mydev;
+      o.comm = comm;
+      int rc = sym<decltype(&gph_run)>(h, "gph_run")(&o);
       fflush(stdout);
       if (rc == 0) destroy(comm);
       _exit(rc ? 1 : 0);
@@ -224,12 +203,12 @@ int main(int argc, char **argv)
       for (int r = 0; r < gpus; r++) if (kids[r] != p) kill(kids[r], SIGTERM);
     }
   }
-  if (summary) {
+  if (o.locus_summary_path) {
     /* the ranks' parts of the summary table, in rank order */
-    FILE *out = bad ? nullptr : fopen(summary, "w");
-    if (!bad && !out) { perror(summary); bad = 1; }
+    FILE *out = bad ? nullptr : fopen(o.locus_summary_path, "w");
+    if (!bad && !out) { perror(o.locus_summary_path); bad = 1; }
     for (int r = 0; r < gpus; r++) {
-      const std::string part = std::string(summary) + ".part" + std::to_string(r);
+      const std::string part = std::string(o.locus_summary_path) + ".part" + std::to_string(r);
       if (out) {
         FILE *in = fopen(part.c_str(), "r");
         if (!in) { fprintf(stderr, "G-PhoCS-hip: %s is missing\n", part.c_str()); bad = 1; }
@@ -237,37 +216,18 @@ int main(int argc, char **argv)
           char buf[1 << 16];
           size_t nr;
           while ((nr = fread(buf, 1, sizeof buf, in)) > 0)
-            if (fwrite(buf, 1, nr, out) != nr) { perror(summary); bad = 1; break; }
+            if (fwrite(buf, 1, nr, out) != nr) { perror(o.locus_summary_path); bad = 1; break; }
           fclose(in);
         }
       }
       unlink(part.c_str());
     }
-    if (out && fclose(out) != 0) { perror(summary); bad = 1; }
-    if (bad && out) unlink(summary);
+    if (out && fclose(out) != 0) { perror(o.locus_summary_path); bad = 1; }
+    if (bad && out) unlink(o.locus_summary_path);
   }
-  void *hgt = nullptr;
-  if (trees) {
-    /* the ranks' parts into PREFIX.trees.tsv, by the library that wrote them; first, so that a later failure removes one file */
-    hgt = load_engine(dir, ctl, ctl2);
-    if (!bad && sym<decltype(&gph_gene_trees_write)>(hgt, "gph_gene_trees_write")(trees, gpus)) bad = 1;
+  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix) {
+    /* the ranks' parts into the files, by the library that wrote them -- or, after a failure, removed */
+    if (sym<decltype(&gph_run_finish)>(load_engine(dir, o.ctl, o.ctl2), "gph_run_finish")(&o, gpus, bad)) bad = 1;
   }
-  void *han = nullptr;
-  if (ancestry) {
-    /* the ranks' parts into the two files, by the library that wrote them; first, so that a later failure removes two files */
-    han = load_engine(dir, ctl, ctl2);
-    if (!bad && sym<decltype(&gph_ancestry_write)>(han, "gph_ancestry_write")(ancestry, gpus)) bad = 1;
-  }
-  if (coal) {
-    /* the ranks' raw rows, added in rank order by the library that wrote them (the launcher itself has not touched a GPU) */
-    void *h = load_engine(dir, ctl, ctl2);
-    /* (the slices file first; should the coal-stats files fail after it, _discard removes it again) */
-    if (slices && !bad && sym<decltype(&gph_time_slices_write)>(h, "gph_time_slices_write")(coal, gpus)) bad = 1;
-    if (bad) sym<decltype(&gph_coal_stats_discard)>(h, "gph_coal_stats_discard")(coal, gpus);
-    else if (sym<decltype(&gph_coal_stats_write)>(h, "gph_coal_stats_write")(coal, gpus)) bad = 1;
-    if (slices && bad) sym<decltype(&gph_time_slices_discard)>(h, "gph_time_slices_discard")(coal, gpus);
-  }
-  if (ancestry && bad) sym<decltype(&gph_ancestry_discard)>(han, "gph_ancestry_discard")(ancestry, gpus);
-  if (trees && bad) sym<decltype(&gph_gene_trees_discard)>(hgt, "gph_gene_trees_discard")(trees, gpus);
   return bad;
 }

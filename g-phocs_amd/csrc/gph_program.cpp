@@ -10,7 +10,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <cstddef>
+#include <initializer_list>
 #include <limits>
+#include <memory>
 #include <string>
 #include <vector>
 #include <unistd.h>
@@ -544,9 +547,9 @@ extern "C" int gph_gene_trees_decode(const void *records, int64_t count, int32_t
 // populations, B bands, n leaf labels, one sequence-file name per selected locus | per sample: iteration (int32), the row |
 // trailer, written when the rank closes its part: the number of samples (int64)
 namespace {
-const char GT_MAGIC[8] = {'G', 'P', 'H', 'G', 'T', '1', '\n', 0};
 const int GT_NH = 4 + GPH_GT_O_COUNT;
-std::string gt_part_path(const char *prefix, int r) { return std::string(prefix) + ".trees.part" + std::to_string(r); }
+/* (written through open_part like the others; read by GtPart below, not by PartReader: its records are no sums) */
+const PartFormat GT_PART = {{'G', 'P', 'H', 'G', 'T', '1', '\n', 0}, ".trees.part", GT_NH, nullptr, true, nullptr, nullptr, 0, false};
 struct GtPart {
   FILE *f = nullptr;
   int32_t h[GT_NH] = {0};
@@ -560,7 +563,7 @@ struct GtPart {
     char magic[8];
     int64_t nsel = -1;
     int32_t nbytes = -1;
-    bool ok = f && fread(magic, 1, 8, f) == 8 && !memcmp(magic, GT_MAGIC, 8) && fread(h, 4, (size_t)GT_NH, f) == (size_t)GT_NH &&
+    bool ok = f && fread(magic, 1, 8, f) == 8 && !memcmp(magic, GT_PART.magic, 8) && fread(h, 4, (size_t)GT_NH, f) == (size_t)GT_NH &&
               fread(&nsel, 8, 1, f) == 1 && nsel >= 0 && h[0] >= 1 && h[1] >= 1 && h[2] >= 0 && h[3] >= 16 * (2 * h[0] - 1);
     if (ok && nsel > 0) { sel.resize((size_t)nsel); ok = fread(sel.data(), 8, (size_t)nsel, f) == (size_t)nsel; }
     ok = ok && fread(&nbytes, 4, 1, f) == 1 && nbytes >= 0;
@@ -585,7 +588,7 @@ struct GtPart {
 extern "C" int gph_gene_trees_discard(const char *prefix, int32_t ranks)
 {
   if (!prefix) return GPH_EARG;
-  for (int r = 0; r < ranks; r++) remove(gt_part_path(prefix, r).c_str());
+  remove_parts(GT_PART, prefix, ranks);
   unlink((std::string(prefix) + ".trees.tsv").c_str());     /* (a file only: whatever else sits under that name is not ours) */
   return GPH_OK;
 }
@@ -599,9 +602,9 @@ extern "C" int gph_gene_trees_write(const char *prefix, int32_t ranks)
   {
     std::vector<GtPart> P((size_t)ranks);
     for (int r = 0; r < ranks && ok; r++) {
-      ok = P[(size_t)r].open(gt_part_path(prefix, r));
+      ok = P[(size_t)r].open(part_path(GT_PART, prefix, r));
       if (ok && r > 0 && (memcmp(P[0].h, P[(size_t)r].h, sizeof P[0].h) || P[0].count != P[(size_t)r].count)) {
-        fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", gt_part_path(prefix, r).c_str());
+        fprintf(stderr, "gphocs_hip: %s does not match rank 0's part\n", part_path(GT_PART, prefix, r).c_str());
         ok = false;
       }
     }
@@ -626,7 +629,7 @@ extern "C" int gph_gene_trees_write(const char *prefix, int32_t ranks)
           row.resize(p.sel.size() * (size_t)rb);
           ok = fread(&it, 4, 1, p.f) == 1 && (row.empty() || fread(row.data(), 1, row.size(), p.f) == row.size());
           if (r == 0) it0 = it;
-          if (!ok || it != it0) { fprintf(stderr, "gphocs_hip: %s ended early or holds another sample than rank 0's part\n", gt_part_path(prefix, r).c_str()); ok = false; break; }
+          if (!ok || it != it0) { fprintf(stderr, "gphocs_hip: %s ended early or holds another sample than rank 0's part\n", part_path(GT_PART, prefix, r).c_str()); ok = false; break; }
           for (size_t q = 0; q < p.sel.size() && ok; q++) {
             int32_t root = 0, nm = 0;
             double dl = 0, gl = 0;
@@ -643,7 +646,7 @@ extern "C" int gph_gene_trees_write(const char *prefix, int32_t ranks)
     }
     if (out && (ferror(out) | fclose(out)) != 0) { fprintf(stderr, "gphocs_hip: writing %s failed\n", path.c_str()); ok = false; }
   }
-  for (int r = 0; r < ranks; r++) remove(gt_part_path(prefix, r).c_str());
+  remove_parts(GT_PART, prefix, ranks);
   if (!ok && out) remove(path.c_str());
   return ok ? GPH_OK : GPH_EARG;
 }
@@ -713,22 +716,6 @@ std::vector<std::string> band_names(const gph_control *C, const gph_config &cfg)
   for (int b = 0; b < cfg.B; b++) v.push_back(std::string(gph_control_pop_name(C, cfg.bandSrc[b])) + "->" + gph_control_pop_name(C, cfg.bandTgt[b]));
   return v;
 }
-// rank `rank`'s part, open, its header written (L: the int64 of the formats that carry one)
-FILE *open_part(const PartFormat &F, const char *prefix, int rank, const int32_t *hdr, int64_t L, const std::vector<std::string> &a,
-                const std::vector<std::string> &b)
-{
-  FILE *f = fopen(part_path(F, prefix, rank).c_str(), "wb");
-  if (!f) return nullptr;
-  std::string names;
-  for (const std::vector<std::string> *v : {&a, &b})
-    for (const std::string &nm : *v) { names += nm; names.push_back('\0'); }
-  const int32_t nbytes = (int32_t)names.size();
-  fwrite(F.magic, 1, 8, f); fwrite(hdr, 4, (size_t)F.nh, f);
-  if (F.has_L) fwrite(&L, 8, 1, f);
-  fwrite(&nbytes, 4, 1, f);
-  fwrite(names.data(), 1, names.size(), f);
-  return f;
-}
 // `got` fetched rows of n elements of esz bytes behind a part, row i with its extra value of xsz bytes, if any, in front of it
 // (ancestry: the iteration) or behind it (coal stats: logPrior)
 int write_rows(FILE *part, const void *rows, size_t esz, int32_t n, int32_t got, const void *extra, size_t xsz, bool in_front)
@@ -743,68 +730,80 @@ int write_rows(FILE *part, const void *rows, size_t esz, int32_t n, int32_t got,
 }
 }   // namespace
 
-static int run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
-                            int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user, gph_comm *comm,
-                            const char *summary_path = nullptr, const char *cs_prefix = nullptr, int32_t cs_capacity = 0,
-                            int32_t ts_slices = 0, const char *an_prefix = nullptr, int32_t an_capacity = 0,
-                            const char *gt_prefix = nullptr, const char *gt_spec = nullptr, int32_t gt_capacity = 0)
+// ---- gph_run: the reference's main() over the engine.  A Run holds what the chain needs and frees it, every output of the program
+// is an Output with the same few operations, the Log prints the acceptance table and searches the finetunes; run_chain strings them together.
+namespace {
+// the caller's options as this library knows them: behind the end of a shorter struct (an older caller) everything is 0 / NULL
+bool take_options(const gph_run_options *in, gph_run_options &o)
 {
-  if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce && !comm)) return GPH_EARG;
-  if (!gt_prefix && (gt_spec || gt_capacity != 0)) { fprintf(stderr, "gphocs_hip: a gene-trees selection or row count needs a gene-trees prefix\n"); return GPH_EARG; }
-  if (gt_capacity < 0) return GPH_EARG;
-  if (ts_slices < 0 || (ts_slices > 0 && !cs_prefix)) { fprintf(stderr, "gphocs_hip: time slices need a coal-stats prefix\n"); return GPH_EARG; }
-  const bool lead = rank == 0;   /* rank 0 talks and writes the trace file; every rank runs the same chain */
+  if (!in || in->size < offsetof(gph_run_options, comm) + sizeof in->comm || in->size > sizeof o) return false;
+  memset(&o, 0, sizeof o);
+  memcpy(&o, in, in->size);
+  return true;
+}
+
+struct Run {
+  const gph_run_options &o;
+  const int32_t rank, world;
+  const bool lead;               /* rank 0 talks and writes the trace file; every rank runs the same chain */
   gph_control *C = nullptr;
   gph_loci *LC = nullptr;
   gph_engine *E = nullptr;
-  gph_mcmc *M = nullptr;
-  gph_config cfg;
-  gph_mcmc_config mc;
-  gph_control_info info;
+  gph_mcmc *M = nullptr;         /* freed in this order: mcmc, engine, loci, control */
+  gph_config cfg; gph_mcmc_config mc; gph_control_info info;   /* gph_control_get */
+  int64_t L = 0, per = 0, lb = 0, le = 0;   /* loci of the sequence file, of a rank's block, this rank's block */
+  const int64_t *offs; const uint8_t *leaf; const uint16_t *ph; const int32_t *cnt, *unph; const double *rates;   /* gph_loci_arrays */
+  FILE *trace = nullptr;
+  std::vector<double> vals;
   char err[512] = "";
-  int rc;
-  FILE *trace = nullptr, *cs_part = nullptr, *ts_part = nullptr, *an_part = nullptr, *gt_part = nullptr;
-  /* a failed run leaves no statistics file and no part behind (several ranks: the caller removes every rank's part) */
-  auto discard_all = [&]() {
-    if (world != 1) return;
-    if (gt_prefix) gph_gene_trees_discard(gt_prefix, 1);
-    if (an_prefix) gph_ancestry_discard(an_prefix, 1);
-    if (cs_prefix) gph_coal_stats_discard(cs_prefix, 1);
-    if (ts_slices) gph_time_slices_discard(cs_prefix, 1);
-  };
-  auto fail = [&](int code, const char *what) {
-    fprintf(stderr, "gphocs_hip: %s failed (status %d)%s%s\n", what, code, err[0] ? ": " : "", err);
-    for (FILE *f : {trace, cs_part, ts_part, an_part, gt_part}) if (f) fclose(f);
-    discard_all();
-    if (M) gph_mcmc_destroy(M);
-    if (E) gph_engine_destroy(E);
+  explicit Run(const gph_run_options &opt) : o(opt), rank(opt.rank), world(opt.world), lead(opt.rank == 0) {}
+  ~Run()
+  {
+    if (trace) fclose(trace);
+    release_device();
     if (LC) gph_loci_free(LC);
     if (C) gph_control_free(C);
+  }
+  void release_device()
+  {
+    if (M) gph_mcmc_destroy(M);
+    if (E) gph_engine_destroy(E);
+    M = nullptr;
+    E = nullptr;
+  }
+  int fail(int code, const char *what)
+  {
+    fprintf(stderr, "gphocs_hip: %s failed (status %d)%s%s\n", what, code, err[0] ? ": " : "", err);
     return code;
-  };
-  if (lead) printf("Reading control settings from file %s...\n", ctl);
-  if (lead && ctl2) printf("Reading control settings from secondary file %s...\n", ctl2);   /* GPhoCS.c:157-158 */
-  if ((rc = gph_control_read(ctl, ctl2, &C))) return fail(rc, "reading the control file");
+  }
+  int check(int rc, const char *what) { return rc ? fail(rc, what) : GPH_OK; }
+  int read_control();
+  int read_loci();
+  int start_engine();
+  int open_trace();
+  void trace_line(int it);
+};
+
+int Run::read_control()
+{
+  int rc;
+  if (lead) printf("Reading control settings from file %s...\n", o.ctl);
+  if (lead && o.ctl2) printf("Reading control settings from secondary file %s...\n", o.ctl2);   /* GPhoCS.c:157-158 */
+  if ((rc = gph_control_read(o.ctl, o.ctl2, &C))) return fail(rc, "reading the control file");
   gph_control_get(C, &cfg, &mc, &info);
   if (lead) printf("Done.\n");
-  if (gt_prefix) {
-    /* the names that will stand in the trees, before anything is computed */
-    for (int p = 0; p < cfg.K; p++)
-      if (!gt_name_ok(gph_control_pop_name(C, p))) {
-        snprintf(err, sizeof err, "the population name '%s' cannot stand in a tree (white space or one of ()[],:;'=&)", gph_control_pop_name(C, p));
-        return fail(GPH_EARG, "--gene-trees");
-      }
-    for (const std::string &nm : leaf_names(C, cfg))
-      if (!gt_name_ok(nm.c_str())) {
-        snprintf(err, sizeof err, "the sample name '%s' cannot stand in a tree (white space or one of ()[],:;'=&)", nm.c_str());
-        return fail(GPH_EARG, "--gene-trees");
-      }
-  }
+  return GPH_OK;
+}
+
+// the seed, the sequence file with readSeqFile's progress text, and this rank's block of the loci
+int Run::read_loci()
+{
+  int rc;
   if (mc.seed < 0) {
     if (world > 1) return fail(GPH_EARG, "random-seed must be given in the control file when several ranks run one chain");
     mc.seed = abs(2 * (int)time(NULL) + 1);   /* GPhoCS.c:188-191 */
   }
-  if (verbose && lead) printf("\nRandom seed set to %d\n", mc.seed);
+  if (o.verbose && lead) printf("\nRandom seed set to %d\n", mc.seed);
 
   auto t0 = std::chrono::steady_clock::now();
   if ((rc = gph_loci_read(C, nullptr, 0, &LC, err, sizeof err))) {
@@ -815,59 +814,51 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     }
     return fail(rc, "reading the sequence file");
   }
-  int64_t L = 0;
   int32_t n = 0;
-  const int64_t *offs; const uint8_t *leaf; const uint16_t *ph; const int32_t *cnt, *unph; const double *rates;
   gph_loci_arrays(LC, &L, &n, &offs, &leaf, &ph, &cnt, &rates, &unph);
-  {
-    int64_t up = 0;
-    for (int64_t g = 0; g < L; g++) up += unph[g];
-    double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (lead) {   /* the progress text of readSeqFile (AlignmentProcessor.c:547, 562, 678-687) and main's blank line (GPhoCS.c:233) */
-      printf("Reading sequence data...  %lld loci, as specified in sequence file %s.\n", (long long)L, info.seqFile);
-      printf("Reading loci (.=100 loci): ");
-      for (int64_t g = 1; g <= L; g++)
-        if (g % 100 == 0) { printf("."); if (g % 1000 == 0) { printf(" "); if (g % 10000 == 0) printf("\n"); } }
-      printf("\n");
-      if (verbose) printf("Read %lld loci over %d samples: %lld patterns (%.2f per locus) -> %lld phased patterns (%.2f per locus) in %.2f s.\n",
+  int64_t up = 0;
+  for (int64_t g = 0; g < L; g++) up += unph[g];
+  double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (lead) {   /* the progress text of readSeqFile (AlignmentProcessor.c:547, 562, 678-687) and main's blank line (GPhoCS.c:233) */
+    printf("Reading sequence data...  %lld loci, as specified in sequence file %s.\n", (long long)L, info.seqFile);
+    printf("Reading loci (.=100 loci): ");
+    for (int64_t g = 1; g <= L; g++)
+      if (g % 100 == 0) { printf("."); if (g % 1000 == 0) { printf(" "); if (g % 10000 == 0) printf("\n"); } }
+    printf("\n");
+    if (o.verbose) printf("Read %lld loci over %d samples: %lld patterns (%.2f per locus) -> %lld phased patterns (%.2f per locus) in %.2f s.\n",
                           (long long)L, n, (long long)up, (double)up / L, (long long)offs[L], (double)offs[L] / L, sec);
-      printf("\n");
-    }
+    printf("\n");
   }
   // loci shard in contiguous blocks of ceil(L / world) (OpenMP static scheduling of the reference, MultiCoreUtils.h:8)
-  const int64_t per = (L + world - 1) / world, lb = std::min<int64_t>(rank * per, L), le = std::min<int64_t>((rank + 1) * per, L);
+  per = (L + world - 1) / world;
+  lb = std::min<int64_t>(rank * per, L);
+  le = std::min<int64_t>((rank + 1) * per, L);
   if ((int64_t)(world - 1) * per >= L) {
     /* the same test on every rank: the whole job stops here, nobody is left waiting in an exchange */
     if (lead) fprintf(stderr, "gphocs_hip: %d ranks over %lld loci in blocks of %lld leave the last rank(s) without loci -- use at most %lld ranks\n",
                       world, (long long)L, (long long)per, (long long)((L + per - 1) / per));
     return fail(GPH_EARG, "sharding the loci over the ranks");
   }
-  std::vector<int64_t> gt_sel;          /* this rank's selected loci (global indices); gt_all: every locus */
-  bool gt_all = true;
-  int64_t gt_widest = 0;                /* selected loci of the rank that holds most: every rank takes the same decisions */
-  if (gt_prefix) {
-    std::vector<int64_t> sel;
-    if ((rc = gt_parse_spec(gt_spec, L, sel, gt_all))) return fail(rc, "--gene-trees-loci");
-    for (int r = 0; r < world; r++) {
-      const int64_t b0 = std::min<int64_t>(r * per, L), b1 = std::min<int64_t>((r + 1) * per, L);
-      int64_t cnt = gt_all ? b1 - b0 : 0;
-      if (!gt_all) for (int64_t g : sel) cnt += g >= b0 && g < b1;
-      gt_widest = std::max(gt_widest, cnt);
-    }
-    if (gt_all) for (int64_t g = lb; g < le; g++) gt_sel.push_back(g);
-    else for (int64_t g : sel) if (g >= lb && g < le) gt_sel.push_back(g);
-  }
+  return GPH_OK;
+}
+
+int Run::start_engine()
+{
+  int rc;
   cfg.L_total = L;
   cfg.locus_begin = lb;
-  cfg.device = device;
+  cfg.device = o.device;
   if ((rc = gph_engine_create(&cfg, &E))) return fail(rc, "gph_engine_create");
-  if (world > 1 && allreduce && (rc = gph_engine_set_allreduce(E, allreduce, user))) return fail(rc, "gph_engine_set_allreduce");
-  if (comm && (rc = gph_engine_set_comm(E, comm))) return fail(rc, "gph_engine_set_comm");
+  if (world > 1 && o.allreduce && (rc = gph_engine_set_allreduce(E, o.allreduce, o.user))) return fail(rc, "gph_engine_set_allreduce");
+  if (o.comm && (rc = gph_engine_set_comm(E, o.comm))) return fail(rc, "gph_engine_set_comm");
   /* pattern offsets are absolute indices into the pattern arrays: the shard is a window of the offset array */
   if ((rc = gph_engine_load_loci(E, le - lb, offs + lb, leaf, ph, cnt, info.mutRateMode == 2 ? rates + lb : nullptr))) return fail(rc, "gph_engine_load_loci");
-  if ((rc = gph_mcmc_create(E, &cfg, &mc, &M))) return fail(rc, "gph_mcmc_create");
+  return check(gph_mcmc_create(E, &cfg, &mc, &M), "gph_mcmc_create");
+}
 
-  // trace file header, GPhoCS.c:1273-1311
+// trace file header, GPhoCS.c:1273-1311
+int Run::open_trace()
+{
   trace = fopen(lead ? info.traceFile : "/dev/null", "w");
   if (!trace) { snprintf(err, sizeof err, "Could not open trace file %s", info.traceFile); return fail(GPH_EARG, "opening the trace file"); }
   fprintf(trace, "Sample");
@@ -879,446 +870,604 @@ static int run_control_file(const char *ctl, const char *ctl2, int32_t device, i
     if (mc.updateSampleAge[p] || mc.sampleAge[p] > 0.0) fprintf(trace, "\ttau_%s", gph_control_pop_name(C, p));
   if (info.mutRateMode == 1) fprintf(trace, "\tVariance-Mut");   /* GPhoCS.c:1311-1312 */
   fprintf(trace, "\tData-ld-ln\tFull-ld-ln\n");
+  vals.assign(mc.numParameters + 4, 0.0);
+  return GPH_OK;
+}
 
-  if (lead) printf("Starting MCMC: %d burnin, %d running, sampled every %d iteration(s).\n", info.burnin, info.numSamples, info.sampleSkip);
-  if (lead && info.mutRateMode == 2) printf("Reading locus rates from file %s... ", info.rateFile);   /* readRateFile's progress text (GPhoCS.c:514), printed from initializeMCMC upstream */
-  int64_t totalCoals = 0;
-  if ((rc = gph_mcmc_initialize(M, &totalCoals))) return fail(rc, "gph_mcmc_initialize");
-  if (summary_path && (rc = gph_engine_locus_summary_enable(E, 1))) return fail(rc, "gph_engine_locus_summary_enable");
-  /* coalescent / sample-pair statistics: the device buffer, this rank's part file and its header */
-  int32_t cs_rd = 0;
-  int64_t cs_written = 0;
-  std::vector<double> cs_rows, cs_prior;
-  std::vector<double> cs_theta(cfg.K), cs_age(cfg.K), cs_mig(cfg.B > 0 ? cfg.B : 1);
-  if (cs_prefix) {
-    if (cs_capacity <= 0) cs_capacity = cs_default_rows(7 + 3 * (cfg.n * (cfg.n - 1) / 2) * cfg.K);
-    if ((rc = gph_engine_coal_stats_enable(E, cs_capacity))) return fail(rc, "gph_engine_coal_stats_enable");
-    gph_engine_coal_stats_shape(E, &cs_rd, nullptr, nullptr, nullptr);
-    cs_rows.resize((size_t)cs_rd * cs_capacity);
-    const int32_t hdr[3] = {cfg.n, cfg.K, cs_rd};
-    cs_part = open_part(CS_PART, cs_prefix, rank, hdr, L, leaf_names(C, cfg), pop_names(C, cfg));
-    if (!cs_part) { snprintf(err, sizeof err, "Could not open %s", part_path(CS_PART, cs_prefix, rank).c_str()); return fail(GPH_EARG, "opening the coal-stats part file"); }
+void Run::trace_line(int it)   /* GPhoCS.c:1763-1769 */
+{
+  double logL = 0, dataL = 0;
+  gph_mcmc_param_vals(M, vals.data(), mc.numParameters);
+  gph_mcmc_get_state(M, &logL, &dataL, nullptr, nullptr, nullptr);
+  fprintf(trace, "%d\t", it);
+  for (int i = 0; i < mc.numParameters; i++) fprintf(trace, "%8.5f\t", vals[i] * mc.printFactors[i]);
+  fprintf(trace, "\t%.6f\t%.6f\n", logL, dataL);
+  fflush(trace);
+}
+
+// ---- the outputs.  open: enable on the engine, take the shape, size the host buffer, open this rank's part and write its
+// header; sample: at a trace line, and a flush when the buffer is full; close: the last flush, the trailer, the part closed;
+// write / discard: what becomes of the ranks' parts once the last rank is done (gph_run_finish)
+struct Output {
+  virtual ~Output() {}
+  virtual int open(Run &R) = 0;
+  virtual int sample(Run &R, int it) = 0;
+  virtual int close(Run &R) = 0;
+  virtual int write(int32_t) { return GPH_OK; }
+  virtual void discard(int32_t) {}
+};
+
+// this rank's part file of one output, as the messages name it
+struct Part {
+  const std::string name;
+  FILE *f = nullptr;
+  int64_t written = 0;
+  explicit Part(const char *nm) : name(nm) {}
+  ~Part() { if (f) fclose(f); }
+  /* open, the header written (L: the int64 of the formats that carry one; the gene-trees part: L selected loci and, behind it,
+   * their indices) */
+  int open(Run &R, const PartFormat &F, const char *prefix, const int32_t *hdr, int64_t L, const int64_t *sel,
+           std::initializer_list<std::vector<std::string>> groups)
+  {
+    if (!(f = fopen(part_path(F, prefix, R.rank).c_str(), "wb"))) {
+      snprintf(R.err, sizeof R.err, "Could not open %s", part_path(F, prefix, R.rank).c_str());
+      return R.fail(GPH_EARG, ("opening the " + name + " part file").c_str());
+    }
+    std::string names;
+    for (const std::vector<std::string> &v : groups)
+      for (const std::string &nm : v) { names += nm; names.push_back('\0'); }
+    const int32_t nbytes = (int32_t)names.size();
+    fwrite(F.magic, 1, 8, f); fwrite(hdr, 4, (size_t)F.nh, f);
+    if (F.has_L) fwrite(&L, 8, 1, f);
+    if (sel && L > 0) fwrite(sel, 8, (size_t)L, f);
+    fwrite(&nbytes, 4, 1, f);
+    fwrite(names.data(), 1, names.size(), f);
+    return GPH_OK;
   }
-  /* time-sliced statistics: a device buffer of as many rows, this rank's part file and its header */
-  int32_t ts_rd = 0;
-  int64_t ts_written = 0;
-  std::vector<double> ts_rows;
-  if (ts_slices) {
-    if ((rc = gph_engine_time_slices_enable(E, ts_slices, cs_capacity))) return fail(rc, "gph_engine_time_slices_enable");
-    gph_engine_time_slices_shape(E, &ts_rd, nullptr, nullptr, nullptr, nullptr, nullptr);
-    ts_rows.resize((size_t)ts_rd * cs_capacity);
-    const int32_t hdr[4] = {ts_slices, cfg.K, cfg.B, ts_rd};
-    ts_part = open_part(TS_PART, cs_prefix, rank, hdr, 0, pop_names(C, cfg), band_names(C, cfg));
-    if (!ts_part) { snprintf(err, sizeof err, "Could not open %s", part_path(TS_PART, cs_prefix, rank).c_str()); return fail(GPH_EARG, "opening the time-slices part file"); }
+  int written_ok(Run &R, int rc) { return R.check(rc, ("writing the " + name + " part file").c_str()); }
+  /* the filled rows of a device buffer behind the part: fetch(&got) brings them to `rows`, write_rows sets each with its
+   * extra value; the one host synchronisation of an output */
+  template <class Fetch> int flush(Run &R, Fetch fetch, const void *rows, size_t esz, int32_t n, const void *extra, size_t xsz, bool in_front)
+  {
+    int32_t got = 0;
+    int rc = fetch(&got);
+    if (!rc) rc = write_rows(f, rows, esz, n, got, extra, xsz, in_front);
+    written += got;
+    return written_ok(R, rc);
   }
-  /* migration ancestry: accumulators and a device buffer of an_capacity per-sample rows, this rank's part file and its header */
-  int32_t an_ncol = 0, an_ri = 0;
-  int64_t an_written = 0;
-  std::vector<int32_t> an_rows, an_iters;
-  std::vector<std::string> an_names;
-  if (an_prefix) {
-    if (an_capacity <= 0) an_capacity = 64;
-    if ((rc = gph_engine_ancestry_enable(E, an_capacity, 0))) return fail(rc, "gph_engine_ancestry_enable");
-    gph_engine_ancestry_shape(E, &an_ncol, &an_ri, nullptr, nullptr);
-    an_rows.resize((size_t)an_ri * an_capacity);
-    an_iters.resize((size_t)an_capacity);
-    an_names = leaf_names(C, cfg);
-    const int32_t hdr[3] = {cfg.n, cfg.B, an_ri};
-    an_part = open_part(AN_PART, an_prefix, rank, hdr, 0, an_names, band_names(C, cfg));
-    if (!an_part) { snprintf(err, sizeof err, "Could not open %s", part_path(AN_PART, an_prefix, rank).c_str()); return fail(GPH_EARG, "opening the ancestry part file"); }
+  /* the trailer: records in this part (ancestry: and the bytes of text behind them) */
+  int close(Run &R, int64_t text_bytes = -1)
+  {
+    const int64_t tail[2] = {written, text_bytes};
+    const size_t nt = text_bytes < 0 ? 1 : 2;
+    if (fwrite(tail, 8, nt, f) != nt) return written_ok(R, GPH_EARG);
+    const int rcc = ferror(f) | fclose(f);
+    f = nullptr;
+    return R.check(rcc ? GPH_EARG : GPH_OK, ("closing the " + name + " part file").c_str());
   }
-  int32_t an_held = 0;
-  /* sampled genealogies: the row buffer for this rank's selected loci, this rank's part file and its header */
-  int32_t gt_rb = 0, gt_held = 0;
-  int64_t gt_written = 0;
-  std::vector<char> gt_rows;
-  std::vector<int32_t> gt_iters;
-  if (gt_prefix) {
+};
+
+struct LocusSummary : Output {
+  int32_t ncol = 0;
+  int64_t samples = 0;
+  std::vector<double> raw;
+  int open(Run &R) override { return R.check(gph_engine_locus_summary_enable(R.E, 1), "gph_engine_locus_summary_enable"); }
+  int sample(Run &R, int) override { return R.check(gph_engine_locus_summary_sample(R.E), "gph_engine_locus_summary_sample"); }
+  int close(Run &R) override
+  {
+    gph_engine_locus_summary_columns(R.E, &ncol, &samples);
+    raw.resize((size_t)ncol * (R.le - R.lb));
+    return R.check(gph_engine_locus_summary_fetch(R.E, raw.data(), ncol, 0), "gph_engine_locus_summary_fetch");
+  }
+  /* one rank: the file itself; several: this rank's part, concatenated in rank order by the caller (rank 0's has the header) */
+  int write_table(Run &R)
+  {
+    const std::string path = R.world > 1 ? std::string(R.o.locus_summary_path) + ".part" + std::to_string(R.rank) : std::string(R.o.locus_summary_path);
+    return write_locus_summary(path, R.lead, R.C, R.cfg, R.LC, R.lb, R.le - R.lb, ncol, samples, raw, R.info.mutRateMode == 1);
+  }
+};
+
+// coalescent / sample-pair statistics and, with slices > 0, the time-sliced statistics: one prefix, device buffers of as many
+// rows that fill and are flushed together, logPrior behind every coal-stats row
+struct CoalStats : Output {
+  const char *prefix;
+  int32_t capacity, slices, rd = 0, ts_rd = 0;
+  Part cs{"coal-stats"}, ts{"time-slices"};
+  std::vector<double> rows, prior, ts_rows, theta, age, mig;
+  explicit CoalStats(const gph_run_options &o) : prefix(o.coal_stats_prefix), capacity(o.coal_stats_rows), slices(o.time_slices) {}
+  static int validate(const gph_run_options &o)
+  {
+    const bool ok = o.time_slices == 0 || (o.time_slices > 0 && o.coal_stats_prefix);
+    if (!ok) fprintf(stderr, "gphocs_hip: time slices need a coal-stats prefix\n");
+    return ok ? GPH_OK : GPH_EARG;
+  }
+  int open(Run &R) override
+  {
+    int rc;
+    const gph_config &cfg = R.cfg;
+    theta.resize(cfg.K); age.resize(cfg.K); mig.resize(cfg.B > 0 ? cfg.B : 1);
+    if (capacity <= 0) capacity = cs_default_rows(7 + 3 * (cfg.n * (cfg.n - 1) / 2) * cfg.K);
+    if ((rc = gph_engine_coal_stats_enable(R.E, capacity))) return R.fail(rc, "gph_engine_coal_stats_enable");
+    gph_engine_coal_stats_shape(R.E, &rd, nullptr, nullptr, nullptr);
+    rows.resize((size_t)rd * capacity);
+    const int32_t hdr[3] = {cfg.n, cfg.K, rd};
+    if ((rc = cs.open(R, CS_PART, prefix, hdr, R.L, nullptr, {leaf_names(R.C, cfg), pop_names(R.C, cfg)})) || !slices) return rc;
+    if ((rc = gph_engine_time_slices_enable(R.E, slices, capacity))) return R.fail(rc, "gph_engine_time_slices_enable");
+    gph_engine_time_slices_shape(R.E, &ts_rd, nullptr, nullptr, nullptr, nullptr, nullptr);
+    ts_rows.resize((size_t)ts_rd * capacity);
+    const int32_t ts_hdr[4] = {slices, cfg.K, cfg.B, ts_rd};
+    return ts.open(R, TS_PART, prefix, ts_hdr, 0, nullptr, {pop_names(R.C, cfg), band_names(R.C, cfg)});
+  }
+  /* logPrior of the parameters a trace line shows: what getLogPrior sums (GPhoCS.c:858-898) -- theta of every population,
+   * tau of every ancestral one, the rate of every band, each under its gamma prior of the control file */
+  double log_prior(Run &R)
+  {
+    const gph_config &cfg = R.cfg;
+    const gph_mcmc_config &mc = R.mc;
+    gph_mcmc_get_state(R.M, nullptr, nullptr, theta.data(), age.data(), mig.data());
+    /* log density of a gamma(shape, rate) prior at x: shape ln(rate) - ln Gamma(shape) + (shape - 1) ln x - rate x */
+    auto gamma_lpdf = [](double shape, double rate, double x) {
+      return shape * std::log(rate) - std::lgamma(shape) + (shape - 1.0) * std::log(x) - rate * x;
+    };
+    double lp = 0.0;
+    for (int p = 0; p < cfg.K; p++) lp += gamma_lpdf(mc.thetaAlpha[p], mc.thetaBeta[p], theta[p]);
+    for (int p = cfg.Kc; p < cfg.K; p++) lp += gamma_lpdf(mc.ageAlpha[p], mc.ageBeta[p], age[p]);
+    for (int b = 0; b < cfg.B; b++) lp += gamma_lpdf(mc.mrAlpha[b], mc.mrBeta[b], mig[b]);
+    return lp;
+  }
+  /* (both buffers have `capacity` rows and fill together) */
+  int flush(Run &R)
+  {
+    auto fetch = [&](int32_t *got) {
+      const int rc = gph_engine_coal_stats_fetch(R.E, rows.data(), capacity, got);
+      return rc ? rc : *got != (int32_t)prior.size() ? GPH_ESTATE : GPH_OK;
+    };
+    const int rc = cs.flush(R, fetch, rows.data(), sizeof(double), rd, prior.data(), sizeof(double), false);
+    prior.clear();
+    if (rc || !slices) return rc;
+    return ts.flush(R, [&](int32_t *got) { return gph_engine_time_slices_fetch(R.E, ts_rows.data(), capacity, got); }, ts_rows.data(),
+                    sizeof(double), ts_rd, nullptr, 0, false);
+  }
+  int sample(Run &R, int it) override
+  {
+    int rc;
+    if ((rc = gph_engine_coal_stats_sample(R.E, it))) return R.fail(rc, "gph_engine_coal_stats_sample");
+    if (slices && (rc = gph_engine_time_slices_sample(R.E, it))) return R.fail(rc, "gph_engine_time_slices_sample");
+    prior.push_back(log_prior(R));
+    return (int32_t)prior.size() < capacity ? GPH_OK : flush(R);
+  }
+  int close(Run &R) override
+  {
+    int rc;
+    if ((rc = flush(R)) || (rc = cs.close(R)) || !slices) return rc;
+    return ts.close(R);
+  }
+  /* (the slices file first; should the coal-stats files fail after it, one file is removed again, not 1 + 3 K) */
+  int write(int32_t ranks) override { const int rc = slices ? gph_time_slices_write(prefix, ranks) : GPH_OK; return rc ? rc : gph_coal_stats_write(prefix, ranks); }
+  void discard(int32_t ranks) override { gph_coal_stats_discard(prefix, ranks); if (slices) gph_time_slices_discard(prefix, ranks); }
+};
+
+// migration ancestry: accumulators and a device buffer of per-sample rows; the part's records each behind their iteration
+struct Ancestry : Output {
+  const char *prefix;
+  int32_t capacity, held = 0, ncol = 0, ri = 0;
+  Part part{"ancestry"};
+  std::vector<int32_t> rows, iters;
+  std::vector<std::string> names;
+  explicit Ancestry(const gph_run_options &o) : prefix(o.ancestry_prefix), capacity(o.ancestry_rows) {}
+  int open(Run &R) override
+  {
+    int rc;
+    if (capacity <= 0) capacity = 64;
+    if ((rc = gph_engine_ancestry_enable(R.E, capacity, 0))) return R.fail(rc, "gph_engine_ancestry_enable");
+    gph_engine_ancestry_shape(R.E, &ncol, &ri, nullptr, nullptr);
+    rows.resize((size_t)ri * capacity);
+    iters.resize((size_t)capacity);
+    names = leaf_names(R.C, R.cfg);
+    const int32_t hdr[3] = {R.cfg.n, R.cfg.B, ri};
+    return part.open(R, AN_PART, prefix, hdr, 0, nullptr, {names, band_names(R.C, R.cfg)});
+  }
+  int flush(Run &R)
+  {
+    held = 0;
+    return part.flush(R, [&](int32_t *got) { return gph_engine_ancestry_fetch_rows(R.E, iters.data(), rows.data(), ri, capacity, got); },
+                      rows.data(), 4, ri, iters.data(), 4, true);
+  }
+  int sample(Run &R, int it) override
+  {
+    const int rc = R.check(gph_engine_ancestry_sample(R.E, it), "gph_engine_ancestry_sample");
+    return rc || ++held < capacity ? rc : flush(R);
+  }
+  /* this rank's rows of the per-locus table, as text behind its records */
+  int close(Run &R) override
+  {
+    int rc;
+    if ((rc = flush(R))) return rc;
+    int64_t S = 0;
+    gph_engine_ancestry_shape(R.E, nullptr, nullptr, &S, nullptr);
+    std::vector<double> raw((size_t)ncol * (R.le - R.lb));
+    if ((rc = gph_engine_ancestry_fetch_loci(R.E, raw.data(), ncol, 0))) return R.fail(rc, "gph_engine_ancestry_fetch_loci");
+    const long text0 = ftell(part.f);
+    const int n = R.cfg.n, B = R.cfg.B;
+    const double Sd = (double)S;
+    for (int64_t g = 0; g < R.le - R.lb; g++) {
+      const double *a = raw.data() + (size_t)g * ncol;
+      const char *nm = gph_loci_name(R.LC, R.lb + g);
+      for (int i = 0; i < n; i++) {
+        const double any = a[2 * B * n + i];
+        if (!(any > 0.0)) continue;
+        fprintf(part.f, "%lld\t%s\t%d\t%s\t%lld\t%.10g", (long long)(R.lb + g), nm ? nm : "", i, names[i].c_str(), (long long)S, any / Sd);
+        for (int b = 0; b < B; b++) {
+          const double c = a[b * n + i], t = a[B * n + b * n + i];
+          fprintf(part.f, "\t%.10g\t%.10g", c / Sd, c > 0.0 ? t / c : 0.0);
+        }
+        fprintf(part.f, "\n");
+      }
+    }
+    const long text1 = ftell(part.f);
+    return text0 < 0 || text1 < text0 ? part.written_ok(R, GPH_EARG) : part.close(R, (int64_t)(text1 - text0));
+  }
+  int write(int32_t ranks) override { return gph_ancestry_write(prefix, ranks); }
+  void discard(int32_t ranks) override { gph_ancestry_discard(prefix, ranks); }
+};
+
+// sampled genealogies: the row buffer for this rank's selected loci; the part's samples each behind their iteration
+struct GeneTrees : Output {
+  const char *prefix, *spec;
+  int32_t capacity, held = 0, rb = 0;
+  Part part{"gene-trees"};
+  std::vector<int64_t> sel;          /* this rank's selected loci (global indices) */
+  int64_t widest = 0;                /* selected loci of the rank that holds most: every rank takes the same decisions */
+  std::vector<char> rows;
+  std::vector<int32_t> iters;
+  explicit GeneTrees(const gph_run_options &o) : prefix(o.gene_trees_prefix), spec(o.gene_trees_loci), capacity(o.gene_trees_rows) {}
+  static int validate(const gph_run_options &o)
+  {
+    if (!o.gene_trees_prefix && (o.gene_trees_loci || o.gene_trees_rows != 0)) { fprintf(stderr, "gphocs_hip: a gene-trees selection or row count needs a gene-trees prefix\n"); return GPH_EARG; }
+    return o.gene_trees_rows < 0 ? GPH_EARG : GPH_OK;
+  }
+  /* the names that will stand in the trees, once the control file is read and before anything is computed */
+  int check_names(Run &R)
+  {
+    auto refuse = [&](const char *kind, const char *nm) {
+      snprintf(R.err, sizeof R.err, "the %s name '%s' cannot stand in a tree (white space or one of ()[],:;'=&)", kind, nm);
+      return R.fail(GPH_EARG, "--gene-trees");
+    };
+    for (int p = 0; p < R.cfg.K; p++)
+      if (!gt_name_ok(gph_control_pop_name(R.C, p))) return refuse("population", gph_control_pop_name(R.C, p));
+    for (const std::string &nm : leaf_names(R.C, R.cfg))
+      if (!gt_name_ok(nm.c_str())) return refuse("sample", nm.c_str());
+    return GPH_OK;
+  }
+  /* the selection over the loci just read, and this rank's share of it */
+  int select(Run &R)
+  {
+    std::vector<int64_t> all_sel, held_by(R.world, 0);
+    bool all = true;
+    if (int rc = gt_parse_spec(spec, R.L, all_sel, all)) return R.fail(rc, "--gene-trees-loci");
+    if (all) for (int64_t g = 0; g < R.L; g++) all_sel.push_back(g);
+    for (int64_t g : all_sel) {
+      widest = std::max(widest, ++held_by[g / R.per]);
+      if (g >= R.lb && g < R.le) sel.push_back(g);
+    }
+    return GPH_OK;
+  }
+  int open(Run &R) override
+  {
     /* the bytes of a record (the same on every rank) from an empty selection, then the rows that fit */
+    int rc;
     const int64_t none = 0;
-    if ((rc = gph_engine_gene_trees_enable(E, 1, &none, 0, 0))) return fail(rc, "gph_engine_gene_trees_enable");
-    gph_engine_gene_trees_shape(E, nullptr, nullptr, &gt_rb, nullptr, nullptr);
-    const int64_t limit = (int64_t)256 << 20, row_bytes = gt_widest * gt_rb;
+    if ((rc = gph_engine_gene_trees_enable(R.E, 1, &none, 0, 0))) return R.fail(rc, "gph_engine_gene_trees_enable");
+    gph_engine_gene_trees_shape(R.E, nullptr, nullptr, &rb, nullptr, nullptr);
+    const int64_t limit = (int64_t)256 << 20, row_bytes = widest * rb;
     if (row_bytes > limit) {
-      snprintf(err, sizeof err, "one sample of %lld loci x %d bytes a record is %lld bytes, the limit is %lld: narrow --gene-trees-loci",
-               (long long)gt_widest, (int)gt_rb, (long long)row_bytes, (long long)limit);
-      return fail(GPH_EFULL, "--gene-trees");
+      snprintf(R.err, sizeof R.err, "one sample of %lld loci x %d bytes a record is %lld bytes, the limit is %lld: narrow --gene-trees-loci",
+               (long long)widest, (int)rb, (long long)row_bytes, (long long)limit);
+      return R.fail(GPH_EFULL, "--gene-trees");
     }
     const int64_t fit = row_bytes > 0 ? limit / row_bytes : limit;
-    gt_capacity = (int32_t)std::min<int64_t>(gt_capacity > 0 ? gt_capacity : 64, fit);
+    capacity = (int32_t)std::min<int64_t>(capacity > 0 ? capacity : 64, fit);
     /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
-    if ((rc = gph_engine_gene_trees_enable(E, gt_capacity, gt_sel.empty() ? &none : gt_sel.data(), (int64_t)gt_sel.size(), 0))) return fail(rc, "gph_engine_gene_trees_enable");
-    int32_t offs[GPH_GT_O_COUNT];
-    gph_engine_gene_trees_shape(E, nullptr, nullptr, nullptr, offs, nullptr);
-    gt_rows.resize((size_t)gt_capacity * gt_sel.size() * (size_t)gt_rb);
-    gt_iters.resize((size_t)gt_capacity);
-    gt_part = fopen(gt_part_path(gt_prefix, rank).c_str(), "wb");
-    if (!gt_part) { snprintf(err, sizeof err, "Could not open %s", gt_part_path(gt_prefix, rank).c_str()); return fail(GPH_EARG, "opening the gene-trees part file"); }
-    int32_t hdr[GT_NH] = {cfg.n, cfg.K, cfg.B, gt_rb};
-    memcpy(hdr + 4, offs, sizeof offs);
-    std::string names;
-    for (const std::string &nm : pop_names(C, cfg)) { names += nm; names.push_back('\0'); }
-    for (const std::string &nm : band_names(C, cfg)) { names += nm; names.push_back('\0'); }
-    const std::vector<std::string> leaves = leaf_names(C, cfg);
-    for (int i = 0; i < cfg.n; i++) { names += leaves[(size_t)i] + "." + std::to_string(i); names.push_back('\0'); }
-    for (int64_t g : gt_sel) { const char *nm = gph_loci_name(LC, g); names += nm ? nm : ""; names.push_back('\0'); }
-    const int64_t nsel = (int64_t)gt_sel.size();
-    const int32_t nbytes = (int32_t)names.size();
-    fwrite(GT_MAGIC, 1, 8, gt_part); fwrite(hdr, 4, (size_t)GT_NH, gt_part); fwrite(&nsel, 8, 1, gt_part);
-    if (nsel > 0) fwrite(gt_sel.data(), 8, (size_t)nsel, gt_part);
-    fwrite(&nbytes, 4, 1, gt_part); fwrite(names.data(), 1, names.size(), gt_part);
+    if ((rc = gph_engine_gene_trees_enable(R.E, capacity, sel.empty() ? &none : sel.data(), (int64_t)sel.size(), 0))) return R.fail(rc, "gph_engine_gene_trees_enable");
+    int32_t hdr[GT_NH] = {R.cfg.n, R.cfg.K, R.cfg.B, rb};
+    gph_engine_gene_trees_shape(R.E, nullptr, nullptr, nullptr, hdr + 4, nullptr);
+    rows.resize((size_t)capacity * sel.size() * (size_t)rb);
+    iters.resize((size_t)capacity);
+    std::vector<std::string> labels = leaf_names(R.C, R.cfg), loci;
+    for (int i = 0; i < R.cfg.n; i++) labels[(size_t)i] += "." + std::to_string(i);
+    for (int64_t g : sel) { const char *nm = gph_loci_name(R.LC, g); loci.push_back(nm ? nm : ""); }
+    return part.open(R, GT_PART, prefix, hdr, (int64_t)sel.size(), sel.data(), {pop_names(R.C, R.cfg), band_names(R.C, R.cfg), labels, loci});
   }
-  /* the rows of the buffer behind this rank's part, each behind its iteration: the one host synchronisation of the option */
-  auto gt_flush = [&]() -> int {
-    int32_t got = 0;
-    int rcf = gph_engine_gene_trees_fetch(E, gt_iters.data(), gt_rows.data(), gt_capacity, &got);
-    if (rcf) return rcf;
-    gt_written += got;
-    gt_held = 0;
-    return write_rows(gt_part, gt_rows.data(), (size_t)gt_rb, (int32_t)gt_sel.size(), got, gt_iters.data(), 4, true);
-  };
-  /* the filled rows of a device buffer behind this rank's part: ancestry rows each behind their iteration, coal-stats rows
-   * each in front of their logPrior */
-  auto an_flush = [&]() -> int {
-    int32_t got = 0;
-    int rcf = gph_engine_ancestry_fetch_rows(E, an_iters.data(), an_rows.data(), an_ri, an_capacity, &got);
-    if (rcf) return rcf;
-    an_written += got;
-    an_held = 0;
-    return write_rows(an_part, an_rows.data(), 4, an_ri, got, an_iters.data(), 4, true);
-  };
-  auto ts_flush = [&]() -> int {
-    int32_t got = 0;
-    int rcf = gph_engine_time_slices_fetch(E, ts_rows.data(), cs_capacity, &got);
-    if (rcf) return rcf;
-    ts_written += got;
-    return write_rows(ts_part, ts_rows.data(), sizeof(double), ts_rd, got, nullptr, 0, false);
-  };
-  auto cs_flush = [&]() -> int {
-    int32_t got = 0;
-    int rcf = gph_engine_coal_stats_fetch(E, cs_rows.data(), cs_capacity, &got);
-    if (rcf) return rcf;
-    if (got != (int32_t)cs_prior.size()) return GPH_ESTATE;
-    rcf = write_rows(cs_part, cs_rows.data(), sizeof(double), cs_rd, got, cs_prior.data(), sizeof(double), false);
-    cs_written += got;
-    cs_prior.clear();
-    return rcf;
-  };
-  std::vector<double> vals(mc.numParameters + 4, 0.0);
-  double logL = 0, dataL = 0;
-  auto t1 = std::chrono::steady_clock::now();
+  int flush(Run &R)
+  {
+    held = 0;
+    return part.flush(R, [&](int32_t *got) { return gph_engine_gene_trees_fetch(R.E, iters.data(), rows.data(), capacity, got); },
+                      rows.data(), (size_t)rb, (int32_t)sel.size(), iters.data(), 4, true);
+  }
+  int sample(Run &R, int it) override
+  {
+    const int rc = R.check(gph_engine_gene_trees_sample(R.E, it), "gph_engine_gene_trees_sample");
+    return rc || ++held < capacity ? rc : flush(R);
+  }
+  int close(Run &R) override { const int rc = flush(R); return rc ? rc : part.close(R); }
+  int write(int32_t ranks) override { return gph_gene_trees_write(prefix, ranks); }
+  void discard(int32_t ranks) override { gph_gene_trees_discard(prefix, ranks); }
+};
+
+// the enabled outputs in the order of their engine calls at a sample, which is also the order in which gph_run_finish writes
+// their files (the groups of fewer files first: should a later one fail, fewer are removed again).  A run closes them in the
+// opposite order, as it always did, and opens them in that order too: the summary is now enabled last, not first
+struct Outputs {
+  std::vector<std::unique_ptr<Output>> list;
+  LocusSummary *summary = nullptr;   /* these two have a step of their own in run_chain */
+  GeneTrees *trees = nullptr;
+  explicit Outputs(const gph_run_options &o)
+  {
+    if (o.locus_summary_path) list.emplace_back(summary = new LocusSummary);
+    if (o.gene_trees_prefix) list.emplace_back(trees = new GeneTrees(o));
+    if (o.ancestry_prefix) list.emplace_back(new Ancestry(o));
+    if (o.coal_stats_prefix) list.emplace_back(new CoalStats(o));
+  }
+};
+
+// ---- the log on stdout and the find-finetunes search (GPhoCS.c:1329, 1356-1447, 1808-2249)
+struct Log {
+  Run &R;
+  const int64_t totalCoals;
   const time_t wall0 = time(NULL);
-  auto printtime = [&](char *buf, size_t len) {   /* printtime(), utils.c:314-326 */
+  int logsPerLine = R.info.logsPerLine, samplesPerLog = R.mc.samplesPerLog, findingFinetunes = 0;
+  Finetune fCoal{R.mc.ftCoalTime}, fMig{R.mc.ftMigTime}, fTheta{R.mc.ftTheta}, fRate{R.mc.ftMigRate}, fMix{R.mc.ftMixing}, fLocus{R.mc.ftLocusRate}, fAdmix{-1.0};
+  /* fAdmix: upstream also bisects the (unused) admixture step and prints it (GPhoCS.c:2040-2066, 2190) */
+  std::vector<Finetune> fTau = std::vector<Finetune>(R.cfg.K);
+  int64_t logCount = 1, a0[9] = {0}, aLocus0 = 0;
+  std::vector<int64_t> t0v = std::vector<int64_t>(R.cfg.K, 0), tv = t0v;
+  /* TAU columns of the log exactly as upstream accumulates them (GPhoCS.c:1620-1650): the whole accept array is
+   * added after UpdateTau AND after UpdateSampleAge, so an ancestral population's count goes in twice and an
+   * estimated sample age's goes in once stale (the previous iteration's) and once fresh */
+  std::vector<int64_t> tauPrevTotal = t0v, tauLastIter = t0v, tauShown = t0v;
+  Log(Run &run, int64_t coals) : R(run), totalCoals(coals) { for (int p = 0; p < R.cfg.K; p++) fTau[p].v = R.mc.ftTaus[p]; }
+  const char *printtime(char *buf, size_t len) const   /* printtime(), utils.c:314-326 */
+  {
     const long t = (long)(time(NULL) - wall0);
     const long h = t / 3600, mm = (t % 3600) / 60, ss = t - (t / 60) * 60;
     if (h) snprintf(buf, len, "%ld:%02ld:%02ld", h, mm, ss);
     else snprintf(buf, len, "%2ld:%02ld", mm, ss);
     return buf;
-  };
-  char tbuf[64];
-  // the log on stdout: title, GPhoCS.c:1329, 1356-1374
-  if (lead) {
-    printf("There are %d parameters in the model.\n", mc.numParameters);
+  }
+  int push_finetunes()
+  {
+    std::vector<double> taus(R.cfg.K);
+    for (int p = 0; p < R.cfg.K; p++) taus[p] = fTau[p].v;
+    gph_mcmc_set_locus_rate_finetune(R.M, fLocus.v);
+    return R.check(gph_mcmc_set_finetunes(R.M, fCoal.v, fMig.v, fTheta.v, fRate.v, fMix.v, taus.data()), "gph_mcmc_set_finetunes");
+  }
+  int start();
+  void account();
+  int period(int it);
+};
+
+// the title and, where the control file asks for it, the start of the search
+int Log::start()
+{
+  if (R.lead) {
+    printf("There are %d parameters in the model.\n", R.mc.numParameters);
     printf("Samples   CoalTimes MigTimes  SPRs      Thetas    MigRates ");
-    for (int p = 0; p < cfg.K; p++) if (p >= cfg.Kc || mc.updateSampleAge[p]) printf("TAU_%2d    ", p);
+    for (int p = 0; p < R.cfg.K; p++) if (p >= R.cfg.Kc || R.mc.updateSampleAge[p]) printf("TAU_%2d    ", p);
     printf("RbberBnd  MutRates  Mixing    | DATA-ln-ld |  TIME\n");
     printf("-------------------------------------------------------------"
            "-------------------------------------------------------------"
            "---------------------------\n");
     fflush(stdout);
   }
-  int logsPerLine = info.logsPerLine;
-  // log periods and the find-finetunes search, GPhoCS.c:1401-1447, 1808-2249
-  int samplesPerLog = mc.samplesPerLog, findingFinetunes = 0;
-  Finetune fCoal{mc.ftCoalTime}, fMig{mc.ftMigTime}, fTheta{mc.ftTheta}, fRate{mc.ftMigRate}, fMix{mc.ftMixing}, fLocus{mc.ftLocusRate}, fAdmix{-1.0};
-  /* fAdmix: upstream also bisects the (unused) admixture step and prints it (GPhoCS.c:2040-2066, 2190) */
-  std::vector<Finetune> fTau(cfg.K);
-  for (int p = 0; p < cfg.K; p++) fTau[p].v = mc.ftTaus[p];
-  auto push_finetunes = [&]() {
-    std::vector<double> taus(cfg.K);
-    for (int p = 0; p < cfg.K; p++) taus[p] = fTau[p].v;
-    gph_mcmc_set_locus_rate_finetune(M, fLocus.v);
-    return gph_mcmc_set_finetunes(M, fCoal.v, fMig.v, fTheta.v, fRate.v, fMix.v, taus.data());
-  };
-  if (info.findFinetunes) {
-    findingFinetunes = 1;
-    samplesPerLog = info.findFinetunesSamplesPerStep;
-    logsPerLine = 1;
-    if (lead) {
-      printf("   ---  Dynamically finding finetune settings for the first %d samples, updating finetunes every %d samples  ---- \n",
-             samplesPerLog * info.findFinetunesNumSteps, samplesPerLog);
-      printf("------------------------------------------------------------"
-             "------------------------------------------------------------"
-             "-----------------------------\n");
-    }
-    for (Finetune *f : {&fCoal, &fMig, &fTheta, &fRate, &fMix, &fLocus, &fAdmix}) if (f->v < 0) f->v = 1.0;
-    for (int p = 0; p < cfg.K; p++) if (fTau[p].v < 0) fTau[p].v = 1.0;
-    if ((rc = push_finetunes())) return fail(rc, "gph_mcmc_set_finetunes");
-    gph_mcmc_set_log_period(M, samplesPerLog);
+  if (!R.info.findFinetunes) return GPH_OK;
+  findingFinetunes = 1;
+  samplesPerLog = R.info.findFinetunesSamplesPerStep;
+  logsPerLine = 1;
+  if (R.lead) {
+    printf("   ---  Dynamically finding finetune settings for the first %d samples, updating finetunes every %d samples  ---- \n",
+           samplesPerLog * R.info.findFinetunesNumSteps, samplesPerLog);
+    printf("------------------------------------------------------------"
+           "------------------------------------------------------------"
+           "-----------------------------\n");
   }
-  int64_t logCount = 1, a0[9] = {0}, a[9], aLocus0 = 0, aLocus = 0;
-  std::vector<int64_t> t0v(cfg.K, 0), tv(cfg.K, 0);
-  /* TAU columns of the log exactly as upstream accumulates them (GPhoCS.c:1620-1650): the whole accept array is
-   * added after UpdateTau AND after UpdateSampleAge, so an ancestral population's count goes in twice and an
-   * estimated sample age's goes in once stale (the previous iteration's) and once fresh */
-  std::vector<int64_t> tauPrevTotal(cfg.K, 0), tauLastIter(cfg.K, 0), tauShown(cfg.K, 0);
+  for (Finetune *f : {&fCoal, &fMig, &fTheta, &fRate, &fMix, &fLocus, &fAdmix}) if (f->v < 0) f->v = 1.0;
+  for (int p = 0; p < R.cfg.K; p++) if (fTau[p].v < 0) fTau[p].v = 1.0;
+  if (int rc = push_finetunes()) return rc;
+  gph_mcmc_set_log_period(R.M, samplesPerLog);
+  return GPH_OK;
+}
+
+// after every iteration: the TAU columns' counts
+void Log::account()
+{
+  gph_mcmc_tau_accept_counts(R.M, tv.data());
+  for (int p = 0; p < R.cfg.K; p++) {
+    const int64_t now = tv[p] - tauPrevTotal[p];
+    tauShown[p] += p >= R.cfg.Kc ? 2 * now : tauLastIter[p] + now;
+    tauLastIter[p] = now;
+    tauPrevTotal[p] = tv[p];
+  }
+}
+
+// the end of a log period: acceptance percentages of the period exactly as upstream computes them (GPhoCS.c:1821-1853):
+// logCount starts at 1, and the tau counts of a period are added twice (after UpdateTau and again after UpdateSampleAge,
+// GPhoCS.c:1620-1623, 1646-1649)
+int Log::period(int it)
+{
+  const gph_config &cfg = R.cfg;
+  int64_t a[9], aLocus = 0;
+  double logL = 0, dataL = 0;
+  gph_mcmc_accept_counts(R.M, a);
+  gph_mcmc_tau_accept_counts(R.M, tv.data());
+  gph_mcmc_get_state(R.M, &logL, &dataL, nullptr, nullptr, nullptr);
+  const double lc = (double)logCount;
+  gph_mcmc_locus_rate_state(R.M, &aLocus, nullptr);
+  const double pCoal = (a[0] - a0[0]) * 100.0 / (lc * (double)totalCoals);
+  const double pMig = (a[1] - a0[1]) * 100.0 / ((double)(a[7] - a0[7]) + 0.000001);
+  const double pSpr = (a[2] - a0[2]) * 100.0 / (lc * 2 * (double)totalCoals);
+  const double pTheta = (a[3] - a0[3]) * 100.0 / (lc * cfg.K);
+  const double pRate = (a[4] - a0[4]) * 100.0 / (lc * cfg.B + 0.000001);
+  const double pMix = (a[6] - a0[6]) * 100.0 / lc;
+  const double pLocus = (aLocus - aLocus0) * 100.0 / (lc * (double)(R.info.numLoci - 1));   /* GPhoCS.c:1842-1845 */
+  if (R.lead) {   /* the log line, GPhoCS.c:1857-1895 */
+    char tbuf[64];
+    printf("\r%7d   %5.1f%%    %5.1f%%    %5.1f%%    %5.1f%%    %5.1f%%    ", it + 1, pCoal, pMig, pSpr, pTheta, pRate);
+    for (int p = 0; p < cfg.K; p++)
+      if (p >= cfg.Kc || R.mc.updateSampleAge[p]) printf("%5.1f%%    ", tauShown[p] * 100.0 / lc);
+    printf("%6.1f%%    %5.1f%%    %5.1f%%    ", (a[8] - a0[8]) * 100.0 / (lc * (cfg.K - cfg.Kc)), pLocus, pMix);
+    printf("|%12.6f|", logL);
+    printf(" %s", printtime(tbuf, sizeof tbuf));
+    if ((it + 1) % (samplesPerLog * logsPerLine) == 0) printf("\n");
+    fflush(stdout);
+  }
+  if (findingFinetunes) {   /* one step of the search (GPhoCS.c:1896-2251) */
+    fCoal.adjust(pCoal); fMig.adjust(pMig); fTheta.adjust(pTheta); fRate.adjust(pRate); fMix.adjust(pMix);
+    fLocus.adjust(pLocus);
+    fAdmix.adjust(0.0);
+    for (int p = cfg.Kc; p < cfg.K; p++) fTau[p].adjust(2 * (tv[p] - t0v[p]) * 100.0 / lc);
+    if (int rc = push_finetunes()) return rc;
+    if (R.lead) printf("          %-9.7lf %-9.7lf           %-9.7lf %-9.7lf %-9.7lf ", fCoal.v, fMig.v, fTheta.v, fRate.v, fAdmix.v);
+    for (int p = cfg.Kc; p < cfg.K; p++) if (R.lead) printf("%-9.7lf ", fTau[p].v);
+    if (R.lead) printf("          %-9.7lf %-9.7lf \n", fLocus.v, fMix.v);
+  }
+  logCount = 1;
+  memcpy(a0, a, sizeof a0);
+  aLocus0 = aLocus;
+  t0v = tv;
+  std::fill(tauShown.begin(), tauShown.end(), 0);
+  if (findingFinetunes && it + 1 >= R.info.findFinetunesSamplesPerStep * R.info.findFinetunesNumSteps) {
+    findingFinetunes = 0;
+    samplesPerLog = R.mc.samplesPerLog;
+    gph_mcmc_set_log_period(R.M, samplesPerLog);
+    logsPerLine = R.info.logsPerLine;
+    if (R.lead) {   /* GPhoCS.c:2232-2251 */
+      printf("\n");
+      printf("-------------------------------------  finetunes  ------------------------------------\n");
+      printf("          %8lf  %8lf            %8lf  %8lf  ", fCoal.v, fMig.v, fTheta.v, fRate.v);
+      for (int p = 0; p < cfg.K; p++) printf("%8lf  ", fTau[p].v);
+      printf("          %8lf  %8lf  \n", fLocus.v, fMix.v);
+      printf("--------------------------------------------------------------------------------------\n");
+    }
+  }
+  return GPH_OK;
+}
+
+// one rank's run up to its parts: what becomes of those is gph_run_finish's
+int run_chain(const gph_run_options &o)
+{
+  Run R(o);
+  Outputs outs(o);   /* (behind R: the parts are closed before anything is freed) */
+  int rc;
+  if ((rc = R.read_control())) return rc;
+  if (outs.trees && (rc = outs.trees->check_names(R))) return rc;
+  if ((rc = R.read_loci())) return rc;
+  if (outs.trees && (rc = outs.trees->select(R))) return rc;
+  if ((rc = R.start_engine()) || (rc = R.open_trace())) return rc;
+
+  const gph_control_info &info = R.info;
+  if (R.lead) printf("Starting MCMC: %d burnin, %d running, sampled every %d iteration(s).\n", info.burnin, info.numSamples, info.sampleSkip);
+  if (R.lead && info.mutRateMode == 2) printf("Reading locus rates from file %s... ", info.rateFile);   /* readRateFile's progress text (GPhoCS.c:514), printed from initializeMCMC upstream */
+  int64_t totalCoals = 0;
+  if ((rc = gph_mcmc_initialize(R.M, &totalCoals))) return R.fail(rc, "gph_mcmc_initialize");
+  for (auto x = outs.list.rbegin(); x != outs.list.rend(); ++x)
+    if ((rc = (*x)->open(R))) return rc;
+  auto t1 = std::chrono::steady_clock::now();
+  Log log(R, totalCoals);
+  if ((rc = log.start())) return rc;
   for (int it = -info.burnin; it < info.numSamples; it++) {
-    if ((rc = gph_mcmc_iteration(M, it))) return fail(rc, "gph_mcmc_iteration");
-    gph_mcmc_tau_accept_counts(M, tv.data());
-    for (int p = 0; p < cfg.K; p++) {
-      const int64_t now = tv[p] - tauPrevTotal[p];
-      tauShown[p] += p >= cfg.Kc ? 2 * now : tauLastIter[p] + now;
-      tauLastIter[p] = now;
-      tauPrevTotal[p] = tv[p];
+    if ((rc = gph_mcmc_iteration(R.M, it))) return R.fail(rc, "gph_mcmc_iteration");
+    log.account();
+    if (it >= 0 && it % (info.sampleSkip + 1) == 0) {
+      R.trace_line(it);
+      for (auto &x : outs.list)
+        if ((rc = x->sample(R, it))) return rc;
     }
-    if (it >= 0 && it % (info.sampleSkip + 1) == 0) {   /* GPhoCS.c:1763-1769 */
-      gph_mcmc_param_vals(M, vals.data(), mc.numParameters);
-      gph_mcmc_get_state(M, &logL, &dataL, nullptr, nullptr, nullptr);
-      fprintf(trace, "%d\t", it);
-      for (int i = 0; i < mc.numParameters; i++) fprintf(trace, "%8.5f\t", vals[i] * mc.printFactors[i]);
-      fprintf(trace, "\t%.6f\t%.6f\n", logL, dataL);
-      fflush(trace);
-      if (summary_path && (rc = gph_engine_locus_summary_sample(E))) return fail(rc, "gph_engine_locus_summary_sample");
-      if (gt_prefix) {
-        if ((rc = gph_engine_gene_trees_sample(E, it))) return fail(rc, "gph_engine_gene_trees_sample");
-        if (++gt_held == gt_capacity && (rc = gt_flush())) return fail(rc, "writing the gene-trees part file");
-      }
-      if (an_prefix) {
-        if ((rc = gph_engine_ancestry_sample(E, it))) return fail(rc, "gph_engine_ancestry_sample");
-        if (++an_held == an_capacity && (rc = an_flush())) return fail(rc, "writing the ancestry part file");
-      }
-      if (cs_prefix) {
-        if ((rc = gph_engine_coal_stats_sample(E, it))) return fail(rc, "gph_engine_coal_stats_sample");
-        if (ts_slices && (rc = gph_engine_time_slices_sample(E, it))) return fail(rc, "gph_engine_time_slices_sample");
-        /* logPrior of the parameters this trace line shows: what getLogPrior sums (GPhoCS.c:858-898) -- theta of every population,
-         * tau of every ancestral one, the rate of every band, each under its gamma prior of the control file */
-        gph_mcmc_get_state(M, nullptr, nullptr, cs_theta.data(), cs_age.data(), cs_mig.data());
-        /* log density of a gamma(shape, rate) prior at x: shape ln(rate) - ln Gamma(shape) + (shape - 1) ln x - rate x */
-        auto gamma_lpdf = [](double shape, double rate, double x) {
-          return shape * std::log(rate) - std::lgamma(shape) + (shape - 1.0) * std::log(x) - rate * x;
-        };
-        double lp = 0.0;
-        for (int p = 0; p < cfg.K; p++) lp += gamma_lpdf(mc.thetaAlpha[p], mc.thetaBeta[p], cs_theta[p]);
-        for (int p = cfg.Kc; p < cfg.K; p++) lp += gamma_lpdf(mc.ageAlpha[p], mc.ageBeta[p], cs_age[p]);
-        for (int b = 0; b < cfg.B; b++) lp += gamma_lpdf(mc.mrAlpha[b], mc.mrBeta[b], cs_mig[b]);
-        cs_prior.push_back(lp);
-        if ((int32_t)cs_prior.size() == cs_capacity) {
-          /* (both buffers have cs_capacity rows and fill together) */
-          if ((rc = cs_flush())) return fail(rc, "writing the coal-stats part file");
-          if (ts_slices && (rc = ts_flush())) return fail(rc, "writing the time-slices part file");
-        }
-      }
-    }
-    logCount++;
-    if ((it + 1) % samplesPerLog == 0) {
-      gph_mcmc_accept_counts(M, a);
-      gph_mcmc_tau_accept_counts(M, tv.data());
-      gph_mcmc_get_state(M, &logL, &dataL, nullptr, nullptr, nullptr);
-      // acceptance percentages of the period exactly as upstream computes them (GPhoCS.c:1821-1853): logCount
-      // starts at 1, and the tau counts of a period are added twice (after UpdateTau and again after
-      // UpdateSampleAge, GPhoCS.c:1620-1623, 1646-1649)
-      const double lc = (double)logCount;
-      const double pCoal = (a[0] - a0[0]) * 100.0 / (lc * (double)totalCoals);
-      const double pMig = (a[1] - a0[1]) * 100.0 / ((double)(a[7] - a0[7]) + 0.000001);
-      const double pSpr = (a[2] - a0[2]) * 100.0 / (lc * 2 * (double)totalCoals);
-      const double pTheta = (a[3] - a0[3]) * 100.0 / (lc * cfg.K);
-      const double pRate = (a[4] - a0[4]) * 100.0 / (lc * cfg.B + 0.000001);
-      const double pMix = (a[6] - a0[6]) * 100.0 / lc;
-      gph_mcmc_locus_rate_state(M, &aLocus, nullptr);
-      const double pLocus = (aLocus - aLocus0) * 100.0 / (lc * (double)(info.numLoci - 1));   /* GPhoCS.c:1842-1845 */
-      if (lead) {   /* the log line, GPhoCS.c:1857-1895 */
-        printf("\r%7d   %5.1f%%    %5.1f%%    %5.1f%%    %5.1f%%    %5.1f%%    ", it + 1, pCoal, pMig, pSpr, pTheta, pRate);
-        for (int p = 0; p < cfg.K; p++)
-          if (p >= cfg.Kc || mc.updateSampleAge[p]) printf("%5.1f%%    ", tauShown[p] * 100.0 / lc);
-        printf("%6.1f%%    %5.1f%%    %5.1f%%    ", (a[8] - a0[8]) * 100.0 / (lc * (cfg.K - cfg.Kc)), pLocus, pMix);
-        printf("|%12.6f|", logL);
-        printf(" %s", printtime(tbuf, sizeof tbuf));
-        if ((it + 1) % (samplesPerLog * logsPerLine) == 0) printf("\n");
-        fflush(stdout);
-      }
-      if (findingFinetunes) {
-        fCoal.adjust(pCoal); fMig.adjust(pMig); fTheta.adjust(pTheta); fRate.adjust(pRate); fMix.adjust(pMix);
-        fLocus.adjust(pLocus);
-        fAdmix.adjust(0.0);
-        for (int p = cfg.Kc; p < cfg.K; p++) fTau[p].adjust(2 * (tv[p] - t0v[p]) * 100.0 / lc);
-        if ((rc = push_finetunes())) return fail(rc, "gph_mcmc_set_finetunes");
-        if (lead) printf("          %-9.7lf %-9.7lf           %-9.7lf %-9.7lf %-9.7lf ", fCoal.v, fMig.v, fTheta.v, fRate.v, fAdmix.v);
-        for (int p = cfg.Kc; p < cfg.K; p++) if (lead) printf("%-9.7lf ", fTau[p].v);
-        if (lead) printf("          %-9.7lf %-9.7lf \n", fLocus.v, fMix.v);
-      }
-      logCount = 1;
-      memcpy(a0, a, sizeof a0);
-      aLocus0 = aLocus;
-      t0v = tv;
-      std::fill(tauShown.begin(), tauShown.end(), 0);
-      if (findingFinetunes && it + 1 >= info.findFinetunesSamplesPerStep * info.findFinetunesNumSteps) {
-        findingFinetunes = 0;
-        samplesPerLog = mc.samplesPerLog;
-        gph_mcmc_set_log_period(M, samplesPerLog);
-        logsPerLine = info.logsPerLine;
-        if (lead) {   /* GPhoCS.c:2232-2251 */
-          printf("\n");
-          printf("-------------------------------------  finetunes  ------------------------------------\n");
-          printf("          %8lf  %8lf            %8lf  %8lf  ", fCoal.v, fMig.v, fTheta.v, fRate.v);
-          for (int p = 0; p < cfg.K; p++) printf("%8lf  ", fTau[p].v);
-          printf("          %8lf  %8lf  \n", fLocus.v, fMix.v);
-          printf("--------------------------------------------------------------------------------------\n");
-        }
-      }
-    }
+    log.logCount++;
+    if ((it + 1) % log.samplesPerLog == 0 && (rc = log.period(it))) return rc;
   }
   double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-  if (lead) {
-    printf("\nMCMC finished. Time used: %s\n", printtime(tbuf, sizeof tbuf));   /* GPhoCS.c:2262 */
-    if (verbose) printf("(%.2f s, %.3f iterations/s)\n", sec, (info.burnin + info.numSamples) / (sec > 0 ? sec : 1));
+  if (R.lead) {
+    char tbuf[64];
+    printf("\nMCMC finished. Time used: %s\n", log.printtime(tbuf, sizeof tbuf));   /* GPhoCS.c:2262 */
+    if (o.verbose) printf("(%.2f s, %.3f iterations/s)\n", sec, (info.burnin + info.numSamples) / (sec > 0 ? sec : 1));
   }
-  fclose(trace);
-  trace = nullptr;
-  if (cs_prefix) {
-    if ((rc = cs_flush())) return fail(rc, "writing the coal-stats part file");
-    if (fwrite(&cs_written, sizeof cs_written, 1, cs_part) != 1) return fail(GPH_EARG, "writing the coal-stats part file");   /* the trailer: records in this part */
-    const int rcc = fclose(cs_part);
-    cs_part = nullptr;
-    if (rcc != 0) return fail(GPH_EARG, "closing the coal-stats part file");
-  }
-  if (ts_slices) {
-    if ((rc = ts_flush())) return fail(rc, "writing the time-slices part file");
-    if (fwrite(&ts_written, sizeof ts_written, 1, ts_part) != 1) return fail(GPH_EARG, "writing the time-slices part file");
-    const int rcc = fclose(ts_part);
-    ts_part = nullptr;
-    if (rcc != 0) return fail(GPH_EARG, "closing the time-slices part file");
-  }
-  if (an_prefix) {
-    if ((rc = an_flush())) return fail(rc, "writing the ancestry part file");
-    /* this rank's rows of the per-locus table, behind its records */
-    int64_t S = 0;
-    gph_engine_ancestry_shape(E, nullptr, nullptr, &S, nullptr);
-    std::vector<double> raw((size_t)an_ncol * (le - lb));
-    if ((rc = gph_engine_ancestry_fetch_loci(E, raw.data(), an_ncol, 0))) return fail(rc, "gph_engine_ancestry_fetch_loci");
-    const long text0 = ftell(an_part);
-    const int n = cfg.n, B = cfg.B;
-    const double Sd = (double)S;
-    for (int64_t g = 0; g < le - lb; g++) {
-      const double *a = raw.data() + (size_t)g * an_ncol;
-      const char *nm = gph_loci_name(LC, lb + g);
-      for (int i = 0; i < n; i++) {
-        const double any = a[2 * B * n + i];
-        if (!(any > 0.0)) continue;
-        fprintf(an_part, "%lld\t%s\t%d\t%s\t%lld\t%.10g", (long long)(lb + g), nm ? nm : "", i, an_names[i].c_str(), (long long)S, any / Sd);
-        for (int b = 0; b < B; b++) {
-          const double c = a[b * n + i], t = a[B * n + b * n + i];
-          fprintf(an_part, "\t%.10g\t%.10g", c / Sd, c > 0.0 ? t / c : 0.0);
-        }
-        fprintf(an_part, "\n");
-      }
-    }
-    const long text1 = ftell(an_part);
-    const int64_t tail[2] = {an_written, (int64_t)(text1 - text0)};
-    if (text0 < 0 || text1 < text0 || fwrite(tail, 8, 2, an_part) != 2) return fail(GPH_EARG, "writing the ancestry part file");
-    const int rcc = ferror(an_part) | fclose(an_part);
-    an_part = nullptr;
-    if (rcc != 0) return fail(GPH_EARG, "closing the ancestry part file");
-  }
-  if (gt_prefix) {
-    if ((rc = gt_flush())) return fail(rc, "writing the gene-trees part file");
-    if (fwrite(&gt_written, sizeof gt_written, 1, gt_part) != 1) return fail(GPH_EARG, "writing the gene-trees part file");   /* the trailer: samples in this part */
-    const int rcc = ferror(gt_part) | fclose(gt_part);
-    gt_part = nullptr;
-    if (rcc != 0) return fail(GPH_EARG, "closing the gene-trees part file");
-  }
-  int32_t ls_ncol = 0;
-  int64_t ls_samples = 0;
-  std::vector<double> ls_raw;
-  if (summary_path) {
-    gph_engine_locus_summary_columns(E, &ls_ncol, &ls_samples);
-    ls_raw.resize((size_t)ls_ncol * (le - lb));
-    if ((rc = gph_engine_locus_summary_fetch(E, ls_raw.data(), ls_ncol, 0))) return fail(rc, "gph_engine_locus_summary_fetch");
-  }
+  fclose(R.trace);
+  R.trace = nullptr;
+  for (auto x = outs.list.rbegin(); x != outs.list.rend(); ++x)
+    if ((rc = (*x)->close(R))) return rc;
   /* a CHECKED build of the library (-DGPH_BOUNDS, tests only) says here whether an index left its array during the run */
-  int32_t oob_where = 0, oob_checked = 0;
-  (void)gph_engine_debug_oob(E, &oob_where, &oob_checked);
-  gph_mcmc_destroy(M);
-  gph_engine_destroy(E);
-  if (oob_checked && oob_where != 0) {
+  int32_t where = 0, checked = 0;
+  (void)gph_engine_debug_oob(R.E, &where, &checked);
+  R.release_device();
+  if (checked && where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)oob_where);
-    gph_loci_free(LC);
-    gph_control_free(C);
-    discard_all();
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
     return GPH_EKERNEL;
   }
-  rc = GPH_OK;
-  if (summary_path) {
-    /* one rank: the file itself; several: this rank's part, concatenated in rank order by the caller (rank 0's has the header) */
-    const std::string path = world > 1 ? std::string(summary_path) + ".part" + std::to_string(rank) : std::string(summary_path);
-    rc = write_locus_summary(path, lead, C, cfg, LC, lb, le - lb, ls_ncol, ls_samples, ls_raw, info.mutRateMode == 1);
-  }
-  gph_loci_free(LC);
-  gph_control_free(C);
+  return outs.summary ? outs.summary->write_table(R) : GPH_OK;
+}
+}   // namespace
+
+extern "C" int gph_run_finish(const gph_run_options *in, int32_t ranks, int32_t failed)
+{
+  gph_run_options o;
+  if (!take_options(in, o) || ranks < 1) return GPH_EARG;
+  Outputs outs(o);
+  int rc = GPH_OK;
+  for (auto &x : outs.list)
+    if (!failed && !rc) rc = x->write(ranks);
+  /* a failed run leaves no statistics file and no part behind */
+  if (failed || rc)
+    for (auto &x : outs.list) x->discard(ranks);
+  return rc;
+}
+
+extern "C" int gph_run(const gph_run_options *in)
+{
+  gph_run_options o;
+  if (!take_options(in, o)) return GPH_EARG;
+  if (o.comm) { o.rank = gph_comm_rank(o.comm); o.world = gph_comm_world(o.comm); o.allreduce = nullptr; o.user = nullptr; }
+  else if (o.world == 0) o.world = 1;
+  if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
+  /* the checks on the options alone, before anything is read */
+  int rc;
+  if ((rc = GeneTrees::validate(o)) || (rc = CoalStats::validate(o))) return rc;
+  rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
-  /* (the ancestry files first, then the slices file: should a later group fail, two files and one are removed again,
-   * not 1 + 3 K) */
-  if (world == 1) {
-    if (!rc && gt_prefix) rc = gph_gene_trees_write(gt_prefix, 1);
-    if (!rc && an_prefix) rc = gph_ancestry_write(an_prefix, 1);
-    if (!rc && ts_slices) rc = gph_time_slices_write(cs_prefix, 1);
-    if (!rc && cs_prefix) rc = gph_coal_stats_write(cs_prefix, 1);
-    if (rc) discard_all();
+  if (o.world == 1) {
+    const int rcf = gph_run_finish(&o, 1, rc);
+    if (!rc) rc = rcf;
   }
   return rc;
+}
+
+// the simple forms
+static gph_run_options plain_options(const char *ctl, const char *ctl2, int32_t device, int32_t verbose)
+{
+  gph_run_options o;
+  memset(&o, 0, sizeof o);
+  o.size = sizeof o;
+  o.ctl = ctl; o.ctl2 = ctl2; o.device = device; o.verbose = verbose;
+  return o;
+}
+
+extern "C" int gph_run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose)
+{
+  const gph_run_options o = plain_options(ctl, ctl2, device, verbose);
+  return gph_run(&o);
 }
 
 extern "C" int gph_run_control_file_ranked(const char *ctl, const char *ctl2, int32_t device, int32_t verbose,
                                            int32_t rank, int32_t world, gph_allreduce_fn allreduce, void *user)
 {
-  return run_control_file(ctl, ctl2, device, verbose, rank, world, allreduce, user, nullptr);
+  gph_run_options o = plain_options(ctl, ctl2, device, verbose);
+  o.rank = rank; o.world = world; o.allreduce = allreduce; o.user = user;
+  return world < 1 ? GPH_EARG : gph_run(&o);
 }
 
 extern "C" int gph_run_control_file_comm(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm)
 {
-  return gph_run_control_file_ex(ctl, ctl2, device, verbose, comm, nullptr);
-}
-
-extern "C" int gph_run_control_file_ex(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
-                                       const char *locus_summary_path)
-{
-  return gph_run_control_file_ex2(ctl, ctl2, device, verbose, comm, locus_summary_path, nullptr, 0);
-}
-
-extern "C" int gph_run_control_file_ex2(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
-                                        const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity)
-{
-  return gph_run_control_file_ex3(ctl, ctl2, device, verbose, comm, locus_summary_path, coal_stats_prefix, coal_stats_capacity, 0);
-}
-
-extern "C" int gph_run_control_file_ex3(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
-                                        const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity,
-                                        int32_t time_slices)
-{
-  return gph_run_control_file_ex4(ctl, ctl2, device, verbose, comm, locus_summary_path, coal_stats_prefix, coal_stats_capacity, time_slices, nullptr, 0);
-}
-
-extern "C" int gph_run_control_file_ex4(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
-                                        const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity,
-                                        int32_t time_slices, const char *ancestry_prefix, int32_t ancestry_capacity)
-{
-  return gph_run_control_file_ex5(ctl, ctl2, device, verbose, comm, locus_summary_path, coal_stats_prefix, coal_stats_capacity, time_slices,
-                                  ancestry_prefix, ancestry_capacity, nullptr, nullptr, 0);
-}
-
-extern "C" int gph_run_control_file_ex5(const char *ctl, const char *ctl2, int32_t device, int32_t verbose, gph_comm *comm,
-                                        const char *locus_summary_path, const char *coal_stats_prefix, int32_t coal_stats_capacity,
-                                        int32_t time_slices, const char *ancestry_prefix, int32_t ancestry_capacity,
-                                        const char *gene_trees_prefix, const char *gene_trees_loci_spec, int32_t gene_trees_capacity)
-{
-  if (comm) return run_control_file(ctl, ctl2, device, verbose, gph_comm_rank(comm), gph_comm_world(comm), nullptr, nullptr, comm, locus_summary_path,
-                                    coal_stats_prefix, coal_stats_capacity, time_slices, ancestry_prefix, ancestry_capacity,
-                                    gene_trees_prefix, gene_trees_loci_spec, gene_trees_capacity);
-  return run_control_file(ctl, ctl2, device, verbose, 0, 1, nullptr, nullptr, nullptr, locus_summary_path, coal_stats_prefix, coal_stats_capacity,
-                          time_slices, ancestry_prefix, ancestry_capacity, gene_trees_prefix, gene_trees_loci_spec, gene_trees_capacity);
-}
-
-extern "C" int gph_run_control_file(const char *ctl, const char *ctl2, int32_t device, int32_t verbose)
-{
-  return gph_run_control_file_ex(ctl, ctl2, device, verbose, nullptr, nullptr);
+  gph_run_options o = plain_options(ctl, ctl2, device, verbose);
+  o.comm = comm;
+  return gph_run(&o);
 }

@@ -555,86 +555,82 @@ int gph_mcmc_initialize_genealogies(gph_mcmc *m);
  * its N child processes */
 int gph_run_control_file_comm(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
                               int32_t verbose, gph_comm *comm);
-/* either of the two above (comm NULL = one rank), plus the per-locus summary table (`G-PhoCS-hip -l FILE`): a sample
- * after every trace line, the table written once after the last iteration and only on success.  One rank writes
- * locus_summary_path; under a communicator of several ranks rank r writes locus_summary_path.part<r> with its own loci
- * (rank 0's part holds the header) and the caller concatenates the parts in rank order.  NULL = no table. */
-int gph_run_control_file_ex(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
-                            int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null);
-/* the same, plus the coalescent / sample-pair statistics (`G-PhoCS-hip -s PREFIX`; printCoalStats, GPhoCS.c:911-1040): a
- * sample after every trace line into a device buffer of coal_stats_capacity rows (<= 0: 64, fewer when 64 rows of
- * 7 + 3 * n(n-1)/2 * K doubles would exceed 256 MB).  Whenever the buffer is
- * full, and at the end, rank r appends its raw rows (each followed by logPrior) to the binary file
- * coal_stats_prefix.coal.part<r>.  gph_coal_stats_write(prefix, ranks) then adds the parts in rank order and writes
- * PREFIX.coal.tsv and, per population, PREFIX.<pop>.probCoal.tsv / .probFirstCoal.tsv / .meanCoal.tsv, and removes the
- * parts; gph_coal_stats_discard(prefix, ranks) only removes them.  A one-rank run (comm NULL or of one rank) calls
- * _write itself when it succeeds and _discard when it fails; with several ranks the caller does, after every rank has
- * returned.  Either way a run that did not finish leaves none of the .tsv files.  NULL prefix = no statistics. */
-int gph_run_control_file_ex2(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
-                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null,
-                             const char *coal_stats_prefix_or_null, int32_t coal_stats_capacity);
+
+/* ------------------------------------------------------------------------------------
+ * gph_run: any of the three above plus the outputs of the program, each switched on by its own field.  `size` is
+ * sizeof(gph_run_options) AS THE CALLER COMPILED IT: a library that knows more fields reads the missing tail as 0 / NULL
+ * (the smallest size accepted ends behind `comm`); a larger size than the library's own, or a NULL struct, is GPH_EARG.
+ * A later output adds a field at the end, not a function.
+ * Every output takes its sample wherever a trace line is written (never in the burn-in), into a device buffer of <rows>
+ * rows; whenever that buffer is full, and at the end, rank r appends the rows to a binary part file PREFIX.<kind>.part<r>.
+ * gph_run_finish(o, ranks, failed), called once after the last rank has returned, makes the files of the parts and removes
+ * the parts (failed == 0: gph_gene_trees_write, gph_ancestry_write, gph_time_slices_write, gph_coal_stats_write, in this
+ * order; everything is discarded at the first failure) or only discards, parts and files.  A one-rank run calls it itself.
+ * Either way a run that did not finish leaves neither parts nor files, and a part that is missing, damaged or was not
+ * closed by its rank is an error.  The outputs compose freely. */
+typedef struct gph_run_options {
+  uint32_t size;                   /* sizeof(gph_run_options) of the caller */
+  const char *ctl, *ctl2;          /* control file; secondary control file or NULL */
+  int32_t device, verbose;
+  gph_comm *comm;                  /* NULL, or the communicator whose rank this process is (gph_run_control_file_comm) */
+  int32_t rank, world;             /* without comm: 0, 0 or 0, 1 = one rank, else gph_run_control_file_ranked with ... */
+  gph_allreduce_fn allreduce; void *user;   /* ... this exchange and its argument */
+  /* `-l FILE`: the per-locus summary table, written once after the last iteration and only on success.  One rank writes
+   * the file; of several, rank r writes FILE.part<r> with its own loci (rank 0's part holds the header) and the caller
+   * concatenates the parts in rank order (gph_run_finish leaves them alone). */
+  const char *locus_summary_path;
+  /* `-s PREFIX`: the coalescent / sample-pair statistics (printCoalStats, GPhoCS.c:911-1040).  rows <= 0: 64, fewer when 64
+   * rows of 7 + 3 * n(n-1)/2 * K doubles would exceed 256 MB.  Parts PREFIX.coal.part<r>, every raw row followed by logPrior.
+   * gph_coal_stats_write adds the parts in rank order and writes PREFIX.coal.tsv and, per population,
+   * PREFIX.<pop>.probCoal.tsv / .probFirstCoal.tsv / .meanCoal.tsv. */
+  const char *coal_stats_prefix;
+  int32_t coal_stats_rows;
+  /* `--time-slices S` (needs coal_stats_prefix: GPH_EARG without one): a sample of gph_engine_time_slices_* wherever a
+   * coal-stats sample is, into a device buffer of as many rows; parts PREFIX.slices.part<r>.  gph_time_slices_write adds them
+   * in rank order, sample by sample, and writes PREFIX.slices.tsv -- header iter, numCoal_<pop>:<k> deltaT_<pop>:<k> (k = 1 .. S,
+   * GPhoCS.c:933), numMig_<src>-><tgt>:<k> migT_<src>-><tgt>:<k>; rows "%7d" then "\t%9d\t%8f" per pair (GPhoCS.c:1005). */
+  int32_t time_slices;
+  /* `--ancestry PREFIX`: the migration ancestry (gph_engine_ancestry_*), rows <= 0: 64.  The part PREFIX.ancestry.part<r>
+   * holds the rank's per-sample rows as they are flushed and, once the last iteration is done, its rows of the per-locus
+   * table.  gph_ancestry_write writes, from the parts,
+   *   PREFIX.loci.tsv     header locus name leaf sample samples pAny, then per band p_<src>-><tgt> age_<src>-><tgt>; one row
+   *                       per (locus, leaf) with any.<i> > 0 (all-zero rows are omitted), in sequence-file order, then leaf
+   *                       order; sample = the leaf's name as the header of PREFIX.<pop>.probCoal.tsv names it; pAny = any / S,
+   *                       p = cnt / S, age = age_sum / cnt (0 where cnt = 0) in the genealogy's own units, all "%.10g"; the
+   *                       ranks' rows concatenated in rank order
+   *   PREFIX.samples.tsv  header iter, any_<sample>#<i> per leaf, <src>-><tgt>|<sample>#<i> per band and leaf; rows "%7d" then
+   *                       "\t%9d" per count; the ranks' rows added sample by sample */
+  const char *ancestry_prefix;
+  int32_t ancestry_rows;
+  /* `--gene-trees PREFIX [--gene-trees-loci SPEC] [--gene-trees-rows N]`: the sampled genealogies (gph_engine_gene_trees_*).
+   * gene_trees_loci: NULL or "all", or a comma list of i, i-j (both ends included) or i-j:step, 0-based indices in
+   * sequence-file order; an index named twice or >= the number of loci is refused, with a message that names it, before the
+   * first iteration (GPH_EARG), and so is a population or sample name that holds white space or one of ()[],:;'=& ; a
+   * selection or a row count without a prefix is GPH_EARG.  The row buffer holds min(gene_trees_rows or 64, 256 MB / bytes of a
+   * row) rows; a single row above 256 MB stops the run before the first iteration (GPH_EFULL, with a message).  Parts
+   * PREFIX.trees.part<r>.  gph_gene_trees_write writes, from the parts, PREFIX.trees.tsv:
+   *   header  iter locus name dataLnL genLnL tmrca numMigs tree
+   *   one line per (sample, selected locus), sample order then locus order (the ranks' records of one sample in rank order);
+   *   iter, locus (0-based), numMigs "%d"; name from the sequence file; dataLnL, genLnL, tmrca = age[root] in the genealogy's
+   *   own units "%.10g"; tree: gph_gene_tree_newick with leaf labels <sample>.<i>, <sample> as PREFIX.<pop>.probCoal.tsv
+   *   names leaf i */
+  const char *gene_trees_prefix, *gene_trees_loci;
+  int32_t gene_trees_rows;
+} gph_run_options;
+int gph_run(const gph_run_options *o);
+int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
+/* what gph_run_finish calls, one output at a time: _write makes the files of the parts of `ranks` ranks and removes the
+ * parts; _discard removes the parts and the output's files should they exist; _combined hands out the records _write would
+ * print: *rows samples of *row_doubles doubles (the ranks' raw rows added in rank order; coal stats: then logPrior) into
+ * out[max_rows >= *rows]; out NULL: the two counts only. */
 int gph_coal_stats_write(const char *prefix, int32_t ranks);
-/* the records gph_coal_stats_write would print, before it is called: *rows samples of *row_doubles doubles (the raw row
- * of the ranks' parts added in rank order, then logPrior) into out[max_rows >= *rows]; out NULL: the two counts only.
- * A part that is missing, damaged or was not closed by its rank (no record count at its end) is an error. */
 int gph_coal_stats_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles);
 int gph_coal_stats_discard(const char *prefix, int32_t ranks);
-/* the same, plus the time-sliced statistics (`G-PhoCS-hip -s PREFIX --time-slices S`): with time_slices >= 1 (which needs
- * a coal_stats_prefix: GPH_EARG without one) a sample of gph_engine_time_slices_* is taken wherever a coal-stats sample is,
- * into a device buffer of as many rows, and rank r appends its raw rows to the binary file PREFIX.slices.part<r>.
- * gph_time_slices_write(prefix, ranks) adds the parts in rank order, sample by sample, writes PREFIX.slices.tsv -- header
- * iter, numCoal_<pop>:<k> deltaT_<pop>:<k> (k = 1 .. S, GPhoCS.c:933), numMig_<src>-><tgt>:<k> migT_<src>-><tgt>:<k>; rows
- * "%7d" then "\t%9d\t%8f" per pair (GPhoCS.c:1005) -- and removes the parts; _discard only removes them; _combined hands
- * out the added rows (out NULL: the two counts only).  A one-rank run writes or discards itself, as for the coal-stats
- * files; with several ranks the caller does.  time_slices 0 = gph_run_control_file_ex2. */
-int gph_run_control_file_ex3(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
-                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null,
-                             const char *coal_stats_prefix_or_null, int32_t coal_stats_capacity, int32_t time_slices);
 int gph_time_slices_write(const char *prefix, int32_t ranks);
 int gph_time_slices_combined(const char *prefix, int32_t ranks, double *out, int64_t max_rows, int64_t *rows, int32_t *row_doubles);
 int gph_time_slices_discard(const char *prefix, int32_t ranks);
-/* the same, plus the migration ancestry (`G-PhoCS-hip --ancestry PREFIX`; needs none of the other options): with an
- * ancestry_prefix a sample of gph_engine_ancestry_* is taken wherever a trace line is written, into a device buffer of
- * ancestry_capacity rows (<= 0: 64), and rank r keeps the binary file PREFIX.ancestry.part<r>: its per-sample rows as they
- * are flushed and, once the last iteration is done, its rows of the per-locus table.
- * gph_ancestry_write(prefix, ranks) writes, from the parts,
- *   PREFIX.loci.tsv     header locus name leaf sample samples pAny, then per band p_<src>-><tgt> age_<src>-><tgt>; one row
- *                       per (locus, leaf) with any.<i> > 0 (all-zero rows are omitted), in sequence-file order, then leaf
- *                       order; sample = the leaf's name as the header of PREFIX.<pop>.probCoal.tsv names it; pAny = any / S,
- *                       p = cnt / S, age = age_sum / cnt (0 where cnt = 0) in the genealogy's own units, all "%.10g"; the
- *                       ranks' rows concatenated in rank order
- *   PREFIX.samples.tsv  header iter, any_<sample>#<i> per leaf, <src>-><tgt>|<sample>#<i> per band and leaf; rows "%7d" then
- *                       "\t%9d" per count; the ranks' rows added sample by sample
- * and removes the parts; _discard removes the parts and both files.  A one-rank run writes or discards itself; with several
- * ranks the caller does.  A failed run leaves neither parts nor files.  ancestry_prefix NULL = gph_run_control_file_ex3. */
-int gph_run_control_file_ex4(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
-                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null,
-                             const char *coal_stats_prefix_or_null, int32_t coal_stats_capacity, int32_t time_slices,
-                             const char *ancestry_prefix_or_null, int32_t ancestry_capacity);
 int gph_ancestry_write(const char *prefix, int32_t ranks);
 int gph_ancestry_discard(const char *prefix, int32_t ranks);
-/* the same, plus the sampled genealogies (`G-PhoCS-hip --gene-trees PREFIX [--gene-trees-loci SPEC] [--gene-trees-rows N]`;
- * needs none of the other options): with a gene_trees_prefix a sample of gph_engine_gene_trees_* is taken wherever a trace
- * line is written (never in the burn-in).  gene_trees_loci_spec: NULL or "all", or a comma list of i, i-j (both ends included)
- * or i-j:step, 0-based indices in sequence-file order; an index named twice or >= the number of loci is refused, with a
- * message that names it, before the first iteration (GPH_EARG), and so is a population or sample name that holds white
- * space or one of ()[],:;'=& .  The row buffer holds min(gene_trees_capacity or 64, 256 MB / bytes of a row) rows; a single
- * row above 256 MB stops the run before the first iteration (GPH_EFULL, with a message).  Whenever the buffer is full, and
- * at the end, rank r appends its rows to the binary file PREFIX.trees.part<r> (the only host synchronisation the option adds).
- * gph_gene_trees_write(prefix, ranks) writes, from the parts, PREFIX.trees.tsv:
- *   header  iter locus name dataLnL genLnL tmrca numMigs tree
- *   one line per (sample, selected locus), sample order then locus order (the ranks' records of one sample in rank order);
- *   iter, locus (0-based), numMigs "%d"; name from the sequence file; dataLnL, genLnL, tmrca = age[root] in the genealogy's
- *   own units "%.10g"; tree: gph_gene_tree_newick with leaf labels <sample>.<i>, <sample> as PREFIX.<pop>.probCoal.tsv
- *   names leaf i
- * and removes the parts; _discard removes the parts and the file.  A one-rank run writes or discards itself; with several
- * ranks the caller does.  A failed run leaves neither parts nor file; a part that is missing, damaged or was not closed by
- * its rank is an error.  gene_trees_prefix NULL = gph_run_control_file_ex4. */
-int gph_run_control_file_ex5(const char *ctl_path, const char *secondary_ctl_path_or_null, int32_t device,
-                             int32_t verbose, gph_comm *comm_or_null, const char *locus_summary_path_or_null,
-                             const char *coal_stats_prefix_or_null, int32_t coal_stats_capacity, int32_t time_slices,
-                             const char *ancestry_prefix_or_null, int32_t ancestry_capacity,
-                             const char *gene_trees_prefix_or_null, const char *gene_trees_loci_spec_or_null, int32_t gene_trees_capacity);
 int gph_gene_trees_write(const char *prefix, int32_t ranks);
 int gph_gene_trees_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,

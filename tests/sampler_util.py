@@ -91,3 +91,35 @@ def printed_names(sample_names):
 
 def read_outputs(d, prefix):
     return {f[len(prefix) + 1:]: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.startswith(prefix + ".")}
+
+
+RANK_WORKER = r'''
+import os, sys
+sys.path.insert(0, %(repo)r)
+import gphocs_amd as G
+rank, world = int(sys.argv[1]), int(sys.argv[2])
+lib = G.load_library(%(lib)r) if %(lib)r else G.load_library(dims=%(dims)r)
+comm = lib.gph_comm_create_shm(%(name)r.encode(), rank, world)
+assert comm
+os.chdir(%(cwd)r)
+rc = G.run_control_file(lib, %(ctl)r, comm=comm, **%(options)r)
+sys.stdout.flush()
+if rc == 0:
+    lib.gph_comm_destroy(comm)
+os._exit(1 if rc else 0)
+'''
+
+
+def run_ranks(lib_path, name, ranks, d, **options):
+    """`ranks` processes over a shared-memory communicator, each the program's own loop on golden `name` in directory d with
+    the outputs that `options` (those of gphocs_amd.run_control_file) switch on: their parts stay.  The pack of the golden."""
+    import gphocs_amd as G
+    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
+    _copy_case(name, d)
+    script = d / "w.py"
+    script.write_text(RANK_WORKER % dict(repo=REPO, lib=lib_path, dims=(pk.n, pk.K, pk.B), name=f"/gphocs-{os.getpid()}-{d.name}-{name}-{ranks}",
+                                         cwd=str(d), ctl=name + ".ctl", options=options))
+    procs = [subprocess.Popen([sys.executable, str(script), str(r), str(ranks)], stdout=subprocess.DEVNULL) for r in range(ranks)]
+    for p in procs:
+        assert p.wait(timeout=600) == 0
+    return pk

@@ -21,7 +21,7 @@ import pytest
 from conftest import GOLDEN, REPO
 from parity_util import compare_records, compare_trace_files
 from sampler_util import (EXE, _copy_case, _data_lines, _fmt, _locus_names, _pop_names, _run, hostemu_library, printed_names,  # noqa: F401
-                          read_outputs)
+                          read_outputs, run_ranks)
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
 
@@ -428,23 +428,6 @@ def test_failed_run_leaves_no_ancestry_file(hostemu, tmp_path):
     check_failed_runs_leave_nothing(hostemu[0], tmp_path)
 
 
-RANK_WORKER = r'''
-import os, sys
-sys.path.insert(0, %(repo)r)
-import gphocs_amd as G
-rank, world = int(sys.argv[1]), int(sys.argv[2])
-lib = G.load_library(%(lib)r) if %(lib)r else G.load_library(dims=%(dims)r)
-comm = lib.gph_comm_create_shm(%(name)r.encode(), rank, world)
-assert comm
-os.chdir(%(cwd)r)
-rc = lib.gph_run_control_file_ex4(%(ctl)r.encode(), None, 0, 0, comm, None, None, 0, 0, b"out", %(rows)d)
-sys.stdout.flush()
-if rc == 0:
-    lib.gph_comm_destroy(comm)
-os._exit(1 if rc else 0)
-'''
-
-
 def read_part(path):
     """(n, B, records [samples][1 + n (B + 1)] int32, per-locus text) of a rank's PREFIX.ancestry.part<r>"""
     b = open(path, "rb").read()
@@ -458,20 +441,6 @@ def read_part(path):
     return n, B, rec, b[body + count * (ri + 1) * 4:len(b) - 16].decode()
 
 
-def run_ranks(lib_path, name, ranks, d, rows=7):
-    """`ranks` processes over a shared-memory communicator, each the program's own loop with --ancestry out: their parts stay"""
-    import gphocs_amd as G
-    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
-    _copy_case(name, d)
-    script = d / "w.py"
-    script.write_text(RANK_WORKER % dict(repo=REPO, lib=lib_path, dims=(pk.n, pk.K, pk.B), name=f"/gphocs-an-{os.getpid()}-{name}-{ranks}",
-                                         cwd=str(d), ctl=name + ".ctl", rows=rows))
-    procs = [subprocess.Popen([sys.executable, str(script), str(r), str(ranks)], stdout=subprocess.DEVNULL) for r in range(ranks)]
-    for p in procs:
-        assert p.wait(timeout=600) == 0
-    return pk
-
-
 def check_ranks(lib_path, lib, name, tmp_path, rank_counts=(1, 2, 3)):
     """item 4: the ranks' parts -- per-locus rows concatenated in rank order, per-sample rows added -- are the one-rank
     files, whether this test combines them itself or gph_ancestry_write does; a part cut short is refused and nothing is left"""
@@ -481,7 +450,7 @@ def check_ranks(lib_path, lib, name, tmp_path, rank_counts=(1, 2, 3)):
     head = want["loci.tsv"].splitlines(True)[0]
     for ranks in rank_counts:
         d = tmp_path / f"w{ranks}"
-        run_ranks(lib_path, name, ranks, d)
+        run_ranks(lib_path, name, ranks, d, ancestry="out", ancestry_rows=7)
         if ranks == 1:                 # one rank writes its files itself (a communicator of one included)
             assert read_outputs(d, "out") == want
             continue
@@ -494,7 +463,7 @@ def check_ranks(lib_path, lib, name, tmp_path, rank_counts=(1, 2, 3)):
         assert lib.gph_ancestry_write(str(d / "out").encode(), ranks) == 0
         assert read_outputs(d, "out") == want                          # no part among them: written once
     d = tmp_path / "cut"
-    run_ranks(lib_path, name, 2, d)
+    run_ranks(lib_path, name, 2, d, ancestry="out", ancestry_rows=7)
     b = open(d / "out.ancestry.part1", "rb").read()
     open(d / "out.ancestry.part1", "wb").write(b[:-8])
     assert lib.gph_ancestry_write(str(d / "out").encode(), 2) != 0

@@ -32,7 +32,7 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import REL_TOL, compare_records, compare_trace_files
-from sampler_util import (EXE, U, _copy_case, _data_lines, _pop_names, _run, hostemu_library, printed_names, read_outputs,  # noqa: F401
+from sampler_util import (EXE, U, _copy_case, _data_lines, _pop_names, _run, hostemu_library, printed_names, read_outputs, run_ranks,  # noqa: F401
                           within_bound)
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
@@ -397,23 +397,6 @@ def test_burn_in_sample_skip_and_composition_with_the_locus_table(hostemu, tmp_p
     assert read_outputs(a, "out") == want
 
 
-RANK_WORKER = r'''
-import os, sys
-sys.path.insert(0, %(repo)r)
-import gphocs_amd as G
-rank, world = int(sys.argv[1]), int(sys.argv[2])
-lib = G.load_library(%(lib)r) if %(lib)r else G.load_library(dims=%(dims)r)
-comm = lib.gph_comm_create_shm(%(name)r.encode(), rank, world)
-assert comm
-os.chdir(%(cwd)r)
-rc = lib.gph_run_control_file_ex2(%(ctl)r.encode(), None, 0, 0, comm, None, b"out", %(rows)d)
-sys.stdout.flush()
-if rc == 0:
-    lib.gph_comm_destroy(comm)
-os._exit(1 if rc else 0)
-'''
-
-
 def read_part(path):
     """(n, K, row_doubles, L, records [samples][row_doubles + 1], trailer count) of a rank's PREFIX.coal.part<r>"""
     import struct
@@ -425,20 +408,6 @@ def read_part(path):
     body = b[32 + nbytes:-8]
     count, = struct.unpack_from("<q", b, len(b) - 8)
     return n, K, rd, L, np.frombuffer(body, dtype=np.float64).reshape(-1, rd + 1), count
-
-
-def run_ranks(lib_path, name, ranks, d, rows=5):
-    """`ranks` processes over a shared-memory communicator, each the program's own loop with -s out: their parts stay"""
-    import gphocs_amd as G
-    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
-    _copy_case(name, d)
-    script = d / "w.py"
-    script.write_text(RANK_WORKER % dict(repo=REPO, lib=lib_path, dims=(pk.n, pk.K, pk.B), name=f"/gphocs-cs-{os.getpid()}-{name}-{ranks}",
-                                         cwd=str(d), ctl=name + ".ctl", rows=rows))
-    procs = [subprocess.Popen([sys.executable, str(script), str(r), str(ranks)], stdout=subprocess.DEVNULL) for r in range(ranks)]
-    for p in procs:
-        assert p.wait(timeout=600) == 0
-    return pk
 
 
 def check_ranks(lib_path, lib, name, tmp_path, rank_counts=(2, 3)):
@@ -457,7 +426,7 @@ def check_ranks(lib_path, lib, name, tmp_path, rank_counts=(2, 3)):
     pops, names = _pop_names(one_dir / (name + ".ctl")), printed_names(p.sampleNames)
     for ranks in rank_counts:
         d = tmp_path / f"w{ranks}"
-        run_ranks(lib_path, name, ranks, d)
+        run_ranks(lib_path, name, ranks, d, coal_stats="out", coal_stats_rows=5)
         parts = [read_part(d / f"out.coal.part{r}") for r in range(ranks)]
         assert all(q[:4] == (n, K, 7 + 3 * npk, L) and q[5] == len(its) for q in parts)
         mine = parts[0][4].copy()
@@ -486,7 +455,7 @@ def check_ranks(lib_path, lib, name, tmp_path, rank_counts=(2, 3)):
         assert read_outputs(e, "out") == got
     # a part cut short (its record count gone) is refused, and nothing is left
     d = tmp_path / "cut"
-    run_ranks(lib_path, name, 2, d)
+    run_ranks(lib_path, name, 2, d, coal_stats="out", coal_stats_rows=5)
     b = open(d / "out.coal.part1", "rb").read()
     open(d / "out.coal.part1", "wb").write(b[:-8])
     assert lib.gph_coal_stats_write(str(d / "out").encode(), 2) != 0

@@ -376,3 +376,73 @@ def test_rate_file_errors_carry_the_reference_text(lib, kind, tmp_path):
     assert r.returncode == 1
     got = [ln for ln in r.stderr.splitlines() if ln.startswith("Error: ")]
     assert got == want, (got, want)
+
+
+# ---------------------------------------------------------------- gph_run: the options struct and its size rule
+def _options_up_to(field, **values):
+    """gph_run_options whose `size` ends behind `field`, in memory that holds 0xFF everywhere the values do not reach: a
+    library that read behind `size` would find negative counts and wild pointers there"""
+    import ctypes as C
+    buf = (C.c_ubyte * C.sizeof(G.GphRunOptions))(*([0xFF] * C.sizeof(G.GphRunOptions)))
+    o = G.GphRunOptions.from_buffer(buf)
+    last = getattr(G.GphRunOptions, field)
+    o.size = last.offset + last.size
+    for name, _ in G.GphRunOptions._fields_[1:]:
+        if getattr(G.GphRunOptions, name).offset < o.size:
+            setattr(o, name, values.get(name, G.ALLREDUCE_FN() if name == "allreduce" else None if name in ("ctl2", "comm", "user",
+                    "locus_summary_path") else 0))
+    return o
+
+
+def test_run_refuses_no_options(lib):
+    assert lib.gph_run(None) == -1 and lib.gph_run_finish(None, 1, 0) == -1
+
+
+def test_run_refuses_options_larger_than_its_own_and_shorter_than_the_fixed_part(lib):
+    import ctypes as C
+
+    class OneFieldMore(C.Structure):
+        _fields_ = [("o", G.GphRunOptions), ("later_output_prefix", C.c_char_p)]
+    big = OneFieldMore()
+    big.o.size, big.o.ctl = C.sizeof(OneFieldMore), b"g1.ctl"
+    assert C.sizeof(OneFieldMore) == C.sizeof(G.GphRunOptions) + C.sizeof(C.c_char_p)
+    assert lib.gph_run(C.cast(C.pointer(big), C.POINTER(G.GphRunOptions))) == -1
+    small = _options_up_to("verbose", ctl=b"g1.ctl")          # one field short of the fixed part
+    assert lib.gph_run(small) == -1
+
+
+def test_run_reads_options_cut_behind_the_fixed_part_as_the_plain_program(lib, tmp_path):
+    from sampler_util import _copy_case
+    traces = []
+    for d, cut in ((tmp_path / "plain", False), (tmp_path / "cut", True)):
+        _copy_case("g1", d)
+        with _in_dir(d):
+            assert (lib.gph_run(_options_up_to("comm", ctl=b"g1.ctl")) if cut else lib.gph_run_control_file(b"g1.ctl", None, 0, 0)) == 0
+        assert sorted(os.listdir(d)) == ["g1.ctl", "g1.seq", "g1.trace"]
+        traces.append(open(d / "g1.trace", "rb").read())
+    assert traces[0] == traces[1] and len(traces[0].splitlines()) == 31
+
+
+def test_run_does_not_read_behind_the_size_it_is_given(lib, tmp_path):
+    """cut behind coal_stats_prefix: the row count, the slices, the other prefixes lie in the 0xFF behind it"""
+    from sampler_util import _copy_case, _pop_names, read_outputs
+    _copy_case("g1", tmp_path)
+    with _in_dir(tmp_path):
+        assert lib.gph_run(_options_up_to("coal_stats_prefix", ctl=b"g1.ctl", coal_stats_prefix=b"out")) == 0
+    want = ["coal.tsv"] + [f"{p}.{st}.tsv" for p in _pop_names(tmp_path / "g1.ctl") for st in ("probCoal", "probFirstCoal", "meanCoal")]
+    assert sorted(read_outputs(tmp_path, "out")) == sorted(want)
+    assert sorted(f for f in os.listdir(tmp_path) if not f.startswith("out.")) == ["g1.ctl", "g1.seq", "g1.trace"]
+
+
+def test_run_finish_after_a_failure_leaves_no_file(lib, tmp_path):
+    import ctypes as C
+    from sampler_util import run_ranks
+    options = dict(coal_stats="out", coal_stats_rows=5, time_slices=4, ancestry="out", gene_trees="out", gene_trees_loci="0-15:3")
+    run_ranks(R.build_hostemu(), "g1", 2, tmp_path, **options)
+    parts = sorted(f for f in os.listdir(tmp_path) if f.startswith("out."))
+    assert parts == [f"out.{kind}.part{r}" for kind in ("ancestry", "coal", "slices", "trees") for r in range(2)]
+    o = G.GphRunOptions(size=C.sizeof(G.GphRunOptions), ctl=b"g1.ctl", coal_stats_prefix=b"out", time_slices=4, ancestry_prefix=b"out",
+                        gene_trees_prefix=b"out")
+    with _in_dir(tmp_path):
+        assert lib.gph_run_finish(o, 2, 1) == 0
+    assert not [f for f in os.listdir(tmp_path) if f.startswith("out.")]

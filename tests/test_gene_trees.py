@@ -20,7 +20,7 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_records
-from sampler_util import EXE, _copy_case, _fmt, _locus_names, _pop_names, _run, hostemu_library, printed_names, read_outputs
+from sampler_util import EXE, _copy_case, _fmt, _locus_names, _pop_names, _run, hostemu_library, printed_names, read_outputs, run_ranks
 from test_ancestry import BIG, CASES, GOLDEN_ITERS
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
@@ -595,51 +595,20 @@ def test_failed_run_leaves_no_trees_file(hostemu, tmp_path):
 
 
 # ---------------------------------------------------------------- ranks
-RANK_WORKER = r'''
-import os, sys
-sys.path.insert(0, %(repo)r)
-import gphocs_amd as G
-rank, world = int(sys.argv[1]), int(sys.argv[2])
-lib = G.load_library(%(lib)r) if %(lib)r else G.load_library(dims=%(dims)r)
-comm = lib.gph_comm_create_shm(%(name)r.encode(), rank, world)
-assert comm
-os.chdir(%(cwd)r)
-rc = lib.gph_run_control_file_ex5(%(ctl)r.encode(), None, 0, 0, comm, None, None, 0, 0, None, 0, b"out", %(spec)r, %(rows)d)
-sys.stdout.flush()
-if rc == 0:
-    lib.gph_comm_destroy(comm)
-os._exit(1 if rc else 0)
-'''
-
-
-def run_ranks(lib_path, name, ranks, d, spec, rows=7):
-    """`ranks` processes over a shared-memory communicator, each the program's own loop with --gene-trees out: their parts stay"""
-    import gphocs_amd as G
-    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
-    _copy_case(name, d)
-    script = d / "w.py"
-    script.write_text(RANK_WORKER % dict(repo=REPO, lib=lib_path, dims=(pk.n, pk.K, pk.B), name=f"/gphocs-gt-{os.getpid()}-{name}-{ranks}-{d.name}",
-                                         cwd=str(d), ctl=name + ".ctl", rows=rows, spec=spec.encode() if spec else None))
-    procs = [subprocess.Popen([sys.executable, str(script), str(r), str(ranks)], stdout=subprocess.DEVNULL) for r in range(ranks)]
-    for p in procs:
-        assert p.wait(timeout=600) == 0
-    return pk
-
-
 def check_ranks(lib_path, lib, tmp_path, name="m3"):
     """item 8: two ranks' parts, written into the file by gph_gene_trees_write, are the one-rank file -- for all loci, and
     for a selection that lies wholly in rank 1's block (rank 0 holds no selected locus); the launcher does the same; a part
     cut short or missing is refused and nothing is left"""
     for tag, spec in (("all", None), ("upper", "9-15:2")):
         one, two, three = tmp_path / f"one-{tag}", tmp_path / f"two-{tag}", tmp_path / f"g2-{tag}"
-        pk = run_ranks(lib_path, name, 1, one, spec)
+        pk = run_ranks(lib_path, name, 1, one, gene_trees="out", gene_trees_loci=spec, gene_trees_rows=7)
         assert pk.L == 16
         want = read_outputs(one, "out")                              # one rank writes its file itself (a communicator of one included)
         assert sorted(want) == ["trees.tsv"]
         loci = list(range(pk.L)) if spec is None else [9, 11, 13, 15]
         rows = [ln.split("\t") for ln in want["trees.tsv"].splitlines()[1:]]
         assert [(int(r[0]), int(r[1])) for r in rows] == [(it, g) for it in range(GOLDEN_ITERS[name]) for g in loci]
-        run_ranks(lib_path, name, 2, two, spec)
+        run_ranks(lib_path, name, 2, two, gene_trees="out", gene_trees_loci=spec, gene_trees_rows=7)
         assert sorted(f for f in os.listdir(two) if f.startswith("out.")) == ["out.trees.part0", "out.trees.part1"]
         if spec is not None:                                         # rank 0's part: a header, 120 iterations, no record
             b0 = open(two / "out.trees.part0", "rb").read()

@@ -28,7 +28,7 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_trace_files
-from sampler_util import EXE, _copy_case, _data_lines, _pop_names, _run, hostemu_library, read_outputs, within_bound  # noqa: F401
+from sampler_util import EXE, _copy_case, _data_lines, _pop_names, _run, hostemu_library, read_outputs, run_ranks, within_bound  # noqa: F401
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
 
@@ -452,7 +452,8 @@ def test_time_slices_without_a_prefix_is_a_usage_error(hostemu, tmp_path):
     env = dict(os.environ, GPHOCS_HIP_LIB=path)
     r = subprocess.run([EXE, "--time-slices", "4", "g1.ctl"], cwd=tmp_path, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode != 0 and "usage" in r.stderr and not os.path.exists(tmp_path / "g1.trace")
-    assert lib.gph_run_control_file_ex3(b"g1.ctl", None, 0, 0, None, None, None, 0, 4) == -1
+    import gphocs_amd as G
+    assert G.run_control_file(lib, "g1.ctl", time_slices=4) == -1
 
 
 def check_ranks(lib_path, lib, name, S, tmp_path, rank_counts=(2, 3)):
@@ -472,7 +473,7 @@ def check_ranks(lib_path, lib, name, S, tmp_path, rank_counts=(2, 3)):
     assert terms.shape == (len(its), S * (p.K + p.B))
     for ranks in rank_counts:
         d = tmp_path / f"w{ranks}"
-        run_ranks(lib_path, name, ranks, S, d)
+        run_ranks(lib_path, name, ranks, d, coal_stats="out", coal_stats_rows=5, time_slices=S)
         parts = [read_part(d / f"out.slices.part{r}") for r in range(ranks)]
         assert all(q[0] == (S, p.K, p.B, rd) and q[2] == len(its) for q in parts)
         mine = parts[0][1].copy()
@@ -497,35 +498,6 @@ def check_ranks(lib_path, lib, name, S, tmp_path, rank_counts=(2, 3)):
         _run(lib_path, e, ["-g", str(ranks), "-s", "out", "--coal-stats-rows", "5", "--time-slices", str(S), name + ".ctl"])
         out = read_outputs(e, "out")
         assert not [f for f in out if "part" in f] and out["slices.tsv"] == files["slices.tsv"]
-
-
-RANK_WORKER = r'''
-import os, sys
-sys.path.insert(0, %(repo)r)
-import gphocs_amd as G
-rank, world = int(sys.argv[1]), int(sys.argv[2])
-lib = G.load_library(%(lib)r) if %(lib)r else G.load_library(dims=%(dims)r)
-comm = lib.gph_comm_create_shm(%(name)r.encode(), rank, world)
-assert comm
-os.chdir(%(cwd)r)
-rc = lib.gph_run_control_file_ex3(%(ctl)r.encode(), None, 0, 0, comm, None, b"out", 5, %(S)d)
-sys.stdout.flush()
-if rc == 0:
-    lib.gph_comm_destroy(comm)
-os._exit(1 if rc else 0)
-'''
-
-
-def run_ranks(lib_path, name, ranks, S, d):
-    import gphocs_amd as G
-    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
-    _copy_case(name, d)
-    script = d / "w.py"
-    script.write_text(RANK_WORKER % dict(repo=REPO, lib=lib_path, dims=(pk.n, pk.K, pk.B), name=f"/gphocs-ts-{os.getpid()}-{name}-{ranks}",
-                                         cwd=str(d), ctl=name + ".ctl", S=S))
-    procs = [subprocess.Popen([sys.executable, str(script), str(r), str(ranks)], stdout=subprocess.DEVNULL) for r in range(ranks)]
-    for p in procs:
-        assert p.wait(timeout=600) == 0
 
 
 def read_part(path):
