@@ -171,15 +171,15 @@ GPH_SM_FN void gph_an_leaf(const GphAnLds &s, const GphLayout &y, const GphAnSha
 }
 
 #ifdef GPH_HOSTEMU
-// host emulation: workgroup w with its lanes one after the other, phase by phase as the barriers order them
-static inline void ancestry_workgroup(const GphLayout &y, const GphAnShape &h, const char *pages, double *acc, uint32_t *row, int L, int w,
-                                      std::vector<char> &lds)
+// host emulation: workgroup w = block x with its lanes one after the other, phase by phase as the barriers order them; the
+// launch hands it a zeroed buffer for its dynamic LDS
+static inline void k_ancestry(GphBlk blk, GphLayout y, GphAnShape h, const char *pages, double *acc, uint32_t *row,
+                              int L)
 {
   const int n = y.n, N = y.N, ncol = gph_an_locus_columns(n, y.B), upl = h.img.bytes / 16;
-  lds.assign((size_t)h.lds_bytes + 16, 0);
   GphAnLds s;
-  gph_an_carve(lds.data(), N, h, s);
-  const int j0 = w * h.G;
+  gph_an_carve(blk.lds, N, h, s);
+  const int j0 = blk.x * h.G;
   bool some = false;
   for (int g = 0; g < h.G; g++) {
     s.nm[g] = j0 + g < L ? gph_an_num_migs(pages + (size_t)(j0 + g) * y.page_bytes, y) : 0;

@@ -1,0 +1,543 @@
+// gph_backend.h -- the one place in the engine's host code that knows which build it is in.
+//
+// gph_engine.hip serves two builds from one text: the gfx950 library, and the host-emulation library (-DGPH_HOSTEMU,
+// tests/hostemu: the CPU parity suite and the sanitizer builds).  Host emulation is a fake that the tests substitute for
+// the GPU; this file is its interface.  Both halves of the one conditional below define the same names with the same
+// signatures -- memory and stream, the chain state's two copies, the engine's own resources, the reduction / stage paths
+// (a fixed-shape tree with a last-block ticket on the device, a serial loop on the host) and the launch functions -- and
+// everything below the include in gph_engine.hip is one text for both.
+//
+// Included by gph_engine.hip after the kernels and gph_engine_state; it completes the engine object (struct gph_engine)
+// with the members only one build has.
+#pragma once
+
+// blocks of a flat launch (launch_grid): x, and y for the samplers that tile a chunk
+struct GphGrid { int x, y; };
+
+// What a launch counts -- host_stats(), class_stats() and last_kernel_ms are asserted by tests, so the rules are kept as
+// they grew, and they are not the same in the two builds:
+//
+//   site                          device build                           host build
+//   launch_loci                   n_launches += one per launch group     n_launches += one per call
+//   launch_wave                   not added to n_launches                not added to n_launches
+//   sample_end (k launches)       n_launches += k, sets last_which       neither
+//   apply_list (flat_launched)    n_launches += 1                        nothing
+//   cls_launches[cls]             += 1 per call                          += 1 per call
+//
+// launch_loci and launch_wave set last_which in both builds; launch_grid itself counts nothing (its callers do, above);
+// the reduction and stage kernels of the device build add one to n_launches each.
+
+#ifdef GPH_HOSTEMU
+// ================================================================ host emulation
+#define SETDEV(e) ((void)0)
+
+struct gph_engine : gph_engine_state {
+  std::vector<char> lds;             // the dynamic LDS of the block that is running
+};
+
+static int dev_alloc(void **p, size_t bytes) { *p = calloc(1, bytes ? bytes : 1); return *p ? 0 : GPH_EHIP; }
+static void dev_free(void *p) { free(p); }
+static int h2d(gph_engine *, void *d, const void *h, size_t n) { memcpy(d, h, n); return 0; }
+static int d2h(gph_engine *, void *h, const void *d, size_t n) { memcpy(h, d, n); return 0; }
+static int acc_zero(gph_engine *, void *p, size_t bytes) { if (p) memset(p, 0, bytes); return 0; }
+static int stream_sync(gph_engine *e) { e->n_syncs++; return 0; }
+static int collect_times(gph_engine *) { return 0; }
+static int tm_begin(gph_engine *, int) { return -1; }
+static void tm_end(gph_engine *, int) {}
+static int push_G(gph_engine *e) { e->G_dirty = false; return 0; }     /* one copy of the chain state: G_d == G_h */
+static int pull_G(gph_engine *e) { e->n_syncs++; return 0; }
+static int pull_row(gph_engine *e) { memcpy(e->h_red, e->d_red, sizeof(double) * GPH_RED_ROW); e->n_syncs++; return 0; }
+static bool resident(const gph_engine *) { return false; }
+static int flush_pending(gph_engine *) { return 0; }
+static int stage_defer(gph_engine *, int, int, int, bool &queued) { queued = false; return 0; }
+static void flat_launched(gph_engine *, int, int) {}     /* k flat launches of class cls (-1: none) went out: not counted here */
+
+static int reduce_local(gph_engine *e, int sec, int ncols)
+{
+  double *red = e->d_red + sec * GPH_RED_STRIDE;
+  for (int c = 0; c < ncols; c++) {
+    double s = 0, mn = 1e300, mx = -1e300;
+    for (int64_t g = 0; g < e->L; g++) {
+      double v;
+      if (sec == 0) v = e->dev.out[(size_t)g * GPH_OUT_SLOTS + c];
+      else v = e->dev.stats[(size_t)g * ncols + c];
+      s += v; mn = v < mn ? v : mn; mx = v > mx ? v : mx;
+    }
+    red[c] = s; red[GPH_RED_COLS + c] = mn; red[2 * GPH_RED_COLS + c] = mx;
+  }
+  red[3 * GPH_RED_COLS] = (double)*e->dev.err;
+  return 0;
+}
+
+// ---- engine resources
+static int backend_open(gph_engine *e)
+{
+  e->G_h = (GphGlobal *)calloc(1, sizeof(GphGlobal));
+  e->G_d = e->G_h;
+  e->h_red = (double *)calloc(GPH_RED_ROW, sizeof(double));
+  e->d_red = (double *)calloc(GPH_RED_ROW, sizeof(double));
+  e->d_gather = e->d_red;
+  return 0;
+}
+static void backend_close(gph_engine *e) { free(e->h_red); free(e->G_h); }
+static int wide_terms_bytes(int P) { return 8 * P; }     /* the host form keeps the root reduction's per-pattern terms behind the block */
+static int zero_error_word(gph_engine *e) { if (e->dev.err) *e->dev.err = 0; return 0; }
+static int loci_loaded(gph_engine *) { return 0; }
+static int scan_lds_limit(gph_engine *) { return 0; }
+static int peer_stream(gph_engine *, gph_comm *) { return 0; }
+static void runtime_version(char *buf, size_t n) { snprintf(buf, n, "host emulation (no HIP runtime)"); }
+#ifdef GPH_BOUNDS
+static int oob_take(int32_t *where) { *where = gph_oob_word; gph_oob_word = 0; return 0; }
+#endif
+
+// ---- launches: a kernel's host form takes its block first (GPH_KERNEL: the block index; a flat kernel: GphBlk) and is
+// called once per block, one block after the other, with a zeroed scratch buffer for its dynamic LDS
+static void launch_pre(gph_engine *e)
+{
+  g_model = e->G_h->model; g_lay = e->lay; gph_G_emu = e->G_h;
+  GPH_KA_MODEL(e->ka, e); e->ka.lay = e->lay; e->ka.G = e->G_h;
+}
+template <class... P, class... A>
+static int launch_loci(gph_engine *e, int cls, void (*kernel)(int, GphKargs, GphDev, int, P...), A &&...args)
+{
+  launch_pre(e);
+  for (auto &bk : e->buckets) {
+    e->lds.assign(bk.lds_bytes + 8 * e->lay.Pmax + 64, 0);     /* the host form keeps per-pattern terms for every P */
+    gph_sm = e->lds.data();
+    for (int b = 0; b < bk.count; b++) kernel(b, e->ka, e->dev, bk.j0, static_cast<P>(args)...);
+  }
+  e->last_which = cls; e->cls_launches[cls] += 1; e->n_launches++;
+  return 0;
+}
+template <class... P, class... A>
+static int launch_wave(gph_engine *e, int cls, void (*kernel)(int, GphKargs, GphDev, int, P...), size_t lds_bytes, A &&...args)
+{
+  launch_pre(e);
+  e->lds.assign(lds_bytes + 64, 0);
+  gph_sm = e->lds.data();
+  kernel(0, e->ka, e->dev, 0, static_cast<P>(args)...);
+  e->last_which = cls; e->cls_launches[cls] += 1;
+  return 0;
+}
+template <class... P, class... A>
+static int run_blocks(std::vector<char> &lds, GphGrid grid, int block, size_t lds_bytes, void (*kernel)(GphBlk, P...), A &&...args)
+{
+  for (int x = 0; x < grid.x; x++)
+    for (int y = 0; y < grid.y; y++) {
+      lds.assign(lds_bytes + 64, 0);
+      kernel(GphBlk{x, y, block, lds.data()}, static_cast<P>(args)...);
+    }
+  return 0;
+}
+template <class... P, class... A>
+static int launch_grid(gph_engine *e, GphGrid grid, int block, size_t lds_bytes, void (*kernel)(GphBlk, P...), A &&...args)
+{
+  return run_blocks(e->lds, grid, block, lds_bytes, kernel, args...);
+}
+
+static int debug_math(const double *x, const double *y, int n, double *out, int)
+{
+  GphKargs ka;
+  memset(&ka, 0, sizeof ka);
+  fill_math_constants(ka);
+  std::vector<char> lds;
+  return run_blocks(lds, GphGrid{(n + 255) / 256, 1}, 256, 0, k_debug_math, ka, x, y, n, out);
+}
+
+#else
+// ================================================================ gfx950
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "gphocs_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return GPH_EHIP; } } while (0)
+#define SETDEV(e) do { if (hipSetDevice((e)->cfg.device) != hipSuccess) return GPH_EHIP; } while (0)
+
+struct gph_engine : gph_engine_state {
+  unsigned *d_ticket = nullptr;                  // last-block ticket of the fused reduction
+  // resident mode: reductions and stages requested since the last launch; they go out as ONE kernel when the next
+  // per-locus kernel is launched (or the host needs the result)
+  int pend_nc0 = 0, pend_nc1 = 0;
+  GphStageList pend_sl = {0, {0}, {0}};
+  int pend_iteration = 0;
+  hipStream_t stream = nullptr;
+  // the launch group of the pattern-rich loci (P > 64: a few per cent of a data set, long wavefronts) runs NEXT TO the
+  // main group on a stream of its own, forked from and joined to the engine's stream with two events per launch point:
+  // one after the other, the small group cost a wavefront lifetime of its own per kernel class (configs[4]: 5 % of a sweep)
+  hipStream_t stream_wide = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  bool side_stream = true;            // GPH_SIDE_STREAM=0: the groups one after the other on the engine's stream (A/B, tests)
+  struct Tm { hipEvent_t a, b; int which; };
+  std::vector<Tm> tm;                // event pairs of the launches since the last synchronisation
+  size_t tm_used = 0;
+};
+
+static int dev_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 16) == hipSuccess ? 0 : GPH_EHIP; }
+static void dev_free(void *p) { if (p) (void)hipFree(p); }
+// elapsed times of the launches bracketed since the last synchronisation (the stream is idle: every event is complete)
+static int collect_times(gph_engine *e)
+{
+  for (size_t i = 0; i < e->tm_used; i++) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, e->tm[i].a, e->tm[i].b) == hipSuccess) { e->last_ms[e->tm[i].which] = ms; e->cls_ms[e->tm[i].which] += ms; }
+  }
+  e->tm_used = 0;
+  return 0;
+}
+static int stream_sync(gph_engine *e)
+{
+  HIPCHK(hipStreamSynchronize(e->stream));
+  e->n_syncs++;
+  return collect_times(e);
+}
+static int h2d(gph_engine *e, void *d, const void *h, size_t n)
+{
+  HIPCHK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+static int d2h(gph_engine *e, void *h, const void *d, size_t n)
+{
+  HIPCHK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+// a buffer on the device back to zero, queued on the engine's stream (nothing for a null pointer: a sampler that is off)
+static int acc_zero(gph_engine *e, void *p, size_t bytes)
+{
+  if (p) HIPCHK(hipMemsetAsync(p, 0, bytes, e->stream));
+  return 0;
+}
+// HIP events on the engine's own stream bracket the launches of a timed class; no host synchronisation here
+static int tm_begin(gph_engine *e, int which)
+{
+  if (!((e->timing_mask >> which) & 1)) return -1;
+  if (e->tm_used == e->tm.size()) {
+    gph_engine::Tm t;
+    if (hipEventCreate(&t.a) != hipSuccess || hipEventCreate(&t.b) != hipSuccess) return -1;
+    e->tm.push_back(t);
+  }
+  e->tm[e->tm_used].which = which;
+  (void)hipEventRecord(e->tm[e->tm_used].a, e->stream);
+  return (int)e->tm_used++;
+}
+static void tm_end(gph_engine *e, int slot) { if (slot >= 0) (void)hipEventRecord(e->tm[slot].b, e->stream); }
+// host mirror -> HBM: a synchronous copy, the mirror may be modified again as soon as this returns
+static int push_G(gph_engine *e)
+{
+  e->G_dirty = false;
+  return h2d(e, e->G_d, e->G_h, sizeof(GphGlobal));
+}
+// HBM -> host mirror, with a host synchronisation (the end of an iteration in resident mode)
+static int pull_G(gph_engine *e)
+{
+  HIPCHK(hipMemcpyAsync(e->G_h, e->G_d, sizeof(GphGlobal), hipMemcpyDeviceToHost, e->stream));
+  { int rcs = stream_sync(e); if (rcs) return rcs; }
+  e->mirror_current = true;
+  return 0;
+}
+// this rank's reduced row -> its pinned copy, with a host synchronisation (host mode)
+static int pull_row(gph_engine *e)
+{
+  HIPCHK(hipMemcpyAsync(e->h_red, e->d_red, sizeof(double) * GPH_RED_ROW, hipMemcpyDeviceToHost, e->stream));
+  return stream_sync(e);
+}
+// are the decisions above the loci taken on the device?  Yes unless something forces a host synchronisation at every
+// reduction point anyway: a caller-supplied all-reduce hook, the host shared-memory exchange of ranks that share a
+// GPU, or GPH_HOST_DECISIONS=1 (tests compare the two modes); never in the host-emulation build
+static bool resident(const gph_engine *e)
+{
+  if (e->force_host || e->allreduce || e->var_rates) return false;
+  if (e->comm && !gph_comm_on_stream(e->comm)) return false;
+  return true;
+}
+// k flat launches of class cls (-1: none, apply_list) went out
+static void flat_launched(gph_engine *e, int cls, int k) { e->n_launches += k; if (cls >= 0) e->last_which = cls; }
+
+static void launch_pre(gph_engine *e) { GPH_KA_MODEL(e->ka, e); e->ka.lay = e->lay; e->ka.G = e->G_d; }
+template <class... P, class... A>
+static int launch_on(hipStream_t stream, GphGrid grid, int block, size_t lds_bytes, void (*kernel)(P...), A &&...args)
+{
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid.x, (unsigned)grid.y), dim3((unsigned)block), lds_bytes, stream, static_cast<P>(args)...);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// a flat kernel on the engine's stream; what is pending and what is counted is the caller's business (sample_begin / _end,
+// apply_list, the reductions below)
+template <class... P, class... A>
+static int launch_grid(gph_engine *e, GphGrid grid, int block, size_t lds_bytes, void (*kernel)(P...), A &&...args)
+{
+  return launch_on(e->stream, grid, block, lds_bytes, kernel, args...);
+}
+
+// ---- the reductions and the stages above the loci
+// resident mode: everything requested since the last per-locus launch -- the reduction(s) of its outputs and the stages
+// above the loci -- as one kernel (single rank), or reduction -> RCCL all-gather -> stages (several ranks)
+static int flush_pending(gph_engine *e)
+{
+  const bool red = e->pend_nc0 > 0 || e->pend_nc1 > 0;
+  if (!red && e->pend_sl.n == 0) return 0;
+  const GphStageList sl = e->pend_sl;
+  const int nc0 = e->pend_nc0, nc1 = e->pend_nc1;
+  e->pend_nc0 = e->pend_nc1 = 0;
+  e->pend_sl.n = 0;
+  const bool multi = e->comm && gph_comm_world(e->comm) > 1;
+  int rc;
+  launch_pre(e);
+  if (red) {
+    /* several ranks whose kernels can address each other's rows (gph_comm_peer_exchange): the exchange happens INSIDE the
+     * reduction kernel's last block and the stages run there on everybody's rows -- one launch per reduction point, as
+     * with a single rank */
+    const bool inkernel = multi && e->peer_rows != nullptr;
+    const int fuse = sl.n > 0 && (!multi || inkernel);
+    GphPeerX X{1, 0, 0, 0, nullptr, nullptr, nullptr, 0};
+    if (inkernel) X = GphPeerX{gph_comm_world(e->comm), gph_comm_rank(e->comm), e->peer_stride, 0, e->peer_rows, e->peer_flags, e->d_gather, gph_comm_peer_next_gen(e->comm)};
+    if ((rc = launch_grid(e, GphGrid{GPH_RED_BLOCKS, 1}, GPH_RED_THREADS, 0, k_reduce_stage, e->ka, e->dev, nc0, nc1, e->d_part, e->d_ticket,
+                          e->d_red, fuse, sl, e->pend_iteration, X))) return rc;
+    e->n_launches++;
+    if (inkernel) {
+      e->n_collectives++;
+    } else if (multi) {
+      if (gph_comm_allgather_stream(e->comm, e->d_red, e->d_gather, GPH_RED_ROW, (void *)e->stream)) return GPH_EHIP;
+      e->n_collectives++;
+    } else if (e->comm) {
+      e->n_collectives++;   /* a one-rank communicator: the row is already everybody's */
+      if (gph_comm_allgather_stream(e->comm, e->d_red, e->d_gather, GPH_RED_ROW, (void *)e->stream)) return GPH_EHIP;
+    }
+    if (fuse) return 0;
+  }
+  if (sl.n > 0) {
+    const double *rows = e->comm ? e->d_gather : e->d_red;
+    if ((rc = launch_grid(e, GphGrid{1, 1}, GPH_RED_THREADS, 0, k_global, e->ka, rows, world_of(e), sl, e->pend_iteration))) return rc;
+    e->n_launches++;
+  }
+  return 0;
+}
+// reduce the per-locus outputs (section 0) or the page statistics (section 1) over the local loci into this rank's row
+static int reduce_local(gph_engine *e, int sec, int ncols)
+{
+  if (resident(e)) {
+    /* lazily: fused with the stages that consume the row (flush_pending) */
+    if (e->pend_sl.n > 0) { int rcf = flush_pending(e); if (rcf) return rcf; }
+    if (sec == 0) e->pend_nc0 = ncols; else e->pend_nc1 = ncols;
+    return 0;
+  }
+  int rc;
+  if ((rc = flush_pending(e))) return rc;
+  GphStageList none = {0, {0}, {0}};
+  launch_pre(e);
+  if ((rc = launch_grid(e, GphGrid{GPH_RED_BLOCKS, 1}, GPH_RED_THREADS, 0, k_reduce_stage, e->ka, e->dev, sec == 0 ? ncols : 0, sec == 1 ? ncols : 0,
+                        e->d_part, e->d_ticket, e->d_red, 0, none, 0, GphPeerX{1, 0, 0, 0, nullptr, nullptr, nullptr, 0}))) return rc;
+  e->n_launches += 1;
+  return 0;
+}
+// a stage above the loci in resident mode: queued, it goes out fused with the reduction before it (and the stages next to
+// it) at the next launch.  Host mode (queued = false): what is pending goes out, the caller runs the stage on the mirror
+static int stage_defer(gph_engine *e, int stage, int arg, int iteration, bool &queued)
+{
+  queued = resident(e);
+  if (!queued) return flush_pending(e);
+  if (e->pend_sl.n == 6) { int rcf = flush_pending(e); if (rcf) return rcf; }
+  e->pend_sl.stage[e->pend_sl.n] = stage;
+  e->pend_sl.arg[e->pend_sl.n] = arg;
+  e->pend_sl.n++;
+  e->pend_iteration = iteration;
+  e->mirror_current = false;     /* the stage writes the chain state on the device: the mirror is stale until pull_G */
+  return 0;
+}
+
+// ---- launches of the per-locus kernels.  One dispatch covers every locus with at most one pattern per lane (slots in
+// decreasing P: longest wavefronts first), a second one the rare loci with more (they also need the per-pattern terms
+// array in LDS), forked onto the side stream and joined again.  What is pending goes first; no host synchronisation here.
+template <class... P, class... A>
+static int launch_loci(gph_engine *e, int cls, void (*kernel)(GphKargs, GphDev, int, P...), A &&...args)
+{
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  launch_pre(e);
+  const int tms = tm_begin(e, cls);
+  const size_t nb = e->buckets.size();
+  const bool fork = e->side_stream && nb >= 2;
+  if (fork) { HIPCHK(hipEventRecord(e->ev_fork, e->stream)); HIPCHK(hipStreamWaitEvent(e->stream_wide, e->ev_fork, 0)); }
+  for (size_t bi = 0; bi < nb; bi++) {
+    const gph_engine::Bucket &bk = e->buckets[bi];
+    e->ka.lay.dyn_bytes = bk.lds_bytes;
+    { int rcl = launch_on(fork && bi + 1 < nb ? e->stream_wide : e->stream, GphGrid{bk.count, 1}, GPH_WAVE, bk.lds_bytes + e->lds_pad[cls],
+                          kernel, e->ka, e->dev, bk.j0, args...); if (rcl) return rcl; }
+    e->n_launches++;
+  }
+  if (fork) { HIPCHK(hipEventRecord(e->ev_join, e->stream_wide)); HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join, 0)); }
+  tm_end(e, tms);
+  e->last_which = cls; e->cls_launches[cls] += 1;
+  return 0;
+}
+// one single-wave workgroup with its own dynamic-LDS size (the serial scan of UpdateLocusRate)
+template <class... P, class... A>
+static int launch_wave(gph_engine *e, int cls, void (*kernel)(GphKargs, GphDev, int, P...), size_t lds_bytes, A &&...args)
+{
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  launch_pre(e);
+  const int tms = tm_begin(e, cls);
+  { int rcl = launch_on(e->stream, GphGrid{1, 1}, GPH_WAVE, lds_bytes, kernel, e->ka, e->dev, 0, args...); if (rcl) return rcl; }
+  tm_end(e, tms);
+  e->last_which = cls; e->cls_launches[cls] += 1;
+  return 0;
+}
+
+// ---- engine resources
+static int fill_math_tables(GphKargs &ka)
+{
+  void *p = nullptr;
+  if (hipGetSymbolAddress(&p, HIP_SYMBOL(gph_log_t_d)) != hipSuccess) return 1;
+  ka.log_t = (const double *)p;
+  if (hipGetSymbolAddress(&p, HIP_SYMBOL(gph_exp_t_d)) != hipSuccess) return 1;
+  ka.exp_t = (const uint64_t *)p;
+  return 0;
+}
+// streams, events, the pinned mirror of the chain state and of the reduced row, their copies in HBM, the ticket
+static int backend_open(gph_engine *e)
+{
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= e->cfg.device) {
+    fprintf(stderr, "gphocs_hip: no usable HIP device %d (found %d) -- this library has no CPU path\n", e->cfg.device, ndev);
+    return GPH_EHIP;
+  }
+  if (hipSetDevice(e->cfg.device) != hipSuccess || fill_math_tables(e->ka)) {
+    fprintf(stderr, "gphocs_hip: cannot resolve the device math tables\n");
+    return GPH_EHIP;
+  }
+  if (const char *ov = getenv("GPH_SIDE_STREAM")) e->side_stream = atoi(ov) != 0;
+  /* GPH_NONBLOCKING_STREAM=1 (tests): the engine's stream does not order itself against the legacy null stream -- what the
+   * in-kernel exchange of thread ranks needs (gph_engine_set_comm) */
+  const bool nb_ = getenv("GPH_NONBLOCKING_STREAM") && atoi(getenv("GPH_NONBLOCKING_STREAM")) != 0;
+  if ((nb_ ? hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) : hipStreamCreate(&e->stream)) != hipSuccess ||
+      hipStreamCreateWithFlags(&e->stream_wide, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess ||
+      hipHostMalloc((void **)&e->G_h, sizeof(GphGlobal), hipHostMallocDefault) != hipSuccess ||
+      hipMalloc((void **)&e->G_d, sizeof(GphGlobal)) != hipSuccess ||
+      hipHostMalloc((void **)&e->h_red, sizeof(double) * GPH_RED_ROW * 64, hipHostMallocDefault) != hipSuccess ||
+      hipMalloc((void **)&e->d_red, sizeof(double) * GPH_RED_ROW) != hipSuccess ||
+      hipMemset(e->d_red, 0, sizeof(double) * GPH_RED_ROW) != hipSuccess ||
+      hipMalloc((void **)&e->d_ticket, 64) != hipSuccess || hipMemset(e->d_ticket, 0, 64) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) return GPH_EHIP;
+  e->d_gather = e->d_red;
+  return 0;
+}
+static void backend_close(gph_engine *e)
+{
+  dev_free(e->G_d);
+  dev_free(e->d_ticket);
+  if (e->h_red) (void)hipHostFree(e->h_red);
+  if (e->G_h) (void)hipHostFree(e->G_h);
+  for (auto &t : e->tm) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
+  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
+  if (e->ev_join) (void)hipEventDestroy(e->ev_join);
+  if (e->stream_wide) (void)hipStreamDestroy(e->stream_wide);
+  if (e->stream) (void)hipStreamDestroy(e->stream);
+}
+static int wide_terms_bytes(int) { return 0; }     /* the root sum of the pattern-rich loci needs no terms array on the device */
+/* (null-stream operations; the engine's stream may be a non-blocking one, which does not order itself against them) */
+static int zero_error_word(gph_engine *e)
+{
+  return hipMemset(e->dev.err, 0, sizeof(int32_t)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess ? GPH_EHIP : 0;
+}
+// the loci are in HBM: the per-locus kernels use up to the wide group's dynamic LDS size; allow > 64 KiB
+static int loci_loaded(gph_engine *e)
+{
+  const void *ks[] = {(const void *)k_init, (const void *)k_sweep, (const void *)k_tau_eval, (const void *)k_tau_finish,
+                      (const void *)k_mix_eval, (const void *)k_mix_finish,
+                      (const void *)k_sync, (const void *)k_check, (const void *)k_lrate_apply, (const void *)k_lrate_prep,
+                      (const void *)k_unit};
+  int pad_max = 0;
+  if (const char *pe = getenv("GPH_LDS_PAD")) {
+    for (const char *q = pe; *q;) {
+      int w = -1, by = 0;
+      if (sscanf(q, "%d:%d", &w, &by) == 2 && w >= 0 && w < 16 && by >= 0) { e->lds_pad[w] = by; pad_max = by > pad_max ? by : pad_max; }
+      while (*q && *q != ',') q++;
+      if (*q == ',') q++;
+    }
+  }
+  /* image + the largest launch group's block (+ an experiment's padding) must fit the CU's LDS: said with the numbers, whatever
+   * made it too big (the message used to blame GPH_LDS_PAD for a block that was too large by itself) */
+  if (e->lay.lds_bytes + pad_max + (int)sizeof(GphLds) > 160 * 1024) {
+    fprintf(stderr, "gphocs_hip: %d-byte image + %d-byte sequence block%s = %d bytes of LDS per locus, the CU has %d%s\n", (int)sizeof(GphLds),
+            e->lay.lds_bytes, pad_max ? " + GPH_LDS_PAD" : "", e->lay.lds_bytes + pad_max + (int)sizeof(GphLds), 160 * 1024,
+            getenv("GPH_HUGE_LDS") ? " (GPH_HUGE_LDS is set: lower it, the block then stays in HBM)" : "");
+    return GPH_EARG;
+  }
+  for (auto k : ks) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lay.lds_bytes + pad_max));
+  return 0;
+}
+static int scan_lds_limit(gph_engine *e)
+{
+  HIPCHK(hipFuncSetAttribute((const void *)k_lrate_scan, hipFuncAttributeMaxDynamicSharedMemorySize, e->lr_lds_bytes));
+  return 0;
+}
+// the in-kernel exchange of the reduced rows between thread ranks of one device, where the communicator offers it: the
+// rows and generation words, and a stream of this rank's own priority level in place of the engine's
+static int peer_stream(gph_engine *e, gph_comm *c)
+{
+  if (!(c && gph_comm_world(c) > 1 && gph_comm_on_stream(c))) return 0;
+  double *rows = nullptr; unsigned long long *flags = nullptr; int32_t stride = 0;
+  int least_ = 0, greatest_ = 0;
+  if (hipDeviceGetStreamPriorityRange(&least_, &greatest_) != hipSuccess) { least_ = greatest_ = 0; }
+  const int levels_ = least_ - greatest_ + 1;
+  if (gph_comm_peer_exchange(c, &rows, &flags, &stride) && stride >= GPH_RED_ROW && gph_comm_world(c) > levels_) {
+    /* more thread ranks than stream priority levels: two ranks would share a hardware-queue pool and could end up behind
+     * each other (tools/peer_exchange_stress.py: world 4 gave up 4 times in 10) -- the event-ordered gather instead */
+    if (gph_comm_rank(c) == 0)
+      fprintf(stderr, "gphocs_hip: the in-kernel exchange is offered for up to %d thread ranks on one device (one stream priority level "
+                      "each); %d ranks use the event-ordered gather\n", levels_, gph_comm_world(c));
+  } else if (gph_comm_peer_exchange(c, &rows, &flags, &stride) && stride >= GPH_RED_ROW) {
+    e->peer_rows = rows; e->peer_flags = flags; e->peer_stride = stride;
+    /* a reduction kernel of this engine may WAIT for another rank's kernel: the engine's stream must not be a blocking
+     * stream then -- a blocking stream orders itself against the legacy null stream, and a null-stream operation of the
+     * other rank's host thread (hipMemset at load time) would wait for this rank's waiting kernel: a deadlock until the
+     * bounded wait gives up (found with tools/probe/peer_dbg.py; the plain two-stream probe, peer_probe.cpp, runs) */
+    /* ... and the ranks' streams must sit on DIFFERENT hardware queues (a kernel that waits for a kernel queued behind it on
+     * the same queue waits for ever).  HIP keeps a pool of hardware queues PER PRIORITY level and hands streams of one level
+     * to its pool round-robin: streams of different priority levels never share a queue, so rank r takes level r mod levels
+     * -- by construction for up to `levels` thread ranks (3 on this runtime: low / normal / high), round-robin luck beyond */
+    hipStream_t ns = nullptr;
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { least = greatest = 0; }
+    const int levels = least - greatest + 1;
+    const int prio = levels > 1 ? least - (gph_comm_rank(c) % levels) : 0;
+    if (hipStreamSynchronize(e->stream) != hipSuccess || hipStreamCreateWithPriority(&ns, hipStreamNonBlocking, prio) != hipSuccess) return GPH_EHIP;
+    (void)hipStreamDestroy(e->stream);
+    e->stream = ns;
+  }
+  return 0;
+}
+static void runtime_version(char *buf, size_t n)
+{
+  int rt = 0, dr = 0;
+  if (hipRuntimeGetVersion(&rt) != hipSuccess) rt = -1;
+  if (hipDriverGetVersion(&dr) != hipSuccess) dr = -1;
+  snprintf(buf, n, "HIP runtime %d, driver %d", rt, dr);
+}
+#ifdef GPH_BOUNDS
+static int oob_take(int32_t *where)
+{
+  int w = 0, z = 0;
+  HIPCHK(hipMemcpyFromSymbol(&w, HIP_SYMBOL(gph_oob_word), sizeof(int)));
+  if (w != 0) HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(gph_oob_word), &z, sizeof(int)));
+  *where = w;
+  return 0;
+}
+#endif
+// the parity probe's round trip: no engine, the null stream of `device`
+static int debug_math(const double *x, const double *y, int n, double *out, int device)
+{
+  double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipMalloc((void **)&dx, sizeof(double) * n));
+  HIPCHK(hipMalloc((void **)&dy, sizeof(double) * n));
+  HIPCHK(hipMalloc((void **)&dout, sizeof(double) * 5 * n));
+  HIPCHK(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dy, y, sizeof(double) * n, hipMemcpyHostToDevice));
+  GphKargs ka;
+  memset(&ka, 0, sizeof ka);
+  fill_math_constants(ka);
+  if (fill_math_tables(ka)) return GPH_EHIP;
+  { int rcl = launch_on(nullptr, GphGrid{(n + 255) / 256, 1}, 256, 0, k_debug_math, ka, dx, dy, n, dout); if (rcl) return rcl; }
+  HIPCHK(hipMemcpy(out, dout, sizeof(double) * 5 * n, hipMemcpyDeviceToHost));
+  (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
+  return 0;
+}
+#endif

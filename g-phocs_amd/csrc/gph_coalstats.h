@@ -194,14 +194,14 @@ GPH_SM_FN void gph_cs_chunk_pair_out(const GphCsLds &s, int n, int K, int bd, in
 }
 
 #ifdef GPH_HOSTEMU
-// host emulation: workgroup (ch, tile) with its lanes one after the other, phase by phase as the barriers order them
-static inline void coal_stats_workgroup(const GphLayout &y, const char *pages, double *part, int L, int chunk, int bd, int ch, int tile,
-                                        std::vector<char> &lds)
+// host emulation: workgroup (ch, tile) = block (x, y) with its lanes one after the other, phase by phase as the barriers
+// order them; the launch hands it a zeroed buffer for its dynamic LDS
+static inline void k_coal_stats(GphBlk blk, GphLayout y, const char *pages, double *part, int L, int chunk)
 {
   const int n = y.n, N = y.N, K = y.K, B = y.B, np = gph_cs_pairs(n), rd = gph_cs_row_doubles(n, K);
-  lds.assign(gph_cs_lds_bytes(n, K, B, bd) + 16, 0);
+  const int bd = blk.dim, ch = blk.x, tile = blk.y;
   GphCsLds s;
-  gph_cs_carve(lds.data(), n, K, B, bd, s);
+  gph_cs_carve(blk.lds, n, K, B, bd, s);
   const int j0 = ch * chunk, j1 = j0 + chunk < L ? j0 + chunk : L;
   const int valid = np - tile * bd < bd ? np - tile * bd : bd;
   double sgen = 0.0, sdata = 0.0;

@@ -52,7 +52,6 @@ int gph_oob_word = 0;
 #endif
 #define GPH_SWEEP_ATTR __attribute__((amdgpu_waves_per_eu(GPH_SWEEP_WAVES, GPH_SWEEP_WAVES)))
 #define GPH_SWEEP_WAVES_ GPH_SWEEP_WAVES
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "gphocs_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return GPH_EHIP; } } while (0)
 #endif
 
 // j0 = first slot of the launch group (see GphDev).  GphCtx reads the model from the kernel-argument segment (the host
@@ -97,7 +96,14 @@ GPH_HD void apply_list_locus(char *pg, const GphLayout &y, const GphApply *ap, i
   }
   fs[FS_GENLNL] = v;
 }
-#ifndef GPH_HOSTEMU
+#ifdef GPH_HOSTEMU
+static void k_apply_list(GphBlk b, GphKargs KA, GphDev D)
+{
+  const int na = KA.G->napply;
+  for (int g = b.x * b.dim; g < (b.x + 1) * b.dim && g < D.L && na > 0; g++)
+    apply_list_locus(D.pages + (size_t)g * KA.lay.page_bytes, KA.lay, KA.G->apply, na);
+}
+#else
 __global__ void k_apply_list(GphKargs KA, GphDev D)
 {
   int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -350,8 +356,17 @@ __global__ void __launch_bounds__(GPH_RED_THREADS) k_reduce_stage(GphKargs KA, G
 }
 #endif
 
-#ifndef GPH_HOSTEMU
 // parity probe: the device's exp/log (gph_math.h) and its native sqrt / divide / floor
+#ifdef GPH_HOSTEMU
+static void k_debug_math(GphBlk b, GphKargs KA, const double *x, const double *y, int n, double *o)
+{
+  (void)KA;
+  for (int i = b.x * b.dim; i < (b.x + 1) * b.dim && i < n; i++) {
+    o[i] = gph_exp(x[i]); o[n + i] = gph_log(x[i]); o[2 * n + i] = sqrt(fabs(x[i]));
+    o[3 * n + i] = x[i] / y[i]; o[4 * n + i] = floor(x[i]);
+  }
+}
+#else
 __global__ void k_debug_math(GphKargs KA, const double *x, const double *y, int n, double *o)
 {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -378,7 +393,8 @@ struct SmParts {     // one partial row of rd doubles per chunk of `chunk` slots
   int32_t chunk_next = 0;      // slots per chunk of the next alloc (the _set_chunk entry points; 0: the default)
 };
 
-struct gph_engine {
+// what both builds keep of an engine; gph_backend.h completes it (struct gph_engine) with the members only one has
+struct gph_engine_state {
   gph_config cfg;
   std::vector<int32_t> samplesPerPop, popFather, popSon0, popSon1, bandSrc, bandTgt;
   GphLayout lay;
@@ -419,14 +435,6 @@ struct gph_engine {
   int lds_pad[16] = {0};             // GPH_LDS_PAD="class:bytes,...": extra dynamic LDS per kernel class (occupancy experiments)
   // reductions: block partials, this rank's reduced row (GPH_RED_ROW doubles) and every rank's row after the all-gather
   double *d_part = nullptr, *d_red = nullptr, *d_gather = nullptr;
-#ifndef GPH_HOSTEMU
-  unsigned *d_ticket = nullptr;                  // last-block ticket of the fused reduction
-  // resident mode: reductions and stages requested since the last launch; they go out as ONE kernel when the next
-  // per-locus kernel is launched (or the host needs the result)
-  int pend_nc0 = 0, pend_nc1 = 0;
-  GphStageList pend_sl = {0, {0}, {0}};
-  int pend_iteration = 0;
-#endif
   double *h_red = nullptr;                       // pinned: this rank's row (host mode)
   // several ranks, one process per GPU: a native communicator (RCCL all-gather on the engine's stream, or -- ranks
   // sharing one GPU, tests only -- a host shared-memory exchange) or a caller-supplied hook
@@ -464,20 +472,6 @@ struct gph_engine {
   double cls_evals0[16] = {0}, cls_bytes0[16] = {0}, cls_nodes0[16] = {0};   // offsets of the last reset
   int last_which = 0;
   uint32_t timing_mask = 0xffffffffu;   // classes whose launches are bracketed by HIP events
-#ifndef GPH_HOSTEMU
-  hipStream_t stream = nullptr;
-  // the launch group of the pattern-rich loci (P > 64: a few per cent of a data set, long wavefronts) runs NEXT TO the
-  // main group on a stream of its own, forked from and joined to the engine's stream with two events per launch point:
-  // one after the other, the small group cost a wavefront lifetime of its own per kernel class (configs[4]: 5 % of a sweep)
-  hipStream_t stream_wide = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool side_stream = true;            // GPH_SIDE_STREAM=0: the groups one after the other on the engine's stream (A/B, tests)
-  struct Tm { hipEvent_t a, b; int which; };
-  std::vector<Tm> tm;                // event pairs of the launches since the last synchronisation
-  size_t tm_used = 0;
-#else
-  std::vector<char> lds;
-#endif
 };
 
 static int align_up(int x, int a) { return (x + a - 1) / a * a; }
@@ -510,7 +504,7 @@ static void build_layout(GphLayout &y, int n, int Kc, int K, int B, int rootPop,
   y.huge_P = 0x7fffffff;
 }
 
-static void build_model_static(gph_engine *e)
+static void build_model_static(gph_engine_state *e)
 {
   GphModel &m = e->G_h->model;
   const gph_config &c = e->cfg;
@@ -533,7 +527,7 @@ static void build_model_static(gph_engine *e)
     for (int b = 0; b < c.B; b++) if ((m.isAnc[e->bandTgt[b]] >> p) & 1) m.bandsOver[p][b >> 5] |= 1u << (b & 31);
   // populationPostOrder(rootPop), patch.c:1936-1951
   std::vector<int> order;
-  struct Rec { static void go(gph_engine *e, int pop, std::vector<int> &o) {
+  struct Rec { static void go(gph_engine_state *e, int pop, std::vector<int> &o) {
     if (pop >= e->cfg.Kc) { go(e, e->popSon0[pop], o); go(e, e->popSon1[pop], o); }
     o.push_back(pop); } };
   Rec::go(e, c.rootPop, order);
@@ -547,229 +541,30 @@ static void build_model_static(gph_engine *e)
 long long gph_ws[4];
 struct GphWsPrint { ~GphWsPrint() { fprintf(stderr, "WALKSTAT proposals %lld: prune steps %.2f, regraft steps %.2f, common prefix %.2f per proposal\n", gph_ws[3], (double)gph_ws[0] / gph_ws[3], (double)gph_ws[1] / gph_ws[3], (double)gph_ws[2] / gph_ws[3]); } } gph_ws_print;
 #endif
-// ---------------------------------------------------------------- runtime shim
+// ---------------------------------------------------------------- the backend
 // the model in the kernel-argument segment (every build but the many-band one, whose kernels all read G->model)
 #if GPH_BIG_BANDS
 #define GPH_KA_MODEL(ka, e) ((void)0)
 #else
 #define GPH_KA_MODEL(ka, e) ((ka).model = (e)->G_h->model)
 #endif
-#ifdef GPH_HOSTEMU
-static int dev_alloc(void **p, size_t bytes) { *p = calloc(1, bytes ? bytes : 1); return *p ? 0 : GPH_EHIP; }
-static void dev_free(void *p) { free(p); }
-static int h2d(gph_engine *, void *d, const void *h, size_t n) { memcpy(d, h, n); return 0; }
-static int d2h(gph_engine *, void *h, const void *d, size_t n) { memcpy(h, d, n); return 0; }
-static int stream_sync(gph_engine *e) { e->n_syncs++; return 0; }
-#define LAUNCH_PRE(e) do { g_model = (e)->G_h->model; g_lay = (e)->lay; gph_G_emu = (e)->G_h; \
-    GphKargs &ka_ = (e)->ka; GPH_KA_MODEL(ka_, e); ka_.lay = (e)->lay; ka_.G = (e)->G_h; } while (0)
-#define LAUNCH(e, which, name, ...) do { LAUNCH_PRE(e); GphKargs &ka_ = (e)->ka; \
-    for (auto &bk_ : (e)->buckets) { (e)->lds.assign(bk_.lds_bytes + 8 * (e)->lay.Pmax + 64, 0); /* the host form keeps per-pattern terms for every P */ gph_sm = (e)->lds.data(); \
-      for (int b_ = 0; b_ < bk_.count; b_++) name(b_, ka_, (e)->dev, bk_.j0, __VA_ARGS__); } \
-    (e)->last_which = (which); (e)->cls_launches[which] += 1; (e)->n_launches++; } while (0)
-#else
-static int dev_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 16) == hipSuccess ? 0 : GPH_EHIP; }
-static void dev_free(void *p) { if (p) (void)hipFree(p); }
-static int collect_times(gph_engine *e);
-static int flush_pending(gph_engine *e);
-static int stream_sync(gph_engine *e)
+// exp/log/rndu constants of gph_math.h / gph_locus.h (GphKargs::mathc); the device build adds the addresses of the two
+// 128-entry libm tables
+static void fill_math_constants(GphKargs &ka)
 {
-  HIPCHK(hipStreamSynchronize(e->stream));
-  e->n_syncs++;
-  return collect_times(e);
+  const double ec[8] = GPH_EXP_CONSTS, lc[18] = GPH_LOG_CONSTS;
+  const double rc[6] = {1.0 / 30269.0, 1.0 / 30307.0, 1.0 / 30323.0, 30269.0, 30307.0, 30323.0};
+  memcpy(&ka.mathc[0], ec, sizeof ec);
+  memcpy(&ka.mathc[8], lc, sizeof lc);
+  memcpy(&ka.mathc[26], rc, sizeof rc);
 }
-static int h2d(gph_engine *e, void *d, const void *h, size_t n)
-{
-  HIPCHK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
-}
-static int d2h(gph_engine *e, void *h, const void *d, size_t n)
-{
-  HIPCHK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
-}
-// elapsed times of the launches bracketed since the last synchronisation (the stream is idle: every event is complete)
-static int collect_times(gph_engine *e)
-{
-  for (size_t i = 0; i < e->tm_used; i++) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, e->tm[i].a, e->tm[i].b) == hipSuccess) { e->last_ms[e->tm[i].which] = ms; e->cls_ms[e->tm[i].which] += ms; }
-  }
-  e->tm_used = 0;
-  return 0;
-}
-static int tm_begin(gph_engine *e, int which)
-{
-  if (!((e->timing_mask >> which) & 1)) return -1;
-  if (e->tm_used == e->tm.size()) {
-    gph_engine::Tm t;
-    if (hipEventCreate(&t.a) != hipSuccess || hipEventCreate(&t.b) != hipSuccess) return -1;
-    e->tm.push_back(t);
-  }
-  e->tm[e->tm_used].which = which;
-  (void)hipEventRecord(e->tm[e->tm_used].a, e->stream);
-  return (int)e->tm_used++;
-}
-static void tm_end(gph_engine *e, int slot) { if (slot >= 0) (void)hipEventRecord(e->tm[slot].b, e->stream); }
-// timed launch: HIP events on the engine's own stream bracket the kernel.  One dispatch covers every
-// locus with at most one pattern per lane (slots in decreasing P: longest wavefronts first), a second one
-// the rare loci with more (they also need the per-pattern terms array in LDS).  No host synchronisation here.
-#define LAUNCH_PRE(e) do { GphKargs &ka_ = (e)->ka; GPH_KA_MODEL(ka_, e); ka_.lay = (e)->lay; ka_.G = (e)->G_d; } while (0)
-#define LAUNCH(e, which, name, ...) do { { int rcf_ = flush_pending(e); if (rcf_) return rcf_; } LAUNCH_PRE(e); GphKargs &ka_ = (e)->ka; \
-    const int tms_ = tm_begin((e), (which)); \
-    const bool fork_ = (e)->side_stream && (e)->buckets.size() >= 2; \
-    if (fork_) { HIPCHK(hipEventRecord((e)->ev_fork, (e)->stream)); HIPCHK(hipStreamWaitEvent((e)->stream_wide, (e)->ev_fork, 0)); } \
-    for (size_t bi_ = 0; bi_ < (e)->buckets.size(); bi_++) { auto &bk_ = (e)->buckets[bi_]; \
-      ka_.lay.dyn_bytes = bk_.lds_bytes; \
-      hipLaunchKernelGGL(name, dim3((unsigned)bk_.count), dim3(GPH_WAVE), bk_.lds_bytes + (e)->lds_pad[which], fork_ && bi_ + 1 < (e)->buckets.size() ? (e)->stream_wide : (e)->stream, ka_, (e)->dev, bk_.j0, __VA_ARGS__); \
-      HIPCHK(hipGetLastError()); (e)->n_launches++; } \
-    if (fork_) { HIPCHK(hipEventRecord((e)->ev_join, (e)->stream_wide)); HIPCHK(hipStreamWaitEvent((e)->stream, (e)->ev_join, 0)); } \
-    tm_end((e), tms_); \
-    (e)->last_which = (which); (e)->cls_launches[which] += 1; } while (0)
-#endif
-
-// one single-wave workgroup with its own dynamic-LDS size (the serial scan of UpdateLocusRate)
-#ifdef GPH_HOSTEMU
-#define LAUNCH1(e, which, name, ldsbytes, ...) do { LAUNCH_PRE(e); GphKargs &ka_ = (e)->ka; \
-    (e)->lds.assign((size_t)(ldsbytes) + 64, 0); gph_sm = (e)->lds.data(); \
-    name(0, ka_, (e)->dev, 0, __VA_ARGS__); \
-    (e)->last_which = (which); (e)->cls_launches[which] += 1; } while (0)
-#else
-#define LAUNCH1(e, which, name, ldsbytes, ...) do { { int rcf_ = flush_pending(e); if (rcf_) return rcf_; } LAUNCH_PRE(e); GphKargs &ka_ = (e)->ka; \
-    const int tms_ = tm_begin((e), (which)); \
-    hipLaunchKernelGGL(name, dim3(1), dim3(GPH_WAVE), (ldsbytes), (e)->stream, ka_, (e)->dev, 0, __VA_ARGS__); \
-    HIPCHK(hipGetLastError()); \
-    tm_end((e), tms_); \
-    (e)->last_which = (which); (e)->cls_launches[which] += 1; } while (0)
-#endif
-
-// host mirror -> HBM (the host changed settings or, in host mode, took a decision); a synchronous copy: the mirror
-// may be modified again as soon as this returns
-static int push_G(gph_engine *e)
-{
-  e->G_dirty = false;
-#ifdef GPH_HOSTEMU
-  return 0;
-#else
-  HIPCHK(hipMemcpyAsync(e->G_d, e->G_h, sizeof(GphGlobal), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
-#endif
-}
-// HBM -> host mirror, with a host synchronisation (the end of an iteration in resident mode)
-static int pull_G(gph_engine *e)
-{
-#ifdef GPH_HOSTEMU
-  e->n_syncs++;
-  return 0;
-#else
-  HIPCHK(hipMemcpyAsync(e->G_h, e->G_d, sizeof(GphGlobal), hipMemcpyDeviceToHost, e->stream));
-  { int rcs = stream_sync(e); if (rcs) return rcs; }
-  e->mirror_current = true;
-  return 0;
-#endif
-}
-#define PUSH_IF_DIRTY(e) do { if ((e)->G_dirty) { int rcp_ = push_G(e); if (rcp_) return rcp_; } } while (0)
-
-// are the decisions above the loci taken on the device?  Yes unless something forces a host synchronisation at every
-// reduction point anyway: a caller-supplied all-reduce hook, the host shared-memory exchange of ranks that share a
-// GPU, the host-emulation build, or GPH_HOST_DECISIONS=1 (tests compare the two modes)
-static bool resident(const gph_engine *e)
-{
-#ifdef GPH_HOSTEMU
-  (void)e;
-  return false;
-#else
-  if (e->force_host || e->allreduce || e->var_rates) return false;
-  if (e->comm && !gph_comm_on_stream(e->comm)) return false;
-  return true;
-#endif
-}
+static int world_of(const gph_engine *e);
+// memory and stream, the chain state's two copies (push_G: host mirror -> HBM after the host changed settings or, in host
+// mode, took a decision; pull_G: back), the engine's resources, the reductions, the launch functions: one form per build
+#include "gph_backend.h"
 static int world_of(const gph_engine *e) { return e->comm ? gph_comm_world(e->comm) : 1; }
+static int push_if_dirty(gph_engine *e) { return e->G_dirty ? push_G(e) : 0; }
 
-#ifdef GPH_HOSTEMU
-static int flush_pending(gph_engine *) { return 0; }
-#else
-// resident mode: everything requested since the last per-locus launch -- the reduction(s) of its outputs and the stages
-// above the loci -- as one kernel (single rank), or reduction -> RCCL all-gather -> stages (several ranks)
-static int flush_pending(gph_engine *e)
-{
-  const bool red = e->pend_nc0 > 0 || e->pend_nc1 > 0;
-  if (!red && e->pend_sl.n == 0) return 0;
-  const GphStageList sl = e->pend_sl;
-  const int nc0 = e->pend_nc0, nc1 = e->pend_nc1;
-  e->pend_nc0 = e->pend_nc1 = 0;
-  e->pend_sl.n = 0;
-  const bool multi = e->comm && gph_comm_world(e->comm) > 1;
-  LAUNCH_PRE(e);
-  if (red) {
-    /* several ranks whose kernels can address each other's rows (gph_comm_peer_exchange): the exchange happens INSIDE the
-     * reduction kernel's last block and the stages run there on everybody's rows -- one launch per reduction point, as
-     * with a single rank */
-    const bool inkernel = multi && e->peer_rows != nullptr;
-    const int fuse = sl.n > 0 && (!multi || inkernel);
-    GphPeerX X{1, 0, 0, 0, nullptr, nullptr, nullptr, 0};
-    if (inkernel) X = GphPeerX{gph_comm_world(e->comm), gph_comm_rank(e->comm), e->peer_stride, 0, e->peer_rows, e->peer_flags, e->d_gather, gph_comm_peer_next_gen(e->comm)};
-    hipLaunchKernelGGL(k_reduce_stage, dim3(GPH_RED_BLOCKS), dim3(GPH_RED_THREADS), 0, e->stream, e->ka, e->dev, nc0, nc1, e->d_part, e->d_ticket,
-                       e->d_red, fuse, sl, e->pend_iteration, X);
-    HIPCHK(hipGetLastError());
-    e->n_launches++;
-    if (inkernel) {
-      e->n_collectives++;
-    } else if (multi) {
-      if (gph_comm_allgather_stream(e->comm, e->d_red, e->d_gather, GPH_RED_ROW, (void *)e->stream)) return GPH_EHIP;
-      e->n_collectives++;
-    } else if (e->comm) {
-      e->n_collectives++;   /* a one-rank communicator: the row is already everybody's */
-      if (gph_comm_allgather_stream(e->comm, e->d_red, e->d_gather, GPH_RED_ROW, (void *)e->stream)) return GPH_EHIP;
-    }
-    if (fuse) return 0;
-  }
-  if (sl.n > 0) {
-    const double *rows = e->comm ? e->d_gather : e->d_red;
-    hipLaunchKernelGGL(k_global, dim3(1), dim3(GPH_RED_THREADS), 0, e->stream, e->ka, rows, world_of(e), sl, e->pend_iteration);
-    HIPCHK(hipGetLastError());
-    e->n_launches++;
-  }
-  return 0;
-}
-#endif
-
-// reduce the per-locus outputs (section 0) or the page statistics (section 1) over the local loci into this rank's row
-static int reduce_local(gph_engine *e, int sec, int ncols)
-{
-#ifdef GPH_HOSTEMU
-  double *red = e->d_red + sec * GPH_RED_STRIDE;
-  for (int c = 0; c < ncols; c++) {
-    double s = 0, mn = 1e300, mx = -1e300;
-    for (int64_t g = 0; g < e->L; g++) {
-      double v;
-      if (sec == 0) v = e->dev.out[(size_t)g * GPH_OUT_SLOTS + c];
-      else v = e->dev.stats[(size_t)g * ncols + c];
-      s += v; mn = v < mn ? v : mn; mx = v > mx ? v : mx;
-    }
-    red[c] = s; red[GPH_RED_COLS + c] = mn; red[2 * GPH_RED_COLS + c] = mx;
-  }
-  red[3 * GPH_RED_COLS] = (double)*e->dev.err;
-  return 0;
-#else
-  if (resident(e)) {
-    /* lazily: fused with the stages that consume the row (flush_pending) */
-    if (e->pend_sl.n > 0) { int rcf = flush_pending(e); if (rcf) return rcf; }
-    if (sec == 0) e->pend_nc0 = ncols; else e->pend_nc1 = ncols;
-    return 0;
-  }
-  { int rcf = flush_pending(e); if (rcf) return rcf; }
-  GphStageList none = {0, {0}, {0}};
-  LAUNCH_PRE(e);
-  hipLaunchKernelGGL(k_reduce_stage, dim3(GPH_RED_BLOCKS), dim3(GPH_RED_THREADS), 0, e->stream, e->ka, e->dev, sec == 0 ? ncols : 0, sec == 1 ? ncols : 0,
-                     e->d_part, e->d_ticket, e->d_red, 0, none, 0, GphPeerX{1, 0, 0, 0, nullptr, nullptr, nullptr, 0});
-  HIPCHK(hipGetLastError());
-  e->n_launches += 1;
-  return 0;
-#endif
-}
 static int reduce_stats(gph_engine *e) { return reduce_local(e, 1, 2 * e->cfg.K + 2 * e->cfg.B); }
 
 // which columns of the reduced row a stage consumes (host mode with a caller-supplied all-reduce hook: only these
@@ -816,31 +611,13 @@ static double *colp(double *row, const int sc[2], int kind)   /* kind 0 sum, 1 m
 // gg_stage on the host mirror and push the mirror.
 static int run_stage(gph_engine *e, int stage, int arg, int iteration)
 {
-  const bool reads = stage_reads_row(stage);
-#ifndef GPH_HOSTEMU
-  if (resident(e)) {
-    /* queued: goes out fused with the reduction before it (and the stages next to it) at the next launch */
-    if (e->pend_sl.n == 6) { int rcf = flush_pending(e); if (rcf) return rcf; }
-    e->pend_sl.stage[e->pend_sl.n] = stage;
-    e->pend_sl.arg[e->pend_sl.n] = arg;
-    e->pend_sl.n++;
-    e->pend_iteration = iteration;
-    e->mirror_current = false;     /* the stage writes the chain state on the device: the mirror is stale until pull_G */
-    (void)reads;
-    return 0;
-  }
-  { int rcf = flush_pending(e); if (rcf) return rcf; }
-#endif
+  int rc;
+  bool queued;
+  if ((rc = stage_defer(e, stage, arg, iteration, queued)) || queued) return rc;
   GphRed R;
   R.rows = e->h_red; R.world = 1;
-  if (reads) {
-#ifdef GPH_HOSTEMU
-    memcpy(e->h_red, e->d_red, sizeof(double) * GPH_RED_ROW);
-    e->n_syncs++;
-#else
-    HIPCHK(hipMemcpyAsync(e->h_red, e->d_red, sizeof(double) * GPH_RED_ROW, hipMemcpyDeviceToHost, e->stream));
-    { int rcs = stream_sync(e); if (rcs) return rcs; }
-#endif
+  if (stage_reads_row(stage)) {
+    if ((rc = pull_row(e))) return rc;
     if (e->allreduce || e->comm) {
       StageCols c;
       stage_columns(e, stage, c);
@@ -848,7 +625,6 @@ static int run_stage(gph_engine *e, int stage, int arg, int iteration)
       for (int k = 0; k < c.ns; k++) sums[k] = *colp(e->h_red, c.s[k], 0);
       for (int k = 0; k < c.nm; k++) mins[k] = *colp(e->h_red, c.m[k], 1);
       for (int k = 0; k < c.nx; k++) mins[c.nm + k] = -*colp(e->h_red, c.x[k], 2);   /* a maximum as the minimum of the negatives */
-      int rc = 0;
       if (e->allreduce) rc = e->allreduce(e->allreduce_user, sums, c.ns, mins, c.nm + c.nx);
       else rc = gph_comm_allreduce_host(e->comm, sums, c.ns, mins, c.nm + c.nx);
       if (rc) return GPH_EHIP;
@@ -963,8 +739,9 @@ static int run_stage_now(gph_engine *e, int stage, int arg);
 // other than the sweep is about to read or write the pages)
 static int mix_finish_owed(gph_engine *e)
 {
-  if (e->mix_owed) { e->mix_owed = false; LAUNCH(e, 7, k_mix_finish, 0); }
-  return 0;
+  if (!e->mix_owed) return 0;
+  e->mix_owed = false;
+  return launch_loci(e, 7, k_mix_finish, 0);
 }
 // run a deferred synchronizeEvents pass now (anything but the next genealogy sweep is about to touch the pages).
 // now = the caller is a stepwise entry point that goes on to edit the host mirror of the chain state and push it: the
@@ -972,41 +749,16 @@ static int mix_finish_owed(gph_engine *e)
 // checked -- before that, or the push would overwrite what a queued device-side stage wrote
 static int flush_sync(gph_engine *e, bool now)
 {
-  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }     /* a mixing commit left for the next sweep kernel goes first */
+  int rc;
+  if ((rc = mix_finish_owed(e))) return rc;     /* a mixing commit left for the next sweep kernel goes first */
   if (!e->sync_pending) return 0;
   e->sync_pending = false;
-  PUSH_IF_DIRTY(e);
-  LAUNCH(e, 8, k_sync, 0);
-  int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
-  if (rc) return rc;
+  if ((rc = push_if_dirty(e))) return rc;
+  if ((rc = launch_loci(e, 8, k_sync, 0))) return rc;
+  if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
   if (now) return run_stage_now(e, GS_REFRESH_DONE, 0);
   return run_stage(e, GS_REFRESH_DONE, 0, e->G_h->iteration);
 }
-
-// exp/log/rndu constants of gph_math.h / gph_locus.h (GphKargs::mathc) and, on the device, the addresses of the two
-// 128-entry libm tables
-static void fill_math_constants(GphKargs &ka)
-{
-  const double ec[8] = GPH_EXP_CONSTS, lc[18] = GPH_LOG_CONSTS;
-  const double rc[6] = {1.0 / 30269.0, 1.0 / 30307.0, 1.0 / 30323.0, 30269.0, 30307.0, 30323.0};
-  memcpy(&ka.mathc[0], ec, sizeof ec);
-  memcpy(&ka.mathc[8], lc, sizeof lc);
-  memcpy(&ka.mathc[26], rc, sizeof rc);
-}
-#ifndef GPH_HOSTEMU
-static int fill_math_tables(GphKargs &ka)
-{
-  void *p = nullptr;
-  if (hipGetSymbolAddress(&p, HIP_SYMBOL(gph_log_t_d)) != hipSuccess) return 1;
-  ka.log_t = (const double *)p;
-  if (hipGetSymbolAddress(&p, HIP_SYMBOL(gph_exp_t_d)) != hipSuccess) return 1;
-  ka.exp_t = (const uint64_t *)p;
-  return 0;
-}
-#define SETDEV(e) do { if (hipSetDevice((e)->cfg.device) != hipSuccess) return GPH_EHIP; } while (0)
-#else
-#define SETDEV(e) ((void)0)
-#endif
 
 // a stage whose result the CALLER needs now (the stepwise entry points of the C ABI): host path whatever the mode
 static int run_stage_now(gph_engine *e, int stage, int arg)
@@ -1017,19 +769,6 @@ static int run_stage_now(gph_engine *e, int stage, int arg)
   e->force_host = fh;
   if (rc) return rc;
   return check_error(e);
-}
-
-// accumulators of a sampler on the device back to zero (queued on the engine's stream; nothing while the feature is off)
-static int acc_zero(gph_engine *e, void *p, size_t bytes)
-{
-  if (!p) return 0;
-#ifdef GPH_HOSTEMU
-  (void)e;
-  memset(p, 0, bytes);
-#else
-  HIPCHK(hipMemsetAsync(p, 0, bytes, e->stream));
-#endif
-  return 0;
 }
 
 // ---------------------------------------------------------------- C ABI
@@ -1063,40 +802,7 @@ int gph_engine_create(const gph_config *cfg, gph_engine **out)
   fill_math_constants(e->ka);
   if (const char *fh = getenv("GPH_HOST_DECISIONS")) e->force_host = atoi(fh) != 0;
   if (const char *nf = getenv("GPH_NO_FUSE")) e->no_fuse = atoi(nf) != 0;
-#ifndef GPH_HOSTEMU
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= cfg->device) {
-    fprintf(stderr, "gphocs_hip: no usable HIP device %d (found %d) -- this library has no CPU path\n", cfg->device, ndev);
-    delete e;
-    return GPH_EHIP;
-  }
-  if (hipSetDevice(cfg->device) != hipSuccess || fill_math_tables(e->ka)) {
-    fprintf(stderr, "gphocs_hip: cannot resolve the device math tables\n");
-    delete e;
-    return GPH_EHIP;
-  }
-  if (const char *ov = getenv("GPH_SIDE_STREAM")) e->side_stream = atoi(ov) != 0;
-  /* GPH_NONBLOCKING_STREAM=1 (tests): the engine's stream does not order itself against the legacy null stream -- what the
-   * in-kernel exchange of thread ranks needs (gph_engine_set_comm) */
-  const bool nb_ = getenv("GPH_NONBLOCKING_STREAM") && atoi(getenv("GPH_NONBLOCKING_STREAM")) != 0;
-  if ((nb_ ? hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) : hipStreamCreate(&e->stream)) != hipSuccess ||
-      hipStreamCreateWithFlags(&e->stream_wide, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void **)&e->G_h, sizeof(GphGlobal), hipHostMallocDefault) != hipSuccess ||
-      hipMalloc((void **)&e->G_d, sizeof(GphGlobal)) != hipSuccess ||
-      hipHostMalloc((void **)&e->h_red, sizeof(double) * GPH_RED_ROW * 64, hipHostMallocDefault) != hipSuccess ||
-      hipMalloc((void **)&e->d_red, sizeof(double) * GPH_RED_ROW) != hipSuccess ||
-      hipMemset(e->d_red, 0, sizeof(double) * GPH_RED_ROW) != hipSuccess ||
-      hipMalloc((void **)&e->d_ticket, 64) != hipSuccess || hipMemset(e->d_ticket, 0, 64) != hipSuccess ||
-      hipStreamSynchronize(nullptr) != hipSuccess) { gph_engine_destroy(e); return GPH_EHIP; }
-  e->d_gather = e->d_red;
-#else
-  e->G_h = (GphGlobal *)calloc(1, sizeof(GphGlobal));
-  e->G_d = e->G_h;
-  e->h_red = (double *)calloc(GPH_RED_ROW, sizeof(double));
-  e->d_red = (double *)calloc(GPH_RED_ROW, sizeof(double));
-  e->d_gather = e->d_red;
-#endif
+  if (int rc = backend_open(e)) { gph_engine_destroy(e); return rc; }
   memset(e->G_h, 0, sizeof(GphGlobal));
   e->G_h->error_locus = -1;          /* (0 is a locus: an error that is not per-locus must not name it -- ADVICE round 5) */
   build_model_static(e);
@@ -1119,20 +825,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
   dev_free(e->d_red);
-#ifdef GPH_HOSTEMU
-  free(e->h_red);
-  free(e->G_h);
-#else
-  dev_free(e->G_d);
-  dev_free(e->d_ticket);
-  if (e->h_red) (void)hipHostFree(e->h_red);
-  if (e->G_h) (void)hipHostFree(e->G_h);
-  for (auto &t : e->tm) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-  if (e->stream_wide) (void)hipStreamDestroy(e->stream_wide);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-#endif
+  backend_close(e);
   delete e;
 }
 
@@ -1159,40 +852,7 @@ int gph_engine_set_comm(gph_engine *e, gph_comm *c)
   /* (the generation of the exchange belongs to the GROUP -- gph_comm_peer_next_gen: a second engine on the same communicator
    * goes on where the first one stopped instead of finding flags of generations it has not reached yet) */
   e->peer_rows = nullptr; e->peer_flags = nullptr; e->peer_stride = 0;
-#ifndef GPH_HOSTEMU
-  if (c && gph_comm_world(c) > 1 && gph_comm_on_stream(c)) {
-    double *rows = nullptr; unsigned long long *flags = nullptr; int32_t stride = 0;
-    int least_ = 0, greatest_ = 0;
-    if (hipDeviceGetStreamPriorityRange(&least_, &greatest_) != hipSuccess) { least_ = greatest_ = 0; }
-    const int levels_ = least_ - greatest_ + 1;
-    if (gph_comm_peer_exchange(c, &rows, &flags, &stride) && stride >= GPH_RED_ROW && gph_comm_world(c) > levels_) {
-      /* more thread ranks than stream priority levels: two ranks would share a hardware-queue pool and could end up behind
-       * each other (tools/peer_exchange_stress.py: world 4 gave up 4 times in 10) -- the event-ordered gather instead */
-      if (gph_comm_rank(c) == 0)
-        fprintf(stderr, "gphocs_hip: the in-kernel exchange is offered for up to %d thread ranks on one device (one stream priority level "
-                        "each); %d ranks use the event-ordered gather\n", levels_, gph_comm_world(c));
-    } else if (gph_comm_peer_exchange(c, &rows, &flags, &stride) && stride >= GPH_RED_ROW) {
-      e->peer_rows = rows; e->peer_flags = flags; e->peer_stride = stride;
-      /* a reduction kernel of this engine may WAIT for another rank's kernel: the engine's stream must not be a blocking
-       * stream then -- a blocking stream orders itself against the legacy null stream, and a null-stream operation of the
-       * other rank's host thread (hipMemset at load time) would wait for this rank's waiting kernel: a deadlock until the
-       * bounded wait gives up (found with tools/probe/peer_dbg.py; the plain two-stream probe, peer_probe.cpp, runs) */
-      /* ... and the ranks' streams must sit on DIFFERENT hardware queues (a kernel that waits for a kernel queued behind it on
-       * the same queue waits for ever).  HIP keeps a pool of hardware queues PER PRIORITY level and hands streams of one level
-       * to its pool round-robin: streams of different priority levels never share a queue, so rank r takes level r mod levels
-       * -- by construction for up to `levels` thread ranks (3 on this runtime: low / normal / high), round-robin luck beyond */
-      hipStream_t ns = nullptr;
-      int least = 0, greatest = 0;
-      if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { least = greatest = 0; }
-      const int levels = least - greatest + 1;
-      const int prio = levels > 1 ? least - (gph_comm_rank(c) % levels) : 0;
-      if (hipStreamSynchronize(e->stream) != hipSuccess || hipStreamCreateWithPriority(&ns, hipStreamNonBlocking, prio) != hipSuccess) return GPH_EHIP;
-      (void)hipStreamDestroy(e->stream);
-      e->stream = ns;
-    }
-  }
-#endif
-  return 0;
+  return peer_stream(e, c);
 }
 
 GphGlobal *gph_engine_global_(gph_engine *e) { if (!e) return nullptr; e->G_dirty = true; return e->G_h; }
@@ -1259,10 +919,7 @@ int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *poff, const ui
       const int pw = (int)(poff[e->h_orig[nhuge] + 1] - poff[e->h_orig[nhuge]]);
       gph_engine::Bucket bk;
       bk.j0 = (int)nhuge; bk.count = (int)(nwide - nhuge);
-      bk.lds_bytes = GPH_Q_TERMS(pw, n, cnt16);
-#ifdef GPH_HOSTEMU
-      bk.lds_bytes += 8 * pw;
-#endif
+      bk.lds_bytes = GPH_Q_TERMS(pw, n, cnt16) + wide_terms_bytes(pw);
       e->buckets.push_back(bk);
     }
     if (nwide < L) {
@@ -1351,12 +1008,7 @@ int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *poff, const ui
   rc |= dev_alloc((void **)&e->dev.stats, sizeof(double) * (2 * e->cfg.K + 2 * e->cfg.B) * L);
   rc |= dev_alloc((void **)&e->d_part, sizeof(double) * 2 * 3 * GPH_RED_BLOCKS * GPH_RED_COLS);
   rc |= dev_alloc((void **)&e->dev.err, sizeof(int32_t));
-#ifdef GPH_HOSTEMU
-  if (e->dev.err) *e->dev.err = 0;
-#else
-  /* (null-stream operations; the engine's stream may be a non-blocking one, which does not order itself against them) */
-  if (!rc && (hipMemset(e->dev.err, 0, sizeof(int32_t)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)) rc = GPH_EHIP;
-#endif
+  if (!rc) rc = zero_error_word(e);
   if (mutRates) rc |= dev_alloc((void **)&e->d_mutRate, sizeof(double) * L);
   if (rc) { fprintf(stderr, "gphocs_hip: device allocation failed\n"); return GPH_EHIP; }
   rc |= h2d(e, (void *)e->dev.cond_off, e->h_cond_off.data(), sizeof(uint64_t) * (L + 1));
@@ -1379,32 +1031,7 @@ int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *poff, const ui
   e->dev.Ltot = (int32_t)e->cfg.L_total;
   e->dev.locus_begin = e->cfg.locus_begin;
   e->loaded = true;
-#ifndef GPH_HOSTEMU
-  // per-locus kernels use up to the wide group's dynamic LDS size; allow > 64 KiB
-  const void *ks[] = {(const void *)k_init, (const void *)k_sweep, (const void *)k_tau_eval, (const void *)k_tau_finish,
-                      (const void *)k_mix_eval, (const void *)k_mix_finish,
-                      (const void *)k_sync, (const void *)k_check, (const void *)k_lrate_apply, (const void *)k_lrate_prep,
-                      (const void *)k_unit};
-  int pad_max = 0;
-  if (const char *pe = getenv("GPH_LDS_PAD")) {
-    for (const char *q = pe; *q;) {
-      int w = -1, by = 0;
-      if (sscanf(q, "%d:%d", &w, &by) == 2 && w >= 0 && w < 16 && by >= 0) { e->lds_pad[w] = by; pad_max = by > pad_max ? by : pad_max; }
-      while (*q && *q != ',') q++;
-      if (*q == ',') q++;
-    }
-  }
-  /* image + the largest launch group's block (+ an experiment's padding) must fit the CU's LDS: said with the numbers, whatever
-   * made it too big (the message used to blame GPH_LDS_PAD for a block that was too large by itself) */
-  if (e->lay.lds_bytes + pad_max + (int)sizeof(GphLds) > 160 * 1024) {
-    fprintf(stderr, "gphocs_hip: %d-byte image + %d-byte sequence block%s = %d bytes of LDS per locus, the CU has %d%s\n", (int)sizeof(GphLds),
-            e->lay.lds_bytes, pad_max ? " + GPH_LDS_PAD" : "", e->lay.lds_bytes + pad_max + (int)sizeof(GphLds), 160 * 1024,
-            getenv("GPH_HUGE_LDS") ? " (GPH_HUGE_LDS is set: lower it, the block then stays in HBM)" : "");
-    return GPH_EARG;
-  }
-  for (auto k : ks) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lay.lds_bytes + pad_max));
-#endif
-  return 0;
+  return loci_loaded(e);
 }
 
 int gph_engine_set_model(gph_engine *e, const double *theta, const double *popAge, const double *sampleAge,
@@ -1436,7 +1063,7 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   { int rcf = flush_pending(e); if (rcf) return rcf; }
   e->mix_owed = e->fin_owed = e->sync_pending = false;
   if (e->G_h->mix_flag || e->G_h->tau_flag) { e->G_h->mix_flag = 0; e->G_h->tau_flag = 0; e->G_dirty = true; }
-  PUSH_IF_DIRTY(e);
+  { int rcp = push_if_dirty(e); if (rcp) return rcp; }
   /* summaries of the old chain do not carry over; the locus-rate columns come and go with `locus-mut-rate VAR` */
   if (e->ls.d && e->ls.ncol != gph_ls_columns(e->cfg.K, e->cfg.B, e->var_rates)) { int rce = gph_engine_locus_summary_enable(e, 1); if (rce) return rce; }
   e->ls.samples = e->an.samples = 0;
@@ -1445,8 +1072,8 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   e->gt.iters.clear();
   { int rcz = acc_zero(e, e->ls.d, sizeof(double) * (size_t)e->ls.ncol * e->L); if (rcz) return rcz; }
   { int rcz = acc_zero(e, e->an.d_acc, sizeof(double) * (size_t)e->an.ncol * e->L); if (rcz) return rcz; }
-  LAUNCH(e, 3, k_init, e->seedz, (const double *)e->d_mutRate, e->init_predraws);
-  int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
+  int rc = launch_loci(e, 3, k_init, e->seedz, e->d_mutRate, e->init_predraws);
+  if (!rc) rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
   if (rc) return rc;
   e->G_h->nrec = 0;
@@ -1459,29 +1086,37 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   return rc;
 }
 
+// The three genealogy proposals fused in one launch (GPhoCS.c:1495-1538; flags: which of them) and the reductions of its
+// outputs.  Two things decided earlier ride at the kernel's head: the deferred synchronizeEvents of the finished iteration
+// (flag 8; with_sync tells the stage that follows) and the commit of an accepted mixing proposal (flag 16) -- its flag and
+// factor travel as kernel arguments off the host mirror, which must then be what the decision stage wrote
+static int sweep_launch(gph_engine *e, int flags, double ftCoal, double ftMig, int &with_sync)
+{
+  int rc;
+  with_sync = e->sync_pending ? 8 : 0;
+  e->sync_pending = false;
+  int with_mix = 0;
+  if (e->mix_owed) {
+    if (!e->mirror_current && (rc = finish_sync(e))) return rc;
+    e->mix_owed = false;
+    if (e->G_h->mix_flag) with_mix = 16;
+  }
+  if ((rc = launch_loci(e, 0, k_sweep, flags | with_sync | with_mix, ftCoal, ftMig, e->G_h->mix_c, e->G_h->mix_lnc))) return rc;
+  if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
+  return reduce_stats(e);
+}
+
 // ---- the stepwise entry points: one reference proposal function each (include/gphocs_hip.h), the result is on the
 // host when the call returns.  gph_engine_iteration_() below runs the same launches without the round trips.
 int gph_engine_genealogy_sweep(gph_engine *e, int32_t flags, double ftCoal, double ftMig, gph_sweep_result *out)
 {
   if (!e || !e->initialized || !out) return GPH_ESTATE;
   SETDEV(e);
-  PUSH_IF_DIRTY(e);
-  const int with_sync = e->sync_pending ? 8 : 0;   /* flag 8: synchronizeEvents first, in the same kernel */
-  e->sync_pending = false;
+  int rc, with_sync;
+  if ((rc = push_if_dirty(e))) return rc;
   GphGlobal &G = *e->G_h;
-  const double d0 = G.dataLogLikelihood, l0 = G.logLikelihood;
   const int64_t a0 = G.acc[0], a1 = G.acc[1], a2 = G.acc[2], a7 = G.acc[7];
-  int with_mix = 0;
-  if (e->mix_owed) {
-    /* the owed decision (flag, factor) travels as kernel arguments off the host mirror: it must be what the decision stage wrote */
-    if (!e->mirror_current) { int rcm = finish_sync(e); if (rcm) return rcm; }
-    e->mix_owed = false;
-    if (e->G_h->mix_flag) with_mix = 16;
-  }
-  LAUNCH(e, 0, k_sweep, (int)flags | with_sync | with_mix, ftCoal, ftMig, e->G_h->mix_c, e->G_h->mix_lnc);
-  int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
-  if (!rc) rc = reduce_stats(e);
-  if (rc) return rc;
+  if ((rc = sweep_launch(e, flags, ftCoal, ftMig, with_sync))) return rc;
   if ((rc = run_stage_now(e, GS_SWEEP_DONE, with_sync))) return rc;
   /* the per-class deltas, as the caller adds them (GPhoCS.c:1495-1545) */
   GphRed R; R.rows = e->h_red; R.world = 1;
@@ -1494,7 +1129,6 @@ int gph_engine_genealogy_sweep(gph_engine *e, int32_t flags, double ftCoal, doub
   out->dLog_mignode = R.sum(0, 5);
   out->dData_spr = R.sum(0, 6);
   out->dLog_spr = R.sum(0, 7);
-  (void)d0; (void)l0;
   return 0;
 }
 
@@ -1516,7 +1150,7 @@ int gph_engine_tau_evaluate(gph_engine *e, const gph_tau_args *a, gph_tau_result
   }
   int rc = push_G(e);
   if (rc) return rc;
-  LAUNCH(e, 1, k_tau_eval, 0);     /* stepwise: the finish of the previous proposal was a call of its own */
+  if ((rc = launch_loci(e, 1, k_tau_eval, 0))) return rc;     /* stepwise: the finish of the previous proposal was a call of its own */
   if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
   if ((rc = run_stage_now(e, GS_COUNT_ONLY, 1))) return rc;
   // first conflicting locus in serial (input) order: loci after it were never touched by
@@ -1530,30 +1164,22 @@ int gph_engine_tau_evaluate(gph_engine *e, const gph_tau_args *a, gph_tau_result
   return 0;
 }
 
-int gph_engine_tau_commit(gph_engine *e)
+// the commit (flag 1) or revert (flag 0: of the loci before `limit`, the first conflicting one) of the evaluated tau proposal
+static int tau_finish_now(gph_engine *e, int flag, long long limit)
 {
   if (!e || !e->initialized) return GPH_ESTATE;
   SETDEV(e);
-  e->G_h->tau_flag = 1;
-  e->G_h->tau_limit = (long long)1 << 62;
-  gg_fill_fin(*e->G_h, 1, e->G_h->tau_limit);
+  e->G_h->tau_flag = flag;
+  e->G_h->tau_limit = limit;
+  gg_fill_fin(*e->G_h, flag, limit);
   int rc = push_G(e);
   if (rc) return rc;
-  LAUNCH(e, 5, k_tau_finish, 0);
-  return 0;
+  return launch_loci(e, 5, k_tau_finish, 0);
 }
-
+int gph_engine_tau_commit(gph_engine *e) { return tau_finish_now(e, 1, (long long)1 << 62); }
 int gph_engine_tau_revert(gph_engine *e, int64_t first_conflict)
 {
-  if (!e || !e->initialized) return GPH_ESTATE;
-  SETDEV(e);
-  e->G_h->tau_flag = 0;
-  e->G_h->tau_limit = first_conflict >= 0 ? (long long)first_conflict : (long long)1 << 62;
-  gg_fill_fin(*e->G_h, 0, e->G_h->tau_limit);
-  int rc = push_G(e);
-  if (rc) return rc;
-  LAUNCH(e, 5, k_tau_finish, 0);
-  return 0;
+  return tau_finish_now(e, 0, first_conflict >= 0 ? (long long)first_conflict : (long long)1 << 62);
 }
 
 int gph_engine_mixing_evaluate(gph_engine *e, double c, double *dataDelta)
@@ -1564,7 +1190,7 @@ int gph_engine_mixing_evaluate(gph_engine *e, double c, double *dataDelta)
   e->G_h->mix_c = c;
   int rc = push_G(e);
   if (rc) return rc;
-  LAUNCH(e, 2, k_mix_eval, 0);
+  if ((rc = launch_loci(e, 2, k_mix_eval, 0))) return rc;
   if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
   if ((rc = run_stage_now(e, GS_COUNT_ONLY, 2))) return rc;
   GphRed R; R.rows = e->h_red; R.world = 1;
@@ -1579,8 +1205,7 @@ int gph_engine_mixing_commit(gph_engine *e, double c, double lnc)
   e->G_h->mix_flag = 1; e->G_h->mix_c = c; e->G_h->mix_lnc = lnc;
   int rc = push_G(e);
   if (rc) return rc;
-  LAUNCH(e, 7, k_mix_finish, 0);
-  return 0;
+  return launch_loci(e, 7, k_mix_finish, 0);
 }
 
 // mixing reject (GPhoCS.c:4881-4887): revertToSaved restores every locus exactly, and
@@ -1597,43 +1222,36 @@ static int owed_finishes(gph_engine *e)
 }
 static int apply_list(gph_engine *e)
 {
-  { int rco = owed_finishes(e); if (rco) return rco; }
-#ifdef GPH_HOSTEMU
-  for (int64_t g = 0; g < e->L; g++) apply_list_locus(e->dev.pages + (size_t)g * e->lay.page_bytes, e->lay, e->G_h->apply, e->G_h->napply);
-#else
-  { int rcf = flush_pending(e); if (rcf) return rcf; }
-  LAUNCH_PRE(e);
-  hipLaunchKernelGGL(k_apply_list, dim3((unsigned)((e->L + 255) / 256)), dim3(256), 0, e->stream, e->ka, e->dev);
-  HIPCHK(hipGetLastError());
-  e->n_launches++;
-#endif
+  int rc;
+  if ((rc = owed_finishes(e))) return rc;
+  if ((rc = flush_pending(e))) return rc;
+  launch_pre(e);
+  if ((rc = launch_grid(e, GphGrid{(int)((e->L + 255) / 256), 1}, 256, 0, k_apply_list, e->ka, e->dev))) return rc;
+  flat_launched(e, -1, 1);
   return 0;
 }
 
-int gph_engine_apply_theta(gph_engine *e, int32_t pop, double lnc, double thetaold, double thetanew)
+// one accepted UpdateTheta (kind 0, population idx, diff = 1/new - 1/old) or UpdateMigRates (kind 1, band idx, diff = new -
+// old rate) proposal as a touch-up list of its own
+static int apply_one(gph_engine *e, int kind, int idx, int limit, double lnc, double diff)
 {
-  if (!e || !e->initialized || pop < 0 || pop >= e->cfg.K) return GPH_EARG;
+  if (!e || !e->initialized || idx < 0 || idx >= limit) return GPH_EARG;
   SETDEV(e);
   { int rco = owed_finishes(e); if (rco) return rco; }    /* the touch-up edits the MAIN page: a commit that still sits in the shadow page goes first */
   GphGlobal &G = *e->G_h;
   G.napply = 1;
-  G.apply[0].kind = 0; G.apply[0].idx = pop; G.apply[0].lnc = lnc; G.apply[0].diff = (1 / thetanew - 1 / thetaold);
+  G.apply[0].kind = kind; G.apply[0].idx = idx; G.apply[0].lnc = lnc; G.apply[0].diff = diff;
   int rc = push_G(e);
   if (rc) return rc;
   return apply_list(e);
 }
-
+int gph_engine_apply_theta(gph_engine *e, int32_t pop, double lnc, double thetaold, double thetanew)
+{
+  return apply_one(e, 0, pop, e ? e->cfg.K : 0, lnc, (1 / thetanew - 1 / thetaold));
+}
 int gph_engine_apply_migrate(gph_engine *e, int32_t band, double lnc, double old_rate, double new_rate)
 {
-  if (!e || !e->initialized || band < 0 || band >= e->cfg.B) return GPH_EARG;
-  SETDEV(e);
-  { int rco = owed_finishes(e); if (rco) return rco; }    /* the touch-up edits the MAIN page: a commit that still sits in the shadow page goes first */
-  GphGlobal &G = *e->G_h;
-  G.napply = 1;
-  G.apply[0].kind = 1; G.apply[0].idx = band; G.apply[0].lnc = lnc; G.apply[0].diff = (new_rate - old_rate);
-  int rc = push_G(e);
-  if (rc) return rc;
-  return apply_list(e);
+  return apply_one(e, 1, band, e ? e->cfg.B : 0, lnc, (new_rate - old_rate));
 }
 
 int gph_engine_get_totals(gph_engine *e, double *cs, double *nc, double *ms, double *nm)
@@ -1641,10 +1259,10 @@ int gph_engine_get_totals(gph_engine *e, double *cs, double *nc, double *ms, dou
   if (!e || !e->initialized) return GPH_ESTATE;
   SETDEV(e);
   const int K = e->cfg.K, B = e->cfg.B;
-  PUSH_IF_DIRTY(e);
-  { int rcm = mix_finish_owed(e); if (rcm) return rcm; }    /* the statistics of an accepted mixing proposal are scaled by its commit */
-  int rc = reduce_stats(e);
-  if (rc) return rc;
+  int rc;
+  if ((rc = push_if_dirty(e))) return rc;
+  if ((rc = mix_finish_owed(e))) return rc;    /* the statistics of an accepted mixing proposal are scaled by its commit */
+  if ((rc = reduce_stats(e))) return rc;
   if ((rc = run_stage_now(e, GS_TOTALS, 0))) return rc;
   const GphGlobal &G = *e->G_h;
   for (int p = 0; p < K; p++) { if (cs) cs[p] = G.tot_coal[p]; if (nc) nc[p] = G.tot_ncoal[p]; }
@@ -1664,14 +1282,12 @@ int gph_engine_synchronize(gph_engine *e, int32_t refresh, double *oldGen, doubl
     if (newGen) *newGen = 0.0;
     return 0;
   }
-  { int rcs = flush_sync(e, true); if (rcs) return rcs; }
-  PUSH_IF_DIRTY(e);
-  LAUNCH(e, 8, k_sync, (int)refresh);
-  int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
-  if (rc) return rc;
-  const double l0 = e->G_h->logLikelihood;
+  int rc;
+  if ((rc = flush_sync(e, true))) return rc;
+  if ((rc = push_if_dirty(e))) return rc;
+  if ((rc = launch_loci(e, 8, k_sync, refresh))) return rc;
+  if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
   if ((rc = run_stage_now(e, GS_REFRESH_DONE, 0))) return rc;   /* arg 0: the caller applies the difference */
-  (void)l0;
   GphRed R; R.rows = e->h_red; R.world = 1;
   if (oldGen) *oldGen = R.sum(0, 1);
   if (newGen) *newGen = R.sum(0, 2);
@@ -1682,12 +1298,12 @@ int gph_engine_check_all(gph_engine *e, int32_t *ok, double *sumData, double *su
 {
   if (!e || !e->initialized) return GPH_ESTATE;
   SETDEV(e);
-  { int rcs = flush_sync(e, true); if (rcs) return rcs; }
-  PUSH_IF_DIRTY(e);
-  LAUNCH(e, 4, k_check, 0);
-  int rc = reduce_local(e, 0, GPH_OUT_SLOTS);
-  if (!rc) rc = reduce_stats(e);
-  if (rc) return rc;
+  int rc;
+  if ((rc = flush_sync(e, true))) return rc;
+  if ((rc = push_if_dirty(e))) return rc;
+  if ((rc = launch_loci(e, 4, k_check, 0))) return rc;
+  if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
+  if ((rc = reduce_stats(e))) return rc;
   e->G_h->nrec = 0;
   rc = run_stage_now(e, GS_CHECK_DONE, 0);
   if (ok) *ok = e->G_h->error != 9999;
@@ -1762,31 +1378,7 @@ int gph_engine_set_timing(gph_engine *e, uint32_t class_mask)
 int gph_debug_math(const double *x, const double *y, int32_t n, double *out, int32_t device)
 {
   if (!x || !y || !out || n <= 0) return GPH_EARG;
-#ifdef GPH_HOSTEMU
-  (void)device;
-  for (int i = 0; i < n; i++) {
-    out[i] = gph_exp(x[i]); out[n + i] = gph_log(x[i]); out[2 * n + i] = sqrt(fabs(x[i]));
-    out[3 * n + i] = x[i] / y[i]; out[4 * n + i] = floor(x[i]);
-  }
-  return 0;
-#else
-  double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipMalloc((void **)&dx, sizeof(double) * n));
-  HIPCHK(hipMalloc((void **)&dy, sizeof(double) * n));
-  HIPCHK(hipMalloc((void **)&dout, sizeof(double) * 5 * n));
-  HIPCHK(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dy, y, sizeof(double) * n, hipMemcpyHostToDevice));
-  GphKargs ka;
-  memset(&ka, 0, sizeof ka);
-  fill_math_constants(ka);
-  if (fill_math_tables(ka)) return GPH_EHIP;
-  hipLaunchKernelGGL(k_debug_math, dim3((n + 255) / 256), dim3(256), 0, 0, ka, dx, dy, (int)n, dout);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(out, dout, sizeof(double) * 5 * n, hipMemcpyDeviceToHost));
-  (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
-  return 0;
-#endif
+  return debug_math(x, y, n, out, device);
 }
 
 #ifndef GPH_BUILD_ID
@@ -1804,14 +1396,7 @@ const char *gph_build_compiler(void)
 const char *gph_runtime_version(void)
 {
   static char buf[96];
-#ifdef GPH_HOSTEMU
-  snprintf(buf, sizeof buf, "host emulation (no HIP runtime)");
-#else
-  int rt = 0, dr = 0;
-  if (hipRuntimeGetVersion(&rt) != hipSuccess) rt = -1;
-  if (hipDriverGetVersion(&dr) != hipSuccess) dr = -1;
-  snprintf(buf, sizeof buf, "HIP runtime %d, driver %d", rt, dr);
-#endif
+  runtime_version(buf, sizeof buf);
   return buf;
 }
 
@@ -1940,11 +1525,11 @@ int gph_engine_locus_rate_update(gph_engine *e, double finetune, double alpha, g
     fprintf(stderr, "gphocs_hip: UpdateLocusRate over a shard of the loci needs the all-reduce hook (gph_engine_set_allreduce)\n");
     return GPH_EARG;
   }
-  { int rcs = flush_sync(e, true); if (rcs) return rcs; }
-  PUSH_IF_DIRTY(e);
+  int rc = 0;
+  if ((rc = flush_sync(e, true))) return rc;
+  if ((rc = push_if_dirty(e))) return rc;
   const GphLayout &y = e->lay;
   const int n = e->cfg.n, N = 2 * n - 1;
-  int rc = 0;
   /* ---- the reference locus as every rank needs it: node records + rate, likelihood, root (every call), sequence
    * block (first call: it never changes).  32-bit words travel as doubles */
   std::vector<char> refpg(y.page_bytes, 0);
@@ -2042,15 +1627,14 @@ int gph_engine_locus_rate_update(gph_engine *e, double finetune, double alpha, g
     if (e->lr.ref_seq_bytes > 0 && h2d(e, e->d_ref_seq, seqblk.data(), e->lr.ref_seq_bytes)) return GPH_EHIP;
     e->lr.ref_seq = e->d_ref_seq;
     e->lr.ref_page = e->d_ref_page;
-#ifndef GPH_HOSTEMU
-    HIPCHK(hipFuncSetAttribute((const void *)k_lrate_scan, hipFuncAttributeMaxDynamicSharedMemorySize, e->lr_lds_bytes));
-#endif
+    if ((rc = scan_lds_limit(e))) return rc;
   }
   if (h2d(e, e->d_ref_page, refpg.data(), y.page_bytes)) return GPH_EHIP;
   e->lr.finetune = finetune; e->lr.alpha = alpha;
   e->lr.first = owner ? 1 : 0;
-  LAUNCH(e, 11, k_lrate_prep, finetune, e->d_lpre);
-  { int rcp = reduce_local(e, 0, GPH_OUT_SLOTS); if (!rcp) rcp = run_stage_now(e, GS_COUNT_ONLY, 11); if (rcp) return rcp; }
+  if ((rc = launch_loci(e, 11, k_lrate_prep, finetune, e->d_lpre))) return rc;
+  if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
+  if ((rc = run_stage_now(e, GS_COUNT_ONLY, 11))) return rc;
   /* ---- the scan, rank after rank in locus order: state = {next locus, rref, likref, dataLogLikelihood,
    * logLikelihood, rateVar, accepted, prepared rates used}; the rank whose block starts at `next` scans and
    * publishes the state, the others add zeros */
@@ -2063,11 +1647,9 @@ int gph_engine_locus_rate_update(gph_engine *e, double finetune, double alpha, g
     if (mine) {
       e->lr.rref0 = st[1]; e->lr.likref0 = st[2];
       e->lr.dataLnL = st[3]; e->lr.logL = st[4]; e->lr.rateVar = st[5];
-      LAUNCH1(e, 9, k_lrate_scan, e->lr_lds_bytes, e->lr);
+      if ((rc = launch_wave(e, 9, k_lrate_scan, e->lr_lds_bytes, e->lr))) return rc;
       if ((rc = d2h(e, res, e->d_lr_result, sizeof res))) return rc;
-#ifndef GPH_HOSTEMU
       collect_times(e);
-#endif
       if (res[4] != 0.0) { fprintf(stderr, "gphocs_hip: Fatal Error %04d reported by the locus-rate scan\n", (int)res[4]); return GPH_EKERNEL; }
       nx[0] = (double)(e->cfg.locus_begin + e->L); nx[1] = res[13]; nx[2] = res[14];
       nx[3] = res[1]; nx[4] = res[2]; nx[5] = res[3]; nx[6] = st[6] + res[0]; nx[7] = st[7] + res[5];
@@ -2085,10 +1667,9 @@ int gph_engine_locus_rate_update(gph_engine *e, double finetune, double alpha, g
     r.flag = (int32_t)st[6] << 2;
     if (h2d(e, e->d_lrec + jr, &r, sizeof r)) return GPH_EHIP;
   }
-  LAUNCH(e, 10, k_lrate_apply, (const GphLrRec *)e->d_lrec);
-  rc = reduce_local(e, 0, GPH_OUT_SLOTS);
-  if (!rc) rc = run_stage_now(e, GS_COUNT_ONLY, 10);
-  if (rc) return rc;
+  if ((rc = launch_loci(e, 10, k_lrate_apply, e->d_lrec))) return rc;
+  if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
+  if ((rc = run_stage_now(e, GS_COUNT_ONLY, 10))) return rc;
   io->accepted = (int64_t)st[6];
   io->dataLogLikelihood = st[3];
   io->logLikelihood = st[4];
@@ -2112,27 +1693,25 @@ int gph_engine_locus_rate_update(gph_engine *e, double finetune, double alpha, g
 // GPH_NO_FUSE=1 (tests) runs every finish as a kernel of its own, as the stepwise entry points do.
 static int finish_owed(gph_engine *e)
 {
-  if (e->fin_owed) { e->fin_owed = false; LAUNCH(e, 5, k_tau_finish, 0); }
-  return 0;
+  if (!e->fin_owed) return 0;
+  e->fin_owed = false;
+  return launch_loci(e, 5, k_tau_finish, 0);
+}
+// an evaluate kernel of the iteration and the reduction of its outputs; the finish that is owed rides at the kernel's head
+// (GPH_NO_FUSE: goes first, as a kernel of its own)
+static int evaluate_fused(gph_engine *e, int cls, decltype(&k_tau_eval) kernel)
+{
+  int rc;
+  if (e->no_fuse && (rc = finish_owed(e))) return rc;
+  const int fuse = e->fin_owed;
+  e->fin_owed = false;
+  if ((rc = launch_loci(e, cls, kernel, fuse))) return rc;
+  return reduce_local(e, 0, GPH_OUT_SLOTS);
 }
 static int part_sweep(gph_engine *e, int32_t iteration, double ftCoal, double ftMig)
 {
-  int rc;
-  // the three genealogy proposals run fused in one launch (GPhoCS.c:1495-1538); the deferred synchronizeEvents of the
-  // previous iteration rides at its head
-  const int with_sync = e->sync_pending ? 8 : 0;
-  e->sync_pending = false;
-  /* a mixing commit left over from the previous iteration: the host mirror of the chain state is current here (the
-   * previous iteration ended with a synchronisation), so the flag and the factor travel as kernel arguments */
-  int with_mix = 0;
-  if (e->mix_owed) {
-    if (!e->mirror_current) { int rcm = finish_sync(e); if (rcm) return rcm; }
-    e->mix_owed = false;
-    if (e->G_h->mix_flag) with_mix = 16;
-  }
-  LAUNCH(e, 0, k_sweep, 7 | with_sync | with_mix, ftCoal, ftMig, e->G_h->mix_c, e->G_h->mix_lnc);
-  if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
-  if ((rc = reduce_stats(e))) return rc;
+  int rc, with_sync;
+  if ((rc = sweep_launch(e, 7, ftCoal, ftMig, with_sync))) return rc;
   return run_stage(e, GS_SWEEP_DONE, with_sync, iteration);
 }
 static int part_lrate(gph_engine *e, int32_t iteration, const double *lr_alpha_finetune, int64_t *lr_accepted, double *lr_rateVar)
@@ -2155,12 +1734,9 @@ static int part_tau(gph_engine *e, int32_t iteration, bool first_proposed)
   int rc;
   const GphGlobal &Gh = *e->G_h;
   const int K = Gh.K, Kc = Gh.Kc;
-  const bool no_fuse = e->no_fuse;
   for (int ap = Kc; ap < K; ++ap) {
     if ((ap > Kc || !first_proposed) && (rc = run_stage(e, GS_TAU_PROPOSE, ap, iteration))) return rc;
-    if (no_fuse && (rc = finish_owed(e))) return rc;
-    { const int fuse = e->fin_owed; e->fin_owed = false; LAUNCH(e, 1, k_tau_eval, fuse); }
-    if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
+    if ((rc = evaluate_fused(e, 1, k_tau_eval))) return rc;
     if ((rc = run_stage(e, GS_TAU_DECIDE, ap, iteration))) return rc;
     e->fin_owed = true;
   }
@@ -2170,13 +1746,10 @@ static int part_sage(gph_engine *e, int32_t iteration)
 {
   int rc;
   const GphGlobal &Gh = *e->G_h;
-  const bool no_fuse = e->no_fuse;
   for (int pop = 0; pop < Gh.Kc; ++pop) {
     if (!Gh.updateSampleAge[pop]) continue;
     if ((rc = run_stage(e, GS_SAGE_PROPOSE, pop, iteration))) return rc;
-    if (no_fuse && (rc = finish_owed(e))) return rc;
-    { const int fuse = e->fin_owed; e->fin_owed = false; LAUNCH(e, 1, k_tau_eval, fuse); }
-    if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
+    if ((rc = evaluate_fused(e, 1, k_tau_eval))) return rc;
     if ((rc = run_stage(e, GS_SAGE_DECIDE, pop, iteration))) return rc;
     e->fin_owed = true;
   }
@@ -2186,15 +1759,12 @@ static int part_mix(gph_engine *e, int32_t iteration)
 {
   int rc;
   const GphGlobal &Gh = *e->G_h;
-  const bool no_fuse = e->no_fuse;
   if ((rc = run_stage(e, GS_MIX_PROPOSE, 0, iteration))) return rc;
   if (Gh.ftMixing > 0.0) {
-    if (no_fuse && (rc = finish_owed(e))) return rc;
-    { const int fuse = e->fin_owed; e->fin_owed = false; LAUNCH(e, 2, k_mix_eval, fuse); }
-    if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
+    if ((rc = evaluate_fused(e, 2, k_mix_eval))) return rc;
     if ((rc = run_stage(e, GS_MIX_DECIDE, 0, iteration))) return rc;
-    if (no_fuse) { LAUNCH(e, 7, k_mix_finish, 0); }
-    else e->mix_owed = true;        /* at the head of the next sweep kernel (part_sweep), or mix_finish_owed() */
+    e->mix_owed = true;        /* at the head of the next sweep kernel (sweep_launch), or mix_finish_owed() -- GPH_NO_FUSE: now */
+    if (e->no_fuse) return mix_finish_owed(e);
   }
   return 0;
 }
@@ -2202,7 +1772,7 @@ static int part_mix(gph_engine *e, int32_t iteration)
 static int part_refresh(gph_engine *e, int32_t iteration)
 {
   int rc;
-  LAUNCH(e, 8, k_sync, 1);
+  if ((rc = launch_loci(e, 8, k_sync, 1))) return rc;
   if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
   return run_stage(e, GS_REFRESH_DONE, 1, iteration);
 }
@@ -2211,7 +1781,7 @@ static int part_check(gph_engine *e, int32_t iteration)
 {
   int rc;
   if ((rc = flush_sync(e, false))) return rc;
-  LAUNCH(e, 4, k_check, 0);
+  if ((rc = launch_loci(e, 4, k_check, 0))) return rc;
   if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
   if ((rc = reduce_stats(e))) return rc;
   return run_stage(e, GS_CHECK_DONE, 0, iteration);
@@ -2232,7 +1802,7 @@ int gph_engine_iteration_(gph_engine *e, int32_t iteration, const double *lr_alp
   SETDEV(e);
   int rc;
   GphGlobal &Gh = *e->G_h;    /* settings only: the running state is on the device until finish_sync */
-  PUSH_IF_DIRTY(e);
+  if ((rc = push_if_dirty(e))) return rc;
   if ((rc = part_sweep(e, iteration, Gh.ftCoalTime, Gh.ftMigTime))) return rc;
   if (lr_alpha_finetune && (rc = part_lrate(e, iteration, lr_alpha_finetune, lr_accepted, lr_rateVar))) return rc;
   if ((rc = run_stage(e, GS_THETA, 0, iteration))) return rc;
@@ -2265,7 +1835,7 @@ int gph_engine_part_(gph_engine *e, int32_t part, int32_t iteration, const doubl
   SETDEV(e);
   int rc = 0;
   GphGlobal &Gh = *e->G_h;
-  PUSH_IF_DIRTY(e);
+  if ((rc = push_if_dirty(e))) return rc;
   if (part != GPH_PART_SWEEP && part != GPH_PART_SYNC) { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
   if (part == GPH_PART_LRATE || part == GPH_PART_TAU || part == GPH_PART_SAGE || part == GPH_PART_MIX) {
     int rcs = flush_sync(e, true);    /* a deferred synchronizeEvents pass must not be overtaken by a kernel that edits the pages */
@@ -2281,7 +1851,7 @@ int gph_engine_part_(gph_engine *e, int32_t part, int32_t iteration, const doubl
   case GPH_PART_MIX: rc = part_mix(e, iteration); break;
   case GPH_PART_SYNC: e->sync_pending = true; break;
   case GPH_PART_REFRESH: e->sync_pending = false; rc = part_refresh(e, iteration); break;
-  case GPH_PART_CHECK: Gh.nrec = 0; e->G_dirty = true; PUSH_IF_DIRTY(e); rc = part_check(e, iteration); break;
+  case GPH_PART_CHECK: Gh.nrec = 0; e->G_dirty = true; rc = push_if_dirty(e); if (!rc) rc = part_check(e, iteration); break;
   default: return GPH_EARG;
   }
   if (rc) return rc;
@@ -2327,20 +1897,12 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
     A.taufactor1 = isRoot ? A.taufactor0 : (taunew - taub1) / (tauold - taub1);
     e->G_dirty = true;
   }
-  PUSH_IF_DIRTY(e);
+  { int rcp = push_if_dirty(e); if (rcp) return rcp; }
   double *d_out = nullptr;
   const size_t bytes = sizeof(double) * (size_t)stride * e->L;
   if (dev_alloc((void **)&d_out, bytes)) return GPH_EHIP;
-  int rc = 0;
-#ifdef GPH_HOSTEMU
-  memset(d_out, 0, bytes);
-#else
-  if (hipMemsetAsync(d_out, 0, bytes, e->stream) != hipSuccess) rc = GPH_EHIP;
-#endif
-  if (!rc) {
-    auto launch = [&]() -> int { LAUNCH(e, 12, k_unit, (int)op, (int)arg, d_out, (int)stride); return 0; };
-    rc = launch();
-  }
+  int rc = acc_zero(e, d_out, bytes);
+  if (!rc) rc = launch_loci(e, 12, k_unit, op, arg, d_out, stride);
   if (!rc) rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = run_stage_now(e, GS_COUNT_ONLY, 12);
   if (!rc) rc = d2h(e, out, d_out, bytes);
@@ -2400,16 +1962,7 @@ int gph_engine_debug_oob(gph_engine *e, int32_t *where, int32_t *checked)
   SETDEV(e);
   if (e->initialized) { int rcs = flush_sync(e, true); if (!rcs) rcs = finish_sync(e); if (rcs) return rcs; }
   /* read and clear: the word belongs to the library (every engine of the process), a report must not be seen twice */
-#ifdef GPH_HOSTEMU
-  *where = gph_oob_word;
-  gph_oob_word = 0;
-#else
-  int w = 0, z = 0;
-  HIPCHK(hipMemcpyFromSymbol(&w, HIP_SYMBOL(gph_oob_word), sizeof(int)));
-  if (w != 0) HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(gph_oob_word), &z, sizeof(int)));
-  *where = w;
-#endif
-  return 0;
+  return oob_take(where);
 #endif
 }
 
@@ -2465,32 +2018,25 @@ int gph_engine_dump_loci(gph_engine *e, const char *path, int32_t withCond, int3
 enum { SETTLE_PAGES, SETTLE_PAGES_AND_AGES, SETTLE_CHAIN };
 static int sample_settle(gph_engine *e, int level)
 {
-  if (level == SETTLE_CHAIN) PUSH_IF_DIRTY(e);
+  if (level == SETTLE_CHAIN) { int rcp = push_if_dirty(e); if (rcp) return rcp; }
   if (level != SETTLE_PAGES) { int rcw = finish_owed(e); if (rcw) return rcw; }
   if (e->mix_owed && e->mirror_current && !e->G_h->mix_flag) e->mix_owed = false;
   return mix_finish_owed(e);
 }
 
 // the launch bookkeeping of one sample, k launches of timing class cls queued on the engine's stream between the two:
-// what is pending on the stream goes first, HIP events bracket the launches (tms: their slot).  The host form only counts
+// what is pending on the stream goes first, HIP events bracket the launches (tms: their slot); what is counted: gph_backend.h
 static int sample_begin(gph_engine *e, int cls, int &tms)
 {
   tms = -1;
-#ifndef GPH_HOSTEMU
   { int rcf = flush_pending(e); if (rcf) return rcf; }
   tms = tm_begin(e, cls);
-#endif
-  (void)e; (void)cls;
   return 0;
 }
 static void sample_end(gph_engine *e, int cls, int k, int tms)
 {
-#ifndef GPH_HOSTEMU
   tm_end(e, tms);
-  e->n_launches += k;
-  e->last_which = cls;
-#endif
-  (void)k; (void)tms;
+  flat_launched(e, cls, k);
   e->cls_launches[cls] += 1;
 }
 
@@ -2523,15 +2069,8 @@ static int parts_alloc(gph_engine *e, SmParts &p, int32_t rd, int32_t default_ch
 // the partial rows of a sample into its row, in chunk order (one launch)
 static int parts_fold(gph_engine *e, const SmParts &p, int32_t iteration, double *row)
 {
-#ifdef GPH_HOSTEMU
-  (void)e;
-  for (int c = 0; c < p.rd; c++) gph_fold_column(p.d_part, p.nchunks, p.rd, c, (double)iteration, row);
-#else
-  hipLaunchKernelGGL(k_rows_fold, dim3((unsigned)((p.rd + GPH_FOLD_THREADS - 1) / GPH_FOLD_THREADS)), dim3(GPH_FOLD_THREADS), 0, e->stream,
-                     (const double *)p.d_part, p.nchunks, p.rd, (double)iteration, row);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return launch_grid(e, GphGrid{(p.rd + GPH_FOLD_THREADS - 1) / GPH_FOLD_THREADS, 1}, GPH_FOLD_THREADS, 0, k_rows_fold,
+                     p.d_part, p.nchunks, p.rd, iteration, row);
 }
 // a chunked sampler's two buffers: partial rows for its L slots, `capacity` rows of rd doubles
 static int chunked_alloc(gph_engine *e, SmParts &p, SmRows &b, int32_t rd, int32_t default_chunk, int32_t capacity)
@@ -2585,14 +2124,8 @@ int gph_engine_locus_summary_sample(gph_engine *e)
   const int L = (int)e->L, ncol = e->ls.ncol, var = e->var_rates;
   int tms;
   { int rcb = sample_begin(e, 13, tms); if (rcb) return rcb; }
-#ifdef GPH_HOSTEMU
-  for (int j = 0; j < L; j++)
-    locus_summary_slot(e->dev.pages + (size_t)j * e->lay.page_bytes, e->lay, e->ls.d + j, (size_t)L, ncol, first, var);
-#else
-  hipLaunchKernelGGL(k_locus_summary, dim3((unsigned)((L + GPH_LS_THREADS - 1) / GPH_LS_THREADS)), dim3(GPH_LS_THREADS), 0, e->stream,
-                     e->lay, (const char *)e->dev.pages, e->ls.d, L, ncol, first, var);
-  HIPCHK(hipGetLastError());
-#endif
+  { int rcl = launch_grid(e, GphGrid{(L + GPH_LS_THREADS - 1) / GPH_LS_THREADS, 1}, GPH_LS_THREADS, 0, k_locus_summary,
+                          e->lay, e->dev.pages, e->ls.d, L, ncol, first, var); if (rcl) return rcl; }
   sample_end(e, 13, 1, tms);
   e->ls.samples++;
   return 0;
@@ -2661,16 +2194,8 @@ int gph_engine_coal_stats_sample(gph_engine *e, int32_t iteration)
   const int ntiles = (gph_cs_pairs(n) + bd - 1) / bd;
   int tms;
   { int rcb = sample_begin(e, 14, tms); if (rcb) return rcb; }
-#ifdef GPH_HOSTEMU
-  (void)K; (void)B;
-  std::vector<char> lds;
-  for (int ch = 0; ch < p.nchunks; ch++)
-    for (int t = 0; t < ntiles; t++) coal_stats_workgroup(e->lay, (const char *)e->dev.pages, p.d_part, L, p.chunk, bd, ch, t, lds);
-#else
-  hipLaunchKernelGGL(k_coal_stats, dim3((unsigned)p.nchunks, (unsigned)ntiles), dim3((unsigned)bd), gph_cs_lds_bytes(n, K, B, bd), e->stream,
-                     e->lay, (const char *)e->dev.pages, p.d_part, L, p.chunk);
-  HIPCHK(hipGetLastError());
-#endif
+  { int rcl = launch_grid(e, GphGrid{p.nchunks, ntiles}, bd, gph_cs_lds_bytes(n, K, B, bd), k_coal_stats,
+                          e->lay, e->dev.pages, p.d_part, L, p.chunk); if (rcl) return rcl; }
   { int rcf = parts_fold(e, p, iteration, (double *)rows_next(e->cs.rows)); if (rcf) return rcf; }
   sample_end(e, 14, 2, tms);
   e->cs.rows.fill++;
@@ -2757,15 +2282,8 @@ int gph_engine_time_slices_sample(gph_engine *e, int32_t iteration)
   const GphTsShape &h = e->ts.shape;
   int tms;
   { int rcb = sample_begin(e, 15, tms); if (rcb) return rcb; }
-#ifdef GPH_HOSTEMU
-  std::vector<char> lds;
-  for (int ch = 0; ch < p.nchunks; ch++)
-    for (int t = 0; t < h.ntiles; t++) time_slices_workgroup(e->lay, h, e->G_h, (const char *)e->dev.pages, p.d_part, L, p.chunk, p.rd, vsync, ch, t, lds);
-#else
-  hipLaunchKernelGGL(k_time_slices, dim3((unsigned)p.nchunks, (unsigned)h.ntiles), dim3((unsigned)h.bd), (size_t)h.lds_bytes, e->stream,
-                     e->lay, h, (const GphGlobal *)e->G_d, (const char *)e->dev.pages, p.d_part, L, p.chunk, p.rd, vsync);
-  HIPCHK(hipGetLastError());
-#endif
+  { int rcl = launch_grid(e, GphGrid{p.nchunks, h.ntiles}, h.bd, (size_t)h.lds_bytes, k_time_slices,
+                          e->lay, h, e->G_d, e->dev.pages, p.d_part, L, p.chunk, p.rd, vsync); if (rcl) return rcl; }
   { int rcf = parts_fold(e, p, iteration, (double *)rows_next(e->ts.rows)); if (rcf) return rcf; }
   sample_end(e, 15, 2, tms);
   e->ts.rows.fill++;
@@ -2851,16 +2369,9 @@ int gph_engine_ancestry_sample(gph_engine *e, int32_t iteration)
   const size_t row_bytes = sizeof(uint32_t) * (size_t)e->an.rows.n;
   int tms;
   { int rcb = sample_begin(e, 16, tms); if (rcb) return rcb; }
-#ifdef GPH_HOSTEMU
-  memset(row, 0, row_bytes);
-  std::vector<char> lds;
-  for (int w = 0; w < groups; w++) ancestry_workgroup(e->lay, h, (const char *)e->dev.pages, e->an.d_acc, row, L, w, lds);
-#else
-  HIPCHK(hipMemsetAsync(row, 0, row_bytes, e->stream));
-  hipLaunchKernelGGL(k_ancestry, dim3((unsigned)groups), dim3((unsigned)h.bd), (size_t)h.lds_bytes, e->stream,
-                     e->lay, h, (const char *)e->dev.pages, e->an.d_acc, row, L);
-  HIPCHK(hipGetLastError());
-#endif
+  { int rcl = acc_zero(e, row, row_bytes);
+    if (!rcl) rcl = launch_grid(e, GphGrid{groups, 1}, h.bd, (size_t)h.lds_bytes, k_ancestry, e->lay, h, e->dev.pages, e->an.d_acc, row, L);
+    if (rcl) return rcl; }
   sample_end(e, 16, 1, tms);
   e->an.iters.push_back(iteration);
   e->an.rows.fill++;
@@ -2986,13 +2497,8 @@ int gph_engine_gene_trees_sample(gph_engine *e, int32_t iteration)
     char *row = (char *)rows_next(e->gt.rows);
     int tms;
     { int rcb = sample_begin(e, 17, tms); if (rcb) return rcb; }
-#ifdef GPH_HOSTEMU
-    for (int w = 0; w < groups; w++) gene_trees_workgroup(e->lay, h, (const char *)e->dev.pages, e->gt.d_sel, nsel, L, row, w);
-#else
-    hipLaunchKernelGGL(k_gene_trees, dim3((unsigned)groups), dim3(GPH_GT_THREADS), 0, e->stream,
-                       e->lay, h, (const char *)e->dev.pages, (const int32_t *)e->gt.d_sel, nsel, L, row);
-    HIPCHK(hipGetLastError());
-#endif
+    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_GT_THREADS, 0, k_gene_trees, e->lay, h, e->dev.pages, e->gt.d_sel, nsel, L, row);
+      if (rcl) return rcl; }
     sample_end(e, 17, 1, tms);
   }
   e->gt.iters.push_back(iteration);

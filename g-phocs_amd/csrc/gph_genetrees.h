@@ -77,9 +77,9 @@ GPH_SM_FN bool gph_gt_unit(const GphLayout &y, const GphGtShape &h, const int32_
 
 #ifdef GPH_HOSTEMU
 // host emulation: workgroup w with its lanes one after the other
-static inline void gene_trees_workgroup(const GphLayout &y, const GphGtShape &h, const char *pages, const int32_t *sel_slot, int nsel, int L,
-                                        char *row, int w)
+static inline void k_gene_trees(GphBlk blk, GphLayout y, GphGtShape h, const char *pages, const int32_t *sel_slot, int nsel, int L, char *row)
 {
+  const int w = blk.x;
   for (int tid = 0; tid < GPH_GT_THREADS; tid++)
     for (int t = tid; t < h.G * h.units; t += GPH_GT_THREADS) {
       size_t src, dst;

@@ -33,6 +33,11 @@ __global__ void __launch_bounds__(GPH_FOLD_THREADS) k_rows_fold(const double *pa
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < rd) gph_fold_column(part, nchunks, rd, c, iteration, row);
 }
+#else
+static inline void k_rows_fold(GphBlk blk, const double *part, int nchunks, int rd, double iteration, double *row)
+{
+  for (int c = blk.x * blk.dim; c < (blk.x + 1) * blk.dim && c < rd; c++) gph_fold_column(part, nchunks, rd, c, iteration, row);
+}
 #endif
 
 // ---- the packed image.  The part of a page a kernel needs, copied into LDS with 128-bit loads, consecutive lanes on

@@ -58,13 +58,19 @@ void locus_summary_slot(const char *pg, const GphLayout &y, double *a, size_t L,
   if (var) moment(LS_FIXED + 2 * B + K, fs[FS_MUTRATE]);
 }
 
-#ifndef GPH_HOSTEMU
 #define GPH_LS_THREADS 256
+#ifndef GPH_HOSTEMU
 __global__ void __launch_bounds__(GPH_LS_THREADS) k_locus_summary(GphLayout y, const char *pages, double *acc, int L, int ncol, int first, int var)
 {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= L) return;
   locus_summary_slot(pages + (size_t)j * y.page_bytes, y, acc + j, (size_t)L, ncol, first, var);
+}
+#else
+static inline void k_locus_summary(GphBlk blk, GphLayout y, const char *pages, double *acc, int L, int ncol, int first, int var)
+{
+  for (int j = blk.x * blk.dim; j < (blk.x + 1) * blk.dim && j < L; j++)
+    locus_summary_slot(pages + (size_t)j * y.page_bytes, y, acc + j, (size_t)L, ncol, first, var);
 }
 #endif
 

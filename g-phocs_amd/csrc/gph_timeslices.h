@@ -230,14 +230,14 @@ GPH_SM_FN void gph_ts_chunk_out(const GphTsLds &s, const GphLayout &y, const Gph
 }
 
 #ifdef GPH_HOSTEMU
-// host emulation: workgroup (ch, tile) with its lanes one after the other, phase by phase as the barriers order them
-static inline void time_slices_workgroup(const GphLayout &y, const GphTsShape &h, const GphGlobal *G, const char *pages, double *part, int L, int chunk,
-                                         int rd, int vsync, int ch, int tile, std::vector<char> &lds)
+// host emulation: workgroup (ch, tile) = block (x, y) with its lanes one after the other, phase by phase as the barriers
+// order them; the launch hands it a zeroed buffer for its dynamic LDS
+static inline void k_time_slices(GphBlk blk, GphLayout y, GphTsShape h, const GphGlobal *G, const char *pages, double *part, int L, int chunk,
+                                 int rd, int vsync)
 {
-  const int K = y.K, B = y.B, W = K + B;
-  lds.assign((size_t)h.lds_bytes + 16, 0);
+  const int K = y.K, B = y.B, W = K + B, ch = blk.x, tile = blk.y;
   GphTsLds s;
-  gph_ts_carve(lds.data(), K, B, h, s);
+  gph_ts_carve(blk.lds, K, B, h, s);
   for (int q = 0; q < 3 * K + 3 * B; q++) gph_ts_load_model(s, G->model, K, B, q);
   const int j0 = ch * chunk, j1 = j0 + chunk < L ? j0 + chunk : L, upl = h.img.bytes / 16;
   for (int jg = j0; jg < j1; jg += h.G) {

@@ -199,3 +199,80 @@ def reinit_after_accepted_mixing(G, lib, pack_path, tmp_path, max_iters=200, mor
     assert open(sa, "rb").read() == open(sb, "rb").read(), "per-locus state differs after re-initialisation"
     ra, rb = open(ta).read(), open(tb).read()
     assert ra == rb and len(ra.splitlines()) > more, "records differ after re-initialisation"
+
+
+def stepwise_entry_points(G, load, golden, tmp_path):
+    """The stepwise entry points of the C ABI (one reference proposal function each), pinned without a reference.
+    load(pack) -> the library for a pack.
+    (a) m3, j1: three sweeps through gph_engine_genealogy_sweep on one engine and through gph_mcmc_update_gb on another
+        give the same four accept counts per sweep and the same per-locus state, conditionals included.
+    (b) g2 (ancestral populations 3 and 4) and g1 (population 5: no band touches it or a son of it): a tau proposal that
+        is evaluated and reverted, and a mixing proposal that is only evaluated, leave the per-locus state as it was;
+        the chain runs on."""
+    import ctypes as C
+    import os
+
+    class TauArgs(C.Structure):
+        _fields_ = [("ap", C.c_int32), ("son0", C.c_int32), ("son1", C.c_int32), ("isRoot", C.c_int32), ("num_aff", C.c_int32),
+                    ("mode", C.c_int32), ("tauold", C.c_double), ("taunew", C.c_double), ("taub0", C.c_double), ("taub1", C.c_double),
+                    ("taufactor0", C.c_double), ("taufactor1", C.c_double), ("aff_bands", C.c_int32 * 200),
+                    ("start_or_end", C.c_int32 * 200), ("new_band_ages", C.c_double * 200)]
+
+    class TauResult(C.Structure):
+        _fields_ = [("ntj0", C.c_int64), ("ntj1", C.c_int64), ("first_conflict_locus", C.c_int64), ("genDelta", C.c_double),
+                    ("dataDelta", C.c_double)]
+
+    def locus_lines(s, lib, tag):
+        path = str(tmp_path / tag)
+        assert lib.gph_engine_dump_loci(s.engine, path.encode(), 1, 0) == 0
+        lines = [ln for ln in open(path) if ln.split(" ", 1)[0] in ("LOCUS", "R", "N", "C", "K", "M", "S")]
+        assert len(lines) > 4 * s.pack.L
+        return lines
+
+    for name in ("m3", "j1"):
+        pk = G.Pack.load(os.path.join(golden, name + ".gpk"))
+        lib = load(pk)
+        a, b = G.Sampler(pk, lib=lib), G.Sampler(pk, lib=lib)
+        a.initialize()
+        b.initialize()
+        for it in range(3):
+            out = G.GphSweepResult()
+            assert lib.gph_engine_genealogy_sweep(a.engine, 7, pk.ftCoalTime, pk.ftMigTime, C.byref(out)) == 0
+            acc, mig = (C.c_int64 * 3)(), C.c_int64()
+            assert lib.gph_mcmc_update_gb(b.mcmc, C.c_int32(it), C.c_double(pk.ftCoalTime), C.c_double(pk.ftMigTime), acc, C.byref(mig)) == 0
+            got = (out.accepted_internal, out.accepted_mignode, out.accepted_spr, out.total_mig_nodes)
+            print(f"stepwise {name} sweep {it}: accept counts {got}")
+            assert got == (acc[0], acc[1], acc[2], mig.value), (name, it)
+            assert out.accepted_internal + out.accepted_spr > 0, (name, it)
+        assert locus_lines(a, lib, name + ".a") == locus_lines(b, lib, name + ".b"), name
+        a.close()
+        b.close()
+
+    for name, pops in (("g2", (3, 4)), ("g1", (5,))):
+        pk = G.Pack.load(os.path.join(golden, name + ".gpk"))
+        lib = load(pk)
+        s = G.Sampler(pk, lib=lib)
+        s.initialize()
+        for it in range(5):
+            s.iteration(it)
+        before = locus_lines(s, lib, name + ".0")
+        age = s.state()["popAge"]
+        for ap in pops:
+            assert ap >= pk.Kc
+            s0, s1, root = int(pk.popSon0[ap]), int(pk.popSon1[ap]), ap == pk.rootPop
+            tauold, taub0 = float(age[ap]), float(max(age[s0], age[s1]))
+            taub1 = 1e300 if root else float(age[int(pk.popFather[ap])])
+            taunew = tauold + 0.01 * (tauold - taub0)
+            assert taub0 < tauold < taunew < taub1
+            args = TauArgs(ap=ap, son0=s0, son1=s1, isRoot=int(root), num_aff=0, mode=0, tauold=tauold, taunew=taunew, taub0=taub0, taub1=taub1,
+                           taufactor0=(taunew - taub0) / (tauold - taub0), taufactor1=1.0 if root else (taub1 - taunew) / (taub1 - tauold))
+            res = TauResult()
+            assert lib.gph_engine_tau_evaluate(s.engine, C.byref(args), C.byref(res)) == 0
+            assert res.first_conflict_locus == -1, (name, ap)
+            assert lib.gph_engine_tau_revert(s.engine, -1) == 0
+            assert locus_lines(s, lib, f"{name}.{ap}") == before, (name, ap)
+        delta = C.c_double()
+        assert lib.gph_engine_mixing_evaluate(s.engine, 1.01, C.byref(delta)) == 0
+        assert locus_lines(s, lib, name + ".mix") == before, name
+        s.iteration(5)
+        s.close()

@@ -808,6 +808,13 @@ def test_reinitialise_drops_an_owed_mixing_commit(G, tmp_path):
     reinit_after_accepted_mixing(G, G.load_library(dims=(pk.n, pk.K, pk.B)), os.path.join(GOLDEN, "m3.gpk"), tmp_path)
 
 
+def test_stepwise_entry_points(G, tmp_path):
+    """gph_engine_genealogy_sweep against gph_mcmc_update_gb; tau evaluate + revert and mixing evaluate leave the loci as they
+    were (parity_util.stepwise_entry_points), on the device library of each golden's dimensions"""
+    from parity_util import stepwise_entry_points
+    stepwise_entry_points(G, lambda pk: G.load_library(dims=(pk.n, pk.K, pk.B)), GOLDEN, tmp_path)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("victim,second", [(11, 14), (13, 15)])
 def test_fatal_error_names_the_locus_and_prints_its_genealogy(G, tmp_path, capfd, victim, second):

@@ -273,6 +273,15 @@ def test_reinitialise_drops_an_owed_mixing_commit(hostemu, tmp_path):
     reinit_after_accepted_mixing(G, lib, os.path.join(GOLDEN, "m3.gpk"), tmp_path)
 
 
+def test_stepwise_entry_points(hostemu, tmp_path):
+    """gph_engine_genealogy_sweep against gph_mcmc_update_gb; tau evaluate + revert and mixing evaluate leave the loci as they
+    were (parity_util.stepwise_entry_points), host-emulation build"""
+    from parity_util import stepwise_entry_points
+    import gphocs_amd as G
+    _, lib = hostemu
+    stepwise_entry_points(G, lambda pk: lib, GOLDEN, tmp_path)
+
+
 @pytest.mark.parametrize("config,loci,iters,mut", [(12, 40, 12, 3.0), (13, 12, 8, 2.0), (14, 6, 6, 0.5)])
 def test_big_build_against_live_oracle(oracle_cli, tmp_path, config, loci, iters, mut):
     """the reference's own capacities on the host build of the engine sources (200 leaves / 39 populations / 100 bands) against
