@@ -42,8 +42,7 @@ HIPCC_TUNING_SPILLING = HIPCC_TUNING[:4]
 HIPCC_FLAGS = HIPCC_BASE + HIPCC_TUNING
 HIPCC_LIBS = ["-ldl", "-lrt"]        # after the sources: an --as-needed linker drops libraries named before their users
 # The tuning switches above are backend options of THIS compiler (uniformity analysis decides what
-# -structurizecfg-skip-uniform-regions leaves alone; the batched generator's inline asm relies on nothing else in
-# the translation unit using M0): the version they were validated with is recorded, build() warns when hipcc
+# -structurizecfg-skip-uniform-regions leaves alone): the version they were validated with is recorded, build() warns when hipcc
 # differs, and a control build WITHOUT them (`libgphocs_hip_plain.so`) runs the golden parity tests next to the
 # tuned one (tests/test_gpu_parity.py::test_plain_build_parity), so a compiler change that breaks an assumption
 # shows as a difference between the two.

@@ -22,6 +22,8 @@ struct GphGrid { int x, y; };
 //   launch_wave                   not added to n_launches                not added to n_launches
 //   sample_end (k launches)       n_launches += k, sets last_which       neither
 //   apply_list (flat_launched)    n_launches += 1                        nothing
+//   rng_ahead_launch / _side      n_launches += 1, cls_launches[18] += 1 n_launches += 1, cls_launches[18] += 1
+//                                 (last_which is left alone: the sweep that follows sets it)
 //   cls_launches[cls]             += 1 per call                          += 1 per call
 //
 // launch_loci and launch_wave set last_which in both builds; launch_grid itself counts nothing (its callers do, above);
@@ -51,6 +53,11 @@ static bool resident(const gph_engine *) { return false; }
 static int flush_pending(gph_engine *) { return 0; }
 static int stage_defer(gph_engine *, int, int, int, bool &queued) { queued = false; return 0; }
 static void flat_launched(gph_engine *, int, int) {}     /* k flat launches of class cls (-1: none) went out: not counted here */
+static void dev_clear_error() {}
+// placement B of k_rng_ahead needs resident mode: never here
+static int rng_ahead_side(gph_engine *, GphGrid) { return 0; }
+static int rng_ahead_wait(gph_engine *) { return 0; }
+static void rng_ahead_drain(gph_engine *) {}
 
 static int reduce_local(gph_engine *e, int sec, int ncols)
 {
@@ -163,6 +170,10 @@ struct gph_engine : gph_engine_state {
   hipStream_t stream_wide = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool side_stream = true;            // GPH_SIDE_STREAM=0: the groups one after the other on the engine's stream (A/B, tests)
+  // k_rng_ahead for the NEXT sweep (placement B): on a stream of its own behind the sweep kernel, next to the tau / mixing
+  // kernels; the next sweep kernel waits for ev_ra_done
+  hipStream_t stream_ra = nullptr;
+  hipEvent_t ev_ra_go = nullptr, ev_ra_done = nullptr;
   struct Tm { hipEvent_t a, b; int which; };
   std::vector<Tm> tm;                // event pairs of the launches since the last synchronisation
   size_t tm_used = 0;
@@ -170,6 +181,9 @@ struct gph_engine : gph_engine_state {
 
 static int dev_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 16) == hipSuccess ? 0 : GPH_EHIP; }
 static void dev_free(void *p) { if (p) (void)hipFree(p); }
+// a failed allocation that the caller survives: the runtime keeps its last error until somebody takes it, and the check
+// after the next launch (launch_on) would report it
+static void dev_clear_error() { (void)hipGetLastError(); }
 // elapsed times of the launches bracketed since the last synchronisation (the stream is idle: every event is complete)
 static int collect_times(gph_engine *e)
 {
@@ -250,7 +264,6 @@ static bool resident(const gph_engine *e)
 // k flat launches of class cls (-1: none, apply_list) went out
 static void flat_launched(gph_engine *e, int cls, int k) { e->n_launches += k; if (cls >= 0) e->last_which = cls; }
 
-static void launch_pre(gph_engine *e) { GPH_KA_MODEL(e->ka, e); e->ka.lay = e->lay; e->ka.G = e->G_d; }
 template <class... P, class... A>
 static int launch_on(hipStream_t stream, GphGrid grid, int block, size_t lds_bytes, void (*kernel)(P...), A &&...args)
 {
@@ -258,6 +271,25 @@ static int launch_on(hipStream_t stream, GphGrid grid, int block, size_t lds_byt
   HIPCHK(hipGetLastError());
   return 0;
 }
+static void launch_pre(gph_engine *e) { GPH_KA_MODEL(e->ka, e); e->ka.lay = e->lay; e->ka.G = e->G_d; }
+// k_rng_ahead for the sweep AFTER the one just launched on the engine's stream: forked behind it onto its own stream
+static int rng_ahead_side(gph_engine *e, GphGrid grid)
+{
+  if (!e->stream_ra) {
+    if (hipStreamCreateWithFlags(&e->stream_ra, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_ra_go, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_ra_done, hipEventDisableTiming) != hipSuccess) return GPH_EHIP;
+  }
+  HIPCHK(hipEventRecord(e->ev_ra_go, e->stream));
+  HIPCHK(hipStreamWaitEvent(e->stream_ra, e->ev_ra_go, 0));
+  { int rcl = launch_on(e->stream_ra, grid, GPH_WAVE, 0, k_rng_ahead, e->ka, e->dev); if (rcl) return rcl; }
+  HIPCHK(hipEventRecord(e->ev_ra_done, e->stream_ra));
+  return 0;
+}
+// the engine's stream goes on when that pass has finished
+static int rng_ahead_wait(gph_engine *e) { HIPCHK(hipStreamWaitEvent(e->stream, e->ev_ra_done, 0)); return 0; }
+// nothing of it in flight any more (before its buffers or the pages are released)
+static void rng_ahead_drain(gph_engine *e) { if (e->stream_ra) (void)hipStreamSynchronize(e->stream_ra); }
 // a flat kernel on the engine's stream; what is pending and what is counted is the caller's business (sample_begin / _end,
 // apply_list, the reductions below)
 template <class... P, class... A>
@@ -425,6 +457,9 @@ static void backend_close(gph_engine *e)
   if (e->h_red) (void)hipHostFree(e->h_red);
   if (e->G_h) (void)hipHostFree(e->G_h);
   for (auto &t : e->tm) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
+  if (e->ev_ra_go) (void)hipEventDestroy(e->ev_ra_go);
+  if (e->ev_ra_done) (void)hipEventDestroy(e->ev_ra_done);
+  if (e->stream_ra) (void)hipStreamDestroy(e->stream_ra);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   if (e->stream_wide) (void)hipStreamDestroy(e->stream_wide);

@@ -379,8 +379,96 @@ __global__ void k_debug_math(GphKargs KA, const double *x, const double *y, int 
 }
 #endif
 
+// ---------------------------------------------------------------- the sweep's uniforms, generated ahead of it
+// One lane per locus slot: the three Wichmann-Hill recurrences of the slot's stream from the generator state in its page
+// (read only) and the draws exactly as l_rndu(GphRng &) forms them -- serial per locus, 64 loci per instruction here, where
+// k_sweep spent 5.7 % of its dependent instruction stream on them.  Per slot: the first n_ahead = min(M, roundup64(k_prev + 64))
+// draws (k_prev: what the locus consumed in its previous sweep), the state after every C of them and after the last one.
+// The consumer is GphRngA (gph_locus.h), which goes on by itself where the draws end.
+GPH_HD int rng_ahead_count(int kprev, int M)
+{
+  int n = (kprev + 64 + 63) & ~63;
+  return n < 0 ? 0 : n > M ? M : n;
+}
+#ifdef GPH_HOSTEMU
+static void k_rng_ahead(GphBlk b, GphKargs KA, GphDev D)
+{
+  const int cs = D.ra_cshift, nck = (D.ra_M >> cs) + 1;
+  for (int slot = b.x * b.dim; slot < (b.x + 1) * b.dim && slot < D.L; slot++) {
+    const int32_t *is = (const int32_t *)(D.pages + (size_t)slot * KA.lay.page_bytes + KA.lay.o_iscal);
+    uint32_t x = (uint32_t)is[IS_RX], y = (uint32_t)is[IS_RY], z = (uint32_t)is[IS_RZ];
+    const int n = rng_ahead_count(D.ra_kprev[slot], D.ra_M);
+    for (int d = 0; d <= n; d++) {
+      if ((d & ((1 << cs) - 1)) == 0) {
+        uint32_t *c = D.ra_ckpt + 4 * ((size_t)GPH_IX(d >> cs, nck) * D.L + slot);
+        c[0] = x; c[1] = y; c[2] = z; c[3] = 0;
+      }
+      if (d == n) break;
+      GPH_RNG_STEP(x, y, z);
+      const double r = x / 30269.0 + y / 30307.0 + z / 30323.0;
+      D.ra_draws[(size_t)slot * D.ra_M + GPH_IX(d, D.ra_M)] = r - (int)r;
+    }
+    uint32_t *t = D.ra_tail + 4 * (size_t)slot;
+    t[0] = x; t[1] = y; t[2] = z; t[3] = (uint32_t)n;
+  }
+}
+#else
+// A tile of 64 loci x 16 draws goes through LDS so that a store instruction writes whole 128-byte lines: 16 lanes per
+// locus, 4 loci per instruction (a lane-strided store would be 64 separate 8-byte transactions).  The checkpoints and the
+// tail are laid out with the slot as the fastest index: lane-consecutive 16-byte stores.
+#define GPH_RA_TILE 16
+__global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
+{
+  typedef uint32_t gu32x4 __attribute__((ext_vector_type(4)));
+  __shared__ double tile[GPH_WAVE][GPH_RA_TILE + 1];
+  __shared__ int n_of[GPH_WAVE];
+  const int lane = threadIdx.x, slot0 = blockIdx.x * GPH_WAVE, slot = slot0 + lane;
+  const bool live = slot < D.L;
+  const int cs = D.ra_cshift, nck = (D.ra_M >> cs) + 1;
+  const double rx = KA.mathc[26], ry = KA.mathc[27], rz = KA.mathc[28], mx = KA.mathc[29], my = KA.mathc[30], mz = KA.mathc[31];
+  uint32_t x = 0, y = 0, z = 0;
+  int n = 0;
+  gu32x4 *ckpt = (gu32x4 *)D.ra_ckpt;
+  if (live) {
+    const int32_t *is = (const int32_t *)(D.pages + (size_t)slot * KA.lay.page_bytes + KA.lay.o_iscal);
+    x = (uint32_t)is[IS_RX]; y = (uint32_t)is[IS_RY]; z = (uint32_t)is[IS_RZ];
+    n = rng_ahead_count(D.ra_kprev[slot], D.ra_M);
+    ckpt[slot] = gu32x4{x, y, z, 0u};
+  }
+  n_of[lane] = n;
+  int nmax = n;
+  for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(nmax, o, GPH_WAVE); nmax = w > nmax ? w : nmax; }
+  __syncthreads();
+  for (int d0 = 0; d0 < nmax; d0 += GPH_RA_TILE) {
+    if (d0 < n) {      /* (n is a multiple of 64, the tile divides 64: a tile is generated in full or not at all) */
+#pragma unroll
+      for (int t = 0; t < GPH_RA_TILE; t++) {
+        GPH_RNG_STEP(x, y, z);
+        /* x / 30269.0 + y / 30307.0 + z / 30323.0 with the exact quotients of l_rndu (gph_locus.h) */
+        const double xd = (double)x, yd = (double)y, zd = (double)z;
+        double q;
+        q = xd * rx; const double qx = __builtin_fma(__builtin_fma(-q, mx, xd), rx, q);
+        q = yd * ry; const double qy = __builtin_fma(__builtin_fma(-q, my, yd), ry, q);
+        q = zd * rz; const double qz = __builtin_fma(__builtin_fma(-q, mz, zd), rz, q);
+        tile[lane][t] = __builtin_amdgcn_fract(qx + qy + qz);
+      }
+      const int d1 = d0 + GPH_RA_TILE;
+      if ((d1 & ((1 << cs) - 1)) == 0) ckpt[(size_t)GPH_IX(d1 >> cs, nck) * D.L + slot] = gu32x4{x, y, z, 0u};
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < GPH_WAVE / 4; i++) {
+      const int r = (lane >> 4) + 4 * i, c = lane & 15;
+      if (slot0 + r < D.L && d0 < n_of[r]) D.ra_draws[(size_t)(slot0 + r) * D.ra_M + GPH_IX(d0 + c, D.ra_M)] = tile[r][c];
+    }
+    __syncthreads();
+  }
+  if (live) ((gu32x4 *)D.ra_tail)[slot] = gu32x4{x, y, z, (uint32_t)n};
+}
+#endif
+
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 18     // kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 19     // (18: k_rng_ahead) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -452,6 +540,18 @@ struct gph_engine_state {
   int32_t slog_sel = 0;        // loci selected for the decision-level transcript (GPH_LOGSTEPS builds)
   bool mirror_current = true;  // the host mirror G_h holds what the device-side stages last wrote (false between a queued stage and pull_G)
   bool no_fuse = false;        // GPH_NO_FUSE=1 (tests): every finish as a kernel of its own; read once in gph_engine_create
+  // the sweep's uniforms generated ahead of it (k_rng_ahead); read once in gph_engine_create:
+  // GPH_RNG_AHEAD=0 off, GPH_RNG_AHEAD_DRAWS=<M> draws kept per locus at most (a multiple of 64), GPH_RNG_AHEAD_CKPT=16|64 draws
+  // between two checkpoints, GPH_RNG_AHEAD_FIRST=<n> draws generated for a locus's first sweep
+  bool rng_ahead = true;
+  // placement of the pass: B (resident mode: the pass for the next sweep goes out behind this one's kernel on a stream of its
+  // own and overlaps the tau / mixing kernels) or A (GPH_RNG_AHEAD_PLACE=A, and whenever B's draws cannot be trusted: right in
+  // front of the sweep kernel).  B's draws are those of the pages as the sweep left them: they hold for the next sweep of the
+  // chained iterations only, and only while ra_b_valid stands: whatever else steps a locus's generator or rewrites the pages'
+  // generator states (k_init, the locus-rate kernels, k_unit, a stepwise sweep, the tests' hook) takes it down
+  bool ra_place_b = true, ra_b_valid = false;
+  int32_t ra_M = 512, ra_C = 16, ra_first = 320;
+  size_t ra_bytes = 0;
   gph_counters counters = {0, 0, 0.0, 0};
   // the statistics samplers; all null / 0 while a feature is off
   // per-locus summaries (gph_summary.h): [ncol][L] accumulators in slot order, samples since they were last zeroed
@@ -771,8 +871,37 @@ static int run_stage_now(gph_engine *e, int stage, int arg)
   return check_error(e);
 }
 
+// the buffers of k_rng_ahead, by slot.  Not getting them is not an error: the sweep then generates its draws itself (and a
+// data set at the edge of the device's memory still loads)
+static int rng_ahead_alloc(gph_engine *e)
+{
+  const size_t L = (size_t)e->L, nck = (size_t)(e->ra_M / e->ra_C) + 1;
+  const size_t b_draws = sizeof(double) * L * e->ra_M, b_ckpt = 16 * nck * L, b_tail = 16 * L, b_kprev = sizeof(int32_t) * L;
+  GphDev &d = e->dev;
+  /* GPH_RNG_AHEAD_FAIL_ALLOC=1 (tests): as if the last of them had not been had */
+  const bool forced = getenv("GPH_RNG_AHEAD_FAIL_ALLOC") && atoi(getenv("GPH_RNG_AHEAD_FAIL_ALLOC")) != 0;
+  if (dev_alloc((void **)&d.ra_draws, b_draws) || dev_alloc((void **)&d.ra_ckpt, b_ckpt) || dev_alloc((void **)&d.ra_tail, b_tail) ||
+      forced || dev_alloc((void **)&d.ra_kprev, b_kprev)) {
+    dev_clear_error();
+    fprintf(stderr, "gphocs_hip: no memory for %d draws ahead of the sweep per locus (%.1f MB): the sweep kernel generates its own\n",
+            e->ra_M, (double)(b_draws + b_ckpt + b_tail + b_kprev) / 1e6);
+    eng_free(e, d.ra_draws); eng_free(e, d.ra_ckpt); eng_free(e, d.ra_tail); eng_free(e, d.ra_kprev);
+    d.ra_draws = nullptr; d.ra_ckpt = nullptr; d.ra_tail = nullptr; d.ra_kprev = nullptr;
+    e->rng_ahead = false;
+    return 0;
+  }
+  /* n_ahead of a locus's first sweep = ra_first rounded up to 64 (rng_ahead_count) */
+  std::vector<int32_t> kp(L, ((e->ra_first + 63) & ~63) - 64);
+  if (h2d(e, d.ra_kprev, kp.data(), b_kprev)) return GPH_EHIP;
+  d.ra_M = e->ra_M;
+  d.ra_cshift = e->ra_C == 64 ? 6 : 4;
+  e->ra_bytes = b_draws + b_ckpt + b_tail + b_kprev;
+  return 0;
+}
+
 // ---------------------------------------------------------------- C ABI
 extern "C" {
+static void rng_ahead_dirty(gph_engine *e);
 
 int gph_engine_create(const gph_config *cfg, gph_engine **out)
 {
@@ -802,6 +931,16 @@ int gph_engine_create(const gph_config *cfg, gph_engine **out)
   fill_math_constants(e->ka);
   if (const char *fh = getenv("GPH_HOST_DECISIONS")) e->force_host = atoi(fh) != 0;
   if (const char *nf = getenv("GPH_NO_FUSE")) e->no_fuse = atoi(nf) != 0;
+  if (const char *ra = getenv("GPH_RNG_AHEAD")) e->rng_ahead = atoi(ra) != 0;
+  if (const char *ra = getenv("GPH_RNG_AHEAD_DRAWS")) e->ra_M = atoi(ra);
+  if (const char *ra = getenv("GPH_RNG_AHEAD_PLACE")) e->ra_place_b = ra[0] == 'B' || ra[0] == 'b';
+  if (const char *ra = getenv("GPH_RNG_AHEAD_CKPT")) e->ra_C = atoi(ra);
+  if (const char *ra = getenv("GPH_RNG_AHEAD_FIRST")) e->ra_first = atoi(ra);
+  if (e->rng_ahead && (e->ra_M < 64 || e->ra_M % 64 != 0 || e->ra_M > (1 << 20) || (e->ra_C != 16 && e->ra_C != 64) || e->ra_first < 0)) {
+    fprintf(stderr, "gphocs_hip: GPH_RNG_AHEAD_DRAWS must be a multiple of 64 (up to 2^20), GPH_RNG_AHEAD_CKPT 16 or 64, GPH_RNG_AHEAD_FIRST >= 0\n");
+    delete e;
+    return GPH_EARG;
+  }
   if (int rc = backend_open(e)) { gph_engine_destroy(e); return rc; }
   memset(e->G_h, 0, sizeof(GphGlobal));
   e->G_h->error_locus = -1;          /* (0 is a locus: an error that is not per-locus must not name it -- ADVICE round 5) */
@@ -813,10 +952,12 @@ int gph_engine_create(const gph_config *cfg, gph_engine **out)
 void gph_engine_destroy(gph_engine *e)
 {
   if (!e) return;
+  rng_ahead_drain(e);
   dev_free(e->dev.pages); dev_free(e->dev.shadow); dev_free(e->dev.cond); dev_free((void *)e->dev.cond_off);
   dev_free((void *)e->dev.seq); dev_free((void *)e->dev.seq_off); dev_free((void *)e->dev.orig); dev_free((void *)e->dev.P); dev_free(e->dev.out); dev_free(e->dev.stats); dev_free(e->d_mutRate);
   dev_free(e->d_lrec); dev_free(e->d_lpre); dev_free(e->d_slot_of); dev_free(e->d_lr_result); dev_free(e->d_lr_gscr); dev_free(e->d_ref_page); dev_free(e->d_ref_seq);
   dev_free(e->d_part); dev_free(e->dev.err);
+  dev_free(e->dev.ra_draws); dev_free(e->dev.ra_ckpt); dev_free(e->dev.ra_tail); dev_free(e->dev.ra_kprev);
   dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   dev_free(e->gt.rows.d); dev_free(e->gt.d_sel);
@@ -1028,6 +1169,7 @@ int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *poff, const ui
   if (mutRates) rc |= h2d(e, e->d_mutRate, rates.data(), sizeof(double) * L);
   if (rc) return GPH_EHIP;
   e->dev.L = (int32_t)L;
+  if (e->rng_ahead && rng_ahead_alloc(e)) return GPH_EHIP;
   e->dev.Ltot = (int32_t)e->cfg.L_total;
   e->dev.locus_begin = e->cfg.locus_begin;
   e->loaded = true;
@@ -1060,6 +1202,7 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   SETDEV(e);
   /* the pages are rewritten from scratch: nothing decided on the old chain is owed to them any more (a commit left for the
    * next sweep kernel would stage in the OLD chain's shadow page over the fresh genealogies) */
+  rng_ahead_dirty(e);
   { int rcf = flush_pending(e); if (rcf) return rcf; }
   e->mix_owed = e->fin_owed = e->sync_pending = false;
   if (e->G_h->mix_flag || e->G_h->tau_flag) { e->G_h->mix_flag = 0; e->G_h->tau_flag = 0; e->G_dirty = true; }
@@ -1086,13 +1229,40 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   return rc;
 }
 
+// the draws of every slot's next sweep (k_rng_ahead), on the engine's stream right in front of the sweep kernel -- ahead of
+// the fork of its launch groups, so every group finds its draws -- from the generator states the pages hold now
+// a pass that is still in flight on its own stream and whose draws will not be used must be over before the next one writes
+// the same buffers
+static void rng_ahead_drain_if(gph_engine *e, bool stale) { if (stale && e->ra_b_valid) rng_ahead_drain(e); }
+// something other than the chained sweep is about to step the loci's generators: a pass made behind the last sweep (it may
+// still be running) is void
+static void rng_ahead_dirty(gph_engine *e) { rng_ahead_drain_if(e, true); e->ra_b_valid = false; }
+static int rng_ahead_launch(gph_engine *e)
+{
+  if (e->dev.ra_M <= 0) return 0;
+  int rc;
+  if ((rc = flush_pending(e))) return rc;
+  launch_pre(e);
+  const int tms = tm_begin(e, 18);
+  if ((rc = launch_grid(e, GphGrid{(int)((e->L + GPH_WAVE - 1) / GPH_WAVE), 1}, GPH_WAVE, 0, k_rng_ahead, e->ka, e->dev))) return rc;
+  tm_end(e, tms);
+  e->cls_launches[18] += 1; e->n_launches++;
+  return 0;
+}
+
 // The three genealogy proposals fused in one launch (GPhoCS.c:1495-1538; flags: which of them) and the reductions of its
 // outputs.  Two things decided earlier ride at the kernel's head: the deferred synchronizeEvents of the finished iteration
 // (flag 8; with_sync tells the stage that follows) and the commit of an accepted mixing proposal (flag 16) -- its flag and
 // factor travel as kernel arguments off the host mirror, which must then be what the decision stage wrote
-static int sweep_launch(gph_engine *e, int flags, double ftCoal, double ftMig, int &with_sync)
+static int sweep_launch(gph_engine *e, int flags, double ftCoal, double ftMig, int &with_sync, bool chained = false)
 {
   int rc;
+  /* chained: the sweep of gph_engine_iteration_.  The draws the pass made behind the previous iteration's sweep are this
+   * sweep's unless something stepped a generator since (rng_ahead_dirty) */
+  const bool side = chained && e->ra_place_b && e->dev.ra_M > 0 && resident(e);
+  const bool have = side && e->ra_b_valid;
+  rng_ahead_drain_if(e, !have);
+  e->ra_b_valid = false;
   with_sync = e->sync_pending ? 8 : 0;
   e->sync_pending = false;
   int with_mix = 0;
@@ -1101,7 +1271,15 @@ static int sweep_launch(gph_engine *e, int flags, double ftCoal, double ftMig, i
     e->mix_owed = false;
     if (e->G_h->mix_flag) with_mix = 16;
   }
+  if (have) { if ((rc = flush_pending(e)) || (rc = rng_ahead_wait(e))) return rc; }
+  else if ((rc = rng_ahead_launch(e))) return rc;
   if ((rc = launch_loci(e, 0, k_sweep, flags | with_sync | with_mix, ftCoal, ftMig, e->G_h->mix_c, e->G_h->mix_lnc))) return rc;
+  if (side) {
+    launch_pre(e);
+    if ((rc = rng_ahead_side(e, GphGrid{(int)((e->L + GPH_WAVE - 1) / GPH_WAVE), 1}))) return rc;
+    e->cls_launches[18] += 1; e->n_launches++;
+    e->ra_b_valid = true;
+  }
   if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;
   return reduce_stats(e);
 }
@@ -1381,6 +1559,29 @@ int gph_debug_math(const double *x, const double *y, int32_t n, double *out, int
   return debug_math(x, y, n, out, device);
 }
 
+// tests only (not part of include/gphocs_hip.h): the pass ahead of the sweep.  info[4] = on, M, C, bytes per locus;
+// kprev (may be null): the per-locus counts in input order -- what each locus consumed in its last sweep -- read
+// (set = 0) or written (set != 0: the next pass generates min(M, roundup64(kprev + 64)) draws for the locus)
+int gph_engine_rng_ahead_(gph_engine *e, int32_t *info, int32_t *kprev, int32_t set)
+{
+  if (!e || !e->loaded) return GPH_EARG;
+  SETDEV(e);
+  if (info) { if (set < 0) { info[0] = e->ra_place_b && e->dev.ra_M > 0 && resident(e); info[1] = e->ra_b_valid; return 0; }
+    info[0] = e->dev.ra_M > 0; info[1] = e->dev.ra_M; info[2] = 1 << e->dev.ra_cshift; info[3] = (int32_t)(e->ra_bytes / (size_t)e->L); }
+  if (!kprev) return 0;
+  if (e->dev.ra_M <= 0) return GPH_ESTATE;
+  if (e->initialized) { int rcs = finish_sync(e); if (rcs) return rcs; }
+  std::vector<int32_t> by_slot((size_t)e->L);
+  if (set) {
+    rng_ahead_dirty(e);         /* (a pass made behind the last sweep used the old counts) */
+    for (int64_t j = 0; j < e->L; j++) by_slot[j] = kprev[e->h_orig[j]];
+    return h2d(e, e->dev.ra_kprev, by_slot.data(), sizeof(int32_t) * e->L);
+  }
+  if (d2h(e, by_slot.data(), e->dev.ra_kprev, sizeof(int32_t) * e->L)) return GPH_EHIP;
+  for (int64_t j = 0; j < e->L; j++) kprev[e->h_orig[j]] = by_slot[j];
+  return 0;
+}
+
 #ifndef GPH_BUILD_ID
 #define GPH_BUILD_ID "unidentified"
 #endif
@@ -1468,7 +1669,7 @@ int gph_engine_steplog_fetch(gph_engine *e, int32_t idx, double *out, int32_t ma
 int gph_engine_hbm_bytes(gph_engine *e, double *bytes)
 {
   if (!e || !bytes) return GPH_EARG;
-  *bytes = 2.0 * e->pages_bytes + (double)e->cond_bytes + (double)e->seq_bytes_total + 8.0 * GPH_OUT_SLOTS * e->L;
+  *bytes = 2.0 * e->pages_bytes + (double)e->cond_bytes + (double)e->seq_bytes_total + 8.0 * GPH_OUT_SLOTS * e->L + (double)e->ra_bytes;
   return 0;
 }
 
@@ -1519,6 +1720,7 @@ int gph_engine_locus_rate_update(gph_engine *e, double finetune, double alpha, g
   if (!e || !e->initialized || !io) return GPH_ESTATE;
   io->accepted = 0;
   if (finetune <= 0.0) return 0;                       /* GPhoCS.c:4606 */
+  rng_ahead_dirty(e);
   const bool owner = e->cfg.locus_begin == 0;          /* this rank holds the reference locus (genRateRef = 0) */
   SETDEV(e);
   if (!multi_rank(e) && (!owner || e->cfg.L_total != e->L)) {
@@ -1708,10 +1910,10 @@ static int evaluate_fused(gph_engine *e, int cls, decltype(&k_tau_eval) kernel)
   if ((rc = launch_loci(e, cls, kernel, fuse))) return rc;
   return reduce_local(e, 0, GPH_OUT_SLOTS);
 }
-static int part_sweep(gph_engine *e, int32_t iteration, double ftCoal, double ftMig)
+static int part_sweep(gph_engine *e, int32_t iteration, double ftCoal, double ftMig, bool chained = false)
 {
   int rc, with_sync;
-  if ((rc = sweep_launch(e, 7, ftCoal, ftMig, with_sync))) return rc;
+  if ((rc = sweep_launch(e, 7, ftCoal, ftMig, with_sync, chained))) return rc;
   return run_stage(e, GS_SWEEP_DONE, with_sync, iteration);
 }
 static int part_lrate(gph_engine *e, int32_t iteration, const double *lr_alpha_finetune, int64_t *lr_accepted, double *lr_rateVar)
@@ -1803,7 +2005,7 @@ int gph_engine_iteration_(gph_engine *e, int32_t iteration, const double *lr_alp
   int rc;
   GphGlobal &Gh = *e->G_h;    /* settings only: the running state is on the device until finish_sync */
   if ((rc = push_if_dirty(e))) return rc;
-  if ((rc = part_sweep(e, iteration, Gh.ftCoalTime, Gh.ftMigTime))) return rc;
+  if ((rc = part_sweep(e, iteration, Gh.ftCoalTime, Gh.ftMigTime, true))) return rc;
   if (lr_alpha_finetune && (rc = part_lrate(e, iteration, lr_alpha_finetune, lr_accepted, lr_rateVar))) return rc;
   if ((rc = run_stage(e, GS_THETA, 0, iteration))) return rc;
   /* the first tau proposal touches no locus: its stage rides in the launch of the stages before it, ahead of the
@@ -1835,6 +2037,7 @@ int gph_engine_part_(gph_engine *e, int32_t part, int32_t iteration, const doubl
   SETDEV(e);
   int rc = 0;
   GphGlobal &Gh = *e->G_h;
+  rng_ahead_dirty(e);      /* (the stepwise driver: every pass in front of its sweep) */
   if ((rc = push_if_dirty(e))) return rc;
   if (part != GPH_PART_SWEEP && part != GPH_PART_SYNC) { int rcm = mix_finish_owed(e); if (rcm) return rcm; }
   if (part == GPH_PART_LRATE || part == GPH_PART_TAU || part == GPH_PART_SAGE || part == GPH_PART_MIX) {
@@ -1877,6 +2080,7 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
   if ((op == 3 || op == 6) && (arg < 0 || arg >= 2 * e->cfg.n - 1)) return GPH_EARG;
   if (op == 8 && (arg < 0 || arg > 100000)) return GPH_EARG;      /* (the checked build's self-test: arg = a node index, possibly out of range) */
   SETDEV(e);
+  rng_ahead_dirty(e);
   { int rcs = flush_sync(e, true); if (!rcs) rcs = finish_sync(e); if (rcs) return rcs; }
   if (op == 2) {
     if (arg < e->cfg.Kc || arg >= e->cfg.K) return GPH_EARG;

@@ -30,6 +30,12 @@ struct GphDev {            // device pointers (passed by value to every kernel)
   double *slog;            // [selected][slog_cap][8]: kind, six values, spare
   int32_t *slog_n;         // [selected] records written (may exceed slog_cap: the excess is dropped)
   int32_t slog_cap, pad_;
+  // the sweep's uniforms generated ahead of it by k_rng_ahead (gph_engine.hip; consumer: GphRngA, gph_locus.h), by slot; ra_M = 0: off
+  double *ra_draws;        // [L][ra_M]: draw d of the stream that starts at the page's generator state
+  uint32_t *ra_ckpt;       // [ra_M / C + 1][L][4]: x, y, z after C j draws (C = 1 << ra_cshift), a spare word
+  uint32_t *ra_tail;       // [L][4]: x, y, z after the last draw generated, and how many were (n_ahead)
+  int32_t *ra_kprev;       // [L]: draws the locus consumed in its previous sweep
+  int32_t ra_M, ra_cshift;
 };
 
 #include "gph_locus.h"   // opens struct GphCtx; closed at the end of this file
@@ -464,7 +470,7 @@ template <class RNG> GPH_DEV void sweep_spr(const GphDev &D, int g, RNG &rng)
 // flag 16: the mixing proposal of the previous iteration was ACCEPTED and its commit (GPhoCS.c:4815-4848) has not run: the
 // evaluated state is taken from the shadow page and committed here, in LDS -- the page the sweep writes at its end is
 // the only one written, and the commit costs no launch and no page round trip of its own
-GPH_DEV void kb_sweep(const GphDev &D, int g, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc)
+template <class RNG> GPH_DEV void kb_sweep_(const GphDev &D, int g, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc)
 {
   STAMP_BEGIN(0);
   if (flags & 16) {
@@ -474,8 +480,8 @@ GPH_DEV void kb_sweep(const GphDev &D, int g, int flags, double ftCoal, double f
     stage_in(D, g, D.pages, 1);
   }
   GPH_SLOG_OPEN(D, g);
-  GphRngB rng;       /* uniforms in batches of 64: gph_locus.h */
-  rng_load(rng);
+  RNG rng;           /* uniforms in chunks of 64, generated ahead of the kernel: gph_locus.h */
+  rng_load(rng, D, g);
   /* flag 8: synchronizeEvents of the previous iteration (patch.c:3548), deferred into this kernel */
   OUT(g, 15, (flags & 8) ? (double)synchronize_events() : 1.0);
   OUT(g, 0, 0.0); OUT(g, 1, 0.0); OUT(g, 2, 0.0); OUT(g, 3, 0.0); OUT(g, 4, 0.0);
@@ -483,7 +489,7 @@ GPH_DEV void kb_sweep(const GphDev &D, int g, int flags, double ftCoal, double f
   { STAMP_BEGIN(5); if ((flags & 1) && ftCoal > 0.0) sweep_internal(D, g, ftCoal, rng); STAMP_END(5); }
   { STAMPC_BEGIN(4); if ((flags & 2) && ftMig > 0.0 && !gph_failed()) sweep_mignodes(D, g, ftMig, rng); STAMPC_END(4); }
   { STAMP_BEGIN(6); if ((flags & 4) && !gph_failed()) sweep_spr(D, g, rng); STAMP_END(6); }
-  rng_store(rng);
+  rng_store(rng, D, g);
   out_common(D, g);
   STAMP_END(0);
 #if defined(GPH_STAMPS) && !defined(GPH_HOSTEMU)
@@ -491,6 +497,14 @@ GPH_DEV void kb_sweep(const GphDev &D, int g, int flags, double ftCoal, double f
   for (int k = 0; k < 8; k++) OUT(g, k, gph_lds.s_stamp[k]);
 #endif
   stage_out(D, g, D.pages, 1);
+}
+GPH_DEV void kb_sweep(const GphDev &D, int g, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc)
+{
+#ifdef GPH_HOSTEMU
+  /* the pass ahead switched off: the serial generator, as every other kernel */
+  if (D.ra_M <= 0) { kb_sweep_<GphRng>(D, g, flags, ftCoal, ftMig, mix_c, mix_lnc); return; }
+#endif
+  kb_sweep_<GphRngA>(D, g, flags, ftCoal, ftMig, mix_c, mix_lnc);
 }
 
 // ---------------------------------------------------------------- UpdateTau

@@ -331,170 +331,143 @@ GPH_DEV double l_rndu(GphRng &g)
   r = (r - (int)r);
   return r;
 }
-// ---- the sweep kernel's generator: the SAME stream, a batch of draws (GPH_RNG_BATCH) at a time.  The integer recurrences stay serial (scalar
-// unit, one lane of three registers written per step); the expensive part of a draw -- three exact quotients, two sums and
-// the fractional part, 15 fp64 vector instructions that used to run for ONE useful lane -- runs once per batch with a draw in
-// every lane.  Handing a draw out is two lane reads.  The state written back to the page is the one after the last draw
-// handed out (lane pos-1 of the batch), so a kernel leaves the generator exactly where the serial code leaves it.
+// ---- the sweep kernel's generator: the SAME stream, handed out from chunks of 64 draws with a draw in every lane of `u`
+// (two lane reads per draw).  The recurrences are serial per locus but not across loci: k_rng_ahead (gph_engine.hip) steps
+// them for 64 loci per instruction ahead of the sweep and leaves, per slot, the first n_ahead draws (GphDev::ra_draws), the
+// generator state after every C of them (ra_ckpt) and after the last one (ra_tail).  A refill is then one 512-byte load.
+// A locus that runs past n_ahead -- or a run with the pass switched off (n_ahead = 0) -- goes on with chunks generated in
+// the kernel from the state where the pass stopped: one out-of-line function, the same values.  The state written back to
+// the page is the one after the last draw handed out, so a kernel leaves the generator exactly where the serial code
+// leaves it: the checkpoint below it replayed for k % C steps (a chunk of the kernel's own: from the chunk's start).
+//   CN_RAN: n_ahead; CN_RALO / CN_RAHI: address of the slot's draws; CN_RX.. : the state the next in-kernel chunk starts
+//   from; IS_RX.. (page scalars): the state the current in-kernel chunk started from
+GPH_DEV void rng_load(GphRng &g, const GphDev &, int) { rng_load(g); }
+GPH_DEV void rng_store(const GphRng &g, const GphDev &, int) { rng_store(g); }
+#define GPH_RNG_STEP(x, y, z) do { x = 171u * x - 30269u * (x / 177u); y = 172u * y - 30307u * (y / 176u); z = 170u * z - 30323u * (z / 178u); } while (0)
 #ifdef GPH_HOSTEMU
-typedef GphRng GphRngB;
-#else
-// draws per batch: a batch is generated in full and the draws a kernel has not handed out when it ends are thrown away
-// (and the state replayed to where it stopped): 64 per batch wasted 32 draws + 32 replay steps per kernel on average;
-// measured 64 / 32 / 16 / 8: 16 and 32 are the fastest (-0.6 % sweep against 64), 8 pays more in refills than it saves
-#ifndef GPH_RNG_BATCH
-#define GPH_RNG_BATCH 16
-#endif
-struct GphRngB {
-  int pos;               // draws of the batch handed out; GPH_RNG_BATCH = none left
-  double u;              // per lane: draw `lane` of the batch
+struct GphRngA {
+  int k;                 // draws handed out
+  double u[64];          // draw (k - 1 & ~63) + i of the stream
 };
-// The generator's integer state is touched twice per batch of draws, so it lives in lanes of the scalar pad, not in scalar
-// registers that stay allocated (and get spilled) across the whole sweep: page scalars IS_RX / IS_RY / IS_RZ = the state
-// the current batch STARTED from, CN_RX / CN_RY / CN_RZ = the state after its last draw (where the next batch starts).
-GPH_DEV void rng_load(GphRngB &g)
-{
-  setCNT(CN_RX, ISC(IS_RX)); setCNT(CN_RY, ISC(IS_RY)); setCNT(CN_RZ, ISC(IS_RZ));
-  g.pos = GPH_RNG_BATCH; g.u = 0.0;
-}
-// The state to leave behind is the one after the last draw handed out: the recurrences replayed from the batch's start
-// for `pos` steps, once per kernel (scalar unit).  Keeping the per-lane states of the batch for this instead cost three
-// vector registers for the whole kernel, and the sweep kernel is compiled for 64 of them.
-GPH_DEV void rng_store(const GphRngB &g)
-{
-  uint32_t x = (uint32_t)CNT(CN_RX), y = (uint32_t)CNT(CN_RY), z = (uint32_t)CNT(CN_RZ);
-  if (g.pos < GPH_RNG_BATCH) {
-    x = (uint32_t)ISC(IS_RX); y = (uint32_t)ISC(IS_RY); z = (uint32_t)ISC(IS_RZ);
-    for (int k = 0; k < g.pos; k++) {
-      x = 171u * x - 30269u * (x / 177u);
-      y = 172u * y - 30307u * (y / 176u);
-      z = 170u * z - 30323u * (z / 178u);
-    }
-  }
-  setISC(IS_RX, (int)x); setISC(IS_RY, (int)y); setISC(IS_RZ, (int)z);
-}
-#ifndef GPH_RNG_ROLLED
-template <int K> GPH_DEV void rng_steps_(uint32_t &x, uint32_t &y, uint32_t &z, int &vx, int &vy, int &vz)
-{
-  if constexpr (K < GPH_RNG_BATCH) {
-    x = 171u * x - 30269u * (x / 177u);
-    y = 172u * y - 30307u * (y / 176u);
-    z = 170u * z - 30323u * (z / 178u);
-    asm("v_writelane_b32 %0, %3, %6\n\tv_writelane_b32 %1, %4, %6\n\tv_writelane_b32 %2, %5, %6"
-        : "+v"(vx), "+v"(vy), "+v"(vz) : "s"(x), "s"(y), "s"(z), "i"(K));
-    rng_steps_<K + 1>(x, y, z, vx, vy, vz);
-  }
-}
-#endif
-#ifndef GPH_RNG_VECTOR_REFILL      /* the three recurrences on the scalar unit: the product form (see the measurement at the vector form below) */
-GPH_DEV void rng_refill(GphRngB &g)
-{
-  uint32_t x = (uint32_t)CNT(CN_RX), y = (uint32_t)CNT(CN_RY), z = (uint32_t)CNT(CN_RZ);
-  int vx = 0, vy = 0, vz = 0;
-  setISC(IS_RX, (int)x); setISC(IS_RY, (int)y); setISC(IS_RZ, (int)z);
-#ifndef GPH_RNG_ROLLED
-  /* fully unrolled (round 5): the lane of every write is an immediate -- no s_mov m0 / s_nop / index add per draw, 21 instead
-   * of 24 instructions per draw at 16 x the code per refill site: sweep -0.8 %, four interleaved A/B pairs, every pair in
-   * favour (profiles/r05_ab_rng_unroll.txt) */
-  rng_steps_<0>(x, y, z, vx, vy, vz);
 #else
-#pragma unroll 4
-  for (int k = 0; k < GPH_RNG_BATCH; k++) {
-    x = 171u * x - 30269u * (x / 177u);
-    y = 172u * y - 30307u * (y / 176u);
-    z = 170u * z - 30323u * (z / 178u);
-    /* lane select through M0: a VOP3 instruction reads one scalar register besides it (constant-bus limit).  Nothing
-     * else in this translation unit's code uses M0 (gfx9 DS instructions do not need it; checked in the ISA) */
-    asm("s_mov_b32 m0, %6\n\ts_nop 0\n\tv_writelane_b32 %0, %3, m0\n\tv_writelane_b32 %1, %4, m0\n\tv_writelane_b32 %2, %5, m0"
-        : "+v"(vx), "+v"(vy), "+v"(vz) : "s"(x), "s"(y), "s"(z), "s"(k) : "m0");
-  }
+struct GphRngA {
+  int k;                 // draws handed out
+  double u;              // per lane: draw (k - 1 & ~63) + lane of the stream
+};
+struct GphRngChunk { double u; int x, y, z; };
+// 64 draws from (x, y, z) on, draw `lane` in lane `lane`, and the state after them.  The integer recurrences run on the
+// scalar unit, a lane of three registers taking the state of each step; the three exact quotients, the sums and the
+// fractional part once for all 64.  The rare path, out of line: the twelve places that hand out draws share one copy
+// (inlined, the rolled loop cost a vector spill more; by value in and out: the context object stays in registers)
+#ifndef GPH_RNG_CHUNK_ATTR
+#define GPH_RNG_CHUNK_ATTR __noinline__
 #endif
-  setCNT(CN_RX, (int)x); setCNT(CN_RY, (int)y); setCNT(CN_RZ, (int)z);
+static __device__ GPH_RNG_CHUNK_ATTR GphRngChunk rng_chunk64(uint32_t x_, uint32_t y_, uint32_t z_)
+{
+  uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane((int)x_), y = (uint32_t)__builtin_amdgcn_readfirstlane((int)y_),
+           z = (uint32_t)__builtin_amdgcn_readfirstlane((int)z_);
+  uint32_t vx = 0, vy = 0, vz = 0;
+  const int lane = GPH_LANE;
+  GphRngChunk r;
+  r.u = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < 64; k++) {
+    GPH_RNG_STEP(x, y, z);
+    const bool mine = lane == k;
+    vx = mine ? x : vx; vy = mine ? y : vy; vz = mine ? z : vz;
+  }
 #if defined(__HIP_DEVICE_COMPILE__)       /* (the host pass of hipcc only parses this) */
   {
-    const gph_cdbl *RC = GPH_RNGC;
-    const double rx = RC[0], ry = RC[1], rz = RC[2], mx = RC[3], my = RC[4], mz = RC[5];
-    double xd = (double)(uint32_t)vx, yd = (double)(uint32_t)vy, zd = (double)(uint32_t)vz, q;
+    /* the constants of GPH_RNGC (gph_engine.hip: fill_math_constants) as literals: no kernel-argument segment in here */
+    const double rx = 1.0 / 30269.0, ry = 1.0 / 30307.0, rz = 1.0 / 30323.0, mx = 30269.0, my = 30307.0, mz = 30323.0;
+    double xd = (double)vx, yd = (double)vy, zd = (double)vz, q;
     q = xd * rx; double qx = __builtin_fma(__builtin_fma(-q, mx, xd), rx, q);
     q = yd * ry; double qy = __builtin_fma(__builtin_fma(-q, my, yd), ry, q);
     q = zd * rz; double qz = __builtin_fma(__builtin_fma(-q, mz, zd), rz, q);
-    g.u = __builtin_amdgcn_fract(qx + qy + qz);
+    r.u = __builtin_amdgcn_fract(qx + qy + qz);
   }
 #endif
-  g.pos = 0;
+  r.x = (int)x; r.y = (int)y; r.z = (int)z;
+  return r;
 }
+#endif
+GPH_DEV void rng_load(GphRngA &g, const GphDev &D, int slot)
+{
+  g.k = 0;
+#ifndef GPH_HOSTEMU
+  g.u = 0.0;
+#endif
+  if (D.ra_M > 0) {
+    const uint32_t *t = D.ra_tail + 4 * (size_t)GPH_IX(slot, D.L);
+    const uint64_t a = (uint64_t)(uintptr_t)(D.ra_draws + (size_t)slot * D.ra_M);
+    setCNT(CN_RX, (int)t[0]); setCNT(CN_RY, (int)t[1]); setCNT(CN_RZ, (int)t[2]); setCNT(CN_RAN, (int)t[3]);
+    setCNT(CN_RALO, (int)(uint32_t)a); setCNT(CN_RAHI, (int)(uint32_t)(a >> 32));
+  } else {
+    setCNT(CN_RX, ISC(IS_RX)); setCNT(CN_RY, ISC(IS_RY)); setCNT(CN_RZ, ISC(IS_RZ));      /* CN_RAN = 0 (scratch_init) */
+  }
+}
+GPH_DEV void rng_refill(GphRngA &g)
+{
+  if (g.k < CNT(CN_RAN)) {
+    const uint64_t a = (uint64_t)(uint32_t)CNT(CN_RALO) | ((uint64_t)(uint32_t)CNT(CN_RAHI) << 32);
+#ifdef GPH_HOSTEMU
+    for (int i = 0; i < 64; i++) g.u[i] = ((const double *)(uintptr_t)a)[GPH_IX(g.k + i, CNT(CN_RAN))];
 #else
-// Round 5 experiment, NOT the product form: measured 3 % SLOWER (sweep 9.46 / 9.52 -> 9.77 / 9.78 ms, two
-// interleaved A/B pairs on one box, same accept counters: profiles/r05_ab_rng_vector.txt) -- the vector pipe is the busier one
-// (9 quarter-/full-rate vector instructions per draw = 28 SIMD-cycles replace 18 scalar ones + 12.6 SIMD-cycles of lane writes),
-// seven live vector registers at every refill site add spills (9 -> 28), and twelve inlined sites add 750 static instructions.
-// The recurrences run on the VECTOR unit, one component per row of 16 lanes (row 0 = x, 1 = y, 2 = z; row 3 runs z
-// again and is ignored), every lane of a row redundantly.  A step is
-//   q = x / d      by the 33-bit multiply-shift of Granlund & Montgomery: t = mulhi(x, M'), q = (t + ((x - t) >> 1)) >> 7
-//                  with M' = floor(2^32 (256 - d) / d) + 1 -- equal to x / d for ALL 2^32 x and d = 177, 176, 178
-//                  (exhaustively: tools/verify_rng_magic.c),
-//   x = a x - m q  modulo 2^32 (= a (x % d) - c (x / d), utils.c:503-505, as in the scalar form above),
-// and one v_cndmask_b32_dpp that shifts the row's history register one lane down (row_shl:1: lane i <- lane i + 1) and puts
-// the new state into the row's last lane: after 16 steps lane j of a row holds the state after step j + 1, i.e. the integers of
-// draw j.  9 vector instructions per draw where the scalar form had 18 scalar ones + s_mov m0 + s_nop + 3 v_writelane; the
-// three quotients x / 30269.0 ... then run ONCE over the 48 lanes with per-row constants, and the y / z quotients come down
-// to row 0 with four ds_bpermute_b32.  One asm statement: the DPP select reads the row-end mask from vcc, which must
-// survive the 16 steps (no instruction in between writes it), and the compiler must not re-schedule a write of the history
-// register next to its DPP read (2 wait states on gfx9: inside the block the previous write is 8 instructions away).
-#define GPH_RNGV_STEP \
-  "v_mul_hi_u32 %[q], %[st], %[mg]\n\t" \
-  "v_mul_lo_u32 %[t], %[st], %[a]\n\t" \
-  "v_sub_u32 %[st], %[st], %[q]\n\t" \
-  "v_lshrrev_b32 %[st], 1, %[st]\n\t" \
-  "v_add_u32 %[st], %[st], %[q]\n\t" \
-  "v_lshrrev_b32 %[st], 7, %[st]\n\t" \
-  "v_mul_lo_u32 %[st], %[st], %[nm]\n\t" \
-  "v_add_u32 %[st], %[st], %[t]\n\t" \
-  "v_cndmask_b32_dpp %[h], %[h], %[st], vcc row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-#define GPH_RNGV_STEP4 GPH_RNGV_STEP GPH_RNGV_STEP GPH_RNGV_STEP GPH_RNGV_STEP
-GPH_DEV void rng_refill(GphRngB &g)
-{
-  static_assert(GPH_RNG_BATCH == 16, "one draw per lane of a 16-lane row");
-  const uint32_t x0 = (uint32_t)CNT(CN_RX), y0 = (uint32_t)CNT(CN_RY), z0 = (uint32_t)CNT(CN_RZ);
-  setISC(IS_RX, (int)x0); setISC(IS_RY, (int)y0); setISC(IS_RZ, (int)z0);
-#if defined(__HIP_DEVICE_COMPILE__)       /* (the host pass of hipcc only parses this) */
-  const int row = GPH_LANE >> 4;
-  const bool r0 = row == 0, r1 = row == 1;
-  uint32_t st = r0 ? x0 : r1 ? y0 : z0, h = 0, q, t;
-  const uint32_t mg = r0 ? 0x724287f5u : r1 ? 0x745d1746u : 0x702e05c1u;      /* M' of 177, 176, 178 */
-  const uint32_t a = r0 ? 171u : r1 ? 172u : 170u;
-  const uint32_t nm = r0 ? 0u - 30269u : r1 ? 0u - 30307u : 0u - 30323u;      /* -(a d + c): 171 * 177 + 2 = 30269, ... */
-  asm("s_mov_b32 vcc_lo, 0x80008000\n\t"
-      "s_mov_b32 vcc_hi, 0x80008000\n\t"
-      GPH_RNGV_STEP4 GPH_RNGV_STEP4 GPH_RNGV_STEP4 GPH_RNGV_STEP4
-      : [st] "+v"(st), [h] "+v"(h), [q] "=&v"(q), [t] "=&v"(t) : [mg] "v"(mg), [a] "v"(a), [nm] "v"(nm) : "vcc");
-  /* every lane of a row holds the state after the batch's last draw */
-  setCNT(CN_RX, __builtin_amdgcn_readlane((int)st, 0)); setCNT(CN_RY, __builtin_amdgcn_readlane((int)st, 16));
-  setCNT(CN_RZ, __builtin_amdgcn_readlane((int)st, 32));
-  {
-    const gph_cdbl *RC = GPH_RNGC;
-    const double rr = r0 ? RC[0] : r1 ? RC[1] : RC[2], mm = r0 ? RC[3] : r1 ? RC[4] : RC[5];
-    const double hd = (double)h, q0 = hd * rr;
-    const double qq = __builtin_fma(__builtin_fma(-q0, mm, hd), rr, q0);      /* x / 30269.0 | y / 30307.0 | z / 30323.0, exact (l_rndu above) */
-    union { double d; int32_t i[2]; } u, vy, vz;
-    u.d = qq;
-    const int ay = (GPH_LANE + 16) << 2, az = (GPH_LANE + 32) << 2;
-    vy.i[0] = __builtin_amdgcn_ds_bpermute(ay, u.i[0]); vy.i[1] = __builtin_amdgcn_ds_bpermute(ay, u.i[1]);
-    vz.i[0] = __builtin_amdgcn_ds_bpermute(az, u.i[0]); vz.i[1] = __builtin_amdgcn_ds_bpermute(az, u.i[1]);
-    g.u = __builtin_amdgcn_fract(qq + vy.d + vz.d);      /* lanes 0 .. 15: draw `lane` (the other rows hold sums nobody reads) */
+    /* one 512-byte load: scalar base + a 32-bit offset per lane.  The lane's offset is made here, every time (an opaque
+     * value): computed once and kept, it is one more vector register alive through the whole sweep, i.e. spills */
+    int lane = GPH_LANE;
+    asm volatile("" : "+v"(lane));
+    g.u = *(const GPH_GLB double *)((const GPH_GLB char *)(uintptr_t)a + (uint32_t)(GPH_IX(g.k + lane, CNT(CN_RAN)) << 3));
+#endif
+    return;
   }
+  uint32_t x = (uint32_t)CNT(CN_RX), y = (uint32_t)CNT(CN_RY), z = (uint32_t)CNT(CN_RZ);
+  setISC(IS_RX, (int)x); setISC(IS_RY, (int)y); setISC(IS_RZ, (int)z);
+#ifdef GPH_HOSTEMU
+  for (int i = 0; i < 64; i++) {
+    GPH_RNG_STEP(x, y, z);
+    const double r = x / 30269.0 + y / 30307.0 + z / 30323.0;
+    g.u[i] = r - (int)r;
+  }
+  setCNT(CN_RX, (int)x); setCNT(CN_RY, (int)y); setCNT(CN_RZ, (int)z);
+#else
+  const GphRngChunk c = rng_chunk64(x, y, z);
+  setCNT(CN_RX, c.x); setCNT(CN_RY, c.y); setCNT(CN_RZ, c.z);
+  g.u = c.u;
 #endif
-  g.pos = 0;
 }
-#endif
-GPH_DEV double l_rndu(GphRngB &g)
+GPH_DEV double l_rndu(GphRngA &g)
 {
-  if (g.pos >= GPH_RNG_BATCH) rng_refill(g);
-  const double u = gph_readlane64(g.u, g.pos);
-  g.pos++;
+  if ((g.k & 63) == 0) rng_refill(g);
+#ifdef GPH_HOSTEMU
+  const double u = g.u[g.k & 63];
+#else
+  const double u = gph_readlane64(g.u, g.k & 63);
+#endif
+  g.k++;
   return u;
 }
-#endif
+// k draws were handed out: the state after them into the page (k = 0: it is there), k into the slot's count
+GPH_DEV void rng_store(const GphRngA &g, const GphDev &D, int slot)
+{
+  const int k = g.k;
+  if (k > 0) {
+    uint32_t x, y, z;
+    int r;
+    if (k <= CNT(CN_RAN)) {
+      const int j = k >> D.ra_cshift;
+      const uint32_t *c = D.ra_ckpt + 4 * ((size_t)GPH_IX(j, (D.ra_M >> D.ra_cshift) + 1) * D.L + GPH_IX(slot, D.L));
+      x = (uint32_t)RFL(c[0]); y = (uint32_t)RFL(c[1]); z = (uint32_t)RFL(c[2]);
+      r = k & ((1 << D.ra_cshift) - 1);
+    } else {
+      x = (uint32_t)ISC(IS_RX); y = (uint32_t)ISC(IS_RY); z = (uint32_t)ISC(IS_RZ);
+      r = k - ((k - 1) & ~63);
+    }
+    for (int i = 0; i < r; i++) GPH_RNG_STEP(x, y, z);
+    setISC(IS_RX, (int)x); setISC(IS_RY, (int)y); setISC(IS_RZ, (int)z);
+  }
+  if (D.ra_M > 0 && GPH_LANE == 0) D.ra_kprev[GPH_IX(slot, D.L)] = k;
+}
 // rndnormal, utils.c:459-472
 template <class RNG> GPH_DEV double l_rndnormal(RNG &g)
 {
