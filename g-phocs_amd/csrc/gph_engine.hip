@@ -1581,6 +1581,35 @@ int gph_engine_rng_ahead_(gph_engine *e, int32_t *info, int32_t *kprev, int32_t 
   for (int64_t j = 0; j < e->L; j++) kprev[e->h_orig[j]] = by_slot[j];
   return 0;
 }
+// tests only (not part of include/gphocs_hip.h): the buffers of the last pass as they stand, in input order (any of them may
+// be null): draws[L][M], ckpt[L][M / C + 1][4] (the device keeps them with the slot as the fastest index), tail[L][4].
+// Only reads: a pass made behind the last sweep stays valid (it is waited for, its draws are what the buffers then hold)
+int gph_engine_rng_ahead_fetch_(gph_engine *e, double *draws, uint32_t *ckpt, uint32_t *tail)
+{
+  if (!e || !e->loaded) return GPH_EARG;
+  SETDEV(e);
+  if (e->dev.ra_M <= 0) return GPH_ESTATE;
+  if (e->initialized) { int rcs = finish_sync(e); if (rcs) return rcs; }
+  if (e->ra_b_valid) rng_ahead_drain(e);
+  const size_t L = (size_t)e->L, M = (size_t)e->dev.ra_M, nck = (M >> e->dev.ra_cshift) + 1;
+  if (draws) {
+    std::vector<double> by_slot(L * M);
+    if (d2h(e, by_slot.data(), e->dev.ra_draws, sizeof(double) * L * M)) return GPH_EHIP;
+    for (size_t j = 0; j < L; j++) memcpy(draws + (size_t)e->h_orig[j] * M, by_slot.data() + j * M, sizeof(double) * M);
+  }
+  if (ckpt) {
+    std::vector<uint32_t> by_slot(4 * nck * L);
+    if (d2h(e, by_slot.data(), e->dev.ra_ckpt, 16 * nck * L)) return GPH_EHIP;
+    for (size_t j = 0; j < L; j++)
+      for (size_t c = 0; c < nck; c++) memcpy(ckpt + 4 * ((size_t)e->h_orig[j] * nck + c), by_slot.data() + 4 * (c * L + j), 16);
+  }
+  if (tail) {
+    std::vector<uint32_t> by_slot(4 * L);
+    if (d2h(e, by_slot.data(), e->dev.ra_tail, 16 * L)) return GPH_EHIP;
+    for (size_t j = 0; j < L; j++) memcpy(tail + 4 * (size_t)e->h_orig[j], by_slot.data() + 4 * j, 16);
+  }
+  return 0;
+}
 
 #ifndef GPH_BUILD_ID
 #define GPH_BUILD_ID "unidentified"

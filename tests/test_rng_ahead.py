@@ -4,7 +4,6 @@ The pass must change nothing: the random stream, the records and every byte of t
 generator whichever path serves a draw -- the buffer, the in-kernel chunks behind it, or only those.  Every setting below is
 compared with the run that has the pass switched off (GPH_RNG_AHEAD=0: the serial generator of every other kernel), after
 every iteration, so the generator state a sweep leaves in the page is checked each time and not only at the end."""
-import ctypes as C
 import os
 import sys
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, REPO
+from rng_ahead_util import ENV, ahead
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
 
@@ -24,7 +24,6 @@ SETTINGS = {
     "ckpt64": {"GPH_RNG_AHEAD_CKPT": "64"},          # the other checkpoint distance
     "m64ckpt64": {"GPH_RNG_AHEAD_DRAWS": "64", "GPH_RNG_AHEAD_CKPT": "64"},
 }
-ENV = ("GPH_RNG_AHEAD", "GPH_RNG_AHEAD_DRAWS", "GPH_RNG_AHEAD_CKPT", "GPH_RNG_AHEAD_FIRST", "GPH_RNG_AHEAD_FAIL_ALLOC", "GPH_RNG_AHEAD_PLACE")
 
 
 @pytest.fixture(scope="module")
@@ -32,18 +31,6 @@ def lib():
     import run_hostemu as R
     import gphocs_amd as G
     return G.load_library(R.build_hostemu())
-
-
-def ahead(lib, s, kprev=None, set_=False):
-    """(on, M, C, bytes per locus) and, if asked for, the per-locus draw counts (read, or written from `kprev`)"""
-    fn = lib.gph_engine_rng_ahead_
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    info = np.zeros(4, dtype=np.int32)
-    assert fn(s.engine, info.ctypes.data, None, 0) == 0
-    if kprev is not None:
-        assert kprev.dtype == np.int32 and len(kprev) == s.end - s.begin
-        assert fn(s.engine, None, kprev.ctypes.data, int(set_)) == 0
-    return tuple(int(v) for v in info)
 
 
 def run(lib, name, iters, env, tmp, monkeypatch, before=None):

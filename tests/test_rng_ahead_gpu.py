@@ -16,12 +16,12 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from rng_ahead_util import ENV, info_and_counts as _info
 
 pytestmark = pytest.mark.gpu
 
 SETTINGS = {"off": {"GPH_RNG_AHEAD": "0"}, "on": {}, "m64": {"GPH_RNG_AHEAD_DRAWS": "64"},
             "placeA": {"GPH_RNG_AHEAD_PLACE": "A"}, "noalloc": {"GPH_RNG_AHEAD_FAIL_ALLOC": "1"}}
-ENV = ("GPH_RNG_AHEAD", "GPH_RNG_AHEAD_DRAWS", "GPH_RNG_AHEAD_CKPT", "GPH_RNG_AHEAD_FIRST", "GPH_RNG_AHEAD_FAIL_ALLOC", "GPH_RNG_AHEAD_PLACE")
 ITERS = 30
 
 
@@ -37,18 +37,6 @@ def G():
 def _pack(G, loci, mut):
     from gphocs_amd_pkg import synth
     return synth.make_synthetic_pack(G.Pack, 4, loci, mut_scale=mut, data_seed=4100 + loci, mcmc_seed=4242, samples_per_log=8)
-
-
-def _info(s):
-    fn = s.lib.gph_engine_rng_ahead_
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    info = np.zeros(4, dtype=np.int32)
-    assert fn(s.engine, info.ctypes.data, None, 0) == 0
-    kp = None
-    if info[0]:
-        kp = np.zeros(s.end - s.begin, dtype=np.int32)
-        assert fn(s.engine, None, kp.ctypes.data, 0) == 0
-    return tuple(int(v) for v in info), kp
 
 
 def _run(G, pk, setting, monkeypatch, tmp_path, body):
