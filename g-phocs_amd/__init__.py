@@ -266,18 +266,22 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("comm", C.c_void_p), ("rank", C.c_int32), ("world", C.c_int32), ("allreduce", ALLREDUCE_FN), ("user", C.c_void_p),
                 ("locus_summary_path", C.c_char_p), ("coal_stats_prefix", C.c_char_p), ("coal_stats_rows", C.c_int32),
                 ("time_slices", C.c_int32), ("ancestry_prefix", C.c_char_p), ("ancestry_rows", C.c_int32),
-                ("gene_trees_prefix", C.c_char_p), ("gene_trees_loci", C.c_char_p), ("gene_trees_rows", C.c_int32)]
+                ("gene_trees_prefix", C.c_char_p), ("gene_trees_loci", C.c_char_p), ("gene_trees_rows", C.c_int32),
+                ("clades_prefix", C.c_char_p), ("clades_loci", C.c_char_p), ("clades_slots", C.c_int32), ("clades_min_support", C.c_double)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
-                     ancestry=None, ancestry_rows=0, gene_trees=None, gene_trees_loci=None, gene_trees_rows=0):
+                     ancestry=None, ancestry_rows=0, gene_trees=None, gene_trees_loci=None, gene_trees_rows=0,
+                     clades=None, clades_loci=None, clades_slots=0, clades_min_support=None):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
                       locus_summary_path=b(locus_summary), coal_stats_prefix=b(coal_stats), coal_stats_rows=coal_stats_rows,
                       time_slices=time_slices, ancestry_prefix=b(ancestry), ancestry_rows=ancestry_rows,
-                      gene_trees_prefix=b(gene_trees), gene_trees_loci=b(gene_trees_loci), gene_trees_rows=gene_trees_rows)
+                      gene_trees_prefix=b(gene_trees), gene_trees_loci=b(gene_trees_loci), gene_trees_rows=gene_trees_rows,
+                      clades_prefix=b(clades), clades_loci=b(clades_loci), clades_slots=clades_slots,
+                      clades_min_support=0.0 if clades_min_support is None else -1.0 if clades_min_support == 0 else clades_min_support)
     return lib.gph_run(C.byref(o))
 
 
@@ -317,6 +321,8 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_gene_trees_enable", "gph_engine_gene_trees_sample", "gph_engine_gene_trees_shape", "gph_engine_gene_trees_selected",
     "gph_engine_gene_trees_fetch", "gph_gene_trees_write", "gph_gene_trees_discard", "gph_gene_trees_decode",
     "gph_gene_tree_newick", "gph_run", "gph_run_finish",
+    "gph_engine_clades_enable", "gph_engine_clades_sample", "gph_engine_clades_shape", "gph_engine_clades_selected",
+    "gph_engine_clades_fetch", "gph_clades_consensus", "gph_clades_write", "gph_clades_discard",
 ]
 
 
@@ -463,6 +469,16 @@ def _load_library(path):
     lib.gph_run_finish.argtypes = [C.POINTER(GphRunOptions), C.c_int32, C.c_int32]
     lib.gph_gene_tree_newick.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + \
         [C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gph_engine_clades_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int64]
+    lib.gph_engine_clades_sample.argtypes = [C.c_void_p]
+    lib.gph_engine_clades_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int64)]
+    lib.gph_engine_clades_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_clades_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.gph_clades_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_clades_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_clades_consensus.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     return lib
 
 
@@ -776,6 +792,29 @@ def gene_tree_newick(lib, age, father, left, right, npop, root, mig_branch, mig_
     if rc != 0:
         raise ValueError(f"gphocs_hip: gene_tree_newick refused the record or a name (status {rc})")
     return buf.value.decode()
+
+
+def clades_consensus(lib, keys, cnt, age, samples, leaf_labels):
+    """the majority-rule consensus of one locus's clade table -- keys (P, W), cnt (P), age (P) of Sampler.clades() at one locus,
+    over `samples` samples -- as (Newick text, resolved clades) (gph_clades_consensus: host only).  ValueError for a set of
+    clades that is no tree or a refused label"""
+    n = len(leaf_labels)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    P, W = keys.shape
+    ent = np.zeros((P, W + 2), dtype=np.uint64)
+    ent[:, :W] = keys
+    ent[:, W] = np.ascontiguousarray(cnt, dtype=np.uint64)
+    ent[:, W + 1] = np.ascontiguousarray(age, dtype=np.float64).view(np.uint64)
+    labels = (C.c_char_p * max(n, 1))(*[x.encode() for x in leaf_labels])
+    ln, res = C.c_size_t(), C.c_int32()
+    args = (n, P, ent.ctypes.data, int(samples), labels)
+    rc = lib.gph_clades_consensus(*args, None, 0, C.byref(ln), C.byref(res))
+    if rc == 0:
+        buf = C.create_string_buffer(ln.value + 1)
+        rc = lib.gph_clades_consensus(*args, buf, ln.value + 1, C.byref(ln), C.byref(res))
+    if rc != 0:
+        raise ValueError(f"gphocs_hip: clades_consensus refused the table or a label (status {rc})")
+    return buf.value.decode(), res.value
 
 
 def _dp(a):
@@ -1126,6 +1165,45 @@ class Sampler:
         if raw:
             out["records"] = rec
         return out
+
+    # ---- clade tables of selected loci (gph_engine_clades_*): accumulated on the device, one sample per call
+    def enable_clades(self, slots=0, loci=None, max_bytes=0):
+        """per-locus clade tables of `slots` physical slots (a power of two; 0: the smallest one >= 8 (n - 1)) for the selected
+        loci (as enable_gene_trees; None: all loci of this rank).  ValueError for refused slots or a refused selection,
+        MemoryError when the tables would exceed max_bytes (0: 1 GiB); the sampler stays usable"""
+        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
+        rc = self.lib.gph_engine_clades_enable(self.engine, int(slots), None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               0 if sel is None else len(sel), int(max_bytes))
+        if rc == GPH_EFULL:
+            raise MemoryError("gphocs_hip: the clade tables exceed max_bytes (GPH_EFULL)")
+        if rc == -1:
+            raise ValueError("gphocs_hip: clades_enable refused the slots or the selection (GPH_EARG)")
+        self._chk(rc, "clades_enable")
+
+    def sample_clades(self):
+        """one sample of the current state into the tables"""
+        self._chk(self.lib.gph_engine_clades_sample(self.engine), "clades_sample")
+
+    def _clades_shape(self):
+        q, P, W, lim, S = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self._chk(self.lib.gph_engine_clades_shape(self.engine, C.byref(q), C.byref(P), C.byref(W), C.byref(lim), C.byref(S)), "clades_shape")
+        return q.value, P.value, W.value, lim.value, S.value
+
+    def clades(self, reset=False):
+        """the tables of this rank's Q selected loci as the device holds them: a dict of loci[Q] (global indices), samples,
+        slots (P), words (W), limit, nkeys[Q], dropped[Q], keys (Q, P, W) uint64, cnt (Q, P) uint64 (0: an empty slot) and
+        age (Q, P) float64 (the age sums).  reset=True zeroes tables, header words and the sample count afterwards"""
+        Q, P, W, lim, S = self._clades_shape()
+        loci = np.zeros(max(Q, 1), dtype=np.int64)
+        cnt = C.c_int64()
+        self._chk(self.lib.gph_engine_clades_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)),
+                  "clades_selected")
+        ent = np.zeros((max(Q, 1), max(P, 1), W + 2), dtype=np.uint64)
+        nk, dr = np.zeros(max(Q, 1), dtype=np.uint32), np.zeros(max(Q, 1), dtype=np.uint32)
+        self._chk(self.lib.gph_engine_clades_fetch(self.engine, ent.ctypes.data, nk.ctypes.data, dr.ctypes.data, int(bool(reset))), "clades_fetch")
+        ent = ent[:Q, :P]
+        return dict(loci=loci[:Q].copy(), samples=S, slots=P, words=W, limit=lim, nkeys=nk[:Q].copy(), dropped=dr[:Q].copy(),
+                    keys=ent[:, :, :W].copy(), cnt=ent[:, :, W].copy(), age=ent[:, :, W + 1].copy().view(np.float64))
 
     def hbm_bytes(self):
         b = C.c_double()

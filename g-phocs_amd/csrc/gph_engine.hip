@@ -26,6 +26,7 @@
 #include "gph_timeslices.h"
 #include "gph_ancestry.h"
 #include "gph_genetrees.h"
+#include "gph_clades.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
 
@@ -468,7 +469,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 19     // (18: k_rng_ahead) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 20     // (18: k_rng_ahead, 19: k_clades) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -566,6 +567,10 @@ struct gph_engine_state {
   // sampled genealogies of selected loci (gph_genetrees.h): the rows of records, the selected loci of this rank (global indices,
   // increasing) with their slots in HBM, and the iterations of the rows held
   struct { SmRows rows; GphGtShape shape = {}; int32_t *d_sel = nullptr; std::vector<int64_t> sel; std::vector<int32_t> iters; } gt;
+  // clade tables of selected loci (gph_clades.h): entries [nsel][P][W + 2] and header words [nsel][2] in selection order, the
+  // selected loci of this rank with their slots in HBM, samples since the tables were last zeroed
+  struct { uint64_t *d_ent = nullptr; uint32_t *d_hdr = nullptr; int32_t *d_sel = nullptr; GphClShape shape = {}; std::vector<int64_t> sel;
+           int64_t samples = 0; bool on = false; } cl;
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -797,6 +802,8 @@ static void eng_free(gph_engine *e, void *p)
   else dev_free(p);
 }
 
+extern "C" { static int clades_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables) */
+
 static int check_error(gph_engine *e)
 {
   const int code = e->G_h->error;
@@ -961,6 +968,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   dev_free(e->gt.rows.d); dev_free(e->gt.d_sel);
+  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_sel);
   for (void *p : e->deferred_free) dev_free(p);
   e->deferred_free.clear();
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
@@ -1209,12 +1217,13 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   { int rcp = push_if_dirty(e); if (rcp) return rcp; }
   /* summaries of the old chain do not carry over; the locus-rate columns come and go with `locus-mut-rate VAR` */
   if (e->ls.d && e->ls.ncol != gph_ls_columns(e->cfg.K, e->cfg.B, e->var_rates)) { int rce = gph_engine_locus_summary_enable(e, 1); if (rce) return rce; }
-  e->ls.samples = e->an.samples = 0;
+  e->ls.samples = e->an.samples = e->cl.samples = 0;
   e->cs.rows.fill = e->ts.rows.fill = e->an.rows.fill = e->gt.rows.fill = 0;
   e->an.iters.clear();
   e->gt.iters.clear();
   { int rcz = acc_zero(e, e->ls.d, sizeof(double) * (size_t)e->ls.ncol * e->L); if (rcz) return rcz; }
   { int rcz = acc_zero(e, e->an.d_acc, sizeof(double) * (size_t)e->an.ncol * e->L); if (rcz) return rcz; }
+  { int rcz = clades_zero(e); if (rcz) return rcz; }
   int rc = launch_loci(e, 3, k_init, e->seedz, e->d_mutRate, e->init_predraws);
   if (!rc) rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -2773,6 +2782,125 @@ int gph_engine_gene_trees_fetch(gph_engine *e, int32_t *iters, void *out, int32_
   else { int rc = rows_fetch(e, b, out, rows); if (rc) return rc; }
   e->gt.iters.clear();
   return 0;
+}
+
+// ---- clade tables of selected loci (gph_clades.h)
+static size_t clades_entry_bytes(const gph_engine *e) { return sizeof(uint64_t) * e->cl.sel.size() * (size_t)e->cl.shape.P * e->cl.shape.ew; }
+static int clades_zero(gph_engine *e)
+{
+  if (!e->cl.on) return 0;
+  e->cl.samples = 0;
+  { int rcz = acc_zero(e, e->cl.d_ent, clades_entry_bytes(e)); if (rcz) return rcz; }
+  return acc_zero(e, e->cl.d_hdr, sizeof(uint32_t) * 2 * e->cl.sel.size());
+}
+static void clades_free(gph_engine *e)
+{
+  eng_free(e, e->cl.d_ent); eng_free(e, e->cl.d_hdr); eng_free(e, e->cl.d_sel);
+  e->cl.d_ent = nullptr; e->cl.d_hdr = nullptr; e->cl.d_sel = nullptr;
+  e->cl.sel.clear();
+  e->cl.shape = GphClShape{};
+  e->cl.samples = 0;
+  e->cl.on = false;
+}
+
+int gph_engine_clades_enable(gph_engine *e, int32_t slots, const int64_t *loci, int64_t nloci, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (slots != 0 && (slots < 2 || (slots & (slots - 1)) != 0)) return GPH_EARG;
+  if (loci && nloci < 0) return GPH_EARG;
+  if (loci)
+    for (int64_t k = 0; k < nloci; k++)
+      if (loci[k] < 0 || (k > 0 && loci[k] <= loci[k - 1])) return GPH_EARG;
+  SETDEV(e);
+  clades_free(e);
+  const int64_t L = e->L, lb = e->cfg.locus_begin;
+  std::vector<int64_t> sel;
+  if (!loci) for (int64_t g = 0; g < L; g++) sel.push_back(lb + g);
+  else for (int64_t k = 0; k < nloci; k++) if (loci[k] >= lb && loci[k] < lb + L) sel.push_back(loci[k]);
+  GphClShape h;
+  gph_cl_shape(e->lay, slots ? slots : gph_cl_default_slots(e->cfg.n), h);
+  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
+  const int64_t per = (int64_t)h.P * h.ew * 8 + 8, need = (int64_t)sel.size() * per;
+  if (need > limit) {
+    fprintf(stderr, "gphocs_hip: clades: the tables need %lld bytes (%lld loci x (%d slots x %d words x 8 + 8)), the limit is %lld\n",
+            (long long)need, (long long)sel.size(), (int)h.P, (int)h.ew, (long long)limit);
+    return GPH_EFULL;
+  }
+  /* selected -> slot, as for the gene trees */
+  std::vector<int32_t> slot_of((size_t)L), sel_slot(sel.size());
+  for (int64_t j = 0; j < L; j++) slot_of[(size_t)e->h_orig[j]] = (int32_t)j;
+  for (size_t q = 0; q < sel.size(); q++) sel_slot[q] = slot_of[(size_t)(sel[q] - lb)];
+  if (dev_alloc((void **)&e->cl.d_sel, sizeof(int32_t) * sel_slot.size()) ||
+      dev_alloc((void **)&e->cl.d_ent, sizeof(uint64_t) * sel.size() * (size_t)h.P * h.ew) ||
+      dev_alloc((void **)&e->cl.d_hdr, sizeof(uint32_t) * 2 * sel.size())) {
+    dev_clear_error();
+    clades_free(e);
+    return GPH_EHIP;
+  }
+  if (!sel_slot.empty()) { int rc = h2d(e, e->cl.d_sel, sel_slot.data(), sizeof(int32_t) * sel_slot.size()); if (rc) { clades_free(e); return rc; } }
+  e->cl.shape = h;
+  e->cl.sel.swap(sel);
+  e->cl.on = true;
+  return clades_zero(e);
+}
+
+// one sample of the current state, queued on the engine's stream
+int gph_engine_clades_sample(gph_engine *e)
+{
+  if (!e || !e->initialized || !e->cl.on) return GPH_ESTATE;
+  SETDEV(e);
+  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
+  const GphClShape &h = e->cl.shape;
+  const int nsel = (int)e->cl.sel.size(), L = (int)e->L;
+  const int groups = (nsel + h.G - 1) / h.G;
+  if (groups > 0 && e->cfg.n > 1) {        /* (a rank without a selected locus launches nothing; one leaf has no clade) */
+    int tms;
+    { int rcb = sample_begin(e, 19, tms); if (rcb) return rcb; }
+    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_CL_THREADS, (size_t)h.lds_bytes, k_clades, e->lay, h, e->dev.pages, e->cl.d_sel, nsel, L,
+                            e->cl.d_ent, e->cl.d_hdr);
+      if (rcl) return rcl; }
+    sample_end(e, 19, 1, tms);
+  }
+  e->cl.samples++;
+  return 0;
+}
+
+int gph_engine_clades_shape(gph_engine *e, int64_t *selected, int32_t *slots, int32_t *words, int32_t *limit, int64_t *samples)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->cl.on;
+  if (selected) *selected = on ? (int64_t)e->cl.sel.size() : 0;
+  if (slots) *slots = on ? e->cl.shape.P : 0;
+  if (words) *words = on ? e->cl.shape.W : 0;
+  if (limit) *limit = on ? e->cl.shape.limit : 0;
+  if (samples) *samples = on ? e->cl.samples : 0;
+  return 0;
+}
+
+int gph_engine_clades_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
+{
+  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
+  if (!e->cl.on) return GPH_ESTATE;
+  *count = (int64_t)e->cl.sel.size();
+  if (max_loci < *count) return out ? GPH_EARG : 0;
+  for (size_t q = 0; q < e->cl.sel.size(); q++) out[q] = e->cl.sel[q];
+  return 0;
+}
+
+int gph_engine_clades_fetch(gph_engine *e, uint64_t *entries, uint32_t *nkeys, uint32_t *dropped, int32_t reset)
+{
+  if (!e) return GPH_EARG;
+  if (!e->cl.on) return GPH_ESTATE;
+  const size_t nsel = e->cl.sel.size();
+  if (nsel > 0 && (!entries || !nkeys || !dropped)) return GPH_EARG;
+  SETDEV(e);
+  if (nsel > 0) {
+    std::vector<uint32_t> hdr(2 * nsel);
+    { int rc = d2h(e, entries, e->cl.d_ent, clades_entry_bytes(e)); if (rc) return rc; }
+    { int rc = d2h(e, hdr.data(), e->cl.d_hdr, sizeof(uint32_t) * 2 * nsel); if (rc) return rc; }
+    for (size_t q = 0; q < nsel; q++) { nkeys[q] = hdr[2 * q]; dropped[q] = hdr[2 * q + 1]; }
+  }
+  return reset ? clades_zero(e) : 0;
 }
 
 } // extern "C"

@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -16,7 +16,11 @@
 // between two flushes, default 64), with --time-slices S additionally per time slice; --ancestry PREFIX, which sample's
 // lineage went through which migration band at which locus; --gene-trees PREFIX, the sampled genealogy of every selected
 // locus at every sample as a line of extended Newick (--gene-trees-loci SPEC: a comma list of i, i-j or i-j:step, 0-based in
-// sequence-file order, default all; --gene-trees-rows N: rows of the device buffer, default 64, fewer when a row is large).
+// sequence-file order, default all; --gene-trees-rows N: rows of the device buffer, default 64, fewer when a row is large);
+// --clades PREFIX, per selected locus the clades its sampled genealogies support, with posterior probability and mean age,
+// and its majority-rule consensus tree, from tables accumulated on the device (--clades-loci SPEC as --gene-trees-loci;
+// --clades-slots P: slots of a locus's table, a power of two, default the smallest one >= 8 (leaves - 1); --clades-min-support
+// F: the clades listed have support >= F, default 0.5, 0 lists every kept clade).
 // They compose freely.  Under -g N every child leaves parts: of the summary table FILE.part<r>, which the launcher
 // concatenates in rank order into FILE once every child has exited 0; of the others the library's own, which gph_run_finish
 // turns into the files (the launcher itself has not touched a GPU).  A run that did not finish leaves neither parts nor files.
@@ -92,7 +96,7 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
@@ -114,12 +118,25 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--gene-trees") && i + 1 < argc) o.gene_trees_prefix = argv[++i];
     else if (!strcmp(argv[i], "--gene-trees-loci") && i + 1 < argc) o.gene_trees_loci = argv[++i];
     else if (!strcmp(argv[i], "--gene-trees-rows") && i + 1 < argc) { o.gene_trees_rows = atoi(argv[++i]); if (o.gene_trees_rows < 1) return usage(argv[0]); }
+    else if (!strcmp(argv[i], "--clades") && i + 1 < argc) o.clades_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--clades-loci") && i + 1 < argc) o.clades_loci = argv[++i];
+    else if (!strcmp(argv[i], "--clades-slots") && i + 1 < argc) {
+      o.clades_slots = atoi(argv[++i]);
+      if (o.clades_slots < 2 || (o.clades_slots & (o.clades_slots - 1))) { fprintf(stderr, "%s: --clades-slots takes a power of two >= 2\n", argv[0]); return usage(argv[0]); }
+    }
+    else if (!strcmp(argv[i], "--clades-min-support") && i + 1 < argc) {
+      char *end = nullptr;
+      const double F = strtod(argv[++i], &end);
+      if (end == argv[i] || *end || !(F >= 0.0 && F <= 1.0)) { fprintf(stderr, "%s: --clades-min-support takes a number in [0, 1]\n", argv[0]); return usage(argv[0]); }
+      o.clades_min_support = F == 0.0 ? -1.0 : F;      /* (0 in the options struct means the default) */
+    }
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
   if (i >= argc || gpus < 1 || gpus > 64) return usage(argv[0]);
   if (o.time_slices && !o.coal_stats_prefix) { fprintf(stderr, "%s: --time-slices needs -s PREFIX\n", argv[0]); return usage(argv[0]); }
   if ((o.gene_trees_loci || o.gene_trees_rows) && !o.gene_trees_prefix) { fprintf(stderr, "%s: --gene-trees-loci and --gene-trees-rows need --gene-trees PREFIX\n", argv[0]); return usage(argv[0]); }
+  if ((o.clades_loci || o.clades_slots || o.clades_min_support != 0.0) && !o.clades_prefix) { fprintf(stderr, "%s: --clades-loci, --clades-slots and --clades-min-support need --clades PREFIX\n", argv[0]); return usage(argv[0]); }
   o.ctl = argv[i];
   o.ctl2 = i + 1 < argc ? argv[i + 1] : nullptr;
   char self[PATH_MAX];
@@ -225,7 +242,7 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(o.locus_summary_path); bad = 1; }
     if (bad && out) unlink(o.locus_summary_path);
   }
-  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix) {
+  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix) {
     /* the ranks' parts into the files, by the library that wrote them -- or, after a failure, removed */
     if (sym<decltype(&gph_run_finish)>(load_engine(dir, o.ctl, o.ctl2), "gph_run_finish")(&o, gpus, bad)) bad = 1;
   }

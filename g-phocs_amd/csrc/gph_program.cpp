@@ -496,6 +496,101 @@ extern "C" int gph_gene_tree_newick(int32_t n, const double *age, const int32_t 
   return GPH_OK;
 }
 
+// ---- clade tables (gph_engine_clades_*): the majority-rule consensus of one locus's table as text
+namespace {
+struct ClNode {
+  const uint64_t *key;       // nullptr: the unannotated top level of a table that does not hold the root's clade
+  uint64_t cnt;
+  double age;
+  int size, low, parent;     // leaves, smallest leaf, enclosing clade (-1: none)
+  std::vector<int> kids;     // >= 0: clade, < 0: leaf -1 - i
+};
+int cl_popcount(const uint64_t *k, int W) { int c = 0; for (int w = 0; w < W; w++) c += __builtin_popcountll(k[w]); return c; }
+int cl_low(const uint64_t *k, int W) { for (int w = 0; w < W; w++) if (k[w]) return 64 * w + __builtin_ctzll(k[w]); return -1; }
+void cl_emit(const std::vector<ClNode> &nd, int v, const char *const *labels, int64_t S, std::string &out)
+{
+  if (v < 0) { out += labels[-1 - v]; return; }
+  out += '(';
+  for (size_t c = 0; c < nd[v].kids.size(); c++) {
+    if (c) out += ',';
+    cl_emit(nd, nd[v].kids[c], labels, S, out);
+  }
+  out += ')';
+  if (nd[v].key) out += "[&support=" + gt_len((double)nd[v].cnt / (double)S) + ",age=" + gt_len(nd[v].age / (double)nd[v].cnt) + "]";
+}
+}   // namespace
+
+extern "C" int gph_clades_consensus(int32_t n, int32_t slots, const uint64_t *entries, int64_t samples, const char *const *leaf_labels,
+                                    char *out, size_t out_cap, size_t *out_len, int32_t *resolved)
+{
+  if (n < 1 || slots < 0 || (slots > 0 && !entries) || samples < 0 || !leaf_labels) return GPH_EARG;
+  for (int i = 0; i < n; i++)
+    if (!gt_name_ok(leaf_labels[i])) {
+      fprintf(stderr, "gphocs_hip: clades: the leaf label '%s' cannot stand in a tree (white space or one of ()[],:;'=&)\n", leaf_labels[i] ? leaf_labels[i] : "");
+      return GPH_EARG;
+    }
+  const int W = (n + 63) / 64, ew = W + 2;
+  std::vector<ClNode> nd;
+  for (int s = 0; s < slots; s++) {
+    const uint64_t *en = entries + (size_t)s * ew;
+    if (en[W] == 0 || 2 * en[W] <= (uint64_t)samples) continue;
+    ClNode c;
+    c.key = en; c.cnt = en[W]; memcpy(&c.age, en + W + 1, 8);
+    c.size = cl_popcount(en, W); c.low = cl_low(en, W); c.parent = -1;
+    bool inside = c.size >= 2;                                  /* no bit beyond the leaves, two leaves at least */
+    for (int w = 0; w < W; w++) {
+      const int top = n - 64 * w;
+      if (top < 64 && (en[w] >> (top > 0 ? top : 0)) != 0) inside = false;
+    }
+    if (!inside) { fprintf(stderr, "gphocs_hip: clades: an entry of the table is no clade of %d leaves\n", (int)n); return GPH_EARG; }
+    nd.push_back(c);
+  }
+  const int m = (int)nd.size();
+  /* a set of clades is a tree iff every two are nested or disjoint */
+  for (int a = 0; a < m; a++)
+    for (int b = a + 1; b < m; b++) {
+      bool meet = false, a_in_b = true, b_in_a = true;
+      for (int w = 0; w < W; w++) {
+        const uint64_t x = nd[a].key[w], y = nd[b].key[w];
+        meet = meet || (x & y) != 0; a_in_b = a_in_b && (x & ~y) == 0; b_in_a = b_in_a && (y & ~x) == 0;
+      }
+      if ((meet && !a_in_b && !b_in_a) || (a_in_b && b_in_a)) {
+        fprintf(stderr, "gphocs_hip: clades: two clades of the consensus are %s: no tree holds both\n", a_in_b && b_in_a ? "equal" : "neither nested nor disjoint");
+        return GPH_EARG;
+      }
+      if (a_in_b && (nd[a].parent < 0 || nd[b].size < nd[nd[a].parent].size)) nd[a].parent = b;
+      if (b_in_a && (nd[b].parent < 0 || nd[a].size < nd[nd[b].parent].size)) nd[b].parent = a;
+    }
+  int top = -1;
+  for (int a = 0; a < m; a++) if (nd[a].size == n) top = a;
+  if (top < 0) {
+    ClNode c;
+    c.key = nullptr; c.cnt = 0; c.age = 0.0; c.size = n; c.low = 0; c.parent = -1;
+    nd.push_back(c);
+    top = m;
+    for (int a = 0; a < m; a++) if (nd[a].parent < 0) nd[a].parent = top;
+  }
+  for (int a = 0; a < m; a++) if (a != top) nd[nd[a].parent].kids.push_back(a);
+  for (int i = 0; i < n; i++) {
+    int best = top;
+    for (int a = 0; a < m; a++)
+      if (((nd[a].key[i / 64] >> (i % 64)) & 1) && nd[a].size < nd[best].size) best = a;
+    nd[best].kids.push_back(-1 - i);
+  }
+  for (auto &c : nd)
+    std::sort(c.kids.begin(), c.kids.end(), [&](int a, int b) { return (a < 0 ? -1 - a : nd[a].low) < (b < 0 ? -1 - b : nd[b].low); });
+  std::string text;
+  if (n == 1) text = leaf_labels[0];
+  else cl_emit(nd, top, leaf_labels, samples, text);
+  text += ';';
+  if (resolved) *resolved = m;
+  if (out_len) *out_len = text.size();
+  if (!out) return GPH_OK;
+  if (out_cap < text.size() + 1) return 2;
+  memcpy(out, text.c_str(), text.size() + 1);
+  return GPH_OK;
+}
+
 extern "C" int gph_gene_trees_decode(const void *records, int64_t count, int32_t record_bytes, const int32_t *off, int32_t N,
                                      double *age, int32_t *father, int32_t *left, int32_t *right, int32_t *npop, int32_t *root, int32_t *num_migs,
                                      double *dataLnL, double *genLnL, int32_t *mig_branch, int32_t *mig_band, int32_t *mig_spop, int32_t *mig_tpop,
@@ -651,9 +746,63 @@ extern "C" int gph_gene_trees_write(const char *prefix, int32_t ranks)
   return ok ? GPH_OK : GPH_EARG;
 }
 
+// ---- clade tables (`--clades PREFIX`).  Rank r's part PREFIX.clades.part<r> is text, written once when the chain is done:
+// a first line GPHCL1, the rank's rows of the two files -- "C\t" + a row of PREFIX.clades.tsv, "T\t" + a row of
+// PREFIX.consensus.tsv, locus by locus -- and a last line "E\t<rows>", written when the rank closes its part
+namespace {
+const PartFormat CL_PART = {{'G', 'P', 'H', 'C', 'L', '1', '\n', 0}, ".clades.part", 0, nullptr, false, nullptr, nullptr, 0, true};
+const char *const CL_FILES[2] = {".clades.tsv", ".consensus.tsv"};
+}   // namespace
+
+extern "C" int gph_clades_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  remove_parts(CL_PART, prefix, ranks);
+  for (const char *sfx : CL_FILES) unlink((std::string(prefix) + sfx).c_str());     /* (files only: whatever else sits there is not ours) */
+  return GPH_OK;
+}
+
+extern "C" int gph_clades_write(const char *prefix, int32_t ranks)
+{
+  if (!prefix || ranks < 1) return GPH_EARG;
+  FILE *out[2] = {nullptr, nullptr};
+  bool ok = true;
+  for (int k = 0; k < 2 && ok; k++)
+    if (!(out[k] = fopen((std::string(prefix) + CL_FILES[k]).c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s%s\n", prefix, CL_FILES[k]); ok = false; }
+  if (ok) {
+    fprintf(out[0], "locus\tname\tsamples\tdropped\tsize\tsupport\tmeanAge\tmembers\n");
+    fprintf(out[1], "locus\tname\tsamples\tdistinct\tdropped\tresolved\ttree\n");
+  }
+  for (int r = 0; r < ranks && ok; r++) {
+    const std::string path = part_path(CL_PART, prefix, r);
+    FILE *in = fopen(path.c_str(), "r");
+    char *line = nullptr;
+    size_t cap = 0;
+    ssize_t len;
+    long long rows = 0, told = -1;
+    bool first = true;
+    while (in && ok && (len = getline(&line, &cap, in)) > 0) {
+      if (first) { ok = !strcmp(line, "GPHCL1\n"); first = false; continue; }
+      if (told >= 0) { ok = false; break; }                      /* something behind the last line */
+      if (line[0] == 'E' && line[1] == '\t') { told = atoll(line + 2); continue; }
+      ok = len > 2 && line[1] == '\t' && (line[0] == 'C' || line[0] == 'T') && line[len - 1] == '\n';
+      if (ok) { fputs(line + 2, out[line[0] == 'C' ? 0 : 1]); rows++; }
+    }
+    free(line);
+    if (in) fclose(in);
+    if (!in || !ok || first || told != rows) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); ok = false; }
+  }
+  for (int k = 0; k < 2; k++)
+    if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s%s failed\n", prefix, CL_FILES[k]); ok = false; }
+  remove_parts(CL_PART, prefix, ranks);
+  if (!ok)
+    for (int k = 0; k < 2; k++) if (out[k]) remove((std::string(prefix) + CL_FILES[k]).c_str());
+  return ok ? GPH_OK : GPH_EARG;
+}
+
 // the selection of `--gene-trees-loci SPEC`: a comma list of i, i-j (both ends included) or i-j:step over 0 .. L - 1, sorted;
 // an index named twice or beyond the loci is refused by name
-static int gt_parse_spec(const char *spec, int64_t L, std::vector<int64_t> &sel, bool &all)
+static int gt_parse_spec(const char *spec, int64_t L, std::vector<int64_t> &sel, bool &all, const char *opt = "--gene-trees-loci")
 {
   sel.clear();
   all = !spec || !strcmp(spec, "all");
@@ -672,21 +821,21 @@ static int gt_parse_spec(const char *spec, int64_t L, std::vector<int64_t> &sel,
     if (!number(a)) break;
     b = a;
     if (*p == '-') { p++; if (!number(b) || b < a) break; if (*p == ':') { p++; if (!number(step) || step < 1) break; } }
-    if (a >= L) { fprintf(stderr, "gphocs_hip: --gene-trees-loci: locus %lld is beyond the %lld loci of the sequence file (indices are 0-based)\n", (long long)a, (long long)L); return GPH_EARG; }
+    if (a >= L) { fprintf(stderr, "gphocs_hip: %s: locus %lld is beyond the %lld loci of the sequence file (indices are 0-based)\n", opt, (long long)a, (long long)L); return GPH_EARG; }
     for (int64_t g = a; g <= b; g += step) {
-      if (g >= L) { fprintf(stderr, "gphocs_hip: --gene-trees-loci: locus %lld is beyond the %lld loci of the sequence file (indices are 0-based)\n", (long long)g, (long long)L); return GPH_EARG; }
+      if (g >= L) { fprintf(stderr, "gphocs_hip: %s: locus %lld is beyond the %lld loci of the sequence file (indices are 0-based)\n", opt, (long long)g, (long long)L); return GPH_EARG; }
       sel.push_back(g);
     }
     if (*p == ',') { p++; continue; }
     if (*p == 0) {
       std::sort(sel.begin(), sel.end());
       for (size_t k = 1; k < sel.size(); k++)
-        if (sel[k] == sel[k - 1]) { fprintf(stderr, "gphocs_hip: --gene-trees-loci: locus %lld is named twice\n", (long long)sel[k]); return GPH_EARG; }
+        if (sel[k] == sel[k - 1]) { fprintf(stderr, "gphocs_hip: %s: locus %lld is named twice\n", opt, (long long)sel[k]); return GPH_EARG; }
       return GPH_OK;
     }
     break;
   }
-  fprintf(stderr, "gphocs_hip: --gene-trees-loci: '%s' is not a comma list of i, i-j or i-j:step (0-based indices), nor 'all'\n", spec);
+  fprintf(stderr, "gphocs_hip: %s: '%s' is not a comma list of i, i-j or i-j:step (0-based indices), nor 'all'\n", opt, spec);
   return GPH_EARG;
 }
 
@@ -1111,6 +1260,33 @@ struct Ancestry : Output {
   void discard(int32_t ranks) override { gph_ancestry_discard(prefix, ranks); }
 };
 
+// the names that will stand in trees and member lists, once the control file is read and before anything is computed
+static int tree_names_ok(Run &R, const char *opt)
+{
+  auto refuse = [&](const char *kind, const char *nm) {
+    snprintf(R.err, sizeof R.err, "the %s name '%s' cannot stand in a tree (white space or one of ()[],:;'=&)", kind, nm);
+    return R.fail(GPH_EARG, opt);
+  };
+  for (int p = 0; p < R.cfg.K; p++)
+    if (!gt_name_ok(gph_control_pop_name(R.C, p))) return refuse("population", gph_control_pop_name(R.C, p));
+  for (const std::string &nm : leaf_names(R.C, R.cfg))
+    if (!gt_name_ok(nm.c_str())) return refuse("sample", nm.c_str());
+  return GPH_OK;
+}
+// a selection SPEC over the loci just read: this rank's share of it, and the share of the rank that holds most
+static int select_loci(Run &R, const char *spec, const char *opt, std::vector<int64_t> &sel, int64_t &widest)
+{
+  std::vector<int64_t> all_sel, held_by(R.world, 0);
+  bool all = true;
+  if (int rc = gt_parse_spec(spec, R.L, all_sel, all, opt)) return R.fail(rc, opt);
+  if (all) for (int64_t g = 0; g < R.L; g++) all_sel.push_back(g);
+  for (int64_t g : all_sel) {
+    widest = std::max(widest, ++held_by[g / R.per]);
+    if (g >= R.lb && g < R.le) sel.push_back(g);
+  }
+  return GPH_OK;
+}
+
 // sampled genealogies: the row buffer for this rank's selected loci; the part's samples each behind their iteration
 struct GeneTrees : Output {
   const char *prefix, *spec;
@@ -1126,32 +1302,8 @@ struct GeneTrees : Output {
     if (!o.gene_trees_prefix && (o.gene_trees_loci || o.gene_trees_rows != 0)) { fprintf(stderr, "gphocs_hip: a gene-trees selection or row count needs a gene-trees prefix\n"); return GPH_EARG; }
     return o.gene_trees_rows < 0 ? GPH_EARG : GPH_OK;
   }
-  /* the names that will stand in the trees, once the control file is read and before anything is computed */
-  int check_names(Run &R)
-  {
-    auto refuse = [&](const char *kind, const char *nm) {
-      snprintf(R.err, sizeof R.err, "the %s name '%s' cannot stand in a tree (white space or one of ()[],:;'=&)", kind, nm);
-      return R.fail(GPH_EARG, "--gene-trees");
-    };
-    for (int p = 0; p < R.cfg.K; p++)
-      if (!gt_name_ok(gph_control_pop_name(R.C, p))) return refuse("population", gph_control_pop_name(R.C, p));
-    for (const std::string &nm : leaf_names(R.C, R.cfg))
-      if (!gt_name_ok(nm.c_str())) return refuse("sample", nm.c_str());
-    return GPH_OK;
-  }
-  /* the selection over the loci just read, and this rank's share of it */
-  int select(Run &R)
-  {
-    std::vector<int64_t> all_sel, held_by(R.world, 0);
-    bool all = true;
-    if (int rc = gt_parse_spec(spec, R.L, all_sel, all)) return R.fail(rc, "--gene-trees-loci");
-    if (all) for (int64_t g = 0; g < R.L; g++) all_sel.push_back(g);
-    for (int64_t g : all_sel) {
-      widest = std::max(widest, ++held_by[g / R.per]);
-      if (g >= R.lb && g < R.le) sel.push_back(g);
-    }
-    return GPH_OK;
-  }
+  int check_names(Run &R) { return tree_names_ok(R, "--gene-trees"); }
+  int select(Run &R) { return select_loci(R, spec, "--gene-trees-loci", sel, widest); }
   int open(Run &R) override
   {
     /* the bytes of a record (the same on every rank) from an empty selection, then the rows that fit */
@@ -1194,6 +1346,108 @@ struct GeneTrees : Output {
   void discard(int32_t ranks) override { gph_gene_trees_discard(prefix, ranks); }
 };
 
+// clade tables: accumulated on the device over the whole run, fetched once; this rank's rows of the two files as its part
+struct Clades : Output {
+  const char *prefix, *spec;
+  int32_t slots;
+  double F;
+  std::vector<int64_t> sel;          /* this rank's selected loci (global indices) */
+  int64_t widest = 0;
+  FILE *f = nullptr;
+  explicit Clades(const gph_run_options &o) : prefix(o.clades_prefix), spec(o.clades_loci), slots(o.clades_slots),
+                                              F(o.clades_min_support == 0.0 ? 0.5 : o.clades_min_support < 0.0 ? 0.0 : o.clades_min_support) {}
+  ~Clades() { if (f) fclose(f); }
+  static int validate(const gph_run_options &o)
+  {
+    if (!o.clades_prefix && (o.clades_loci || o.clades_slots != 0 || o.clades_min_support != 0.0)) {
+      fprintf(stderr, "gphocs_hip: a clades selection, slot count or support threshold needs a clades prefix\n");
+      return GPH_EARG;
+    }
+    if (o.clades_slots != 0 && (o.clades_slots < 2 || (o.clades_slots & (o.clades_slots - 1)) != 0)) {
+      fprintf(stderr, "gphocs_hip: clades: %d slots are no power of two >= 2\n", (int)o.clades_slots);
+      return GPH_EARG;
+    }
+    if (!(o.clades_min_support <= 1.0)) { fprintf(stderr, "gphocs_hip: clades: the support threshold lies in [0, 1]\n"); return GPH_EARG; }
+    return GPH_OK;
+  }
+  int check_names(Run &R) { return tree_names_ok(R, "--clades"); }
+  int select(Run &R) { return select_loci(R, spec, "--clades-loci", sel, widest); }
+  int open(Run &R) override
+  {
+    const int64_t none = 0;
+    /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
+    if (int rc = gph_engine_clades_enable(R.E, slots, sel.empty() ? &none : sel.data(), (int64_t)sel.size(), 0)) {
+      if (rc == GPH_EFULL) snprintf(R.err, sizeof R.err, "the tables exceed 1 GiB: narrow --clades-loci or lower --clades-slots");
+      return R.fail(rc, "gph_engine_clades_enable");
+    }
+    if (!(f = fopen(part_path(CL_PART, prefix, R.rank).c_str(), "w"))) {
+      snprintf(R.err, sizeof R.err, "Could not open %s", part_path(CL_PART, prefix, R.rank).c_str());
+      return R.fail(GPH_EARG, "opening the clades part file");
+    }
+    fputs("GPHCL1\n", f);
+    return GPH_OK;
+  }
+  int sample(Run &R, int) override { return R.check(gph_engine_clades_sample(R.E), "gph_engine_clades_sample"); }
+  int close(Run &R) override
+  {
+    int32_t P = 0, W = 0;
+    int64_t S = 0;
+    gph_engine_clades_shape(R.E, nullptr, &P, &W, nullptr, &S);
+    const int n = R.cfg.n, ew = W + 2;
+    std::vector<uint64_t> ent(sel.size() * (size_t)P * ew + 1);
+    std::vector<uint32_t> nkeys(sel.size() + 1), dropped(sel.size() + 1);
+    if (int rc = gph_engine_clades_fetch(R.E, ent.data(), nkeys.data(), dropped.data(), 0)) return R.fail(rc, "gph_engine_clades_fetch");
+    std::vector<std::string> labels = leaf_names(R.C, R.cfg);
+    std::vector<const char *> lab;
+    for (int i = 0; i < n; i++) labels[(size_t)i] += "." + std::to_string(i);
+    for (int i = 0; i < n; i++) lab.push_back(labels[(size_t)i].c_str());
+    long long rows = 0;
+    std::vector<const uint64_t *> kept;
+    std::string tree;
+    for (size_t q = 0; q < sel.size(); q++) {
+      const uint64_t *tab = ent.data() + q * (size_t)P * ew;
+      const char *nm = gph_loci_name(R.LC, sel[q]);
+      kept.clear();
+      for (int s = 0; s < P; s++) {
+        const uint64_t *en = tab + (size_t)s * ew;
+        if (en[W] != 0 && (double)en[W] / (double)S >= F) kept.push_back(en);
+      }
+      auto size_of = [&](const uint64_t *en) { int c = 0; for (int w = 0; w < W; w++) c += __builtin_popcountll(en[w]); return c; };
+      std::sort(kept.begin(), kept.end(), [&](const uint64_t *a, const uint64_t *b) {
+        if (a[W] != b[W]) return a[W] > b[W];
+        const int sa = size_of(a), sb = size_of(b);
+        if (sa != sb) return sa < sb;
+        for (int w = W - 1; w >= 0; w--) if (a[w] != b[w]) return a[w] < b[w];
+        return false;
+      });
+      for (const uint64_t *en : kept) {
+        double age;
+        memcpy(&age, en + W + 1, 8);
+        fprintf(f, "C\t%lld\t%s\t%lld\t%u\t%d\t%.10g\t%.10g\t", (long long)sel[q], nm ? nm : "", (long long)S, (unsigned)dropped[q], size_of(en),
+                (double)en[W] / (double)S, age / (double)en[W]);
+        bool some = false;
+        for (int i = 0; i < n; i++)
+          if ((en[i / 64] >> (i % 64)) & 1) { fprintf(f, "%s%s", some ? "," : "", lab[(size_t)i]); some = true; }
+        fputc('\n', f);
+        rows++;
+      }
+      size_t len = 0;
+      int32_t resolved = 0;
+      int rc = gph_clades_consensus(n, P, tab, S, lab.data(), nullptr, 0, &len, &resolved);
+      if (!rc) { tree.assign(len + 1, '\0'); rc = gph_clades_consensus(n, P, tab, S, lab.data(), &tree[0], len + 1, &len, &resolved); }
+      if (rc) { snprintf(R.err, sizeof R.err, "the table of locus %lld gives no consensus tree", (long long)sel[q]); return R.fail(rc, "gph_clades_consensus"); }
+      fprintf(f, "T\t%lld\t%s\t%lld\t%u\t%u\t%d\t%s\n", (long long)sel[q], nm ? nm : "", (long long)S, (unsigned)nkeys[q], (unsigned)dropped[q], (int)resolved, tree.c_str());
+      rows++;
+    }
+    fprintf(f, "E\t%lld\n", rows);
+    const int rcc = ferror(f) | fclose(f);
+    f = nullptr;
+    return R.check(rcc ? GPH_EARG : GPH_OK, "writing the clades part file");
+  }
+  int write(int32_t ranks) override { return gph_clades_write(prefix, ranks); }
+  void discard(int32_t ranks) override { gph_clades_discard(prefix, ranks); }
+};
+
 // the enabled outputs in the order of their engine calls at a sample, which is also the order in which gph_run_finish writes
 // their files (the groups of fewer files first: should a later one fail, fewer are removed again).  A run closes them in the
 // opposite order, as it always did, and opens them in that order too: the summary is now enabled last, not first
@@ -1201,9 +1455,11 @@ struct Outputs {
   std::vector<std::unique_ptr<Output>> list;
   LocusSummary *summary = nullptr;   /* these two have a step of their own in run_chain */
   GeneTrees *trees = nullptr;
+  Clades *clades = nullptr;
   explicit Outputs(const gph_run_options &o)
   {
     if (o.locus_summary_path) list.emplace_back(summary = new LocusSummary);
+    if (o.clades_prefix) list.emplace_back(clades = new Clades(o));
     if (o.gene_trees_prefix) list.emplace_back(trees = new GeneTrees(o));
     if (o.ancestry_prefix) list.emplace_back(new Ancestry(o));
     if (o.coal_stats_prefix) list.emplace_back(new CoalStats(o));
@@ -1360,8 +1616,10 @@ int run_chain(const gph_run_options &o)
   int rc;
   if ((rc = R.read_control())) return rc;
   if (outs.trees && (rc = outs.trees->check_names(R))) return rc;
+  if (outs.clades && (rc = outs.clades->check_names(R))) return rc;
   if ((rc = R.read_loci())) return rc;
   if (outs.trees && (rc = outs.trees->select(R))) return rc;
+  if (outs.clades && (rc = outs.clades->select(R))) return rc;
   if ((rc = R.start_engine()) || (rc = R.open_trace())) return rc;
 
   const gph_control_info &info = R.info;
@@ -1401,7 +1659,7 @@ int run_chain(const gph_run_options &o)
   R.release_device();
   if (checked && where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
     return GPH_EKERNEL;
   }
   return outs.summary ? outs.summary->write_table(R) : GPH_OK;
@@ -1431,7 +1689,7 @@ extern "C" int gph_run(const gph_run_options *in)
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
   /* the checks on the options alone, before anything is read */
   int rc;
-  if ((rc = GeneTrees::validate(o)) || (rc = CoalStats::validate(o))) return rc;
+  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = CoalStats::validate(o))) return rc;
   rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
   if (o.world == 1) {

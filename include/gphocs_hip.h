@@ -226,7 +226,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * 11 locus-rate prepare, 13 locus summary (gph_engine_locus_summary_sample), 14 coalescent / sample-pair statistics
  * (gph_engine_coal_stats_sample: k_coal_stats + k_rows_fold together), 15 time-sliced statistics
  * (gph_engine_time_slices_sample: k_time_slices + k_rows_fold together), 16 migration ancestry
- * (gph_engine_ancestry_sample: k_ancestry) */
+ * (gph_engine_ancestry_sample: k_ancestry), 17 sampled genealogies (gph_engine_gene_trees_sample: k_gene_trees), 18 the
+ * sweep's draws generated ahead of it (k_rng_ahead), 19 clade tables (gph_engine_clades_sample: k_clades) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -418,6 +419,34 @@ int gph_engine_gene_trees_sample(gph_engine *e, int32_t iteration);
 int gph_engine_gene_trees_shape(gph_engine *e, int64_t *selected, int32_t *nodes, int32_t *record_bytes, int32_t *offsets, int32_t *rows_held);
 int gph_engine_gene_trees_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
 int gph_engine_gene_trees_fetch(gph_engine *e, int32_t *iters, void *out, int32_t max_rows, int32_t *rows);
+/* CLADE TABLES per selected locus, accumulated on the device over the samples taken (k_clades: csrc/gph_clades.h).  With n
+ * leaves, N = 2n - 1 nodes and W = ceil(n / 64): the clade of internal node v is the set of leaves whose path to the root
+ * contains v, as W 64-bit words (bit i % 64 of word i / 64), the root's clade (all leaves) included.  A locus's TABLE has
+ * `slots` physical slots (a power of two >= 2) and holds at most limit = 3 slots / 4 distinct clades; an entry is key[W],
+ * cnt, age (the bit pattern of an fp64), cnt = 0 marks an empty slot; nkeys and dropped are kept per locus.  A sample takes
+ * the internal nodes v = n .. N - 1 in node-index order: key in the table -> cnt += 1, age = age + age[v] (one plain fp64
+ * addition: the sums can be rebuilt bit for bit in sample order); else nkeys < limit -> insert with cnt = 1, age = age[v],
+ * nkeys += 1; else dropped += 1.  Hence: counts of kept clades are exact; a table never leaves the full state and a clade
+ * dropped once is never inserted later; the root key has cnt = samples; sum of cnt + dropped = samples x (n - 1).  Where an
+ * entry lies inside its table is unspecified.
+ *   _enable(slots, loci, nloci, max_bytes)  slots 0: the smallest power of two >= 8 (n - 1); any other value that is no
+ *                      power of two or below 2 is GPH_EARG.  The selection as for gph_engine_gene_trees_enable (loci NULL:
+ *                      all loci of the rank).  GPH_EFULL (with a message, nothing allocated, the feature off) when the tables
+ *                      exceed max_bytes (<= 0: 1 GiB).  Everything is allocated here and freed with the engine;
+ *                      gph_engine_init_genealogies zeroes the tables and the sample count
+ *   _sample            GPH_ESTATE when not enabled or not initialised.  One kernel (none on a rank without a selected locus,
+ *                      which still counts the sample), no host synchronisation, no exchange; the state is settled as for
+ *                      gph_engine_ancestry_sample
+ *   _shape             selected loci of this rank, slots, W, limit, samples since the tables were last zeroed (any pointer
+ *                      may be NULL; all 0 while the feature is off)
+ *   _selected          as gph_engine_gene_trees_selected
+ *   _fetch             entries[selected][slots][W + 2] in selection order, nkeys[selected], dropped[selected] (one host
+ *                      synchronisation); reset != 0 then zeroes tables, header words and the sample count */
+int gph_engine_clades_enable(gph_engine *e, int32_t slots, const int64_t *loci, int64_t nloci, int64_t max_bytes);
+int gph_engine_clades_sample(gph_engine *e);
+int gph_engine_clades_shape(gph_engine *e, int64_t *selected, int32_t *slots, int32_t *words, int32_t *limit, int64_t *samples);
+int gph_engine_clades_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_clades_fetch(gph_engine *e, uint64_t *entries, uint32_t *nkeys, uint32_t *dropped, int32_t reset);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -564,7 +593,7 @@ int gph_run_control_file_comm(const char *ctl_path, const char *secondary_ctl_pa
  * Every output takes its sample wherever a trace line is written (never in the burn-in), into a device buffer of <rows>
  * rows; whenever that buffer is full, and at the end, rank r appends the rows to a binary part file PREFIX.<kind>.part<r>.
  * gph_run_finish(o, ranks, failed), called once after the last rank has returned, makes the files of the parts and removes
- * the parts (failed == 0: gph_gene_trees_write, gph_ancestry_write, gph_time_slices_write, gph_coal_stats_write, in this
+ * the parts (failed == 0: gph_clades_write, gph_gene_trees_write, gph_ancestry_write, gph_time_slices_write, gph_coal_stats_write, in this
  * order; everything is discarded at the first failure) or only discards, parts and files.  A one-rank run calls it itself.
  * Either way a run that did not finish leaves neither parts nor files, and a part that is missing, damaged or was not
  * closed by its rank is an error.  The outputs compose freely. */
@@ -616,6 +645,22 @@ typedef struct gph_run_options {
    *   names leaf i */
   const char *gene_trees_prefix, *gene_trees_loci;
   int32_t gene_trees_rows;
+  /* `--clades PREFIX [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]`: the clade tables
+   * (gph_engine_clades_*).  clades_loci as gene_trees_loci, with the same refusals (names included); clades_slots 0: the
+   * default, else a power of two >= 2; clades_min_support: 0 = the default F = 0.5, a negative value = F = 0 (every kept
+   * clade), else F in (0, 1]; a selection, a slot count or a threshold without a prefix, slots that are no power of two and a
+   * threshold above 1 are GPH_EARG before anything is read.  The tables stay on the device during the run; rank r writes its
+   * part PREFIX.clades.part<r> once, at the end.  gph_clades_write concatenates the parts in rank order into
+   *   PREFIX.clades.tsv     header locus name samples dropped size support meanAge members; one row per (locus, kept clade)
+   *                         with cnt / S >= F, in sequence-file order, then decreasing cnt, then increasing size, then the
+   *                         key compared from word W - 1 down to word 0; support = cnt / S, meanAge = age / cnt in the
+   *                         genealogy's own units, both "%.10g"; members: the comma list of the leaf labels <sample>.<i> in
+   *                         leaf order, labels as PREFIX.trees.tsv prints them
+   *   PREFIX.consensus.tsv  header locus name samples distinct dropped resolved tree; one row per selected locus;
+   *                         distinct = nkeys, resolved and tree: gph_clades_consensus */
+  const char *clades_prefix, *clades_loci;
+  int32_t clades_slots;
+  double clades_min_support;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
@@ -633,6 +678,8 @@ int gph_ancestry_write(const char *prefix, int32_t ranks);
 int gph_ancestry_discard(const char *prefix, int32_t ranks);
 int gph_gene_trees_write(const char *prefix, int32_t ranks);
 int gph_gene_trees_discard(const char *prefix, int32_t ranks);
+int gph_clades_write(const char *prefix, int32_t ranks);
+int gph_clades_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
  * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
  * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
@@ -657,6 +704,19 @@ int gph_gene_tree_newick(int32_t n, const double *age, const int32_t *father, co
                          const int32_t *npop, int32_t root, int32_t num_migs, const int32_t *mig_branch, const int32_t *mig_band,
                          const double *mig_age, const char *const *pop_names, int32_t K, const char *const *band_names, int32_t B,
                          const char *const *leaf_labels, char *out, size_t out_cap, size_t *out_len);
+/* the majority-rule consensus of one locus's clade table as one line of Newick without branch lengths (host only).
+ * entries[slots][W + 2] as gph_engine_clades_fetch hands them out (W = ceil(n / 64)), `samples` the samples they were
+ * accumulated over, leaf_labels[n].  The consensus holds the kept clades with 2 cnt > samples: pairwise nested or disjoint by
+ * construction; a set that is not, or an entry that is no clade of n leaves (fewer than two leaves, a bit beyond leaf n - 1), is
+ * refused with GPH_EARG and a message -- never a wrong tree.  *resolved = their number, the root's clade included.
+ *   tree    := node(all leaves) ";"
+ *   node(c) := "(" child "," child ... ")" "[&support=" cnt / samples ",age=" age / cnt "]"      both "%.10g"
+ *   child   := node(c') for the largest clades c' inside c | the label of a leaf of c that lies in none of them
+ * children in the order of their smallest leaf index.  Mean ages of nested clades are conditional on different sample sets and
+ * need not nest: no branch lengths.  A table that does not hold the clade of all leaves (a full table dropped it) gives the top
+ * level without annotation; one leaf gives its label.  Returns as gph_gene_tree_newick does, label rules included. */
+int gph_clades_consensus(int32_t n, int32_t slots, const uint64_t *entries, int64_t samples, const char *const *leaf_labels,
+                         char *out, size_t out_cap, size_t *out_len, int32_t *resolved);
 
 /* ------------------------------------------------------------------------------------
  * post-run summary of a trace file (host only): block means per column, the output of the reference's
