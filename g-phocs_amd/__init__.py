@@ -267,13 +267,18 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("locus_summary_path", C.c_char_p), ("coal_stats_prefix", C.c_char_p), ("coal_stats_rows", C.c_int32),
                 ("time_slices", C.c_int32), ("ancestry_prefix", C.c_char_p), ("ancestry_rows", C.c_int32),
                 ("gene_trees_prefix", C.c_char_p), ("gene_trees_loci", C.c_char_p), ("gene_trees_rows", C.c_int32),
-                ("clades_prefix", C.c_char_p), ("clades_loci", C.c_char_p), ("clades_slots", C.c_int32), ("clades_min_support", C.c_double)]
+                ("clades_prefix", C.c_char_p), ("clades_loci", C.c_char_p), ("clades_slots", C.c_int32), ("clades_min_support", C.c_double),
+                ("beta", C.c_double), ("marginal_prefix", C.c_char_p), ("marginal_steps", C.c_int32), ("marginal_burnin", C.c_int32),
+                ("marginal_samples", C.c_int32), ("marginal_alpha", C.c_double)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
                      ancestry=None, ancestry_rows=0, gene_trees=None, gene_trees_loci=None, gene_trees_rows=0,
-                     clades=None, clades_loci=None, clades_slots=0, clades_min_support=None):
-    """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status"""
+                     clades=None, clades_loci=None, clades_slots=0, clades_min_support=None,
+                     beta=None, marginal=None, marginal_steps=0, marginal_burnin=None, marginal_samples=0, marginal_alpha=0.0):
+    """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
+    beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
+    marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -281,7 +286,11 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       time_slices=time_slices, ancestry_prefix=b(ancestry), ancestry_rows=ancestry_rows,
                       gene_trees_prefix=b(gene_trees), gene_trees_loci=b(gene_trees_loci), gene_trees_rows=gene_trees_rows,
                       clades_prefix=b(clades), clades_loci=b(clades_loci), clades_slots=clades_slots,
-                      clades_min_support=0.0 if clades_min_support is None else -1.0 if clades_min_support == 0 else clades_min_support)
+                      clades_min_support=0.0 if clades_min_support is None else -1.0 if clades_min_support == 0 else clades_min_support,
+                      beta=0.0 if beta is None else -1.0 if beta == 0 else beta,
+                      marginal_prefix=b(marginal), marginal_steps=marginal_steps,
+                      marginal_burnin=0 if marginal_burnin is None else -1 if marginal_burnin == 0 else marginal_burnin,
+                      marginal_samples=marginal_samples, marginal_alpha=marginal_alpha)
     return lib.gph_run(C.byref(o))
 
 
@@ -323,6 +332,7 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_gene_tree_newick", "gph_run", "gph_run_finish",
     "gph_engine_clades_enable", "gph_engine_clades_sample", "gph_engine_clades_shape", "gph_engine_clades_selected",
     "gph_engine_clades_fetch", "gph_clades_consensus", "gph_clades_write", "gph_clades_discard",
+    "gph_engine_set_beta", "gph_engine_get_beta", "gph_mcmc_set_beta", "gph_mcmc_get_beta",
 ]
 
 
@@ -477,6 +487,10 @@ def _load_library(path):
     lib.gph_engine_clades_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.gph_clades_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_clades_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_mcmc_set_beta.argtypes = [C.c_void_p, C.c_double]
+    lib.gph_mcmc_get_beta.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.gph_engine_set_beta.argtypes = [C.c_void_p, C.c_double]
+    lib.gph_engine_get_beta.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.gph_clades_consensus.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     return lib
@@ -909,6 +923,17 @@ class Sampler:
 
     def iteration(self, it):
         self._chk(self.lib.gph_mcmc_iteration(self.mcmc, it), f"iteration {it}")
+
+    def set_beta(self, b):
+        """power posterior p(D|G)^b p(G|Theta) p(Theta) from the next proposal on (gph_mcmc_set_beta): 1 the posterior, 0 the
+        prior; finite, in [0, 64].  Every rank of a chain must be given the same value."""
+        self._chk(self.lib.gph_mcmc_set_beta(self.mcmc, float(b)), f"set_beta({b!r})")
+
+    @property
+    def beta(self):
+        b = C.c_double()
+        self._chk(self.lib.gph_mcmc_get_beta(self.mcmc, C.byref(b)), "get_beta")
+        return b.value
 
     def state(self):
         ll, dl = C.c_double(), C.c_double()

@@ -474,7 +474,7 @@ static int zero_error_word(gph_engine *e)
 // the loci are in HBM: the per-locus kernels use up to the wide group's dynamic LDS size; allow > 64 KiB
 static int loci_loaded(gph_engine *e)
 {
-  const void *ks[] = {(const void *)k_init, (const void *)k_sweep, (const void *)k_tau_eval, (const void *)k_tau_finish,
+  const void *ks[] = {(const void *)k_init, (const void *)k_sweep, (const void *)k_sweep_heated, (const void *)k_tau_eval, (const void *)k_tau_finish,
                       (const void *)k_mix_eval, (const void *)k_mix_finish,
                       (const void *)k_sync, (const void *)k_check, (const void *)k_lrate_apply, (const void *)k_lrate_prep,
                       (const void *)k_unit};

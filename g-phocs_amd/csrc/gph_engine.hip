@@ -59,7 +59,9 @@ int gph_oob_word = 0;
 // knows it when it launches: the genealogy sweep at the head of an iteration, the locus-rate kernels), GphCtxG from the
 // device-resident chain state KA.G (everything launched after a decision the host has not seen yet)
 GPH_KERNEL(k_init, GphKargs KA, GphDev D, int j0, uint32_t seedz, const double *mutRate, int preDraws) { GphCtxG lx; lx.kb_init(D, j0 + GPH_BLK, seedz, mutRate ? mutRate[j0 + GPH_BLK] : 1.0, preDraws); }
-GPH_SWEEP_ATTR GPH_KERNEL(k_sweep, GphKargs KA, GphDev D, int j0, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc) { GphCtx lx; lx.kb_sweep(D, j0 + GPH_BLK, flags, ftCoal, ftMig, mix_c, mix_lnc); }
+GPH_SWEEP_ATTR GPH_KERNEL(k_sweep, GphKargs KA, GphDev D, int j0, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc) { GphCtx lx; lx.kb_sweep<false>(D, j0 + GPH_BLK, flags, ftCoal, ftMig, mix_c, mix_lnc, 1.0); }
+// the sweep of a heated chain (beta != 1, gph_engine_set_beta): a kernel of its own, chosen at launch, so that the sweep of the posterior carries no factor
+GPH_SWEEP_ATTR GPH_KERNEL(k_sweep_heated, GphKargs KA, GphDev D, int j0, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc, double beta) { GphCtx lx; lx.kb_sweep<true>(D, j0 + GPH_BLK, flags, ftCoal, ftMig, mix_c, mix_lnc, beta); }
 GPH_KERNEL(k_tau_eval, GphKargs KA, GphDev D, int j0, int fuse) { GphCtxG lx; lx.kb_tau_eval(D, j0 + GPH_BLK, GPH_G->tau, fuse); }
 GPH_KERNEL(k_tau_finish, GphKargs KA, GphDev D, int j0, int unused) { (void)unused; GphCtxG lx; lx.kb_tau_finish(D, j0 + GPH_BLK); }
 GPH_KERNEL(k_mix_eval, GphKargs KA, GphDev D, int j0, int fuse) { GphCtxG lx; lx.kb_mix_eval(D, j0 + GPH_BLK, GPH_G->mix_c, fuse); }
@@ -951,6 +953,7 @@ int gph_engine_create(const gph_config *cfg, gph_engine **out)
   if (int rc = backend_open(e)) { gph_engine_destroy(e); return rc; }
   memset(e->G_h, 0, sizeof(GphGlobal));
   e->G_h->error_locus = -1;          /* (0 is a locus: an error that is not per-locus must not name it -- ADVICE round 5) */
+  e->G_h->beta = 1.0;                /* the posterior itself */
   build_model_static(e);
   *out = e;
   return 0;
@@ -1006,6 +1009,20 @@ int gph_engine_set_comm(gph_engine *e, gph_comm *c)
 
 GphGlobal *gph_engine_global_(gph_engine *e) { if (!e) return nullptr; e->G_dirty = true; return e->G_h; }
 const GphGlobal *gph_engine_global_ro_(gph_engine *e) { return e ? e->G_h : nullptr; }
+
+// power posterior (include/gphocs_hip.h): from the next proposal on, the data term of every acceptance ratio is beta * its change
+int gph_engine_set_beta(gph_engine *e, double beta)
+{
+  if (!e || !(beta >= 0.0 && beta <= 64.0)) return GPH_EARG;    /* (a NaN fails both comparisons) */
+  if (e->G_h->beta != beta) { e->G_h->beta = beta; e->G_dirty = true; }
+  return 0;
+}
+int gph_engine_get_beta(gph_engine *e, double *beta)
+{
+  if (!e || !beta) return GPH_EARG;
+  *beta = e->G_h->beta;
+  return 0;
+}
 
 int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *poff, const uint8_t *leafcodes,
                          const uint16_t *numPhases, const int32_t *counts, const double *mutRates)
@@ -1282,7 +1299,10 @@ static int sweep_launch(gph_engine *e, int flags, double ftCoal, double ftMig, i
   }
   if (have) { if ((rc = flush_pending(e)) || (rc = rng_ahead_wait(e))) return rc; }
   else if ((rc = rng_ahead_launch(e))) return rc;
-  if ((rc = launch_loci(e, 0, k_sweep, flags | with_sync | with_mix, ftCoal, ftMig, e->G_h->mix_c, e->G_h->mix_lnc))) return rc;
+  /* beta is a setting: the mirror's value is the chain's (as the step sizes, which the callers read from it) */
+  if (e->G_h->beta == 1.0) rc = launch_loci(e, 0, k_sweep, flags | with_sync | with_mix, ftCoal, ftMig, e->G_h->mix_c, e->G_h->mix_lnc);
+  else rc = launch_loci(e, 0, k_sweep_heated, flags | with_sync | with_mix, ftCoal, ftMig, e->G_h->mix_c, e->G_h->mix_lnc, e->G_h->beta);
+  if (rc) return rc;
   if (side) {
     launch_pre(e);
     if ((rc = rng_ahead_side(e, GphGrid{(int)((e->L + GPH_WAVE - 1) / GPH_WAVE), 1}))) return rc;
@@ -1870,7 +1890,7 @@ int gph_engine_locus_rate_update(gph_engine *e, double finetune, double alpha, g
     if ((rc = scan_lds_limit(e))) return rc;
   }
   if (h2d(e, e->d_ref_page, refpg.data(), y.page_bytes)) return GPH_EHIP;
-  e->lr.finetune = finetune; e->lr.alpha = alpha;
+  e->lr.finetune = finetune; e->lr.alpha = alpha; e->lr.beta = e->G_h->beta;
   e->lr.first = owner ? 1 : 0;
   if ((rc = launch_loci(e, 11, k_lrate_prep, finetune, e->d_lpre))) return rc;
   if ((rc = reduce_local(e, 0, GPH_OUT_SLOTS))) return rc;

@@ -448,7 +448,7 @@ GPH_HD void gg_tau_decide(GphGlobal &G, const GphRed &R, int kind)
   const double fc = R.mn(0, 14);
   const int mig_conflict = fc < 1e299;
   double lnacc = G.pend_lnacc;
-  lnacc += dataDelta + genDelta + ntj0 * gph_log(G.pend_taufactor0) + ntj1 * gph_log(G.pend_taufactor1);
+  lnacc += G.beta * dataDelta + genDelta + ntj0 * gph_log(G.pend_taufactor0) + ntj1 * gph_log(G.pend_taufactor1);
   if (!mig_conflict && (lnacc >= 0 || gg_rndu(G) < gph_exp(lnacc))) {
     G.accArr[pop]++;
     G.dataLogLikelihood += dataDelta;
@@ -529,7 +529,7 @@ GPH_HD void gg_mix_decide(GphGlobal &G, const GphRed &R)
   const double dData = R.sum(0, 0), dGen = G.pend_dGen, c = G.mix_c;
   int pop, b;
   double lnacc = G.pend_lnacc;
-  lnacc += (dData + dGen);
+  lnacc += (G.beta * dData + dGen);
   if (lnacc >= 0 || gg_rndu(G) < gph_exp(lnacc)) {
     for (pop = 0; pop < G.K; pop++) G.tot_coal[pop] *= c;
     for (b = 0; b < G.B; b++) G.tot_mig[b] *= c;

@@ -273,8 +273,13 @@ GPH_DEV void kb_init(const GphDev &D, int g, uint32_t seedz, double mutRate, int
 }
 
 // ---------------------------------------------------------------- genealogy sweeps
+// Power posterior (heated chain): the data term of an acceptance ratio is beta * lnLd, everything the chain records (the
+// accumulators below, FS_DATALNL) stays the plain data log-likelihood.  HEAT = false is the sweep of the posterior itself
+// (beta = 1), compiled without the factor; the heated kernel keeps beta where the step size is kept, in LDS scratch.
+template <bool HEAT> GPH_DEV double heated(double lnLd) { if (HEAT) return gf64(&GphLds::s_cntf, 1) * lnLd; return lnLd; }
+
 // UpdateGB_InternalNode per-locus body, GPhoCS.c:2299-2425
-template <class RNG> GPH_DEV void sweep_internal(const GphDev &D, int g, double finetune, RNG &rng)
+template <bool HEAT, class RNG> GPH_DEV void sweep_internal(const GphDev &D, int g, double finetune, RNG &rng)
 {
   int pop, inode, i, son, mig, acc = 0;
   double t, tnew, lnacc, lnLd, dgen, tb0, tb1;
@@ -308,7 +313,7 @@ template <class RNG> GPH_DEV void sweep_internal(const GphDev &D, int g, double 
     lnLd = -FS(FS_DATALNL);
     { STAMP_BEGIN(1); lnLd += lik_compute(1); STAMP_END(1); }
     { STAMPA_BEGIN(2); dgen = consider_event_move(0, NEV(inode), pop, t, pop, tnew); STAMPA_END(2); }
-    lnacc = dgen + lnLd;
+    lnacc = dgen + heated<HEAT>(lnLd);
     if (gph_failed()) break;
     const bool take_ = UNI(lnacc >= 0) || UNI(l_rndu(rng) < gph_exp_u(lnacc));
     GPH_SLOG(3, take_, lnacc, 0, 0, 0, 0);
@@ -383,7 +388,7 @@ template <class RNG> GPH_DEV void sweep_mignodes(const GphDev &D, int g, double 
 }
 
 // UpdateGB_MigSPR per-locus body, GPhoCS.c:2610-2944 (no admixture)
-template <class RNG> GPH_DEV void sweep_spr(const GphDev &D, int g, RNG &rng)
+template <bool HEAT, class RNG> GPH_DEV void sweep_spr(const GphDev &D, int g, RNG &rng)
 {
   int node, res, father, father_pop_old, sibling, b, i, mig, ev, target, pop, acc = 0, fpn, fen;
   double lnLd, lnacc, t_new;
@@ -409,7 +414,7 @@ template <class RNG> GPH_DEV void sweep_spr(const GphDev &D, int g, RNG &rng)
 #endif
     lnLd = -FS(FS_DATALNL);
     { STAMP_BEGIN(1); lnLd += lik_compute(1); STAMP_END(1); }
-    lnacc = lnLd;
+    lnacc = heated<HEAT>(lnLd);
     if (gph_failed()) break;
     const bool take_ = res >= 0 && (UNI(lnacc >= 0) || UNI(l_rndu(rng) < gph_exp_u(lnacc)));
     GPH_SLOG(3, take_, lnacc, 0, 0, 0, 0);
@@ -470,7 +475,7 @@ template <class RNG> GPH_DEV void sweep_spr(const GphDev &D, int g, RNG &rng)
 // flag 16: the mixing proposal of the previous iteration was ACCEPTED and its commit (GPhoCS.c:4815-4848) has not run: the
 // evaluated state is taken from the shadow page and committed here, in LDS -- the page the sweep writes at its end is
 // the only one written, and the commit costs no launch and no page round trip of its own
-template <class RNG> GPH_DEV void kb_sweep_(const GphDev &D, int g, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc)
+template <class RNG, bool HEAT> GPH_DEV void kb_sweep_(const GphDev &D, int g, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc, double beta)
 {
   STAMP_BEGIN(0);
   if (flags & 16) {
@@ -479,6 +484,7 @@ template <class RNG> GPH_DEV void kb_sweep_(const GphDev &D, int g, int flags, d
   } else {
     stage_in(D, g, D.pages, 1);
   }
+  if (HEAT) sf64(&GphLds::s_cntf, 1, beta);
   GPH_SLOG_OPEN(D, g);
   RNG rng;           /* uniforms in chunks of 64, generated ahead of the kernel: gph_locus.h */
   rng_load(rng, D, g);
@@ -486,9 +492,9 @@ template <class RNG> GPH_DEV void kb_sweep_(const GphDev &D, int g, int flags, d
   OUT(g, 15, (flags & 8) ? (double)synchronize_events() : 1.0);
   OUT(g, 0, 0.0); OUT(g, 1, 0.0); OUT(g, 2, 0.0); OUT(g, 3, 0.0); OUT(g, 4, 0.0);
   OUT(g, 5, 0.0); OUT(g, 6, 0.0); OUT(g, 7, 0.0); OUT(g, 12, 0.0);
-  { STAMP_BEGIN(5); if ((flags & 1) && ftCoal > 0.0) sweep_internal(D, g, ftCoal, rng); STAMP_END(5); }
+  { STAMP_BEGIN(5); if ((flags & 1) && ftCoal > 0.0) sweep_internal<HEAT>(D, g, ftCoal, rng); STAMP_END(5); }
   { STAMPC_BEGIN(4); if ((flags & 2) && ftMig > 0.0 && !gph_failed()) sweep_mignodes(D, g, ftMig, rng); STAMPC_END(4); }
-  { STAMP_BEGIN(6); if ((flags & 4) && !gph_failed()) sweep_spr(D, g, rng); STAMP_END(6); }
+  { STAMP_BEGIN(6); if ((flags & 4) && !gph_failed()) sweep_spr<HEAT>(D, g, rng); STAMP_END(6); }
   rng_store(rng, D, g);
   out_common(D, g);
   STAMP_END(0);
@@ -498,13 +504,13 @@ template <class RNG> GPH_DEV void kb_sweep_(const GphDev &D, int g, int flags, d
 #endif
   stage_out(D, g, D.pages, 1);
 }
-GPH_DEV void kb_sweep(const GphDev &D, int g, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc)
+template <bool HEAT> GPH_DEV void kb_sweep(const GphDev &D, int g, int flags, double ftCoal, double ftMig, double mix_c, double mix_lnc, double beta)
 {
 #ifdef GPH_HOSTEMU
   /* the pass ahead switched off: the serial generator, as every other kernel */
-  if (D.ra_M <= 0) { kb_sweep_<GphRng>(D, g, flags, ftCoal, ftMig, mix_c, mix_lnc); return; }
+  if (D.ra_M <= 0) { kb_sweep_<GphRng, HEAT>(D, g, flags, ftCoal, ftMig, mix_c, mix_lnc, beta); return; }
 #endif
-  kb_sweep_<GphRngA>(D, g, flags, ftCoal, ftMig, mix_c, mix_lnc);
+  kb_sweep_<GphRngA, HEAT>(D, g, flags, ftCoal, ftMig, mix_c, mix_lnc, beta);
 }
 
 // ---------------------------------------------------------------- UpdateTau
@@ -820,6 +826,7 @@ struct alignas(16) GphLrPre {   // prepared proposal of one locus (input order)
 };
 struct GphLrArgs {
   double finetune, alpha, dataLnL, logL, rateVar;
+  double beta;               // power posterior: the data term of the acceptance ratio is beta * lnLd (GphGlobal::beta)
   int32_t o_gnd, o_rnd, o_rseq, o_scr, Pscr, o_prog;   // dynamic-LDS byte offsets; loci with P <= Pscr use LDS scratch
   int32_t o_pe, first;                                 // o_prog / o_pe: compiled program and edge probabilities of the reference locus; first = first local locus that proposes
   int32_t o_lf, pad0;                                  // o_lf: the reference locus's leaves as conditional arrays [n][P][4] (0 = no room: generic evaluator)
@@ -1128,7 +1135,7 @@ GPH_DEV void kb_lrate_scan(const GphDev &D, const GphLrArgs &A)
       const double lr = lik_private(A.o_rnd, A.o_rseq, Pr, rootr, rrefnew, A.o_scr, Pr > A.Pscr ? gs : (gdbl *)0);
 #endif
       lnLd += lr;
-      lnacc += lnLd;
+      lnacc += A.beta * lnLd;
       bool acc = UNI(lnacc >= 0);
       if (!acc) acc = UNI(l_rndu(rng) < gph_exp(lnacc));
       if (acc) {

@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -21,6 +21,11 @@
 // and its majority-rule consensus tree, from tables accumulated on the device (--clades-loci SPEC as --gene-trees-loci;
 // --clades-slots P: slots of a locus's table, a power of two, default the smallest one >= 8 (leaves - 1); --clades-min-support
 // F: the clades listed have support >= F, default 0.5, 0 lists every kept clade).
+// --beta B runs the whole chain on the power posterior p(D|G)^B p(G|Theta) p(Theta), B in [0, 64], 0 = the prior;
+// --marginal-likelihood PREFIX runs, behind the unchanged run, the ladder beta_k = (k/K)^(1/a) from 1 down to 0 (--ml-steps K,
+// default 32; --ml-alpha a, default 0.3; per rung --ml-burnin b discarded iterations, default the control file's burn-in or
+// 1000, and --ml-samples s recorded ones, default 2000) and writes the stepping-stone and thermodynamic-integration estimates
+// of the log marginal likelihood to PREFIX.marginal.tsv (rank 0 alone: no parts).  The two exclude each other.
 // They compose freely.  Under -g N every child leaves parts: of the summary table FILE.part<r>, which the launcher
 // concatenates in rank order into FILE once every child has exited 0; of the others the library's own, which gph_run_finish
 // turns into the files (the launcher itself has not touched a GPU).  A run that did not finish leaves neither parts nor files.
@@ -96,7 +101,7 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
@@ -130,6 +135,31 @@ int main(int argc, char **argv)
       if (end == argv[i] || *end || !(F >= 0.0 && F <= 1.0)) { fprintf(stderr, "%s: --clades-min-support takes a number in [0, 1]\n", argv[0]); return usage(argv[0]); }
       o.clades_min_support = F == 0.0 ? -1.0 : F;      /* (0 in the options struct means the default) */
     }
+    else if (!strcmp(argv[i], "--beta") && i + 1 < argc) {
+      char *end = nullptr;
+      const double B = strtod(argv[++i], &end);
+      if (end == argv[i] || *end || !(B >= 0.0 && B <= 64.0)) { fprintf(stderr, "%s: --beta takes a number in [0, 64]\n", argv[0]); return usage(argv[0]); }
+      o.beta = B == 0.0 ? -1.0 : B;                    /* (0 in the options struct means not given) */
+    }
+    else if (!strcmp(argv[i], "--marginal-likelihood") && i + 1 < argc) o.marginal_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--ml-steps") && i + 1 < argc) {
+      o.marginal_steps = atoi(argv[++i]);
+      if (o.marginal_steps < 1) { fprintf(stderr, "%s: --ml-steps takes a number of steps K >= 1\n", argv[0]); return usage(argv[0]); }
+    }
+    else if (!strcmp(argv[i], "--ml-burnin") && i + 1 < argc) {
+      o.marginal_burnin = atoi(argv[++i]);
+      if (o.marginal_burnin < 0) { fprintf(stderr, "%s: --ml-burnin takes a number of iterations b >= 0\n", argv[0]); return usage(argv[0]); }
+      if (o.marginal_burnin == 0) o.marginal_burnin = -1;     /* (0 in the options struct means the default) */
+    }
+    else if (!strcmp(argv[i], "--ml-samples") && i + 1 < argc) {
+      o.marginal_samples = atoi(argv[++i]);
+      if (o.marginal_samples < 1) { fprintf(stderr, "%s: --ml-samples takes a number of samples s >= 1\n", argv[0]); return usage(argv[0]); }
+    }
+    else if (!strcmp(argv[i], "--ml-alpha") && i + 1 < argc) {
+      char *end = nullptr;
+      o.marginal_alpha = strtod(argv[++i], &end);
+      if (end == argv[i] || *end || !(o.marginal_alpha > 0.0) || o.marginal_alpha > 1e300) { fprintf(stderr, "%s: --ml-alpha takes a finite number a > 0\n", argv[0]); return usage(argv[0]); }
+    }
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
@@ -137,6 +167,11 @@ int main(int argc, char **argv)
   if (o.time_slices && !o.coal_stats_prefix) { fprintf(stderr, "%s: --time-slices needs -s PREFIX\n", argv[0]); return usage(argv[0]); }
   if ((o.gene_trees_loci || o.gene_trees_rows) && !o.gene_trees_prefix) { fprintf(stderr, "%s: --gene-trees-loci and --gene-trees-rows need --gene-trees PREFIX\n", argv[0]); return usage(argv[0]); }
   if ((o.clades_loci || o.clades_slots || o.clades_min_support != 0.0) && !o.clades_prefix) { fprintf(stderr, "%s: --clades-loci, --clades-slots and --clades-min-support need --clades PREFIX\n", argv[0]); return usage(argv[0]); }
+  if ((o.marginal_steps || o.marginal_burnin || o.marginal_samples || o.marginal_alpha != 0.0) && !o.marginal_prefix) {
+    fprintf(stderr, "%s: --ml-steps, --ml-burnin, --ml-samples and --ml-alpha need --marginal-likelihood PREFIX\n", argv[0]);
+    return usage(argv[0]);
+  }
+  if (o.beta != 0.0 && o.marginal_prefix) { fprintf(stderr, "%s: --beta and --marginal-likelihood exclude each other\n", argv[0]); return usage(argv[0]); }
   o.ctl = argv[i];
   o.ctl2 = i + 1 < argc ? argv[i + 1] : nullptr;
   char self[PATH_MAX];
@@ -242,7 +277,7 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(o.locus_summary_path); bad = 1; }
     if (bad && out) unlink(o.locus_summary_path);
   }
-  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix) {
+  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.marginal_prefix) {
     /* the ranks' parts into the files, by the library that wrote them -- or, after a failure, removed */
     if (sym<decltype(&gph_run_finish)>(load_engine(dir, o.ctl, o.ctl2), "gph_run_finish")(&o, gpus, bad)) bad = 1;
   }

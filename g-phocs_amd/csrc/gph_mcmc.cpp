@@ -412,6 +412,10 @@ int gph_mcmc_set_log_period(gph_mcmc *m, int32_t iterations)
   return 0;
 }
 
+// power posterior: the engine keeps beta in the chain state, next to the step sizes, where every decision reads it
+int gph_mcmc_set_beta(gph_mcmc *m, double beta) { return m ? gph_engine_set_beta(m->e, beta) : GPH_EARG; }
+int gph_mcmc_get_beta(gph_mcmc *m, double *beta) { return m ? gph_engine_get_beta(m->e, beta) : GPH_EARG; }
+
 int gph_mcmc_accept_counts(gph_mcmc *m, int64_t *counts9)
 {
   if (!m || !counts9) return GPH_EARG;

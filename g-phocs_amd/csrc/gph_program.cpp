@@ -1608,6 +1608,112 @@ int Log::period(int it)
   return GPH_OK;
 }
 
+// ---- `--beta B` and `--marginal-likelihood PREFIX` (gph_run_options says what they do)
+// the beta of the options: 0 = not given = 1, negative = 0
+double option_beta(const gph_run_options &o) { return o.beta == 0.0 ? 1.0 : o.beta < 0.0 ? 0.0 : o.beta; }
+std::string marginal_path(const char *prefix) { return std::string(prefix) + ".marginal.tsv"; }
+
+struct Marginal {
+  struct Rung { int k; double beta, mean, sd, lnRatio, acc[7]; };
+  const int K, s;
+  const double a;
+  int b = 0;
+  std::vector<Rung> rungs;
+  double lnZss = 0.0, lnZti = 0.0;
+  explicit Marginal(const gph_run_options &o) : K(o.marginal_steps ? o.marginal_steps : 32), s(o.marginal_samples ? o.marginal_samples : 2000),
+                                                a(o.marginal_alpha != 0.0 ? o.marginal_alpha : 0.3) {}
+  static int refuse(const char *msg) { fprintf(stderr, "gphocs_hip: %s\n", msg); return GPH_EARG; }
+  static int validate(const gph_run_options &o)
+  {
+    if (!(o.beta <= 64.0)) return refuse("--beta takes a number in [0, 64]");      /* (a NaN fails the comparison) */
+    if (!o.marginal_prefix) {
+      if (o.marginal_steps) return refuse("--ml-steps needs --marginal-likelihood PREFIX");
+      if (o.marginal_burnin) return refuse("--ml-burnin needs --marginal-likelihood PREFIX");
+      if (o.marginal_samples) return refuse("--ml-samples needs --marginal-likelihood PREFIX");
+      if (o.marginal_alpha != 0.0) return refuse("--ml-alpha needs --marginal-likelihood PREFIX");
+      return GPH_OK;
+    }
+    if (o.beta != 0.0) return refuse("--beta and --marginal-likelihood exclude each other: the ladder sets beta itself");
+    if (o.marginal_steps < 0) return refuse("--ml-steps takes a number of steps K >= 1");
+    if (o.marginal_samples < 0) return refuse("--ml-samples takes a number of samples s >= 1");
+    if (!(o.marginal_alpha >= 0.0) || std::isinf(o.marginal_alpha)) return refuse("--ml-alpha takes a finite number a > 0");
+    return GPH_OK;
+  }
+  double beta_of(int k) const { return k == K ? 1.0 : k == 0 ? 0.0 : pow((double)k / (double)K, 1.0 / a); }
+  /* the ladder, from beta = 1 downward, on the chain as the run left it; `it` goes on counting (the checkAll period with it) but
+   * never passes start-mig a second time.  The host synchronisation at the end of every iteration hands out l: no other one */
+  int run(Run &R, int64_t totalCoals)
+  {
+    const gph_control_info &info = R.info;
+    const gph_config &cfg = R.cfg;
+    b = R.o.marginal_burnin < 0 ? 0 : R.o.marginal_burnin > 0 ? R.o.marginal_burnin : info.burnin > 0 ? info.burnin : 1000;
+    int it = std::max(info.numSamples, R.mc.startMig + 1), ntau = cfg.K - cfg.Kc, rc;
+    for (int p = 0; p < cfg.Kc; p++) ntau += R.mc.updateSampleAge[p] != 0;
+    if (R.lead) printf("Marginal likelihood: %d steps down the ladder beta_k = (k/%d)^(1/%g), %d + %d iterations each.\n", K, K, a, b, s);
+    std::vector<std::vector<double>> l(K + 1, std::vector<double>(s));
+    const double n = (double)(b + s);
+    for (int k = K; k >= 0; k--) {
+      Rung r;
+      r.k = k; r.beta = beta_of(k); r.lnRatio = 0.0;
+      if ((rc = gph_mcmc_set_beta(R.M, r.beta))) return R.fail(rc, "gph_mcmc_set_beta");
+      int64_t a0[9], a1[9];
+      gph_mcmc_accept_counts(R.M, a0);
+      for (int j = -b; j < s; j++, it++) {
+        if ((rc = gph_mcmc_iteration(R.M, it))) return R.fail(rc, "gph_mcmc_iteration");
+        if (j >= 0) gph_mcmc_get_state(R.M, nullptr, &l[k][j], nullptr, nullptr, nullptr);
+      }
+      gph_mcmc_accept_counts(R.M, a1);
+      double sum = 0.0, ss = 0.0;
+      for (int j = 0; j < s; j++) sum += l[k][j];
+      r.mean = sum / s;
+      for (int j = 0; j < s; j++) ss += (l[k][j] - r.mean) * (l[k][j] - r.mean);
+      r.sd = s > 1 ? sqrt(ss / (s - 1)) : 0.0;
+      const int64_t d7 = a1[7] - a0[7];
+      r.acc[0] = (a1[0] - a0[0]) / (n * (double)totalCoals);
+      r.acc[1] = d7 > 0 ? (a1[1] - a0[1]) / (double)d7 : 0.0;
+      r.acc[2] = (a1[2] - a0[2]) / (n * 2 * (double)totalCoals);
+      r.acc[3] = (a1[3] - a0[3]) / (n * cfg.K);
+      r.acc[4] = cfg.B > 0 ? (a1[4] - a0[4]) / (n * cfg.B) : 0.0;
+      r.acc[5] = ntau > 0 ? (a1[5] - a0[5]) / (n * ntau) : 0.0;
+      r.acc[6] = (a1[6] - a0[6]) / n;
+      if (R.lead) {
+        printf("rung %3d  beta %-12.10g meanLnL %-16.10g accepted: CoalTimes %5.1f%% MigTimes %5.1f%% SPRs %5.1f%% Thetas %5.1f%% MigRates %5.1f%% Taus %5.1f%% Mixing %5.1f%%\n",
+               k, r.beta, r.mean, 100 * r.acc[0], 100 * r.acc[1], 100 * r.acc[2], 100 * r.acc[3], 100 * r.acc[4], 100 * r.acc[5], 100 * r.acc[6]);
+        fflush(stdout);
+      }
+      rungs.push_back(r);
+    }
+    /* the estimates: rungs[K - k] is rung k */
+    for (int k = 0; k < K; k++) {
+      const double d = rungs[K - k - 1].beta - rungs[K - k].beta;
+      double m = d * l[k][0], e = 0.0;
+      for (int j = 1; j < s; j++) m = std::max(m, d * l[k][j]);
+      for (int j = 0; j < s; j++) e += exp(d * l[k][j] - m);
+      rungs[K - k].lnRatio = m + log(e / s);
+      lnZss += rungs[K - k].lnRatio;
+      lnZti += d * (rungs[K - k].mean + rungs[K - k - 1].mean) / 2;
+    }
+    if (R.lead) printf("Marginal likelihood: lnZ_ss %.10g lnZ_ti %.10g (steps %d alpha %.10g)\n", lnZss, lnZti, K, a);
+    return gph_mcmc_set_beta(R.M, 1.0);
+  }
+  int write(Run &R) const
+  {
+    const std::string path = marginal_path(R.o.marginal_prefix);
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) { snprintf(R.err, sizeof R.err, "Could not open %s", path.c_str()); return R.fail(GPH_EARG, "writing the marginal-likelihood table"); }
+    fprintf(f, "rung\tbeta\tsamples\tmeanLnL\tsdLnL\tlnRatio\taccCoal\taccMig\taccSpr\taccTheta\taccMigRate\taccTau\taccMixing\n");
+    for (const Rung &r : rungs) {
+      fprintf(f, "%d\t%.10g\t%d\t%.10g\t%.10g\t%.10g", r.k, r.beta, s, r.mean, r.sd, r.lnRatio);
+      for (double v : r.acc) fprintf(f, "\t%.10g", v);
+      fprintf(f, "\n");
+    }
+    fprintf(f, "# lnZ_ss %.10g lnZ_ti %.10g steps %d alpha %.10g\n", lnZss, lnZti, K, a);
+    const int rcc = ferror(f) | fclose(f);
+    if (rcc) { unlink(path.c_str()); return R.fail(GPH_EARG, "writing the marginal-likelihood table"); }
+    return GPH_OK;
+  }
+};
+
 // one rank's run up to its parts: what becomes of those is gph_run_finish's
 int run_chain(const gph_run_options &o)
 {
@@ -1621,6 +1727,11 @@ int run_chain(const gph_run_options &o)
   if (outs.trees && (rc = outs.trees->select(R))) return rc;
   if (outs.clades && (rc = outs.clades->select(R))) return rc;
   if ((rc = R.start_engine()) || (rc = R.open_trace())) return rc;
+  if (o.beta != 0.0) {
+    if ((rc = gph_mcmc_set_beta(R.M, option_beta(o)))) return R.fail(rc, "gph_mcmc_set_beta");
+    if (R.lead) printf("Power posterior: beta = %.10g%s -- the trace and every other output describe p(D|G)^beta p(G|Theta) p(Theta); the log-likelihood columns stay those of the plain likelihood.\n",
+                       option_beta(o), option_beta(o) == 0.0 ? " (the prior)" : "");
+  }
 
   const gph_control_info &info = R.info;
   if (R.lead) printf("Starting MCMC: %d burnin, %d running, sampled every %d iteration(s).\n", info.burnin, info.numSamples, info.sampleSkip);
@@ -1653,6 +1764,12 @@ int run_chain(const gph_run_options &o)
   R.trace = nullptr;
   for (auto x = outs.list.rbegin(); x != outs.list.rend(); ++x)
     if ((rc = (*x)->close(R))) return rc;
+  /* the run is over and what it wrote is closed: the ladder goes on from its last state */
+  std::unique_ptr<Marginal> ml;
+  if (o.marginal_prefix) {
+    ml.reset(new Marginal(o));
+    if ((rc = ml->run(R, totalCoals))) return rc;
+  }
   /* a CHECKED build of the library (-DGPH_BOUNDS, tests only) says here whether an index left its array during the run */
   int32_t where = 0, checked = 0;
   (void)gph_engine_debug_oob(R.E, &where, &checked);
@@ -1662,7 +1779,8 @@ int run_chain(const gph_run_options &o)
                     "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
     return GPH_EKERNEL;
   }
-  return outs.summary ? outs.summary->write_table(R) : GPH_OK;
+  if (outs.summary && (rc = outs.summary->write_table(R))) return rc;
+  return ml && R.lead ? ml->write(R) : GPH_OK;
 }
 }   // namespace
 
@@ -1675,8 +1793,10 @@ extern "C" int gph_run_finish(const gph_run_options *in, int32_t ranks, int32_t 
   for (auto &x : outs.list)
     if (!failed && !rc) rc = x->write(ranks);
   /* a failed run leaves no statistics file and no part behind */
-  if (failed || rc)
+  if (failed || rc) {
     for (auto &x : outs.list) x->discard(ranks);
+    if (o.marginal_prefix) unlink(marginal_path(o.marginal_prefix).c_str());
+  }
   return rc;
 }
 
@@ -1689,7 +1809,7 @@ extern "C" int gph_run(const gph_run_options *in)
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
   /* the checks on the options alone, before anything is read */
   int rc;
-  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = CoalStats::validate(o))) return rc;
+  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o))) return rc;
   rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
   if (o.world == 1) {

@@ -231,7 +231,7 @@ struct alignas(16) GphLds {
   // ---- LDS-only scratch: pending-proposal storage of GENETREE_STATS_DELTA x2 (patch.h:60-72),
   // MIG_SPR_STATS (patch.h:97-105), genetree_stats_check (patch.h:109), pruning work lists
   double s_dcoal[2][GPH_CAP_K], s_dmig[2][GPH_CAP_B];
-  double s_cntf[8];   // s_cntf: 0 algorithmic bytes, 2..6 sweep accumulators, 7 step size
+  double s_cntf[8];   // s_cntf: 0 algorithmic bytes, 1 beta of a heated sweep, 2..6 sweep accumulators, 7 step size
   // the SPR's scalars (sweep kernel, one proposal at a time) and the statistics being re-derived (recalcStats,
   // computeGenetreeStats, checkAll: tau / sample-age / refresh / check code, never inside an SPR) share their bytes
   union {
@@ -330,6 +330,7 @@ struct alignas(16) GphGlobal {
   double mrAlpha[GPH_MAXB], mrBeta[GPH_MAXB];
   int32_t updateSampleAge[GPH_MAXK];
   double ftCoalTime, ftMigTime, ftTheta, ftMigRate, ftMixing;
+  double beta;                       // power posterior p(D|G)^beta p(G|Theta) p(Theta): scales the data term of every acceptance ratio, 1 = the posterior (gph_engine_set_beta)
   // ---- running state
   uint32_t gx, gy, gz, pad1;         // general RNG slot
   double logLikelihood, dataLogLikelihood;

@@ -494,6 +494,19 @@ int gph_mcmc_set_locus_rate_finetune(gph_mcmc *m, double locusRate);
 int gph_mcmc_locus_rate_state(gph_mcmc *m, int64_t *accepted, double *rateVar);
 /* recordParamVals (GPhoCS.c:802-849) of the last iteration: thetas, taus, migration rates, sample ages */
 int gph_mcmc_param_vals(gph_mcmc *m, double *vals, int32_t n);
+/* Power posterior (heated chain): the chain samples p(D | G)^beta p(G | Theta) p(Theta).  beta multiplies the change of the
+ * data log-likelihood in every acceptance ratio that has one -- UpdateGB_InternalNode, UpdateGB_MigSPR, UpdateLocusRate,
+ * UpdateTau / UpdateSampleAge, mixing -- and nothing else: not the draws or their order, not the genealogy term, the priors
+ * or the Hastings factors.  beta = 1 (the default) is the posterior, bit for bit the chain without this call; beta = 0 samples
+ * the prior.  Finite and in [0, 64], else GPH_EARG.  It takes effect from the next proposal call, gph_mcmc_iteration and every
+ * proposal-level call of the drop-in boundary below included (gph_engine_genealogy_sweep and gph_engine_locus_rate_update,
+ * which decide on the device, too).  What the chain RECORDS stays unheated: dataLogLikelihood / logLikelihood, the trace
+ * columns, the per-locus values, checkAll are those of the plain likelihood.  With several ranks every rank must be given the
+ * same beta (nothing is exchanged for it): ranks that differ take different decisions and the chain is undefined. */
+int gph_engine_set_beta(gph_engine *e, double beta);
+int gph_engine_get_beta(gph_engine *e, double *beta);
+int gph_mcmc_set_beta(gph_mcmc *m, double beta);
+int gph_mcmc_get_beta(gph_mcmc *m, double *beta);
 
 /* ------------------------------------------------------------------------------------
  * input front end (host only, no GPU): the reference's file formats, unchanged.
@@ -661,6 +674,35 @@ typedef struct gph_run_options {
   const char *clades_prefix, *clades_loci;
   int32_t clades_slots;
   double clades_min_support;
+  /* `--beta B`: the whole chain, burn-in and finetune search included, samples the power posterior
+   * p(D | G)^B p(G | Theta) p(Theta) (gph_mcmc_set_beta); B = 0 is the prior.  Here 0 = not given = the posterior (B = 1), any
+   * NEGATIVE value = B = 0, else B itself, in (0, 64] (GPH_EARG beyond).  The trace file and every other output keep their
+   * formats; they describe the power posterior (the log-likelihood columns stay those of the plain likelihood), and the log on
+   * stdout says so once.  Not together with marginal_prefix (GPH_EARG). */
+  double beta;
+  /* `--marginal-likelihood PREFIX [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]`: the marginal likelihood
+   * ln Z = ln p(D) by stepping-stone sampling and thermodynamic integration.  The run itself happens first, exactly as without
+   * the option (its trace and every other output are the same bytes, and their parts are closed before anything below starts).
+   * Then the chain goes on from where it ended, with the step sizes it ended with, down the ladder beta_k = (k / K)^(1 / a),
+   * k = K, K - 1, .., 0: at each rung b iterations are discarded, then after each of s iterations the chain's total data
+   * log-likelihood l (over all loci and ranks: gph_mcmc_get_state's dataLogLikelihood) is recorded.  With d_k = beta_{k+1} - beta_k:
+   *   lnZ_ss = sum_{k<K} [ m + ln( (1/s) sum_j exp(d_k l_j(k) - m) ) ],  m = max_j d_k l_j(k)       (Xie et al. 2011)
+   *   lnZ_ti = sum_{k<K} d_k (mean_k + mean_{k+1}) / 2                                              (trapezoid)
+   * in fp64 on rank 0, which alone writes, once, at the end and only on success, PREFIX.marginal.tsv (tab-separated, numbers
+   * "%.10g"): the header
+   *   rung beta samples meanLnL sdLnL lnRatio accCoal accMig accSpr accTheta accMigRate accTau accMixing
+   * one row per rung in the order visited (rung = k; sdLnL: the sample standard deviation; lnRatio: the rung's stepping-stone
+   * term, 0 for k = K; acc*: accepted fractions over the rung's b + s iterations, accMig per migration node visited, accTau
+   * over ancestral populations and estimated sample ages), then one line "# lnZ_ss <v> lnZ_ti <v> steps K alpha a".  The two
+   * values also go into one line of the log on stdout, and every rung's acceptance into one line each.  A failed run leaves
+   * no such file (gph_run_finish removes it).  Step sizes are not re-tuned per rung.
+   * marginal_steps K: 0 = 32; marginal_samples s: 0 = 2000; marginal_alpha a: 0 = 0.3; negative values of these three are
+   * GPH_EARG (what the program passes for `--ml-steps 0`, `--ml-samples 0`, `--ml-alpha 0`: usage errors).  marginal_burnin b:
+   * 0 = the control file's burn-in if positive, else 1000; any negative value = no burn-in.  Any of the four without
+   * marginal_prefix is GPH_EARG.  Every refusal comes with a message that names the option, before anything is read. */
+  const char *marginal_prefix;
+  int32_t marginal_steps, marginal_burnin, marginal_samples;
+  double marginal_alpha;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
