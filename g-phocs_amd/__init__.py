@@ -261,6 +261,12 @@ class GphControlInfo(C.Structure):
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32,
                            C.POINTER(C.c_double), C.c_int32)
 
+class GphMc3Swap(C.Structure):   # gph_mc3_swap: one decision of a swap point
+    _fields_ = [("call", C.c_int32), ("lower", C.c_int32), ("beta_lower", C.c_double), ("beta_upper", C.c_double),
+                ("l_lower", C.c_double), ("l_upper", C.c_double), ("lnr", C.c_double), ("u", C.c_double),
+                ("accepted", C.c_int32), ("pad", C.c_int32)]
+
+
 class GphRunOptions(C.Structure):   # gph_run_options: what each field switches on is said there
     _fields_ = [("size", C.c_uint32), ("ctl", C.c_char_p), ("ctl2", C.c_char_p), ("device", C.c_int32), ("verbose", C.c_int32),
                 ("comm", C.c_void_p), ("rank", C.c_int32), ("world", C.c_int32), ("allreduce", ALLREDUCE_FN), ("user", C.c_void_p),
@@ -269,16 +275,20 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("gene_trees_prefix", C.c_char_p), ("gene_trees_loci", C.c_char_p), ("gene_trees_rows", C.c_int32),
                 ("clades_prefix", C.c_char_p), ("clades_loci", C.c_char_p), ("clades_slots", C.c_int32), ("clades_min_support", C.c_double),
                 ("beta", C.c_double), ("marginal_prefix", C.c_char_p), ("marginal_steps", C.c_int32), ("marginal_burnin", C.c_int32),
-                ("marginal_samples", C.c_int32), ("marginal_alpha", C.c_double)]
+                ("marginal_samples", C.c_int32), ("marginal_alpha", C.c_double),
+                ("mc3_chains", C.c_int32), ("mc3_heat", C.c_double), ("mc3_swap_every", C.c_int32), ("mc3_report_prefix", C.c_char_p)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
                      ancestry=None, ancestry_rows=0, gene_trees=None, gene_trees_loci=None, gene_trees_rows=0,
                      clades=None, clades_loci=None, clades_slots=0, clades_min_support=None,
-                     beta=None, marginal=None, marginal_steps=0, marginal_burnin=None, marginal_samples=0, marginal_alpha=0.0):
+                     beta=None, marginal=None, marginal_steps=0, marginal_burnin=None, marginal_samples=0, marginal_alpha=0.0,
+                     mc3=0, mc3_heat=0.0, mc3_swap_every=0, mc3_report=None):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
-    marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults"""
+    marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
+    mc3: the number of Metropolis-coupled chains (0: off), mc3_heat 0: 0.1, mc3_swap_every 0: every iteration, negative: never,
+    mc3_report: the prefix of the report file"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -290,7 +300,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       beta=0.0 if beta is None else -1.0 if beta == 0 else beta,
                       marginal_prefix=b(marginal), marginal_steps=marginal_steps,
                       marginal_burnin=0 if marginal_burnin is None else -1 if marginal_burnin == 0 else marginal_burnin,
-                      marginal_samples=marginal_samples, marginal_alpha=marginal_alpha)
+                      marginal_samples=marginal_samples, marginal_alpha=marginal_alpha,
+                      mc3_chains=mc3, mc3_heat=mc3_heat, mc3_swap_every=mc3_swap_every, mc3_report_prefix=b(mc3_report))
     return lib.gph_run(C.byref(o))
 
 
@@ -333,6 +344,8 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_clades_enable", "gph_engine_clades_sample", "gph_engine_clades_shape", "gph_engine_clades_selected",
     "gph_engine_clades_fetch", "gph_clades_consensus", "gph_clades_write", "gph_clades_discard",
     "gph_engine_set_beta", "gph_engine_get_beta", "gph_mcmc_set_beta", "gph_mcmc_get_beta",
+    "gph_engine_exchange_state", "gph_mcmc_exchange_state", "gph_mc3_create", "gph_mc3_destroy", "gph_mc3_iteration",
+    "gph_mc3_swap_counts", "gph_mc3_swap_log",
 ]
 
 
@@ -491,6 +504,14 @@ def _load_library(path):
     lib.gph_mcmc_get_beta.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.gph_engine_set_beta.argtypes = [C.c_void_p, C.c_double]
     lib.gph_engine_get_beta.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.gph_engine_exchange_state.argtypes = [C.c_void_p, C.c_void_p]
+    lib.gph_mcmc_exchange_state.argtypes = [C.c_void_p, C.c_void_p]
+    lib.gph_mc3_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.gph_mc3_destroy.argtypes = [C.c_void_p]
+    lib.gph_mc3_destroy.restype = None
+    lib.gph_mc3_iteration.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_mc3_swap_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.gph_mc3_swap_log.argtypes = [C.c_void_p, C.POINTER(GphMc3Swap), C.c_int64, C.POINTER(C.c_int64)]
     lib.gph_clades_consensus.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     return lib
@@ -935,6 +956,11 @@ class Sampler:
         self._chk(self.lib.gph_mcmc_get_beta(self.mcmc, C.byref(b)), "get_beta")
         return b.value
 
+    def exchange_state(self, other):
+        """this chain and `other` exchange their states (gph_mcmc_exchange_state): genealogies, generators, parameters,
+        likelihoods.  Each keeps its beta, step sizes, accept counters, record file and samplers."""
+        self._chk(self.lib.gph_mcmc_exchange_state(self.mcmc, other.mcmc), "exchange_state")
+
     def state(self):
         ll, dl = C.c_double(), C.c_double()
         th, ag, mr = np.zeros(self.pack.K), np.zeros(self.pack.K), np.zeros(max(self.pack.B, 1))
@@ -1242,6 +1268,65 @@ class Sampler:
         if self.engine:
             self.lib.gph_engine_destroy(self.engine)
             self.engine = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MC3:
+    """Metropolis-coupled chains on one device (gph_mc3_*): chain c runs on a copy of the pack seeded with seed + c and keeps
+    betas[c]; at a swap point two neighbours exchange their states, so chains[0] stays the chain of betas[0]."""
+
+    def __init__(self, pack, betas, swap_every=1, swap_seed=None, lib=None):
+        import copy
+        self.betas = [float(b) for b in betas]
+        self.swap_every = int(swap_every)
+        self.swap_seed = int(pack.seed + len(self.betas) if swap_seed is None else swap_seed)
+        self.chains = []
+        self.group = None
+        for c in range(len(self.betas)):
+            q = copy.copy(pack)
+            q.seed = pack.seed + c
+            self.chains.append(Sampler(q, lib=lib))
+        self.lib = self.chains[0].lib if self.chains else (lib or load_library())
+
+    def initialize(self):
+        for s in self.chains:
+            s.initialize()
+        C_ = len(self.chains)
+        hs = (C.c_void_p * max(C_, 1))(*[s.mcmc for s in self.chains])
+        bs = (C.c_double * max(C_, 1))(*self.betas)
+        g = C.c_void_p()
+        Sampler._chk(self.lib.gph_mc3_create(hs, C_, bs, self.swap_every, self.swap_seed & 0xffffffff, C.byref(g)), "mc3_create")
+        self.group = g
+
+    def iteration(self, it):
+        Sampler._chk(self.lib.gph_mc3_iteration(self.group, it), f"mc3 iteration {it}")
+
+    def swap_counts(self):
+        """(attempts, accepted), one entry per pair (c, c + 1)"""
+        n = len(self.chains) - 1
+        a, b = (C.c_int64 * n)(), (C.c_int64 * n)()
+        Sampler._chk(self.lib.gph_mc3_swap_counts(self.group, a, b), "mc3_swap_counts")
+        return list(a), list(b)
+
+    def swap_log(self):
+        """every swap decision so far, as dicts of the fields of gph_mc3_swap"""
+        n = C.c_int64()
+        Sampler._chk(self.lib.gph_mc3_swap_log(self.group, None, 0, C.byref(n)), "mc3_swap_log")
+        buf = (GphMc3Swap * max(n.value, 1))()
+        Sampler._chk(self.lib.gph_mc3_swap_log(self.group, buf, n.value, C.byref(n)), "mc3_swap_log")
+        return [{f: getattr(buf[i], f) for f, _ in GphMc3Swap._fields_ if f != "pad"} for i in range(n.value)]
+
+    def close(self):
+        if self.group:
+            self.lib.gph_mc3_destroy(self.group)
+            self.group = None
+        for s in self.chains:
+            s.close()
 
     def __del__(self):
         try:

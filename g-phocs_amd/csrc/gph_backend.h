@@ -58,6 +58,8 @@ static void dev_clear_error() {}
 static int rng_ahead_side(gph_engine *, GphGrid) { return 0; }
 static int rng_ahead_wait(gph_engine *) { return 0; }
 static void rng_ahead_drain(gph_engine *) {}
+// two engines exchange their pages (gph_exchange.h): one thread of launches here, nothing to order
+static int exchange_order(gph_engine *, gph_engine *) { return 0; }
 
 static int reduce_local(gph_engine *e, int sec, int ncols)
 {
@@ -174,6 +176,7 @@ struct gph_engine : gph_engine_state {
   // kernels; the next sweep kernel waits for ev_ra_done
   hipStream_t stream_ra = nullptr;
   hipEvent_t ev_ra_go = nullptr, ev_ra_done = nullptr;
+  hipEvent_t ev_xchg = nullptr;       // what this engine's stream held when its pages went to another engine (gph_exchange.h)
   struct Tm { hipEvent_t a, b; int which; };
   std::vector<Tm> tm;                // event pairs of the launches since the last synchronisation
   size_t tm_used = 0;
@@ -290,6 +293,28 @@ static int rng_ahead_side(gph_engine *e, GphGrid grid)
 static int rng_ahead_wait(gph_engine *e) { HIPCHK(hipStreamWaitEvent(e->stream, e->ev_ra_done, 0)); return 0; }
 // nothing of it in flight any more (before its buffers or the pages are released)
 static void rng_ahead_drain(gph_engine *e) { if (e->stream_ra) (void)hipStreamSynchronize(e->stream_ra); }
+// two engines are about to exchange their pages (gph_exchange.h): whatever either stream still holds for the pages it gives
+// away -- a finish kernel just queued, a pass of k_rng_ahead reading them on its own stream -- comes before the first launch
+// of the engine that receives them.  Events only: the host does not wait, and no kernel of one engine waits for a kernel of
+// the other.  Both records go out before either wait, so neither stream waits for work queued behind the exchange.  A pass of
+// k_rng_ahead whose draws are dropped also comes before its own engine's next pass, which writes the same buffers.
+static int exchange_order(gph_engine *a, gph_engine *b)
+{
+  gph_engine *const p[2] = {a, b};
+  for (gph_engine *x : p) {
+    if (!x->ev_xchg) HIPCHK(hipEventCreateWithFlags(&x->ev_xchg, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(x->ev_xchg, x->stream));
+  }
+  for (int i = 0; i < 2; i++) {
+    gph_engine *x = p[i], *y = p[1 - i];
+    HIPCHK(hipStreamWaitEvent(y->stream, x->ev_xchg, 0));
+    if (x->ra_b_valid) {
+      HIPCHK(hipStreamWaitEvent(y->stream, x->ev_ra_done, 0));
+      HIPCHK(hipStreamWaitEvent(x->stream, x->ev_ra_done, 0));
+    }
+  }
+  return 0;
+}
 // a flat kernel on the engine's stream; what is pending and what is counted is the caller's business (sample_begin / _end,
 // apply_list, the reductions below)
 template <class... P, class... A>
@@ -457,6 +482,7 @@ static void backend_close(gph_engine *e)
   if (e->h_red) (void)hipHostFree(e->h_red);
   if (e->G_h) (void)hipHostFree(e->G_h);
   for (auto &t : e->tm) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
+  if (e->ev_xchg) (void)hipEventDestroy(e->ev_xchg);
   if (e->ev_ra_go) (void)hipEventDestroy(e->ev_ra_go);
   if (e->ev_ra_done) (void)hipEventDestroy(e->ev_ra_done);
   if (e->stream_ra) (void)hipStreamDestroy(e->stream_ra);

@@ -2923,4 +2923,7 @@ int gph_engine_clades_fetch(gph_engine *e, uint64_t *entries, uint32_t *nkeys, u
   return reset ? clades_zero(e) : 0;
 }
 
+// ---- two engines exchange their chain states (Metropolis-coupled chains)
+#include "gph_exchange.h"
+
 } // extern "C"

@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -26,6 +26,11 @@
 // default 32; --ml-alpha a, default 0.3; per rung --ml-burnin b discarded iterations, default the control file's burn-in or
 // 1000, and --ml-samples s recorded ones, default 2000) and writes the stepping-stone and thermodynamic-integration estimates
 // of the log marginal likelihood to PREFIX.marginal.tsv (rank 0 alone: no parts).  The two exclude each other.
+// --mc3 C runs C = 2 .. 16 Metropolis-coupled chains on the one GPU: chain c on the power posterior with beta_c = 1 / (1 + h c)
+// (--mc3-heat h, default 0.1) and the seed random-seed + c; in front of every k-th iteration (--mc3-swap-every k, default 1,
+// negative: never) two neighbouring chains are proposed to exchange their states.  Chain 0 is the control file's chain and stays
+// the cold one, so the trace and every output above describe the posterior as before; --mc3-report PREFIX writes the ladder,
+// the swap counts and every chain's acceptance to PREFIX.mc3.tsv.  Not with -g N > 1, --beta or --marginal-likelihood.
 // They compose freely.  Under -g N every child leaves parts: of the summary table FILE.part<r>, which the launcher
 // concatenates in rank order into FILE once every child has exited 0; of the others the library's own, which gph_run_finish
 // turns into the files (the launcher itself has not touched a GPU).  A run that did not finish leaves neither parts nor files.
@@ -101,7 +106,7 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
@@ -160,6 +165,20 @@ int main(int argc, char **argv)
       o.marginal_alpha = strtod(argv[++i], &end);
       if (end == argv[i] || *end || !(o.marginal_alpha > 0.0) || o.marginal_alpha > 1e300) { fprintf(stderr, "%s: --ml-alpha takes a finite number a > 0\n", argv[0]); return usage(argv[0]); }
     }
+    else if (!strcmp(argv[i], "--mc3") && i + 1 < argc) {
+      o.mc3_chains = atoi(argv[++i]);
+      if (o.mc3_chains < 2 || o.mc3_chains > 16) { fprintf(stderr, "%s: --mc3 takes a number of chains C in 2 .. 16\n", argv[0]); return usage(argv[0]); }
+    }
+    else if (!strcmp(argv[i], "--mc3-heat") && i + 1 < argc) {
+      char *end = nullptr;
+      o.mc3_heat = strtod(argv[++i], &end);
+      if (end == argv[i] || *end || !(o.mc3_heat > 0.0) || o.mc3_heat > 1e300) { fprintf(stderr, "%s: --mc3-heat takes a finite number h > 0\n", argv[0]); return usage(argv[0]); }
+    }
+    else if (!strcmp(argv[i], "--mc3-swap-every") && i + 1 < argc) {
+      o.mc3_swap_every = atoi(argv[++i]);
+      if (o.mc3_swap_every == 0) { fprintf(stderr, "%s: --mc3-swap-every takes a number of iterations k >= 1, or a negative number for no swaps\n", argv[0]); return usage(argv[0]); }
+    }
+    else if (!strcmp(argv[i], "--mc3-report") && i + 1 < argc) o.mc3_report_prefix = argv[++i];
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
@@ -172,6 +191,13 @@ int main(int argc, char **argv)
     return usage(argv[0]);
   }
   if (o.beta != 0.0 && o.marginal_prefix) { fprintf(stderr, "%s: --beta and --marginal-likelihood exclude each other\n", argv[0]); return usage(argv[0]); }
+  if ((o.mc3_heat != 0.0 || o.mc3_swap_every || o.mc3_report_prefix) && !o.mc3_chains) {
+    fprintf(stderr, "%s: --mc3-heat, --mc3-swap-every and --mc3-report need --mc3 C\n", argv[0]);
+    return usage(argv[0]);
+  }
+  if (o.mc3_chains && gpus > 1) { fprintf(stderr, "%s: --mc3 runs its chains on one GPU: not with -g N > 1\n", argv[0]); return usage(argv[0]); }
+  if (o.mc3_chains && o.beta != 0.0) { fprintf(stderr, "%s: --mc3 and --beta exclude each other\n", argv[0]); return usage(argv[0]); }
+  if (o.mc3_chains && o.marginal_prefix) { fprintf(stderr, "%s: --mc3 and --marginal-likelihood exclude each other\n", argv[0]); return usage(argv[0]); }
   o.ctl = argv[i];
   o.ctl2 = i + 1 < argc ? argv[i + 1] : nullptr;
   char self[PATH_MAX];
@@ -277,7 +303,7 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(o.locus_summary_path); bad = 1; }
     if (bad && out) unlink(o.locus_summary_path);
   }
-  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.marginal_prefix) {
+  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.marginal_prefix || o.mc3_report_prefix) {
     /* the ranks' parts into the files, by the library that wrote them -- or, after a failure, removed */
     if (sym<decltype(&gph_run_finish)>(load_engine(dir, o.ctl, o.ctl2), "gph_run_finish")(&o, gpus, bad)) bad = 1;
   }

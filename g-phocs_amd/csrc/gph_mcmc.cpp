@@ -13,6 +13,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <thread>
+#include <utility>
 #include <vector>
 #include "../../include/gphocs_hip.h"
 #include "gph_global.h"
@@ -423,5 +425,8 @@ int gph_mcmc_accept_counts(gph_mcmc *m, int64_t *counts9)
   counts9[8] = GG(m).rubberband_conflicts;
   return 0;
 }
+
+// ---- Metropolis-coupled chains: the exchange of two chains' states and the group that runs them
+#include "gph_mc3.h"
 
 } // extern "C"

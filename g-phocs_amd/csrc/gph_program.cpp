@@ -1034,6 +1034,9 @@ void Run::trace_line(int it)   /* GPhoCS.c:1763-1769 */
   fflush(trace);
 }
 
+// ---- `--mc3`: the heated chains next to the run's own
+#include "gph_mc3_run.h"
+
 // ---- the outputs.  open: enable on the engine, take the shape, size the host buffer, open this rank's part and write its
 // header; sample: at a trace line, and a flush when the buffer is full; close: the last flush, the trailer, the part closed;
 // write / discard: what becomes of the ranks' parts once the last rank is done (gph_run_finish)
@@ -1481,7 +1484,8 @@ struct Log {
    * added after UpdateTau AND after UpdateSampleAge, so an ancestral population's count goes in twice and an
    * estimated sample age's goes in once stale (the previous iteration's) and once fresh */
   std::vector<int64_t> tauPrevTotal = t0v, tauLastIter = t0v, tauShown = t0v;
-  Log(Run &run, int64_t coals) : R(run), totalCoals(coals) { for (int p = 0; p < R.cfg.K; p++) fTau[p].v = R.mc.ftTaus[p]; }
+  Mc3Run *mc3 = nullptr;         /* `--mc3`: the heated chains are given what chain 0 is given */
+  Log(Run &run, int64_t coals, Mc3Run *chains = nullptr) : R(run), totalCoals(coals), mc3(chains) { for (int p = 0; p < R.cfg.K; p++) fTau[p].v = R.mc.ftTaus[p]; }
   const char *printtime(char *buf, size_t len) const   /* printtime(), utils.c:314-326 */
   {
     const long t = (long)(time(NULL) - wall0);
@@ -1495,6 +1499,7 @@ struct Log {
     std::vector<double> taus(R.cfg.K);
     for (int p = 0; p < R.cfg.K; p++) taus[p] = fTau[p].v;
     gph_mcmc_set_locus_rate_finetune(R.M, fLocus.v);
+    if (mc3) mc3->push_finetunes(fCoal.v, fMig.v, fTheta.v, fRate.v, fMix.v, taus.data(), fLocus.v);
     return R.check(gph_mcmc_set_finetunes(R.M, fCoal.v, fMig.v, fTheta.v, fRate.v, fMix.v, taus.data()), "gph_mcmc_set_finetunes");
   }
   int start();
@@ -1530,6 +1535,7 @@ int Log::start()
   for (int p = 0; p < R.cfg.K; p++) if (fTau[p].v < 0) fTau[p].v = 1.0;
   if (int rc = push_finetunes()) return rc;
   gph_mcmc_set_log_period(R.M, samplesPerLog);
+  if (mc3) mc3->set_log_period(samplesPerLog);
   return GPH_OK;
 }
 
@@ -1595,6 +1601,7 @@ int Log::period(int it)
     findingFinetunes = 0;
     samplesPerLog = R.mc.samplesPerLog;
     gph_mcmc_set_log_period(R.M, samplesPerLog);
+    if (mc3) mc3->set_log_period(samplesPerLog);
     logsPerLine = R.info.logsPerLine;
     if (R.lead) {   /* GPhoCS.c:2232-2251 */
       printf("\n");
@@ -1718,6 +1725,7 @@ struct Marginal {
 int run_chain(const gph_run_options &o)
 {
   Run R(o);
+  std::unique_ptr<Mc3Run> mc3;   /* (behind R: the heated chains go before the loci they were loaded from) */
   Outputs outs(o);   /* (behind R: the parts are closed before anything is freed) */
   int rc;
   if ((rc = R.read_control())) return rc;
@@ -1732,19 +1740,25 @@ int run_chain(const gph_run_options &o)
     if (R.lead) printf("Power posterior: beta = %.10g%s -- the trace and every other output describe p(D|G)^beta p(G|Theta) p(Theta); the log-likelihood columns stay those of the plain likelihood.\n",
                        option_beta(o), option_beta(o) == 0.0 ? " (the prior)" : "");
   }
+  if (o.mc3_chains) {
+    mc3.reset(new Mc3Run(o));
+    if ((rc = mc3->start(R))) return rc;
+  }
 
   const gph_control_info &info = R.info;
   if (R.lead) printf("Starting MCMC: %d burnin, %d running, sampled every %d iteration(s).\n", info.burnin, info.numSamples, info.sampleSkip);
   if (R.lead && info.mutRateMode == 2) printf("Reading locus rates from file %s... ", info.rateFile);   /* readRateFile's progress text (GPhoCS.c:514), printed from initializeMCMC upstream */
   int64_t totalCoals = 0;
   if ((rc = gph_mcmc_initialize(R.M, &totalCoals))) return R.fail(rc, "gph_mcmc_initialize");
+  if (mc3 && (rc = mc3->initialize(R))) return rc;
   for (auto x = outs.list.rbegin(); x != outs.list.rend(); ++x)
     if ((rc = (*x)->open(R))) return rc;
   auto t1 = std::chrono::steady_clock::now();
-  Log log(R, totalCoals);
+  Log log(R, totalCoals, mc3.get());
   if ((rc = log.start())) return rc;
   for (int it = -info.burnin; it < info.numSamples; it++) {
-    if ((rc = gph_mcmc_iteration(R.M, it))) return R.fail(rc, "gph_mcmc_iteration");
+    if (mc3) { if ((rc = mc3->iteration(R, it))) return rc; }
+    else if ((rc = gph_mcmc_iteration(R.M, it))) return R.fail(rc, "gph_mcmc_iteration");
     log.account();
     if (it >= 0 && it % (info.sampleSkip + 1) == 0) {
       R.trace_line(it);
@@ -1760,6 +1774,7 @@ int run_chain(const gph_run_options &o)
     printf("\nMCMC finished. Time used: %s\n", log.printtime(tbuf, sizeof tbuf));   /* GPhoCS.c:2262 */
     if (o.verbose) printf("(%.2f s, %.3f iterations/s)\n", sec, (info.burnin + info.numSamples) / (sec > 0 ? sec : 1));
   }
+  if (mc3) mc3->log_pairs(R);
   fclose(R.trace);
   R.trace = nullptr;
   for (auto x = outs.list.rbegin(); x != outs.list.rend(); ++x)
@@ -1773,7 +1788,12 @@ int run_chain(const gph_run_options &o)
   /* a CHECKED build of the library (-DGPH_BOUNDS, tests only) says here whether an index left its array during the run */
   int32_t where = 0, checked = 0;
   (void)gph_engine_debug_oob(R.E, &where, &checked);
+  /* the report reads the chains' counters: before they go (the group and the heated chains first, then chain 0) */
+  int rcr = GPH_OK;
+  if (mc3 && o.mc3_report_prefix && R.lead) rcr = mc3->write(R, totalCoals);
+  mc3.reset();
   R.release_device();
+  if (rcr) return rcr;
   if (checked && where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
                     "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
@@ -1796,6 +1816,7 @@ extern "C" int gph_run_finish(const gph_run_options *in, int32_t ranks, int32_t 
   if (failed || rc) {
     for (auto &x : outs.list) x->discard(ranks);
     if (o.marginal_prefix) unlink(marginal_path(o.marginal_prefix).c_str());
+    if (o.mc3_report_prefix) unlink(mc3_path(o.mc3_report_prefix).c_str());
   }
   return rc;
 }
@@ -1809,7 +1830,7 @@ extern "C" int gph_run(const gph_run_options *in)
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
   /* the checks on the options alone, before anything is read */
   int rc;
-  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o))) return rc;
+  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o))) return rc;
   rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
   if (o.world == 1) {

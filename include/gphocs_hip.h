@@ -508,6 +508,39 @@ int gph_engine_get_beta(gph_engine *e, double *beta);
 int gph_mcmc_set_beta(gph_mcmc *m, double beta);
 int gph_mcmc_get_beta(gph_mcmc *m, double *beta);
 
+/* Metropolis-coupled chains (MC3) on one device.
+ * gph_engine_exchange_state / gph_mcmc_exchange_state: afterwards a holds the chain STATE b held and the reverse -- per locus
+ * the genealogies, event chains, statistics, generator triples, likelihoods, conditional arrays and (locus-mut-rate VAR) rates;
+ * above the loci everything gph_chain_state carries (below), and at the gph_mcmc level rateVar and the recorded parameter
+ * values.  Each side KEEPS its beta, step sizes, priors, accept counters, log period, record file, samplers and counters.
+ * Device pointers change hands, nothing is copied; the host does not wait for the device; the two engines' streams are
+ * ordered through events.  A commit the engine still owed to its pages runs first (one launch at most).  GPH_EARG, and nothing
+ * changed, unless: a != b, both initialised and without a recorded error, same device, same library variant, the same loci in
+ * the same layout and slot order (two engines loaded from the same arrays), no communicator and no all-reduce hook on either.
+ * gph_mcmc_exchange_state is the call for chains driven by gph_mcmc_iteration; the engine-level call is its per-locus and
+ * chain-state part for a caller with a driver of its own.
+ *
+ * gph_mc3: a group of C = 2 .. 16 chains the caller created and initialised, and goes on owning.  _create gives chain c
+ * betas[c] (gph_mcmc_set_beta) for good.  _iteration is call number t = 0, 1, ... and does two things in this order.  (1) When
+ * swap_every > 0, t > 0 and t % swap_every == 0: two uniforms u1, u2 from the group's own generator -- the general slot's
+ * generator (utils.c:421-426, 459-470) seeded with swap_seed -- pick the pair j = min((int)(u1 (C - 1)), C - 2) and decide:
+ * with l_c chain c's dataLogLikelihood (unheated, as gph_mcmc_get_state gives it), lnr = (beta_j - beta_j+1) (l_j+1 - l_j);
+ * the swap is accepted iff lnr >= 0 or log(u2) < lnr, and then chains j and j + 1 exchange their states.  One gph_mc3_swap is
+ * appended to the log either way (u = u2).  (2) gph_mcmc_iteration(chains[c], iteration) for every c, one host thread a chain,
+ * joined before the call returns; the first failure is returned (with the chain's index on stderr) and stops the group.
+ * Chain 0 holds beta_0 throughout, so with beta_0 = 1 its trace, samplers and outputs describe the posterior.
+ * _swap_counts: attempts and accepted swaps of pair (c, c + 1), C - 1 values each (either may be NULL).  _swap_log: *count =
+ * decisions so far; with out != NULL they are copied (GPH_EARG when max is too small). */
+typedef struct gph_mc3 gph_mc3;
+typedef struct { int32_t call, lower; double beta_lower, beta_upper, l_lower, l_upper, lnr, u; int32_t accepted, pad; } gph_mc3_swap;
+int gph_engine_exchange_state(gph_engine *a, gph_engine *b);
+int gph_mcmc_exchange_state(gph_mcmc *a, gph_mcmc *b);
+int gph_mc3_create(gph_mcmc *const *chains, int32_t C, const double *betas, int32_t swap_every, uint32_t swap_seed, gph_mc3 **out);
+void gph_mc3_destroy(gph_mc3 *g);                       /* the chains stay the caller's */
+int gph_mc3_iteration(gph_mc3 *g, int32_t iteration);
+int gph_mc3_swap_counts(gph_mc3 *g, int64_t *attempts, int64_t *accepted);
+int gph_mc3_swap_log(gph_mc3 *g, gph_mc3_swap *out, int64_t max, int64_t *count);
+
 /* ------------------------------------------------------------------------------------
  * input front end (host only, no GPU): the reference's file formats, unchanged.
  *   gph_control_read   readControlFile + readSecondaryControlFile + checkSettings +
@@ -703,6 +736,26 @@ typedef struct gph_run_options {
   const char *marginal_prefix;
   int32_t marginal_steps, marginal_burnin, marginal_samples;
   double marginal_alpha;
+  /* `--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report PREFIX]`: Metropolis-coupled chains (gph_mc3_* above), all on
+   * this device.  mc3_chains C: 0 = off, 2 .. 16, anything else GPH_EARG.  Chain c has beta_c = 1 / (1 + h c) (mc3_heat h: 0 =
+   * 0.1, negative GPH_EARG) and the seed random-seed + c; the swap generator gets random-seed + C.  Chain 0 is the control
+   * file's chain: the trace, the log lines, the finetune search and every output above are its, exactly as without the option,
+   * and because a swap exchanges states it stays the cold chain -- they describe the posterior.  The heated chains are further
+   * engines loaded from the same host arrays (C times gph_engine_hbm_bytes of device memory; a chain that cannot be allocated
+   * stops the run before the first iteration, with a message).  They are given every step size chain 0 is given (the search
+   * reads chain 0's acceptance only).  A swap of two neighbours is attempted in front of every k-th iteration (mc3_swap_every
+   * k: 0 = 1, negative = never).  The log on stdout states the ladder before the first iteration and attempts / accepted per
+   * pair after the last.  With mc3_report_prefix, rank 0 writes PREFIX.mc3.tsv once, at the end and only on success
+   * (gph_run_finish removes it after a failure; tab-separated, numbers "%.10g"): the header
+   *   chain beta seed swapAttempts swapAccepted accCoal accMig accSpr accTheta accMigRate accTau accMixing meanLnL
+   * one row a chain (the swap columns: pair (c, c + 1), 0 in the last row; acc*: as in PREFIX.marginal.tsv, over all
+   * iterations; meanLnL: the chain's dataLogLikelihood over the iterations >= 0), then "# heat h every k attempted A accepted B".
+   * GPH_EARG, with a message that names the option and before anything is read: mc3_heat, mc3_swap_every or mc3_report_prefix
+   * without mc3_chains; mc3_chains with world > 1, a communicator or an all-reduce hook, with beta, or with marginal_prefix. */
+  int32_t mc3_chains;
+  double mc3_heat;
+  int32_t mc3_swap_every;
+  const char *mc3_report_prefix;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
