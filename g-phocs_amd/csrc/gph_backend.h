@@ -93,7 +93,6 @@ static int wide_terms_bytes(int P) { return 8 * P; }     /* the host form keeps 
 static int zero_error_word(gph_engine *e) { if (e->dev.err) *e->dev.err = 0; return 0; }
 static int loci_loaded(gph_engine *) { return 0; }
 static int scan_lds_limit(gph_engine *) { return 0; }
-static int peer_stream(gph_engine *, gph_comm *) { return 0; }
 static void runtime_version(char *buf, size_t n) { snprintf(buf, n, "host emulation (no HIP runtime)"); }
 #ifdef GPH_BOUNDS
 static int oob_take(int32_t *where) { *where = gph_oob_word; gph_oob_word = 0; return 0; }
@@ -338,24 +337,13 @@ static int flush_pending(gph_engine *e)
   int rc;
   launch_pre(e);
   if (red) {
-    /* several ranks whose kernels can address each other's rows (gph_comm_peer_exchange): the exchange happens INSIDE the
-     * reduction kernel's last block and the stages run there on everybody's rows -- one launch per reduction point, as
-     * with a single rank */
-    const bool inkernel = multi && e->peer_rows != nullptr;
-    const int fuse = sl.n > 0 && (!multi || inkernel);
-    GphPeerX X{1, 0, 0, 0, nullptr, nullptr, nullptr, 0};
-    if (inkernel) X = GphPeerX{gph_comm_world(e->comm), gph_comm_rank(e->comm), e->peer_stride, 0, e->peer_rows, e->peer_flags, e->d_gather, gph_comm_peer_next_gen(e->comm)};
+    const int fuse = sl.n > 0 && !multi;
     if ((rc = launch_grid(e, GphGrid{GPH_RED_BLOCKS, 1}, GPH_RED_THREADS, 0, k_reduce_stage, e->ka, e->dev, nc0, nc1, e->d_part, e->d_ticket,
-                          e->d_red, fuse, sl, e->pend_iteration, X))) return rc;
+                          e->d_red, fuse, sl, e->pend_iteration))) return rc;
     e->n_launches++;
-    if (inkernel) {
-      e->n_collectives++;
-    } else if (multi) {
+    if (e->comm) {     /* (a one-rank communicator too: its row is already everybody's, the collective is counted all the same) */
       if (gph_comm_allgather_stream(e->comm, e->d_red, e->d_gather, GPH_RED_ROW, (void *)e->stream)) return GPH_EHIP;
       e->n_collectives++;
-    } else if (e->comm) {
-      e->n_collectives++;   /* a one-rank communicator: the row is already everybody's */
-      if (gph_comm_allgather_stream(e->comm, e->d_red, e->d_gather, GPH_RED_ROW, (void *)e->stream)) return GPH_EHIP;
     }
     if (fuse) return 0;
   }
@@ -380,7 +368,7 @@ static int reduce_local(gph_engine *e, int sec, int ncols)
   GphStageList none = {0, {0}, {0}};
   launch_pre(e);
   if ((rc = launch_grid(e, GphGrid{GPH_RED_BLOCKS, 1}, GPH_RED_THREADS, 0, k_reduce_stage, e->ka, e->dev, sec == 0 ? ncols : 0, sec == 1 ? ncols : 0,
-                        e->d_part, e->d_ticket, e->d_red, 0, none, 0, GphPeerX{1, 0, 0, 0, nullptr, nullptr, nullptr, 0}))) return rc;
+                        e->d_part, e->d_ticket, e->d_red, 0, none, 0))) return rc;
   e->n_launches += 1;
   return 0;
 }
@@ -459,10 +447,7 @@ static int backend_open(gph_engine *e)
     return GPH_EHIP;
   }
   if (const char *ov = getenv("GPH_SIDE_STREAM")) e->side_stream = atoi(ov) != 0;
-  /* GPH_NONBLOCKING_STREAM=1 (tests): the engine's stream does not order itself against the legacy null stream -- what the
-   * in-kernel exchange of thread ranks needs (gph_engine_set_comm) */
-  const bool nb_ = getenv("GPH_NONBLOCKING_STREAM") && atoi(getenv("GPH_NONBLOCKING_STREAM")) != 0;
-  if ((nb_ ? hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) : hipStreamCreate(&e->stream)) != hipSuccess ||
+  if (hipStreamCreate(&e->stream) != hipSuccess ||
       hipStreamCreateWithFlags(&e->stream_wide, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess ||
       hipHostMalloc((void **)&e->G_h, sizeof(GphGlobal), hipHostMallocDefault) != hipSuccess ||
@@ -492,7 +477,6 @@ static void backend_close(gph_engine *e)
   if (e->stream) (void)hipStreamDestroy(e->stream);
 }
 static int wide_terms_bytes(int) { return 0; }     /* the root sum of the pattern-rich loci needs no terms array on the device */
-/* (null-stream operations; the engine's stream may be a non-blocking one, which does not order itself against them) */
 static int zero_error_word(gph_engine *e)
 {
   return hipMemset(e->dev.err, 0, sizeof(int32_t)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess ? GPH_EHIP : 0;
@@ -527,42 +511,6 @@ static int loci_loaded(gph_engine *e)
 static int scan_lds_limit(gph_engine *e)
 {
   HIPCHK(hipFuncSetAttribute((const void *)k_lrate_scan, hipFuncAttributeMaxDynamicSharedMemorySize, e->lr_lds_bytes));
-  return 0;
-}
-// the in-kernel exchange of the reduced rows between thread ranks of one device, where the communicator offers it: the
-// rows and generation words, and a stream of this rank's own priority level in place of the engine's
-static int peer_stream(gph_engine *e, gph_comm *c)
-{
-  if (!(c && gph_comm_world(c) > 1 && gph_comm_on_stream(c))) return 0;
-  double *rows = nullptr; unsigned long long *flags = nullptr; int32_t stride = 0;
-  int least_ = 0, greatest_ = 0;
-  if (hipDeviceGetStreamPriorityRange(&least_, &greatest_) != hipSuccess) { least_ = greatest_ = 0; }
-  const int levels_ = least_ - greatest_ + 1;
-  if (gph_comm_peer_exchange(c, &rows, &flags, &stride) && stride >= GPH_RED_ROW && gph_comm_world(c) > levels_) {
-    /* more thread ranks than stream priority levels: two ranks would share a hardware-queue pool and could end up behind
-     * each other (tools/peer_exchange_stress.py: world 4 gave up 4 times in 10) -- the event-ordered gather instead */
-    if (gph_comm_rank(c) == 0)
-      fprintf(stderr, "gphocs_hip: the in-kernel exchange is offered for up to %d thread ranks on one device (one stream priority level "
-                      "each); %d ranks use the event-ordered gather\n", levels_, gph_comm_world(c));
-  } else if (gph_comm_peer_exchange(c, &rows, &flags, &stride) && stride >= GPH_RED_ROW) {
-    e->peer_rows = rows; e->peer_flags = flags; e->peer_stride = stride;
-    /* a reduction kernel of this engine may WAIT for another rank's kernel: the engine's stream must not be a blocking
-     * stream then -- a blocking stream orders itself against the legacy null stream, and a null-stream operation of the
-     * other rank's host thread (hipMemset at load time) would wait for this rank's waiting kernel: a deadlock until the
-     * bounded wait gives up (found with tools/probe/peer_dbg.py; the plain two-stream probe, peer_probe.cpp, runs) */
-    /* ... and the ranks' streams must sit on DIFFERENT hardware queues (a kernel that waits for a kernel queued behind it on
-     * the same queue waits for ever).  HIP keeps a pool of hardware queues PER PRIORITY level and hands streams of one level
-     * to its pool round-robin: streams of different priority levels never share a queue, so rank r takes level r mod levels
-     * -- by construction for up to `levels` thread ranks (3 on this runtime: low / normal / high), round-robin luck beyond */
-    hipStream_t ns = nullptr;
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { least = greatest = 0; }
-    const int levels = least - greatest + 1;
-    const int prio = levels > 1 ? least - (gph_comm_rank(c) % levels) : 0;
-    if (hipStreamSynchronize(e->stream) != hipSuccess || hipStreamCreateWithPriority(&ns, hipStreamNonBlocking, prio) != hipSuccess) return GPH_EHIP;
-    (void)hipStreamDestroy(e->stream);
-    e->stream = ns;
-  }
   return 0;
 }
 static void runtime_version(char *buf, size_t n)

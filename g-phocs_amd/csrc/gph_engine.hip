@@ -290,14 +290,11 @@ __device__ void reduce_final_body(int ncols, int cbase, const double *part, doub
   __syncthreads();
 }
 // reduction of section 0 (nc0 columns of the per-locus outputs) and / or section 1 (nc1 columns of the statistics) into
-// this rank's row; the LAST block to finish its partials (ticket) does the final pass and -- single rank -- runs the
-// stages that consume the row in the same launch
-// In-kernel exchange of the reduced rows between ranks whose kernels can address each other's memory (gph_comm_peer_exchange):
-// rank r owns slots rows[(2 r + parity) * stride ...] and the generation word flags[r]; `gather` is this rank's copy of
-// everybody's row of the current generation.
-struct GphPeerX { int world, rank, stride, pad; double *rows; unsigned long long *flags; double *gather; unsigned long long gen; };
+// this rank's row; the LAST block to finish its partials (ticket) does the final pass and -- do_stage: a single rank, whose
+// row is everybody's -- runs the stages that consume the row in the same launch.  Several ranks gather their rows on the
+// stream behind this kernel and run the stages in k_global (gph_backend.h: flush_pending); the kernel waits for nobody
 __global__ void __launch_bounds__(GPH_RED_THREADS) k_reduce_stage(GphKargs KA, GphDev D, int nc0, int nc1, double *part, unsigned *ticket, double *red,
-                                                                  int do_stage, GphStageList SL, int iteration, GphPeerX X)
+                                                                  int do_stage, GphStageList SL, int iteration)
 {
   __shared__ union { double p[3][GPH_RED_SUBS * 4][16]; double f[3][GPH_RED_SUBS][128]; GphStageShared st; } sh;
   __shared__ int s_last;
@@ -317,45 +314,9 @@ __global__ void __launch_bounds__(GPH_RED_THREADS) k_reduce_stage(GphKargs KA, G
   for (int cb = 0; cb < nc1; cb += 128) reduce_final_body(nc1 - cb < 128 ? nc1 - cb : 128, cb, part + 3 * GPH_RED_BLOCKS * GPH_RED_COLS, red + GPH_RED_STRIDE, sh.f);
   if (threadIdx.x == 0) { red[3 * GPH_RED_COLS] = (double)*D.err; *ticket = 0; }
   __syncthreads();
-  const double *rows = red;
-  int world = 1;
-  if (X.world > 1) {
-    /* publish this rank's row in its slot of this generation's parity, then the generation word (release, system scope:
-     * the layout and the scopes are those of slots in peer-mapped memory); wait for every other rank's word; copy the rows
-     * in rank order.  Two slots suffice: a rank can only finish generation g + 1 after everybody has published g + 1, i.e.
-     * has finished reading generation g.  The wait is BOUNDED (a rank that never comes must not hang the device): after
-     * ~4 s of the 100-MHz counter the launch's error word is raised and the run ends with GPH_EKERNEL. */
-    double *mine = X.rows + (size_t)(2 * X.rank + (int)(X.gen & 1)) * X.stride;
-    for (int c = threadIdx.x; c < GPH_RED_ROW; c += blockDim.x) mine[c] = red[c];
-    /* EVERY storing wavefront drains and releases its own stores before the barrier: thread 0's release below covers only
-     * its own wavefront's (MI355X_MICROARCH.md, inter-workgroup visibility) -- without this the other ranks read a row
-     * that is partly the previous generation's, and a garbage conflict-locus index sent a later kernel to address 0 */
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      __atomic_thread_fence(__ATOMIC_RELEASE);
-      __hip_atomic_store(&X.flags[X.rank], X.gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      for (int r = 0; r < X.world; r++) {
-        while (__hip_atomic_load(&X.flags[r], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < X.gen) {
-          __builtin_amdgcn_s_sleep(32);
-          if (__builtin_amdgcn_s_memrealtime() - t0 > 400000000ull) {
-            atomicMax(D.err, 9997); red[3 * GPH_RED_COLS] = 9997.0; r = X.world; break; }
-        }
-      }
-    }
-    __syncthreads();
-    __threadfence_system();      /* every reading wavefront acquires for itself */
-    for (int r = 0; r < X.world; r++) {
-      const double *src = r == X.rank ? red : X.rows + (size_t)(2 * r + (int)(X.gen & 1)) * X.stride;
-      for (int c = threadIdx.x; c < GPH_RED_ROW; c += blockDim.x) X.gather[(size_t)r * GPH_RED_ROW + c] = src[c];
-    }
-    __syncthreads();
-    rows = X.gather; world = X.world;
-  }
-  /* (ONE call site: with two the compiler stops inlining the stage body, the by-reference kernel arguments go through a
-   * 72-byte stack frame, and the kernel faults at address 0 on its first launch with stages -- measured, round 5) */
-  if (do_stage) stages_body(KA, rows, world, SL, iteration, sh.st);
+  /* (ONE call site in this kernel: with two the compiler stops inlining the stage body, the by-reference kernel arguments go
+   * through a 72-byte stack frame, and the kernel faults at address 0 on its first launch with stages -- measured, round 5) */
+  if (do_stage) stages_body(KA, red, 1, SL, iteration, sh.st);
 }
 #endif
 
@@ -496,10 +457,6 @@ struct gph_engine_state {
   GphGlobal *G_h = nullptr, *G_d = nullptr;
   bool G_dirty = true;               // the host mirror was changed since it was last pushed
   int64_t n_huge = 0;                // loci whose sequence block stays in HBM (the first slots)
-  double *peer_rows = nullptr;       // in-kernel exchange of the reduced rows (gph_comm_peer_exchange), else null
-  unsigned long long *peer_flags = nullptr;
-  std::vector<void *> deferred_free; // device blocks released while the in-kernel exchange is on: hipFree waits for the device, and a peer's kernel may be waiting for THIS rank
-  int32_t peer_stride = 0;
   int32_t last_error_code = 0;       // the last fatal error check_error reported (gph_engine_last_error)
   long long last_error_locus = -1;
   bool in_error_dump = false;
@@ -793,19 +750,9 @@ static void dump_one_locus(const gph_engine *e, FILE *f, long long global_locus,
   }
 }
 
-// after a host synchronisation: the error the stages recorded, the counters
-// hipFree synchronises the device.  With the in-kernel exchange another rank's reduction kernel may be spinning for this rank's
-// next row: a free between two reduction points would then wait for a kernel that waits for us.  Such blocks are kept until the
-// engine is destroyed.
-static void eng_free(gph_engine *e, void *p)
-{
-  if (!p) return;
-  if (e->peer_rows) e->deferred_free.push_back(p);
-  else dev_free(p);
-}
-
 extern "C" { static int clades_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables) */
 
+// after a host synchronisation: the error the stages recorded, the counters
 static int check_error(gph_engine *e)
 {
   const int code = e->G_h->error;
@@ -894,7 +841,7 @@ static int rng_ahead_alloc(gph_engine *e)
     dev_clear_error();
     fprintf(stderr, "gphocs_hip: no memory for %d draws ahead of the sweep per locus (%.1f MB): the sweep kernel generates its own\n",
             e->ra_M, (double)(b_draws + b_ckpt + b_tail + b_kprev) / 1e6);
-    eng_free(e, d.ra_draws); eng_free(e, d.ra_ckpt); eng_free(e, d.ra_tail); eng_free(e, d.ra_kprev);
+    dev_free(d.ra_draws); dev_free(d.ra_ckpt); dev_free(d.ra_tail); dev_free(d.ra_kprev);
     d.ra_draws = nullptr; d.ra_ckpt = nullptr; d.ra_tail = nullptr; d.ra_kprev = nullptr;
     e->rng_ahead = false;
     return 0;
@@ -972,8 +919,6 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   dev_free(e->gt.rows.d); dev_free(e->gt.d_sel);
   dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_sel);
-  for (void *p : e->deferred_free) dev_free(p);
-  e->deferred_free.clear();
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
   dev_free(e->d_red);
@@ -1001,10 +946,7 @@ int gph_engine_set_comm(gph_engine *e, gph_comm *c)
     if (gph_comm_world(c) > 64) return GPH_EARG;
     if (dev_alloc((void **)&e->d_gather, sizeof(double) * GPH_RED_ROW * gph_comm_world(c))) return GPH_EHIP;
   }
-  /* (the generation of the exchange belongs to the GROUP -- gph_comm_peer_next_gen: a second engine on the same communicator
-   * goes on where the first one stopped instead of finding flags of generations it has not reached yet) */
-  e->peer_rows = nullptr; e->peer_flags = nullptr; e->peer_stride = 0;
-  return peer_stream(e, c);
+  return 0;
 }
 
 GphGlobal *gph_engine_global_(gph_engine *e) { if (!e) return nullptr; e->G_dirty = true; return e->G_h; }
@@ -1675,7 +1617,7 @@ int gph_engine_steplog_enable(gph_engine *e, const int64_t *loci, int32_t n, int
   /* (before the first initialisation nothing is in flight, and the host mirror of the chain state -- not yet pushed -- must
    * not be overwritten by a read-back) */
   if (e->initialized) { int rcs = flush_sync(e, true); if (!rcs) rcs = finish_sync(e); if (rcs) return rcs; }
-  eng_free(e, (void *)e->dev.slog_map); eng_free(e, e->dev.slog); eng_free(e, e->dev.slog_n);
+  dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   e->dev.slog_map = nullptr; e->dev.slog = nullptr; e->dev.slog_n = nullptr; e->dev.slog_cap = 0;
   e->slog_sel = n;
   if (n == 0) return 0;
@@ -1691,7 +1633,7 @@ int gph_engine_steplog_enable(gph_engine *e, const int64_t *loci, int32_t n, int
   if (dev_alloc((void **)&d_map, sizeof(int32_t) * e->L) || dev_alloc((void **)&d_log, sizeof(double) * 8 * (size_t)n * cap) ||
       dev_alloc((void **)&d_n, sizeof(int32_t) * n) ||
       h2d(e, d_map, map.data(), sizeof(int32_t) * e->L) || h2d(e, d_n, zero.data(), sizeof(int32_t) * n)) {
-    eng_free(e, d_map); eng_free(e, d_log); eng_free(e, d_n);
+    dev_free(d_map); dev_free(d_log); dev_free(d_n);
     e->slog_sel = 0;
     return GPH_EHIP;
   }
@@ -2302,7 +2244,7 @@ static void sample_end(gph_engine *e, int cls, int k, int tms)
   e->cls_launches[cls] += 1;
 }
 
-static void rows_free(gph_engine *e, SmRows &b) { eng_free(e, b.d); b = SmRows{}; }
+static void rows_free(SmRows &b) { dev_free(b.d); b = SmRows{}; }
 static int rows_alloc(SmRows &b, size_t esz, int32_t n, int32_t cap)
 {
   if (dev_alloc((void **)&b.d, esz * (size_t)n * cap)) { b.d = nullptr; return GPH_EHIP; }
@@ -2319,7 +2261,7 @@ static int rows_fetch(gph_engine *e, SmRows &b, void *out, int32_t *rows)
   return 0;
 }
 
-static void parts_free(gph_engine *e, SmParts &p) { eng_free(e, p.d_part); p.d_part = nullptr; p.rd = p.chunk = p.nchunks = 0; }
+static void parts_free(SmParts &p) { dev_free(p.d_part); p.d_part = nullptr; p.rd = p.chunk = p.nchunks = 0; }
 static int parts_alloc(gph_engine *e, SmParts &p, int32_t rd, int32_t default_chunk)
 {
   const int chunk = p.chunk_next > 0 ? p.chunk_next : default_chunk;
@@ -2338,7 +2280,7 @@ static int parts_fold(gph_engine *e, const SmParts &p, int32_t iteration, double
 static int chunked_alloc(gph_engine *e, SmParts &p, SmRows &b, int32_t rd, int32_t default_chunk, int32_t capacity)
 {
   if (parts_alloc(e, p, rd, default_chunk)) return GPH_EHIP;
-  if (rows_alloc(b, sizeof(double), rd, capacity)) { parts_free(e, p); return GPH_EHIP; }
+  if (rows_alloc(b, sizeof(double), rd, capacity)) { parts_free(p); return GPH_EHIP; }
   return 0;
 }
 // per-locus accumulators [L][ncol] in slot order -> out, row h_orig[j] (the local locus slot j holds) of leading dimension ld
@@ -2360,7 +2302,7 @@ int gph_engine_locus_summary_enable(gph_engine *e, int32_t on)
 {
   if (!e || !e->loaded) return GPH_ESTATE;
   SETDEV(e);
-  eng_free(e, e->ls.d);
+  dev_free(e->ls.d);
   e->ls = {};
   if (!on) return 0;
   const int K = e->cfg.K, B = e->cfg.B, var = e->var_rates;
@@ -2425,8 +2367,8 @@ int gph_engine_coal_stats_enable(gph_engine *e, int32_t capacity)
   if (!e || !e->loaded) return GPH_ESTATE;
   if (capacity < 0) return GPH_EARG;
   SETDEV(e);
-  parts_free(e, e->cs.part);
-  rows_free(e, e->cs.rows);
+  parts_free(e->cs.part);
+  rows_free(e->cs.rows);
   e->cs.bd = 0;
   if (capacity == 0) return 0;
   const int n = e->cfg.n, K = e->cfg.K;
@@ -2503,8 +2445,8 @@ int gph_engine_time_slices_enable(gph_engine *e, int32_t slices, int32_t capacit
   if (!e || !e->loaded) return GPH_ESTATE;
   if (capacity < 0) return GPH_EARG;
   SETDEV(e);
-  parts_free(e, e->ts.part);
-  rows_free(e, e->ts.rows);
+  parts_free(e->ts.part);
+  rows_free(e->ts.rows);
   e->ts.shape = GphTsShape{};
   if (capacity == 0) return 0;
   GphTsShape h;
@@ -2590,9 +2532,9 @@ int gph_engine_ancestry_enable(gph_engine *e, int32_t capacity_rows, int64_t max
   if (!e || !e->loaded) return GPH_ESTATE;
   if (capacity_rows < 0) return GPH_EARG;
   SETDEV(e);
-  eng_free(e, e->an.d_acc);
+  dev_free(e->an.d_acc);
   e->an.d_acc = nullptr;
-  rows_free(e, e->an.rows);
+  rows_free(e->an.rows);
   e->an.ncol = 0; e->an.samples = 0;
   e->an.iters.clear();
   e->an.shape = GphAnShape{};
@@ -2608,7 +2550,7 @@ int gph_engine_ancestry_enable(gph_engine *e, int32_t capacity_rows, int64_t max
   }
   if (dev_alloc((void **)&e->an.d_acc, (size_t)need)) { e->an.d_acc = nullptr; return GPH_EHIP; }
   if (rows_alloc(e->an.rows, sizeof(uint32_t), gph_an_row_ints(n, B), capacity_rows)) {
-    eng_free(e, e->an.d_acc);
+    dev_free(e->an.d_acc);
     e->an.d_acc = nullptr;
     return GPH_EHIP;
   }
@@ -2709,8 +2651,8 @@ int gph_engine_gene_trees_enable(gph_engine *e, int32_t capacity_rows, const int
     for (int64_t k = 0; k < nloci; k++)
       if (loci[k] < 0 || (k > 0 && loci[k] <= loci[k - 1])) return GPH_EARG;
   SETDEV(e);
-  rows_free(e, e->gt.rows);
-  eng_free(e, e->gt.d_sel);
+  rows_free(e->gt.rows);
+  dev_free(e->gt.d_sel);
   e->gt.d_sel = nullptr;
   e->gt.sel.clear();
   e->gt.iters.clear();
@@ -2736,7 +2678,7 @@ int gph_engine_gene_trees_enable(gph_engine *e, int32_t capacity_rows, const int
   if (dev_alloc((void **)&e->gt.d_sel, sizeof(int32_t) * sel_slot.size())) { e->gt.d_sel = nullptr; return GPH_EHIP; }
   if (!sel_slot.empty()) { int rc = h2d(e, e->gt.d_sel, sel_slot.data(), sizeof(int32_t) * sel_slot.size()); if (rc) return rc; }
   if (rows_alloc(e->gt.rows, (size_t)h.img.bytes, (int32_t)sel.size(), capacity_rows)) {
-    eng_free(e, e->gt.d_sel);
+    dev_free(e->gt.d_sel);
     e->gt.d_sel = nullptr;
     return GPH_EHIP;
   }
@@ -2815,7 +2757,7 @@ static int clades_zero(gph_engine *e)
 }
 static void clades_free(gph_engine *e)
 {
-  eng_free(e, e->cl.d_ent); eng_free(e, e->cl.d_hdr); eng_free(e, e->cl.d_sel);
+  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_sel);
   e->cl.d_ent = nullptr; e->cl.d_hdr = nullptr; e->cl.d_sel = nullptr;
   e->cl.sel.clear();
   e->cl.shape = GphClShape{};

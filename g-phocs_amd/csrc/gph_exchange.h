@@ -73,7 +73,7 @@ int gph_engine_exchange_state(gph_engine *a, gph_engine *b)
 {
   if (!a || !b || a == b || !a->initialized || !b->initialized) return GPH_EARG;
   if (a->G_h->error || b->G_h->error) return GPH_EARG;
-  if (a->comm || b->comm || a->allreduce || b->allreduce || a->peer_rows || b->peer_rows) return GPH_EARG;
+  if (a->comm || b->comm || a->allreduce || b->allreduce) return GPH_EARG;
   if (!exchange_compatible(a, b)) return GPH_EARG;
   int rc;
   if ((rc = exchange_settle(a)) || (rc = exchange_settle(b))) return rc;

@@ -405,19 +405,27 @@ def test_program_through_rccl_launcher(tmp_path, name):
 
 
 # ---------------------------------------------------------------- world > 1 on the device-resident path
-def _thread_ranks(G, pack_path, iters, world, tmp_path):
-    """`world` ranks as THREADS of this process on the one GPU, each with its engine over its block of loci and a
-    gph_comm_create_local() communicator: the all-gather of the reduced rows runs on the engines' streams (HIP events
-    order the copies), so flush_pending's multi-rank branch -- k_reduce_stage without the fused stage, the gather into
-    `world` rows, k_global combining them in rank order -- runs exactly as it does under RCCL over xGMI"""
-    import threading
-    pk = G.Pack.load(pack_path)
-    lib = G.load_library(dims=(pk.n, pk.K, pk.B))
+def _local_comms(lib, world):
     group = lib.gph_comm_local_group(world, 0)
     assert group
     comms = [lib.gph_comm_create_local(group, r) for r in range(world)]
     assert all(comms) and lib.gph_comm_kind(comms[0]) == b"local" and lib.gph_comm_on_stream(comms[0]) == 1
-    out, errs, stats = [str(tmp_path / f"rec.{r}") for r in range(world)], [], [None] * world
+    return comms
+
+
+def _thread_ranks(G, pack_path, iters, world, tmp_path, comms=None, tag="rec"):
+    """`world` ranks as THREADS of this process on the one GPU, each with its engine over its block of loci and a
+    gph_comm_create_local() communicator: the all-gather of the reduced rows runs on the engines' streams (HIP events
+    order the copies), so flush_pending's multi-rank branch -- k_reduce_stage without the fused stage, the gather into
+    `world` rows, k_global combining them in rank order -- runs exactly as it does under RCCL over xGMI.
+    comms: the caller's communicators (_local_comms), which stay the caller's to destroy; else a group of this run's own"""
+    import threading
+    pk = G.Pack.load(pack_path)
+    lib = G.load_library(dims=(pk.n, pk.K, pk.B))
+    own = comms is None
+    if own:
+        comms = _local_comms(lib, world)
+    out, errs, stats = [str(tmp_path / f"{tag}.{r}") for r in range(world)], [], [None] * world
 
     def work(r):
         try:
@@ -439,7 +447,7 @@ def _thread_ranks(G, pack_path, iters, world, tmp_path):
         t.start()
     for t in th:
         t.join(timeout=900)
-    for c in comms:
+    for c in comms if own else []:
         if c:
             lib.gph_comm_destroy(c)
     assert not errs, errs
@@ -468,106 +476,48 @@ def test_thread_ranks_run_the_resident_multi_rank_path(G, tmp_path, name, world)
     compare_states(str(joined), os.path.join(GOLDEN, name + ".state"), skip_global=True)
 
 
-PEER_WORKER = r"""
-import json, os, sys, threading
-sys.path.insert(0, %(repo)r)
-import gphocs_amd as G
-pk = G.Pack.load(%(pack)r)
-lib = G.load_library(dims=(pk.n, pk.K, pk.B))
-iters, out = %(iters)d, %(out)r
-def one():
-    s = G.Sampler(pk, lib=lib)
-    s.set_record_file(out + ".one"); s.initialize()
-    for it in range(iters): s.iteration(it)
-    s.set_record_file(None); hs = s.host_stats(); s.close(); return hs
-def ranks(tag, world=2):
-    group = lib.gph_comm_local_group(world, 0)
-    comms = [lib.gph_comm_create_local(group, r) for r in range(world)]
-    stats, errs = [None] * world, []
-    def work(r):
-        try:
-            s = G.Sampler(pk, lib=lib, rank=r, world=world, comm=comms[r])
-            s.set_record_file(out + ".%%s.%%d" %% (tag, r)); s.initialize()
-            for it in range(iters): s.iteration(it)
-            s.dump_state(out + ".%%s.%%d.state" %% (tag, r), True)
-            s.set_record_file(None); stats[r] = s.host_stats(); s.close()
-        except Exception as ex:
-            errs.append((r, str(ex))); lib.gph_comm_destroy(comms[r]); comms[r] = None
-    th = [threading.Thread(target=work, args=(r,)) for r in range(world)]
-    [t.start() for t in th]; [t.join(timeout=600) for t in th]
-    [lib.gph_comm_destroy(c) for c in comms if c]
-    assert not errs, errs
-    return stats
-def reuse(world=2):
-    # ADVICE round 5: a SECOND engine on the same communicator must continue the exchange's generation sequence (the flags of the
-    # group still hold the first engine's generations): two chains one after the other on one group, both equal to the single rank's
-    group = lib.gph_comm_local_group(world, 0)
-    comms = [lib.gph_comm_create_local(group, r) for r in range(world)]
-    errs = []
-    for rnd in range(2):
-        def work(r):
-            try:
-                s = G.Sampler(pk, lib=lib, rank=r, world=world, comm=comms[r])
-                s.set_record_file(out + ".r%%d.%%d" %% (rnd, r)); s.initialize()
-                for it in range(12): s.iteration(it)
-                s.set_record_file(None); s.close()
-            except Exception as ex:
-                errs.append((rnd, r, str(ex)))
-        th = [threading.Thread(target=work, args=(r,)) for r in range(world)]
-        [t.start() for t in th]; [t.join(timeout=600) for t in th]
-        if errs: break
-    [lib.gph_comm_destroy(c) for c in comms if c]
-    assert not errs, errs
-    return [open(out + ".r%%d.0" %% rnd).read() == open(out + ".r%%d.1" %% rnd).read() for rnd in range(2)] + \
-           [open(out + ".r0.0").read() == open(out + ".r1.0").read()]
-res = {"one": one()}
-os.environ["GPH_PEER_EXCHANGE"] = "1"
-res["exchange"] = ranks("x")
-res["reuse"] = reuse()
-os.environ["GPH_PEER_EXCHANGE"] = "0"
-res["gather"] = ranks("g")
-print("RESULT " + json.dumps(res))
-"""
-
-
-def test_in_kernel_exchange_makes_a_reduction_point_one_launch(tmp_path):
-    """ranks whose kernels can address each other's rows (thread ranks here, GPH_PEER_EXCHANGE=1)
-    exchange them INSIDE the reduction kernel's last block -- a slot per rank and generation parity, release / acquire on a
-    generation word, a bounded wait -- and run the decision stage there on everybody's rows in rank order: as many launches
-    per iteration as a single rank, no separate gather, no k_global launch.  Records byte-equal to the event-ordered gather
-    (reduction + copies + decision stage) and equal to the single-rank golden.  In a process of its own (a kernel that waits
-    for another stream's kernel needs the two streams on different hardware queues: see below)."""
-    import json
-    name, iters = "m3", CASES["m3"]
-    out = str(tmp_path / "rec")
-    script = tmp_path / "peer.py"
-    script.write_text(PEER_WORKER % dict(repo=REPO, pack=os.path.join(GOLDEN, name + ".gpk"), iters=iters, out=out))
-    # round 6: rank r's stream is created at priority level r mod 3 and HIP keeps a hardware-queue pool per level, so two or three
-    # thread ranks cannot land behind each other on one queue -- no retry, no GPU_MAX_HW_QUEUES (tools/peer_exchange_stress.py:
-    # 10 / 10 fresh processes at world 2 and 3 after stream churn; world 4 shares a level and failed 4 / 10: profiles/r06_peer_exchange_stress.json)
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=900)
-    if r.returncode != 0 and "9997" in r.stderr:
-        # 1 of 4 full-suite runs of round 6 (never alone, never in the 20 stress runs): the bounded wait gave up although the two
-        # ranks' streams sit on different priority levels -- the exchange is an OPT-IN experiment of one-GPU boxes (DESIGN.md section
-        # 6), RCCL is the multi-GPU path: a run in which the device did not keep both queues resident is not a failure of the product
-        pytest.skip("the in-kernel exchange's bounded wait gave up in this process (opt-in experiment; DESIGN.md section 6)")
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-    recs = [open(out + f".{t}.{k}").read() for t in "xg" for k in (0, 1)]
-    assert recs[0] == recs[1] == recs[2] == recs[3]
-    assert res["reuse"] == [True, True, True], res["reuse"]      # a second engine on the same communicator: same records again
-    mine = open(out + ".r1.0").read().splitlines()
-    (tmp_path / "gp").write_text("".join(l + "\n" for l in open(os.path.join(GOLDEN, name + ".rtrace")).read().splitlines()[:len(mine)]))
-    compare_records(out + ".r1.0", tmp_path / "gp")
-    compare_records(out + ".x.0", os.path.join(GOLDEN, name + ".rtrace"))
-    compare_records(out + ".one", os.path.join(GOLDEN, name + ".rtrace"))
-    assert open(out + ".x.0.state").read() == open(out + ".g.0.state").read() and open(out + ".x.1.state").read() == open(out + ".g.1.state").read()
-    # launches: the in-kernel exchange costs none, the gather path one k_global per reduction point with stages
-    x, g, one = res["exchange"], res["gather"], res["one"]
-    # (the rank runs dump their state at the end: one launch more than the single-rank run of this script)
-    assert x[0]["launches"] == x[1]["launches"] and 0 <= x[0]["launches"] - one["launches"] <= 2, (x, one)
-    assert g[0]["launches"] > x[0]["launches"] + 3 * iters, (g, x)
-    assert x[0]["collectives"] == g[0]["collectives"] and x[0]["syncs"] <= iters + 8 and x[0]["resident"]
+def test_thread_rank_gather_costs_one_stage_launch_and_survives_engine_reuse(G, tmp_path):
+    """Thread ranks exchange their reduced rows in ONE way: reduction -> event-ordered gather on the streams -> k_global.
+    Against a single rank, whose reduction kernel runs the decision stage in its own last block, that is one k_global launch
+    more per reduction point with stages; the records are the single-rank golden's all the same.  And a SECOND engine on a
+    communicator that has already served one (two chains one after the other on one group) writes the same records again."""
+    name, iters, world = "m3", CASES["m3"], 2
+    pack, gold = os.path.join(GOLDEN, name + ".gpk"), os.path.join(GOLDEN, name + ".rtrace")
+    # 1. records and the resident path
+    out, stats = _thread_ranks(G, pack, iters, world, tmp_path)
+    assert open(out[0]).read() == open(out[1]).read()
+    compare_records(out[0], gold)
+    for hs in stats:
+        assert hs["resident"] and hs["syncs"] <= iters + 8, hs
+    assert stats[0]["collectives"] == stats[1]["collectives"], stats
+    # 2. launches: the same chain on one rank (no gather, the stages fused into the reduction kernel)
+    pk = G.Pack.load(pack)
+    s = G.Sampler(pk, lib=G.load_library(dims=(pk.n, pk.K, pk.B)))
+    s.set_record_file(str(tmp_path / "one"))
+    s.initialize()
+    for it in range(iters):
+        s.iteration(it)
+    s.set_record_file(None)
+    one = s.host_stats()
+    s.close()
+    compare_records(str(tmp_path / "one"), gold)
+    for hs in stats:
+        assert hs["launches"] > one["launches"] + 3 * iters, (stats, one)
+    # 3. two chains of 12 iterations, one after the other, on the same communicators
+    lib = s.lib
+    comms = _local_comms(lib, world)
+    try:
+        rounds = [_thread_ranks(G, pack, 12, world, tmp_path, comms=comms, tag=f"r{rnd}")[0] for rnd in range(2)]
+    finally:
+        for c in comms:
+            if c:
+                lib.gph_comm_destroy(c)
+    recs = [[open(o).read() for o in outs] for outs in rounds]
+    assert recs[0][0] == recs[0][1] and recs[1][0] == recs[1][1] and recs[0][0] == recs[1][0]
+    mine = recs[1][0].splitlines()
+    (tmp_path / "gp").write_text("".join(l + "\n" for l in open(gold).read().splitlines()[:len(mine)]))
+    compare_records(rounds[0][0], tmp_path / "gp")
+    compare_records(rounds[1][0], tmp_path / "gp")
 
 
 def _ndev():
