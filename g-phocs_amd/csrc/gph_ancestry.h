@@ -30,7 +30,8 @@
 // LDS: G (4 N + about 260) bytes -- 2.5 KB at 16 leaves, 1.9 KB at 200 (G = 1): neither leaves nor bands need tiling in
 // any capacity variant; a lane holds a 10-bit mask, not a set of B bands.
 //
-// The kernel writes no page, draws no random number and touches no chain state.
+// The kernel has one text (the flat-kernel form, gph_sampler.h): the host-emulation build runs it lane by lane, phase by phase.
+// It writes no page, draws no random number and touches no chain state.
 #pragma once
 #include "gph_sampler.h"
 
@@ -67,7 +68,7 @@ GPH_SM_HD void gph_an_shape(const GphLayout &y, GphAnShape &h)
   h.lds_bytes = h.G * h.img.bytes + h.G * y.N * 4 + h.G * 4;
 }
 
-// the LDS of a workgroup (the host form keeps the same arrays in a vector)
+// the LDS of a workgroup
 struct GphAnLds {
   char *img;        // [G][img.bytes]
   uint32_t *up;     // [G][N]: father (low half, as int16) | mask of the live migrations on the node's branch << 16
@@ -114,11 +115,6 @@ GPH_SM_FN void gph_an_mark(const GphAnLds &s, const GphLayout &y, const GphAnSha
 
 // lane (g, i): climb from leaf i to the root of the staged locus g (slot j), then the lane's own columns of the locus's
 // accumulator row `a` and of the sample's row
-#ifdef GPH_HOSTEMU
-#define GPH_AN_ROW_ADD(p) (*(p) += 1u)
-#else
-#define GPH_AN_ROW_ADD(p) ((void)atomicAdd((p), 1u))
-#endif
 GPH_SM_FN void gph_an_leaf(const GphAnLds &s, const GphLayout &y, const GphAnShape &h, int g, int i, double *a, uint32_t *row)
 {
   const int n = y.n, N = y.N, B = y.B, ncol = gph_an_locus_columns(n, B), nrow = gph_an_row_ints(n, B);
@@ -161,80 +157,60 @@ GPH_SM_FN void gph_an_leaf(const GphAnLds &s, const GphLayout &y, const GphAnSha
     const int c = GPH_IX(b * n + i, ncol);
     a[c] = a[c] + 1.0;
     a[GPH_IX(B * n + b * n + i, ncol)] = a[GPH_IX(B * n + b * n + i, ncol)] + first;
-    GPH_AN_ROW_ADD(row + GPH_IX((1 + b) * n + i, nrow));
+    gph_lanes_add(row + GPH_IX((1 + b) * n + i, nrow), 1u);
     anyhit = true;
   }
   if (anyhit) {
     a[GPH_IX(2 * B * n + i, ncol)] = a[GPH_IX(2 * B * n + i, ncol)] + 1.0;
-    GPH_AN_ROW_ADD(row + GPH_IX(i, nrow));
+    gph_lanes_add(row + GPH_IX(i, nrow), 1u);
   }
 }
 
-#ifdef GPH_HOSTEMU
-// host emulation: workgroup w = block x with its lanes one after the other, phase by phase as the barriers order them; the
-// launch hands it a zeroed buffer for its dynamic LDS
-static inline void k_ancestry(GphBlk blk, GphLayout y, GphAnShape h, const char *pages, double *acc, uint32_t *row,
-                              int L)
-{
-  const int n = y.n, N = y.N, ncol = gph_an_locus_columns(n, y.B), upl = h.img.bytes / 16;
-  GphAnLds s;
-  gph_an_carve(blk.lds, N, h, s);
-  const int j0 = blk.x * h.G;
-  bool some = false;
-  for (int g = 0; g < h.G; g++) {
-    s.nm[g] = j0 + g < L ? gph_an_num_migs(pages + (size_t)(j0 + g) * y.page_bytes, y) : 0;
-    some = some || s.nm[g] > 0;
-  }
-  if (!some) return;
-  for (int u = 0; u < h.G * N; u++) {
-    const int g = u / N, v = u - g * N;
-    if (s.nm[g] > 0) s.up[u] = gph_an_up_word(pages + (size_t)(j0 + g) * y.page_bytes + y.o_nd + (size_t)v * 16);
-  }
-  for (int u = 0; u < h.G * upl; u++) {
-    const int g = u / upl, o = (u - g * upl) * 16;
-    if (s.nm[g] > 0) memcpy(s.img + (size_t)g * h.img.bytes + o, pages + (size_t)(j0 + g) * y.page_bytes + gph_pack_unit_src(h.img, o), 16);
-  }
-  for (int g = 0; g < h.G; g++) if (s.nm[g] > 0) gph_an_mark(s, y, h, g);
-  for (int lane = 0; lane < h.G * n; lane++) {
-    const int g = lane / n, i = lane - g * n;
-    if (s.nm[g] > 0) gph_an_leaf(s, y, h, g, i, acc + (size_t)(j0 + g) * ncol, row);
-  }
-}
-#else
-__global__ void __launch_bounds__(GPH_AN_MAXTHREADS) k_ancestry(GphLayout y, GphAnShape h, const char *pages, double *acc, uint32_t *row, int L)
-{
-  extern __shared__ __attribute__((aligned(16))) char an_lds[];
-  const int n = y.n, N = y.N, ncol = gph_an_locus_columns(n, y.B), upl = h.img.bytes / 16;
-  const int tid = threadIdx.x, bd = blockDim.x, j0 = blockIdx.x * h.G;
-  GphAnLds s;
-  gph_an_carve(an_lds, N, h, s);
+// what a lane keeps across the barriers: lane g < G the live migrations of the g-th locus of the group
+struct GphAnLane {
   int mine = 0;
-  if (tid < h.G) {
-    if (j0 + tid < L) mine = gph_an_num_migs(pages + (size_t)(j0 + tid) * y.page_bytes, y);
-    s.nm[tid] = mine;
-  }
-  if (!__syncthreads_or(mine)) return;       /* no live migration in the group: nothing staged, nothing touched (uniform over the workgroup) */
-  for (int u = tid; u < h.G * N; u += bd) {
-    const int g = u / N, v = u - g * N;
-    if (s.nm[GPH_IX(g, h.G)] > 0) {
-      const uint4 rec = *(const uint4 *)(pages + (size_t)(j0 + g) * y.page_bytes + y.o_nd + (size_t)v * 16);
-      s.up[GPH_IX(u, h.G * N)] = gph_an_up_word(&rec);
+};
+
+// workgroup w = block bx
+GPH_FLAT(k_ancestry, GPH_AN_MAXTHREADS, GphLayout y, GphAnShape h, const char *pages, double *acc, uint32_t *row, int L)
+{
+  GPH_FLAT_BODY(GphAnLane);
+  const int n = y.n, N = y.N, ncol = gph_an_locus_columns(n, y.B), upl = h.img.bytes / 16;
+  const int j0 = bx * h.G;
+  GphAnLds s;
+  gph_an_carve(lds, N, h, s);
+  GPH_PHASE {
+    if (tid < h.G) {
+      if (j0 + tid < L) ln.mine = gph_an_num_migs(pages + (size_t)(j0 + tid) * y.page_bytes, y);
+      s.nm[tid] = ln.mine;
     }
   }
-  for (int u = tid; u < h.G * upl; u += bd) {
-    const int g = u / upl, o = (u - g * upl) * 16;
-    if (s.nm[GPH_IX(g, h.G)] > 0) {
-      const uint4 val = *(const uint4 *)(pages + (size_t)(j0 + g) * y.page_bytes + gph_pack_unit_src(h.img, o));
-      *(uint4 *)(s.img + (size_t)g * h.img.bytes + GPH_IX(o, h.img.bytes)) = val;
+  if (!GPH_BLOCK_OR(mine)) return;       /* no live migration in the group: nothing staged, nothing touched (uniform over the workgroup) */
+  GPH_PHASE {
+    for (int u = tid; u < h.G * N; u += bd) {
+      const int g = u / N, v = u - g * N;
+      if (s.nm[GPH_IX(g, h.G)] > 0) {
+        GphNode rec;
+        gph_copy16(&rec, pages + (size_t)(j0 + g) * y.page_bytes + y.o_nd + (size_t)v * 16);
+        s.up[GPH_IX(u, h.G * N)] = gph_an_up_word(&rec);
+      }
+    }
+    for (int u = tid; u < h.G * upl; u += bd) {
+      const int g = u / upl, o = (u - g * upl) * 16;
+      if (s.nm[GPH_IX(g, h.G)] > 0)
+        gph_copy16(s.img + (size_t)g * h.img.bytes + GPH_IX(o, h.img.bytes), pages + (size_t)(j0 + g) * y.page_bytes + gph_pack_unit_src(h.img, o));
     }
   }
-  __syncthreads();
-  if (tid < h.G && mine > 0) gph_an_mark(s, y, h, tid);
-  __syncthreads();
-  const int g = tid / n, i = tid - g * n;
-  if (g < h.G && s.nm[g] > 0) gph_an_leaf(s, y, h, g, i, acc + (size_t)(j0 + g) * ncol, row);
+  GPH_BARRIER;
+  GPH_PHASE {
+    if (tid < h.G && ln.mine > 0) gph_an_mark(s, y, h, tid);
+  }
+  GPH_BARRIER;
+  GPH_PHASE {
+    const int g = tid / n, i = tid - g * n;
+    if (g < h.G && s.nm[g] > 0) gph_an_leaf(s, y, h, g, i, acc + (size_t)(j0 + g) * ncol, row);
+  }
 }
-#endif
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 2

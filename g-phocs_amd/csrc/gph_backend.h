@@ -98,8 +98,9 @@ static void runtime_version(char *buf, size_t n) { snprintf(buf, n, "host emulat
 static int oob_take(int32_t *where) { *where = gph_oob_word; gph_oob_word = 0; return 0; }
 #endif
 
-// ---- launches: a kernel's host form takes its block first (GPH_KERNEL: the block index; a flat kernel: GphBlk) and is
-// called once per block, one block after the other, with a zeroed scratch buffer for its dynamic LDS
+// ---- launches: on the host a kernel takes its block first (GPH_KERNEL: the block index; a flat kernel, GPH_FLAT in
+// gph_sampler.h: GphBlk) and is called once per block, one block after the other, with a zeroed scratch buffer for its dynamic
+// LDS.  A flat kernel is the device text itself, run lane by lane between its barriers; only k_rng_ahead has a host form of its own
 static void launch_pre(gph_engine *e)
 {
   g_model = e->G_h->model; g_lay = e->lay; gph_G_emu = e->G_h;
@@ -149,7 +150,7 @@ static int debug_math(const double *x, const double *y, int n, double *out, int)
   memset(&ka, 0, sizeof ka);
   fill_math_constants(ka);
   std::vector<char> lds;
-  return run_blocks(lds, GphGrid{(n + 255) / 256, 1}, 256, 0, k_debug_math, ka, x, y, n, out);
+  return run_blocks(lds, GphGrid{(n + GPH_FLAT_THREADS - 1) / GPH_FLAT_THREADS, 1}, GPH_FLAT_THREADS, 0, k_debug_math, ka, x, y, n, out);
 }
 
 #else
@@ -544,7 +545,7 @@ static int debug_math(const double *x, const double *y, int n, double *out, int 
   memset(&ka, 0, sizeof ka);
   fill_math_constants(ka);
   if (fill_math_tables(ka)) return GPH_EHIP;
-  { int rcl = launch_on(nullptr, GphGrid{(n + 255) / 256, 1}, 256, 0, k_debug_math, ka, dx, dy, n, dout); if (rcl) return rcl; }
+  { int rcl = launch_on(nullptr, GphGrid{(n + GPH_FLAT_THREADS - 1) / GPH_FLAT_THREADS, 1}, GPH_FLAT_THREADS, 0, k_debug_math, ka, dx, dy, n, dout); if (rcl) return rcl; }
   HIPCHK(hipMemcpy(out, dout, sizeof(double) * 5 * n, hipMemcpyDeviceToHost));
   (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
   return 0;

@@ -19,9 +19,9 @@
 // internal node into one LDS double (ages are STAGED with the records, not read again at update time: the lane that loads
 // record v is not the lane that later owns node v, and 8 (n - 1) bytes a locus are cheaper than a second trip to the page).
 // Lane (g, i) then climbs from leaf i and ORs its bit into the mask of every ancestor ([G][n - 1][2W] u32, zeroed; a 32-bit LDS
-// integer atomic -- order-free; the host form a plain OR), at most N steps, a father outside n .. N - 1 ends the climb.  After
-// a barrier lane (g, v - n) hashes its key (a splitmix64 finaliser folded over the words: plain integer arithmetic, one
-// function for both forms) and probes the locus's table in HBM linearly: a hit updates the lane's own cell -- distinct nodes
+// integer atomic -- order-free: gph_lanes_bits, gph_sampler.h), at most N steps, a father outside n .. N - 1 ends the climb.  After
+// a barrier lane (g, v - n) hashes its key (a splitmix64 finaliser folded over the words: plain integer
+// arithmetic) and probes the locus's table in HBM linearly: a hit updates the lane's own cell -- distinct nodes
 // of a tree have distinct keys, no two lanes share a cell, and this phase writes no key -- a miss sets a flag in LDS.  After a
 // second barrier one lane a locus takes the flagged nodes in node-index order and inserts or drops them by the rule (it
 // probes again, for the key as well: a damaged record with two equal clades still follows the rule).  Misses are rare once a
@@ -29,7 +29,8 @@
 // No fp atomics, no global atomics: a locus has one owner workgroup.
 // LDS: G (4 N + (n - 1) (8 + 8 W + 4)) bytes -- 6.6 KB at 16 leaves (G = 16), 10.1 KB at 200 (G = 1, W = 4).
 //
-// The kernel writes no page, draws no random number and touches no chain state.
+// The kernel has one text (the flat-kernel form, gph_sampler.h): the host-emulation build runs it lane by lane, phase by phase.
+// It writes no page, draws no random number and touches no chain state.
 #pragma once
 #include "gph_sampler.h"
 
@@ -67,7 +68,7 @@ GPH_SM_HD int32_t gph_cl_default_slots(int n)
   return p;
 }
 
-// the LDS of a workgroup (the host form keeps the same arrays in a vector)
+// the LDS of a workgroup
 struct GphClLds {
   double *age;      // [G][n - 1] ages of the internal nodes
   int32_t *up;      // [G][N] father
@@ -102,11 +103,6 @@ GPH_SM_FN void gph_cl_stage(const GphClLds &s, const GphLayout &y, const GphClSh
 }
 
 // lane (g, i): leaf i's bit into the mask of every ancestor
-#ifdef GPH_HOSTEMU
-#define GPH_CL_OR(p, b) (*(p) |= (b))
-#else
-#define GPH_CL_OR(p, b) ((void)atomicOr((p), (b)))
-#endif
 GPH_SM_FN void gph_cl_climb(const GphClLds &s, const GphLayout &y, const GphClShape &h, int g, int i)
 {
   const int n = y.n, N = y.N, mw = 2 * h.W;
@@ -114,7 +110,7 @@ GPH_SM_FN void gph_cl_climb(const GphClLds &s, const GphLayout &y, const GphClSh
   for (int guard = 0; guard < N; guard++) {
     const int f = s.up[GPH_IX(g * N + v, h.G * N)];
     if (f < n || f >= N) break;               /* the root's -1, or a damaged record: no ancestor's mask beyond the arrays */
-    GPH_CL_OR(s.mask + GPH_IX((g * (n - 1) + (f - n)) * mw + (i >> 5), h.G * (n - 1) * mw), 1u << (i & 31));
+    gph_lanes_bits(s.mask + GPH_IX((g * (n - 1) + (f - n)) * mw + (i >> 5), h.G * (n - 1) * mw), 1u << (i & 31));
     v = f;
   }
 }
@@ -204,68 +200,48 @@ GPH_SM_FN void gph_cl_insert(const GphClLds &s, const GphLayout &y, const GphClS
   if (any) { hdr[0] = nkeys; hdr[1] = dropped; }
 }
 
-#ifdef GPH_HOSTEMU
-// host emulation: workgroup w = block x with its lanes one after the other, phase by phase as the barriers order them; the
-// launch hands it a zeroed buffer for its dynamic LDS
-static inline void k_clades(GphBlk blk, GphLayout y, GphClShape h, const char *pages, const int32_t *sel_slot, int nsel, int L,
-                            uint64_t *ent, uint32_t *hdr)
+// workgroup w = block bx
+GPH_FLAT(k_clades, GPH_CL_THREADS, GphLayout y, GphClShape h, const char *pages, const int32_t *sel_slot, int nsel, int L, uint64_t *ent,
+         uint32_t *hdr)
 {
-  const int n = y.n, N = y.N, ni = n - 1;
+  GPH_FLAT_BODY(GphNoLane);
+  const int n = y.n, N = y.N, ni = n - 1, w = bx;
   if (ni < 1) return;
   GphClLds s;
-  gph_cl_carve(blk.lds, y, h, s);
-  for (int u = 0; u < h.G * N; u++) {
-    const int g = u / N, v = u - g * N, j = gph_cl_slot(h, sel_slot, nsel, L, blk.x, g);
-    if (j >= 0) gph_cl_stage(s, y, h, g, v, pages + (size_t)j * y.page_bytes + y.o_nd + (size_t)v * 16);
-  }
-  for (int t = 0; t < h.G * n; t++) {
-    const int g = t / n, i = t - g * n;
-    if (blk.x * h.G + g < nsel) gph_cl_climb(s, y, h, g, i);
-  }
-  for (int t = 0; t < h.G * ni; t++) {
-    const int g = t / ni, k = t - g * ni, q = blk.x * h.G + g;
-    if (q < nsel) gph_cl_lookup(s, y, h, g, k, ent + (size_t)q * h.P * h.ew);
-  }
-  for (int g = 0; g < h.G; g++) {
-    const int q = blk.x * h.G + g;
-    if (q < nsel) gph_cl_insert(s, y, h, g, ent + (size_t)q * h.P * h.ew, hdr + (size_t)q * 2);
-  }
-}
-#else
-__global__ void __launch_bounds__(GPH_CL_THREADS) k_clades(GphLayout y, GphClShape h, const char *pages, const int32_t *sel_slot, int nsel, int L,
-                                                           uint64_t *ent, uint32_t *hdr)
-{
-  extern __shared__ __attribute__((aligned(16))) char cl_lds[];
-  const int n = y.n, N = y.N, ni = n - 1;
-  if (ni < 1) return;
-  const int tid = threadIdx.x, bd = blockDim.x, w = blockIdx.x;
-  GphClLds s;
-  gph_cl_carve(cl_lds, y, h, s);
-  for (int u = tid; u < h.G * ni * 2 * h.W; u += bd) s.mask[GPH_IX(u, h.G * ni * 2 * h.W)] = 0u;
-  for (int u = tid; u < h.G * N; u += bd) {
-    const int g = u / N, v = u - g * N, j = gph_cl_slot(h, sel_slot, nsel, L, w, g);
-    if (j >= 0) {
-      const uint4 rec = *(const uint4 *)(pages + (size_t)j * y.page_bytes + y.o_nd + (size_t)v * 16);
-      gph_cl_stage(s, y, h, g, v, &rec);
+  gph_cl_carve(lds, y, h, s);
+  GPH_PHASE {
+    for (int u = tid; u < h.G * ni * 2 * h.W; u += bd) s.mask[GPH_IX(u, h.G * ni * 2 * h.W)] = 0u;
+    for (int u = tid; u < h.G * N; u += bd) {
+      const int g = u / N, v = u - g * N, j = gph_cl_slot(h, sel_slot, nsel, L, w, g);
+      if (j >= 0) {
+        GphNode rec;
+        gph_copy16(&rec, pages + (size_t)j * y.page_bytes + y.o_nd + (size_t)v * 16);
+        gph_cl_stage(s, y, h, g, v, &rec);
+      }
     }
   }
-  __syncthreads();
-  for (int t = tid; t < h.G * n; t += bd) {
-    const int g = t / n, i = t - g * n;
-    if (w * h.G + g < nsel) gph_cl_climb(s, y, h, g, i);
+  GPH_BARRIER;
+  GPH_PHASE {
+    for (int t = tid; t < h.G * n; t += bd) {
+      const int g = t / n, i = t - g * n;
+      if (w * h.G + g < nsel) gph_cl_climb(s, y, h, g, i);
+    }
   }
-  __syncthreads();
-  for (int t = tid; t < h.G * ni; t += bd) {
-    const int g = t / ni, k = t - g * ni, q = w * h.G + g;
-    if (q < nsel) gph_cl_lookup(s, y, h, g, k, ent + (size_t)q * h.P * h.ew);
+  GPH_BARRIER;
+  GPH_PHASE {
+    for (int t = tid; t < h.G * ni; t += bd) {
+      const int g = t / ni, k = t - g * ni, q = w * h.G + g;
+      if (q < nsel) gph_cl_lookup(s, y, h, g, k, ent + (size_t)q * h.P * h.ew);
+    }
   }
-  __syncthreads();
-  if (tid < h.G) {
-    const int q = w * h.G + tid;
-    if (q < nsel) gph_cl_insert(s, y, h, tid, ent + (size_t)q * h.P * h.ew, hdr + (size_t)q * 2);
+  GPH_BARRIER;
+  GPH_PHASE {
+    if (tid < h.G) {
+      const int q = w * h.G + tid;
+      if (q < nsel) gph_cl_insert(s, y, h, tid, ent + (size_t)q * h.P * h.ew, hdr + (size_t)q * 2);
+    }
   }
 }
-#endif
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 2

@@ -40,6 +40,7 @@
 // below 2^53).  Ranks: each rank's row covers its own loci; the rows are added in rank order by whoever combines them
 // (INTEGRATION.md).
 //
+// Each kernel has one text (the flat-kernel form, gph_sampler.h): the host-emulation build runs it lane by lane, phase by phase.
 // The kernels write no page, draw no random number and touch no chain state.
 #pragma once
 #include "gph_sampler.h"
@@ -67,7 +68,7 @@ GPH_SM_HD int gph_cs_block(int n, int K)
   return bd < 64 ? 64 : bd;
 }
 
-// the LDS of a workgroup (the host form keeps the same arrays in a vector)
+// the LDS of a workgroup
 struct GphCsLds {
   GphNode *nd;          // [N] node records of the current locus
   double *agesum;       // [K][bd]
@@ -193,85 +194,65 @@ GPH_SM_FN void gph_cs_chunk_pair_out(const GphCsLds &s, int n, int K, int bd, in
   out[CS_FIXED + 2 * npk + col] = s.agesum[at];
 }
 
-#ifdef GPH_HOSTEMU
-// host emulation: workgroup (ch, tile) = block (x, y) with its lanes one after the other, phase by phase as the barriers
-// order them; the launch hands it a zeroed buffer for its dynamic LDS
-static inline void k_coal_stats(GphBlk blk, GphLayout y, const char *pages, double *part, int L, int chunk)
-{
-  const int n = y.n, N = y.N, K = y.K, B = y.B, np = gph_cs_pairs(n), rd = gph_cs_row_doubles(n, K);
-  const int bd = blk.dim, ch = blk.x, tile = blk.y;
-  GphCsLds s;
-  gph_cs_carve(blk.lds, n, K, B, bd, s);
-  const int j0 = ch * chunk, j1 = j0 + chunk < L ? j0 + chunk : L;
-  const int valid = np - tile * bd < bd ? np - tile * bd : bd;
-  double sgen = 0.0, sdata = 0.0;
-  for (int j = j0; j < j1; j++) {
-    const char *pg = pages + (size_t)j * y.page_bytes;
-    memcpy((void *)s.nd, pg + y.o_nd, (size_t)N * sizeof(GphNode));
-    for (int v = n; v < N; v++) gph_cs_rank_first(s, n, N, v);
-    for (int lane = 0; lane < valid; lane++) {
-      int a, b;
-      gph_cs_pair(tile * bd + lane, n, a, b);
-      gph_cs_pair_add(s, N, K, bd, lane, gph_cs_lca(s, N, a, b));
-    }
-    if (tile == 0) {
-      for (int i = 0; i < n - 1; i++) gph_cs_flat_add(s, n, i);
-      const int16_t *ncoal = (const int16_t *)(pg + y.o_ncoal), *nmig = (const int16_t *)(pg + y.o_nmig);
-      for (int q = 0; q < K + B; q++) s.evt[q] += q < K ? ncoal[q] : nmig[q - K];
-      const double *fs = (const double *)(pg + y.o_fscal);
-      sgen = sgen + fs[FS_GENLNL];
-      sdata = sdata + fs[FS_DATALNL];
-    }
-  }
-  double *out = part + (size_t)ch * rd;
-  for (int q = 0; q < valid * K; q++) gph_cs_chunk_pair_out(s, n, K, bd, tile, q, out);
-  if (tile == 0) gph_cs_chunk_fixed(s, n, K, B, sgen, sdata, out);
-}
-#else
-__global__ void __launch_bounds__(GPH_CS_MAXTHREADS) k_coal_stats(GphLayout y, const char *pages, double *part, int L, int chunk)
-{
-  extern __shared__ __attribute__((aligned(16))) char cs_lds[];
-  const int n = y.n, N = y.N, K = y.K, B = y.B, np = gph_cs_pairs(n), rd = gph_cs_row_doubles(n, K);
-  const int tid = threadIdx.x, bd = blockDim.x, ch = blockIdx.x, tile = blockIdx.y;
-  GphCsLds s;
-  gph_cs_carve(cs_lds, n, K, B, bd, s);
-  const int valid = np - tile * bd < bd ? np - tile * bd : bd;
-  int la = 0, lb = 1;
-  if (tid < valid) gph_cs_pair(tile * bd + tid, n, la, lb);
-  for (int q = tid; q < K * bd; q += bd) { s.agesum[q] = 0.0; s.cnt[q] = 0u; s.first[q] = 0u; }
-  for (int q = tid; q < n - 1; q += bd) { s.flat_m[q] = 0.0; s.flat_c[q] = 0.0; }
-  for (int q = tid; q < K + B; q += bd) s.evt[q] = 0;
-  const int j0 = ch * chunk, j1 = j0 + chunk < L ? j0 + chunk : L;
-  double sgen = 0.0, sdata = 0.0;
+// what a lane keeps across the barriers: its pair, the node record of the next locus (on its way while this one is worked on),
+// the LCA of its pair, and (lane 0 of tile 0) the log-likelihoods of the locus and their sums over the chunk
+struct GphCsLane {
+  int la = 0, lb = 1, l = 0;
   GphNode pre = {0.0, -1, -1, -1, 0};
-  if (tid < N && j0 < j1) pre = ((const GphNode *)(pages + (size_t)j0 * y.page_bytes + y.o_nd))[tid];
+  double lg = 0.0, ld = 0.0, sgen = 0.0, sdata = 0.0;
+};
+
+// workgroup (ch, tile) = block (bx, by)
+GPH_FLAT(k_coal_stats, GPH_CS_MAXTHREADS, GphLayout y, const char *pages, double *part, int L, int chunk)
+{
+  GPH_FLAT_BODY(GphCsLane);
+  const int n = y.n, N = y.N, K = y.K, B = y.B, np = gph_cs_pairs(n), rd = gph_cs_row_doubles(n, K);
+  const int ch = bx, tile = by;
+  GphCsLds s;
+  gph_cs_carve(lds, n, K, B, bd, s);
+  const int valid = np - tile * bd < bd ? np - tile * bd : bd;
+  const int j0 = ch * chunk, j1 = j0 + chunk < L ? j0 + chunk : L;
+  GPH_PHASE {
+    if (tid < valid) gph_cs_pair(tile * bd + tid, n, ln.la, ln.lb);
+    for (int q = tid; q < K * bd; q += bd) { s.agesum[q] = 0.0; s.cnt[q] = 0u; s.first[q] = 0u; }
+    for (int q = tid; q < n - 1; q += bd) { s.flat_m[q] = 0.0; s.flat_c[q] = 0.0; }
+    for (int q = tid; q < K + B; q += bd) s.evt[q] = 0;
+    if (tid < N && j0 < j1) ln.pre = ((const GphNode *)(pages + (size_t)j0 * y.page_bytes + y.o_nd))[tid];
+  }
   for (int j = j0; j < j1; j++) {
     const char *pg = pages + (size_t)j * y.page_bytes;
-    __syncthreads();        /* everybody is done with the previous locus's records (first pass: with zeroing) */
-    if (tid < N) s.nd[tid] = pre;
-    for (int v = tid + bd; v < N; v += bd) s.nd[v] = ((const GphNode *)(pg + y.o_nd))[v];
-    if (tid < N && j + 1 < j1) pre = ((const GphNode *)(pg + y.page_bytes + y.o_nd))[tid];
-    double lg = 0.0, ld = 0.0;
-    if (tile == 0 && tid == 0) { const double *fs = (const double *)(pg + y.o_fscal); lg = fs[FS_GENLNL]; ld = fs[FS_DATALNL]; }
-    __syncthreads();
-    for (int v = n + tid; v < N; v += bd) gph_cs_rank_first(s, n, N, v);
-    const int l = tid < valid ? gph_cs_lca(s, N, la, lb) : 0;
-    __syncthreads();        /* the first-coalescence flags and the sorted ages are complete */
-    if (tid < valid) gph_cs_pair_add(s, N, K, bd, tid, l);
-    if (tile == 0) {
-      for (int i = tid; i < n - 1; i += bd) gph_cs_flat_add(s, n, i);
-      const int16_t *ncoal = (const int16_t *)(pg + y.o_ncoal), *nmig = (const int16_t *)(pg + y.o_nmig);
-      for (int q = tid; q < K + B; q += bd) s.evt[q] += q < K ? ncoal[q] : nmig[q - K];
-      sgen = sgen + lg;
-      sdata = sdata + ld;
+    GPH_BARRIER;        /* everybody is done with the previous locus's records (first pass: with zeroing) */
+    GPH_PHASE {
+      if (tid < N) s.nd[tid] = ln.pre;
+      for (int v = tid + bd; v < N; v += bd) s.nd[v] = ((const GphNode *)(pg + y.o_nd))[v];
+      if (tid < N && j + 1 < j1) ln.pre = ((const GphNode *)(pg + y.page_bytes + y.o_nd))[tid];
+      ln.lg = 0.0; ln.ld = 0.0;
+      if (tile == 0 && tid == 0) { const double *fs = (const double *)(pg + y.o_fscal); ln.lg = fs[FS_GENLNL]; ln.ld = fs[FS_DATALNL]; }
+    }
+    GPH_BARRIER;
+    GPH_PHASE {
+      for (int v = n + tid; v < N; v += bd) gph_cs_rank_first(s, n, N, v);
+      ln.l = tid < valid ? gph_cs_lca(s, N, ln.la, ln.lb) : 0;
+    }
+    GPH_BARRIER;        /* the first-coalescence flags and the sorted ages are complete */
+    GPH_PHASE {
+      if (tid < valid) gph_cs_pair_add(s, N, K, bd, tid, ln.l);
+      if (tile == 0) {
+        for (int i = tid; i < n - 1; i += bd) gph_cs_flat_add(s, n, i);
+        const int16_t *ncoal = (const int16_t *)(pg + y.o_ncoal), *nmig = (const int16_t *)(pg + y.o_nmig);
+        for (int q = tid; q < K + B; q += bd) s.evt[q] += q < K ? ncoal[q] : nmig[q - K];
+        ln.sgen = ln.sgen + ln.lg;
+        ln.sdata = ln.sdata + ln.ld;
+      }
     }
   }
-  __syncthreads();
+  GPH_BARRIER;
   double *out = part + (size_t)ch * rd;
-  for (int q = tid; q < valid * K; q += bd) gph_cs_chunk_pair_out(s, n, K, bd, tile, q, out);
-  if (tile == 0 && tid == 0) gph_cs_chunk_fixed(s, n, K, B, sgen, sdata, out);
+  GPH_PHASE {
+    for (int q = tid; q < valid * K; q += bd) gph_cs_chunk_pair_out(s, n, K, bd, tile, q, out);
+    if (tile == 0 && tid == 0) gph_cs_chunk_fixed(s, n, K, B, ln.sgen, ln.sdata, out);
+  }
 }
-#endif
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 2

@@ -99,21 +99,18 @@ GPH_HD void apply_list_locus(char *pg, const GphLayout &y, const GphApply *ap, i
   }
   fs[FS_GENLNL] = v;
 }
-#ifdef GPH_HOSTEMU
-static void k_apply_list(GphBlk b, GphKargs KA, GphDev D)
+// (a flat kernel: one text for both builds, gph_sampler.h)
+#define GPH_FLAT_THREADS 256
+GPH_FLAT(k_apply_list, GPH_FLAT_THREADS, GphKargs KA, GphDev D)
 {
+  GPH_FLAT_BODY(GphNoLane);
   const int na = KA.G->napply;
-  for (int g = b.x * b.dim; g < (b.x + 1) * b.dim && g < D.L && na > 0; g++)
-    apply_list_locus(D.pages + (size_t)g * KA.lay.page_bytes, KA.lay, KA.G->apply, na);
+  GPH_PHASE {
+    const int g = bx * bd + tid;
+    if (g < D.L && na != 0) apply_list_locus(D.pages + (size_t)g * KA.lay.page_bytes, KA.lay, KA.G->apply, na);
+  }
 }
-#else
-__global__ void k_apply_list(GphKargs KA, GphDev D)
-{
-  int g = blockIdx.x * blockDim.x + threadIdx.x;
-  const int na = KA.G->napply;
-  if (g >= D.L || na == 0) return;
-  apply_list_locus(D.pages + (size_t)g * KA.lay.page_bytes, KA.lay, KA.G->apply, na);
-}
+#ifndef GPH_HOSTEMU
 // the stage above the loci (gph_global.h): one wavefront, every lane runs the same scalar code, lane 0's stores count
 // ---- the stage(s) above the loci (gph_global.h) and the reductions that feed them, as ONE launch.
 // The chain state (12 KB) and the ranks' reduced rows are staged through LDS by the whole block -- coalesced copies
@@ -321,27 +318,21 @@ __global__ void __launch_bounds__(GPH_RED_THREADS) k_reduce_stage(GphKargs KA, G
 #endif
 
 // parity probe: the device's exp/log (gph_math.h) and its native sqrt / divide / floor
-#ifdef GPH_HOSTEMU
-static void k_debug_math(GphBlk b, GphKargs KA, const double *x, const double *y, int n, double *o)
+GPH_FLAT(k_debug_math, GPH_FLAT_THREADS, GphKargs KA, const double *x, const double *y, int n, double *o)
 {
+  GPH_FLAT_BODY(GphNoLane);
   (void)KA;
-  for (int i = b.x * b.dim; i < (b.x + 1) * b.dim && i < n; i++) {
-    o[i] = gph_exp(x[i]); o[n + i] = gph_log(x[i]); o[2 * n + i] = sqrt(fabs(x[i]));
-    o[3 * n + i] = x[i] / y[i]; o[4 * n + i] = floor(x[i]);
+  GPH_PHASE {
+    const int i = bx * bd + tid;
+    if (i < n) {
+      o[i] = gph_exp(x[i]);
+      o[n + i] = gph_log(x[i]);
+      o[2 * n + i] = sqrt(fabs(x[i]));
+      o[3 * n + i] = x[i] / y[i];
+      o[4 * n + i] = floor(x[i]);
+    }
   }
 }
-#else
-__global__ void k_debug_math(GphKargs KA, const double *x, const double *y, int n, double *o)
-{
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  o[i] = gph_exp(x[i]);
-  o[n + i] = gph_log(x[i]);
-  o[2 * n + i] = sqrt(fabs(x[i]));
-  o[3 * n + i] = x[i] / y[i];
-  o[4 * n + i] = floor(x[i]);
-}
-#endif
 
 // ---------------------------------------------------------------- the sweep's uniforms, generated ahead of it
 // One lane per locus slot: the three Wichmann-Hill recurrences of the slot's stream from the generator state in its page
@@ -354,6 +345,8 @@ GPH_HD int rng_ahead_count(int kprev, int M)
   int n = (kprev + 64 + 63) & ~63;
   return n < 0 ? 0 : n > M ? M : n;
 }
+// Two forms on purpose (not the flat-kernel form of gph_sampler.h): the host form below is the plain-division statement of
+// l_rndu that the tests pin, the device form reaches the same bits with shuffles, an LDS transpose and FMA quotients.
 #ifdef GPH_HOSTEMU
 static void k_rng_ahead(GphBlk b, GphKargs KA, GphDev D)
 {
@@ -445,6 +438,11 @@ struct SmParts {     // one partial row of rd doubles per chunk of `chunk` slots
   int32_t chunk_next = 0;      // slots per chunk of the next alloc (the _set_chunk entry points; 0: the default)
 };
 
+struct SmSel {       // a selection of loci: those of this rank, global indices in increasing order, and the page slot of each in HBM
+  std::vector<int64_t> loci;
+  int32_t *d_slot = nullptr;
+};
+
 // what both builds keep of an engine; gph_backend.h completes it (struct gph_engine) with the members only one has
 struct gph_engine_state {
   gph_config cfg;
@@ -525,10 +523,10 @@ struct gph_engine_state {
   struct { double *d_acc = nullptr; SmRows rows; int32_t ncol = 0; int64_t samples = 0; GphAnShape shape = {}; std::vector<int32_t> iters; std::string name; } an;
   // sampled genealogies of selected loci (gph_genetrees.h): the rows of records, the selected loci of this rank (global indices,
   // increasing) with their slots in HBM, and the iterations of the rows held
-  struct { SmRows rows; GphGtShape shape = {}; int32_t *d_sel = nullptr; std::vector<int64_t> sel; std::vector<int32_t> iters; } gt;
+  struct { SmRows rows; GphGtShape shape = {}; SmSel sel; std::vector<int32_t> iters; } gt;
   // clade tables of selected loci (gph_clades.h): entries [nsel][P][W + 2] and header words [nsel][2] in selection order, the
   // selected loci of this rank with their slots in HBM, samples since the tables were last zeroed
-  struct { uint64_t *d_ent = nullptr; uint32_t *d_hdr = nullptr; int32_t *d_sel = nullptr; GphClShape shape = {}; std::vector<int64_t> sel;
+  struct { uint64_t *d_ent = nullptr; uint32_t *d_hdr = nullptr; GphClShape shape = {}; SmSel sel;
            int64_t samples = 0; bool on = false; } cl;
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
@@ -917,8 +915,8 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->dev.ra_draws); dev_free(e->dev.ra_ckpt); dev_free(e->dev.ra_tail); dev_free(e->dev.ra_kprev);
   dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
-  dev_free(e->gt.rows.d); dev_free(e->gt.d_sel);
-  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_sel);
+  dev_free(e->gt.rows.d); dev_free(e->gt.sel.d_slot);
+  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.sel.d_slot);
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
   dev_free(e->d_red);
@@ -1375,7 +1373,7 @@ static int apply_list(gph_engine *e)
   if ((rc = owed_finishes(e))) return rc;
   if ((rc = flush_pending(e))) return rc;
   launch_pre(e);
-  if ((rc = launch_grid(e, GphGrid{(int)((e->L + 255) / 256), 1}, 256, 0, k_apply_list, e->ka, e->dev))) return rc;
+  if ((rc = launch_grid(e, GphGrid{(int)((e->L + GPH_FLAT_THREADS - 1) / GPH_FLAT_THREADS), 1}, GPH_FLAT_THREADS, 0, k_apply_list, e->ka, e->dev))) return rc;
   flat_launched(e, -1, 1);
   return 0;
 }
@@ -2283,6 +2281,40 @@ static int chunked_alloc(gph_engine *e, SmParts &p, SmRows &b, int32_t rd, int32
   if (rows_alloc(b, sizeof(double), rd, capacity)) { parts_free(p); return GPH_EHIP; }
   return 0;
 }
+// a caller's selection of loci: nothing (null: every locus) or global indices, strictly increasing
+static bool sel_valid(const int64_t *loci, int64_t nloci)
+{
+  if (loci && nloci < 0) return false;
+  if (loci)
+    for (int64_t k = 0; k < nloci; k++)
+      if (loci[k] < 0 || (k > 0 && loci[k] <= loci[k - 1])) return false;
+  return true;
+}
+static void sel_free(SmSel &s) { dev_free(s.d_slot); s = SmSel{}; }
+// the loci of the selection that this rank holds, and their slots in HBM: slots are sorted by decreasing pattern count, h_orig[j]
+// is the local locus slot j holds
+static int sel_alloc(gph_engine *e, SmSel &s, const int64_t *loci, int64_t nloci)
+{
+  const int64_t L = e->L, lb = e->cfg.locus_begin;
+  if (!loci) for (int64_t g = 0; g < L; g++) s.loci.push_back(lb + g);
+  else for (int64_t k = 0; k < nloci; k++) if (loci[k] >= lb && loci[k] < lb + L) s.loci.push_back(loci[k]);
+  std::vector<int32_t> slot_of((size_t)L), slot(s.loci.size());
+  for (int64_t j = 0; j < L; j++) slot_of[(size_t)e->h_orig[j]] = (int32_t)j;
+  for (size_t q = 0; q < slot.size(); q++) slot[q] = slot_of[(size_t)(s.loci[q] - lb)];
+  int rc = dev_alloc((void **)&s.d_slot, sizeof(int32_t) * slot.size());
+  if (rc) s.d_slot = nullptr;
+  else if (!slot.empty()) rc = h2d(e, s.d_slot, slot.data(), sizeof(int32_t) * slot.size());
+  if (rc) sel_free(s);
+  return rc;
+}
+// the selected loci of this rank into out (count alone with out == null)
+static int sel_copy_out(const SmSel &s, int64_t *out, int64_t max_loci, int64_t *count)
+{
+  *count = (int64_t)s.loci.size();
+  if (max_loci < *count) return out ? GPH_EARG : 0;
+  for (size_t q = 0; q < s.loci.size(); q++) out[q] = s.loci[q];
+  return 0;
+}
 // per-locus accumulators [L][ncol] in slot order -> out, row h_orig[j] (the local locus slot j holds) of leading dimension ld
 static int fetch_by_locus(gph_engine *e, const double *d_acc, int ncol, bool column_major, double *out, int64_t ld)
 {
@@ -2646,44 +2678,27 @@ static_assert((int)GT_O_COUNT == (int)GPH_GT_O_COUNT && (int)GT_O_LIVING == (int
 int gph_engine_gene_trees_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int64_t max_bytes)
 {
   if (!e || !e->loaded) return GPH_ESTATE;
-  if (capacity_rows < 0 || (loci && nloci < 0)) return GPH_EARG;
-  if (loci)
-    for (int64_t k = 0; k < nloci; k++)
-      if (loci[k] < 0 || (k > 0 && loci[k] <= loci[k - 1])) return GPH_EARG;
+  if (capacity_rows < 0 || !sel_valid(loci, nloci)) return GPH_EARG;
   SETDEV(e);
   rows_free(e->gt.rows);
-  dev_free(e->gt.d_sel);
-  e->gt.d_sel = nullptr;
-  e->gt.sel.clear();
+  sel_free(e->gt.sel);
   e->gt.iters.clear();
   e->gt.shape = GphGtShape{};
   if (capacity_rows == 0) return 0;
-  const int64_t L = e->L, lb = e->cfg.locus_begin;
-  std::vector<int64_t> sel;
-  if (!loci) for (int64_t g = 0; g < L; g++) sel.push_back(lb + g);
-  else for (int64_t k = 0; k < nloci; k++) if (loci[k] >= lb && loci[k] < lb + L) sel.push_back(loci[k]);
+  { int rcs = sel_alloc(e, e->gt.sel, loci, nloci); if (rcs) return rcs; }
+  const int64_t nsel = (int64_t)e->gt.sel.loci.size();
   GphGtShape h;
   gph_gt_shape(e->lay, h);
   const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)256 << 20;
-  const int64_t need = (int64_t)capacity_rows * (int64_t)sel.size() * h.img.bytes;
+  const int64_t need = (int64_t)capacity_rows * nsel * h.img.bytes;
   if (need > limit) {
     fprintf(stderr, "gphocs_hip: gene trees: the row buffer needs %lld bytes (%d rows x %lld loci x %d bytes a record), the limit is %lld\n",
-            (long long)need, (int)capacity_rows, (long long)sel.size(), (int)h.img.bytes, (long long)limit);
+            (long long)need, (int)capacity_rows, (long long)nsel, (int)h.img.bytes, (long long)limit);
+    sel_free(e->gt.sel);
     return GPH_EFULL;
   }
-  /* selected -> slot: slots are sorted by decreasing pattern count, h_orig[j] is the local locus slot j holds */
-  std::vector<int32_t> slot_of((size_t)L), sel_slot(sel.size());
-  for (int64_t j = 0; j < L; j++) slot_of[(size_t)e->h_orig[j]] = (int32_t)j;
-  for (size_t q = 0; q < sel.size(); q++) sel_slot[q] = slot_of[(size_t)(sel[q] - lb)];
-  if (dev_alloc((void **)&e->gt.d_sel, sizeof(int32_t) * sel_slot.size())) { e->gt.d_sel = nullptr; return GPH_EHIP; }
-  if (!sel_slot.empty()) { int rc = h2d(e, e->gt.d_sel, sel_slot.data(), sizeof(int32_t) * sel_slot.size()); if (rc) return rc; }
-  if (rows_alloc(e->gt.rows, (size_t)h.img.bytes, (int32_t)sel.size(), capacity_rows)) {
-    dev_free(e->gt.d_sel);
-    e->gt.d_sel = nullptr;
-    return GPH_EHIP;
-  }
+  if (rows_alloc(e->gt.rows, (size_t)h.img.bytes, (int32_t)nsel, capacity_rows)) { sel_free(e->gt.sel); return GPH_EHIP; }
   e->gt.shape = h;
-  e->gt.sel.swap(sel);
   return 0;
 }
 
@@ -2701,7 +2716,7 @@ int gph_engine_gene_trees_sample(gph_engine *e, int32_t iteration)
     char *row = (char *)rows_next(e->gt.rows);
     int tms;
     { int rcb = sample_begin(e, 17, tms); if (rcb) return rcb; }
-    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_GT_THREADS, 0, k_gene_trees, e->lay, h, e->dev.pages, e->gt.d_sel, nsel, L, row);
+    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_GT_THREADS, 0, k_gene_trees, e->lay, h, e->dev.pages, e->gt.sel.d_slot, nsel, L, row);
       if (rcl) return rcl; }
     sample_end(e, 17, 1, tms);
   }
@@ -2714,7 +2729,7 @@ int gph_engine_gene_trees_shape(gph_engine *e, int64_t *selected, int32_t *nodes
 {
   if (!e) return GPH_EARG;
   const bool on = e->gt.rows.d != nullptr;
-  if (selected) *selected = on ? (int64_t)e->gt.sel.size() : 0;
+  if (selected) *selected = on ? (int64_t)e->gt.sel.loci.size() : 0;
   if (nodes) *nodes = on ? e->lay.N : 0;
   if (record_bytes) *record_bytes = on ? e->gt.shape.img.bytes : 0;
   if (offsets) for (int k = 0; k < GT_O_COUNT; k++) offsets[k] = on ? e->gt.shape.off[k] : 0;
@@ -2726,10 +2741,7 @@ int gph_engine_gene_trees_selected(gph_engine *e, int64_t *out, int64_t max_loci
 {
   if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
   if (!e->gt.rows.d) return GPH_ESTATE;
-  *count = (int64_t)e->gt.sel.size();
-  if (max_loci < *count) return out ? GPH_EARG : 0;
-  for (size_t q = 0; q < e->gt.sel.size(); q++) out[q] = e->gt.sel[q];
-  return 0;
+  return sel_copy_out(e->gt.sel, out, max_loci, count);
 }
 
 int gph_engine_gene_trees_fetch(gph_engine *e, int32_t *iters, void *out, int32_t max_rows, int32_t *rows)
@@ -2747,19 +2759,19 @@ int gph_engine_gene_trees_fetch(gph_engine *e, int32_t *iters, void *out, int32_
 }
 
 // ---- clade tables of selected loci (gph_clades.h)
-static size_t clades_entry_bytes(const gph_engine *e) { return sizeof(uint64_t) * e->cl.sel.size() * (size_t)e->cl.shape.P * e->cl.shape.ew; }
+static size_t clades_entry_bytes(const gph_engine *e) { return sizeof(uint64_t) * e->cl.sel.loci.size() * (size_t)e->cl.shape.P * e->cl.shape.ew; }
 static int clades_zero(gph_engine *e)
 {
   if (!e->cl.on) return 0;
   e->cl.samples = 0;
   { int rcz = acc_zero(e, e->cl.d_ent, clades_entry_bytes(e)); if (rcz) return rcz; }
-  return acc_zero(e, e->cl.d_hdr, sizeof(uint32_t) * 2 * e->cl.sel.size());
+  return acc_zero(e, e->cl.d_hdr, sizeof(uint32_t) * 2 * e->cl.sel.loci.size());
 }
 static void clades_free(gph_engine *e)
 {
-  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_sel);
-  e->cl.d_ent = nullptr; e->cl.d_hdr = nullptr; e->cl.d_sel = nullptr;
-  e->cl.sel.clear();
+  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr);
+  e->cl.d_ent = nullptr; e->cl.d_hdr = nullptr;
+  sel_free(e->cl.sel);
   e->cl.shape = GphClShape{};
   e->cl.samples = 0;
   e->cl.on = false;
@@ -2769,39 +2781,28 @@ int gph_engine_clades_enable(gph_engine *e, int32_t slots, const int64_t *loci, 
 {
   if (!e || !e->loaded) return GPH_ESTATE;
   if (slots != 0 && (slots < 2 || (slots & (slots - 1)) != 0)) return GPH_EARG;
-  if (loci && nloci < 0) return GPH_EARG;
-  if (loci)
-    for (int64_t k = 0; k < nloci; k++)
-      if (loci[k] < 0 || (k > 0 && loci[k] <= loci[k - 1])) return GPH_EARG;
+  if (!sel_valid(loci, nloci)) return GPH_EARG;
   SETDEV(e);
   clades_free(e);
-  const int64_t L = e->L, lb = e->cfg.locus_begin;
-  std::vector<int64_t> sel;
-  if (!loci) for (int64_t g = 0; g < L; g++) sel.push_back(lb + g);
-  else for (int64_t k = 0; k < nloci; k++) if (loci[k] >= lb && loci[k] < lb + L) sel.push_back(loci[k]);
+  { int rcs = sel_alloc(e, e->cl.sel, loci, nloci); if (rcs) return rcs; }
+  const size_t nsel = e->cl.sel.loci.size();
   GphClShape h;
   gph_cl_shape(e->lay, slots ? slots : gph_cl_default_slots(e->cfg.n), h);
   const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
-  const int64_t per = (int64_t)h.P * h.ew * 8 + 8, need = (int64_t)sel.size() * per;
+  const int64_t per = (int64_t)h.P * h.ew * 8 + 8, need = (int64_t)nsel * per;
   if (need > limit) {
     fprintf(stderr, "gphocs_hip: clades: the tables need %lld bytes (%lld loci x (%d slots x %d words x 8 + 8)), the limit is %lld\n",
-            (long long)need, (long long)sel.size(), (int)h.P, (int)h.ew, (long long)limit);
+            (long long)need, (long long)nsel, (int)h.P, (int)h.ew, (long long)limit);
+    clades_free(e);
     return GPH_EFULL;
   }
-  /* selected -> slot, as for the gene trees */
-  std::vector<int32_t> slot_of((size_t)L), sel_slot(sel.size());
-  for (int64_t j = 0; j < L; j++) slot_of[(size_t)e->h_orig[j]] = (int32_t)j;
-  for (size_t q = 0; q < sel.size(); q++) sel_slot[q] = slot_of[(size_t)(sel[q] - lb)];
-  if (dev_alloc((void **)&e->cl.d_sel, sizeof(int32_t) * sel_slot.size()) ||
-      dev_alloc((void **)&e->cl.d_ent, sizeof(uint64_t) * sel.size() * (size_t)h.P * h.ew) ||
-      dev_alloc((void **)&e->cl.d_hdr, sizeof(uint32_t) * 2 * sel.size())) {
+  if (dev_alloc((void **)&e->cl.d_ent, sizeof(uint64_t) * nsel * (size_t)h.P * h.ew) ||
+      dev_alloc((void **)&e->cl.d_hdr, sizeof(uint32_t) * 2 * nsel)) {
     dev_clear_error();
     clades_free(e);
     return GPH_EHIP;
   }
-  if (!sel_slot.empty()) { int rc = h2d(e, e->cl.d_sel, sel_slot.data(), sizeof(int32_t) * sel_slot.size()); if (rc) { clades_free(e); return rc; } }
   e->cl.shape = h;
-  e->cl.sel.swap(sel);
   e->cl.on = true;
   return clades_zero(e);
 }
@@ -2813,12 +2814,12 @@ int gph_engine_clades_sample(gph_engine *e)
   SETDEV(e);
   { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
   const GphClShape &h = e->cl.shape;
-  const int nsel = (int)e->cl.sel.size(), L = (int)e->L;
+  const int nsel = (int)e->cl.sel.loci.size(), L = (int)e->L;
   const int groups = (nsel + h.G - 1) / h.G;
   if (groups > 0 && e->cfg.n > 1) {        /* (a rank without a selected locus launches nothing; one leaf has no clade) */
     int tms;
     { int rcb = sample_begin(e, 19, tms); if (rcb) return rcb; }
-    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_CL_THREADS, (size_t)h.lds_bytes, k_clades, e->lay, h, e->dev.pages, e->cl.d_sel, nsel, L,
+    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_CL_THREADS, (size_t)h.lds_bytes, k_clades, e->lay, h, e->dev.pages, e->cl.sel.d_slot, nsel, L,
                             e->cl.d_ent, e->cl.d_hdr);
       if (rcl) return rcl; }
     sample_end(e, 19, 1, tms);
@@ -2831,7 +2832,7 @@ int gph_engine_clades_shape(gph_engine *e, int64_t *selected, int32_t *slots, in
 {
   if (!e) return GPH_EARG;
   const bool on = e->cl.on;
-  if (selected) *selected = on ? (int64_t)e->cl.sel.size() : 0;
+  if (selected) *selected = on ? (int64_t)e->cl.sel.loci.size() : 0;
   if (slots) *slots = on ? e->cl.shape.P : 0;
   if (words) *words = on ? e->cl.shape.W : 0;
   if (limit) *limit = on ? e->cl.shape.limit : 0;
@@ -2843,17 +2844,14 @@ int gph_engine_clades_selected(gph_engine *e, int64_t *out, int64_t max_loci, in
 {
   if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
   if (!e->cl.on) return GPH_ESTATE;
-  *count = (int64_t)e->cl.sel.size();
-  if (max_loci < *count) return out ? GPH_EARG : 0;
-  for (size_t q = 0; q < e->cl.sel.size(); q++) out[q] = e->cl.sel[q];
-  return 0;
+  return sel_copy_out(e->cl.sel, out, max_loci, count);
 }
 
 int gph_engine_clades_fetch(gph_engine *e, uint64_t *entries, uint32_t *nkeys, uint32_t *dropped, int32_t reset)
 {
   if (!e) return GPH_EARG;
   if (!e->cl.on) return GPH_ESTATE;
-  const size_t nsel = e->cl.sel.size();
+  const size_t nsel = e->cl.sel.loci.size();
   if (nsel > 0 && (!entries || !nkeys || !dropped)) return GPH_EARG;
   SETDEV(e);
   if (nsel > 0) {

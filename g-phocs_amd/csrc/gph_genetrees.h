@@ -23,7 +23,8 @@
 // 64-bit division a lane, which costs as much as the copy).  No LDS, no atomics; nothing grows with the band capacity.  16 N + 288 bytes a record (up to 16 more where a
 // range straddles a boundary): 0.8 KB at 16 leaves, 2.6 KB at 72.
 //
-// The kernel writes no page, draws no random number and touches no chain state.
+// The kernel has one text (the flat-kernel form, gph_sampler.h): the host-emulation build runs it lane by lane, phase by phase.
+// It writes no page, draws no random number and touches no chain state.
 #pragma once
 #include "gph_sampler.h"
 
@@ -75,30 +76,17 @@ GPH_SM_FN bool gph_gt_unit(const GphLayout &y, const GphGtShape &h, const int32_
   return true;
 }
 
-#ifdef GPH_HOSTEMU
-// host emulation: workgroup w with its lanes one after the other
-static inline void k_gene_trees(GphBlk blk, GphLayout y, GphGtShape h, const char *pages, const int32_t *sel_slot, int nsel, int L, char *row)
+// workgroup w = block bx
+GPH_FLAT(k_gene_trees, GPH_GT_THREADS, GphLayout y, GphGtShape h, const char *pages, const int32_t *sel_slot, int nsel, int L, char *row)
 {
-  const int w = blk.x;
-  for (int tid = 0; tid < GPH_GT_THREADS; tid++)
+  GPH_FLAT_BODY(GphNoLane);
+  GPH_PHASE {
     for (int t = tid; t < h.G * h.units; t += GPH_GT_THREADS) {
       size_t src, dst;
-      if (gph_gt_unit(y, h, sel_slot, nsel, L, w, t, src, dst)) memcpy(row + dst, pages + src, 16);
-    }
-}
-#else
-__global__ void __launch_bounds__(GPH_GT_THREADS) k_gene_trees(GphLayout y, GphGtShape h, const char *pages, const int32_t *sel_slot, int nsel, int L,
-                                                               char *row)
-{
-  for (int t = threadIdx.x; t < h.G * h.units; t += GPH_GT_THREADS) {
-    size_t src, dst;
-    if (gph_gt_unit(y, h, sel_slot, nsel, L, (int)blockIdx.x, t, src, dst)) {
-      const uint4 val = *(const uint4 *)(pages + src);
-      *(uint4 *)(row + dst) = val;
+      if (gph_gt_unit(y, h, sel_slot, nsel, L, bx, t, src, dst)) gph_copy16(row + dst, pages + src);
     }
   }
 }
-#endif
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 2

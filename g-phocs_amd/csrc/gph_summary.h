@@ -1,8 +1,8 @@
 // gph_summary.h -- k_locus_summary: per-locus posterior summaries accumulated on the device (include/gphocs_hip.h,
 // gph_engine_locus_summary_*).  One lane per locus slot reads a few dozen bytes of its page (the values
 // gph_engine_dump_loci prints) and updates fp64 accumulators in HBM.  The accumulators are column-major, [ncol][L] in
-// slot order, so that every column's reads and writes coalesce across the lanes.  The kernel writes no page, draws no
-// random number and touches no chain state.
+// slot order, so that every column's reads and writes coalesce across the lanes.  The kernel has one text (the flat-kernel
+// form, gph_sampler.h); it writes no page, draws no random number and touches no chain state.
 //
 // Columns: 0-2 dataLnL, 3-5 genLnL, 6-8 TMRCA (shift, s1, s2 each), then per band the summed migration count and the
 // number of samples with a migration (nmig.b at 9 + b, pmig.b at 9 + B + b), per population the summed coalescence count
@@ -10,23 +10,18 @@
 // sample; a later sample x adds d = x - shift to s1 and d * d to s2, in sample order, with plain (uncontracted) fp64
 // operations: the sums can be rebuilt bit for bit from state dumps.
 #pragma once
-#include "gph_kernels.h"
+#include "gph_sampler.h"
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 3
 
 enum { LS_DATALNL = 0, LS_GENLNL = 3, LS_TMRCA = 6, LS_FIXED = 9 };
 
-static inline int gph_ls_columns(int K, int B, int var) { return LS_FIXED + 2 * B + K + (var ? 3 : 0); }
+GPH_SM_HD int gph_ls_columns(int K, int B, int var) { return LS_FIXED + 2 * B + K + (var ? 3 : 0); }
 
 // one locus: pg = its page, a = its first accumulator (column c at a[c * L]); first = the first sample since the
 // accumulators were zeroed
-#ifdef GPH_HOSTEMU
-static inline
-#else
-__device__ inline
-#endif
-void locus_summary_slot(const char *pg, const GphLayout &y, double *a, size_t L, int ncol, int first, int var)
+GPH_SM_FN void locus_summary_slot(const char *pg, const GphLayout &y, double *a, size_t L, int ncol, int first, int var)
 {
   const double *fs = (const double *)(pg + y.o_fscal);
   const int32_t *is = (const int32_t *)(pg + y.o_iscal);
@@ -59,20 +54,15 @@ void locus_summary_slot(const char *pg, const GphLayout &y, double *a, size_t L,
 }
 
 #define GPH_LS_THREADS 256
-#ifndef GPH_HOSTEMU
-__global__ void __launch_bounds__(GPH_LS_THREADS) k_locus_summary(GphLayout y, const char *pages, double *acc, int L, int ncol, int first, int var)
+// one lane per locus slot
+GPH_FLAT(k_locus_summary, GPH_LS_THREADS, GphLayout y, const char *pages, double *acc, int L, int ncol, int first, int var)
 {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= L) return;
-  locus_summary_slot(pages + (size_t)j * y.page_bytes, y, acc + j, (size_t)L, ncol, first, var);
+  GPH_FLAT_BODY(GphNoLane);
+  GPH_PHASE {
+    const int j = bx * bd + tid;
+    if (j < L) locus_summary_slot(pages + (size_t)j * y.page_bytes, y, acc + j, (size_t)L, ncol, first, var);
+  }
 }
-#else
-static inline void k_locus_summary(GphBlk blk, GphLayout y, const char *pages, double *acc, int L, int ncol, int first, int var)
-{
-  for (int j = blk.x * blk.dim; j < (blk.x + 1) * blk.dim && j < L; j++)
-    locus_summary_slot(pages + (size_t)j * y.page_bytes, y, acc + j, (size_t)L, ncol, first, var);
-}
-#endif
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 2

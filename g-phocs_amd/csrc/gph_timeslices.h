@@ -46,6 +46,7 @@
 // partial row; k_rows_fold, one lane per column, adds the partial rows in chunk order.  No atomics, nothing
 // depends on how workgroups are scheduled.  Counts are integers held as doubles.
 //
+// Each kernel has one text (the flat-kernel form, gph_sampler.h): the host-emulation build runs it lane by lane, phase by phase.
 // The kernels write no page, draw no random number and touch no chain state.
 #pragma once
 #include "gph_sampler.h"
@@ -102,7 +103,7 @@ GPH_SM_HD int gph_ts_shape(const GphLayout &y, int S, GphTsShape &h)
   return 0;
 }
 
-// the LDS of a workgroup (the host form keeps the same arrays in a vector)
+// the LDS of a workgroup
 struct GphTsLds {
   char *img;                 // [G][img.bytes]
   double *popAge, *sampleAge, *bandStart, *bandEnd;   // [K] [K] [B] [B]
@@ -229,63 +230,49 @@ GPH_SM_FN void gph_ts_chunk_out(const GphTsLds &s, const GphLayout &y, const Gph
   out[col + 1] = d;
 }
 
-#ifdef GPH_HOSTEMU
-// host emulation: workgroup (ch, tile) = block (x, y) with its lanes one after the other, phase by phase as the barriers
-// order them; the launch hands it a zeroed buffer for its dynamic LDS
-static inline void k_time_slices(GphBlk blk, GphLayout y, GphTsShape h, const GphGlobal *G, const char *pages, double *part, int L, int chunk,
-                                 int rd, int vsync)
+// what a lane keeps across the barriers: which locus of a group and which walker it is
+struct GphTsLane {
+  int g = 0, Wk = 0;
+  bool walker = false;
+};
+
+// workgroup (ch, tile) = block (bx, by)
+GPH_FLAT(k_time_slices, GPH_TS_MAXTHREADS, GphLayout y, GphTsShape h, const GphGlobal *G, const char *pages, double *part, int L, int chunk,
+         int rd, int vsync)
 {
-  const int K = y.K, B = y.B, W = K + B, ch = blk.x, tile = blk.y;
+  GPH_FLAT_BODY(GphTsLane);
+  const int K = y.K, B = y.B, W = K + B, ch = bx, tile = by;
   GphTsLds s;
-  gph_ts_carve(blk.lds, K, B, h, s);
-  for (int q = 0; q < 3 * K + 3 * B; q++) gph_ts_load_model(s, G->model, K, B, q);
+  gph_ts_carve(lds, K, B, h, s);
   const int j0 = ch * chunk, j1 = j0 + chunk < L ? j0 + chunk : L, upl = h.img.bytes / 16;
+  GPH_PHASE {
+    for (int q = tid; q < h.S * bd; q += bd) { s.accD[q] = 0.0; s.accC[q] = 0u; }
+    for (int q = tid; q < 3 * K + 3 * B; q += bd) gph_ts_load_model(s, G->model, K, B, q);
+    ln.g = tid / h.wt; ln.Wk = tile * h.wt + (tid - ln.g * h.wt);
+    ln.walker = ln.g < h.G && ln.Wk < W;
+  }
   for (int jg = j0; jg < j1; jg += h.G) {
     const int nl = j1 - jg < h.G ? j1 - jg : h.G;
-    for (int u = 0; u < nl * upl; u++) {
-      const int loc = u / upl, o = (u - loc * upl) * 16;
-      memcpy(s.img + (size_t)loc * h.img.bytes + o, pages + (size_t)(jg + loc) * y.page_bytes + gph_pack_unit_src(h.img, o), 16);
+    GPH_BARRIER;        /* everybody is done with the previous group's images (first pass: with zeroing and the tables) */
+    GPH_PHASE {
+      for (int u = tid; u < nl * upl; u += bd) {
+        const int loc = u / upl, o = (u - loc * upl) * 16;
+        gph_copy16(s.img + (size_t)GPH_IX(loc, h.G) * h.img.bytes + GPH_IX(o, h.img.bytes),
+                   pages + (size_t)(jg + loc) * y.page_bytes + gph_pack_unit_src(h.img, o));
+      }
     }
-    for (int lane = 0; lane < h.G * h.wt; lane++) {
-      const int g = lane / h.wt, Wk = tile * h.wt + (lane - g * h.wt);
-      if (g < nl && Wk < W) gph_ts_walk(s, y, h, lane, g, Wk, vsync);
+    GPH_BARRIER;
+    GPH_PHASE {
+      if (ln.walker && ln.g < nl) gph_ts_walk(s, y, h, tid, ln.g, ln.Wk, vsync);
     }
   }
+  GPH_BARRIER;
   double *out = part + (size_t)ch * rd;
-  for (int q = 0; q < h.wt * h.S; q++) gph_ts_chunk_out(s, y, h, tile, q, out);
-  if (tile == 0) out[0] = 0.0;
-}
-#else
-__global__ void __launch_bounds__(GPH_TS_MAXTHREADS) k_time_slices(GphLayout y, GphTsShape h, const GphGlobal *G, const char *pages, double *part, int L,
-                                                                   int chunk, int rd, int vsync)
-{
-  extern __shared__ __attribute__((aligned(16))) char ts_lds[];
-  const int K = y.K, B = y.B, W = K + B;
-  const int tid = threadIdx.x, bd = blockDim.x, ch = blockIdx.x, tile = blockIdx.y;
-  GphTsLds s;
-  gph_ts_carve(ts_lds, K, B, h, s);
-  for (int q = tid; q < h.S * bd; q += bd) { s.accD[q] = 0.0; s.accC[q] = 0u; }
-  for (int q = tid; q < 3 * K + 3 * B; q += bd) gph_ts_load_model(s, G->model, K, B, q);
-  const int j0 = ch * chunk, j1 = j0 + chunk < L ? j0 + chunk : L, upl = h.img.bytes / 16;
-  const int g = tid / h.wt, Wk = tile * h.wt + (tid - g * h.wt);
-  const bool walker = g < h.G && Wk < W;
-  for (int jg = j0; jg < j1; jg += h.G) {
-    const int nl = j1 - jg < h.G ? j1 - jg : h.G;
-    __syncthreads();        /* everybody is done with the previous group's images (first pass: with zeroing and the tables) */
-    for (int u = tid; u < nl * upl; u += bd) {
-      const int loc = u / upl, o = (u - loc * upl) * 16;
-      const uint4 v = *(const uint4 *)(pages + (size_t)(jg + loc) * y.page_bytes + gph_pack_unit_src(h.img, o));
-      *(uint4 *)(s.img + (size_t)GPH_IX(loc, h.G) * h.img.bytes + GPH_IX(o, h.img.bytes)) = v;
-    }
-    __syncthreads();
-    if (walker && g < nl) gph_ts_walk(s, y, h, tid, g, Wk, vsync);
+  GPH_PHASE {
+    for (int q = tid; q < h.wt * h.S; q += bd) gph_ts_chunk_out(s, y, h, tile, q, out);
+    if (tile == 0 && tid == 0) out[0] = 0.0;
   }
-  __syncthreads();
-  double *out = part + (size_t)ch * rd;
-  for (int q = tid; q < h.wt * h.S; q += bd) gph_ts_chunk_out(s, y, h, tile, q, out);
-  if (tile == 0 && tid == 0) out[0] = 0.0;
 }
-#endif
 
 #undef GPH_FILE_ID
 #define GPH_FILE_ID 2

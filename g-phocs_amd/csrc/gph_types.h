@@ -352,6 +352,6 @@ struct alignas(16) GphGlobal {
   GphTauFin fin;                     // the decided proposal whose commit / revert has not run yet
 };
 
-// host emulation (gph_backend.h): what the host form of a flat kernel takes first, in place of blockIdx, blockDim and its
+// host emulation (gph_backend.h): what a flat kernel (GPH_FLAT, gph_sampler.h) takes first on the host, in place of blockIdx, blockDim and its
 // dynamic LDS -- the block's coordinates in the grid, its threads, a zeroed scratch buffer
 struct GphBlk { int x, y, dim; char *lds; };

@@ -32,6 +32,9 @@ CONFIGS = {  # diploid samples per current pop, migration bands (src, tgt), anci
              [(i + 2, i) for i in range(4)] + [(0, 3), (3, 0)]),
     13: dict(pops=[6] * 6, bands=[(0, 1), (1, 0), (3, 2), (4, 3)]),
     14: dict(pops=[66, 2], bands=[(0, 1)]),
+    # the reference's own caps on populations and bands (NSPECIES 20: 39 populations; MAX_MIG_BANDS 100), 40 leaves: 139 walkers
+    # of the time-slice sampler (csrc/gph_timeslices.h), more than one workgroup holds
+    15: dict(pops=[1] * 20, bands=[(i, j) for i in range(20) for j in range(20) if i != j][:100]),
 }
 
 

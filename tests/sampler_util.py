@@ -25,6 +25,23 @@ def hostemu_library():
     return path, G.load_library(path)
 
 
+# launch shapes no golden has: a few loci from the benchmark's generator (g-phocs_amd/synth.py), the same data every time.
+# name: (configuration there, loci)
+SYNTHETIC = {"t136": (14, 2),       # 136 leaves: a gene-tree record of 290 units, one clade table a workgroup (three key words)
+             "w139": (15, 2),       # 39 populations + 100 bands: the walkers of the time slices in more than one tile
+             "a70": (1, 70)}        # 8 leaves, 70 loci: three groups of 32 loci in k_ancestry, migrations in few of them
+
+
+def load_pack(name):
+    """the pack of a case: golden `name`, or the synthetic data set of that name (SYNTHETIC)"""
+    import gphocs_amd as G
+    if name in SYNTHETIC:
+        from gphocs_amd_pkg import synth
+        config, loci = SYNTHETIC[name]
+        return synth.make_synthetic_pack(G.Pack, config, loci, seqlen=200, samples_per_log=8)
+    return G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
+
+
 def _fmt(x):
     return "%.10g" % x
 

@@ -20,7 +20,7 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_records, compare_trace_files
-from sampler_util import (EXE, _copy_case, _data_lines, _fmt, _locus_names, _pop_names, _run, hostemu_library, printed_names,  # noqa: F401
+from sampler_util import (EXE, _copy_case, _data_lines, _fmt, _locus_names, _pop_names, _run, hostemu_library, load_pack, printed_names,  # noqa: F401
                           read_outputs, run_ranks)
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
@@ -133,7 +133,7 @@ def run_chain(lib, name, iters, tmp, sample=True, dumps=False, record=None, capa
     accumulators, the per-sample rows with their iterations, the final state dump, the per-iteration dumps, the pack,
     host_stats() after initialize and at the end, debug_oob()"""
     import gphocs_amd as G
-    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
+    pk = load_pack(name)
     s = G.Sampler(pk, lib=lib)
     try:
         if record:
@@ -235,6 +235,20 @@ def test_the_case_set_reaches_every_path(hostemu, hostemu_big, tmp_path):
         if ("cpu", name) not in _SEEN:        # (run alone: the dumps of the cases not checked yet in this process)
             check_against_dumps(hostemu_big if name in BIG else hostemu[1], name, CASES[name], tmp_path)
     check_case_set("cpu", list(CASES))
+
+
+def test_a_group_without_migrations_next_to_one_with(hostemu, tmp_path):
+    """a70: 70 loci of 8 leaves are three workgroups of 32 slots (the last one cut by L), and live migrations are rare: a sample
+    with fewer loci that hold one than there are workgroups has a workgroup that returns at the vote next to one that stays"""
+    name, iters = "a70", 40
+    r = check_against_dumps(hostemu[1], name, iters, tmp_path, key="edge")
+    pk = r["pack"]
+    per_group = 256 // pk.n
+    groups = (pk.L + per_group - 1) // per_group
+    assert groups >= 2 and pk.L % per_group
+    with_migs = [sum(1 for d in parse_dump(p, pk.K, pk.B).values() if d["migs"]) for p in r["dumps"]]
+    assert any(0 < k < groups for k in with_migs), with_migs
+    assert r["oob"][0] == 0
 
 
 # ---------------------------------------------------------------- capacity and lifecycle

@@ -31,7 +31,7 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_records
-from sampler_util import EXE, _copy_case, _fmt, _locus_names, _run, hostemu_library, printed_names, read_outputs, run_ranks
+from sampler_util import EXE, _copy_case, _fmt, _locus_names, _run, hostemu_library, load_pack, printed_names, read_outputs, run_ranks
 from test_ancestry import BIG, CASES, GOLDEN_ITERS
 from test_gene_trees import PROGRAM_CASE, PROGRAM_LOCI, PROGRAM_SPEC, program_ctl
 
@@ -126,7 +126,7 @@ def run_chain(lib, name, iters, slots=0, loci=None, sample=True, record=None, tr
     clades after every iteration: the tables, the decoded gene trees, the final state dump, host_stats() after initialize
     and at the end, the launches of timing class 19, debug_oob()"""
     import gphocs_amd as G
-    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
+    pk = load_pack(name)
     s = G.Sampler(pk, lib=lib)
     try:
         if record:
@@ -207,6 +207,17 @@ def check_case(lib, name, iters, key="cpu"):
 @pytest.mark.parametrize("name", list(CASES))
 def test_tables_equal_the_model_over_the_gene_tree_records(hostemu, hostemu_big, name):
     check_case(hostemu_big if name in BIG else hostemu[1], name, CASES[name])
+
+
+def test_one_record_a_workgroup(hostemu_big):
+    """t136: 136 leaves -- G = 1, every lane of a workgroup on the one locus, keys of three words"""
+    iters = 4
+    r = run_chain(hostemu_big, "t136", iters)
+    c, n = r["clades"], r["pack"].n
+    assert 256 // n == 1 and c["words"] == 3 and c["samples"] == iters and r["launches"] == iters
+    model = check_tables(c, r["trees"], n, "t136")
+    assert all(m["dropped"] == 0 for m in model) and any(k >> 128 and k & ((1 << 64) - 1) for m in model for k in m["tab"])
+    assert r["oob"][0] == 0
 
 
 # ---------------------------------------------------------------- group edges

@@ -19,9 +19,10 @@ Which golden runs which path: m3, a7, j1, v8, g1 fit one tile of pairs (66 pairs
 lanes); x8 (32 leaves, 31 populations: 496 pairs, 64 lanes a workgroup) runs the tiled path with 8 tiles, and n7 (72
 leaves: 2556 pairs in 10 tiles of 256) runs it on the device (tests/test_coal_stats_gpu.py).  With chunks of 5 slots
 (gph_engine_coal_stats_set_chunk) the 16 loci of m3 make four chunks, so the fold adds several partial rows.
-NOT reached by any golden: a workgroup with fewer lanes than genealogy nodes (64 lanes, which takes 25 populations or
-more, with 33 leaves or more: N = 2n - 1 > 64) -- there the node records beyond the first 64 are staged by a strided loop
-straight from the page and a lane ranks several internal nodes.  x8 has N = 63 in 64 lanes, n7 N = 143 in 256."""
+A workgroup with fewer lanes than genealogy nodes (64 lanes, which takes 25 populations or more, with 33 leaves or more:
+N = 2n - 1 > 64) stages the node records beyond the first 64 by a strided loop straight from the page, and a lane ranks
+several internal nodes: y9 (40 leaves, 39 populations: N = 79 in 64 lanes, 780 pairs in 13 tiles) on the host build with
+the 64-leaf capacities.  x8 has N = 63 in 64 lanes, n7 N = 143 in 256."""
 import math
 import os
 import subprocess
@@ -226,6 +227,18 @@ def test_tiled_pairs_on_a_wide_model(hostemu, tmp_path):
     _, lib = hostemu
     r = check_against_restatement(lib, "x8", 8, tmp_path)
     check_chain_untouched(lib, "x8", 8, GOLDEN_ITERS["x8"], r["raw"], tmp_path)
+
+
+def test_more_node_records_than_lanes(tmp_path):
+    """y9: 79 node records in a workgroup of 64 lanes -- the second trip of the staging loop and of the ranking loop; chunks
+    of 3 slots: 3 + 3 + 2 loci, the last chunk the short one"""
+    import run_hostemu
+    import gphocs_amd as G
+    mid = G.load_library(run_hostemu.build_hostemu(mid=True))
+    r = check_against_restatement(mid, "y9", 4, tmp_path, chunk=3)
+    pk = r["pack"]
+    assert 2 * pk.n - 1 > 64 and pk.K >= 25          # what makes the workgroup 64 lanes wide and the records more than that
+    assert r["oob"][0] == 0
 
 
 def test_several_chunks_fold_in_chunk_order(hostemu, tmp_path):

@@ -20,7 +20,7 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_records
-from sampler_util import EXE, _copy_case, _fmt, _locus_names, _pop_names, _run, hostemu_library, printed_names, read_outputs, run_ranks
+from sampler_util import EXE, _copy_case, _fmt, _locus_names, _pop_names, _run, hostemu_library, load_pack, printed_names, read_outputs, run_ranks
 from test_ancestry import BIG, CASES, GOLDEN_ITERS
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
@@ -111,7 +111,7 @@ def run_chain(lib, name, iters, tmp, sample=True, dumps=False, record=None, capa
     records (with the raw bytes), the final state dump, the per-iteration dumps, the pack, host_stats() after initialize and
     at the end, the launches of timing class 17, debug_oob()"""
     import gphocs_amd as G
-    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
+    pk = load_pack(name)
     s = G.Sampler(pk, lib=lib)
     try:
         if record:
@@ -198,6 +198,13 @@ def test_the_case_set_reaches_every_path(hostemu, hostemu_big, tmp_path):
         if ("cpu", name) not in _SEEN:        # (run alone: the dumps of the cases not checked yet in this process)
             check_against_dumps(hostemu_big if name in BIG else hostemu[1], name, CASES[name], tmp_path)
     check_case_set("cpu", list(CASES))
+
+
+def test_a_record_of_more_than_one_trip(hostemu_big, tmp_path):
+    """t136: 136 leaves -- a record of more than 256 units, which takes its workgroup's 256 lanes a second trip"""
+    r = check_against_dumps(hostemu_big, "t136", 3, tmp_path, key="edge")
+    assert r["trees"]["records"].shape[2] // 16 > 256
+    assert r["oob"][0] == 0
 
 
 def check_no_bands(lib, tmp_path, key="cpu"):

@@ -28,7 +28,7 @@ import pytest
 
 from conftest import GOLDEN, REPO
 from parity_util import compare_trace_files
-from sampler_util import EXE, _copy_case, _data_lines, _pop_names, _run, hostemu_library, read_outputs, run_ranks, within_bound  # noqa: F401
+from sampler_util import EXE, _copy_case, _data_lines, _pop_names, _run, hostemu_library, load_pack, read_outputs, run_ranks, within_bound  # noqa: F401
 
 sys.path.insert(0, os.path.join(REPO, "tests", "hostemu"))
 
@@ -168,7 +168,7 @@ def split_row(row, S, K, B):
 def run_chain(lib, name, iters, S, tmp, sample=True, dumps=False, record=None, capacity=None, tag="", chunk=0, log_period=None):
     """one chain over golden `name` (lib None: the tightest capacity variant), a sample after every iteration"""
     import gphocs_amd as G
-    pk = G.Pack.load(os.path.join(GOLDEN, name + ".gpk"))
+    pk = load_pack(name)
     if log_period:
         pk.samplesPerLog = log_period
     s = G.Sampler(pk, lib=lib)
@@ -288,6 +288,20 @@ def test_slices_add_up_to_the_pages_own_statistics(hostemu, tmp_path, name, S):
     sums are the whole row.  Every golden of the test above, the same iteration counts"""
     _, lib = hostemu
     check_against_restatement(lib, name, ITERS[name], S, tmp_path, log_period=1, need_mig=name in ("m3", "j1"))
+
+
+def test_walkers_in_more_than_one_tile(tmp_path):
+    """w139: 39 populations and 100 bands, 32 slices -- 139 walkers, and 192 lanes of accumulators alone (12 * 32 bytes a lane)
+    are more LDS than a workgroup may have, whatever the image of a locus takes: the walkers are tiled over blockIdx.y, and
+    every tile stages the group's images itself"""
+    import run_hostemu
+    import gphocs_amd as G
+    big = G.load_library(run_hostemu.build_hostemu(big=True))
+    S = 32
+    r = check_against_restatement(big, "w139", 3, S, tmp_path)
+    pk = r["pack"]
+    assert (pk.K + pk.B + 63) // 64 * 64 * 12 * S > 61440          # GPH_TS_LDS_MAX
+    assert r["oob"][0] == 0
 
 
 def test_several_chunks_fold_in_chunk_order(hostemu, tmp_path):
