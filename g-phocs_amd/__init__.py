@@ -276,19 +276,24 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("clades_prefix", C.c_char_p), ("clades_loci", C.c_char_p), ("clades_slots", C.c_int32), ("clades_min_support", C.c_double),
                 ("beta", C.c_double), ("marginal_prefix", C.c_char_p), ("marginal_steps", C.c_int32), ("marginal_burnin", C.c_int32),
                 ("marginal_samples", C.c_int32), ("marginal_alpha", C.c_double),
-                ("mc3_chains", C.c_int32), ("mc3_heat", C.c_double), ("mc3_swap_every", C.c_int32), ("mc3_report_prefix", C.c_char_p)]
+                ("mc3_chains", C.c_int32), ("mc3_heat", C.c_double), ("mc3_swap_every", C.c_int32), ("mc3_report_prefix", C.c_char_p),
+                ("replicates", C.c_int32), ("replicates_prefix", C.c_char_p), ("replicates_min_freq", C.c_double),
+                ("replicates_every", C.c_int32)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
                      ancestry=None, ancestry_rows=0, gene_trees=None, gene_trees_loci=None, gene_trees_rows=0,
                      clades=None, clades_loci=None, clades_slots=0, clades_min_support=None,
                      beta=None, marginal=None, marginal_steps=0, marginal_burnin=None, marginal_samples=0, marginal_alpha=0.0,
-                     mc3=0, mc3_heat=0.0, mc3_swap_every=0, mc3_report=None):
+                     mc3=0, mc3_heat=0.0, mc3_swap_every=0, mc3_report=None,
+                     replicates=0, replicates_out=None, replicates_min_freq=None, replicates_every=0):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
     marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
     mc3: the number of Metropolis-coupled chains (0: off), mc3_heat 0: 0.1, mc3_swap_every 0: every iteration, negative: never,
-    mc3_report: the prefix of the report file"""
+    mc3_report: the prefix of the report file.  replicates: the number of independent replicate chains (0: off), replicates_out:
+    the prefix of PREFIX.psrf.tsv / PREFIX.asdsf.tsv / PREFIX.chain<r>.trace, replicates_min_freq None: 0.1, replicates_every
+    k: an ASDSF line on stdout after every k-th sample (0: off)"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -301,7 +306,10 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       marginal_prefix=b(marginal), marginal_steps=marginal_steps,
                       marginal_burnin=0 if marginal_burnin is None else -1 if marginal_burnin == 0 else marginal_burnin,
                       marginal_samples=marginal_samples, marginal_alpha=marginal_alpha,
-                      mc3_chains=mc3, mc3_heat=mc3_heat, mc3_swap_every=mc3_swap_every, mc3_report_prefix=b(mc3_report))
+                      mc3_chains=mc3, mc3_heat=mc3_heat, mc3_swap_every=mc3_swap_every, mc3_report_prefix=b(mc3_report),
+                      replicates=replicates, replicates_prefix=b(replicates_out),
+                      replicates_min_freq=0.0 if replicates_min_freq is None else -1.0 if replicates_min_freq == 0 else replicates_min_freq,
+                      replicates_every=replicates_every)
     return lib.gph_run(C.byref(o))
 
 
@@ -345,7 +353,7 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_clades_fetch", "gph_clades_consensus", "gph_clades_write", "gph_clades_discard",
     "gph_engine_set_beta", "gph_engine_get_beta", "gph_mcmc_set_beta", "gph_mcmc_get_beta",
     "gph_engine_exchange_state", "gph_mcmc_exchange_state", "gph_mc3_create", "gph_mc3_destroy", "gph_mc3_iteration",
-    "gph_mc3_swap_counts", "gph_mc3_swap_log",
+    "gph_mc3_swap_counts", "gph_mc3_swap_log", "gph_engine_clades_compare", "gph_psrf",
 ]
 
 
@@ -512,6 +520,8 @@ def _load_library(path):
     lib.gph_mc3_iteration.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_mc3_swap_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.gph_mc3_swap_log.argtypes = [C.c_void_p, C.POINTER(GphMc3Swap), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_clades_compare.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_psrf.argtypes = [C.POINTER(C.c_double), C.c_int32, C.c_int64, C.POINTER(C.c_double)]
     lib.gph_clades_consensus.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     return lib
@@ -850,6 +860,47 @@ def clades_consensus(lib, keys, cnt, age, samples, leaf_labels):
     if rc != 0:
         raise ValueError(f"gphocs_hip: clades_consensus refused the table or a label (status {rc})")
     return buf.value.decode(), res.value
+
+
+def clades_compare(samplers, min_freq=0.1):
+    """the clade tables of R = 2 .. 16 replicate chains compared on the device (gph_engine_clades_compare; samplers[0] leads): a
+    dict of loci[Q] (global indices), asdsf[Q], max_sd[Q] (float64) and compared, distinct, shared, dropped [Q] (int64).
+    ValueError for what the library refuses (GPH_EARG), RuntimeError for tables that are off or empty (GPH_ESTATE)"""
+    samplers = list(samplers)
+    R = len(samplers)
+    lead = samplers[0] if R else None
+    if lead is None or any(s.lib is not lead.lib for s in samplers):
+        raise ValueError("gphocs_hip: clades_compare takes samplers of one library")
+    Q = lead._clades_shape()[0]
+    hs = (C.c_void_p * max(R, 1))(*[s.engine for s in samplers])
+    rows = np.zeros((max(Q, 1), 6))
+    cnt = C.c_int64()
+    rc = lead.lib.gph_engine_clades_compare(hs, R, float(min_freq), rows.ctypes.data_as(C.POINTER(C.c_double)), rows.shape[0], C.byref(cnt))
+    if rc == -1:
+        raise ValueError("gphocs_hip: clades_compare refused the chains, their tables or min_freq (GPH_EARG)")
+    Sampler._chk(rc, "clades_compare")
+    rows = rows[:cnt.value]
+    loci = np.zeros(max(cnt.value, 1), dtype=np.int64)
+    n = C.c_int64()
+    Sampler._chk(lead.lib.gph_engine_clades_selected(lead.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(n)), "clades_selected")
+    out = dict(loci=loci[:cnt.value].copy(), asdsf=rows[:, 0].copy(), max_sd=rows[:, 1].copy())
+    for k, name in enumerate(("compared", "distinct", "shared", "dropped")):
+        out[name] = rows[:, 2 + k].astype(np.int64)
+    return out
+
+
+def psrf(x, lib=None):
+    """gph_psrf of x[R][S] (R chains, S samples of one quantity): a dict of mean, sd_within, sd_between, psrf.  ValueError for
+    fewer than two chains or samples"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("gphocs_hip: psrf takes x[R][S]")
+    o = (C.c_double * 4)()
+    rc = (lib or load_library()).gph_psrf(x.ctypes.data_as(C.POINTER(C.c_double)), x.shape[0], x.shape[1], o)
+    if rc == -1:
+        raise ValueError("gphocs_hip: psrf needs at least two chains of at least two samples (GPH_EARG)")
+    Sampler._chk(rc, "psrf")
+    return dict(mean=o[0], sd_within=o[1], sd_between=o[2], psrf=o[3])
 
 
 def _dp(a):

@@ -60,6 +60,11 @@ static int rng_ahead_wait(gph_engine *) { return 0; }
 static void rng_ahead_drain(gph_engine *) {}
 // two engines exchange their pages (gph_exchange.h): one thread of launches here, nothing to order
 static int exchange_order(gph_engine *, gph_engine *) { return 0; }
+// R engines' clade tables are read by one kernel of engines[0] (gph_engine_clades_compare): nothing to order here either
+static int compare_order_before(gph_engine *const *, int) { return 0; }
+static int compare_order_after(gph_engine *const *, int) { return 0; }
+// a sampler's result -> the caller's buffer, with the call's one host synchronisation
+static int pull_rows(gph_engine *e, void *h, const void *d, size_t n) { memcpy(h, d, n); e->n_syncs++; return 0; }
 
 static int reduce_local(gph_engine *e, int sec, int ncols)
 {
@@ -177,6 +182,7 @@ struct gph_engine : gph_engine_state {
   hipStream_t stream_ra = nullptr;
   hipEvent_t ev_ra_go = nullptr, ev_ra_done = nullptr;
   hipEvent_t ev_xchg = nullptr;       // what this engine's stream held when its pages went to another engine (gph_exchange.h)
+  hipEvent_t ev_cmp = nullptr;        // gph_engine_clades_compare: what this engine's stream held in front of / behind the kernel
   struct Tm { hipEvent_t a, b; int which; };
   std::vector<Tm> tm;                // event pairs of the launches since the last synchronisation
   size_t tm_used = 0;
@@ -314,6 +320,34 @@ static int exchange_order(gph_engine *a, gph_engine *b)
     }
   }
   return 0;
+}
+// R engines' clade tables are read by one kernel on the stream of p[0] (gph_engine_clades_compare).  Before it: what every other
+// stream holds -- a k_clades that is still writing its tables -- comes first.  Behind it: the others' next k_clades waits until
+// the tables have been read.  Events only, as above: the host does not wait here, no kernel waits for another engine's kernel,
+// and the device is never synchronised as a whole.
+static int compare_event(gph_engine *x)
+{
+  if (!x->ev_cmp) HIPCHK(hipEventCreateWithFlags(&x->ev_cmp, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(x->ev_cmp, x->stream));
+  return 0;
+}
+static int compare_order_before(gph_engine *const *p, int R)
+{
+  for (int r = 1; r < R; r++) { int rc = compare_event(p[r]); if (rc) return rc; }
+  for (int r = 1; r < R; r++) HIPCHK(hipStreamWaitEvent(p[0]->stream, p[r]->ev_cmp, 0));
+  return 0;
+}
+static int compare_order_after(gph_engine *const *p, int R)
+{
+  { int rc = compare_event(p[0]); if (rc) return rc; }
+  for (int r = 1; r < R; r++) HIPCHK(hipStreamWaitEvent(p[r]->stream, p[0]->ev_cmp, 0));
+  return 0;
+}
+// a sampler's result -> the caller's buffer, with the call's one host synchronisation (and the times of what it waited for)
+static int pull_rows(gph_engine *e, void *h, const void *d, size_t n)
+{
+  HIPCHK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, e->stream));
+  return stream_sync(e);
 }
 // a flat kernel on the engine's stream; what is pending and what is counted is the caller's business (sample_begin / _end,
 // apply_list, the reductions below)
@@ -469,6 +503,7 @@ static void backend_close(gph_engine *e)
   if (e->G_h) (void)hipHostFree(e->G_h);
   for (auto &t : e->tm) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   if (e->ev_xchg) (void)hipEventDestroy(e->ev_xchg);
+  if (e->ev_cmp) (void)hipEventDestroy(e->ev_cmp);
   if (e->ev_ra_go) (void)hipEventDestroy(e->ev_ra_go);
   if (e->ev_ra_done) (void)hipEventDestroy(e->ev_ra_done);
   if (e->stream_ra) (void)hipStreamDestroy(e->stream_ra);

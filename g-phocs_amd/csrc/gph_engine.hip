@@ -16,6 +16,8 @@
 #include <vector>
 #include <string>
 #include <algorithm>
+#include <mutex>
+#include <set>
 #if defined(GPH_HOSTEMU) && defined(GPH_EMU64)
 #define GPH_EMU64_IMPL      /* this translation unit holds the micro-wave scheduler (gph_emu64.h; test builds only) */
 #endif
@@ -27,6 +29,7 @@
 #include "gph_ancestry.h"
 #include "gph_genetrees.h"
 #include "gph_clades.h"
+#include "gph_cladecmp.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
 
@@ -425,7 +428,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 20     // (18: k_rng_ahead, 19: k_clades) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 21     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -526,8 +529,9 @@ struct gph_engine_state {
   struct { SmRows rows; GphGtShape shape = {}; SmSel sel; std::vector<int32_t> iters; } gt;
   // clade tables of selected loci (gph_clades.h): entries [nsel][P][W + 2] and header words [nsel][2] in selection order, the
   // selected loci of this rank with their slots in HBM, samples since the tables were last zeroed
+  // d_cmp: the rows of the last gph_engine_clades_compare this engine led ([nsel][GPH_CC_COLS], allocated by the first one)
   struct { uint64_t *d_ent = nullptr; uint32_t *d_hdr = nullptr; GphClShape shape = {}; SmSel sel;
-           int64_t samples = 0; bool on = false; } cl;
+           int64_t samples = 0; bool on = false; double *d_cmp = nullptr; } cl;
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -853,6 +857,16 @@ static int rng_ahead_alloc(gph_engine *e)
   return 0;
 }
 
+// the engines this library has made and not yet destroyed: a call that takes several engines (gph_engine_clades_compare) is
+// handed pointers it cannot look into before it knows they are its own -- every capacity variant has its own gph_engine
+static std::mutex g_engines_lock;
+static std::set<const gph_engine *> g_engines;
+static bool engine_is_ours(const gph_engine *e)
+{
+  std::lock_guard<std::mutex> hold(g_engines_lock);
+  return g_engines.count(e) != 0;
+}
+
 // ---------------------------------------------------------------- C ABI
 extern "C" {
 static void rng_ahead_dirty(gph_engine *e);
@@ -900,6 +914,7 @@ int gph_engine_create(const gph_config *cfg, gph_engine **out)
   e->G_h->error_locus = -1;          /* (0 is a locus: an error that is not per-locus must not name it -- ADVICE round 5) */
   e->G_h->beta = 1.0;                /* the posterior itself */
   build_model_static(e);
+  { std::lock_guard<std::mutex> hold(g_engines_lock); g_engines.insert(e); }
   *out = e;
   return 0;
 }
@@ -907,6 +922,7 @@ int gph_engine_create(const gph_config *cfg, gph_engine **out)
 void gph_engine_destroy(gph_engine *e)
 {
   if (!e) return;
+  { std::lock_guard<std::mutex> hold(g_engines_lock); g_engines.erase(e); }
   rng_ahead_drain(e);
   dev_free(e->dev.pages); dev_free(e->dev.shadow); dev_free(e->dev.cond); dev_free((void *)e->dev.cond_off);
   dev_free((void *)e->dev.seq); dev_free((void *)e->dev.seq_off); dev_free((void *)e->dev.orig); dev_free((void *)e->dev.P); dev_free(e->dev.out); dev_free(e->dev.stats); dev_free(e->d_mutRate);
@@ -916,7 +932,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   dev_free(e->gt.rows.d); dev_free(e->gt.sel.d_slot);
-  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.sel.d_slot);
+  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp); dev_free(e->cl.sel.d_slot);
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
   dev_free(e->d_red);
@@ -2769,8 +2785,8 @@ static int clades_zero(gph_engine *e)
 }
 static void clades_free(gph_engine *e)
 {
-  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr);
-  e->cl.d_ent = nullptr; e->cl.d_hdr = nullptr;
+  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp);
+  e->cl.d_ent = nullptr; e->cl.d_hdr = nullptr; e->cl.d_cmp = nullptr;
   sel_free(e->cl.sel);
   e->cl.shape = GphClShape{};
   e->cl.samples = 0;
@@ -2861,6 +2877,50 @@ int gph_engine_clades_fetch(gph_engine *e, uint64_t *entries, uint32_t *nkeys, u
     for (size_t q = 0; q < nsel; q++) { nkeys[q] = hdr[2 * q]; dropped[q] = hdr[2 * q + 1]; }
   }
   return reset ? clades_zero(e) : 0;
+}
+
+// ---- the clade tables of R replicate chains compared where they lie (gph_cladecmp.h); engines[0] leads: its stream runs the
+// kernel, its counters count it, its host thread waits for the rows
+int gph_engine_clades_compare(gph_engine *const *engines, int32_t R, double min_freq, double *rows, int64_t max_loci, int64_t *count)
+{
+  if (!engines || !count || R < 2 || R > GPH_CC_MAXR || max_loci < 0 || (!rows && max_loci > 0)) return GPH_EARG;
+  if (!(min_freq >= 0.0 && min_freq <= 1.0)) return GPH_EARG;       /* (a NaN fails both) */
+  for (int r = 0; r < R; r++) {
+    if (!engines[r] || !engine_is_ours(engines[r])) return GPH_EARG;
+    for (int j = 0; j < r; j++) if (engines[j] == engines[r]) return GPH_EARG;
+  }
+  gph_engine *e = engines[0];
+  for (int r = 1; r < R; r++)
+    if (engines[r]->cfg.device != e->cfg.device || engines[r]->cfg.n != e->cfg.n) return GPH_EARG;
+  for (int r = 0; r < R; r++) if (!engines[r]->cl.on) return GPH_ESTATE;
+  const GphClShape &h = e->cl.shape;
+  for (int r = 1; r < R; r++) {
+    const auto &c = engines[r]->cl;
+    if (c.shape.P != h.P || c.shape.W != h.W || c.shape.ew != h.ew || c.sel.loci != e->cl.sel.loci) return GPH_EARG;
+  }
+  const int64_t nsel = (int64_t)e->cl.sel.loci.size();
+  if (max_loci < nsel) return GPH_EARG;
+  for (int r = 0; r < R; r++) if (engines[r]->cl.samples < 1) return GPH_ESTATE;
+  *count = nsel;
+  if (nsel == 0) return 0;           /* (a rank without a selected locus launches nothing) */
+  SETDEV(e);
+  if (!e->cl.d_cmp && dev_alloc((void **)&e->cl.d_cmp, sizeof(double) * GPH_CC_COLS * (size_t)nsel)) {
+    dev_clear_error();
+    e->cl.d_cmp = nullptr;
+    return GPH_EHIP;
+  }
+  GphCcTables T;
+  memset(&T, 0, sizeof T);
+  for (int r = 0; r < R; r++) { T.ent[r] = engines[r]->cl.d_ent; T.hdr[r] = engines[r]->cl.d_hdr; T.samples[r] = engines[r]->cl.samples; }
+  const int groups = (int)((nsel + GPH_CC_THREADS / GPH_CC_WAVE - 1) / (GPH_CC_THREADS / GPH_CC_WAVE));
+  int tms, rc;
+  if ((rc = compare_order_before(engines, R))) return rc;      /* (in front of the timing events: the kernel's time, not the wait) */
+  if ((rc = sample_begin(e, 20, tms))) return rc;
+  if ((rc = launch_grid(e, GphGrid{groups, 1}, GPH_CC_THREADS, (size_t)gph_cc_lds_bytes(h.W), k_clades_compare, h, T, (int)R, (int)e->cfg.n, (int)nsel,
+                        min_freq, e->cl.d_cmp))) return rc;
+  sample_end(e, 20, 1, tms);
+  if ((rc = compare_order_after(engines, R))) return rc;
+  return pull_rows(e, rows, e->cl.d_cmp, sizeof(double) * GPH_CC_COLS * (size_t)nsel);
 }
 
 // ---- two engines exchange their chain states (Metropolis-coupled chains)

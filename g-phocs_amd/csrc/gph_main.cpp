@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] [--replicates R --replicates-out rep-prefix [--replicates-min-freq F] [--replicates-every k]] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -31,6 +31,12 @@
 // negative: never) two neighbouring chains are proposed to exchange their states.  Chain 0 is the control file's chain and stays
 // the cold one, so the trace and every output above describe the posterior as before; --mc3-report PREFIX writes the ladder,
 // the swap counts and every chain's acceptance to PREFIX.mc3.tsv.  Not with -g N > 1, --beta or --marginal-likelihood.
+// --replicates R --replicates-out PREFIX runs R = 2 .. 16 independent chains on the one GPU (chain r seeded with random-seed + r,
+// chain 0 the control file's own, its outputs unchanged) and writes the convergence diagnostics across them: the potential
+// scale reduction factor of every trace column to PREFIX.psrf.tsv, with --clades the per-locus average standard deviation of
+// split frequencies to PREFIX.asdsf.tsv (over the clades some chain holds with frequency >= F, --replicates-min-freq F, default
+// 0.1), the other chains' traces to PREFIX.chain<r>.trace; --replicates-every k prints the ASDSF after every k-th sample.  Not
+// with -g N > 1, --mc3, --beta or --marginal-likelihood.
 // They compose freely.  Under -g N every child leaves parts: of the summary table FILE.part<r>, which the launcher
 // concatenates in rank order into FILE once every child has exited 0; of the others the library's own, which gph_run_finish
 // turns into the files (the launcher itself has not touched a GPU).  A run that did not finish leaves neither parts nor files.
@@ -106,7 +112,7 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] [--replicates R --replicates-out rep-prefix [--replicates-min-freq F] [--replicates-every k]] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
@@ -179,6 +185,21 @@ int main(int argc, char **argv)
       if (o.mc3_swap_every == 0) { fprintf(stderr, "%s: --mc3-swap-every takes a number of iterations k >= 1, or a negative number for no swaps\n", argv[0]); return usage(argv[0]); }
     }
     else if (!strcmp(argv[i], "--mc3-report") && i + 1 < argc) o.mc3_report_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--replicates") && i + 1 < argc) {
+      o.replicates = atoi(argv[++i]);
+      if (o.replicates < 2 || o.replicates > 16) { fprintf(stderr, "%s: --replicates takes a number of chains R in 2 .. 16\n", argv[0]); return usage(argv[0]); }
+    }
+    else if (!strcmp(argv[i], "--replicates-out") && i + 1 < argc) o.replicates_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--replicates-min-freq") && i + 1 < argc) {
+      char *end = nullptr;
+      const double F = strtod(argv[++i], &end);
+      if (end == argv[i] || *end || !(F >= 0.0 && F <= 1.0)) { fprintf(stderr, "%s: --replicates-min-freq takes a number in [0, 1]\n", argv[0]); return usage(argv[0]); }
+      o.replicates_min_freq = F == 0.0 ? -1.0 : F;     /* (0 in the options struct means the default) */
+    }
+    else if (!strcmp(argv[i], "--replicates-every") && i + 1 < argc) {
+      o.replicates_every = atoi(argv[++i]);
+      if (o.replicates_every < 1) { fprintf(stderr, "%s: --replicates-every takes a number of samples k >= 1\n", argv[0]); return usage(argv[0]); }
+    }
     else if (!strcmp(argv[i], "-n") && i + 1 < argc) ++i;   /* thread count of the OpenMP build: accepted, ignored */
     else return usage(argv[0]);
   }
@@ -198,6 +219,16 @@ int main(int argc, char **argv)
   if (o.mc3_chains && gpus > 1) { fprintf(stderr, "%s: --mc3 runs its chains on one GPU: not with -g N > 1\n", argv[0]); return usage(argv[0]); }
   if (o.mc3_chains && o.beta != 0.0) { fprintf(stderr, "%s: --mc3 and --beta exclude each other\n", argv[0]); return usage(argv[0]); }
   if (o.mc3_chains && o.marginal_prefix) { fprintf(stderr, "%s: --mc3 and --marginal-likelihood exclude each other\n", argv[0]); return usage(argv[0]); }
+  if ((o.replicates_prefix || o.replicates_min_freq != 0.0 || o.replicates_every) && !o.replicates) {
+    fprintf(stderr, "%s: --replicates-out, --replicates-min-freq and --replicates-every need --replicates R\n", argv[0]);
+    return usage(argv[0]);
+  }
+  if (o.replicates && !o.replicates_prefix) { fprintf(stderr, "%s: --replicates needs --replicates-out PREFIX\n", argv[0]); return usage(argv[0]); }
+  if (o.replicates_every && !o.clades_prefix) { fprintf(stderr, "%s: --replicates-every needs --clades PREFIX\n", argv[0]); return usage(argv[0]); }
+  if (o.replicates && gpus > 1) { fprintf(stderr, "%s: --replicates runs its chains on one GPU: not with -g N > 1\n", argv[0]); return usage(argv[0]); }
+  if (o.replicates && o.mc3_chains) { fprintf(stderr, "%s: --replicates and --mc3 exclude each other\n", argv[0]); return usage(argv[0]); }
+  if (o.replicates && o.beta != 0.0) { fprintf(stderr, "%s: --replicates and --beta exclude each other\n", argv[0]); return usage(argv[0]); }
+  if (o.replicates && o.marginal_prefix) { fprintf(stderr, "%s: --replicates and --marginal-likelihood exclude each other\n", argv[0]); return usage(argv[0]); }
   o.ctl = argv[i];
   o.ctl2 = i + 1 < argc ? argv[i + 1] : nullptr;
   char self[PATH_MAX];
@@ -303,7 +334,7 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(o.locus_summary_path); bad = 1; }
     if (bad && out) unlink(o.locus_summary_path);
   }
-  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.marginal_prefix || o.mc3_report_prefix) {
+  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.marginal_prefix || o.mc3_report_prefix || o.replicates_prefix) {
     /* the ranks' parts into the files, by the library that wrote them -- or, after a failure, removed */
     if (sym<decltype(&gph_run_finish)>(load_engine(dir, o.ctl, o.ctl2), "gph_run_finish")(&o, gpus, bad)) bad = 1;
   }

@@ -15,6 +15,9 @@ struct Mc3Run {
   gph_mc3 *G = nullptr;
   std::vector<double> betas, sumL;
   int64_t nL = 0, nIter = 0;
+  const char *const opt = "--mc3";     /* the option the group runs for */
+  /* `--replicates R` (gph_replicates_run.h): the same group with every beta = 1 and no swaps */
+  Mc3Run(int chains, const char *option) : C(chains), every(-1), h(0.0), opt(option) {}
   explicit Mc3Run(const gph_run_options &o) : C(o.mc3_chains), every(o.mc3_swap_every == 0 ? 1 : o.mc3_swap_every < 0 ? -1 : o.mc3_swap_every),
                                               h(o.mc3_heat != 0.0 ? o.mc3_heat : 0.1) {}
   ~Mc3Run()
@@ -55,7 +58,7 @@ struct Mc3Run {
       if ((rc = gph_engine_create(&R.cfg, &e))) return R.fail(rc, "gph_engine_create of a heated chain");
       E.push_back(e);
       if ((rc = gph_engine_load_loci(e, R.le - R.lb, R.offs + R.lb, R.leaf, R.ph, R.cnt, R.info.mutRateMode == 2 ? R.rates + R.lb : nullptr))) {
-        snprintf(R.err, sizeof R.err, "--mc3 %d: chain %d could not be allocated; every chain takes %.1f MB of device memory, %.1f MB in all", C, c,
+        snprintf(R.err, sizeof R.err, "%s %d: chain %d could not be allocated; every chain takes %.1f MB of device memory, %.1f MB in all", opt, C, c,
                  bytes / 1e6, C * bytes / 1e6);
         return R.fail(rc, "gph_engine_load_loci of a heated chain");
       }
@@ -73,7 +76,7 @@ struct Mc3Run {
       if ((rc = gph_mcmc_initialize(m, nullptr))) return R.fail(rc, "gph_mcmc_initialize of a heated chain");
     if ((rc = gph_mc3_create(all.data(), C, betas.data(), every, (uint32_t)(R.mc.seed + C), &G))) return R.fail(rc, "gph_mc3_create");
     sumL.assign(C, 0.0);
-    if (R.lead) {
+    if (R.lead && h != 0.0) {
       printf("MC3: %d chains on the ladder beta_c = 1 / (1 + %.10g c):", C, h);
       for (double b : betas) printf(" %.10g", b);
       if (every > 0) printf("; a swap of two neighbours is attempted every %d iteration(s).\n", every);

@@ -428,5 +428,7 @@ int gph_mcmc_accept_counts(gph_mcmc *m, int64_t *counts9)
 
 // ---- Metropolis-coupled chains: the exchange of two chains' states and the group that runs them
 #include "gph_mc3.h"
+// ---- the potential scale reduction factor of a trace column over replicate chains
+#include "gph_psrf.h"
 
 } // extern "C"

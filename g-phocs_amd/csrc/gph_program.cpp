@@ -930,6 +930,9 @@ struct Run {
   int read_loci();
   int start_engine();
   int open_trace();
+  std::vector<std::string> trace_columns() const;
+  void trace_header(FILE *f) const;
+  void trace_values(FILE *f, int it, const double *v, double logL, double dataL) const;
   void trace_line(int it);
 };
 
@@ -1010,28 +1013,48 @@ int Run::open_trace()
 {
   trace = fopen(lead ? info.traceFile : "/dev/null", "w");
   if (!trace) { snprintf(err, sizeof err, "Could not open trace file %s", info.traceFile); return fail(GPH_EARG, "opening the trace file"); }
-  fprintf(trace, "Sample");
-  for (int p = 0; p < cfg.K; p++) fprintf(trace, "\ttheta_%s", gph_control_pop_name(C, p));
-  for (int p = cfg.Kc; p < cfg.K; p++) fprintf(trace, "\ttau_%s", gph_control_pop_name(C, p));
-  for (int b = 0; b < cfg.B; b++)
-    fprintf(trace, "\tm_%s->%s", gph_control_pop_name(C, cfg.bandSrc[b]), gph_control_pop_name(C, cfg.bandTgt[b]));
-  for (int p = 0; p < cfg.Kc; p++)
-    if (mc.updateSampleAge[p] || mc.sampleAge[p] > 0.0) fprintf(trace, "\ttau_%s", gph_control_pop_name(C, p));
-  if (info.mutRateMode == 1) fprintf(trace, "\tVariance-Mut");   /* GPhoCS.c:1311-1312 */
-  fprintf(trace, "\tData-ld-ln\tFull-ld-ln\n");
+  trace_header(trace);
   vals.assign(mc.numParameters + 4, 0.0);
   return GPH_OK;
 }
 
-void Run::trace_line(int it)   /* GPhoCS.c:1763-1769 */
+// the columns behind "Sample", as the header names them
+std::vector<std::string> Run::trace_columns() const
+{
+  std::vector<std::string> c;
+  const auto pop = [&](int p) { return std::string(gph_control_pop_name(C, p)); };
+  for (int p = 0; p < cfg.K; p++) c.push_back("theta_" + pop(p));
+  for (int p = cfg.Kc; p < cfg.K; p++) c.push_back("tau_" + pop(p));
+  for (int b = 0; b < cfg.B; b++) c.push_back("m_" + pop(cfg.bandSrc[b]) + "->" + pop(cfg.bandTgt[b]));
+  for (int p = 0; p < cfg.Kc; p++)
+    if (mc.updateSampleAge[p] || mc.sampleAge[p] > 0.0) c.push_back("tau_" + pop(p));
+  if (info.mutRateMode == 1) c.push_back("Variance-Mut");   /* GPhoCS.c:1311-1312 */
+  c.push_back("Data-ld-ln");
+  c.push_back("Full-ld-ln");
+  return c;
+}
+
+void Run::trace_header(FILE *f) const
+{
+  fprintf(f, "Sample");
+  for (const std::string &c : trace_columns()) fprintf(f, "\t%s", c.c_str());
+  fprintf(f, "\n");
+}
+
+void Run::trace_values(FILE *f, int it, const double *v, double logL, double dataL) const   /* GPhoCS.c:1763-1769 */
+{
+  fprintf(f, "%d\t", it);
+  for (int i = 0; i < mc.numParameters; i++) fprintf(f, "%8.5f\t", v[i] * mc.printFactors[i]);
+  fprintf(f, "\t%.6f\t%.6f\n", logL, dataL);
+  fflush(f);
+}
+
+void Run::trace_line(int it)
 {
   double logL = 0, dataL = 0;
   gph_mcmc_param_vals(M, vals.data(), mc.numParameters);
   gph_mcmc_get_state(M, &logL, &dataL, nullptr, nullptr, nullptr);
-  fprintf(trace, "%d\t", it);
-  for (int i = 0; i < mc.numParameters; i++) fprintf(trace, "%8.5f\t", vals[i] * mc.printFactors[i]);
-  fprintf(trace, "\t%.6f\t%.6f\n", logL, dataL);
-  fflush(trace);
+  trace_values(trace, it, vals.data(), logL, dataL);
 }
 
 // ---- `--mc3`: the heated chains next to the run's own
@@ -1469,6 +1492,9 @@ struct Outputs {
   }
 };
 
+// ---- `--replicates`: independent chains next to the run's own, and the diagnostics across them
+#include "gph_replicates_run.h"
+
 // ---- the log on stdout and the find-finetunes search (GPhoCS.c:1329, 1356-1447, 1808-2249)
 struct Log {
   Run &R;
@@ -1726,6 +1752,7 @@ int run_chain(const gph_run_options &o)
 {
   Run R(o);
   std::unique_ptr<Mc3Run> mc3;   /* (behind R: the heated chains go before the loci they were loaded from) */
+  std::unique_ptr<Replicates> rep;
   Outputs outs(o);   /* (behind R: the parts are closed before anything is freed) */
   int rc;
   if ((rc = R.read_control())) return rc;
@@ -1744,6 +1771,11 @@ int run_chain(const gph_run_options &o)
     mc3.reset(new Mc3Run(o));
     if ((rc = mc3->start(R))) return rc;
   }
+  if (o.replicates) {
+    mc3.reset(new Mc3Run(o.replicates, "--replicates"));
+    if ((rc = mc3->start(R))) return rc;
+    rep.reset(new Replicates(o, *mc3));
+  }
 
   const gph_control_info &info = R.info;
   if (R.lead) printf("Starting MCMC: %d burnin, %d running, sampled every %d iteration(s).\n", info.burnin, info.numSamples, info.sampleSkip);
@@ -1753,6 +1785,7 @@ int run_chain(const gph_run_options &o)
   if (mc3 && (rc = mc3->initialize(R))) return rc;
   for (auto x = outs.list.rbegin(); x != outs.list.rend(); ++x)
     if ((rc = (*x)->open(R))) return rc;
+  if (rep && (rc = rep->open(R, outs.clades))) return rc;
   auto t1 = std::chrono::steady_clock::now();
   Log log(R, totalCoals, mc3.get());
   if ((rc = log.start())) return rc;
@@ -1764,6 +1797,7 @@ int run_chain(const gph_run_options &o)
       R.trace_line(it);
       for (auto &x : outs.list)
         if ((rc = x->sample(R, it))) return rc;
+      if (rep && (rc = rep->sample(R, it))) return rc;
     }
     log.logCount++;
     if ((it + 1) % log.samplesPerLog == 0 && (rc = log.period(it))) return rc;
@@ -1774,7 +1808,8 @@ int run_chain(const gph_run_options &o)
     printf("\nMCMC finished. Time used: %s\n", log.printtime(tbuf, sizeof tbuf));   /* GPhoCS.c:2262 */
     if (o.verbose) printf("(%.2f s, %.3f iterations/s)\n", sec, (info.burnin + info.numSamples) / (sec > 0 ? sec : 1));
   }
-  if (mc3) mc3->log_pairs(R);
+  if (mc3 && !rep) mc3->log_pairs(R);
+  if (rep && (rc = rep->finish(R))) return rc;
   fclose(R.trace);
   R.trace = nullptr;
   for (auto x = outs.list.rbegin(); x != outs.list.rend(); ++x)
@@ -1796,10 +1831,11 @@ int run_chain(const gph_run_options &o)
   if (rcr) return rcr;
   if (checked && where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
     return GPH_EKERNEL;
   }
   if (outs.summary && (rc = outs.summary->write_table(R))) return rc;
+  if (rep && R.lead && (rc = rep->write(R))) return rc;
   return ml && R.lead ? ml->write(R) : GPH_OK;
 }
 }   // namespace
@@ -1817,6 +1853,7 @@ extern "C" int gph_run_finish(const gph_run_options *in, int32_t ranks, int32_t 
     for (auto &x : outs.list) x->discard(ranks);
     if (o.marginal_prefix) unlink(marginal_path(o.marginal_prefix).c_str());
     if (o.mc3_report_prefix) unlink(mc3_path(o.mc3_report_prefix).c_str());
+    if (o.replicates_prefix) { unlink(rep_path(o.replicates_prefix, ".psrf.tsv").c_str()); unlink(rep_path(o.replicates_prefix, ".asdsf.tsv").c_str()); }
   }
   return rc;
 }
@@ -1830,7 +1867,8 @@ extern "C" int gph_run(const gph_run_options *in)
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
   /* the checks on the options alone, before anything is read */
   int rc;
-  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o))) return rc;
+  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
+      (rc = Replicates::validate(o))) return rc;
   rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */
   if (o.world == 1) {

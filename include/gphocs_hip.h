@@ -220,7 +220,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * (gph_engine_coal_stats_sample: k_coal_stats + k_rows_fold together), 15 time-sliced statistics
  * (gph_engine_time_slices_sample: k_time_slices + k_rows_fold together), 16 migration ancestry
  * (gph_engine_ancestry_sample: k_ancestry), 17 sampled genealogies (gph_engine_gene_trees_sample: k_gene_trees), 18 the
- * sweep's draws generated ahead of it (k_rng_ahead), 19 clade tables (gph_engine_clades_sample: k_clades) */
+ * sweep's draws generated ahead of it (k_rng_ahead), 19 clade tables (gph_engine_clades_sample: k_clades), 20 the clade
+ * tables of replicate chains compared (gph_engine_clades_compare: k_clades_compare, counted on engines[0]) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -440,6 +441,39 @@ int gph_engine_clades_sample(gph_engine *e);
 int gph_engine_clades_shape(gph_engine *e, int64_t *selected, int32_t *slots, int32_t *words, int32_t *limit, int64_t *samples);
 int gph_engine_clades_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
 int gph_engine_clades_fetch(gph_engine *e, uint64_t *entries, uint32_t *nkeys, uint32_t *dropped, int32_t reset);
+/* REPLICATE CHAINS COMPARED: how far apart are the clade frequencies of R = 2 .. 16 chains, per selected locus, computed on
+ * the device from the chains' clade tables where they lie (k_clades_compare: csrc/gph_cladecmp.h); only the rows leave it.
+ * All engines belong to this library and one device, and their tables share the selection, the slots and W; chain r has taken
+ * S_r >= 1 samples.  For locus q let U be the distinct keys kept in at least one of the R tables; the trivial clade (all n
+ * leaves) is left out everywhere.  For k in U: c_r = the entry's cnt in table r, 0 where table r does not hold k (a clade
+ * that a FULL table dropped counts as frequency 0 in that chain -- that is what the table says, and dropped > 0 in the row is
+ * the warning, as for the tables themselves), and in plain fp64, in this operand order,
+ *   f_r = (double)c_r / (double)S_r        m = (((f_0 + f_1) + ...) + f_{R-1}) / R
+ *   v = (sum_r (f_r - m) (f_r - m), added in chain order) / (R - 1)        sd = sqrt(v)
+ * k is COMPARED iff max_r f_r >= min_freq.  rows[q][6], q over the selected loci of the rank in increasing locus index:
+ *   asdsf     sum of sd over the compared clades / their number, 0 when there are none (the average standard deviation of
+ *             split frequencies); the sds are added in an order of the kernel's own that does not depend on the other loci
+ *   maxSd     max sd over the compared clades, 0 when there are none
+ *   compared  their number            distinct  |U|
+ *   shared    keys held by all R tables            dropped   sum over the chains of the tables' `dropped` words
+ * (counts are exact in fp64).  *count = the selected loci of the rank; none: nothing is launched.  Order: engines[0]'s stream
+ * waits, through events, for what the other engines' streams hold (their last k_clades), runs the one kernel (timing class
+ * 20, counted on engines[0]), and the other streams wait for it before they go on, so a later sample cannot write a table
+ * that is still being read; then one copy of the rows and ONE host synchronisation, on engines[0].  No device-wide
+ * synchronisation, no kernel waits for another stream.  No table, page or chain state is written.
+ * GPH_EARG, nothing changed: R outside 2 .. 16; a null, foreign (another library variant's) or repeated engine; min_freq not
+ * in [0, 1] or not finite; engines on different devices; different selections, slots or key words; max_loci below the
+ * selection.  GPH_ESTATE: clade tables not enabled on some engine; a sample count of 0. */
+int gph_engine_clades_compare(gph_engine *const *engines, int32_t R, double min_freq, double *rows /* [max_loci][6] */, int64_t max_loci,
+                              int64_t *count);
+/* the potential scale reduction factor (Gelman & Rubin 1992) of one quantity over R >= 2 chains of S >= 2 samples each,
+ * x[R][S]; host code, plain fp64 in this operand order (a loop in the same order reproduces every bit):
+ *   m_r = (sum_s x[r][s], added in sample order) / S        v_r = (sum_s (x[r][s] - m_r)^2, added in sample order) / (S - 1)
+ *   Wv = (sum_r v_r, added in chain order) / R              M = (sum_r m_r, added in chain order) / R
+ *   Bn = (sum_r (m_r - M)^2, added in chain order) / (R - 1)        V = ((double)(S - 1) / (double)S) * Wv + Bn
+ *   out = {mean M, sdWithin sqrt(Wv), sdBetween sqrt(Bn), psrf sqrt(V / Wv)};  Wv == 0: psrf = 1 if Bn == 0, else +inf
+ * R < 2, S < 2 or a null pointer: GPH_EARG. */
+int gph_psrf(const double *x /* [R][S] */, int32_t R, int64_t S, double *out /* mean, sdWithin, sdBetween, psrf */);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -749,6 +783,34 @@ typedef struct gph_run_options {
   double mc3_heat;
   int32_t mc3_swap_every;
   const char *mc3_report_prefix;
+  /* `--replicates R --replicates-out PREFIX [--replicates-min-freq F] [--replicates-every k]`: R = 2 .. 16 INDEPENDENT chains on
+   * this device, all at beta = 1, chain r seeded with random-seed + r, and the convergence diagnostics across them.  Chain 0 is
+   * the control file's chain: its trace and every other output are the bytes of the run without the option.  The chains run
+   * through gph_mc3 with every beta = 1 and no swaps (a host thread and a stream each); chain 0's step sizes and log period are
+   * pushed to all of them, none is tuned by itself; they take R times the device memory, and a chain that cannot be allocated
+   * stops the run before the first iteration with a message.  At every sample point (the rule of the summary table) chain
+   * r >= 1 writes its trace line to PREFIX.chain<r>.trace (the trace file's header and formats; the files behave like the
+   * trace file), every chain samples its clade tables when clades_prefix is given (chains r >= 1 with chain 0's selection and
+   * slots), and the values every chain's trace line prints are kept on the host, before formatting: vals[i] * printFactors[i],
+   * then Full-ld-ln, then Data-ld-ln.  After the last iteration, on success only (gph_run_finish removes both after a failure):
+   *   PREFIX.psrf.tsv    header param mean sdWithin sdBetween psrf; one row per trace column in trace order, named as the
+   *                      trace header names it, numbers "%.10g" (gph_psrf); last line "# chains R samples S maxPsrf v"
+   *   PREFIX.asdsf.tsv   with clades_prefix only: header locus name samples asdsf maxSd compared distinct shared dropped; one
+   *                      row per selected locus in sequence-file order (gph_engine_clades_compare with min_freq F; locus,
+   *                      samples and the four counts "%d", the rest "%.10g"); last line
+   *                      "# chains R minfreq F loci Q meanAsdsf v maxAsdsf v", the mean over the rows in file order
+   * replicates_min_freq F: 0 = 0.1, negative = 0, else F in (0, 1].  replicates_every k >= 1 (0: off; clades_prefix only): after
+   * every k-th sample and after the last, one line "Replicates: sample <S>: ASDSF mean <v> max <v> over <Q> loci" on stdout,
+   * each at the cost of one kernel and one host synchronisation; the last line's values are the file's.  Conventionally an
+   * ASDSF below 0.01 and a PSRF below 1.1 are read as agreement between the chains; nothing here guarantees either.
+   * GPH_EARG, with a message that names the option and before anything is read: replicates outside 2 .. 16; no
+   * replicates_prefix; any other replicates_* field without replicates; F above 1 or not finite; k < 0; replicates_every
+   * without clades_prefix; replicates with world > 1, a communicator or an all-reduce hook, mc3_chains, beta or
+   * marginal_prefix. */
+  int32_t replicates;
+  const char *replicates_prefix;
+  double replicates_min_freq;
+  int32_t replicates_every;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
