@@ -278,7 +278,7 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("marginal_samples", C.c_int32), ("marginal_alpha", C.c_double),
                 ("mc3_chains", C.c_int32), ("mc3_heat", C.c_double), ("mc3_swap_every", C.c_int32), ("mc3_report_prefix", C.c_char_p),
                 ("replicates", C.c_int32), ("replicates_prefix", C.c_char_p), ("replicates_min_freq", C.c_double),
-                ("replicates_every", C.c_int32)]
+                ("replicates_every", C.c_int32), ("ess_prefix", C.c_char_p), ("ess_loci", C.c_char_p)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
@@ -286,14 +286,15 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                      clades=None, clades_loci=None, clades_slots=0, clades_min_support=None,
                      beta=None, marginal=None, marginal_steps=0, marginal_burnin=None, marginal_samples=0, marginal_alpha=0.0,
                      mc3=0, mc3_heat=0.0, mc3_swap_every=0, mc3_report=None,
-                     replicates=0, replicates_out=None, replicates_min_freq=None, replicates_every=0):
+                     replicates=0, replicates_out=None, replicates_min_freq=None, replicates_every=0, ess=None, ess_loci=None):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
     marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
     mc3: the number of Metropolis-coupled chains (0: off), mc3_heat 0: 0.1, mc3_swap_every 0: every iteration, negative: never,
     mc3_report: the prefix of the report file.  replicates: the number of independent replicate chains (0: off), replicates_out:
     the prefix of PREFIX.psrf.tsv / PREFIX.asdsf.tsv / PREFIX.chain<r>.trace, replicates_min_freq None: 0.1, replicates_every
-    k: an ASDSF line on stdout after every k-th sample (0: off)"""
+    k: an ASDSF line on stdout after every k-th sample (0: off).  ess: the prefix of PREFIX.ess.tsv / PREFIX.locus-ess.tsv,
+    ess_loci: the loci of the second (a SPEC as gene_trees_loci; None: all)"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -309,7 +310,7 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       mc3_chains=mc3, mc3_heat=mc3_heat, mc3_swap_every=mc3_swap_every, mc3_report_prefix=b(mc3_report),
                       replicates=replicates, replicates_prefix=b(replicates_out),
                       replicates_min_freq=0.0 if replicates_min_freq is None else -1.0 if replicates_min_freq == 0 else replicates_min_freq,
-                      replicates_every=replicates_every)
+                      replicates_every=replicates_every, ess_prefix=b(ess), ess_loci=b(ess_loci))
     return lib.gph_run(C.byref(o))
 
 
@@ -354,6 +355,8 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_set_beta", "gph_engine_get_beta", "gph_mcmc_set_beta", "gph_mcmc_get_beta",
     "gph_engine_exchange_state", "gph_mcmc_exchange_state", "gph_mc3_create", "gph_mc3_destroy", "gph_mc3_iteration",
     "gph_mc3_swap_counts", "gph_mc3_swap_log", "gph_engine_clades_compare", "gph_psrf",
+    "gph_ess", "gph_ess_read", "gph_engine_ess_enable", "gph_engine_ess_sample", "gph_engine_ess_shape", "gph_engine_ess_selected",
+    "gph_engine_ess_fetch", "gph_ess_write", "gph_ess_discard", "gph_read_trace_ess",
 ]
 
 
@@ -524,6 +527,17 @@ def _load_library(path):
     lib.gph_psrf.argtypes = [C.POINTER(C.c_double), C.c_int32, C.c_int64, C.POINTER(C.c_double)]
     lib.gph_clades_consensus.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+    lib.gph_read_trace_ess.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
+    lib.gph_ess_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_ess_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_ess.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int32, C.POINTER(C.c_double)]
+    lib.gph_ess_read.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int32, C.POINTER(C.c_double)]
+    lib.gph_engine_ess_enable.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_int64]
+    lib.gph_engine_ess_sample.argtypes = [C.c_void_p]
+    lib.gph_engine_ess_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int64)]
+    lib.gph_engine_ess_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_ess_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     return lib
 
 
@@ -901,6 +915,38 @@ def psrf(x, lib=None):
         raise ValueError("gphocs_hip: psrf needs at least two chains of at least two samples (GPH_EARG)")
     Sampler._chk(rc, "psrf")
     return dict(mean=o[0], sd_within=o[1], sd_between=o[2], psrf=o[3])
+
+
+ESS_SERIES = ("dataLnL", "genLnL", "tmrca", "numMigs", "topo", "rate")      # the series k_ess keeps per locus, in order
+ESS_COLUMNS = ("mean", "sd", "tauBatch", "essBatch", "tauAcf", "essAcf", "level", "truncated")
+
+
+def ess(x, max_lag=0, lib=None):
+    """gph_ess of the series x[S]: a dict of mean, sd, tauBatch, essBatch (the batch-sum levels read at the level with
+    batch <= sqrt(S)), tauAcf, essAcf (Geyer's initial positive sequence up to max_lag, 0: 2000), level, truncated.  ValueError
+    for fewer than two samples"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 1:
+        raise ValueError("gphocs_hip: ess takes x[S]")
+    o = (C.c_double * 8)()
+    rc = (lib or load_library()).gph_ess(x.ctypes.data_as(C.POINTER(C.c_double)), x.shape[0], int(max_lag), o)
+    if rc == -1:
+        raise ValueError("gphocs_hip: ess needs at least two samples (GPH_EARG)")
+    Sampler._chk(rc, "ess")
+    out = dict(zip(ESS_COLUMNS, list(o)))
+    out["level"], out["truncated"] = int(out["level"]), int(out["truncated"])
+    return out
+
+
+def ess_read(a, samples, level=-1, lib=None):
+    """gph_ess_read of one series' accumulators a[2 + 2 * 16] over `samples` samples: (mean, sd, tau, ess, level)"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    o = (C.c_double * 5)()
+    rc = (lib or load_library()).gph_ess_read(a.ctypes.data_as(C.POINTER(C.c_double)), int(samples), int(level), o)
+    if rc == -1:
+        raise ValueError("gphocs_hip: ess_read refused the sample count or the level (GPH_EARG)")
+    Sampler._chk(rc, "ess_read")
+    return o[0], o[1], o[2], o[3], int(o[4])
 
 
 def _dp(a):
@@ -1306,6 +1352,58 @@ class Sampler:
         ent = ent[:Q, :P]
         return dict(loci=loci[:Q].copy(), samples=S, slots=P, words=W, limit=lim, nkeys=nk[:Q].copy(), dropped=dr[:Q].copy(),
                     keys=ent[:, :, :W].copy(), cnt=ent[:, :, W].copy(), age=ent[:, :, W + 1].copy().view(np.float64))
+
+    # ---- effective sample sizes of selected loci (gph_engine_ess_*): accumulated on the device, one sample per call
+    def ess_enable(self, loci=None, max_bytes=0):
+        """the batch-sum levels of dataLnL, genLnL, tmrca, numMigs, topo (and rate under locus-mut-rate VAR) for the selected
+        loci (as enable_gene_trees; None: all loci of this rank).  ValueError for a refused selection, MemoryError when the
+        accumulators would exceed max_bytes (0: 1 GiB); the sampler stays usable"""
+        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
+        keep = sel if sel is None or len(sel) else np.zeros(1, dtype=np.int64)      # (a non-null pointer for an empty selection)
+        rc = self.lib.gph_engine_ess_enable(self.engine, None if sel is None else keep.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            0 if sel is None else len(sel), int(max_bytes))
+        if rc == GPH_EFULL:
+            raise MemoryError("gphocs_hip: the ESS accumulators exceed max_bytes (GPH_EFULL)")
+        if rc == -1:
+            raise ValueError("gphocs_hip: ess_enable refused the selection (GPH_EARG)")
+        self._chk(rc, "ess_enable")
+
+    def ess_sample(self):
+        """one sample of the current state into the accumulators"""
+        self._chk(self.lib.gph_engine_ess_sample(self.engine), "ess_sample")
+
+    def _ess_shape(self):
+        q, M, J, W, S = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self._chk(self.lib.gph_engine_ess_shape(self.engine, C.byref(q), C.byref(M), C.byref(J), C.byref(W), C.byref(S)), "ess_shape")
+        return q.value, M.value, J.value, W.value, S.value
+
+    def ess(self, reset=False, level=-1):
+        """the accumulators of this rank's Q selected loci as the device holds them and their read-out: a dict of loci[Q]
+        (global indices), samples, series (names, M of them), levels (J), words (W), acc (Q, M, 2 + 2J) float64, changes[Q]
+        uint32, focal (Q, n - 1, W) uint64, and the table -- mean, sd, tau, ess (Q, M) float64 and `level` (gph_ess_read of every
+        series at `level`, -1: batch <= sqrt(samples)) -- with min_ess[Q]: the smallest ess over the series that were not
+        constant (0 when all were).  reset=True zeroes everything and the sample count afterwards"""
+        Q, M, J, W, S = self._ess_shape()
+        if M == 0:
+            raise RuntimeError("gphocs_hip: ess: not enabled (GPH_ESTATE)")
+        loci = np.zeros(max(Q, 1), dtype=np.int64)
+        cnt = C.c_int64()
+        self._chk(self.lib.gph_engine_ess_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)), "ess_selected")
+        ni = max(self.pack.n - 1, 0)
+        acc = np.zeros((max(Q, 1), M, 2 + 2 * J), dtype=np.float64)
+        changes, focal = np.zeros(max(Q, 1), dtype=np.uint32), np.zeros((max(Q, 1), ni, W), dtype=np.uint64)
+        self._chk(self.lib.gph_engine_ess_fetch(self.engine, acc.ctypes.data, changes.ctypes.data, focal.ctypes.data if focal.size else None,
+                                                int(bool(reset))), "ess_fetch")
+        acc, changes, focal = acc[:Q], changes[:Q], focal[:Q]
+        tab = np.zeros((4, Q, M), dtype=np.float64)
+        used = ess_read(np.zeros(2 + 2 * J), S, level, self.lib)[4]
+        for q in range(Q):
+            for m in range(M):
+                tab[:, q, m] = ess_read(acc[q, m], S, level, self.lib)[:4]
+        moved = tab[1] > 0.0
+        min_ess = np.where(moved.any(axis=1), np.where(moved, tab[3], np.inf).min(axis=1), 0.0) if Q else np.zeros(0)
+        return dict(loci=loci[:Q].copy(), samples=S, series=ESS_SERIES[:M], levels=J, words=W, acc=acc.copy(), changes=changes.copy(),
+                    focal=focal.copy(), mean=tab[0], sd=tab[1], tau=tab[2], ess=tab[3], level=used, min_ess=min_ess)
 
     def hbm_bytes(self):
         b = C.c_double()

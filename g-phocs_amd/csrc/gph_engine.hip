@@ -29,6 +29,7 @@
 #include "gph_ancestry.h"
 #include "gph_genetrees.h"
 #include "gph_clades.h"
+#include "gph_ess.h"
 #include "gph_cladecmp.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
@@ -428,7 +429,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 21     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 22     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -532,6 +533,11 @@ struct gph_engine_state {
   // d_cmp: the rows of the last gph_engine_clades_compare this engine led ([nsel][GPH_CC_COLS], allocated by the first one)
   struct { uint64_t *d_ent = nullptr; uint32_t *d_hdr = nullptr; GphClShape shape = {}; SmSel sel;
            int64_t samples = 0; bool on = false; double *d_cmp = nullptr; } cl;
+  // effective sample sizes of selected loci (gph_ess.h): ONE buffer in selection order -- acc [nsel][M][GPH_ESS_WORDS] doubles,
+  // focal [nsel][n - 1][W] u64, prev [nsel] u64, changes [nsel] u32 (one buffer: a fetch is one copy and one synchronisation) --,
+  // the selected loci of this rank with their slots in HBM, samples since the accumulators were last zeroed
+  struct { char *d = nullptr; size_t o_focal = 0, o_prev = 0, o_changes = 0, bytes = 0; GphClShape shape = {}; SmSel sel;
+           int32_t M = 0; int64_t samples = 0, max_bytes = 0; bool on = false; } es;
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -752,7 +758,7 @@ static void dump_one_locus(const gph_engine *e, FILE *f, long long global_locus,
   }
 }
 
-extern "C" { static int clades_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables) */
+extern "C" { static int clades_zero(gph_engine *e); static int ess_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables and the ESS accumulators) */
 
 // after a host synchronisation: the error the stages recorded, the counters
 static int check_error(gph_engine *e)
@@ -933,6 +939,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   dev_free(e->gt.rows.d); dev_free(e->gt.sel.d_slot);
   dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp); dev_free(e->cl.sel.d_slot);
+  dev_free(e->es.d); dev_free(e->es.sel.d_slot);
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
   dev_free(e->d_red);
@@ -1197,6 +1204,13 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   { int rcz = acc_zero(e, e->ls.d, sizeof(double) * (size_t)e->ls.ncol * e->L); if (rcz) return rcz; }
   { int rcz = acc_zero(e, e->an.d_acc, sizeof(double) * (size_t)e->an.ncol * e->L); if (rcz) return rcz; }
   { int rcz = clades_zero(e); if (rcz) return rcz; }
+  if (e->es.on && e->es.M != (e->var_rates ? 6 : 5)) {       /* the rate series comes and goes with `locus-mut-rate VAR` */
+    std::vector<int64_t> sel = e->es.sel.loci;
+    sel.push_back(0);                                         /* (a non-null pointer for an empty selection too) */
+    int rce = gph_engine_ess_enable(e, sel.data(), (int64_t)sel.size() - 1, e->es.max_bytes);
+    if (rce) return rce;
+  }
+  { int rcz = ess_zero(e); if (rcz) return rcz; }
   int rc = launch_loci(e, 3, k_init, e->seedz, e->d_mutRate, e->init_predraws);
   if (!rc) rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -2921,6 +2935,118 @@ int gph_engine_clades_compare(gph_engine *const *engines, int32_t R, double min_
   sample_end(e, 20, 1, tms);
   if ((rc = compare_order_after(engines, R))) return rc;
   return pull_rows(e, rows, e->cl.d_cmp, sizeof(double) * GPH_CC_COLS * (size_t)nsel);
+}
+
+// ---- effective sample sizes of selected loci (gph_ess.h)
+static int ess_zero(gph_engine *e)
+{
+  if (!e->es.on) return 0;
+  e->es.samples = 0;
+  return acc_zero(e, e->es.d, e->es.bytes);
+}
+static void ess_free(gph_engine *e)
+{
+  dev_free(e->es.d);
+  e->es.d = nullptr;
+  sel_free(e->es.sel);
+  e->es.shape = GphClShape{};
+  e->es.o_focal = e->es.o_prev = e->es.o_changes = e->es.bytes = 0;
+  e->es.M = 0;
+  e->es.samples = 0;
+  e->es.on = false;
+}
+
+int gph_engine_ess_enable(gph_engine *e, const int64_t *loci, int64_t nloci, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (!sel_valid(loci, nloci)) return GPH_EARG;
+  SETDEV(e);
+  ess_free(e);
+  { int rcs = sel_alloc(e, e->es.sel, loci, nloci); if (rcs) return rcs; }
+  const size_t nsel = e->es.sel.loci.size();
+  GphClShape h;
+  gph_cl_shape(e->lay, 2, h);            /* (G, W and the LDS bytes of the climb; there is no table) */
+  const int M = e->var_rates ? 6 : 5, ni = e->cfg.n > 1 ? e->cfg.n - 1 : 0;
+  const size_t o_focal = nsel * (size_t)M * GPH_ESS_WORDS * 8, o_prev = o_focal + nsel * (size_t)ni * h.W * 8, o_changes = o_prev + nsel * 8,
+               bytes = o_changes + nsel * 4;
+  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
+  if ((int64_t)bytes > limit) {
+    fprintf(stderr, "gphocs_hip: ess: the accumulators need %lld bytes (%lld loci x (%d series x %d doubles + %d focal keys of %d words + 12)), the limit is %lld\n",
+            (long long)bytes, (long long)nsel, M, GPH_ESS_WORDS, ni, (int)h.W, (long long)limit);
+    ess_free(e);
+    return GPH_EFULL;
+  }
+  if (dev_alloc((void **)&e->es.d, bytes)) {
+    dev_clear_error();
+    e->es.d = nullptr;
+    ess_free(e);
+    return GPH_EHIP;
+  }
+  e->es.shape = h;
+  e->es.M = M;
+  e->es.max_bytes = max_bytes;
+  e->es.o_focal = o_focal; e->es.o_prev = o_prev; e->es.o_changes = o_changes; e->es.bytes = bytes;
+  e->es.on = true;
+  return ess_zero(e);
+}
+
+// one sample of the current state, queued on the engine's stream
+int gph_engine_ess_sample(gph_engine *e)
+{
+  if (!e || !e->initialized || !e->es.on) return GPH_ESTATE;
+  SETDEV(e);
+  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
+  const GphClShape &h = e->es.shape;
+  const int nsel = (int)e->es.sel.loci.size(), L = (int)e->L;
+  const int groups = (nsel + h.G - 1) / h.G;
+  if (groups > 0 && e->cfg.n > 1) {        /* (a rank without a selected locus launches nothing; one leaf has no clade) */
+    int tms;
+    { int rcb = sample_begin(e, 21, tms); if (rcb) return rcb; }
+    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_CL_THREADS, (size_t)gph_es_lds_bytes(e->lay, h), k_ess, e->lay, h, e->dev.pages,
+                            e->es.sel.d_slot, nsel, L, (int)e->es.M, (long long)e->es.samples, (double *)e->es.d,
+                            (uint64_t *)(e->es.d + e->es.o_focal), (uint64_t *)(e->es.d + e->es.o_prev), (uint32_t *)(e->es.d + e->es.o_changes));
+      if (rcl) return rcl; }
+    sample_end(e, 21, 1, tms);
+  }
+  e->es.samples++;
+  return 0;
+}
+
+int gph_engine_ess_shape(gph_engine *e, int64_t *selected, int32_t *series, int32_t *levels, int32_t *words, int64_t *samples)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->es.on;
+  if (selected) *selected = on ? (int64_t)e->es.sel.loci.size() : 0;
+  if (series) *series = on ? e->es.M : 0;
+  if (levels) *levels = on ? GPH_ESS_LEVELS : 0;
+  if (words) *words = on ? e->es.shape.W : 0;
+  if (samples) *samples = on ? e->es.samples : 0;
+  return 0;
+}
+
+int gph_engine_ess_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
+{
+  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
+  if (!e->es.on) return GPH_ESTATE;
+  return sel_copy_out(e->es.sel, out, max_loci, count);
+}
+
+// acc [selected][series][2 + 2 levels], changes [selected], focal [selected][n - 1][words] (changes / focal may be null)
+int gph_engine_ess_fetch(gph_engine *e, double *acc, uint32_t *changes, uint64_t *focal, int32_t reset)
+{
+  if (!e) return GPH_EARG;
+  if (!e->es.on) return GPH_ESTATE;
+  const size_t nsel = e->es.sel.loci.size();
+  if (nsel > 0 && !acc) return GPH_EARG;
+  SETDEV(e);
+  if (nsel > 0) {
+    std::vector<char> all(e->es.bytes);
+    { int rc = pull_rows(e, all.data(), e->es.d, e->es.bytes); if (rc) return rc; }
+    memcpy(acc, all.data(), e->es.o_focal);
+    if (focal) memcpy(focal, all.data() + e->es.o_focal, e->es.o_prev - e->es.o_focal);
+    if (changes) memcpy(changes, all.data() + e->es.o_changes, nsel * 4);
+  }
+  return reset ? ess_zero(e) : 0;
 }
 
 // ---- two engines exchange their chain states (Metropolis-coupled chains)

@@ -18,6 +18,7 @@
 #include <vector>
 #include "../../include/gphocs_hip.h"
 #include "gph_global.h"
+#include "gph_ess.h"       /* the estimator alone: gph_ess_add, gph_ess_read_, gph_ess_ */
 
 // the engine owns the chain state (host mirror + the copy in HBM the kernels and the k_global stages work on)
 extern "C" GphGlobal *gph_engine_global_(gph_engine *e);             /* mutable: marks the mirror for upload */
@@ -430,5 +431,8 @@ int gph_mcmc_accept_counts(gph_mcmc *m, int64_t *counts9)
 #include "gph_mc3.h"
 // ---- the potential scale reduction factor of a trace column over replicate chains
 #include "gph_psrf.h"
+// ---- effective sample sizes (gph_ess.h)
+int gph_ess_read(const double *a, int64_t S, int32_t level, double *out5) { return gph_ess_read_(a, S, level, out5); }
+int gph_ess(const double *x, int64_t S, int32_t max_lag, double *out8) { return gph_ess_(x, S, max_lag, out8); }
 
 } // extern "C"

@@ -934,6 +934,7 @@ struct Run {
   void trace_header(FILE *f) const;
   void trace_values(FILE *f, int it, const double *v, double logL, double dataL) const;
   void trace_line(int it);
+  void trace_kept(gph_mcmc *m, double *v, std::vector<double> &x, double &logL, double &dataL) const;
 };
 
 int Run::read_control()
@@ -1055,6 +1056,18 @@ void Run::trace_line(int it)
   gph_mcmc_param_vals(M, vals.data(), mc.numParameters);
   gph_mcmc_get_state(M, &logL, &dataL, nullptr, nullptr, nullptr);
   trace_values(trace, it, vals.data(), logL, dataL);
+}
+
+// what a trace line of chain m prints, kept before formatting (behind x: vals[i] * printFactors[i], then logL, then dataL; v:
+// scratch of numParameters doubles) -- the replicate chains' PSRF and the ESS table read these
+void Run::trace_kept(gph_mcmc *m, double *v, std::vector<double> &x, double &logL, double &dataL) const
+{
+  logL = dataL = 0;
+  gph_mcmc_param_vals(m, v, mc.numParameters);
+  gph_mcmc_get_state(m, &logL, &dataL, nullptr, nullptr, nullptr);
+  for (int i = 0; i < mc.numParameters; i++) x.push_back(v[i] * mc.printFactors[i]);
+  x.push_back(logL);
+  x.push_back(dataL);
 }
 
 // ---- `--mc3`: the heated chains next to the run's own
@@ -1474,6 +1487,9 @@ struct Clades : Output {
   void discard(int32_t ranks) override { gph_clades_discard(prefix, ranks); }
 };
 
+// ---- `--ess PREFIX [--ess-loci SPEC]`: effective sample sizes per trace column and per locus
+#include "gph_ess_run.h"
+
 // the enabled outputs in the order of their engine calls at a sample, which is also the order in which gph_run_finish writes
 // their files (the groups of fewer files first: should a later one fail, fewer are removed again).  A run closes them in the
 // opposite order, as it always did, and opens them in that order too: the summary is now enabled last, not first
@@ -1482,9 +1498,11 @@ struct Outputs {
   LocusSummary *summary = nullptr;   /* these two have a step of their own in run_chain */
   GeneTrees *trees = nullptr;
   Clades *clades = nullptr;
+  Ess *ess = nullptr;
   explicit Outputs(const gph_run_options &o)
   {
     if (o.locus_summary_path) list.emplace_back(summary = new LocusSummary);
+    if (o.ess_prefix) list.emplace_back(ess = new Ess(o));
     if (o.clades_prefix) list.emplace_back(clades = new Clades(o));
     if (o.gene_trees_prefix) list.emplace_back(trees = new GeneTrees(o));
     if (o.ancestry_prefix) list.emplace_back(new Ancestry(o));
@@ -1761,6 +1779,7 @@ int run_chain(const gph_run_options &o)
   if ((rc = R.read_loci())) return rc;
   if (outs.trees && (rc = outs.trees->select(R))) return rc;
   if (outs.clades && (rc = outs.clades->select(R))) return rc;
+  if (outs.ess && (rc = outs.ess->select(R))) return rc;
   if ((rc = R.start_engine()) || (rc = R.open_trace())) return rc;
   if (o.beta != 0.0) {
     if ((rc = gph_mcmc_set_beta(R.M, option_beta(o)))) return R.fail(rc, "gph_mcmc_set_beta");
@@ -1831,7 +1850,7 @@ int run_chain(const gph_run_options &o)
   if (rcr) return rcr;
   if (checked && where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h, 12 gph_ess.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
     return GPH_EKERNEL;
   }
   if (outs.summary && (rc = outs.summary->write_table(R))) return rc;
@@ -1839,6 +1858,88 @@ int run_chain(const gph_run_options &o)
   return ml && R.lead ? ml->write(R) : GPH_OK;
 }
 }   // namespace
+
+extern "C" int gph_ess_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  remove_parts(ES_PART, prefix, ranks);
+  for (const char *sfx : ES_FILES) unlink((std::string(prefix) + sfx).c_str());     /* (files only: whatever else sits there is not ours) */
+  return GPH_OK;
+}
+
+extern "C" int gph_ess_write(const char *prefix, int32_t ranks)
+{
+  if (!prefix || ranks < 1) return GPH_EARG;
+  FILE *out[2] = {nullptr, nullptr};
+  bool ok = true;
+  for (int k = 0; k < 2 && ok; k++)
+    if (!(out[k] = fopen((std::string(prefix) + ES_FILES[k]).c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s%s\n", prefix, ES_FILES[k]); ok = false; }
+  long long S = -1, level = -1, M = -1;
+  std::vector<std::pair<double, long long>> least;      /* minEss and locus of every row */
+  std::string params;                                   /* the summary line of PREFIX.ess.tsv */
+  for (int r = 0; r < ranks && ok; r++) {
+    const std::string path = part_path(ES_PART, prefix, r);
+    FILE *in = fopen(path.c_str(), "r");
+    char *line = nullptr;
+    size_t cap = 0;
+    ssize_t len;
+    long long rows = 0, told = -1;
+    int at = 0;
+    while (in && ok && (len = getline(&line, &cap, in)) > 0) {
+      at++;
+      if (at == 1) { ok = !strcmp(line, "GPHES1\n"); continue; }
+      if (at == 2) {
+        long long s = 0, j = 0, m = 0;
+        ok = sscanf(line, "H\t%lld\t%lld\t%lld", &s, &j, &m) == 3 && (S < 0 || (s == S && j == level && m == M)) && m >= 5 && m <= 6;
+        if (ok && S < 0) {
+          S = s; level = j; M = m;
+          fprintf(out[0], "param\tsamples\tmean\tsd\tessBatch\tessAcf\ttauAcf\ttruncated\n");
+          fprintf(out[1], "locus\tname\tsamples");
+          for (int k = 0; k < M; k++) fprintf(out[1], "\t%s", ES_SERIES[k]);
+          fprintf(out[1], "\ttopoChanges\tminEss\n");
+        }
+        continue;
+      }
+      if (told >= 0) { ok = false; break; }                      /* something behind the last line */
+      if (line[0] == 'E' && line[1] == '\t') { told = atoll(line + 2); continue; }
+      ok = len > 2 && line[1] == '\t' && (line[0] == 'P' || line[0] == 'L') && line[len - 1] == '\n' && (line[0] == 'L' || r == 0);
+      if (!ok) break;
+      rows++;
+      if (line[0] == 'P') {
+        fputs(line + 2, out[0]);
+        if (line[2] == '#') params.assign(line + 4, (size_t)len - 5);
+        continue;
+      }
+      char *end = nullptr;
+      const double v = strtod(line + 2, &end);
+      ok = end && *end == '\t';
+      if (ok) { least.emplace_back(v, atoll(end + 1)); fputs(end + 1, out[1]); }
+    }
+    free(line);
+    if (in) fclose(in);
+    if (!in || !ok || at < 2 || told != rows) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); ok = false; }
+  }
+  if (ok) {
+    std::vector<double> v;
+    double lo = 0.0;
+    long long lo_at = -1;
+    for (const auto &p : least) { v.push_back(p.first); if (lo_at < 0 || p.first < lo) { lo = p.first; lo_at = p.second; } }
+    std::sort(v.begin(), v.end());
+    const size_t Q = v.size();
+    const double median = Q == 0 ? 0.0 : Q % 2 ? v[Q / 2] : (v[Q / 2 - 1] + v[Q / 2]) / 2.0;
+    char loci[256];
+    snprintf(loci, sizeof loci, "loci %lld level %lld batch %lld medianMinEss %.10g minMinEss %.10g (locus %lld)", (long long)Q, level, 1ll << level, median, lo, lo_at);
+    fprintf(out[1], "# %s\n", loci);
+    printf("ESS: %s; %s\n", params.c_str(), loci);
+    fflush(stdout);
+  }
+  for (int k = 0; k < 2; k++)
+    if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s%s failed\n", prefix, ES_FILES[k]); ok = false; }
+  remove_parts(ES_PART, prefix, ranks);
+  if (!ok)
+    for (int k = 0; k < 2; k++) if (out[k]) remove((std::string(prefix) + ES_FILES[k]).c_str());
+  return ok ? GPH_OK : GPH_EARG;
+}
 
 extern "C" int gph_run_finish(const gph_run_options *in, int32_t ranks, int32_t failed)
 {
@@ -1867,7 +1968,7 @@ extern "C" int gph_run(const gph_run_options *in)
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
   /* the checks on the options alone, before anything is read */
   int rc;
-  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
+  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = Ess::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
       (rc = Replicates::validate(o))) return rc;
   rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "../../include/gphocs_hip.h"
+#include "gph_ess.h"       /* the estimator alone: gph_ess_ (the stand-alone tool has no library to call) */
 
 namespace {
 
@@ -143,14 +144,62 @@ int summarize(const char *path, int blockSize, int discard, Out &out, std::strin
   return 0;
 }
 
-}  // namespace
-
-extern "C" int gph_read_trace(const char *trace_file, int block_size, int discard, char *out, size_t out_cap,
-                              size_t *out_len, char *err, size_t err_cap)
+// `--ess`: the table of PREFIX.ess.tsv (gph_run_options) for any trace file -- the first column is dropped, the values are
+// parsed as doubles, every column goes through gph_ess with max_lag 0
+int ess_table(const char *path, int discard, Out &out, std::string &err)
 {
-  Out o;
-  std::string e;
-  int rc = summarize(trace_file, block_size, discard, o, e);
+  FILE *f = fopen(path, "r");
+  if (!f) { err = std::string("Could not find trace file '") + path + "' specified.\n"; return 1; }
+  std::string line, header;
+  bool eofh;
+  if (!next_line(f, header, eofh)) { fclose(f); err = "Unable to get the first line of the trace file.\n"; return -1; }
+  if (!header.empty() && header.back() == '\n') header.back() = ' ';
+  std::vector<std::string> names, tok;
+  split(header, names);
+  if (names.empty()) { fclose(f); err = "Unable to get the first line of the trace file.\n"; return -1; }
+  names.erase(names.begin());
+  const int numCols = (int)names.size();
+  std::vector<std::vector<double>> col((size_t)numCols);
+  int numLines = 0;
+  while (next_line(f, line, eofh)) {
+    if (eofh) break;                       /* a last line without its newline is not a sample */
+    if (numLines++ < discard) continue;
+    line.pop_back();
+    split(line, tok);
+    if ((int)tok.size() < numCols + 1) { fclose(f); err = "A trace line has fewer columns than the header.\n"; return -1; }
+    for (int c = 0; c < numCols; c++) col[(size_t)c].push_back(strtod(tok[(size_t)c + 1].c_str(), nullptr));
+  }
+  fclose(f);
+  if (discard >= numLines) {
+    char b[160];
+    snprintf(b, sizeof b, "%d lines specified to discard, but trace file contains only %d lines.\n", discard, numLines);
+    err = b;
+    return 1;
+  }
+  const long long S = numLines - (discard > 0 ? discard : 0);
+  int level = 0;
+  while (level + 1 < GPH_ESS_LEVELS && (1ll << (2 * (level + 1))) <= S) level++;
+  char tmp[512];
+  out.put("param\tsamples\tmean\tsd\tessBatch\tessAcf\ttauAcf\ttruncated\n");
+  double worst = 0.0;
+  int worst_at = -1;
+  for (int c = 0; c < numCols; c++) {
+    double o8[8] = {col[(size_t)c][0], 0, 0, 0, 0, 0, (double)level, 0};
+    if (S >= 2 && gph_ess_(col[(size_t)c].data(), S, 0, o8)) { err = "gph_ess refused a column.\n"; return -1; }
+    snprintf(tmp, sizeof tmp, "\t%lld\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\t%d\n", S, o8[0], o8[1], o8[3], o8[5], o8[4], (int)o8[7]);
+    out.put(names[(size_t)c].c_str());
+    out.put(tmp);
+    if (o8[1] > 0.0 && (worst_at < 0 || o8[5] < worst)) { worst = o8[5]; worst_at = c; }
+  }
+  snprintf(tmp, sizeof tmp, "# samples %lld level %d batch %lld minEssAcf %.10g (", S, level, 1ll << level, worst);
+  out.put(tmp);
+  out.put(worst_at < 0 ? "-" : names[(size_t)worst_at].c_str());
+  out.put(")\n");
+  return 0;
+}
+
+int hand_out(int rc, const Out &o, const std::string &e, char *out, size_t out_cap, size_t *out_len, char *err, size_t err_cap)
+{
   if (out_len) *out_len = o.s.size();
   if (out && out_cap) {
     size_t n = o.s.size() < out_cap - 1 ? o.s.size() : out_cap - 1;
@@ -166,12 +215,33 @@ extern "C" int gph_read_trace(const char *trace_file, int block_size, int discar
   return rc;
 }
 
+}  // namespace
+
+extern "C" int gph_read_trace_ess(const char *trace_file, int discard, char *out, size_t out_cap, size_t *out_len, char *err, size_t err_cap)
+{
+  Out o;
+  std::string e;
+  const int rc = ess_table(trace_file, discard, o, e);
+  return hand_out(rc, o, e, out, out_cap, out_len, err, err_cap);
+}
+
+extern "C" int gph_read_trace(const char *trace_file, int block_size, int discard, char *out, size_t out_cap,
+                              size_t *out_len, char *err, size_t err_cap)
+{
+  Out o;
+  std::string e;
+  int rc = summarize(trace_file, block_size, discard, o, e);
+  return hand_out(rc, o, e, out, out_cap, out_len, err, err_cap);
+}
+
 #ifdef GPH_READTRACE_MAIN
 // readTrace <trace-file-name> [-b SIZE] [-d NUMBER] [-h]     (readTrace.c:14-39, 57-102)
+// readTrace <trace-file-name> --ess [-d NUMBER]              the effective sample size of every column instead
 static void print_help()
 {
   printf("-b, --block-size  SIZE     Blocksize\n");
   printf("-d, --discard  NUMBER      Number of samples from to discard from beginning of file\n");
+  printf("    --ess                  Effective sample sizes per column instead of block means\n");
   printf("-h, --help                 This help page\n");
 }
 static void print_usage(const char *a0)
@@ -182,6 +252,7 @@ static void print_usage(const char *a0)
 int main(int argc, char **argv)
 {
   int block = -1, discard = 0;
+  bool ess = false;
   const char *file = nullptr;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -196,6 +267,7 @@ int main(int argc, char **argv)
     else if (a.rfind("--discard=", 0) == 0) discard = atoi(a.c_str() + 10);
     else if (a.rfind("-d", 0) == 0 && a.size() > 2) discard = atoi(a.c_str() + 2);
     else if (a == "-s" || a == "--sub-sampling" || a == "-t") (void)need("s");   /* accepted and ignored upstream */
+    else if (a == "--ess") ess = true;
     else if (a == "-h" || a == "--help") { print_usage(argv[0]); print_help(); return 0; }
     else if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "Unknown option `%s'.\n", a.c_str()); return 1; }
     else if (!file) file = argv[i];
@@ -207,9 +279,11 @@ int main(int argc, char **argv)
   }
   size_t len = 0;
   char errb[512] = "";
-  gph_read_trace(file, block, discard, nullptr, 0, &len, errb, sizeof errb);
+  if (ess) gph_read_trace_ess(file, discard, nullptr, 0, &len, errb, sizeof errb);
+  else gph_read_trace(file, block, discard, nullptr, 0, &len, errb, sizeof errb);
   std::vector<char> buf(len + 1);
-  int rc = gph_read_trace(file, block, discard, buf.data(), buf.size(), &len, errb, sizeof errb);
+  int rc = ess ? gph_read_trace_ess(file, discard, buf.data(), buf.size(), &len, errb, sizeof errb)
+               : gph_read_trace(file, block, discard, buf.data(), buf.size(), &len, errb, sizeof errb);
   if (rc != 0) {
     fputs(errb, stderr);
     if (rc == 1 && strstr(errb, "Could not find")) print_usage(argv[0]);

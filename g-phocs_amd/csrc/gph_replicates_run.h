@@ -99,13 +99,8 @@ struct Replicates {
   {
     for (int c = 0; c < C; c++) {
       double logL = 0, dataL = 0;
-      gph_mcmc *m = G.all[(size_t)c];
-      gph_mcmc_param_vals(m, vals.data(), R.mc.numParameters);
-      gph_mcmc_get_state(m, &logL, &dataL, nullptr, nullptr, nullptr);
+      R.trace_kept(G.all[(size_t)c], vals.data(), x[(size_t)c], logL, dataL);
       if (c > 0) R.trace_values(trace[(size_t)c - 1], it, vals.data(), logL, dataL);
-      for (int i = 0; i < R.mc.numParameters; i++) x[(size_t)c].push_back(vals[i] * R.mc.printFactors[i]);
-      x[(size_t)c].push_back(logL);
-      x[(size_t)c].push_back(dataL);
       if (clades && c > 0)
         if (int rc = gph_engine_clades_sample(G.E[(size_t)c - 1])) return R.fail(rc, "gph_engine_clades_sample of a replicate chain");
     }

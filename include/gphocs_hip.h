@@ -221,7 +221,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * (gph_engine_time_slices_sample: k_time_slices + k_rows_fold together), 16 migration ancestry
  * (gph_engine_ancestry_sample: k_ancestry), 17 sampled genealogies (gph_engine_gene_trees_sample: k_gene_trees), 18 the
  * sweep's draws generated ahead of it (k_rng_ahead), 19 clade tables (gph_engine_clades_sample: k_clades), 20 the clade
- * tables of replicate chains compared (gph_engine_clades_compare: k_clades_compare, counted on engines[0]) */
+ * tables of replicate chains compared (gph_engine_clades_compare: k_clades_compare, counted on engines[0]), 21 effective
+ * sample sizes per locus (gph_engine_ess_sample: k_ess) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -474,6 +475,55 @@ int gph_engine_clades_compare(gph_engine *const *engines, int32_t R, double min_
  *   out = {mean M, sdWithin sqrt(Wv), sdBetween sqrt(Bn), psrf sqrt(V / Wv)};  Wv == 0: psrf = 1 if Bn == 0, else +inf
  * R < 2, S < 2 or a null pointer: GPH_EARG. */
 int gph_psrf(const double *x /* [R][S] */, int32_t R, int64_t S, double *out /* mean, sdWithin, sdBetween, psrf */);
+/* EFFECTIVE SAMPLE SIZES.  One estimator, two users (csrc/gph_ess.h): the batch-sum LEVELS of a series, kept by binary carry.
+ * J = 16 levels; a series x_0 .. x_S-1 owns a[2 + 2J] doubles: a[0] = shift = x_0, a[1] = s1, a[2 + j] = run[j] (run[0] stays
+ * 0), a[2 + J + j] = sq[j].  Sample t (0-based) brings d = x_t - shift (t = 0: every word is zeroed first, d = 0); plain
+ * uncontracted fp64 in this order (a loop in the same order reproduces every bit):
+ *   s1 = s1 + d;  sq[0] = sq[0] + d * d;  carry = d;
+ *   for j = 1 .. J - 1:  run[j] = run[j] + carry;  if ((t + 1) mod 2^j != 0) stop;
+ *                        carry = run[j];  sq[j] = sq[j] + carry * carry;  run[j] = 0;
+ * so sq[j] is the sum of squares of the completed batch sums of 2^j consecutive samples.
+ * gph_ess_read(a, S, level, out5), host: with b = 2^j, nb = floor(S / b),
+ *   T = s1 - (((run[1] + run[2]) + ...) + run[j])   (j = 0: T = s1)
+ *   vx = (sq[0] - s1 * s1 / S) / (S - 1)            vb = (sq[j] - T * T / nb) / (nb - 1)
+ *   mean = shift + s1 / S     sd = sqrt(max(vx, 0))
+ *   vx <= 0 (the series never changed): tau = 0 and ess = 0 -- a stuck series does not read as perfectly mixed;
+ *   else tau = vb / (b * vx) (0 with fewer than two batches), ess = S / tau capped at S, tau <= 0: ess = S.
+ * level < 0: j* = the largest j < J with 4^j <= S (b <= sqrt(S)).  S < 2: sd = tau = ess = 0 (S = 0: mean = 0 too).
+ * out5 = mean, sd, tau, ess, the level used.  GPH_EARG: a null pointer, S < 0, level >= J.
+ * gph_ess(x, S, max_lag, out8), host: the levels of x by the rule above read at j*, and the autocorrelation estimate (Geyer's
+ * initial positive sequence, no monotone adjustment): d_t = x_t - x_0 (d_0 = 0), m = s1 / S, e_t = d_t - m,
+ *   c_k = (sum_{t = k}^{S - 1} e_t * e_{t - k}, added from 0.0 with t ascending) / S
+ *   Kmax = min(S - 2, max_lag), max_lag <= 0: 2000;  G_i = c_{2i} + c_{2i+1}, computed as the sum reaches them
+ *   sum = G_0 (always taken); for i = 1, 2, ..: 2i + 1 > Kmax: truncated = 1, stop; G_i <= 0: stop; sum = sum + G_i
+ *   c_0 = 0: tauAcf = essAcf = 0; else tauAcf = 2 * sum / c_0 - 1, essAcf = S / tauAcf capped at S, tauAcf <= 0: essAcf = S
+ * out8 = mean, sd, tauBatch, essBatch, tauAcf, essAcf, level, truncated.  S < 2 or a null pointer: GPH_EARG. */
+int gph_ess_read(const double *a /* [2 + 2 * 16] */, int64_t S, int32_t level, double *out5);
+int gph_ess(const double *x, int64_t S, int32_t max_lag, double *out8);
+/* ... PER SELECTED LOCUS, accumulated on the device over the samples taken (k_ess: csrc/gph_ess.h; timing class 21).  Per
+ * locus M = 5 series, + 1 under `locus-mut-rate VAR`, in this order: dataLnL, genLnL, tmrca (age[root]), numMigs (clamped to
+ * 0 .. GPH_GT_MAX_MIGS as a gene-tree record clamps it), topo, rate.  topo: at the first sample since the accumulators were
+ * zeroed the n - 1 clade keys of the locus (W = ceil(n / 64) words each, as for the clade tables), in node-index order, are
+ * stored as its FOCAL SET; x_topo of a sample = the number of internal nodes of the current tree whose clade is in the focal
+ * set (1 .. n - 1, n - 1 at the first sample): the distance-to-a-focal-tree series of Lanfear et al. 2016, its ESS the
+ * topological ESS.  changes[q] counts the samples t >= 1 whose clade set differs from that of sample t - 1, decided by a 64-bit
+ * hash of the set (the sum of the clades' hashes): two different sets collide with probability about 2^-64.
+ * Device memory per selected locus: M (2 + 2J) doubles, (n - 1) W + 1 64-bit words and one 32-bit word (1.5 KB at 16 leaves).
+ *   _enable   the selection as for gph_engine_gene_trees_enable (loci NULL: all loci of the rank); GPH_EFULL, with a message and
+ *             nothing allocated, above max_bytes (<= 0: 1 GiB); GPH_ESTATE before the loci are loaded.  Enabling again frees
+ *             and starts over.  gph_engine_init_genealogies zeroes the accumulators and the sample count.
+ *   _sample   one kernel on the engine's stream, no host synchronisation; a rank without a selected locus launches nothing
+ *             and still counts the sample.  GPH_ESTATE when not enabled or before gph_engine_init_genealogies.
+ *   _shape    selected loci of the rank, M, J, W, samples since the accumulators were zeroed (all 0 while off)
+ *   _selected as gph_engine_gene_trees_selected
+ *   _fetch    acc[selected][M][2 + 2J] (levels as above), changes[selected], focal[selected][n - 1][W] (either may be NULL),
+ *             one copy and ONE host synchronisation; reset != 0 zeroes everything and the sample count afterwards.
+ * The kernel writes no page, draws no random number and touches no chain state. */
+int gph_engine_ess_enable(gph_engine *e, const int64_t *loci, int64_t nloci, int64_t max_bytes);
+int gph_engine_ess_sample(gph_engine *e);
+int gph_engine_ess_shape(gph_engine *e, int64_t *selected, int32_t *series, int32_t *levels, int32_t *words, int64_t *samples);
+int gph_engine_ess_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_ess_fetch(gph_engine *e, double *acc /* [selected][series][2 + 2 levels] */, uint32_t *changes, uint64_t *focal, int32_t reset);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -666,7 +716,7 @@ int gph_run_control_file_comm(const char *ctl_path, const char *secondary_ctl_pa
  * Every output takes its sample wherever a trace line is written (never in the burn-in), into a device buffer of <rows>
  * rows; whenever that buffer is full, and at the end, rank r appends the rows to a binary part file PREFIX.<kind>.part<r>.
  * gph_run_finish(o, ranks, failed), called once after the last rank has returned, makes the files of the parts and removes
- * the parts (failed == 0: gph_clades_write, gph_gene_trees_write, gph_ancestry_write, gph_time_slices_write, gph_coal_stats_write, in this
+ * the parts (failed == 0: gph_ess_write, gph_clades_write, gph_gene_trees_write, gph_ancestry_write, gph_time_slices_write, gph_coal_stats_write, in this
  * order; everything is discarded at the first failure) or only discards, parts and files.  A one-rank run calls it itself.
  * Either way a run that did not finish leaves neither parts nor files, and a part that is missing, damaged or was not
  * closed by its rank is an error.  The outputs compose freely. */
@@ -811,6 +861,25 @@ typedef struct gph_run_options {
   const char *replicates_prefix;
   double replicates_min_freq;
   int32_t replicates_every;
+  /* `--ess PREFIX [--ess-loci SPEC]`: effective sample sizes, of every trace column and of every selected locus (gph_ess,
+   * gph_engine_ess_* above).  A sample is taken wherever a trace line is written.  ess_loci as gene_trees_loci (an index named
+   * twice or >= the number of loci is refused by name before the first iteration); ess_loci without ess_prefix is GPH_EARG
+   * before anything is read.  The values every trace line prints are kept on the host before formatting (vals[i] *
+   * printFactors[i], then the two log-likelihood columns) and the per-locus levels stay on the device during the run; rank r
+   * writes its part PREFIX.ess.part<r> once, at the end.  gph_ess_write makes of the parts (numbers "%.10g")
+   *   PREFIX.ess.tsv        (rank 0's) header param samples mean sd essBatch essAcf tauAcf truncated; one row per trace column
+   *                         in trace order, named as the trace header names it (gph_ess with max_lag 0; fewer than two
+   *                         samples: zeros); last line "# samples S level j batch b minEssAcf v (<param>)", the minimum over
+   *                         the columns that were not constant ("-" and 0 when all were)
+   *   PREFIX.locus-ess.tsv  header locus name samples essDataLnL essGenLnL essTmrca essNumMigs essTopo [essRate] topoChanges
+   *                         minEss; one row per selected locus in sequence-file order, the ranks' rows concatenated in rank
+   *                         order; ESS = gph_ess_read at the level with batch <= sqrt(samples); minEss over the series that
+   *                         were not constant, 0 when all were; last line
+   *                         "# loci Q level j batch b medianMinEss v minMinEss v (locus <i>)" (the median of an even number of
+   *                         rows is the mean of the two in the middle; no row: 0 0 (locus -1))
+   * and prints both summary lines as one line "ESS: ...; ..." on stdout.  With mc3_chains, replicates and marginal_prefix the
+   * files describe chain 0 and the run proper, as the clade tables do; every other output is the same bytes with and without. */
+  const char *ess_prefix, *ess_loci;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
@@ -830,6 +899,8 @@ int gph_gene_trees_write(const char *prefix, int32_t ranks);
 int gph_gene_trees_discard(const char *prefix, int32_t ranks);
 int gph_clades_write(const char *prefix, int32_t ranks);
 int gph_clades_discard(const char *prefix, int32_t ranks);
+int gph_ess_write(const char *prefix, int32_t ranks);
+int gph_ess_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
  * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
  * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
@@ -876,6 +947,11 @@ int gph_clades_consensus(int32_t n, int32_t slots, const uint64_t *entries, int6
  * code on error, or 2 when out_cap was too small. */
 int gph_read_trace(const char *trace_file, int block_size, int discard, char *out, size_t out_cap, size_t *out_len,
                    char *err, size_t err_cap);
+/* `readTrace <trace-file> --ess [-d N]`: the table of PREFIX.ess.tsv (gph_run_options: ess_prefix) for any trace file -- the
+ * reference's own, a chain<r>.trace -- its summary line included: the first column is dropped, the first N samples are
+ * discarded, the values are parsed as doubles and every column goes through gph_ess with max_lag 0.  Buffers and status as
+ * gph_read_trace. */
+int gph_read_trace_ess(const char *trace_file, int discard, char *out, size_t out_cap, size_t *out_len, char *err, size_t err_cap);
 
 #ifdef __cplusplus
 }
