@@ -356,7 +356,7 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_exchange_state", "gph_mcmc_exchange_state", "gph_mc3_create", "gph_mc3_destroy", "gph_mc3_iteration",
     "gph_mc3_swap_counts", "gph_mc3_swap_log", "gph_engine_clades_compare", "gph_psrf",
     "gph_ess", "gph_ess_read", "gph_engine_ess_enable", "gph_engine_ess_sample", "gph_engine_ess_shape", "gph_engine_ess_selected",
-    "gph_engine_ess_fetch", "gph_ess_write", "gph_ess_discard", "gph_read_trace_ess",
+    "gph_engine_ess_fetch", "gph_ess_write", "gph_ess_discard", "gph_read_trace_ess", "gph_engine_last_error_text",
 ]
 
 
@@ -399,6 +399,8 @@ def _load_library(path):
     lib.gph_mcmc_dump_state.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     lib.gph_engine_dump_loci.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32]
     lib.gph_engine_last_error.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gph_engine_last_error_text.argtypes = [C.c_void_p]
+    lib.gph_engine_last_error_text.restype = C.c_char_p
     lib.gph_engine_debug_break_chain.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
     lib.gph_mcmc_set_record_file.argtypes = [C.c_void_p, C.c_char_p]
     lib.gph_engine_last_kernel_ms.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
@@ -1008,9 +1010,16 @@ class Sampler:
         cn = np.ascontiguousarray(p.counts[o0:o1])
         rates = np.ascontiguousarray(p.mutRates[b:e], dtype=np.float64)
         use_rates = bool(np.any(rates != 1.0))
-        self._chk(self.lib.gph_engine_load_loci(self.engine, e - b, offs.ctypes.data, leaf.ctypes.data,
-                                                ph.ctypes.data, cn.ctypes.data,
-                                                rates.ctypes.data if use_rates else None), "load_loci")
+        rc = self.lib.gph_engine_load_loci(self.engine, e - b, offs.ctypes.data, leaf.ctypes.data, ph.ctypes.data, cn.ctypes.data,
+                                           rates.ctypes.data if use_rates else None)
+        if rc != 0:
+            # a refused data set (include/gphocs_hip.h: GPH_LOAD_*): the engine goes, the refusal stays readable
+            self.load_error = self.last_error() + (self.lib.gph_engine_last_error_text(self.engine).decode(),)
+            self.lib.gph_engine_destroy(self.engine)
+            self.engine = None
+            err = RuntimeError(f"gphocs_hip: load_loci failed with status {rc}: {self.load_error[2]}")
+            err.locus, err.code, err.text = self.load_error
+            raise err
         k.update(ta=p.thetaAlpha, tb=p.thetaBeta, ts=p.thetaStart, aa=p.ageAlpha, ab=p.ageBeta,
                  as_=p.ageStart, sa=p.sampleAge, ma=p.mrAlpha, mb=p.mrBeta, ft=p.ftTaus, pf_=p.printFactors,
                  usa=np.ascontiguousarray(getattr(p, "updateSampleAge", np.zeros(p.K, np.int32)), dtype=np.int32))

@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <stddef.h>
+#include <stdarg.h>
 #include <string.h>
 #include <vector>
 #include <string>
@@ -461,6 +462,7 @@ struct gph_engine_state {
   int64_t n_huge = 0;                // loci whose sequence block stays in HBM (the first slots)
   int32_t last_error_code = 0;       // the last fatal error check_error reported (gph_engine_last_error)
   long long last_error_locus = -1;
+  char last_error_text[288] = "";    // the line a refused gph_engine_load_loci printed (gph_engine_last_error_text)
   bool in_error_dump = false;
   int64_t L = 0;
   size_t cond_bytes = 0, pages_bytes = 0, seq_bytes_total = 0;
@@ -987,20 +989,79 @@ int gph_engine_get_beta(gph_engine *e, double *beta)
   return 0;
 }
 
+// What gph_engine_load_loci accepts (include/gphocs_hip.h says it to the caller).  The first violation is refused with GPH_EARG and
+// a line on stderr that names the locus (global index) and the pattern (row of the locus); gph_engine_last_error then returns that
+// locus with one of the GPH_LOAD_* codes, gph_engine_last_error_text the line.  The sizes of ALL loci are judged first, from
+// the offsets alone: a caller whose offsets are wrong is told so before a row is read.
+static int refuse_loci(gph_engine *e, int64_t g, int32_t code, const char *fmt, ...)
+{
+  char what[160];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(what, sizeof what, fmt, ap);
+  va_end(ap);
+  e->last_error_locus = (long long)e->cfg.locus_begin + g;
+  e->last_error_code = code;
+  snprintf(e->last_error_text, sizeof e->last_error_text, "gphocs_hip: gph_engine_load_loci: locus %lld: %s", e->last_error_locus, what);
+  fprintf(stderr, "%s\n", e->last_error_text);
+  return GPH_EARG;
+}
+
+static int check_loci(gph_engine *e, int64_t L, const int64_t *poff, const uint8_t *leafcodes, const uint16_t *numPhases, const int32_t *counts)
+{
+  const int n = e->cfg.n;
+  const int64_t lim = (int64_t)1 << 31;
+  /* the device code indexes a locus's conditionals ((half * (n - 1) + node - n) * P + p) * 4 + base and its sequence block with
+   * 32-bit integers */
+  for (int64_t g = 0; g < L; g++) {
+    const int64_t P = poff[g + 1] - poff[g];
+    if (P < 0) return refuse_loci(e, g, GPH_LOAD_SIZE, "pattern_offsets decrease (%lld patterns)", (long long)P);
+    if (P >= lim || (int64_t)8 * (n - 1) * P >= lim || (int64_t)GPH_Q_BYTES(P, (int64_t)n, 1) >= lim)     /* (the block with 16-bit counts: the smaller form; load_loci judges the other once it knows the form) */
+      return refuse_loci(e, g, GPH_LOAD_SIZE, "%lld phased patterns at %d leaves: 8 (n - 1) P or the sequence block reaches 2^31", (long long)P, n);
+  }
+  for (int64_t g = 0; g < L; g++) {
+    const int64_t P = poff[g + 1] - poff[g], r0 = poff[g];
+    for (int64_t p = 0; p < P; ) {
+      const int w = numPhases[r0 + p];
+      if (w == 0) return refuse_loci(e, g, GPH_LOAD_NO_GROUP, "pattern %lld: phase word 0 on a row that belongs to no group of phases", (long long)p);
+      if (w >= GPH_PHASES_ENCODE_MIN && ((w & 0x7fff) < 15 || (w & 0x7fff) > 24))
+        return refuse_loci(e, g, GPH_LOAD_WORD, "pattern %lld: phase word 0x%04x is no count (0x8000 | exponent takes exponents 15 .. 24)", (long long)p, w);
+      const int64_t k = GPH_PHASES(w);
+      if (k > P - p) return refuse_loci(e, g, GPH_LOAD_OVERRUN, "pattern %lld: %lld phases run past the locus's last row (%lld patterns)", (long long)p, (long long)k, (long long)P);
+      if (counts[r0 + p] < 0) return refuse_loci(e, g, GPH_LOAD_COUNT, "pattern %lld: negative count %d", (long long)p, (int)counts[r0 + p]);
+      for (int64_t q = p + 1; q < p + k; q++)
+        if (numPhases[r0 + q] != 0 || counts[r0 + q] != 0)
+          return refuse_loci(e, g, GPH_LOAD_INSIDE, "pattern %lld: phase word 0x%04x and count %d inside the %lld phases of pattern %lld (both are 0 there)",
+                             (long long)q, (int)numPhases[r0 + q], (int)counts[r0 + q], (long long)k, (long long)p);
+      p += k;
+    }
+    for (int64_t p = 0; p < P; p++)
+      for (int i = 0; i < n; i++)
+        if (leafcodes[(size_t)(r0 + p) * n + i] > 4)
+          return refuse_loci(e, g, GPH_LOAD_LEAF, "pattern %lld: leaf code %d of sample %d (0 .. 3 = T C A G, 4 = N)", (long long)p, (int)leafcodes[(size_t)(r0 + p) * n + i], i);
+  }
+  return 0;
+}
+
 int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *poff, const uint8_t *leafcodes,
                          const uint16_t *numPhases, const int32_t *counts, const double *mutRates)
 {
   if (!e || L <= 0 || !poff || !leafcodes || !numPhases || !counts) return GPH_EARG;
   if (e->loaded) { fprintf(stderr, "gphocs_hip: gph_engine_load_loci called twice on one engine\n"); return GPH_ESTATE; }
+  { int rcv = check_loci(e, L, poff, leafcodes, numPhases, counts); if (rcv) return rcv; }      /* before anything is allocated */
   SETDEV(e);
   const int n = e->cfg.n;
   int Pmax = 1;
-  for (int64_t g = 0; g < L; g++) { int P = (int)(poff[g + 1] - poff[g]); if (P > Pmax) Pmax = P; if (P < 0) return GPH_EARG; }   /* P == 0: a locus with no informative column (all N) is legal upstream */
+  for (int64_t g = 0; g < L; g++) { int P = (int)(poff[g + 1] - poff[g]); if (P > Pmax) Pmax = P; }   /* P == 0: a locus with no informative column (all N) is legal upstream */
   /* pattern counts as 16-bit words when every count of the data set allows it (a count is at most the length of its
    * locus): 2 bytes per pattern of every resident sequence block */
   int cnt16 = 1;
   for (int64_t i = 0; i < poff[L]; i++) if (counts[i] < 0 || counts[i] > 65535) { cnt16 = 0; break; }
   if (const char *ov = getenv("GPH_CNT16")) cnt16 = cnt16 && atoi(ov) != 0;     /* tests: the 32-bit form */
+  if (!cnt16)       /* (check_loci judged the block with 16-bit counts; with 32-bit counts it is the larger limit only where n == 1) */
+    for (int64_t g = 0; g < L; g++)
+      if ((int64_t)GPH_Q_BYTES(poff[g + 1] - poff[g], (int64_t)n, 0) >= ((int64_t)1 << 31))
+        return refuse_loci(e, g, GPH_LOAD_SIZE, "%lld phased patterns at %d leaves: the sequence block reaches 2^31", (long long)(poff[g + 1] - poff[g]), n);
   build_layout(e->lay, n, e->cfg.Kc, e->cfg.K, e->cfg.B, e->cfg.rootPop, Pmax, cnt16);
   /* A locus whose sequence block does not fit the LDS budget of a launch group keeps it in HBM ("huge": its own launch
    * group, the generic (pattern, base) paths read the block through GphSeq -- gph_rt.h; the reference mallocs any P,
@@ -1113,7 +1174,6 @@ int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *poff, const ui
     for (int p = 0; p < P; p++) {
       for (int i = 0; i < n; i++) {
         uint8_t c = leafcodes[(size_t)(poff[g] + p) * n + i];
-        if (c > 4) return GPH_EARG;
         blk[GPH_Q_LEAF + p * GPH_Q_NH(n) + (i >> 1)] |= (char)(c << ((i & 1) << 2));
       }
       ((uint16_t *)(blk + GPH_Q_PHASES(P, n)))[p] = numPhases[poff[g] + p];
@@ -2151,6 +2211,8 @@ int gph_engine_last_error(gph_engine *e, int64_t *locus, int32_t *code)
   if (code) *code = e->last_error_code;
   return 0;
 }
+
+const char *gph_engine_last_error_text(gph_engine *e) { return e ? e->last_error_text : ""; }
 
 // tests only: break the event chain of population `pop` of one locus (the `next` link of its first event becomes -1), so
 // that the next kernel's bounded chain walks raise a fatal code for exactly that locus (tests/test_host_logic.py,

@@ -139,10 +139,33 @@ int gph_engine_set_allreduce(gph_engine *e, gph_allreduce_fn fn, void *user);
 int gph_engine_set_comm(gph_engine *e, gph_comm *c);
 /* leafcodes: [Ptot][n] with 0..3 = T,C,A,G and 4 = N; numPhases non-zero on the first phase
  * of each unphased pattern (the reference keeps an int, 2^hets; here a 16-bit word: a count below 2^15 as it is, a count of 2^15 or
- * more -- always a power of two -- as 0x8000 | exponent, GPH_NUMPHASES below); counts on the same rows; pattern_offsets[L+1] */
+ * more -- always a power of two -- as 0x8000 | exponent, GPH_NUMPHASES below); counts on the same rows; pattern_offsets[L+1]
+ *
+ * What is legal is checked before anything is allocated; the first violation returns GPH_EARG, prints one line to stderr that
+ * names the locus (global index) and the pattern (row of the locus), and leaves that locus and its GPH_LOAD_* code for
+ * gph_engine_last_error and the line for gph_engine_last_error_text.  The sizes come first, from pattern_offsets alone, then
+ * the rows locus by locus:
+ *   GPH_LOAD_SIZE      a locus of P rows with 8 (n - 1) P >= 2^31 or a sequence block of 2^31 bytes or more (the device code
+ *                      indexes a locus's conditionals and its block with 32-bit integers), or pattern_offsets that decrease
+ *   GPH_LOAD_WORD      a phase word >= 0x8000 whose low 15 bits are not an exponent of 15 .. 24 (0x8003, 0x801f, a raw 32768)
+ *   GPH_LOAD_NO_GROUP  a row with word 0 that no first row's count covers (a locus's first row among them)
+ *   GPH_LOAD_OVERRUN   a first row whose decoded count runs past the last row of its locus
+ *   GPH_LOAD_INSIDE    a non-zero word or a non-zero count on one of the count - 1 rows behind a first row
+ *   GPH_LOAD_COUNT     a negative count
+ *   GPH_LOAD_LEAF      a leaf code above 4
+ * A count below 2^15 need not be a power of two (3, 5, 12 phases are legal); a locus of 0 rows is legal. */
 #define GPH_NUMPHASES(w) ((int)(w) < 0x8000 ? (int)(w) : (1 << ((int)(w) & 31)))
+#define GPH_LOAD_SIZE     (-101)
+#define GPH_LOAD_WORD     (-102)
+#define GPH_LOAD_NO_GROUP (-103)
+#define GPH_LOAD_OVERRUN  (-104)
+#define GPH_LOAD_INSIDE   (-105)
+#define GPH_LOAD_COUNT    (-106)
+#define GPH_LOAD_LEAF     (-107)
 int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *pattern_offsets, const uint8_t *leafcodes,
                          const uint16_t *numPhases, const int32_t *counts, const double *mutRates);
+/* the line the last refused gph_engine_load_loci printed ("" if none); valid until the engine is destroyed */
+const char *gph_engine_last_error_text(gph_engine *e);
 int gph_engine_set_model(gph_engine *e, const double *theta, const double *popAge, const double *sampleAge,
                          const double *migRate, const double *bandStart, const double *bandEnd);
 int gph_engine_seed(gph_engine *e, uint32_t seed);

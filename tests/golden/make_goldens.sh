@@ -145,5 +145,10 @@ rm -f q6.seq
 python3 make_p6.py
 timeout 900 $REF main -n 1 p6.ctl >/dev/null 2>&1
 
+# p7: groups of 64 and of 32 phases in loci of at most 64 phased patterns -- a repeated column in which all six (five) diploids are
+# heterozygous (make_p7.py writes the inputs): the real binary's trace file
+python3 make_p7.py
+timeout 900 $REF main -n 1 p7.ctl >/dev/null 2>&1
+
 # decision-level fixtures: the reference compiled with -DLOG_STEPS (oracle/_ref/gphocs_ref_log), two loci each of m3 and a7
 python3 make_logsteps.py

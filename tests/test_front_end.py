@@ -119,6 +119,30 @@ def test_phase_count_beyond_16_bits(tmp_path):
     assert compare_trace_files(os.path.join(GOLDEN, "p6.trace"), os.path.join(tmp_path, "p6.trace")) == 0
 
 
+def test_phase_groups_that_fill_a_wavefront(tmp_path):
+    """golden p7 -- a locus that is 24 repeats of one column in which all six diploids are heterozygous: ONE pattern of 2^6 = 64
+    phases, so the 64 phased patterns of the locus are one group (the root sum's lane shift runs over the whole wavefront and
+    feeds nothing in at its last lane); a second locus with 32 phases of one pattern among 40.  The front end's phase words and
+    counts, and the program's trace file against the real binary's"""
+    from parity_util import compare_trace_files
+    lib = G.load_library(R.build_hostemu())
+    for ext in (".ctl", ".seq"):
+        shutil.copy(os.path.join(GOLDEN, "p7" + ext), tmp_path)
+    pk = G.Pack.from_control(os.path.join(tmp_path, "p7.ctl"), lib=lib, seq_path=os.path.join(tmp_path, "p7.seq"))
+    o = [int(x) for x in pk.pattern_offsets]
+    assert pk.n == 12 and list(np.diff(o)) == [64, 40, 9, 8, 8]
+    assert pk.numPhases[o[0]:o[1]].tolist() == [64] + [0] * 63 and pk.counts[o[0]:o[1]].tolist() == [24] + [0] * 63
+    assert pk.numPhases[o[1]:o[2]].tolist() == [32] + [0] * 31 + [1] * 8 and int(pk.counts[o[1]]) == 20
+    assert not pk.counts[o[1] + 1:o[1] + 32].any() and int(pk.counts[o[1]:o[2]].sum()) == 40
+    assert (pk.numPhases[o[2]:] == 1).all() and [int(pk.counts[o[g]:o[g + 1]].sum()) for g in range(2, 5)] == [40, 40, 40]
+    # every row of a group is a phasing of the same column: the 64 rows of locus 1 are distinct and hold T and C only
+    rows = pk.leafcodes[o[0]:o[1]]
+    assert len({r.tobytes() for r in rows}) == 64 and set(np.unique(rows).tolist()) == {0, 1}
+    with _in_dir(tmp_path):
+        assert lib.gph_run_control_file(b"p7.ctl", None, 0, 0) == 0
+    assert compare_trace_files(os.path.join(GOLDEN, "p7.trace"), os.path.join(tmp_path, "p7.trace")) == 0
+
+
 def _seq_error(lib, tmp_path, mutate):
     for ext in (".ctl", ".seq"):
         shutil.copy(os.path.join(GOLDEN, "g1" + ext), tmp_path)

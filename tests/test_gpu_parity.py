@@ -367,7 +367,8 @@ def test_native_library_is_the_path(G):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["g1", "m3", "a7", "f3", "v8", "w2", "x8", "y9", "r5", "b2", "n7", "j1", "j2", "j3",
                                   "k3",     # k3: burn-in 13: iteration numbers below zero on the device, mcmc-sample-skip 2, log period 10
-                                  "p6"])    # p6: 2^16 phases of one pattern (a repeated column of 16 hets), 65 554 phased patterns in one locus
+                                  "p6",     # p6: 2^16 phases of one pattern (a repeated column of 16 hets), 65 554 phased patterns in one locus
+                                  "p7"])    # p7: 64 phases of one pattern = the 64 phased patterns of a locus; 32 phases among 40: the lane shift of add_phases over a whole wavefront
 def test_program_trace_file(name, tmp_path):
     """G-PhoCS-hip <control-file> on the MI355X: the trace file of the real G-PhoCS binary for the same
     control + sequence files (tests/golden/*.trace): parameter columns character-identical, the two log-likelihood
