@@ -278,7 +278,8 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("marginal_samples", C.c_int32), ("marginal_alpha", C.c_double),
                 ("mc3_chains", C.c_int32), ("mc3_heat", C.c_double), ("mc3_swap_every", C.c_int32), ("mc3_report_prefix", C.c_char_p),
                 ("replicates", C.c_int32), ("replicates_prefix", C.c_char_p), ("replicates_min_freq", C.c_double),
-                ("replicates_every", C.c_int32), ("ess_prefix", C.c_char_p), ("ess_loci", C.c_char_p)]
+                ("replicates_every", C.c_int32), ("ess_prefix", C.c_char_p), ("ess_loci", C.c_char_p),
+                ("predictive_prefix", C.c_char_p), ("predictive_loci", C.c_char_p), ("predictive_seed", C.c_char_p), ("predictive_rows", C.c_int32)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
@@ -286,7 +287,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                      clades=None, clades_loci=None, clades_slots=0, clades_min_support=None,
                      beta=None, marginal=None, marginal_steps=0, marginal_burnin=None, marginal_samples=0, marginal_alpha=0.0,
                      mc3=0, mc3_heat=0.0, mc3_swap_every=0, mc3_report=None,
-                     replicates=0, replicates_out=None, replicates_min_freq=None, replicates_every=0, ess=None, ess_loci=None):
+                     replicates=0, replicates_out=None, replicates_min_freq=None, replicates_every=0, ess=None, ess_loci=None,
+                     predictive=None, predictive_loci=None, predictive_seed=None, predictive_rows=0):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
     marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
@@ -294,7 +296,9 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
     mc3_report: the prefix of the report file.  replicates: the number of independent replicate chains (0: off), replicates_out:
     the prefix of PREFIX.psrf.tsv / PREFIX.asdsf.tsv / PREFIX.chain<r>.trace, replicates_min_freq None: 0.1, replicates_every
     k: an ASDSF line on stdout after every k-th sample (0: off).  ess: the prefix of PREFIX.ess.tsv / PREFIX.locus-ess.tsv,
-    ess_loci: the loci of the second (a SPEC as gene_trees_loci; None: all)"""
+    ess_loci: the loci of the second (a SPEC as gene_trees_loci; None: all).  predictive: the prefix of PREFIX.predictive.tsv /
+    PREFIX.predictive-genome.tsv, predictive_loci a SPEC, predictive_seed None: the control file's random-seed, predictive_rows
+    0: the default row buffer"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -310,7 +314,9 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       mc3_chains=mc3, mc3_heat=mc3_heat, mc3_swap_every=mc3_swap_every, mc3_report_prefix=b(mc3_report),
                       replicates=replicates, replicates_prefix=b(replicates_out),
                       replicates_min_freq=0.0 if replicates_min_freq is None else -1.0 if replicates_min_freq == 0 else replicates_min_freq,
-                      replicates_every=replicates_every, ess_prefix=b(ess), ess_loci=b(ess_loci))
+                      replicates_every=replicates_every, ess_prefix=b(ess), ess_loci=b(ess_loci),
+                      predictive_prefix=b(predictive), predictive_loci=b(predictive_loci),
+                      predictive_seed=None if predictive_seed is None else str(predictive_seed).encode(), predictive_rows=predictive_rows)
     return lib.gph_run(C.byref(o))
 
 
@@ -357,6 +363,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_mc3_swap_counts", "gph_mc3_swap_log", "gph_engine_clades_compare", "gph_psrf",
     "gph_ess", "gph_ess_read", "gph_engine_ess_enable", "gph_engine_ess_sample", "gph_engine_ess_shape", "gph_engine_ess_selected",
     "gph_engine_ess_fetch", "gph_ess_write", "gph_ess_discard", "gph_read_trace_ess", "gph_engine_last_error_text",
+    "gph_engine_predictive_enable", "gph_engine_predictive_sample", "gph_engine_predictive_shape", "gph_engine_predictive_selected",
+    "gph_engine_predictive_fetch_loci", "gph_engine_predictive_fetch_rows", "gph_engine_predictive_column_name",
+    "gph_predictive_write", "gph_predictive_discard",
 ]
 
 
@@ -540,6 +549,16 @@ def _load_library(path):
                                          C.POINTER(C.c_int64)]
     lib.gph_engine_ess_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     lib.gph_engine_ess_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.gph_engine_predictive_enable.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int64]
+    lib.gph_engine_predictive_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_predictive_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gph_engine_predictive_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_predictive_fetch_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.gph_engine_predictive_fetch_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_predictive_column_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_predictive_column_name.restype = C.c_char_p
+    lib.gph_predictive_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_predictive_discard.argtypes = [C.c_char_p, C.c_int32]
     return lib
 
 
@@ -1413,6 +1432,65 @@ class Sampler:
         min_ess = np.where(moved.any(axis=1), np.where(moved, tab[3], np.inf).min(axis=1), 0.0) if Q else np.zeros(0)
         return dict(loci=loci[:Q].copy(), samples=S, series=ESS_SERIES[:M], levels=J, words=W, acc=acc.copy(), changes=changes.copy(),
                     focal=focal.copy(), mean=tab[0], sd=tab[1], tau=tab[2], ess=tab[3], level=used, min_ess=min_ess)
+
+    # ---- posterior predictive checks of selected loci (gph_engine_predictive_*): simulated on the device, one sample per call
+    def predictive_enable(self, seed, capacity, loci=None, max_bytes=0):
+        """per-locus accumulators of the replicate statistics for the selected loci (as enable_gene_trees; None: all loci of
+        this rank) and a device buffer of `capacity` per-sample rows; capacity 0 switches the feature off.  The replicates are
+        a pure function of (seed, locus, sample, site, node).  ValueError for a refused selection or a locus whose statistics
+        do not fit 32 bits, MemoryError when accumulators and rows would exceed max_bytes (0: 1 GiB); the sampler stays usable"""
+        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
+        keep = sel if sel is None or len(sel) else np.zeros(1, dtype=np.int64)      # (a non-null pointer for an empty selection)
+        rc = self.lib.gph_engine_predictive_enable(self.engine, int(seed) & 0xffffffffffffffff, int(capacity),
+                                                   None if sel is None else keep.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   0 if sel is None else len(sel), int(max_bytes))
+        if rc == GPH_EFULL:
+            raise MemoryError("gphocs_hip: the predictive accumulators and rows exceed max_bytes (GPH_EFULL)")
+        if rc == -1:
+            raise ValueError("gphocs_hip: predictive_enable refused the capacity, the selection or a locus (GPH_EARG)")
+        self._chk(rc, "predictive_enable")
+
+    def predictive_sample(self, it):
+        """one replicate of every selected locus under the current state, labelled iteration `it`; BufferError when the row
+        buffer is full"""
+        self._sample(self.lib.gph_engine_predictive_sample, "predictive row", "predictive_rows", int(it))
+
+    def _predictive_shape(self):
+        q, c, S, held = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32()
+        self._chk(self.lib.gph_engine_predictive_shape(self.engine, C.byref(q), C.byref(c), C.byref(S), C.byref(held)), "predictive_shape")
+        return q.value, c.value, S.value, held.value
+
+    def predictive_columns(self):
+        return [self.lib.gph_engine_predictive_column_name(self.engine, c).decode() for c in range(self._predictive_shape()[1])]
+
+    def predictive(self, reset=False):
+        """the accumulators of this rank's Q selected loci as the device holds them: a dict of loci[Q] (global indices), samples,
+        stats (the C names), sites[Q] and acc (Q, C, 5) float64 -- obs, gt, eq, s1, s2.  reset=True zeroes them afterwards and
+        restarts the sample count"""
+        Q, nc, S, _ = self._predictive_shape()
+        if nc == 0:
+            raise RuntimeError("gphocs_hip: predictive: not enabled (GPH_ESTATE)")
+        loci = np.zeros(max(Q, 1), dtype=np.int64)
+        cnt = C.c_int64()
+        self._chk(self.lib.gph_engine_predictive_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)),
+                  "predictive_selected")
+        names = self.predictive_columns()
+        acc, sites = np.zeros((max(Q, 1), nc, 5), dtype=np.float64), np.zeros(max(Q, 1), dtype=np.int64)
+        self._chk(self.lib.gph_engine_predictive_fetch_loci(self.engine, acc.ctypes.data, sites.ctypes.data, int(bool(reset))), "predictive_fetch_loci")
+        return dict(loci=loci[:Q].copy(), samples=S, stats=names, sites=sites[:Q].copy(), acc=acc[:Q].copy())
+
+    def predictive_rows(self):
+        """(iterations, rows, observed): the per-sample rows taken since the last call, a uint64 (samples, C) array of the
+        replicate totals over THIS rank's selected loci, their iterations, and the data's totals observed[C]; the device
+        buffer is emptied"""
+        _, nc, _, held = self._predictive_shape()
+        if nc == 0:
+            raise RuntimeError("gphocs_hip: predictive_rows: not enabled (GPH_ESTATE)")
+        rows, its = np.zeros((max(held, 1), nc), dtype=np.uint64), np.zeros(max(held, 1), dtype=np.int32)
+        obs, got = np.zeros(nc, dtype=np.uint64), C.c_int32()
+        self._chk(self.lib.gph_engine_predictive_fetch_rows(self.engine, its.ctypes.data, rows.ctypes.data, obs.ctypes.data, rows.shape[0], C.byref(got)),
+                  "predictive_fetch_rows")
+        return its[:got.value].copy(), rows[:got.value].copy(), obs
 
     def hbm_bytes(self):
         b = C.c_double()

@@ -31,6 +31,7 @@
 #include "gph_genetrees.h"
 #include "gph_clades.h"
 #include "gph_ess.h"
+#include "gph_predictive.h"
 #include "gph_cladecmp.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
@@ -430,7 +431,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 22     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 23     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -469,6 +470,7 @@ struct gph_engine_state {
   std::vector<uint64_t> h_cond_off;
   std::vector<int32_t> h_P;          // per slot (sorted order)
   std::vector<int32_t> h_orig;       // slot -> original local index
+  std::vector<int64_t> h_sites;      // per local locus: the alignment columns it stands for (the counts of its unphased patterns)
   struct Bucket { int j0, count, lds_bytes; };   // a launch group: slots [j0, j0+count), dynamic LDS per wave
   std::vector<Bucket> buckets;
   double *d_mutRate = nullptr;
@@ -540,6 +542,12 @@ struct gph_engine_state {
   // the selected loci of this rank with their slots in HBM, samples since the accumulators were last zeroed
   struct { char *d = nullptr; size_t o_focal = 0, o_prev = 0, o_changes = 0, bytes = 0; GphClShape shape = {}; SmSel sel;
            int32_t M = 0; int64_t samples = 0, max_bytes = 0; bool on = false; } es;
+  // posterior predictive checks of selected loci (gph_predictive.h): ONE buffer in selection order -- acc [nsel][C][5] doubles,
+  // observed [C] u64 (the data's totals), key [nsel] u64 (Kl of each locus), pop [n] bytes (leaf -> current population) --, the
+  // per-sample rows [cap][C] u64 with their iterations, the sites of each selected locus, samples since the accumulators
+  // were last zeroed
+  struct { char *d = nullptr; size_t o_obs = 0, o_key = 0, o_pop = 0, bytes = 0; GphPdShape shape = {}; SmSel sel; SmRows rows;
+           std::vector<int32_t> iters; std::vector<int64_t> sites; uint64_t seed = 0; int64_t samples = 0; bool on = false; std::string name; } pd;
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -760,7 +768,7 @@ static void dump_one_locus(const gph_engine *e, FILE *f, long long global_locus,
   }
 }
 
-extern "C" { static int clades_zero(gph_engine *e); static int ess_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables and the ESS accumulators) */
+extern "C" { static int clades_zero(gph_engine *e); static int ess_zero(gph_engine *e); static int predictive_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables, the ESS and the predictive accumulators) */
 
 // after a host synchronisation: the error the stages recorded, the counters
 static int check_error(gph_engine *e)
@@ -942,6 +950,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->gt.rows.d); dev_free(e->gt.sel.d_slot);
   dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp); dev_free(e->cl.sel.d_slot);
   dev_free(e->es.d); dev_free(e->es.sel.d_slot);
+  dev_free(e->pd.d); dev_free(e->pd.sel.d_slot); dev_free(e->pd.rows.d);
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
   dev_free(e->d_red);
@@ -1166,6 +1175,9 @@ int gph_engine_load_loci(gph_engine *e, int64_t L, const int64_t *poff, const ui
   e->h_cond_off[L] = off;
   seq_off[L] = soff;
   e->h_seq_off = seq_off;
+  e->h_sites.assign(L, 0);
+  for (int64_t g = 0; g < L; g++)
+    for (int64_t p = poff[g]; p < poff[g + 1]; p++) if (numPhases[p] != 0) e->h_sites[g] += counts[p];
   std::vector<char> seq(soff, 0);
   for (int64_t j = 0; j < L; j++) {
     int64_t g = e->h_orig[j];
@@ -1271,6 +1283,9 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
     if (rce) return rce;
   }
   { int rcz = ess_zero(e); if (rcz) return rcz; }
+  e->pd.rows.fill = 0;
+  e->pd.iters.clear();
+  { int rcz = predictive_zero(e); if (rcz) return rcz; }
   int rc = launch_loci(e, 3, k_init, e->seedz, e->d_mutRate, e->init_predraws);
   if (!rc) rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -3109,6 +3124,181 @@ int gph_engine_ess_fetch(gph_engine *e, double *acc, uint32_t *changes, uint64_t
     if (changes) memcpy(changes, all.data() + e->es.o_changes, nsel * 4);
   }
   return reset ? ess_zero(e) : 0;
+}
+
+// ---- posterior predictive checks of selected loci (gph_predictive.h)
+// k_predictive over the selection: the data's statistics (observed) or sample t of the current state
+static int predictive_launch(gph_engine *e, int observed, uint64_t *row)
+{
+  const int nsel = (int)e->pd.sel.loci.size();
+  launch_pre(e);
+  return launch_grid(e, GphGrid{nsel, 1}, e->pd.shape.bd, (size_t)e->pd.shape.lds_bytes, k_predictive, e->ka, e->pd.shape, (const char *)e->dev.pages,
+                     e->dev.seq, e->dev.seq_off, e->dev.P, (const int32_t *)e->pd.sel.d_slot, (const uint64_t *)(e->pd.d + e->pd.o_key),
+                     (const uint8_t *)(e->pd.d + e->pd.o_pop), nsel, (int)e->L, (long long)e->pd.samples, observed, (double *)e->pd.d, row);
+}
+// the accumulators back to zero, t back to 0, and the data's statistics formed again (they live in the same words)
+static int predictive_zero(gph_engine *e)
+{
+  if (!e->pd.on) return 0;
+  e->pd.samples = 0;
+  { int rcz = acc_zero(e, e->pd.d, e->pd.o_key); if (rcz) return rcz; }
+  if (e->pd.sel.loci.empty()) return 0;          /* (a rank without a selected locus launches nothing) */
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  { int rcl = predictive_launch(e, 1, (uint64_t *)(e->pd.d + e->pd.o_obs)); if (rcl) return rcl; }
+  flat_launched(e, -1, 1);
+  return 0;
+}
+static void predictive_free(gph_engine *e)
+{
+  dev_free(e->pd.d);
+  e->pd.d = nullptr;
+  rows_free(e->pd.rows);
+  sel_free(e->pd.sel);
+  e->pd.iters.clear();
+  e->pd.sites.clear();
+  e->pd.shape = GphPdShape{};
+  e->pd.o_obs = e->pd.o_key = e->pd.o_pop = e->pd.bytes = 0;
+  e->pd.samples = 0;
+  e->pd.on = false;
+}
+
+int gph_engine_predictive_enable(gph_engine *e, uint64_t seed, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity_rows < 0 || !sel_valid(loci, nloci)) return GPH_EARG;
+  SETDEV(e);
+  predictive_free(e);
+  if (capacity_rows == 0) return 0;
+  const int n = e->cfg.n, Kc = e->cfg.Kc;
+  GphPdShape h;
+  gph_pd_shape(e->lay, h);
+  if (n > 255 || h.lds_bytes > 65536) {
+    fprintf(stderr, "gphocs_hip: predictive: %d leaves in %d current populations need byte counts above 255 or %d bytes of LDS a workgroup (65536 at most)\n",
+            n, Kc, (int)h.lds_bytes);
+    return GPH_EARG;
+  }
+  { int rcs = sel_alloc(e, e->pd.sel, loci, nloci); if (rcs) return rcs; }
+  const size_t nsel = e->pd.sel.loci.size();
+  int64_t maxpair = 1;
+  for (int p = 0; p < Kc; p++) if ((int64_t)e->samplesPerPop[p] * e->samplesPerPop[p] > maxpair) maxpair = (int64_t)e->samplesPerPop[p] * e->samplesPerPop[p];
+  for (size_t q = 0; q < nsel; q++) {
+    const int64_t g = e->pd.sel.loci[q], sites = e->h_sites[(size_t)(g - e->cfg.locus_begin)];
+    if (sites >= ((int64_t)1 << 31) || sites * maxpair >= ((int64_t)1 << 32)) {
+      fprintf(stderr, "gphocs_hip: predictive: locus %lld: %lld sites x %lld sample pairs reach 2^32: its statistics do not fit 32 bits\n",
+              (long long)g, (long long)sites, (long long)maxpair);
+      predictive_free(e);
+      return GPH_EARG;
+    }
+    e->pd.sites.push_back(sites);
+  }
+  const size_t o_obs = nsel * (size_t)h.C * GPH_PD_WORDS * 8, o_key = o_obs + (size_t)h.C * 8, o_pop = o_key + nsel * 8, bytes = o_pop + (((size_t)n + 15) & ~(size_t)15);
+  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
+  const int64_t need = (int64_t)bytes + (int64_t)capacity_rows * h.C * 8;
+  if (need > limit) {
+    fprintf(stderr, "gphocs_hip: predictive: the accumulators and rows need %lld bytes (%lld loci x (%d statistics x 40 + 8) + %d rows x %d x 8 + %d), the limit is %lld\n",
+            (long long)need, (long long)nsel, (int)h.C, (int)capacity_rows, (int)h.C, (int)(h.C * 8 + ((n + 15) & ~15)), (long long)limit);
+    predictive_free(e);
+    return GPH_EFULL;
+  }
+  if (dev_alloc((void **)&e->pd.d, bytes)) { dev_clear_error(); e->pd.d = nullptr; predictive_free(e); return GPH_EHIP; }
+  if (rows_alloc(e->pd.rows, sizeof(uint64_t), h.C, capacity_rows)) { dev_clear_error(); predictive_free(e); return GPH_EHIP; }
+  std::vector<uint64_t> key(nsel + 1);
+  for (size_t q = 0; q < nsel; q++) key[q] = gph_pd_locus_key(seed, (uint64_t)e->pd.sel.loci[q]);
+  std::vector<uint8_t> pop(((size_t)n + 15) & ~(size_t)15, 0);
+  for (int p = 0, i = 0; p < Kc; p++)
+    for (int k = 0; k < e->samplesPerPop[p] && i < n; k++) pop[(size_t)i++] = (uint8_t)p;
+  int rc = 0;
+  if (nsel > 0) rc = h2d(e, e->pd.d + o_key, key.data(), nsel * 8);
+  if (!rc) rc = h2d(e, e->pd.d + o_pop, pop.data(), pop.size());
+  if (rc) { predictive_free(e); return rc; }
+  e->pd.shape = h;
+  e->pd.seed = seed;
+  e->pd.o_obs = o_obs; e->pd.o_key = o_key; e->pd.o_pop = o_pop; e->pd.bytes = bytes;
+  e->pd.on = true;
+  return predictive_zero(e);
+}
+
+// one sample of the current state, queued on the engine's stream
+int gph_engine_predictive_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->pd.on) return GPH_ESTATE;
+  if (e->pd.rows.fill >= e->pd.rows.cap) return GPH_EFULL;
+  SETDEV(e);
+  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
+  uint64_t *row = (uint64_t *)rows_next(e->pd.rows);
+  { int rcz = acc_zero(e, row, sizeof(uint64_t) * (size_t)e->pd.rows.n); if (rcz) return rcz; }
+  if (!e->pd.sel.loci.empty()) {        /* (a rank without a selected locus launches nothing: its row stays 0) */
+    int tms;
+    { int rcb = sample_begin(e, 22, tms); if (rcb) return rcb; }
+    { int rcl = predictive_launch(e, 0, row); if (rcl) return rcl; }
+    sample_end(e, 22, 1, tms);
+  }
+  e->pd.iters.push_back(iteration);
+  e->pd.rows.fill++;
+  e->pd.samples++;
+  return 0;
+}
+
+int gph_engine_predictive_shape(gph_engine *e, int64_t *selected, int32_t *stats, int64_t *samples, int32_t *rows_held)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->pd.on;
+  if (selected) *selected = on ? (int64_t)e->pd.sel.loci.size() : 0;
+  if (stats) *stats = on ? e->pd.shape.C : 0;
+  if (samples) *samples = on ? e->pd.samples : 0;
+  if (rows_held) *rows_held = on ? e->pd.rows.fill : 0;
+  return 0;
+}
+
+int gph_engine_predictive_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
+{
+  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
+  if (!e->pd.on) return GPH_ESTATE;
+  return sel_copy_out(e->pd.sel, out, max_loci, count);
+}
+
+// acc [selected][C][5] (obs, gt, eq, s1, s2), sites [selected] (may be null)
+int gph_engine_predictive_fetch_loci(gph_engine *e, double *acc, int64_t *sites, int32_t reset)
+{
+  if (!e) return GPH_EARG;
+  if (!e->pd.on) return GPH_ESTATE;
+  const size_t nsel = e->pd.sel.loci.size();
+  if (nsel > 0 && !acc) return GPH_EARG;
+  SETDEV(e);
+  if (nsel > 0) { int rc = pull_rows(e, acc, e->pd.d, e->pd.o_obs); if (rc) return rc; }
+  if (sites) for (size_t q = 0; q < nsel; q++) sites[q] = e->pd.sites[q];
+  return reset ? predictive_zero(e) : 0;
+}
+
+// the rows taken since the last fetch ([rows][C], with their iterations) and the data's totals (observed [C], may be null);
+// the row buffer is empty again
+int gph_engine_predictive_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *rows_out, uint64_t *observed, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || ((!rows_out || !iters) && max_rows > 0)) return GPH_EARG;
+  if (!e->pd.on) return GPH_ESTATE;
+  SmRows &b = e->pd.rows;
+  if (max_rows < b.fill) return GPH_EARG;
+  SETDEV(e);
+  const size_t C = (size_t)b.n, held = (size_t)b.fill;
+  if (observed) { int rc = pull_rows(e, observed, e->pd.d + e->pd.o_obs, C * 8); if (rc) return rc; }
+  if (held > 0) { int rc = pull_rows(e, rows_out, b.d, b.esz * C * held); if (rc) return rc; }
+  for (size_t r = 0; r < held; r++) iters[r] = e->pd.iters[r];
+  *rows = b.fill;
+  b.fill = 0;
+  e->pd.iters.clear();
+  return 0;
+}
+
+// seg, then diff_<p>|<q> for the current populations p <= q (model order), p-major
+const char *gph_engine_predictive_column_name(gph_engine *e, int32_t col)
+{
+  if (!e || !e->pd.on || col < 0 || col >= e->pd.shape.C) return nullptr;
+  if (col == 0) return "seg";
+  const int Kc = e->cfg.Kc;
+  for (int p = 0; p < Kc; p++)
+    for (int q = p; q < Kc; q++)
+      if (gph_pd_pair(Kc, p, q) == col) { e->pd.name = "diff_" + std::to_string(p) + "|" + std::to_string(q); return e->pd.name.c_str(); }
+  return nullptr;
 }
 
 // ---- two engines exchange their chain states (Metropolis-coupled chains)

@@ -1490,6 +1490,9 @@ struct Clades : Output {
 // ---- `--ess PREFIX [--ess-loci SPEC]`: effective sample sizes per trace column and per locus
 #include "gph_ess_run.h"
 
+// ---- `--predictive PREFIX [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]`: posterior predictive checks
+#include "gph_predictive_run.h"
+
 // the enabled outputs in the order of their engine calls at a sample, which is also the order in which gph_run_finish writes
 // their files (the groups of fewer files first: should a later one fail, fewer are removed again).  A run closes them in the
 // opposite order, as it always did, and opens them in that order too: the summary is now enabled last, not first
@@ -1499,10 +1502,12 @@ struct Outputs {
   GeneTrees *trees = nullptr;
   Clades *clades = nullptr;
   Ess *ess = nullptr;
+  Predictive *predictive = nullptr;
   explicit Outputs(const gph_run_options &o)
   {
     if (o.locus_summary_path) list.emplace_back(summary = new LocusSummary);
     if (o.ess_prefix) list.emplace_back(ess = new Ess(o));
+    if (o.predictive_prefix) list.emplace_back(predictive = new Predictive(o));
     if (o.clades_prefix) list.emplace_back(clades = new Clades(o));
     if (o.gene_trees_prefix) list.emplace_back(trees = new GeneTrees(o));
     if (o.ancestry_prefix) list.emplace_back(new Ancestry(o));
@@ -1780,6 +1785,7 @@ int run_chain(const gph_run_options &o)
   if (outs.trees && (rc = outs.trees->select(R))) return rc;
   if (outs.clades && (rc = outs.clades->select(R))) return rc;
   if (outs.ess && (rc = outs.ess->select(R))) return rc;
+  if (outs.predictive && (rc = outs.predictive->select(R))) return rc;
   if ((rc = R.start_engine()) || (rc = R.open_trace())) return rc;
   if (o.beta != 0.0) {
     if ((rc = gph_mcmc_set_beta(R.M, option_beta(o)))) return R.fail(rc, "gph_mcmc_set_beta");
@@ -1850,7 +1856,7 @@ int run_chain(const gph_run_options &o)
   if (rcr) return rcr;
   if (checked && where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h, 12 gph_ess.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h, 12 gph_ess.h, 13 gph_predictive.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
     return GPH_EKERNEL;
   }
   if (outs.summary && (rc = outs.summary->write_table(R))) return rc;
@@ -1941,6 +1947,136 @@ extern "C" int gph_ess_write(const char *prefix, int32_t ranks)
   return ok ? GPH_OK : GPH_EARG;
 }
 
+extern "C" int gph_predictive_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  remove_parts(PD_PART, prefix, ranks);
+  for (const char *sfx : PD_FILES) unlink((std::string(prefix) + sfx).c_str());     /* (files only: whatever else sits there is not ours) */
+  return GPH_OK;
+}
+
+extern "C" int gph_predictive_write(const char *prefix, int32_t ranks)
+{
+  if (!prefix || ranks < 1) return GPH_EARG;
+  FILE *out[2] = {nullptr, nullptr};
+  bool ok = true;
+  for (int k = 0; k < 2 && ok; k++)
+    if (!(out[k] = fopen((std::string(prefix) + PD_FILES[k]).c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s%s\n", prefix, PD_FILES[k]); ok = false; }
+  long long S = -1, C = -1;
+  unsigned long long seed = 0;
+  std::vector<std::string> names;
+  std::vector<unsigned long long> observed, totals;     /* [C]; [sample][C] */
+  std::vector<long long> iters;
+  long long Q = 0, lo_at = -1;
+  double lo = 0.0;
+  auto numbers = [](char *at, long long count, unsigned long long *into, bool add) {      /* count tab-separated u64 behind `at` */
+    for (long long c = 0; c < count; c++) {
+      if (*at != '\t') return false;
+      char *end = nullptr;
+      const unsigned long long v = strtoull(at + 1, &end, 10);
+      if (end == at + 1) return false;
+      into[c] = add ? into[c] + v : v;
+      at = end;
+    }
+    return *at == '\n';
+  };
+  for (int r = 0; r < ranks && ok; r++) {
+    const std::string path = part_path(PD_PART, prefix, r);
+    FILE *in = fopen(path.c_str(), "r");
+    char *line = nullptr;
+    size_t cap = 0;
+    ssize_t len;
+    long long lines = 0, told = -1, sample = 0;
+    int at = 0;
+    while (in && ok && (len = getline(&line, &cap, in)) > 0) {
+      at++;
+      if (at == 1) { ok = !strcmp(line, "GPHPD1\n"); continue; }
+      if (at == 2) {
+        long long s = 0, c = 0;
+        unsigned long long sd = 0;
+        int used = 0;
+        ok = sscanf(line, "H\t%lld\t%lld\t%llu%n", &s, &c, &sd, &used) == 3 && (S < 0 || (s == S && c == C && sd == seed)) && c >= 1 && line[len - 1] == '\n';
+        if (ok && S < 0) {
+          S = s; C = c; seed = sd;
+          std::string rest(line + used, (size_t)len - used - 1);
+          size_t from = 0;
+          while (from < rest.size() && rest[from] == '\t') {
+            const size_t to = rest.find('\t', from + 1);
+            names.push_back(rest.substr(from + 1, to == std::string::npos ? std::string::npos : to - from - 1));
+            from = to == std::string::npos ? rest.size() : to;
+          }
+          ok = (long long)names.size() == C;
+          if (ok) {
+            observed.assign((size_t)C, 0);
+            totals.assign((size_t)(S * C), 0);
+            iters.assign((size_t)S, 0);
+            fprintf(out[0], "locus\tname\tsamples\tsites");
+            for (const std::string &nm : names) fprintf(out[0], "\tobs_%s\tmean_%s\tsd_%s\tp_%s", nm.c_str(), nm.c_str(), nm.c_str(), nm.c_str());
+            fprintf(out[0], "\tminP\tstat\n");
+          }
+        }
+        continue;
+      }
+      if (told >= 0) { ok = false; break; }                      /* something behind the last line */
+      if (line[0] == 'E' && line[1] == '\t') { told = atoll(line + 2); continue; }
+      ok = len > 2 && line[len - 1] == '\n';
+      if (!ok) break;
+      lines++;
+      if (line[0] == 'L' && line[1] == '\t') {
+        char *end = nullptr;
+        const double v = strtod(line + 2, &end);
+        ok = end && *end == '\t';
+        if (ok) {
+          if (lo_at < 0 || v < lo) { lo = v; lo_at = atoll(end + 1); }
+          Q++;
+          fputs(end + 1, out[0]);
+        }
+      } else if (line[0] == 'O') ok = numbers(line + 1, C, observed.data(), true);
+      else if (line[0] == 'R' && line[1] == '\t') {
+        char *end = nullptr;
+        const long long it = strtoll(line + 2, &end, 10);
+        ok = sample < S && end != line + 2 && (r == 0 || iters[(size_t)sample] == it) && numbers(end, C, totals.data() + (size_t)(sample * C), true);
+        if (ok) iters[(size_t)sample++] = it;
+      } else ok = false;
+    }
+    free(line);
+    if (in) fclose(in);
+    if (!in || !ok || at < 2 || told != lines || sample != S) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); ok = false; }
+  }
+  if (ok) {
+    fprintf(out[0], "# loci %lld samples %lld seed %llu minMinP %.10g (locus %lld)\n", Q, S, seed, lo, lo_at);
+    fprintf(out[1], "iter");
+    for (const std::string &nm : names) fprintf(out[1], "\t%s", nm.c_str());
+    fputc('\n', out[1]);
+    for (long long s = 0; s < S; s++) {
+      fprintf(out[1], "%7d", (int)iters[(size_t)s]);
+      for (long long c = 0; c < C; c++) fprintf(out[1], "\t%llu", totals[(size_t)(s * C + c)]);
+      fputc('\n', out[1]);
+    }
+    std::string obs = "# observed", mean = "# mean", pl = "# p";
+    char num[64];
+    for (long long c = 0; c < C; c++) {
+      unsigned long long sum = 0, gt = 0, eq = 0;
+      for (long long s = 0; s < S; s++) {
+        const unsigned long long t = totals[(size_t)(s * C + c)];
+        sum += t; gt += t > observed[(size_t)c]; eq += t == observed[(size_t)c];
+      }
+      snprintf(num, sizeof num, "\t%llu", observed[(size_t)c]); obs += num;
+      snprintf(num, sizeof num, "\t%.10g", S > 0 ? (double)sum / (double)S : 0.0); mean += num;
+      snprintf(num, sizeof num, "\t%.10g", S > 0 ? ((double)gt + (double)eq / 2) / (double)S : 0.0); pl += num;
+    }
+    fprintf(out[1], "%s\n%s\n%s\n# loci %lld samples %lld seed %llu\n", obs.c_str(), mean.c_str(), pl.c_str(), Q, S, seed);
+    printf("Predictive: %s\n", pl.c_str() + 2);
+    fflush(stdout);
+  }
+  for (int k = 0; k < 2; k++)
+    if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s%s failed\n", prefix, PD_FILES[k]); ok = false; }
+  remove_parts(PD_PART, prefix, ranks);
+  if (!ok)
+    for (int k = 0; k < 2; k++) if (out[k]) remove((std::string(prefix) + PD_FILES[k]).c_str());
+  return ok ? GPH_OK : GPH_EARG;
+}
+
 extern "C" int gph_run_finish(const gph_run_options *in, int32_t ranks, int32_t failed)
 {
   gph_run_options o;
@@ -1968,7 +2104,7 @@ extern "C" int gph_run(const gph_run_options *in)
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
   /* the checks on the options alone, before anything is read */
   int rc;
-  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = Ess::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
+  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = Ess::validate(o)) || (rc = Predictive::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
       (rc = Replicates::validate(o))) return rc;
   rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */

@@ -245,7 +245,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * (gph_engine_ancestry_sample: k_ancestry), 17 sampled genealogies (gph_engine_gene_trees_sample: k_gene_trees), 18 the
  * sweep's draws generated ahead of it (k_rng_ahead), 19 clade tables (gph_engine_clades_sample: k_clades), 20 the clade
  * tables of replicate chains compared (gph_engine_clades_compare: k_clades_compare, counted on engines[0]), 21 effective
- * sample sizes per locus (gph_engine_ess_sample: k_ess) */
+ * sample sizes per locus (gph_engine_ess_sample: k_ess), 22 posterior predictive checks (gph_engine_predictive_sample:
+ * k_predictive) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -547,6 +548,50 @@ int gph_engine_ess_sample(gph_engine *e);
 int gph_engine_ess_shape(gph_engine *e, int64_t *selected, int32_t *series, int32_t *levels, int32_t *words, int64_t *samples);
 int gph_engine_ess_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
 int gph_engine_ess_fetch(gph_engine *e, double *acc /* [selected][series][2 + 2 levels] */, uint32_t *changes, uint64_t *focal, int32_t reset);
+
+/* POSTERIOR PREDICTIVE CHECKS of selected loci, simulated on the device (k_predictive: csrc/gph_predictive.h; timing class 22).
+ * At every sample one replicate alignment of each selected locus is drawn under the sampled genealogy (the settled node
+ * records a gene-tree record holds) and locus rate (FS_MUTRATE) with JC69, the likelihood's model, and the locus's own
+ * missing-data pattern, and C = 1 + Kc (Kc + 1) / 2 integer statistics are summed over its sites; the same statistics of the
+ * data are formed once.  All arithmetic is uncontracted fp64 and 64-bit unsigned integers modulo 2^64.
+ *   columns   the pattern rows of the locus as gph_engine_load_loci received them, in order; a column is the FIRST row of a
+ *             group of phases (non-zero phase word), the others are skipped (the statistics do not depend on the order of the
+ *             leaves within a population).  Column c stands for count_c sites: site s = 0, 1, ... belongs to c iff
+ *             prefix_c <= s < prefix_c + count_c; a leaf with code 4 (N) is missing at them, in the data and in the replicate
+ *   generator mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *             Kl = mix(seed ^ mix(g + 0x9E3779B97F4A7C15)), g the GLOBAL locus index;  K = mix(Kl + t), t = samples taken since
+ *             _enable / a reset (0-based);  h(s, v) = mix(K ^ ((s << 16) | v)), site s < 2^31, node v < 2^16
+ *   branches  v != root: len = rate * (age[father v] - age[v]); q_v = 0 when len < 1e-100, else 1 - exp(-4 len / 3.0) (glibc's
+ *             exp); thr_v = (uint64)(q_v * 2^53); v FIRES at s iff (h(s, v) >> 11) < thr_v; the root always fires
+ *   replicate the base of leaf i at s = h(s, a) & 3, a the first node on the path i, father(i), ..., root that fires at s
+ *   statistics per site, cnt[p][b] = the non-missing leaves of current population p showing base b, m_p = sum_b cnt[p][b]:
+ *             seg = 1 iff at least two bases b are shown by some leaf; diff_p|p = (m_p^2 - sum_b cnt[p][b]^2) / 2;
+ *             diff_p|q (p < q) = m_p m_q - sum_b cnt[p][b] cnt[q][b].  Order: seg, then (p, q), p <= q, p-major
+ *             (gph_engine_predictive_column_name: "seg", "diff_<p>|<q>")
+ *   accumulators per (selected locus, statistic), five doubles: obs = T of the data; per sample with the replicate's T:
+ *             gt += (T > obs), eq += (T == obs), s1 = s1 + T, s2 = s2 + T * T, in sample order
+ *   rows      per sample the iteration and C uint64 totals of T over the rank's selected loci; the data's totals once
+ *   _enable   capacity_rows per-sample rows; 0 frees everything, the feature is off.  The selection as for
+ *             gph_engine_gene_trees_enable.  GPH_EARG with a message that names the locus for a selected locus whose
+ *             sites x max n_p n_q reach 2^32 (or whose sites reach 2^31); GPH_EFULL, with a message and nothing allocated, above
+ *             max_bytes (<= 0: 1 GiB); GPH_ESTATE before the loci are loaded.  Enabling again frees and starts over.
+ *             gph_engine_init_genealogies zeroes the accumulators, the sample count and the rows held
+ *   _sample   one kernel on the engine's stream, no host synchronisation; a rank without a selected locus launches nothing and
+ *             still takes the (zero) row.  GPH_EFULL when the row buffer is full; GPH_ESTATE when off or before
+ *             gph_engine_init_genealogies
+ *   _shape    selected loci of the rank, C, samples since the accumulators were zeroed, rows held (all 0 while off)
+ *   _fetch_loci  acc[selected][C][5] (obs, gt, eq, s1, s2), sites[selected] (may be NULL); one copy and one host
+ *             synchronisation; reset != 0 zeroes the accumulators afterwards and restarts t at 0 (obs is formed again)
+ *   _fetch_rows  the rows taken since the last call (iters[rows], rows[rows][C]) and observed[C] (may be NULL); the row buffer
+ *             is empty again
+ * The kernel writes no page, reads the sequence blocks read-only, and touches neither the chain state nor a locus generator. */
+int gph_engine_predictive_enable(gph_engine *e, uint64_t seed, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int64_t max_bytes);
+int gph_engine_predictive_sample(gph_engine *e, int32_t iteration);
+int gph_engine_predictive_shape(gph_engine *e, int64_t *selected, int32_t *stats, int64_t *samples, int32_t *rows_held);
+int gph_engine_predictive_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_predictive_fetch_loci(gph_engine *e, double *acc /* [selected][C][5] */, int64_t *sites, int32_t reset);
+int gph_engine_predictive_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *rows_out, uint64_t *observed, int32_t max_rows, int32_t *rows);
+const char *gph_engine_predictive_column_name(gph_engine *e, int32_t col);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -903,6 +948,28 @@ typedef struct gph_run_options {
    * and prints both summary lines as one line "ESS: ...; ..." on stdout.  With mc3_chains, replicates and marginal_prefix the
    * files describe chain 0 and the run proper, as the clade tables do; every other output is the same bytes with and without. */
   const char *ess_prefix, *ess_loci;
+  /* `--predictive PREFIX [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]`: posterior predictive checks
+   * (gph_engine_predictive_* above).  A sample is taken wherever a trace line is written.  predictive_loci as gene_trees_loci
+   * (an index named twice or >= the number of loci is refused by name before the first iteration); predictive_seed: the seed as
+   * decimal text (NULL: the control file's random-seed); predictive_rows: the rows of the device buffer (0: a default), fetched
+   * when it is full and at the end.  Any of the three without predictive_prefix, a seed that is no unsigned number and negative
+   * rows are GPH_EARG with a message, before anything is read.  Rank r writes its part PREFIX.predictive.part<r> once, at the end.
+   * gph_predictive_write makes of the parts (numbers "%.10g")
+   *   PREFIX.predictive.tsv         header locus name samples sites, then per statistic s obs_<s> mean_<s> sd_<s> p_<s>, then minP
+   *                                 stat; one row per selected locus in sequence-file order (the ranks' rows concatenated); <s> =
+   *                                 seg, diff_<P>|<Q> with the populations' names; mean = s1 / S, sd = sqrt(max((s2 - s1^2 / S) /
+   *                                 (S - 1), 0)) (0 for S < 2), p = (gt + eq / 2) / S (upper-tail mid-p), minP = the smallest
+   *                                 2 min(p, 1 - p) over the statistics, stat its name (the first of equal ones); last line
+   *                                 "# loci Q samples S seed N minMinP v (locus <i>)" (no row: 0 (locus -1))
+   *   PREFIX.predictive-genome.tsv  header iter and the statistics' names; one row per sample, "%7d" and "\t%llu" per statistic:
+   *                                 the totals over the selected loci (the ranks' rows added); then "# observed", "# mean",
+   *                                 "# p" (the same mid-p, over the samples), each with one tab-separated value per statistic, and
+   *                                 "# loci Q samples S seed N"
+   * and prints "Predictive: " and the "# p" line without its "# " on stdout.  Both files are written once, on success only; a
+   * failed run leaves neither parts nor files.  With mc3_chains, replicates and marginal_prefix they describe chain 0 and the run
+   * proper; every other output is the same bytes with and without. */
+  const char *predictive_prefix, *predictive_loci, *predictive_seed;
+  int32_t predictive_rows;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
@@ -924,6 +991,8 @@ int gph_clades_write(const char *prefix, int32_t ranks);
 int gph_clades_discard(const char *prefix, int32_t ranks);
 int gph_ess_write(const char *prefix, int32_t ranks);
 int gph_ess_discard(const char *prefix, int32_t ranks);
+int gph_predictive_write(const char *prefix, int32_t ranks);
+int gph_predictive_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
  * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
  * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
