@@ -149,13 +149,13 @@ static int launch_grid(gph_engine *e, GphGrid grid, int block, size_t lds_bytes,
   return run_blocks(e->lds, grid, block, lds_bytes, kernel, args...);
 }
 
-static int debug_math(const double *x, const double *y, int n, double *out, int)
+static int debug_math(const double *x, const double *y, int n, double *out, int, int which = 0)
 {
   GphKargs ka;
   memset(&ka, 0, sizeof ka);
   fill_math_constants(ka);
   std::vector<char> lds;
-  return run_blocks(lds, GphGrid{(n + GPH_FLAT_THREADS - 1) / GPH_FLAT_THREADS, 1}, GPH_FLAT_THREADS, 0, k_debug_math, ka, x, y, n, out);
+  return run_blocks(lds, GphGrid{(n + GPH_FLAT_THREADS - 1) / GPH_FLAT_THREADS, 1}, GPH_FLAT_THREADS, 0, which ? k_debug_accept : k_debug_math, ka, x, y, n, out);
 }
 
 #else
@@ -567,7 +567,8 @@ static int oob_take(int32_t *where)
 }
 #endif
 // the parity probe's round trip: no engine, the null stream of `device`
-static int debug_math(const double *x, const double *y, int n, double *out, int device)
+// which: 0 k_debug_math (out[5n]), 1 k_debug_accept (out[3n])
+static int debug_math(const double *x, const double *y, int n, double *out, int device, int which = 0)
 {
   double *dx = nullptr, *dy = nullptr, *dout = nullptr;
   HIPCHK(hipSetDevice(device));
@@ -580,8 +581,8 @@ static int debug_math(const double *x, const double *y, int n, double *out, int 
   memset(&ka, 0, sizeof ka);
   fill_math_constants(ka);
   if (fill_math_tables(ka)) return GPH_EHIP;
-  { int rcl = launch_on(nullptr, GphGrid{(n + GPH_FLAT_THREADS - 1) / GPH_FLAT_THREADS, 1}, GPH_FLAT_THREADS, 0, k_debug_math, ka, dx, dy, n, dout); if (rcl) return rcl; }
-  HIPCHK(hipMemcpy(out, dout, sizeof(double) * 5 * n, hipMemcpyDeviceToHost));
+  { int rcl = launch_on(nullptr, GphGrid{(n + GPH_FLAT_THREADS - 1) / GPH_FLAT_THREADS, 1}, GPH_FLAT_THREADS, 0, which ? k_debug_accept : k_debug_math, ka, dx, dy, n, dout); if (rcl) return rcl; }
+  HIPCHK(hipMemcpy(out, dout, sizeof(double) * (which ? 3 : 5) * n, hipMemcpyDeviceToHost));
   (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
   return 0;
 }

@@ -339,6 +339,20 @@ GPH_FLAT(k_debug_math, GPH_FLAT_THREADS, GphKargs KA, const double *x, const dou
     }
   }
 }
+// ... and the sweep's accept test: gph_accept(u = y, x) next to the plain y < gph_exp(x), and what the bounds alone said
+GPH_FLAT(k_debug_accept, GPH_FLAT_THREADS, GphKargs KA, const double *x, const double *y, int n, double *o)
+{
+  GPH_FLAT_BODY(GphNoLane);
+  (void)KA;
+  GPH_PHASE {
+    const int i = bx * bd + tid;
+    if (i < n) {
+      o[i] = (double)gph_accept(y[i], x[i]);
+      o[n + i] = (double)(y[i] < gph_exp(x[i]));
+      o[2 * n + i] = (double)gph_accept_bounds_t<false>(y[i], x[i]);
+    }
+  }
+}
 
 // ---------------------------------------------------------------- the sweep's uniforms, generated ahead of it
 // One lane per locus slot: the three Wichmann-Hill recurrences of the slot's stream from the generator state in its page
@@ -619,6 +633,12 @@ static void build_model_static(gph_engine_state *e)
   G.tau_limit = (long long)1 << 62;
 }
 
+#ifdef GPH_ACCSTAT
+// host build with -DGPH_ACCSTAT: the sweep's accept tests by site (l_accept, gph_locus.h), printed when the library is unloaded
+long long gph_as[3][3];
+struct GphAsPrint { ~GphAsPrint() { static const char *site[3] = {"internal node", "migration node", "SPR"};
+  for (int s = 0; s < 3; s++) fprintf(stderr, "ACCSTAT %s: tests %lld, lnacc < 0 %lld, decided by the bounds %lld\n", site[s], gph_as[s][0], gph_as[s][1], gph_as[s][2]); } } gph_as_print;
+#endif
 #ifdef GPH_WALKSTAT
 long long gph_ws[4];
 struct GphWsPrint { ~GphWsPrint() { fprintf(stderr, "WALKSTAT proposals %lld: prune steps %.2f, regraft steps %.2f, common prefix %.2f per proposal\n", gph_ws[3], (double)gph_ws[0] / gph_ws[3], (double)gph_ws[1] / gph_ws[3], (double)gph_ws[2] / gph_ws[3]); } } gph_ws_print;
@@ -1631,6 +1651,12 @@ int gph_debug_math(const double *x, const double *y, int32_t n, double *out, int
 {
   if (!x || !y || !out || n <= 0) return GPH_EARG;
   return debug_math(x, y, n, out, device);
+}
+// tests only (not part of include/gphocs_hip.h): out[3n] = gph_accept(u, x), u < gph_exp(x), gph_accept_bounds_t(u, x)
+int gph_debug_accept_(const double *x, const double *u, int32_t n, double *out, int32_t device)
+{
+  if (!x || !u || !out || n <= 0) return GPH_EARG;
+  return debug_math(x, u, n, out, device, 1);
 }
 
 // tests only (not part of include/gphocs_hip.h): the pass ahead of the sweep.  info[4] = on, M, C, bytes per locus;

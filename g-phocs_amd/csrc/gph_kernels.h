@@ -315,7 +315,7 @@ template <bool HEAT, class RNG> GPH_DEV void sweep_internal(const GphDev &D, int
     { STAMPA_BEGIN(2); dgen = consider_event_move(0, NEV(inode), pop, t, pop, tnew); STAMPA_END(2); }
     lnacc = dgen + heated<HEAT>(lnLd);
     if (gph_failed()) break;
-    const bool take_ = UNI(lnacc >= 0) || UNI(l_rndu(rng) < gph_exp_u(lnacc));
+    const bool take_ = l_accept<0>(rng, lnacc);
     GPH_SLOG(3, take_, lnacc, 0, 0, 0, 0);
     if (take_) {
       acc++;
@@ -367,7 +367,7 @@ template <class RNG> GPH_DEV void sweep_mignodes(const GphDev &D, int g, double 
     dgen += consider_event_move(1, ev_t, pop_t, t, pop_t, tnew);
     lnacc = dgen;
     if (gph_failed()) break;
-    const bool take_ = UNI(lnacc >= 0) || UNI(l_rndu(rng) < gph_exp_u(lnacc));
+    const bool take_ = l_accept<1>(rng, lnacc);
     GPH_SLOG(3, take_, lnacc, 0, 0, 0, 0);
     if (take_) {
       acc++;
@@ -416,7 +416,7 @@ template <bool HEAT, class RNG> GPH_DEV void sweep_spr(const GphDev &D, int g, R
     { STAMP_BEGIN(1); lnLd += lik_compute(1); STAMP_END(1); }
     lnacc = heated<HEAT>(lnLd);
     if (gph_failed()) break;
-    const bool take_ = res >= 0 && (UNI(lnacc >= 0) || UNI(l_rndu(rng) < gph_exp_u(lnacc)));
+    const bool take_ = res >= 0 && l_accept<2>(rng, lnacc);
     GPH_SLOG(3, take_, lnacc, 0, 0, 0, 0);
     if (take_) {
       STAMPC_BEGIN(2);

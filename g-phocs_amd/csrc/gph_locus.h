@@ -493,6 +493,24 @@ template <class RNG> GPH_DEV double l_rnd2normal8(RNG &g)
   z = UNI(l_rndu(g) < 0.5) ? z : -z;
   return z;
 }
+// the Metropolis test of the three sweep proposals (GPhoCS.c:2403, 2560, 2720: lnacceptance >= 0 || rndu() < exp(lnacceptance)):
+// the draw is taken only for lnacc < 0, as there; 97 % of those are decided by the bounds of gph_accept_u (gph_math.h) without
+// evaluating the exponential (profiles/r08_bbcount.txt)
+// SITE: 0 internal node, 1 migration node, 2 SPR (the counters of a host build with -DGPH_ACCSTAT: tests, lnacc < 0, decided)
+template <int SITE, class RNG> GPH_DEV bool l_accept(RNG &rng, double lnacc)
+{
+#ifdef GPH_ACCSTAT
+  extern long long gph_as[3][3];
+  __atomic_fetch_add(&gph_as[SITE][0], 1, __ATOMIC_RELAXED);
+#endif
+  if (UNI(lnacc >= 0)) return true;
+  const double u = l_rndu(rng);
+#ifdef GPH_ACCSTAT
+  __atomic_fetch_add(&gph_as[SITE][1], 1, __ATOMIC_RELAXED);
+  __atomic_fetch_add(&gph_as[SITE][2], gph_accept_bounds_t<true>(u, lnacc) != 0, __ATOMIC_RELAXED);
+#endif
+  return gph_accept_u(u, lnacc);
+}
 // reflect, utils.c:333-398
 GPH_DEV double l_reflect(double x, double a, double b)
 {

@@ -132,6 +132,60 @@ GPH_MATH_FN double gph_exp_t(double x)
 GPH_MATH_FN double gph_exp(double x) { return gph_exp_t<false>(x); }
 GPH_MATH_FN double gph_exp_u(double x) { return gph_exp_t<true>(x); }
 
+// The Metropolis test `u < exp(x)` for x < 0, 0 <= u < 1, with EXACTLY the decisions of `u < gph_exp(x)`: two polynomial
+// bounds decide most pairs in a dozen instructions, the rest evaluates gph_exp as before.  m = 2^-40, y = -x > 0,
+// E = gph_exp(x), |E - e^x| < 1 ulp of e^x (glibc's exp stays below 0.52 ulp).  q and c below are the COMPUTED values.
+//   reject:  q = fma(y, fma(y, 1/2, 1), 1): every term is positive, two roundings: q <= (1 + y + y^2/2) (1 + 2^-51)
+//     <= e^y (1 + 2^-51).  fl(u q) >= 1 + m gives u q >= (1 + m) (1 - 2^-53), u >= e^x (1 + m) (1 - 2^-53) / (1 + 2^-51)
+//     > e^x (1 + m/2), and E <= e^x (1 + 2^-52) where e^x is normal: u > E.  Where e^x is subnormal, E is one of the two
+//     grid points next to it and u > e^x is a double too: u >= the grid point above e^x >= E.  Not (u < E) either way.
+//     y = inf (x = -inf) or y^2 overflowing: q = inf, u q = inf for u > 0: reject, and E = 0.  u = 0: fl(0 q) is 0, or NaN
+//     for q = inf: undecided.
+//   accept:  T(x) = 1 + x + x^2/2 + x^3/6 <= e^x for x < 0 (Lagrange remainder e^xi x^4 / 24 >= 0, x < xi < 0), c = fma(x,
+//     fma(x, fma(x, S, 1/2), 1), 1) with S = fl(1/6).  fl(u (1 + m)) < c gives u < c / ((1 + m) (1 - 2^-53)) < c (1 - m/2)
+//     (u (1 + m) subnormal: u < 2^-1022 < E below, where c > 0 needs y <= 2).
+//     y <= 2: the Horner values are 1/2 - y/6 in [1/6, 1/2], 1 - y (..) in [5/8, 1], 1 - y (..) in [-1/3, 1]: three roundings
+//       of at most 2^-53 each, carried through factors y <= 2, and S off by 2^-56: |c - T| < 16 * 2^-53 = 2^-49.  For y <= 1
+//       T >= 1/3, so c (1 - m/2) <= T + 2^-49 - 2^-43 < T (1 - 2^-52) <= e^x (1 - 2^-52) <= E.  For 1 < y <= 2 the remainder is
+//       >= e^-2 / 24 > 2^-8: c (1 - m/2) <= c < T + 2^-49 < e^x - 2^-9 < E (c > 0 here: with c <= 0 the compare cannot hold
+//       for u >= 0, nothing is decided).
+//     y > 2: T <= T(-2) = -1/3 and T <= -y^3 / 24 (y^3/8 - y^2/2 + y - 1 is 0 at y = 2 and grows), while |c - T| <
+//       2^-50 (1 + y + y^2 + y^3) < 2^-44 |T|: c < 0 <= u (c = -inf once y^3 overflows; x = -inf: 1/2 + x S = -inf, times
+//       x = +inf, 1 + that = +inf, times x = -inf): undecided.
+//   NaN x: q and c are NaN, both compares false: gph_exp decides, as it did.
+// UNIFORM: wave-uniform arguments (chain logic), the compares are tested as lane masks on the scalar unit -- UNI of gph_rt.h,
+// which includes this header and is not defined yet down here; GPH_UCMP is local to the functions below.
+// CONTRACT: x < 0 (or NaN, -0.0) and 0 <= u < 1.  For x > 0 the polynomials bound nothing and the answer may be wrong: a
+// caller handles x >= 0 before it draws u, as l_accept (gph_locus.h) does.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GPH_UCMP(c) (UNIFORM ? __builtin_amdgcn_ballot_w64((bool)(c)) != 0 : (bool)(c))
+#else
+#define GPH_UCMP(c) ((bool)(c))
+#endif
+#define GPH_ACC_M 0x1p-40
+// 0: gph_exp has to decide, 1: certainly not below, 2: certainly below
+template <bool UNIFORM>
+GPH_MATH_FN int gph_accept_bounds_t(double u, double x)
+{
+  const double y = -x;
+  const double q = __builtin_fma(y, __builtin_fma(y, 0.5, 1.0), 1.0);
+  if (GPH_UCMP(u * q >= 1.0 + GPH_ACC_M)) return 1;
+  const double c = __builtin_fma(x, __builtin_fma(x, __builtin_fma(x, 1.0 / 6.0, 0.5), 1.0), 1.0);
+  if (GPH_UCMP(u * (1.0 + GPH_ACC_M) < c)) return 2;
+  return 0;
+}
+template <bool UNIFORM>
+GPH_MATH_FN bool gph_accept_t(double u, double x)
+{
+  const int b = gph_accept_bounds_t<UNIFORM>(u, x);
+  if (b) return b == 2;
+  return GPH_UCMP(u < gph_exp_t<UNIFORM>(x));
+}
+GPH_MATH_FN bool gph_accept(double u, double x) { return gph_accept_t<false>(u, x); }
+GPH_MATH_FN bool gph_accept_u(double u, double x) { return gph_accept_t<true>(u, x); }
+#undef GPH_UCMP
+#undef GPH_ACC_M
+
 template <bool UNIFORM>
 GPH_MATH_FN double gph_log_t(double x)
 {
