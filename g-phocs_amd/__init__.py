@@ -279,7 +279,8 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("mc3_chains", C.c_int32), ("mc3_heat", C.c_double), ("mc3_swap_every", C.c_int32), ("mc3_report_prefix", C.c_char_p),
                 ("replicates", C.c_int32), ("replicates_prefix", C.c_char_p), ("replicates_min_freq", C.c_double),
                 ("replicates_every", C.c_int32), ("ess_prefix", C.c_char_p), ("ess_loci", C.c_char_p),
-                ("predictive_prefix", C.c_char_p), ("predictive_loci", C.c_char_p), ("predictive_seed", C.c_char_p), ("predictive_rows", C.c_int32)]
+                ("predictive_prefix", C.c_char_p), ("predictive_loci", C.c_char_p), ("predictive_seed", C.c_char_p), ("predictive_rows", C.c_int32),
+                ("triplets_prefix", C.c_char_p), ("triplets_pops", C.c_char_p), ("triplets_loci", C.c_char_p), ("triplets_rows", C.c_int32)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
@@ -288,7 +289,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                      beta=None, marginal=None, marginal_steps=0, marginal_burnin=None, marginal_samples=0, marginal_alpha=0.0,
                      mc3=0, mc3_heat=0.0, mc3_swap_every=0, mc3_report=None,
                      replicates=0, replicates_out=None, replicates_min_freq=None, replicates_every=0, ess=None, ess_loci=None,
-                     predictive=None, predictive_loci=None, predictive_seed=None, predictive_rows=0):
+                     predictive=None, predictive_loci=None, predictive_seed=None, predictive_rows=0,
+                     triplets=None, triplets_pops=None, triplets_loci=None, triplets_rows=0):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
     marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
@@ -298,7 +300,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
     k: an ASDSF line on stdout after every k-th sample (0: off).  ess: the prefix of PREFIX.ess.tsv / PREFIX.locus-ess.tsv,
     ess_loci: the loci of the second (a SPEC as gene_trees_loci; None: all).  predictive: the prefix of PREFIX.predictive.tsv /
     PREFIX.predictive-genome.tsv, predictive_loci a SPEC, predictive_seed None: the control file's random-seed, predictive_rows
-    0: the default row buffer"""
+    0: the default row buffer.  triplets: the prefix of PREFIX.triplets.tsv / PREFIX.triplets-genome.tsv, triplets_pops the triples
+    as "A,B,C;D,E,F" (None: all), triplets_loci a SPEC, triplets_rows 0: the default row buffer"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -316,7 +319,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       replicates_min_freq=0.0 if replicates_min_freq is None else -1.0 if replicates_min_freq == 0 else replicates_min_freq,
                       replicates_every=replicates_every, ess_prefix=b(ess), ess_loci=b(ess_loci),
                       predictive_prefix=b(predictive), predictive_loci=b(predictive_loci),
-                      predictive_seed=None if predictive_seed is None else str(predictive_seed).encode(), predictive_rows=predictive_rows)
+                      predictive_seed=None if predictive_seed is None else str(predictive_seed).encode(), predictive_rows=predictive_rows,
+                      triplets_prefix=b(triplets), triplets_pops=b(triplets_pops), triplets_loci=b(triplets_loci), triplets_rows=triplets_rows)
     return lib.gph_run(C.byref(o))
 
 
@@ -366,6 +370,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_predictive_enable", "gph_engine_predictive_sample", "gph_engine_predictive_shape", "gph_engine_predictive_selected",
     "gph_engine_predictive_fetch_loci", "gph_engine_predictive_fetch_rows", "gph_engine_predictive_column_name",
     "gph_predictive_write", "gph_predictive_discard",
+    "gph_engine_triplets_enable", "gph_engine_triplets_sample", "gph_engine_triplets_shape", "gph_engine_triplets_selected",
+    "gph_engine_triplets_fetch_loci", "gph_engine_triplets_fetch_rows", "gph_engine_triplets_column_name",
+    "gph_triplets_write", "gph_triplets_discard",
 ]
 
 
@@ -559,6 +566,17 @@ def _load_library(path):
     lib.gph_engine_predictive_column_name.restype = C.c_char_p
     lib.gph_predictive_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_predictive_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_engine_triplets_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int64]
+    lib.gph_engine_triplets_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_triplets_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int32)]
+    lib.gph_engine_triplets_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_triplets_fetch_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    lib.gph_engine_triplets_fetch_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_triplets_column_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_triplets_column_name.restype = C.c_char_p
+    lib.gph_triplets_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_triplets_discard.argtypes = [C.c_char_p, C.c_int32]
     return lib
 
 
@@ -1491,6 +1509,67 @@ class Sampler:
         self._chk(self.lib.gph_engine_predictive_fetch_rows(self.engine, its.ctypes.data, rows.ctypes.data, obs.ctypes.data, rows.shape[0], C.byref(got)),
                   "predictive_fetch_rows")
         return its[:got.value].copy(), rows[:got.value].copy(), obs
+
+    # ---- triplet topology weights of selected loci (gph_engine_triplets_*): accumulated on the device, one sample per call
+    def triplets_enable(self, capacity, loci=None, triples=None, max_bytes=0):
+        """per-locus accumulators W, A of every (triple, topology) slot for the selected loci (as enable_gene_trees; None: all
+        loci of this rank) and a device buffer of `capacity` per-sample rows; capacity 0 switches the feature off.  triples:
+        None = every triple P < Q < R of current populations with samples, else a list of (P, Q, R) population indices in any
+        order.  ValueError for a refused selection or triple list (stderr names the cause; the sampler is left as it was),
+        MemoryError when accumulators and rows would exceed max_bytes (0: 1 GiB)"""
+        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
+        keep = sel if sel is None or len(sel) else np.zeros(1, dtype=np.int64)      # (a non-null pointer for an empty selection)
+        tri = None if triples is None else np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        tkeep = tri if tri is None or len(tri) else np.zeros((1, 3), dtype=np.int32)
+        rc = self.lib.gph_engine_triplets_enable(self.engine, int(capacity), None if sel is None else keep.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 0 if sel is None else len(sel), None if tri is None else tkeep.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 0 if tri is None else len(tri), int(max_bytes))
+        if rc == GPH_EFULL:
+            raise MemoryError("gphocs_hip: the triplets accumulators and rows exceed max_bytes (GPH_EFULL)")
+        if rc == -1:
+            raise ValueError("gphocs_hip: triplets_enable refused the capacity, the selection or the triples (GPH_EARG)")
+        self._chk(rc, "triplets_enable")
+
+    def triplets_sample(self, it):
+        """the weights of every selected locus under the current state, labelled iteration `it`; BufferError when the row
+        buffer is full"""
+        self._sample(self.lib.gph_engine_triplets_sample, "triplets row", "triplets_rows", int(it))
+
+    def _triplets_shape(self):
+        t, sl, q, S, held = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
+        self._chk(self.lib.gph_engine_triplets_shape(self.engine, C.byref(t), C.byref(sl), C.byref(q), C.byref(S), C.byref(held)), "triplets_shape")
+        return t.value, sl.value, q.value, S.value, held.value
+
+    def triplets_columns(self):
+        return [self.lib.gph_engine_triplets_column_name(self.engine, c).decode() for c in range(self._triplets_shape()[1])]
+
+    def triplets(self, reset=False):
+        """the accumulators of this rank's Q selected loci as the device holds them: a dict of loci[Q] (global indices), samples,
+        slots (the 3 T names "<X>,<Y>|<Z>", population indices), triples (T, 3), W and A (Q, T, 3) float64.  reset=True zeroes
+        them afterwards and restarts the sample count"""
+        T, slots, Q, S, _ = self._triplets_shape()
+        if slots == 0:
+            raise RuntimeError("gphocs_hip: triplets: not enabled (GPH_ESTATE)")
+        loci = np.zeros(max(Q, 1), dtype=np.int64)
+        cnt = C.c_int64()
+        self._chk(self.lib.gph_engine_triplets_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)),
+                  "triplets_selected")
+        names = self.triplets_columns()
+        acc = np.zeros((max(Q, 1), 2, T, 3), dtype=np.float64)
+        self._chk(self.lib.gph_engine_triplets_fetch_loci(self.engine, acc.ctypes.data, 2 * slots, int(bool(reset))), "triplets_fetch_loci")
+        triples = np.array([[int(x) for x in nm.replace("|", ",").split(",")] for nm in names[0::3]], dtype=np.int32).reshape(T, 3)
+        return dict(loci=loci[:Q].copy(), samples=S, slots=names, triples=triples, W=acc[:Q, 0].copy(), A=acc[:Q, 1].copy())
+
+    def triplets_rows(self):
+        """(iterations, rows): the per-sample rows taken since the last call, a uint64 (samples, 3 T) array of the totals of cnt
+        over THIS rank's selected loci, and their iterations; the device buffer is emptied"""
+        _, slots, _, _, held = self._triplets_shape()
+        if slots == 0:
+            raise RuntimeError("gphocs_hip: triplets_rows: not enabled (GPH_ESTATE)")
+        rows, its, got = np.zeros((max(held, 1), slots), dtype=np.uint64), np.zeros(max(held, 1), dtype=np.int32), C.c_int32()
+        self._chk(self.lib.gph_engine_triplets_fetch_rows(self.engine, its.ctypes.data, rows.ctypes.data, slots, rows.shape[0], C.byref(got)),
+                  "triplets_fetch_rows")
+        return its[:got.value].copy(), rows[:got.value].copy()
 
     def hbm_bytes(self):
         b = C.c_double()

@@ -32,6 +32,7 @@
 #include "gph_clades.h"
 #include "gph_ess.h"
 #include "gph_predictive.h"
+#include "gph_triplets.h"
 #include "gph_cladecmp.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
@@ -445,7 +446,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 23     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 24     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -562,6 +563,11 @@ struct gph_engine_state {
   // were last zeroed
   struct { char *d = nullptr; size_t o_obs = 0, o_key = 0, o_pop = 0, bytes = 0; GphPdShape shape = {}; SmSel sel; SmRows rows;
            std::vector<int32_t> iters; std::vector<int64_t> sites; uint64_t seed = 0; int64_t samples = 0; bool on = false; std::string name; } pd;
+  // triplet topology weights of selected loci (gph_triplets.h): ONE buffer in selection order -- acc [nsel][2][3 T] doubles (W,
+  // then A, of every slot), tri [T] packed triples, pop [n + Kc] bytes (leaf -> current population, then n_p) --, the per-sample
+  // rows [cap][3 T] u64 with their iterations, the triples as the caller sees them, samples since the accumulators were last zeroed
+  struct { char *d = nullptr; size_t o_tri = 0, o_pop = 0, bytes = 0; GphTrShape shape = {}; SmSel sel; SmRows rows;
+           std::vector<int32_t> iters, tri; int64_t samples = 0; bool on = false; std::string name; } tr;
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -788,7 +794,7 @@ static void dump_one_locus(const gph_engine *e, FILE *f, long long global_locus,
   }
 }
 
-extern "C" { static int clades_zero(gph_engine *e); static int ess_zero(gph_engine *e); static int predictive_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables, the ESS and the predictive accumulators) */
+extern "C" { static int clades_zero(gph_engine *e); static int ess_zero(gph_engine *e); static int predictive_zero(gph_engine *e); static int triplets_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables, the ESS and the predictive accumulators) */
 
 // after a host synchronisation: the error the stages recorded, the counters
 static int check_error(gph_engine *e)
@@ -971,6 +977,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp); dev_free(e->cl.sel.d_slot);
   dev_free(e->es.d); dev_free(e->es.sel.d_slot);
   dev_free(e->pd.d); dev_free(e->pd.sel.d_slot); dev_free(e->pd.rows.d);
+  dev_free(e->tr.d); dev_free(e->tr.sel.d_slot); dev_free(e->tr.rows.d);
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
   dev_free(e->d_red);
@@ -1306,6 +1313,9 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   e->pd.rows.fill = 0;
   e->pd.iters.clear();
   { int rcz = predictive_zero(e); if (rcz) return rcz; }
+  e->tr.rows.fill = 0;
+  e->tr.iters.clear();
+  { int rcz = triplets_zero(e); if (rcz) return rcz; }
   int rc = launch_loci(e, 3, k_init, e->seedz, e->d_mutRate, e->init_predraws);
   if (!rc) rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -3325,6 +3335,200 @@ const char *gph_engine_predictive_column_name(gph_engine *e, int32_t col)
     for (int q = p; q < Kc; q++)
       if (gph_pd_pair(Kc, p, q) == col) { e->pd.name = "diff_" + std::to_string(p) + "|" + std::to_string(q); return e->pd.name.c_str(); }
   return nullptr;
+}
+
+// ---- triplet topology weights of selected loci (gph_triplets.h)
+// the accumulators back to zero, the sample count with them
+static int triplets_zero(gph_engine *e)
+{
+  if (!e->tr.on) return 0;
+  e->tr.samples = 0;
+  return acc_zero(e, e->tr.d, e->tr.o_tri);
+}
+static void triplets_free(gph_engine *e)
+{
+  dev_free(e->tr.d);
+  e->tr.d = nullptr;
+  rows_free(e->tr.rows);
+  sel_free(e->tr.sel);
+  e->tr.iters.clear();
+  e->tr.tri.clear();
+  e->tr.shape = GphTrShape{};
+  e->tr.o_tri = e->tr.o_pop = e->tr.bytes = 0;
+  e->tr.samples = 0;
+  e->tr.on = false;
+}
+static int triplets_refuse(const char *fmt, long long a, long long b, long long c, long long d)
+{
+  fprintf(stderr, "gphocs_hip: triplets: ");
+  fprintf(stderr, fmt, a, b, c, d);
+  fputc('\n', stderr);
+  return GPH_EARG;
+}
+
+int gph_engine_triplets_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, const int32_t *triples, int32_t ntriples, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity_rows < 0 || (loci && nloci < 0) || (triples && ntriples < 0)) return GPH_EARG;
+  SETDEV(e);
+  if (capacity_rows == 0) { triplets_free(e); return 0; }
+  const int n = e->cfg.n, Kc = e->cfg.Kc;
+  /* every refusal before anything is freed or allocated: a refused call leaves the sampler as it was */
+  if (Kc < 3) return triplets_refuse("%lld current population(s): a triple needs three", Kc, 0, 0, 0);
+  if (n > 255) return triplets_refuse("%lld leaves: the byte counts of k_triplets hold 255 at most", n, 0, 0, 0);
+  if (loci)
+    for (int64_t k = 0; k < nloci; k++) {
+      if (loci[k] < 0 || loci[k] >= e->cfg.L_total) return triplets_refuse("locus %lld is out of range (0 .. %lld)", loci[k], e->cfg.L_total - 1, 0, 0);
+      if (k > 0 && loci[k] == loci[k - 1]) return triplets_refuse("locus %lld is named twice", loci[k], 0, 0, 0);
+      if (k > 0 && loci[k] < loci[k - 1]) return triplets_refuse("locus %lld stands behind locus %lld: the selection is not increasing", loci[k], loci[k - 1], 0, 0);
+    }
+  std::vector<int32_t> tri;
+  if (!triples) {
+    for (int P = 0; P < Kc; P++)
+      for (int Q = P + 1; Q < Kc; Q++)
+        for (int R = Q + 1; R < Kc; R++)
+          if (e->samplesPerPop[P] >= 1 && e->samplesPerPop[Q] >= 1 && e->samplesPerPop[R] >= 1) tri.push_back(gph_tr_pack(P, Q, R));
+  } else {
+    for (int32_t k = 0; k < ntriples; k++) {
+      int m[3] = {triples[3 * k], triples[3 * k + 1], triples[3 * k + 2]};
+      for (int a = 0; a < 3; a++)
+        if (m[a] < 0 || m[a] >= Kc) return triplets_refuse("triple %lld names population %lld: the current populations are 0 .. %lld", k, m[a], Kc - 1, 0);
+      std::sort(m, m + 3);
+      if (m[0] == m[1] || m[1] == m[2]) return triplets_refuse("triple %lld (%lld, %lld, %lld) repeats a population", k, triples[3 * k], triples[3 * k + 1], triples[3 * k + 2]);
+      for (int a = 0; a < 3; a++)
+        if (e->samplesPerPop[m[a]] < 1) return triplets_refuse("triple %lld names population %lld, which has no sample", k, m[a], 0, 0);
+      const int32_t word = gph_tr_pack(m[0], m[1], m[2]);
+      for (int32_t q = 0; q < k; q++)
+        if (tri[(size_t)q] == word) return triplets_refuse("triple %lld (%lld, %lld, %lld) is named twice", k, m[0], m[1], m[2]);
+      tri.push_back(word);
+    }
+  }
+  if (tri.empty()) return triplets_refuse("no triple of populations with samples", 0, 0, 0, 0);
+  const int T = (int)tri.size();
+  GphTrShape h;
+  gph_tr_shape(e->lay, T, h);
+  if (h.lds_bytes > 65536) return triplets_refuse("%lld leaves in %lld current populations need %lld bytes of LDS a workgroup (65536 at most)", n, Kc, h.lds_bytes, 0);
+  triplets_free(e);
+  int64_t nsel = 0;
+  if (!loci) nsel = e->L;
+  else for (int64_t k = 0; k < nloci; k++) nsel += loci[k] >= e->cfg.locus_begin && loci[k] < e->cfg.locus_begin + e->L;
+  const size_t npop = ((size_t)n + Kc + 15) & ~(size_t)15;
+  const size_t o_tri = (size_t)nsel * 2 * h.slots * 8, o_pop = (o_tri + (size_t)T * 4 + 15) & ~(size_t)15, bytes = o_pop + npop;
+  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
+  const int64_t need = (int64_t)bytes + (int64_t)capacity_rows * h.slots * 8;
+  if (need > limit) {
+    fprintf(stderr, "gphocs_hip: triplets: the accumulators and rows need %lld bytes (%lld loci x %d triples x 48 + %d rows x %d x 8 + %lld), the limit is %lld\n",
+            (long long)need, (long long)nsel, T, (int)capacity_rows, (int)h.slots, (long long)(bytes - o_tri), (long long)limit);
+    return GPH_EFULL;
+  }
+  { int rcs = sel_alloc(e, e->tr.sel, loci, nloci); if (rcs) return rcs; }
+  if (dev_alloc((void **)&e->tr.d, bytes)) { dev_clear_error(); e->tr.d = nullptr; triplets_free(e); return GPH_EHIP; }
+  if (rows_alloc(e->tr.rows, sizeof(uint64_t), h.slots, capacity_rows)) { dev_clear_error(); triplets_free(e); return GPH_EHIP; }
+  std::vector<uint8_t> pop(npop, 0);
+  for (int p = 0, i = 0; p < Kc; p++) {
+    for (int k = 0; k < e->samplesPerPop[p] && i < n; k++) pop[(size_t)i++] = (uint8_t)p;
+    pop[(size_t)n + p] = (uint8_t)e->samplesPerPop[p];
+  }
+  int rc = h2d(e, e->tr.d + o_tri, tri.data(), (size_t)T * 4);
+  if (!rc) rc = h2d(e, e->tr.d + o_pop, pop.data(), pop.size());
+  if (rc) { triplets_free(e); return rc; }
+  e->tr.shape = h;
+  e->tr.tri = tri;
+  e->tr.o_tri = o_tri; e->tr.o_pop = o_pop; e->tr.bytes = bytes;
+  e->tr.on = true;
+  return triplets_zero(e);
+}
+
+// one sample of the current state, queued on the engine's stream
+int gph_engine_triplets_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->tr.on) return GPH_ESTATE;
+  if (e->tr.rows.fill >= e->tr.rows.cap) return GPH_EFULL;
+  SETDEV(e);
+  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
+  uint64_t *row = (uint64_t *)rows_next(e->tr.rows);
+  { int rcz = acc_zero(e, row, sizeof(uint64_t) * (size_t)e->tr.rows.n); if (rcz) return rcz; }
+  const GphTrShape &h = e->tr.shape;
+  const int nsel = (int)e->tr.sel.loci.size(), groups = (nsel + h.G - 1) / h.G;
+  if (groups > 0) {        /* (a rank without a selected locus launches nothing: its row stays 0) */
+    int tms;
+    { int rcb = sample_begin(e, 23, tms); if (rcb) return rcb; }
+    { int rcl = launch_grid(e, GphGrid{groups, 1}, h.bd, (size_t)h.lds_bytes, k_triplets, e->lay, h, (const char *)e->dev.pages, (const int32_t *)e->tr.sel.d_slot,
+                            (const int32_t *)(e->tr.d + e->tr.o_tri), (const uint8_t *)(e->tr.d + e->tr.o_pop), nsel, (int)e->L, (double *)e->tr.d, row);
+      if (rcl) return rcl; }
+    sample_end(e, 23, 1, tms);
+  }
+  e->tr.iters.push_back(iteration);
+  e->tr.rows.fill++;
+  e->tr.samples++;
+  return 0;
+}
+
+int gph_engine_triplets_shape(gph_engine *e, int32_t *triples, int32_t *slots, int64_t *selected, int64_t *samples, int32_t *rows_held)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->tr.on;
+  if (triples) *triples = on ? e->tr.shape.T : 0;
+  if (slots) *slots = on ? e->tr.shape.slots : 0;
+  if (selected) *selected = on ? (int64_t)e->tr.sel.loci.size() : 0;
+  if (samples) *samples = on ? e->tr.samples : 0;
+  if (rows_held) *rows_held = on ? e->tr.rows.fill : 0;
+  return 0;
+}
+
+int gph_engine_triplets_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
+{
+  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
+  if (!e->tr.on) return GPH_ESTATE;
+  return sel_copy_out(e->tr.sel, out, max_loci, count);
+}
+
+// out [selected][ld], ld >= 2 slots: W of every slot, then A of every slot
+int gph_engine_triplets_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset)
+{
+  if (!e) return GPH_EARG;
+  if (!e->tr.on) return GPH_ESTATE;
+  const size_t nsel = e->tr.sel.loci.size(), w = 2 * (size_t)e->tr.shape.slots;
+  if ((nsel > 0 && !out) || ld < (int64_t)w) return GPH_EARG;
+  SETDEV(e);
+  if (nsel > 0) {
+    std::vector<double> acc(nsel * w);
+    { int rc = pull_rows(e, acc.data(), e->tr.d, e->tr.o_tri); if (rc) return rc; }
+    for (size_t q = 0; q < nsel; q++) memcpy(out + q * (size_t)ld, acc.data() + q * w, w * 8);
+  }
+  return reset ? triplets_zero(e) : 0;
+}
+
+// the rows taken since the last fetch (iters[rows], out[rows][ld], ld >= slots); the row buffer is empty again
+int gph_engine_triplets_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *out, int64_t ld, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || ((!out || !iters) && max_rows > 0)) return GPH_EARG;
+  if (!e->tr.on) return GPH_ESTATE;
+  SmRows &b = e->tr.rows;
+  if (max_rows < b.fill || (b.fill > 0 && ld < b.n)) return GPH_EARG;
+  SETDEV(e);
+  const size_t C = (size_t)b.n, held = (size_t)b.fill;
+  if (held > 0) {
+    std::vector<uint64_t> tmp(C * held);
+    { int rc = pull_rows(e, tmp.data(), b.d, b.esz * C * held); if (rc) return rc; }
+    for (size_t r = 0; r < held; r++) memcpy(out + r * (size_t)ld, tmp.data() + r * C, C * 8);
+  }
+  for (size_t r = 0; r < held; r++) iters[r] = e->tr.iters[r];
+  *rows = b.fill;
+  b.fill = 0;
+  e->tr.iters.clear();
+  return 0;
+}
+
+// slot 3 k + t of triple k = (P, Q, R): "<P>,<Q>|<R>", "<P>,<R>|<Q>", "<Q>,<R>|<P>" with the indices of the current populations
+const char *gph_engine_triplets_column_name(gph_engine *e, int32_t col)
+{
+  if (!e || !e->tr.on || col < 0 || col >= e->tr.shape.slots) return nullptr;
+  const uint32_t word = (uint32_t)e->tr.tri[(size_t)(col / 3)];
+  const int m[3] = {(int)(word & 255u), (int)((word >> 8) & 255u), (int)((word >> 16) & 255u)}, t = col % 3;
+  const int x = t == 2 ? m[1] : m[0], y = t == 0 ? m[1] : m[2], z = t == 0 ? m[2] : t == 1 ? m[1] : m[0];
+  e->tr.name = std::to_string(x) + "," + std::to_string(y) + "|" + std::to_string(z);
+  return e->tr.name.c_str();
 }
 
 // ---- two engines exchange their chain states (Metropolis-coupled chains)

@@ -1493,6 +1493,9 @@ struct Clades : Output {
 // ---- `--predictive PREFIX [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]`: posterior predictive checks
 #include "gph_predictive_run.h"
 
+// ---- `--triplets PREFIX [--triplets-pops "A,B,C;D,E,F"] [--triplets-loci SPEC] [--triplets-rows N]`: triplet topology weights
+#include "gph_triplets_run.h"
+
 // the enabled outputs in the order of their engine calls at a sample, which is also the order in which gph_run_finish writes
 // their files (the groups of fewer files first: should a later one fail, fewer are removed again).  A run closes them in the
 // opposite order, as it always did, and opens them in that order too: the summary is now enabled last, not first
@@ -1503,11 +1506,13 @@ struct Outputs {
   Clades *clades = nullptr;
   Ess *ess = nullptr;
   Predictive *predictive = nullptr;
+  Triplets *triplets = nullptr;
   explicit Outputs(const gph_run_options &o)
   {
     if (o.locus_summary_path) list.emplace_back(summary = new LocusSummary);
     if (o.ess_prefix) list.emplace_back(ess = new Ess(o));
     if (o.predictive_prefix) list.emplace_back(predictive = new Predictive(o));
+    if (o.triplets_prefix) list.emplace_back(triplets = new Triplets(o));
     if (o.clades_prefix) list.emplace_back(clades = new Clades(o));
     if (o.gene_trees_prefix) list.emplace_back(trees = new GeneTrees(o));
     if (o.ancestry_prefix) list.emplace_back(new Ancestry(o));
@@ -1781,11 +1786,13 @@ int run_chain(const gph_run_options &o)
   if ((rc = R.read_control())) return rc;
   if (outs.trees && (rc = outs.trees->check_names(R))) return rc;
   if (outs.clades && (rc = outs.clades->check_names(R))) return rc;
+  if (outs.triplets && (rc = outs.triplets->check_pops(R))) return rc;
   if ((rc = R.read_loci())) return rc;
   if (outs.trees && (rc = outs.trees->select(R))) return rc;
   if (outs.clades && (rc = outs.clades->select(R))) return rc;
   if (outs.ess && (rc = outs.ess->select(R))) return rc;
   if (outs.predictive && (rc = outs.predictive->select(R))) return rc;
+  if (outs.triplets && (rc = outs.triplets->select(R))) return rc;
   if ((rc = R.start_engine()) || (rc = R.open_trace())) return rc;
   if (o.beta != 0.0) {
     if ((rc = gph_mcmc_set_beta(R.M, option_beta(o)))) return R.fail(rc, "gph_mcmc_set_beta");
@@ -1856,7 +1863,7 @@ int run_chain(const gph_run_options &o)
   if (rcr) return rcr;
   if (checked && where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h, 12 gph_ess.h, 13 gph_predictive.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h, 12 gph_ess.h, 13 gph_predictive.h, 14 gph_triplets.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
     return GPH_EKERNEL;
   }
   if (outs.summary && (rc = outs.summary->write_table(R))) return rc;
@@ -2077,6 +2084,140 @@ extern "C" int gph_predictive_write(const char *prefix, int32_t ranks)
   return ok ? GPH_OK : GPH_EARG;
 }
 
+extern "C" int gph_triplets_discard(const char *prefix, int32_t ranks)
+{
+  if (!prefix) return GPH_EARG;
+  remove_parts(TR_PART, prefix, ranks);
+  for (const char *sfx : TR_FILES) unlink((std::string(prefix) + sfx).c_str());     /* (files only: whatever else sits there is not ours) */
+  return GPH_OK;
+}
+
+extern "C" int gph_triplets_write(const char *prefix, int32_t ranks)
+{
+  if (!prefix || ranks < 1) return GPH_EARG;
+  FILE *out[2] = {nullptr, nullptr};
+  bool ok = true;
+  for (int k = 0; k < 2 && ok; k++)
+    if (!(out[k] = fopen((std::string(prefix) + TR_FILES[k]).c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s%s\n", prefix, TR_FILES[k]); ok = false; }
+  long long S = -1, T = -1, rowsL = 0;
+  std::vector<std::string> names;                       /* [T][3] */
+  std::vector<unsigned long long> totals;               /* [sample][3 T] */
+  std::vector<long long> iters;
+  for (int r = 0; r < ranks && ok; r++) {
+    const std::string path = part_path(TR_PART, prefix, r);
+    FILE *in = fopen(path.c_str(), "r");
+    char *line = nullptr;
+    size_t cap = 0;
+    ssize_t len;
+    long long lines = 0, told = -1, sample = 0;
+    int at = 0;
+    while (in && ok && (len = getline(&line, &cap, in)) > 0) {
+      at++;
+      if (at == 1) { ok = !strcmp(line, "GPHTR1\n"); continue; }
+      if (at == 2) {
+        long long s = 0, t = 0;
+        int used = 0;
+        ok = sscanf(line, "H\t%lld\t%lld%n", &s, &t, &used) == 2 && (S < 0 || (s == S && t == T)) && t >= 1 && s >= 0 && line[len - 1] == '\n';
+        if (ok && S < 0) {
+          S = s; T = t;
+          std::string rest(line + used, (size_t)len - used - 1);
+          size_t from = 0;
+          while (from < rest.size() && rest[from] == '\t') {
+            const size_t to = std::min(rest.find('\t', from + 1), rest.size());
+            const std::string three = rest.substr(from + 1, to - from - 1);
+            const size_t c1 = three.find(','), c2 = c1 == std::string::npos ? c1 : three.find(',', c1 + 1);
+            if (c2 == std::string::npos) break;
+            names.push_back(three.substr(0, c1)); names.push_back(three.substr(c1 + 1, c2 - c1 - 1)); names.push_back(three.substr(c2 + 1));
+            from = to;
+          }
+          ok = (long long)names.size() == 3 * T;
+          if (ok) {
+            totals.assign((size_t)(S * 3 * T), 0);
+            iters.assign((size_t)S, 0);
+            fprintf(out[0], "locus\tname\tsamples\tP\tQ\tR\tw_PQ|R\tw_PR|Q\tw_QR|P\tage_PQ|R\tage_PR|Q\tage_QR|P\ttop\n");
+          }
+        }
+        continue;
+      }
+      if (told >= 0) { ok = false; break; }                      /* something behind the last line */
+      if (line[0] == 'E' && line[1] == '\t') { told = atoll(line + 2); continue; }
+      ok = len > 2 && line[len - 1] == '\n';
+      if (!ok) break;
+      lines++;
+      if (line[0] == 'L' && line[1] == '\t') { fputs(line + 2, out[0]); rowsL++; }
+      else if (line[0] == 'R' && line[1] == '\t') {
+        char *end = nullptr;
+        const long long it = strtoll(line + 2, &end, 10);
+        ok = sample < S && end != line + 2 && (r == 0 || iters[(size_t)sample] == it);
+        for (long long c = 0; c < 3 * T && ok; c++) {
+          char *from = end;
+          ok = *from == '\t';
+          if (!ok) break;
+          const unsigned long long v = strtoull(from + 1, &end, 10);
+          ok = end != from + 1;
+          totals[(size_t)(sample * 3 * T + c)] += v;
+        }
+        ok = ok && *end == '\n';
+        if (ok) iters[(size_t)sample++] = it;
+      } else ok = false;
+    }
+    free(line);
+    if (in) fclose(in);
+    if (!in || !ok || at < 2 || told != lines || sample != S) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); ok = false; }
+  }
+  if (ok) {
+    fprintf(out[1], "iter");
+    for (long long k = 0; k < T; k++) {
+      const std::string m[3] = {names[(size_t)(3 * k)], names[(size_t)(3 * k + 1)], names[(size_t)(3 * k + 2)]};
+      for (int t = 0; t < 3; t++) fprintf(out[1], "\t%s", tr_label(m, t).c_str());
+    }
+    fputc('\n', out[1]);
+    for (long long s = 0; s < S; s++) {
+      fprintf(out[1], "%7d", (int)iters[(size_t)s]);
+      for (long long c = 0; c < 3 * T; c++) fprintf(out[1], "\t%llu", totals[(size_t)(s * 3 * T + c)]);
+      fputc('\n', out[1]);
+    }
+    std::string most;
+    double most_d = -1.0;
+    for (long long k = 0; k < T; k++) {
+      const std::string m[3] = {names[(size_t)(3 * k)], names[(size_t)(3 * k + 1)], names[(size_t)(3 * k + 2)]};
+      unsigned long long sum[3] = {0, 0, 0};
+      for (long long s = 0; s < S; s++)
+        for (int t = 0; t < 3; t++) sum[t] += totals[(size_t)(s * 3 * T + 3 * k + t)];
+      int major = 0;
+      for (int t = 1; t < 3; t++) if (sum[t] > sum[major]) major = t;
+      const int ma = major == 0 ? 1 : 0, mb = major == 2 ? 1 : 2;
+      const double all = (double)sum[0] + (double)sum[1] + (double)sum[2];
+      std::vector<double> D((size_t)S);
+      double mean = 0.0, ss = 0.0;
+      long long pos = 0;
+      for (long long s = 0; s < S; s++) {
+        const double a = (double)totals[(size_t)(s * 3 * T + 3 * k + ma)], b = (double)totals[(size_t)(s * 3 * T + 3 * k + mb)];
+        D[(size_t)s] = a + b > 0.0 ? (a - b) / (a + b) : 0.0;
+        mean = mean + D[(size_t)s];
+        pos += D[(size_t)s] > 0.0;
+      }
+      mean = S > 0 ? mean / (double)S : 0.0;
+      for (long long s = 0; s < S; s++) ss = ss + (D[(size_t)s] - mean) * (D[(size_t)s] - mean);
+      const double sd = S > 1 ? sqrt(ss / (double)(S - 1)) : 0.0;
+      char num[256];
+      snprintf(num, sizeof num, " wMajor %.10g D %.10g sd %.10g pPos %.10g", all > 0.0 ? (double)sum[major] / all : 0.0, mean, sd, S > 0 ? (double)pos / (double)S : 0.0);
+      const std::string text = m[0] + "," + m[1] + "," + m[2] + " major " + tr_label(m, major) + " minorA " + tr_label(m, ma) + " minorB " + tr_label(m, mb) + num;
+      fprintf(out[1], "# asym %s\n", text.c_str());
+      if (fabs(mean) > most_d) { most_d = fabs(mean); most = text; }
+    }
+    fprintf(out[1], "# loci %lld samples %lld triples %lld\n", T > 0 ? rowsL / T : 0, S, T);
+    printf("Triplets: %s\n", most.c_str());
+    fflush(stdout);
+  }
+  for (int k = 0; k < 2; k++)
+    if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s%s failed\n", prefix, TR_FILES[k]); ok = false; }
+  remove_parts(TR_PART, prefix, ranks);
+  if (!ok)
+    for (int k = 0; k < 2; k++) if (out[k]) remove((std::string(prefix) + TR_FILES[k]).c_str());
+  return ok ? GPH_OK : GPH_EARG;
+}
+
 extern "C" int gph_run_finish(const gph_run_options *in, int32_t ranks, int32_t failed)
 {
   gph_run_options o;
@@ -2104,7 +2245,7 @@ extern "C" int gph_run(const gph_run_options *in)
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
   /* the checks on the options alone, before anything is read */
   int rc;
-  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = Ess::validate(o)) || (rc = Predictive::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
+  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = Ess::validate(o)) || (rc = Predictive::validate(o)) || (rc = Triplets::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
       (rc = Replicates::validate(o))) return rc;
   rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */

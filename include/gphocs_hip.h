@@ -246,7 +246,7 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * sweep's draws generated ahead of it (k_rng_ahead), 19 clade tables (gph_engine_clades_sample: k_clades), 20 the clade
  * tables of replicate chains compared (gph_engine_clades_compare: k_clades_compare, counted on engines[0]), 21 effective
  * sample sizes per locus (gph_engine_ess_sample: k_ess), 22 posterior predictive checks (gph_engine_predictive_sample:
- * k_predictive) */
+ * k_predictive), 23 triplet topology weights (gph_engine_triplets_sample: k_triplets) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -592,6 +592,54 @@ int gph_engine_predictive_selected(gph_engine *e, int64_t *out, int64_t max_loci
 int gph_engine_predictive_fetch_loci(gph_engine *e, double *acc /* [selected][C][5] */, int64_t *sites, int32_t reset);
 int gph_engine_predictive_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *rows_out, uint64_t *observed, int32_t max_rows, int32_t *rows);
 const char *gph_engine_predictive_column_name(gph_engine *e, int32_t col);
+
+/* TRIPLET TOPOLOGY WEIGHTS of selected loci and genome-wide per sample (k_triplets: csrc/gph_triplets.h; timing class 23): for
+ * three populations P, Q, R, how often are P and Q sisters, how often P and R, how often Q and R -- the topology weighting of
+ * Martin & Van Belleghem (2017, "Twisst"), the gene-tree form of the ABBA-BABA asymmetry: lineage sorting alone makes the two
+ * minority topologies equally frequent, an excess of one is the signature of gene flow.
+ *   populations  the Kc CURRENT populations in model order; leaf i belongs to the population whose samples hold it; n_p = its leaves
+ *   triples      P < Q < R (indices of current populations) with n_P, n_Q, n_R >= 1; default all, in lexicographic order
+ *   topologies   t = 0: PQ|R, 1: PR|Q, 2: QR|P; SLOT (triple, t) has number 3 triple + t
+ *   per node     one locus at one sample, v an internal node with children l = left[v], r = right[v], c_x[p] = the leaves of p in
+ *                the subtree of x (a leaf's own row: 1 at its population), tot[p] = n_p; for slot XY|Z
+ *                    w_v(XY|Z) = (c_l[X] c_r[Y] + c_r[X] c_l[Y]) (tot[Z] - c_l[Z] - c_r[Z])
+ *                = the leaf triples (a in X, b in Y, c in Z) with lca(a, b) = v and c outside v's subtree (a and b sisters
+ *                relative to c); an integer <= n_X n_Y n_Z < 2^32
+ *   per sample   of a slot: cnt = sum_v w_v (integer); age = sum_v age[v] (double)w_v over the internal nodes in NODE-INDEX order,
+ *                terms with w_v = 0 skipped, plain uncontracted fp64 (a multiply, then an add, no fma): the summed age of the
+ *                sister coalescence -- introgression makes it young, lineage sorting leaves it old
+ *   invariant    per triple sum_t cnt = n_P n_Q n_R at every sample (a binary tree gives each leaf triple exactly one topology)
+ *   accumulators per (selected locus, slot) two doubles: W = W + cnt (exact while S n_P n_Q n_R < 2^53), A = A + age, one plain
+ *                fp64 add a sample in sample order
+ *   rows         per sample the iteration and 3 T uint64 totals of cnt over the rank's selected loci (integer atomics: order-free;
+ *                the rows of the ranks add); a triple's three totals sum to (selected loci) n_P n_Q n_R
+ *   input        the settled node records a gene-tree record holds at that point of the chain
+ *   _enable      capacity_rows per-sample rows; 0 frees everything, the feature is off.  loci: NULL = all loci of the rank, else
+ *                nloci global indices, strictly increasing (those of other ranks' blocks are ignored).  triples: NULL = all, else
+ *                ntriples x 3 population indices (P, Q, R) in any order; the members are sorted, the triples keep the caller's
+ *                order.  GPH_EARG with a message that names the cause, nothing freed or allocated: fewer than 3 current
+ *                populations; a triple that repeats a population, names an index >= Kc or a population without samples, or is
+ *                named twice; a locus index >= the number of loci, negative, named twice or out of order.  GPH_EFULL, with the
+ *                size in the message and the feature off, when accumulators and rows exceed max_bytes (<= 0: 1 GiB): 48 T bytes a
+ *                selected locus.  GPH_ESTATE before the loci are loaded.  Enabling again frees and starts over.
+ *                gph_engine_init_genealogies zeroes the accumulators, the sample count and the rows held
+ *   _sample      one kernel on the engine's stream, no host synchronisation; a rank without a selected locus launches nothing and
+ *                still takes the (zero) row.  GPH_EFULL when the row buffer is full; GPH_ESTATE when off or before
+ *                gph_engine_init_genealogies
+ *   _shape       T, 3 T, selected loci of the rank, samples since the accumulators were zeroed, rows held (all 0 while off)
+ *   _fetch_loci  out[selected][ld], ld >= 6 T: W of the 3 T slots, then A of the 3 T slots; one copy and one host
+ *                synchronisation; reset != 0 zeroes the accumulators and the sample count afterwards
+ *   _fetch_rows  the rows taken since the last call (iters[rows], out[rows][ld], ld >= 3 T); the row buffer is empty again
+ *   _column_name slot col as "<X>,<Y>|<Z>" with the indices of the current populations: X and Y are the sisters
+ * The kernel writes no page, draws no random number and touches no chain state. */
+int gph_engine_triplets_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, const int32_t *triples /* [ntriples][3] */,
+                               int32_t ntriples, int64_t max_bytes);
+int gph_engine_triplets_sample(gph_engine *e, int32_t iteration);
+int gph_engine_triplets_shape(gph_engine *e, int32_t *triples, int32_t *slots, int64_t *selected, int64_t *samples, int32_t *rows_held);
+int gph_engine_triplets_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_triplets_fetch_loci(gph_engine *e, double *out /* [selected][ld] */, int64_t ld, int32_t reset);
+int gph_engine_triplets_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *out /* [rows][ld] */, int64_t ld, int32_t max_rows, int32_t *rows);
+const char *gph_engine_triplets_column_name(gph_engine *e, int32_t col);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -970,6 +1018,33 @@ typedef struct gph_run_options {
    * proper; every other output is the same bytes with and without. */
   const char *predictive_prefix, *predictive_loci, *predictive_seed;
   int32_t predictive_rows;
+  /* `--triplets PREFIX [--triplets-pops "A,B,C;D,E,F"] [--triplets-loci SPEC] [--triplets-rows N]`: triplet topology weights
+   * (gph_engine_triplets_* above).  A sample is taken wherever a trace line is written.  triplets_pops: the triples as names of
+   * current populations of the control file, three a triple, triples separated by ';' (NULL: all triples); triplets_loci as
+   * gene_trees_loci; triplets_rows: the rows of the device buffer (0: a default), fetched when it is full and at the end.  Any of
+   * the three without triplets_prefix and negative rows are GPH_EARG with a message, before anything is read; an unknown or
+   * repeated name, a triple named twice and a model with fewer than three current populations are GPH_EARG with a message that
+   * names the option, once the control file is read and before the sequence file is.  Rank r writes its part
+   * PREFIX.triplets.part<r> once, at the end.  gph_triplets_write makes of the parts (numbers "%.10g")
+   *   PREFIX.triplets.tsv         header locus name samples P Q R w_PQ|R w_PR|Q w_QR|P age_PQ|R age_PR|Q age_QR|P top; one row per
+   *                               (selected locus, triple) in sequence-file order, then triple order (the ranks' rows
+   *                               concatenated); P Q R the populations' names; w = W / (S n_P n_Q n_R); age = A / W (0 where
+   *                               W = 0) in the genealogy's own units; top = the label "<X>,<Y>|<Z>" of the slot with the largest
+   *                               W (ties: the lowest t)
+   *   PREFIX.triplets-genome.tsv  header iter, then per triple the labels "<X>,<Y>|<Z>" of its three slots (names); one row per
+   *                               sample, "%7d" and "\t%llu" per slot: the totals over the selected loci (the ranks' rows
+   *                               added); then per triple
+   *                                   # asym <P>,<Q>,<R> major <label> minorA <label> minorB <label> wMajor <v> D <mean> sd <v> pPos <v>
+   *                               major = the slot with the largest total over all samples (ties: the lowest t), the minors the
+   *                               other two in slot order with totals a and b per sample; wMajor = the major's share of the
+   *                               triple's total over all samples; D_s = (a - b) / (a + b) (0 when a + b = 0); D and sd the mean
+   *                               and the sample sd (divisor S - 1; 0 for S = 1) over the samples in sample order; pPos the
+   *                               fraction of samples with D_s > 0; and a last line "# loci Q samples S triples T"
+   * and prints "Triplets: " and the "# asym" values of the triple with the largest |D| (the first of equal ones) on stdout.  Both
+   * files are written once, on success only; a failed run leaves neither parts nor files.  With mc3_chains, replicates and
+   * marginal_prefix they describe chain 0 and the run proper; every other output is the same bytes with and without. */
+  const char *triplets_prefix, *triplets_pops, *triplets_loci;
+  int32_t triplets_rows;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
@@ -993,6 +1068,8 @@ int gph_ess_write(const char *prefix, int32_t ranks);
 int gph_ess_discard(const char *prefix, int32_t ranks);
 int gph_predictive_write(const char *prefix, int32_t ranks);
 int gph_predictive_discard(const char *prefix, int32_t ranks);
+int gph_triplets_write(const char *prefix, int32_t ranks);
+int gph_triplets_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
  * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
  * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
