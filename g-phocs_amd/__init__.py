@@ -933,10 +933,7 @@ def clades_compare(samplers, min_freq=0.1):
         raise ValueError("gphocs_hip: clades_compare refused the chains, their tables or min_freq (GPH_EARG)")
     Sampler._chk(rc, "clades_compare")
     rows = rows[:cnt.value]
-    loci = np.zeros(max(cnt.value, 1), dtype=np.int64)
-    n = C.c_int64()
-    Sampler._chk(lead.lib.gph_engine_clades_selected(lead.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(n)), "clades_selected")
-    out = dict(loci=loci[:cnt.value].copy(), asdsf=rows[:, 0].copy(), max_sd=rows[:, 1].copy())
+    out = dict(loci=lead._selected(lead.lib.gph_engine_clades_selected, cnt.value), asdsf=rows[:, 0].copy(), max_sd=rows[:, 1].copy())
     for k, name in enumerate(("compared", "distinct", "shared", "dropped")):
         out[name] = rows[:, 2 + k].astype(np.int64)
     return out
@@ -1170,16 +1167,42 @@ class Sampler:
             raise BufferError(f"gphocs_hip: the {what} buffer is full; fetch with {full}() first")
         self._chk(rc, fn.__name__[11:])
 
-    def _fetch_rows(self, fn, held, width, dtype=np.float64, with_iters=False):
-        """allocate from the shape, fetch, trim: the rows a sampler took since the last call (the device buffer is emptied)"""
-        ct = C.c_double if dtype is np.float64 else C.c_int32
+    def _fetch_rows(self, fn, held, width, dtype=np.float64, with_iters=False, ld=True, extra=()):
+        """allocate from the shape, fetch, trim: the rows a sampler took since the last call (the device buffer is emptied).
+        ld: the entry point takes the leading dimension of the rows behind them; extra: what else it takes behind those"""
+        ct = {np.float64: C.c_double, np.int32: C.c_int32, np.uint64: C.c_uint64}[dtype]
         out = np.zeros((max(held, 1), max(width, 1)), dtype=dtype)
         its = np.zeros(max(held, 1), dtype=np.int32)
         got = C.c_int32()
-        args = (its.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(C.POINTER(ct)), out.shape[1]) if with_iters else \
+        args = (its.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(C.POINTER(ct))) + ((out.shape[1],) if ld else ()) if with_iters else \
             (out.ctypes.data_as(C.POINTER(ct)),)
-        self._chk(fn(self.engine, *args, out.shape[0], C.byref(got)), fn.__name__[11:])
+        self._chk(fn(self.engine, *args, *extra, out.shape[0], C.byref(got)), fn.__name__[11:])
         return its[:got.value], out[:got.value]
+
+    @staticmethod
+    def _listed(arr, ct=C.c_int64):
+        """(pointer, count) of a list an _enable call takes: (None, 0) for None -- with loci: all of this rank --, and a
+        non-null pointer for an empty list, which is not the same"""
+        if arr is None:
+            return None, 0
+        keep = arr if len(arr) else np.zeros((1,) + arr.shape[1:], dtype=arr.dtype)
+        return keep.ctypes.data_as(C.POINTER(ct)), len(arr)
+
+    def _enabled(self, rc, call, full, refused):
+        """the return code of an _enable call over a selection: MemoryError `full` exceed(s) max_bytes, ValueError for what
+        the call `refused`, RuntimeError for the rest"""
+        if rc == GPH_EFULL:
+            raise MemoryError(f"gphocs_hip: {full} max_bytes (GPH_EFULL)")
+        if rc == -1:
+            raise ValueError(f"gphocs_hip: {call} refused {refused} (GPH_EARG)")
+        self._chk(rc, call)
+
+    def _selected(self, fn, Q):
+        """this rank's Q selected loci (global indices) as a sampler's _selected entry point hands them out"""
+        loci = np.zeros(max(Q, 1), dtype=np.int64)
+        cnt = C.c_int64()
+        self._chk(fn(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)), fn.__name__[11:])
+        return loci[:Q].copy()
 
     def _locus_columns(self, fetch, name, ncol, reset):
         """per-locus columns by name: one array entry per local locus in global locus order"""
@@ -1311,14 +1334,9 @@ class Sampler:
         """a device buffer of `capacity` samples of the selected loci (global 0-based indices, strictly increasing; None:
         all loci of this rank; indices of other ranks' blocks are ignored); capacity 0 switches the feature off.  ValueError
         for a negative index or a list that is not increasing, MemoryError when the buffer would exceed max_bytes (0: 256 MB)"""
-        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
-        rc = self.lib.gph_engine_gene_trees_enable(self.engine, int(capacity), None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                   0 if sel is None else len(sel), int(max_bytes))
-        if rc == GPH_EFULL:
-            raise MemoryError("gphocs_hip: the gene-trees row buffer exceeds max_bytes (GPH_EFULL)")
-        if rc == -1:
-            raise ValueError("gphocs_hip: gene_trees_enable refused the capacity or the selection (GPH_EARG)")
-        self._chk(rc, "gene_trees_enable")
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        self._enabled(self.lib.gph_engine_gene_trees_enable(self.engine, int(capacity), *sel, int(max_bytes)), "gene_trees_enable",
+                      "the gene-trees row buffer exceeds", "the capacity or the selection")
 
     def sample_gene_trees(self, it):
         """one sample of the current state, labelled iteration `it`; BufferError when the row buffer is full"""
@@ -1336,10 +1354,7 @@ class Sampler:
         genLnL [S, Q], and the live migrations in `living` order, mig_branch / mig_band / mig_spop / mig_tpop / mig_age
         [S, Q, 10] (-1 and age 0 beyond num_migs).  raw=True adds records: the bytes as fetched, uint8 [S, Q, record_bytes]"""
         Q, N, rb, off, held = self._gene_trees_shape()
-        loci = np.zeros(max(Q, 1), dtype=np.int64)
-        cnt = C.c_int64()
-        self._chk(self.lib.gph_engine_gene_trees_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)),
-                  "gene_trees_selected")
+        loci = self._selected(self.lib.gph_engine_gene_trees_selected, Q)
         buf = np.zeros((max(held, 1), max(Q * rb, 1)), dtype=np.uint8)
         its = np.zeros(max(held, 1), dtype=np.int32)
         got = C.c_int32()
@@ -1347,7 +1362,7 @@ class Sampler:
                                                        C.byref(got)), "gene_trees_fetch")
         S, M = got.value, GT_MAX_MIGS
         rec = np.ascontiguousarray(buf[:S, :Q * rb]).reshape(S, Q, rb)
-        out = dict(iters=its[:S].copy(), loci=loci[:Q].copy())
+        out = dict(iters=its[:S].copy(), loci=loci)
         shapes = dict(age=((S, Q, N), np.float64), father=((S, Q, N), np.int32), left=((S, Q, N), np.int32), right=((S, Q, N), np.int32),
                       npop=((S, Q, N), np.int32), root=((S, Q), np.int32), num_migs=((S, Q), np.int32), dataLnL=((S, Q), np.float64),
                       genLnL=((S, Q), np.float64), mig_branch=((S, Q, M), np.int32), mig_band=((S, Q, M), np.int32),
@@ -1365,14 +1380,9 @@ class Sampler:
         """per-locus clade tables of `slots` physical slots (a power of two; 0: the smallest one >= 8 (n - 1)) for the selected
         loci (as enable_gene_trees; None: all loci of this rank).  ValueError for refused slots or a refused selection,
         MemoryError when the tables would exceed max_bytes (0: 1 GiB); the sampler stays usable"""
-        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
-        rc = self.lib.gph_engine_clades_enable(self.engine, int(slots), None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int64)),
-                                               0 if sel is None else len(sel), int(max_bytes))
-        if rc == GPH_EFULL:
-            raise MemoryError("gphocs_hip: the clade tables exceed max_bytes (GPH_EFULL)")
-        if rc == -1:
-            raise ValueError("gphocs_hip: clades_enable refused the slots or the selection (GPH_EARG)")
-        self._chk(rc, "clades_enable")
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        self._enabled(self.lib.gph_engine_clades_enable(self.engine, int(slots), *sel, int(max_bytes)), "clades_enable",
+                      "the clade tables exceed", "the slots or the selection")
 
     def sample_clades(self):
         """one sample of the current state into the tables"""
@@ -1388,15 +1398,12 @@ class Sampler:
         slots (P), words (W), limit, nkeys[Q], dropped[Q], keys (Q, P, W) uint64, cnt (Q, P) uint64 (0: an empty slot) and
         age (Q, P) float64 (the age sums).  reset=True zeroes tables, header words and the sample count afterwards"""
         Q, P, W, lim, S = self._clades_shape()
-        loci = np.zeros(max(Q, 1), dtype=np.int64)
-        cnt = C.c_int64()
-        self._chk(self.lib.gph_engine_clades_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)),
-                  "clades_selected")
+        loci = self._selected(self.lib.gph_engine_clades_selected, Q)
         ent = np.zeros((max(Q, 1), max(P, 1), W + 2), dtype=np.uint64)
         nk, dr = np.zeros(max(Q, 1), dtype=np.uint32), np.zeros(max(Q, 1), dtype=np.uint32)
         self._chk(self.lib.gph_engine_clades_fetch(self.engine, ent.ctypes.data, nk.ctypes.data, dr.ctypes.data, int(bool(reset))), "clades_fetch")
         ent = ent[:Q, :P]
-        return dict(loci=loci[:Q].copy(), samples=S, slots=P, words=W, limit=lim, nkeys=nk[:Q].copy(), dropped=dr[:Q].copy(),
+        return dict(loci=loci, samples=S, slots=P, words=W, limit=lim, nkeys=nk[:Q].copy(), dropped=dr[:Q].copy(),
                     keys=ent[:, :, :W].copy(), cnt=ent[:, :, W].copy(), age=ent[:, :, W + 1].copy().view(np.float64))
 
     # ---- effective sample sizes of selected loci (gph_engine_ess_*): accumulated on the device, one sample per call
@@ -1404,15 +1411,8 @@ class Sampler:
         """the batch-sum levels of dataLnL, genLnL, tmrca, numMigs, topo (and rate under locus-mut-rate VAR) for the selected
         loci (as enable_gene_trees; None: all loci of this rank).  ValueError for a refused selection, MemoryError when the
         accumulators would exceed max_bytes (0: 1 GiB); the sampler stays usable"""
-        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
-        keep = sel if sel is None or len(sel) else np.zeros(1, dtype=np.int64)      # (a non-null pointer for an empty selection)
-        rc = self.lib.gph_engine_ess_enable(self.engine, None if sel is None else keep.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            0 if sel is None else len(sel), int(max_bytes))
-        if rc == GPH_EFULL:
-            raise MemoryError("gphocs_hip: the ESS accumulators exceed max_bytes (GPH_EFULL)")
-        if rc == -1:
-            raise ValueError("gphocs_hip: ess_enable refused the selection (GPH_EARG)")
-        self._chk(rc, "ess_enable")
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        self._enabled(self.lib.gph_engine_ess_enable(self.engine, *sel, int(max_bytes)), "ess_enable", "the ESS accumulators exceed", "the selection")
 
     def ess_sample(self):
         """one sample of the current state into the accumulators"""
@@ -1432,9 +1432,7 @@ class Sampler:
         Q, M, J, W, S = self._ess_shape()
         if M == 0:
             raise RuntimeError("gphocs_hip: ess: not enabled (GPH_ESTATE)")
-        loci = np.zeros(max(Q, 1), dtype=np.int64)
-        cnt = C.c_int64()
-        self._chk(self.lib.gph_engine_ess_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)), "ess_selected")
+        loci = self._selected(self.lib.gph_engine_ess_selected, Q)
         ni = max(self.pack.n - 1, 0)
         acc = np.zeros((max(Q, 1), M, 2 + 2 * J), dtype=np.float64)
         changes, focal = np.zeros(max(Q, 1), dtype=np.uint32), np.zeros((max(Q, 1), ni, W), dtype=np.uint64)
@@ -1448,7 +1446,7 @@ class Sampler:
                 tab[:, q, m] = ess_read(acc[q, m], S, level, self.lib)[:4]
         moved = tab[1] > 0.0
         min_ess = np.where(moved.any(axis=1), np.where(moved, tab[3], np.inf).min(axis=1), 0.0) if Q else np.zeros(0)
-        return dict(loci=loci[:Q].copy(), samples=S, series=ESS_SERIES[:M], levels=J, words=W, acc=acc.copy(), changes=changes.copy(),
+        return dict(loci=loci, samples=S, series=ESS_SERIES[:M], levels=J, words=W, acc=acc.copy(), changes=changes.copy(),
                     focal=focal.copy(), mean=tab[0], sd=tab[1], tau=tab[2], ess=tab[3], level=used, min_ess=min_ess)
 
     # ---- posterior predictive checks of selected loci (gph_engine_predictive_*): simulated on the device, one sample per call
@@ -1457,16 +1455,9 @@ class Sampler:
         this rank) and a device buffer of `capacity` per-sample rows; capacity 0 switches the feature off.  The replicates are
         a pure function of (seed, locus, sample, site, node).  ValueError for a refused selection or a locus whose statistics
         do not fit 32 bits, MemoryError when accumulators and rows would exceed max_bytes (0: 1 GiB); the sampler stays usable"""
-        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
-        keep = sel if sel is None or len(sel) else np.zeros(1, dtype=np.int64)      # (a non-null pointer for an empty selection)
-        rc = self.lib.gph_engine_predictive_enable(self.engine, int(seed) & 0xffffffffffffffff, int(capacity),
-                                                   None if sel is None else keep.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                   0 if sel is None else len(sel), int(max_bytes))
-        if rc == GPH_EFULL:
-            raise MemoryError("gphocs_hip: the predictive accumulators and rows exceed max_bytes (GPH_EFULL)")
-        if rc == -1:
-            raise ValueError("gphocs_hip: predictive_enable refused the capacity, the selection or a locus (GPH_EARG)")
-        self._chk(rc, "predictive_enable")
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        self._enabled(self.lib.gph_engine_predictive_enable(self.engine, int(seed) & 0xffffffffffffffff, int(capacity), *sel, int(max_bytes)),
+                      "predictive_enable", "the predictive accumulators and rows exceed", "the capacity, the selection or a locus")
 
     def predictive_sample(self, it):
         """one replicate of every selected locus under the current state, labelled iteration `it`; BufferError when the row
@@ -1488,14 +1479,11 @@ class Sampler:
         Q, nc, S, _ = self._predictive_shape()
         if nc == 0:
             raise RuntimeError("gphocs_hip: predictive: not enabled (GPH_ESTATE)")
-        loci = np.zeros(max(Q, 1), dtype=np.int64)
-        cnt = C.c_int64()
-        self._chk(self.lib.gph_engine_predictive_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)),
-                  "predictive_selected")
+        loci = self._selected(self.lib.gph_engine_predictive_selected, Q)
         names = self.predictive_columns()
         acc, sites = np.zeros((max(Q, 1), nc, 5), dtype=np.float64), np.zeros(max(Q, 1), dtype=np.int64)
         self._chk(self.lib.gph_engine_predictive_fetch_loci(self.engine, acc.ctypes.data, sites.ctypes.data, int(bool(reset))), "predictive_fetch_loci")
-        return dict(loci=loci[:Q].copy(), samples=S, stats=names, sites=sites[:Q].copy(), acc=acc[:Q].copy())
+        return dict(loci=loci, samples=S, stats=names, sites=sites[:Q].copy(), acc=acc[:Q].copy())
 
     def predictive_rows(self):
         """(iterations, rows, observed): the per-sample rows taken since the last call, a uint64 (samples, C) array of the
@@ -1504,11 +1492,9 @@ class Sampler:
         _, nc, _, held = self._predictive_shape()
         if nc == 0:
             raise RuntimeError("gphocs_hip: predictive_rows: not enabled (GPH_ESTATE)")
-        rows, its = np.zeros((max(held, 1), nc), dtype=np.uint64), np.zeros(max(held, 1), dtype=np.int32)
-        obs, got = np.zeros(nc, dtype=np.uint64), C.c_int32()
-        self._chk(self.lib.gph_engine_predictive_fetch_rows(self.engine, its.ctypes.data, rows.ctypes.data, obs.ctypes.data, rows.shape[0], C.byref(got)),
-                  "predictive_fetch_rows")
-        return its[:got.value].copy(), rows[:got.value].copy(), obs
+        obs = np.zeros(nc, dtype=np.uint64)
+        its, rows = self._fetch_rows(self.lib.gph_engine_predictive_fetch_rows, held, nc, np.uint64, with_iters=True, ld=False, extra=(obs.ctypes.data,))
+        return its.copy(), rows.copy(), obs
 
     # ---- triplet topology weights of selected loci (gph_engine_triplets_*): accumulated on the device, one sample per call
     def triplets_enable(self, capacity, loci=None, triples=None, max_bytes=0):
@@ -1517,18 +1503,10 @@ class Sampler:
         None = every triple P < Q < R of current populations with samples, else a list of (P, Q, R) population indices in any
         order.  ValueError for a refused selection or triple list (stderr names the cause; the sampler is left as it was),
         MemoryError when accumulators and rows would exceed max_bytes (0: 1 GiB)"""
-        sel = None if loci is None else np.ascontiguousarray(loci, dtype=np.int64)
-        keep = sel if sel is None or len(sel) else np.zeros(1, dtype=np.int64)      # (a non-null pointer for an empty selection)
-        tri = None if triples is None else np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
-        tkeep = tri if tri is None or len(tri) else np.zeros((1, 3), dtype=np.int32)
-        rc = self.lib.gph_engine_triplets_enable(self.engine, int(capacity), None if sel is None else keep.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                 0 if sel is None else len(sel), None if tri is None else tkeep.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                 0 if tri is None else len(tri), int(max_bytes))
-        if rc == GPH_EFULL:
-            raise MemoryError("gphocs_hip: the triplets accumulators and rows exceed max_bytes (GPH_EFULL)")
-        if rc == -1:
-            raise ValueError("gphocs_hip: triplets_enable refused the capacity, the selection or the triples (GPH_EARG)")
-        self._chk(rc, "triplets_enable")
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        tri = self._listed(None if triples is None else np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3), C.c_int32)
+        self._enabled(self.lib.gph_engine_triplets_enable(self.engine, int(capacity), *sel, *tri, int(max_bytes)), "triplets_enable",
+                      "the triplets accumulators and rows exceed", "the capacity, the selection or the triples")
 
     def triplets_sample(self, it):
         """the weights of every selected locus under the current state, labelled iteration `it`; BufferError when the row
@@ -1550,15 +1528,12 @@ class Sampler:
         T, slots, Q, S, _ = self._triplets_shape()
         if slots == 0:
             raise RuntimeError("gphocs_hip: triplets: not enabled (GPH_ESTATE)")
-        loci = np.zeros(max(Q, 1), dtype=np.int64)
-        cnt = C.c_int64()
-        self._chk(self.lib.gph_engine_triplets_selected(self.engine, loci.ctypes.data_as(C.POINTER(C.c_int64)), len(loci), C.byref(cnt)),
-                  "triplets_selected")
+        loci = self._selected(self.lib.gph_engine_triplets_selected, Q)
         names = self.triplets_columns()
         acc = np.zeros((max(Q, 1), 2, T, 3), dtype=np.float64)
         self._chk(self.lib.gph_engine_triplets_fetch_loci(self.engine, acc.ctypes.data, 2 * slots, int(bool(reset))), "triplets_fetch_loci")
         triples = np.array([[int(x) for x in nm.replace("|", ",").split(",")] for nm in names[0::3]], dtype=np.int32).reshape(T, 3)
-        return dict(loci=loci[:Q].copy(), samples=S, slots=names, triples=triples, W=acc[:Q, 0].copy(), A=acc[:Q, 1].copy())
+        return dict(loci=loci, samples=S, slots=names, triples=triples, W=acc[:Q, 0].copy(), A=acc[:Q, 1].copy())
 
     def triplets_rows(self):
         """(iterations, rows): the per-sample rows taken since the last call, a uint64 (samples, 3 T) array of the totals of cnt
@@ -1566,10 +1541,8 @@ class Sampler:
         _, slots, _, _, held = self._triplets_shape()
         if slots == 0:
             raise RuntimeError("gphocs_hip: triplets_rows: not enabled (GPH_ESTATE)")
-        rows, its, got = np.zeros((max(held, 1), slots), dtype=np.uint64), np.zeros(max(held, 1), dtype=np.int32), C.c_int32()
-        self._chk(self.lib.gph_engine_triplets_fetch_rows(self.engine, its.ctypes.data, rows.ctypes.data, slots, rows.shape[0], C.byref(got)),
-                  "triplets_fetch_rows")
-        return its[:got.value].copy(), rows[:got.value].copy()
+        its, rows = self._fetch_rows(self.lib.gph_engine_triplets_fetch_rows, held, slots, np.uint64, with_iters=True)
+        return its.copy(), rows.copy()
 
     def hbm_bytes(self):
         b = C.c_double()

@@ -463,6 +463,16 @@ struct SmSel {       // a selection of loci: those of this rank, global indices 
   std::vector<int64_t> loci;
   int32_t *d_slot = nullptr;
 };
+struct SmSelected {  // a sampler over a selection: what gene trees, clades, ESS, predictive checks and triplet weights keep alike
+  bool on = false;
+  SmSel sel;
+  int64_t samples = 0;                    // since the accumulators were last zeroed
+  char *d = nullptr;                      // its block on the device, in selection order
+  size_t bytes = 0;
+  SmRows rows;                            // per-sample rows with their iterations, where the sampler takes any
+  std::vector<int32_t> iters;
+  int (*zero)(gph_engine *) = nullptr;    // the accumulators back to zero, queued: the sampler's own step (selected_on sets it)
+};
 
 // what both builds keep of an engine; gph_backend.h completes it (struct gph_engine) with the members only one has
 struct gph_engine_state {
@@ -546,28 +556,24 @@ struct gph_engine_state {
   struct { double *d_acc = nullptr; SmRows rows; int32_t ncol = 0; int64_t samples = 0; GphAnShape shape = {}; std::vector<int32_t> iters; std::string name; } an;
   // sampled genealogies of selected loci (gph_genetrees.h): the rows of records, the selected loci of this rank (global indices,
   // increasing) with their slots in HBM, and the iterations of the rows held
-  struct { SmRows rows; GphGtShape shape = {}; SmSel sel; std::vector<int32_t> iters; } gt;
-  // clade tables of selected loci (gph_clades.h): entries [nsel][P][W + 2] and header words [nsel][2] in selection order, the
-  // selected loci of this rank with their slots in HBM, samples since the tables were last zeroed
+  struct : SmSelected { GphGtShape shape = {}; } gt;       // (no block, no accumulators: on while it has a row buffer)
+  // clade tables of selected loci (gph_clades.h): entries [nsel][P][W + 2] (the block) and header words [nsel][2] in selection order
   // d_cmp: the rows of the last gph_engine_clades_compare this engine led ([nsel][GPH_CC_COLS], allocated by the first one)
-  struct { uint64_t *d_ent = nullptr; uint32_t *d_hdr = nullptr; GphClShape shape = {}; SmSel sel;
-           int64_t samples = 0; bool on = false; double *d_cmp = nullptr; } cl;
+  struct : SmSelected { uint32_t *d_hdr = nullptr; GphClShape shape = {}; double *d_cmp = nullptr;
+                        uint64_t *ent() const { return (uint64_t *)d; } } cl;
   // effective sample sizes of selected loci (gph_ess.h): ONE buffer in selection order -- acc [nsel][M][GPH_ESS_WORDS] doubles,
-  // focal [nsel][n - 1][W] u64, prev [nsel] u64, changes [nsel] u32 (one buffer: a fetch is one copy and one synchronisation) --,
-  // the selected loci of this rank with their slots in HBM, samples since the accumulators were last zeroed
-  struct { char *d = nullptr; size_t o_focal = 0, o_prev = 0, o_changes = 0, bytes = 0; GphClShape shape = {}; SmSel sel;
-           int32_t M = 0; int64_t samples = 0, max_bytes = 0; bool on = false; } es;
+  // focal [nsel][n - 1][W] u64, prev [nsel] u64, changes [nsel] u32 (one buffer: a fetch is one copy and one synchronisation)
+  struct : SmSelected { size_t o_focal = 0, o_prev = 0, o_changes = 0; GphClShape shape = {}; int32_t M = 0; int64_t max_bytes = 0; } es;
   // posterior predictive checks of selected loci (gph_predictive.h): ONE buffer in selection order -- acc [nsel][C][5] doubles,
   // observed [C] u64 (the data's totals), key [nsel] u64 (Kl of each locus), pop [n] bytes (leaf -> current population) --, the
-  // per-sample rows [cap][C] u64 with their iterations, the sites of each selected locus, samples since the accumulators
-  // were last zeroed
-  struct { char *d = nullptr; size_t o_obs = 0, o_key = 0, o_pop = 0, bytes = 0; GphPdShape shape = {}; SmSel sel; SmRows rows;
-           std::vector<int32_t> iters; std::vector<int64_t> sites; uint64_t seed = 0; int64_t samples = 0; bool on = false; std::string name; } pd;
+  // per-sample rows [cap][C] u64 with their iterations, the sites of each selected locus
+  struct : SmSelected { size_t o_obs = 0, o_key = 0, o_pop = 0; GphPdShape shape = {}; std::vector<int64_t> sites; uint64_t seed = 0; std::string name; } pd;
   // triplet topology weights of selected loci (gph_triplets.h): ONE buffer in selection order -- acc [nsel][2][3 T] doubles (W,
   // then A, of every slot), tri [T] packed triples, pop [n + Kc] bytes (leaf -> current population, then n_p) --, the per-sample
-  // rows [cap][3 T] u64 with their iterations, the triples as the caller sees them, samples since the accumulators were last zeroed
-  struct { char *d = nullptr; size_t o_tri = 0, o_pop = 0, bytes = 0; GphTrShape shape = {}; SmSel sel; SmRows rows;
-           std::vector<int32_t> iters, tri; int64_t samples = 0; bool on = false; std::string name; } tr;
+  // rows [cap][3 T] u64 with their iterations, the triples as the caller sees them
+  struct : SmSelected { size_t o_tri = 0, o_pop = 0; GphTrShape shape = {}; std::vector<int32_t> tri; std::string name; } tr;
+  // the samplers with accumulators over a selection, in the order gph_engine_init_genealogies zeroes them
+  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr}; }
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -794,8 +800,6 @@ static void dump_one_locus(const gph_engine *e, FILE *f, long long global_locus,
   }
 }
 
-extern "C" { static int clades_zero(gph_engine *e); static int ess_zero(gph_engine *e); static int predictive_zero(gph_engine *e); static int triplets_zero(gph_engine *e); }     /* (gph_engine_init_genealogies zeroes the clade tables, the ESS and the predictive accumulators) */
-
 // after a host synchronisation: the error the stages recorded, the counters
 static int check_error(gph_engine *e)
 {
@@ -974,10 +978,8 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   dev_free(e->gt.rows.d); dev_free(e->gt.sel.d_slot);
-  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp); dev_free(e->cl.sel.d_slot);
-  dev_free(e->es.d); dev_free(e->es.sel.d_slot);
-  dev_free(e->pd.d); dev_free(e->pd.sel.d_slot); dev_free(e->pd.rows.d);
-  dev_free(e->tr.d); dev_free(e->tr.sel.d_slot); dev_free(e->tr.rows.d);
+  dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp);
+  for (SmSelected *s : e->selected()) { dev_free(s->d); dev_free(s->sel.d_slot); dev_free(s->rows.d); }
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
   dev_free(e->d_red);
@@ -1302,20 +1304,17 @@ int gph_engine_init_genealogies(gph_engine *e, double *sumGen, double *sumData)
   e->gt.iters.clear();
   { int rcz = acc_zero(e, e->ls.d, sizeof(double) * (size_t)e->ls.ncol * e->L); if (rcz) return rcz; }
   { int rcz = acc_zero(e, e->an.d_acc, sizeof(double) * (size_t)e->an.ncol * e->L); if (rcz) return rcz; }
-  { int rcz = clades_zero(e); if (rcz) return rcz; }
-  if (e->es.on && e->es.M != (e->var_rates ? 6 : 5)) {       /* the rate series comes and goes with `locus-mut-rate VAR` */
-    std::vector<int64_t> sel = e->es.sel.loci;
-    sel.push_back(0);                                         /* (a non-null pointer for an empty selection too) */
-    int rce = gph_engine_ess_enable(e, sel.data(), (int64_t)sel.size() - 1, e->es.max_bytes);
-    if (rce) return rce;
+  for (SmSelected *s : e->selected()) {
+    if (s == &e->es && e->es.on && e->es.M != (e->var_rates ? 6 : 5)) {       /* the rate series comes and goes with `locus-mut-rate VAR` */
+      std::vector<int64_t> sel = e->es.sel.loci;
+      sel.push_back(0);                                         /* (a non-null pointer for an empty selection too) */
+      int rce = gph_engine_ess_enable(e, sel.data(), (int64_t)sel.size() - 1, e->es.max_bytes);
+      if (rce) return rce;
+    }
+    s->rows.fill = 0;
+    s->iters.clear();
+    if (s->on) { s->samples = 0; int rcz = s->zero(e); if (rcz) return rcz; }
   }
-  { int rcz = ess_zero(e); if (rcz) return rcz; }
-  e->pd.rows.fill = 0;
-  e->pd.iters.clear();
-  { int rcz = predictive_zero(e); if (rcz) return rcz; }
-  e->tr.rows.fill = 0;
-  e->tr.iters.clear();
-  { int rcz = triplets_zero(e); if (rcz) return rcz; }
   int rc = launch_loci(e, 3, k_init, e->seedz, e->d_mutRate, e->init_predraws);
   if (!rc) rc = reduce_local(e, 0, GPH_OUT_SLOTS);
   if (!rc) rc = reduce_stats(e);
@@ -2347,7 +2346,14 @@ int gph_engine_dump_loci(gph_engine *e, const char *path, int32_t withCond, int3
   return 0;
 }
 
-// ---- the statistics samplers: one scaffold (settle, launch bookkeeping, row buffer, chunked partials) under four features
+// ---- the statistics samplers: one scaffold under nine features
+//   sample_settle, sample_run   what every _sample function does around its launches: the state settled, the row taken, what is
+//                               pending flushed, the timing events, the counters
+//   SmRows, SmParts             the row buffer and the chunked partials (coal stats, time slices)
+//   SmSel, SmSelected           a selection of loci, and the state of a sampler over one: selected_out, selected_free,
+//                               selected_on / selected_zero (zeroing itself stays each sampler's own step), over_limit
+//   rows_iters_fetch            the rows taken since the last fetch with their iterations
+//   leaf_pops                   the leaf -> current population bytes two kernels read
 // A sample reads the current state from the device, so whatever is still owed to it runs first; how much depends on what
 // the sampler's kernels read.  A deferred synchronizeEvents pass STAYS deferred at every level: it corrects event times only
 // (the one sampler that reads them applies the pass's arithmetic itself: vsync, gph_timeslices.h).
@@ -2385,6 +2391,36 @@ static void sample_end(gph_engine *e, int cls, int k, int tms)
   e->cls_launches[cls] += 1;
 }
 
+static void *rows_next(const SmRows &b) { return b.d + b.esz * (size_t)b.n * b.fill; }
+// what a sample leaves behind: a row of `rows` (zero: set to 0 first, outside the timing events), its iteration, one more sample
+struct SmTaken {
+  SmRows *rows = nullptr;
+  bool zero = false;
+  std::vector<int32_t> *iters = nullptr;
+  int32_t iteration = 0;
+  int64_t *samples = nullptr;
+};
+// one sample of a sampler that is on: the state settled to `level`, then k launches of timing class cls -- launch(row) queues
+// them; k == 0: a rank with nothing to launch, which takes its (empty or zero) row all the same -- then what the sample leaves
+extern "C++" { template <class Launch> static int sample_run(gph_engine *e, int level, int cls, int k, const SmTaken &t, Launch launch)
+{
+  if (t.rows && t.rows->fill >= t.rows->cap) return GPH_EFULL;
+  SETDEV(e);
+  { int rcs = sample_settle(e, level); if (rcs) return rcs; }
+  void *row = t.rows ? rows_next(*t.rows) : nullptr;
+  if (t.zero) { int rcz = acc_zero(e, row, t.rows->esz * (size_t)t.rows->n); if (rcz) return rcz; }
+  if (k > 0) {
+    int tms;
+    { int rcb = sample_begin(e, cls, tms); if (rcb) return rcb; }
+    { int rcl = launch(row); if (rcl) return rcl; }
+    sample_end(e, cls, k, tms);
+  }
+  if (t.iters) t.iters->push_back(t.iteration);
+  if (t.rows) t.rows->fill++;
+  if (t.samples) ++*t.samples;
+  return 0;
+} }
+
 static void rows_free(SmRows &b) { dev_free(b.d); b = SmRows{}; }
 static int rows_alloc(SmRows &b, size_t esz, int32_t n, int32_t cap)
 {
@@ -2392,13 +2428,32 @@ static int rows_alloc(SmRows &b, size_t esz, int32_t n, int32_t cap)
   b.esz = esz; b.n = n; b.cap = cap; b.fill = 0;
   return 0;
 }
-static void *rows_next(const SmRows &b) { return b.d + b.esz * (size_t)b.n * b.fill; }
 // every row taken since the last fetch into out, contiguous, and the buffer empty again
 static int rows_fetch(gph_engine *e, SmRows &b, void *out, int32_t *rows)
 {
   *rows = b.fill;
   if (b.fill > 0) { int rc = d2h(e, out, b.d, b.esz * (size_t)b.n * b.fill); if (rc) return rc; }
   b.fill = 0;
+  return 0;
+}
+// the same with the rows' iterations (`its`, emptied too), behind an entry point's own checks of its arguments: out[rows][ld]
+// elements, ld 0: the rows packed, copied straight into out (the ABI has no ld).  counted: the copy is the call's host synchronisation as the
+// counters see it (pull_rows) or the plain copy of rows_fetch -- the entry points differ in that, and keep differing
+static int rows_iters_fetch(gph_engine *e, SmRows &b, std::vector<int32_t> &its, int32_t *iters, void *out, int64_t ld, bool counted, int32_t *rows)
+{
+  SETDEV(e);
+  const size_t row = b.esz * (size_t)b.n, held = (size_t)b.fill;
+  if (held > 0 && row > 0) {       /* (rows without records: nothing to copy) */
+    std::vector<char> tmp(ld ? row * held : 0);
+    void *to = ld ? (void *)tmp.data() : out;
+    int rc = counted ? pull_rows(e, to, b.d, row * held) : d2h(e, to, b.d, row * held);
+    if (rc) return rc;
+    for (size_t r = 0; ld && r < held; r++) memcpy((char *)out + r * (size_t)ld * b.esz, tmp.data() + r * row, row);
+  }
+  for (size_t r = 0; r < held; r++) iters[r] = its[r];
+  *rows = b.fill;
+  b.fill = 0;
+  its.clear();
   return 0;
 }
 
@@ -2458,6 +2513,61 @@ static int sel_copy_out(const SmSel &s, int64_t *out, int64_t max_loci, int64_t 
   for (size_t q = 0; q < s.loci.size(); q++) out[q] = s.loci[q];
   return 0;
 }
+// gph_engine_*_selected: the selected loci of this rank of a sampler that is on (s null with e)
+static int selected_out(const gph_engine *e, const SmSelected *s, int64_t *out, int64_t max_loci, int64_t *count)
+{
+  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
+  if (!s->on) return GPH_ESTATE;
+  return sel_copy_out(s->sel, out, max_loci, count);
+}
+// off, everything on the device released (more: a sampler's further blocks) and every member as in a fresh engine
+extern "C++" { template <class S> static void selected_free(S &s, std::initializer_list<void *> more = {})
+{
+  dev_free(s.d);
+  for (void *p : more) dev_free(p);
+  rows_free(s.rows);
+  sel_free(s.sel);
+  s = S{};
+} }
+// the accumulators of a sampler back to zero, the sample count with them; and the end of an _enable: on, zeroed by `zero`
+static int selected_zero(gph_engine *e, SmSelected &s)
+{
+  if (!s.on) return 0;
+  s.samples = 0;
+  return s.zero(e);
+}
+static int selected_on(gph_engine *e, SmSelected &s, int (*zero)(gph_engine *))
+{
+  s.on = true;
+  s.zero = zero;
+  return selected_zero(e, s);
+}
+// the byte limit of a sampler's device memory, the caller's or 1 GiB: whether `need` exceeds it, then said on stderr as
+// "gphocs_hip: <what> need <need> bytes (<detail>), the limit is <limit>"
+__attribute__((format(printf, 4, 5))) static bool over_limit(int64_t need, int64_t max_bytes, const char *what, const char *detail, ...)
+{
+  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
+  if (need <= limit) return false;
+  char text[256];
+  va_list ap;
+  va_start(ap, detail);
+  vsnprintf(text, sizeof text, detail, ap);
+  va_end(ap);
+  fprintf(stderr, "gphocs_hip: %s need %lld bytes (%s), the limit is %lld\n", what, (long long)need, text, (long long)limit);
+  return true;
+}
+// leaf -> current population, one byte a leaf (leaves stand in population order), behind it with_counts ? the samples of each
+// population : nothing; padded to 16 bytes
+static std::vector<uint8_t> leaf_pops(const gph_engine *e, bool with_counts)
+{
+  const int n = e->cfg.n, Kc = e->cfg.Kc;
+  std::vector<uint8_t> pop(((size_t)n + (with_counts ? Kc : 0) + 15) & ~(size_t)15, 0);
+  for (int p = 0, i = 0; p < Kc; p++) {
+    for (int k = 0; k < e->samplesPerPop[p] && i < n; k++) pop[(size_t)i++] = (uint8_t)p;
+    if (with_counts) pop[(size_t)n + p] = (uint8_t)e->samplesPerPop[p];
+  }
+  return pop;
+}
 // per-locus accumulators [L][ncol] in slot order -> out, row h_orig[j] (the local locus slot j holds) of leading dimension ld
 static int fetch_by_locus(gph_engine *e, const double *d_acc, int ncol, bool column_major, double *out, int64_t ld)
 {
@@ -2497,17 +2607,14 @@ int gph_engine_locus_summary_enable(gph_engine *e, int32_t on)
 int gph_engine_locus_summary_sample(gph_engine *e)
 {
   if (!e || !e->initialized || !e->ls.d) return GPH_ESTATE;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_PAGES); if (rcs) return rcs; }
   const int first = e->ls.samples == 0;
   const int L = (int)e->L, ncol = e->ls.ncol, var = e->var_rates;
-  int tms;
-  { int rcb = sample_begin(e, 13, tms); if (rcb) return rcb; }
-  { int rcl = launch_grid(e, GphGrid{(L + GPH_LS_THREADS - 1) / GPH_LS_THREADS, 1}, GPH_LS_THREADS, 0, k_locus_summary,
-                          e->lay, e->dev.pages, e->ls.d, L, ncol, first, var); if (rcl) return rcl; }
-  sample_end(e, 13, 1, tms);
-  e->ls.samples++;
-  return 0;
+  SmTaken t;
+  t.samples = &e->ls.samples;
+  return sample_run(e, SETTLE_PAGES, 13, 1, t, [&](void *) {
+    return launch_grid(e, GphGrid{(L + GPH_LS_THREADS - 1) / GPH_LS_THREADS, 1}, GPH_LS_THREADS, 0, k_locus_summary,
+                       e->lay, e->dev.pages, e->ls.d, L, ncol, first, var);
+  });
 }
 
 int gph_engine_locus_summary_columns(gph_engine *e, int32_t *ncol, int64_t *samples)
@@ -2565,20 +2672,16 @@ int gph_engine_coal_stats_set_chunk(gph_engine *e, int32_t slots)
 int gph_engine_coal_stats_sample(gph_engine *e, int32_t iteration)
 {
   if (!e || !e->initialized || !e->cs.rows.d) return GPH_ESTATE;
-  if (e->cs.rows.fill >= e->cs.rows.cap) return GPH_EFULL;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_PAGES); if (rcs) return rcs; }
   const SmParts &p = e->cs.part;
   const int L = (int)e->L, n = e->cfg.n, K = e->cfg.K, B = e->cfg.B, bd = e->cs.bd;
   const int ntiles = (gph_cs_pairs(n) + bd - 1) / bd;
-  int tms;
-  { int rcb = sample_begin(e, 14, tms); if (rcb) return rcb; }
-  { int rcl = launch_grid(e, GphGrid{p.nchunks, ntiles}, bd, gph_cs_lds_bytes(n, K, B, bd), k_coal_stats,
-                          e->lay, e->dev.pages, p.d_part, L, p.chunk); if (rcl) return rcl; }
-  { int rcf = parts_fold(e, p, iteration, (double *)rows_next(e->cs.rows)); if (rcf) return rcf; }
-  sample_end(e, 14, 2, tms);
-  e->cs.rows.fill++;
-  return 0;
+  SmTaken t;
+  t.rows = &e->cs.rows;
+  return sample_run(e, SETTLE_PAGES, 14, 2, t, [&](void *row) {
+    int rcl = launch_grid(e, GphGrid{p.nchunks, ntiles}, bd, gph_cs_lds_bytes(n, K, B, bd), k_coal_stats,
+                          e->lay, e->dev.pages, p.d_part, L, p.chunk);
+    return rcl ? rcl : parts_fold(e, p, iteration, (double *)row);
+  });
 }
 
 int gph_engine_coal_stats_shape(gph_engine *e, int32_t *row_doubles, int32_t *filled, int32_t *n, int32_t *K)
@@ -2653,20 +2756,16 @@ int gph_engine_time_slices_set_chunk(gph_engine *e, int32_t slots)
 int gph_engine_time_slices_sample(gph_engine *e, int32_t iteration)
 {
   if (!e || !e->initialized || !e->ts.rows.d) return GPH_ESTATE;
-  if (e->ts.rows.fill >= e->ts.rows.cap) return GPH_EFULL;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_CHAIN); if (rcs) return rcs; }
   const SmParts &p = e->ts.part;
-  const int L = (int)e->L, vsync = e->sync_pending ? 1 : 0;
   const GphTsShape &h = e->ts.shape;
-  int tms;
-  { int rcb = sample_begin(e, 15, tms); if (rcb) return rcb; }
-  { int rcl = launch_grid(e, GphGrid{p.nchunks, h.ntiles}, h.bd, (size_t)h.lds_bytes, k_time_slices,
-                          e->lay, h, e->G_d, e->dev.pages, p.d_part, L, p.chunk, p.rd, vsync); if (rcl) return rcl; }
-  { int rcf = parts_fold(e, p, iteration, (double *)rows_next(e->ts.rows)); if (rcf) return rcf; }
-  sample_end(e, 15, 2, tms);
-  e->ts.rows.fill++;
-  return 0;
+  SmTaken t;
+  t.rows = &e->ts.rows;
+  return sample_run(e, SETTLE_CHAIN, 15, 2, t, [&](void *row) {
+    const int L = (int)e->L, vsync = e->sync_pending ? 1 : 0;       /* (read behind the settling) */
+    int rcl = launch_grid(e, GphGrid{p.nchunks, h.ntiles}, h.bd, (size_t)h.lds_bytes, k_time_slices,
+                          e->lay, h, e->G_d, e->dev.pages, p.d_part, L, p.chunk, p.rd, vsync);
+    return rcl ? rcl : parts_fold(e, p, iteration, (double *)row);
+  });
 }
 
 int gph_engine_time_slices_shape(gph_engine *e, int32_t *row_doubles, int32_t *filled, int32_t *slices, int32_t *K, int32_t *B,
@@ -2716,13 +2815,8 @@ int gph_engine_ancestry_enable(gph_engine *e, int32_t capacity_rows, int64_t max
   if (capacity_rows == 0) return 0;
   const int n = e->cfg.n, B = e->cfg.B;
   const int ncol = gph_an_locus_columns(n, B);
-  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
   const int64_t need = (int64_t)e->L * ncol * 8;
-  if (need > limit) {
-    fprintf(stderr, "gphocs_hip: ancestry: the per-locus accumulators need %lld bytes (%lld loci x %d leaves x %d columns x 8), the limit is %lld\n",
-            (long long)need, (long long)e->L, n, 2 * B + 1, (long long)limit);
-    return GPH_EFULL;
-  }
+  if (over_limit(need, max_bytes, "ancestry: the per-locus accumulators", "%lld loci x %d leaves x %d columns x 8", (long long)e->L, n, 2 * B + 1)) return GPH_EFULL;
   if (dev_alloc((void **)&e->an.d_acc, (size_t)need)) { e->an.d_acc = nullptr; return GPH_EHIP; }
   if (rows_alloc(e->an.rows, sizeof(uint32_t), gph_an_row_ints(n, B), capacity_rows)) {
     dev_free(e->an.d_acc);
@@ -2738,24 +2832,15 @@ int gph_engine_ancestry_enable(gph_engine *e, int32_t capacity_rows, int64_t max
 int gph_engine_ancestry_sample(gph_engine *e, int32_t iteration)
 {
   if (!e || !e->initialized || !e->an.rows.d) return GPH_ESTATE;
-  if (e->an.rows.fill >= e->an.rows.cap) return GPH_EFULL;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
   const int L = (int)e->L;
   const GphAnShape &h = e->an.shape;
   const int groups = (L + h.G - 1) / h.G;
-  uint32_t *row = (uint32_t *)rows_next(e->an.rows);
   const size_t row_bytes = sizeof(uint32_t) * (size_t)e->an.rows.n;
-  int tms;
-  { int rcb = sample_begin(e, 16, tms); if (rcb) return rcb; }
-  { int rcl = acc_zero(e, row, row_bytes);
-    if (!rcl) rcl = launch_grid(e, GphGrid{groups, 1}, h.bd, (size_t)h.lds_bytes, k_ancestry, e->lay, h, e->dev.pages, e->an.d_acc, row, L);
-    if (rcl) return rcl; }
-  sample_end(e, 16, 1, tms);
-  e->an.iters.push_back(iteration);
-  e->an.rows.fill++;
-  e->an.samples++;
-  return 0;
+  /* (this sampler zeroes its row between the timing events, as it always did: not SmTaken's zero, which goes in front) */
+  return sample_run(e, SETTLE_PAGES_AND_AGES, 16, 1, SmTaken{&e->an.rows, false, &e->an.iters, iteration, &e->an.samples}, [&](void *row) {
+    int rcl = acc_zero(e, row, row_bytes);
+    return rcl ? rcl : launch_grid(e, GphGrid{groups, 1}, h.bd, (size_t)h.lds_bytes, k_ancestry, e->lay, h, e->dev.pages, e->an.d_acc, (uint32_t *)row, L);
+  });
 }
 
 int gph_engine_ancestry_shape(gph_engine *e, int32_t *locus_columns, int32_t *row_ints, int64_t *samples, int32_t *rows_held)
@@ -2786,16 +2871,7 @@ int gph_engine_ancestry_fetch_rows(gph_engine *e, int32_t *iters, int32_t *out, 
   const SmRows &b = e->an.rows;
   if (!b.d) return GPH_ESTATE;
   if (max_rows < b.fill || (b.fill > 0 && ld < b.n)) return GPH_EARG;
-  SETDEV(e);
-  std::vector<uint32_t> tmp((size_t)b.n * b.fill);
-  int rc = rows_fetch(e, e->an.rows, tmp.data(), rows);
-  if (rc) return rc;
-  for (int32_t r = 0; r < *rows; r++) {
-    iters[r] = e->an.iters[(size_t)r];
-    memcpy(out + (size_t)r * ld, tmp.data() + (size_t)r * b.n, sizeof(uint32_t) * (size_t)b.n);
-  }
-  e->an.iters.clear();
-  return 0;
+  return rows_iters_fetch(e, e->an.rows, e->an.iters, iters, out, ld, false, rows);
 }
 
 const char *gph_engine_ancestry_column_name(gph_engine *e, int32_t which, int32_t col)
@@ -2823,10 +2899,7 @@ int gph_engine_gene_trees_enable(gph_engine *e, int32_t capacity_rows, const int
   if (!e || !e->loaded) return GPH_ESTATE;
   if (capacity_rows < 0 || !sel_valid(loci, nloci)) return GPH_EARG;
   SETDEV(e);
-  rows_free(e->gt.rows);
-  sel_free(e->gt.sel);
-  e->gt.iters.clear();
-  e->gt.shape = GphGtShape{};
+  selected_free(e->gt);
   if (capacity_rows == 0) return 0;
   { int rcs = sel_alloc(e, e->gt.sel, loci, nloci); if (rcs) return rcs; }
   const int64_t nsel = (int64_t)e->gt.sel.loci.size();
@@ -2842,36 +2915,27 @@ int gph_engine_gene_trees_enable(gph_engine *e, int32_t capacity_rows, const int
   }
   if (rows_alloc(e->gt.rows, (size_t)h.img.bytes, (int32_t)nsel, capacity_rows)) { sel_free(e->gt.sel); return GPH_EHIP; }
   e->gt.shape = h;
+  e->gt.on = true;
   return 0;
 }
 
 // one sample of the current state, queued on the engine's stream
 int gph_engine_gene_trees_sample(gph_engine *e, int32_t iteration)
 {
-  if (!e || !e->initialized || !e->gt.rows.d) return GPH_ESTATE;
-  if (e->gt.rows.fill >= e->gt.rows.cap) return GPH_EFULL;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
+  if (!e || !e->initialized || !e->gt.on) return GPH_ESTATE;
   const GphGtShape &h = e->gt.shape;
   const int nsel = e->gt.rows.n, L = (int)e->L;
   const int groups = (nsel + h.G - 1) / h.G;
-  if (groups > 0) {        /* (a rank without a selected locus launches nothing: a grid of no blocks is no legal launch) */
-    char *row = (char *)rows_next(e->gt.rows);
-    int tms;
-    { int rcb = sample_begin(e, 17, tms); if (rcb) return rcb; }
-    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_GT_THREADS, 0, k_gene_trees, e->lay, h, e->dev.pages, e->gt.sel.d_slot, nsel, L, row);
-      if (rcl) return rcl; }
-    sample_end(e, 17, 1, tms);
-  }
-  e->gt.iters.push_back(iteration);
-  e->gt.rows.fill++;
-  return 0;
+  /* (a rank without a selected locus launches nothing: a grid of no blocks is no legal launch) */
+  return sample_run(e, SETTLE_PAGES_AND_AGES, 17, groups > 0, SmTaken{&e->gt.rows, false, &e->gt.iters, iteration, nullptr}, [&](void *row) {
+    return launch_grid(e, GphGrid{groups, 1}, GPH_GT_THREADS, 0, k_gene_trees, e->lay, h, e->dev.pages, e->gt.sel.d_slot, nsel, L, (char *)row);
+  });
 }
 
 int gph_engine_gene_trees_shape(gph_engine *e, int64_t *selected, int32_t *nodes, int32_t *record_bytes, int32_t *offsets, int32_t *rows_held)
 {
   if (!e) return GPH_EARG;
-  const bool on = e->gt.rows.d != nullptr;
+  const bool on = e->gt.on;
   if (selected) *selected = on ? (int64_t)e->gt.sel.loci.size() : 0;
   if (nodes) *nodes = on ? e->lay.N : 0;
   if (record_bytes) *record_bytes = on ? e->gt.shape.img.bytes : 0;
@@ -2880,45 +2944,24 @@ int gph_engine_gene_trees_shape(gph_engine *e, int64_t *selected, int32_t *nodes
   return 0;
 }
 
-int gph_engine_gene_trees_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
-{
-  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
-  if (!e->gt.rows.d) return GPH_ESTATE;
-  return sel_copy_out(e->gt.sel, out, max_loci, count);
-}
+int gph_engine_gene_trees_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->gt : nullptr, out, max_loci, count); }
 
 int gph_engine_gene_trees_fetch(gph_engine *e, int32_t *iters, void *out, int32_t max_rows, int32_t *rows)
 {
   if (!e || !rows || max_rows < 0 || (!iters && max_rows > 0)) return GPH_EARG;
   SmRows &b = e->gt.rows;
-  if (!b.d) return GPH_ESTATE;
+  if (!e->gt.on) return GPH_ESTATE;
   if (max_rows < b.fill || (!out && b.fill > 0 && b.n > 0)) return GPH_EARG;       /* (rows without records need no `out`) */
-  SETDEV(e);
-  for (int32_t r = 0; r < b.fill; r++) iters[r] = e->gt.iters[(size_t)r];
-  if (b.n == 0) { *rows = b.fill; b.fill = 0; }       /* (rows without records: nothing to copy) */
-  else { int rc = rows_fetch(e, b, out, rows); if (rc) return rc; }
-  e->gt.iters.clear();
-  return 0;
+  return rows_iters_fetch(e, b, e->gt.iters, iters, out, 0, false, rows);
 }
 
 // ---- clade tables of selected loci (gph_clades.h)
-static size_t clades_entry_bytes(const gph_engine *e) { return sizeof(uint64_t) * e->cl.sel.loci.size() * (size_t)e->cl.shape.P * e->cl.shape.ew; }
 static int clades_zero(gph_engine *e)
 {
-  if (!e->cl.on) return 0;
-  e->cl.samples = 0;
-  { int rcz = acc_zero(e, e->cl.d_ent, clades_entry_bytes(e)); if (rcz) return rcz; }
+  { int rcz = acc_zero(e, e->cl.d, e->cl.bytes); if (rcz) return rcz; }
   return acc_zero(e, e->cl.d_hdr, sizeof(uint32_t) * 2 * e->cl.sel.loci.size());
 }
-static void clades_free(gph_engine *e)
-{
-  dev_free(e->cl.d_ent); dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp);
-  e->cl.d_ent = nullptr; e->cl.d_hdr = nullptr; e->cl.d_cmp = nullptr;
-  sel_free(e->cl.sel);
-  e->cl.shape = GphClShape{};
-  e->cl.samples = 0;
-  e->cl.on = false;
-}
+static void clades_free(gph_engine *e) { selected_free(e->cl, {e->cl.d_hdr, e->cl.d_cmp}); }
 
 int gph_engine_clades_enable(gph_engine *e, int32_t slots, const int64_t *loci, int64_t nloci, int64_t max_bytes)
 {
@@ -2931,44 +2974,36 @@ int gph_engine_clades_enable(gph_engine *e, int32_t slots, const int64_t *loci, 
   const size_t nsel = e->cl.sel.loci.size();
   GphClShape h;
   gph_cl_shape(e->lay, slots ? slots : gph_cl_default_slots(e->cfg.n), h);
-  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
   const int64_t per = (int64_t)h.P * h.ew * 8 + 8, need = (int64_t)nsel * per;
-  if (need > limit) {
-    fprintf(stderr, "gphocs_hip: clades: the tables need %lld bytes (%lld loci x (%d slots x %d words x 8 + 8)), the limit is %lld\n",
-            (long long)need, (long long)nsel, (int)h.P, (int)h.ew, (long long)limit);
+  if (over_limit(need, max_bytes, "clades: the tables", "%lld loci x (%d slots x %d words x 8 + 8)", (long long)nsel, (int)h.P, (int)h.ew)) {
     clades_free(e);
     return GPH_EFULL;
   }
-  if (dev_alloc((void **)&e->cl.d_ent, sizeof(uint64_t) * nsel * (size_t)h.P * h.ew) ||
-      dev_alloc((void **)&e->cl.d_hdr, sizeof(uint32_t) * 2 * nsel)) {
+  const size_t bytes = sizeof(uint64_t) * nsel * (size_t)h.P * h.ew;
+  if (dev_alloc((void **)&e->cl.d, bytes) || dev_alloc((void **)&e->cl.d_hdr, sizeof(uint32_t) * 2 * nsel)) {
     dev_clear_error();
     clades_free(e);
     return GPH_EHIP;
   }
   e->cl.shape = h;
-  e->cl.on = true;
-  return clades_zero(e);
+  e->cl.bytes = bytes;
+  return selected_on(e, e->cl, clades_zero);
 }
 
 // one sample of the current state, queued on the engine's stream
 int gph_engine_clades_sample(gph_engine *e)
 {
   if (!e || !e->initialized || !e->cl.on) return GPH_ESTATE;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
   const GphClShape &h = e->cl.shape;
   const int nsel = (int)e->cl.sel.loci.size(), L = (int)e->L;
   const int groups = (nsel + h.G - 1) / h.G;
-  if (groups > 0 && e->cfg.n > 1) {        /* (a rank without a selected locus launches nothing; one leaf has no clade) */
-    int tms;
-    { int rcb = sample_begin(e, 19, tms); if (rcb) return rcb; }
-    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_CL_THREADS, (size_t)h.lds_bytes, k_clades, e->lay, h, e->dev.pages, e->cl.sel.d_slot, nsel, L,
-                            e->cl.d_ent, e->cl.d_hdr);
-      if (rcl) return rcl; }
-    sample_end(e, 19, 1, tms);
-  }
-  e->cl.samples++;
-  return 0;
+  SmTaken t;
+  t.samples = &e->cl.samples;
+  /* (a rank without a selected locus launches nothing; one leaf has no clade) */
+  return sample_run(e, SETTLE_PAGES_AND_AGES, 19, groups > 0 && e->cfg.n > 1, t, [&](void *) {
+    return launch_grid(e, GphGrid{groups, 1}, GPH_CL_THREADS, (size_t)h.lds_bytes, k_clades, e->lay, h, e->dev.pages, e->cl.sel.d_slot, nsel, L,
+                       e->cl.ent(), e->cl.d_hdr);
+  });
 }
 
 int gph_engine_clades_shape(gph_engine *e, int64_t *selected, int32_t *slots, int32_t *words, int32_t *limit, int64_t *samples)
@@ -2983,12 +3018,7 @@ int gph_engine_clades_shape(gph_engine *e, int64_t *selected, int32_t *slots, in
   return 0;
 }
 
-int gph_engine_clades_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
-{
-  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
-  if (!e->cl.on) return GPH_ESTATE;
-  return sel_copy_out(e->cl.sel, out, max_loci, count);
-}
+int gph_engine_clades_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->cl : nullptr, out, max_loci, count); }
 
 int gph_engine_clades_fetch(gph_engine *e, uint64_t *entries, uint32_t *nkeys, uint32_t *dropped, int32_t reset)
 {
@@ -2999,11 +3029,11 @@ int gph_engine_clades_fetch(gph_engine *e, uint64_t *entries, uint32_t *nkeys, u
   SETDEV(e);
   if (nsel > 0) {
     std::vector<uint32_t> hdr(2 * nsel);
-    { int rc = d2h(e, entries, e->cl.d_ent, clades_entry_bytes(e)); if (rc) return rc; }
+    { int rc = d2h(e, entries, e->cl.d, e->cl.bytes); if (rc) return rc; }
     { int rc = d2h(e, hdr.data(), e->cl.d_hdr, sizeof(uint32_t) * 2 * nsel); if (rc) return rc; }
     for (size_t q = 0; q < nsel; q++) { nkeys[q] = hdr[2 * q]; dropped[q] = hdr[2 * q + 1]; }
   }
-  return reset ? clades_zero(e) : 0;
+  return reset ? selected_zero(e, e->cl) : 0;
 }
 
 // ---- the clade tables of R replicate chains compared where they lie (gph_cladecmp.h); engines[0] leads: its stream runs the
@@ -3038,7 +3068,7 @@ int gph_engine_clades_compare(gph_engine *const *engines, int32_t R, double min_
   }
   GphCcTables T;
   memset(&T, 0, sizeof T);
-  for (int r = 0; r < R; r++) { T.ent[r] = engines[r]->cl.d_ent; T.hdr[r] = engines[r]->cl.d_hdr; T.samples[r] = engines[r]->cl.samples; }
+  for (int r = 0; r < R; r++) { T.ent[r] = engines[r]->cl.ent(); T.hdr[r] = engines[r]->cl.d_hdr; T.samples[r] = engines[r]->cl.samples; }
   const int groups = (int)((nsel + GPH_CC_THREADS / GPH_CC_WAVE - 1) / (GPH_CC_THREADS / GPH_CC_WAVE));
   int tms, rc;
   if ((rc = compare_order_before(engines, R))) return rc;      /* (in front of the timing events: the kernel's time, not the wait) */
@@ -3051,23 +3081,8 @@ int gph_engine_clades_compare(gph_engine *const *engines, int32_t R, double min_
 }
 
 // ---- effective sample sizes of selected loci (gph_ess.h)
-static int ess_zero(gph_engine *e)
-{
-  if (!e->es.on) return 0;
-  e->es.samples = 0;
-  return acc_zero(e, e->es.d, e->es.bytes);
-}
-static void ess_free(gph_engine *e)
-{
-  dev_free(e->es.d);
-  e->es.d = nullptr;
-  sel_free(e->es.sel);
-  e->es.shape = GphClShape{};
-  e->es.o_focal = e->es.o_prev = e->es.o_changes = e->es.bytes = 0;
-  e->es.M = 0;
-  e->es.samples = 0;
-  e->es.on = false;
-}
+static int ess_zero(gph_engine *e) { return acc_zero(e, e->es.d, e->es.bytes); }
+static void ess_free(gph_engine *e) { selected_free(e->es); }
 
 int gph_engine_ess_enable(gph_engine *e, const int64_t *loci, int64_t nloci, int64_t max_bytes)
 {
@@ -3082,10 +3097,8 @@ int gph_engine_ess_enable(gph_engine *e, const int64_t *loci, int64_t nloci, int
   const int M = e->var_rates ? 6 : 5, ni = e->cfg.n > 1 ? e->cfg.n - 1 : 0;
   const size_t o_focal = nsel * (size_t)M * GPH_ESS_WORDS * 8, o_prev = o_focal + nsel * (size_t)ni * h.W * 8, o_changes = o_prev + nsel * 8,
                bytes = o_changes + nsel * 4;
-  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
-  if ((int64_t)bytes > limit) {
-    fprintf(stderr, "gphocs_hip: ess: the accumulators need %lld bytes (%lld loci x (%d series x %d doubles + %d focal keys of %d words + 12)), the limit is %lld\n",
-            (long long)bytes, (long long)nsel, M, GPH_ESS_WORDS, ni, (int)h.W, (long long)limit);
+  if (over_limit((int64_t)bytes, max_bytes, "ess: the accumulators", "%lld loci x (%d series x %d doubles + %d focal keys of %d words + 12)",
+                 (long long)nsel, M, GPH_ESS_WORDS, ni, (int)h.W)) {
     ess_free(e);
     return GPH_EFULL;
   }
@@ -3099,30 +3112,24 @@ int gph_engine_ess_enable(gph_engine *e, const int64_t *loci, int64_t nloci, int
   e->es.M = M;
   e->es.max_bytes = max_bytes;
   e->es.o_focal = o_focal; e->es.o_prev = o_prev; e->es.o_changes = o_changes; e->es.bytes = bytes;
-  e->es.on = true;
-  return ess_zero(e);
+  return selected_on(e, e->es, ess_zero);
 }
 
 // one sample of the current state, queued on the engine's stream
 int gph_engine_ess_sample(gph_engine *e)
 {
   if (!e || !e->initialized || !e->es.on) return GPH_ESTATE;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
   const GphClShape &h = e->es.shape;
   const int nsel = (int)e->es.sel.loci.size(), L = (int)e->L;
   const int groups = (nsel + h.G - 1) / h.G;
-  if (groups > 0 && e->cfg.n > 1) {        /* (a rank without a selected locus launches nothing; one leaf has no clade) */
-    int tms;
-    { int rcb = sample_begin(e, 21, tms); if (rcb) return rcb; }
-    { int rcl = launch_grid(e, GphGrid{groups, 1}, GPH_CL_THREADS, (size_t)gph_es_lds_bytes(e->lay, h), k_ess, e->lay, h, e->dev.pages,
-                            e->es.sel.d_slot, nsel, L, (int)e->es.M, (long long)e->es.samples, (double *)e->es.d,
-                            (uint64_t *)(e->es.d + e->es.o_focal), (uint64_t *)(e->es.d + e->es.o_prev), (uint32_t *)(e->es.d + e->es.o_changes));
-      if (rcl) return rcl; }
-    sample_end(e, 21, 1, tms);
-  }
-  e->es.samples++;
-  return 0;
+  SmTaken t;
+  t.samples = &e->es.samples;
+  /* (a rank without a selected locus launches nothing; one leaf has no clade) */
+  return sample_run(e, SETTLE_PAGES_AND_AGES, 21, groups > 0 && e->cfg.n > 1, t, [&](void *) {
+    return launch_grid(e, GphGrid{groups, 1}, GPH_CL_THREADS, (size_t)gph_es_lds_bytes(e->lay, h), k_ess, e->lay, h, e->dev.pages,
+                       e->es.sel.d_slot, nsel, L, (int)e->es.M, (long long)e->es.samples, (double *)e->es.d,
+                       (uint64_t *)(e->es.d + e->es.o_focal), (uint64_t *)(e->es.d + e->es.o_prev), (uint32_t *)(e->es.d + e->es.o_changes));
+  });
 }
 
 int gph_engine_ess_shape(gph_engine *e, int64_t *selected, int32_t *series, int32_t *levels, int32_t *words, int64_t *samples)
@@ -3137,12 +3144,7 @@ int gph_engine_ess_shape(gph_engine *e, int64_t *selected, int32_t *series, int3
   return 0;
 }
 
-int gph_engine_ess_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
-{
-  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
-  if (!e->es.on) return GPH_ESTATE;
-  return sel_copy_out(e->es.sel, out, max_loci, count);
-}
+int gph_engine_ess_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->es : nullptr, out, max_loci, count); }
 
 // acc [selected][series][2 + 2 levels], changes [selected], focal [selected][n - 1][words] (changes / focal may be null)
 int gph_engine_ess_fetch(gph_engine *e, double *acc, uint32_t *changes, uint64_t *focal, int32_t reset)
@@ -3159,7 +3161,7 @@ int gph_engine_ess_fetch(gph_engine *e, double *acc, uint32_t *changes, uint64_t
     if (focal) memcpy(focal, all.data() + e->es.o_focal, e->es.o_prev - e->es.o_focal);
     if (changes) memcpy(changes, all.data() + e->es.o_changes, nsel * 4);
   }
-  return reset ? ess_zero(e) : 0;
+  return reset ? selected_zero(e, e->es) : 0;
 }
 
 // ---- posterior predictive checks of selected loci (gph_predictive.h)
@@ -3175,8 +3177,6 @@ static int predictive_launch(gph_engine *e, int observed, uint64_t *row)
 // the accumulators back to zero, t back to 0, and the data's statistics formed again (they live in the same words)
 static int predictive_zero(gph_engine *e)
 {
-  if (!e->pd.on) return 0;
-  e->pd.samples = 0;
   { int rcz = acc_zero(e, e->pd.d, e->pd.o_key); if (rcz) return rcz; }
   if (e->pd.sel.loci.empty()) return 0;          /* (a rank without a selected locus launches nothing) */
   { int rcf = flush_pending(e); if (rcf) return rcf; }
@@ -3184,19 +3184,7 @@ static int predictive_zero(gph_engine *e)
   flat_launched(e, -1, 1);
   return 0;
 }
-static void predictive_free(gph_engine *e)
-{
-  dev_free(e->pd.d);
-  e->pd.d = nullptr;
-  rows_free(e->pd.rows);
-  sel_free(e->pd.sel);
-  e->pd.iters.clear();
-  e->pd.sites.clear();
-  e->pd.shape = GphPdShape{};
-  e->pd.o_obs = e->pd.o_key = e->pd.o_pop = e->pd.bytes = 0;
-  e->pd.samples = 0;
-  e->pd.on = false;
-}
+static void predictive_free(gph_engine *e) { selected_free(e->pd); }
 
 int gph_engine_predictive_enable(gph_engine *e, uint64_t seed, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int64_t max_bytes)
 {
@@ -3228,11 +3216,9 @@ int gph_engine_predictive_enable(gph_engine *e, uint64_t seed, int32_t capacity_
     e->pd.sites.push_back(sites);
   }
   const size_t o_obs = nsel * (size_t)h.C * GPH_PD_WORDS * 8, o_key = o_obs + (size_t)h.C * 8, o_pop = o_key + nsel * 8, bytes = o_pop + (((size_t)n + 15) & ~(size_t)15);
-  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
   const int64_t need = (int64_t)bytes + (int64_t)capacity_rows * h.C * 8;
-  if (need > limit) {
-    fprintf(stderr, "gphocs_hip: predictive: the accumulators and rows need %lld bytes (%lld loci x (%d statistics x 40 + 8) + %d rows x %d x 8 + %d), the limit is %lld\n",
-            (long long)need, (long long)nsel, (int)h.C, (int)capacity_rows, (int)h.C, (int)(h.C * 8 + ((n + 15) & ~15)), (long long)limit);
+  if (over_limit(need, max_bytes, "predictive: the accumulators and rows", "%lld loci x (%d statistics x 40 + 8) + %d rows x %d x 8 + %d",
+                 (long long)nsel, (int)h.C, (int)capacity_rows, (int)h.C, (int)(h.C * 8 + ((n + 15) & ~15)))) {
     predictive_free(e);
     return GPH_EFULL;
   }
@@ -3240,9 +3226,7 @@ int gph_engine_predictive_enable(gph_engine *e, uint64_t seed, int32_t capacity_
   if (rows_alloc(e->pd.rows, sizeof(uint64_t), h.C, capacity_rows)) { dev_clear_error(); predictive_free(e); return GPH_EHIP; }
   std::vector<uint64_t> key(nsel + 1);
   for (size_t q = 0; q < nsel; q++) key[q] = gph_pd_locus_key(seed, (uint64_t)e->pd.sel.loci[q]);
-  std::vector<uint8_t> pop(((size_t)n + 15) & ~(size_t)15, 0);
-  for (int p = 0, i = 0; p < Kc; p++)
-    for (int k = 0; k < e->samplesPerPop[p] && i < n; k++) pop[(size_t)i++] = (uint8_t)p;
+  const std::vector<uint8_t> pop = leaf_pops(e, false);
   int rc = 0;
   if (nsel > 0) rc = h2d(e, e->pd.d + o_key, key.data(), nsel * 8);
   if (!rc) rc = h2d(e, e->pd.d + o_pop, pop.data(), pop.size());
@@ -3250,29 +3234,16 @@ int gph_engine_predictive_enable(gph_engine *e, uint64_t seed, int32_t capacity_
   e->pd.shape = h;
   e->pd.seed = seed;
   e->pd.o_obs = o_obs; e->pd.o_key = o_key; e->pd.o_pop = o_pop; e->pd.bytes = bytes;
-  e->pd.on = true;
-  return predictive_zero(e);
+  return selected_on(e, e->pd, predictive_zero);
 }
 
 // one sample of the current state, queued on the engine's stream
 int gph_engine_predictive_sample(gph_engine *e, int32_t iteration)
 {
   if (!e || !e->initialized || !e->pd.on) return GPH_ESTATE;
-  if (e->pd.rows.fill >= e->pd.rows.cap) return GPH_EFULL;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
-  uint64_t *row = (uint64_t *)rows_next(e->pd.rows);
-  { int rcz = acc_zero(e, row, sizeof(uint64_t) * (size_t)e->pd.rows.n); if (rcz) return rcz; }
-  if (!e->pd.sel.loci.empty()) {        /* (a rank without a selected locus launches nothing: its row stays 0) */
-    int tms;
-    { int rcb = sample_begin(e, 22, tms); if (rcb) return rcb; }
-    { int rcl = predictive_launch(e, 0, row); if (rcl) return rcl; }
-    sample_end(e, 22, 1, tms);
-  }
-  e->pd.iters.push_back(iteration);
-  e->pd.rows.fill++;
-  e->pd.samples++;
-  return 0;
+  /* (a rank without a selected locus launches nothing: its row stays 0) */
+  return sample_run(e, SETTLE_PAGES_AND_AGES, 22, !e->pd.sel.loci.empty(), SmTaken{&e->pd.rows, true, &e->pd.iters, iteration, &e->pd.samples},
+                    [&](void *row) { return predictive_launch(e, 0, (uint64_t *)row); });
 }
 
 int gph_engine_predictive_shape(gph_engine *e, int64_t *selected, int32_t *stats, int64_t *samples, int32_t *rows_held)
@@ -3286,12 +3257,7 @@ int gph_engine_predictive_shape(gph_engine *e, int64_t *selected, int32_t *stats
   return 0;
 }
 
-int gph_engine_predictive_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
-{
-  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
-  if (!e->pd.on) return GPH_ESTATE;
-  return sel_copy_out(e->pd.sel, out, max_loci, count);
-}
+int gph_engine_predictive_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->pd : nullptr, out, max_loci, count); }
 
 // acc [selected][C][5] (obs, gt, eq, s1, s2), sites [selected] (may be null)
 int gph_engine_predictive_fetch_loci(gph_engine *e, double *acc, int64_t *sites, int32_t reset)
@@ -3303,7 +3269,7 @@ int gph_engine_predictive_fetch_loci(gph_engine *e, double *acc, int64_t *sites,
   SETDEV(e);
   if (nsel > 0) { int rc = pull_rows(e, acc, e->pd.d, e->pd.o_obs); if (rc) return rc; }
   if (sites) for (size_t q = 0; q < nsel; q++) sites[q] = e->pd.sites[q];
-  return reset ? predictive_zero(e) : 0;
+  return reset ? selected_zero(e, e->pd) : 0;
 }
 
 // the rows taken since the last fetch ([rows][C], with their iterations) and the data's totals (observed [C], may be null);
@@ -3315,14 +3281,9 @@ int gph_engine_predictive_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *ro
   SmRows &b = e->pd.rows;
   if (max_rows < b.fill) return GPH_EARG;
   SETDEV(e);
-  const size_t C = (size_t)b.n, held = (size_t)b.fill;
-  if (observed) { int rc = pull_rows(e, observed, e->pd.d + e->pd.o_obs, C * 8); if (rc) return rc; }
-  if (held > 0) { int rc = pull_rows(e, rows_out, b.d, b.esz * C * held); if (rc) return rc; }
-  for (size_t r = 0; r < held; r++) iters[r] = e->pd.iters[r];
-  *rows = b.fill;
-  b.fill = 0;
-  e->pd.iters.clear();
-  return 0;
+  if (observed) { int rc = pull_rows(e, observed, e->pd.d + e->pd.o_obs, (size_t)b.n * 8); if (rc) return rc; }
+  /* (no ld in this entry point: the rows arrive packed) */
+  return rows_iters_fetch(e, b, e->pd.iters, iters, rows_out, 0, true, rows);
 }
 
 // seg, then diff_<p>|<q> for the current populations p <= q (model order), p-major
@@ -3339,25 +3300,8 @@ const char *gph_engine_predictive_column_name(gph_engine *e, int32_t col)
 
 // ---- triplet topology weights of selected loci (gph_triplets.h)
 // the accumulators back to zero, the sample count with them
-static int triplets_zero(gph_engine *e)
-{
-  if (!e->tr.on) return 0;
-  e->tr.samples = 0;
-  return acc_zero(e, e->tr.d, e->tr.o_tri);
-}
-static void triplets_free(gph_engine *e)
-{
-  dev_free(e->tr.d);
-  e->tr.d = nullptr;
-  rows_free(e->tr.rows);
-  sel_free(e->tr.sel);
-  e->tr.iters.clear();
-  e->tr.tri.clear();
-  e->tr.shape = GphTrShape{};
-  e->tr.o_tri = e->tr.o_pop = e->tr.bytes = 0;
-  e->tr.samples = 0;
-  e->tr.on = false;
-}
+static int triplets_zero(gph_engine *e) { return acc_zero(e, e->tr.d, e->tr.o_tri); }
+static void triplets_free(gph_engine *e) { selected_free(e->tr); }
 static int triplets_refuse(const char *fmt, long long a, long long b, long long c, long long d)
 {
   fprintf(stderr, "gphocs_hip: triplets: ");
@@ -3373,7 +3317,9 @@ int gph_engine_triplets_enable(gph_engine *e, int32_t capacity_rows, const int64
   SETDEV(e);
   if (capacity_rows == 0) { triplets_free(e); return 0; }
   const int n = e->cfg.n, Kc = e->cfg.Kc;
-  /* every refusal before anything is freed or allocated: a refused call leaves the sampler as it was */
+  /* every refusal before anything is freed or allocated: a refused call leaves the sampler as it was.  (The other samplers
+   * free first, and refuse a selection through sel_valid without a message; this one says what is wrong with it and also
+   * holds it against the loci of all ranks) */
   if (Kc < 3) return triplets_refuse("%lld current population(s): a triple needs three", Kc, 0, 0, 0);
   if (n > 255) return triplets_refuse("%lld leaves: the byte counts of k_triplets hold 255 at most", n, 0, 0, 0);
   if (loci)
@@ -3412,56 +3358,35 @@ int gph_engine_triplets_enable(gph_engine *e, int32_t capacity_rows, const int64
   int64_t nsel = 0;
   if (!loci) nsel = e->L;
   else for (int64_t k = 0; k < nloci; k++) nsel += loci[k] >= e->cfg.locus_begin && loci[k] < e->cfg.locus_begin + e->L;
-  const size_t npop = ((size_t)n + Kc + 15) & ~(size_t)15;
-  const size_t o_tri = (size_t)nsel * 2 * h.slots * 8, o_pop = (o_tri + (size_t)T * 4 + 15) & ~(size_t)15, bytes = o_pop + npop;
-  const int64_t limit = max_bytes > 0 ? max_bytes : (int64_t)1 << 30;
+  const std::vector<uint8_t> pop = leaf_pops(e, true);
+  const size_t o_tri = (size_t)nsel * 2 * h.slots * 8, o_pop = (o_tri + (size_t)T * 4 + 15) & ~(size_t)15, bytes = o_pop + pop.size();
   const int64_t need = (int64_t)bytes + (int64_t)capacity_rows * h.slots * 8;
-  if (need > limit) {
-    fprintf(stderr, "gphocs_hip: triplets: the accumulators and rows need %lld bytes (%lld loci x %d triples x 48 + %d rows x %d x 8 + %lld), the limit is %lld\n",
-            (long long)need, (long long)nsel, T, (int)capacity_rows, (int)h.slots, (long long)(bytes - o_tri), (long long)limit);
-    return GPH_EFULL;
-  }
+  /* (nothing to free behind this refusal: the sampler is off already) */
+  if (over_limit(need, max_bytes, "triplets: the accumulators and rows", "%lld loci x %d triples x 48 + %d rows x %d x 8 + %lld",
+                 (long long)nsel, T, (int)capacity_rows, (int)h.slots, (long long)(bytes - o_tri))) return GPH_EFULL;
   { int rcs = sel_alloc(e, e->tr.sel, loci, nloci); if (rcs) return rcs; }
   if (dev_alloc((void **)&e->tr.d, bytes)) { dev_clear_error(); e->tr.d = nullptr; triplets_free(e); return GPH_EHIP; }
   if (rows_alloc(e->tr.rows, sizeof(uint64_t), h.slots, capacity_rows)) { dev_clear_error(); triplets_free(e); return GPH_EHIP; }
-  std::vector<uint8_t> pop(npop, 0);
-  for (int p = 0, i = 0; p < Kc; p++) {
-    for (int k = 0; k < e->samplesPerPop[p] && i < n; k++) pop[(size_t)i++] = (uint8_t)p;
-    pop[(size_t)n + p] = (uint8_t)e->samplesPerPop[p];
-  }
   int rc = h2d(e, e->tr.d + o_tri, tri.data(), (size_t)T * 4);
   if (!rc) rc = h2d(e, e->tr.d + o_pop, pop.data(), pop.size());
   if (rc) { triplets_free(e); return rc; }
   e->tr.shape = h;
   e->tr.tri = tri;
   e->tr.o_tri = o_tri; e->tr.o_pop = o_pop; e->tr.bytes = bytes;
-  e->tr.on = true;
-  return triplets_zero(e);
+  return selected_on(e, e->tr, triplets_zero);
 }
 
 // one sample of the current state, queued on the engine's stream
 int gph_engine_triplets_sample(gph_engine *e, int32_t iteration)
 {
   if (!e || !e->initialized || !e->tr.on) return GPH_ESTATE;
-  if (e->tr.rows.fill >= e->tr.rows.cap) return GPH_EFULL;
-  SETDEV(e);
-  { int rcs = sample_settle(e, SETTLE_PAGES_AND_AGES); if (rcs) return rcs; }
-  uint64_t *row = (uint64_t *)rows_next(e->tr.rows);
-  { int rcz = acc_zero(e, row, sizeof(uint64_t) * (size_t)e->tr.rows.n); if (rcz) return rcz; }
   const GphTrShape &h = e->tr.shape;
   const int nsel = (int)e->tr.sel.loci.size(), groups = (nsel + h.G - 1) / h.G;
-  if (groups > 0) {        /* (a rank without a selected locus launches nothing: its row stays 0) */
-    int tms;
-    { int rcb = sample_begin(e, 23, tms); if (rcb) return rcb; }
-    { int rcl = launch_grid(e, GphGrid{groups, 1}, h.bd, (size_t)h.lds_bytes, k_triplets, e->lay, h, (const char *)e->dev.pages, (const int32_t *)e->tr.sel.d_slot,
-                            (const int32_t *)(e->tr.d + e->tr.o_tri), (const uint8_t *)(e->tr.d + e->tr.o_pop), nsel, (int)e->L, (double *)e->tr.d, row);
-      if (rcl) return rcl; }
-    sample_end(e, 23, 1, tms);
-  }
-  e->tr.iters.push_back(iteration);
-  e->tr.rows.fill++;
-  e->tr.samples++;
-  return 0;
+  /* (a rank without a selected locus launches nothing: its row stays 0) */
+  return sample_run(e, SETTLE_PAGES_AND_AGES, 23, groups > 0, SmTaken{&e->tr.rows, true, &e->tr.iters, iteration, &e->tr.samples}, [&](void *row) {
+    return launch_grid(e, GphGrid{groups, 1}, h.bd, (size_t)h.lds_bytes, k_triplets, e->lay, h, (const char *)e->dev.pages, (const int32_t *)e->tr.sel.d_slot,
+                       (const int32_t *)(e->tr.d + e->tr.o_tri), (const uint8_t *)(e->tr.d + e->tr.o_pop), nsel, (int)e->L, (double *)e->tr.d, (uint64_t *)row);
+  });
 }
 
 int gph_engine_triplets_shape(gph_engine *e, int32_t *triples, int32_t *slots, int64_t *selected, int64_t *samples, int32_t *rows_held)
@@ -3476,12 +3401,7 @@ int gph_engine_triplets_shape(gph_engine *e, int32_t *triples, int32_t *slots, i
   return 0;
 }
 
-int gph_engine_triplets_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count)
-{
-  if (!e || !count || max_loci < 0 || (!out && max_loci > 0)) return GPH_EARG;
-  if (!e->tr.on) return GPH_ESTATE;
-  return sel_copy_out(e->tr.sel, out, max_loci, count);
-}
+int gph_engine_triplets_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->tr : nullptr, out, max_loci, count); }
 
 // out [selected][ld], ld >= 2 slots: W of every slot, then A of every slot
 int gph_engine_triplets_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset)
@@ -3496,7 +3416,7 @@ int gph_engine_triplets_fetch_loci(gph_engine *e, double *out, int64_t ld, int32
     { int rc = pull_rows(e, acc.data(), e->tr.d, e->tr.o_tri); if (rc) return rc; }
     for (size_t q = 0; q < nsel; q++) memcpy(out + q * (size_t)ld, acc.data() + q * w, w * 8);
   }
-  return reset ? triplets_zero(e) : 0;
+  return reset ? selected_zero(e, e->tr) : 0;
 }
 
 // the rows taken since the last fetch (iters[rows], out[rows][ld], ld >= slots); the row buffer is empty again
@@ -3506,18 +3426,7 @@ int gph_engine_triplets_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *out,
   if (!e->tr.on) return GPH_ESTATE;
   SmRows &b = e->tr.rows;
   if (max_rows < b.fill || (b.fill > 0 && ld < b.n)) return GPH_EARG;
-  SETDEV(e);
-  const size_t C = (size_t)b.n, held = (size_t)b.fill;
-  if (held > 0) {
-    std::vector<uint64_t> tmp(C * held);
-    { int rc = pull_rows(e, tmp.data(), b.d, b.esz * C * held); if (rc) return rc; }
-    for (size_t r = 0; r < held; r++) memcpy(out + r * (size_t)ld, tmp.data() + r * C, C * 8);
-  }
-  for (size_t r = 0; r < held; r++) iters[r] = e->tr.iters[r];
-  *rows = b.fill;
-  b.fill = 0;
-  e->tr.iters.clear();
-  return 0;
+  return rows_iters_fetch(e, b, e->tr.iters, iters, out, ld, true, rows);
 }
 
 // slot 3 k + t of triple k = (P, Q, R): "<P>,<Q>|<R>", "<P>,<R>|<Q>", "<Q>,<R>|<P>" with the indices of the current populations

@@ -4,40 +4,22 @@
 // trace line prints are kept on the host before formatting (Run::trace_kept, as the replicate chains' are) and go through
 // gph_ess once, at the end, on rank 0.  Per locus: k_ess keeps the levels on the device (gph_engine_ess_*); they are fetched
 // once, at the end, and read at the level with batch <= sqrt(samples).
-// Rank r's part PREFIX.ess.part<r> is text, written once when the chain is done: a first line GPHES1, "H\t<samples>\t<level>\t
+// Rank r's text part PREFIX.ess.part<r> (gph_textparts.h; EsJoin in gph_textjoin.h reads it): "H\t<samples>\t<level>\t
 // <series>", rank 0's rows of PREFIX.ess.tsv as "P\t" + row (its summary line included), this rank's rows of
-// PREFIX.locus-ess.tsv as "L\t<minEss, %a>\t" + row, and a last line "E\t<rows>", written when the rank closes its part.
-const PartFormat ES_PART = {{'G', 'P', 'H', 'E', 'S', '1', '\n', 0}, ".ess.part", 0, nullptr, false, nullptr, nullptr, 0, true};
-const char *const ES_FILES[2] = {".ess.tsv", ".locus-ess.tsv"};
-const char *const ES_SERIES[6] = {"essDataLnL", "essGenLnL", "essTmrca", "essNumMigs", "essTopo", "essRate"};
-
-struct Ess : Output {
-  const char *prefix, *spec;
-  std::vector<int64_t> sel;          /* this rank's selected loci (global indices) */
-  int64_t widest = 0;
+// PREFIX.locus-ess.tsv as "L\t<minEss, %a>\t" + row.
+struct Ess : TextOutput {
   std::vector<double> x, vals;       /* [sample][column]: what the trace lines print, before formatting; scratch */
-  FILE *f = nullptr;
-  explicit Ess(const gph_run_options &o) : prefix(o.ess_prefix), spec(o.ess_loci) {}
-  ~Ess() { if (f) fclose(f); }
+  explicit Ess(const gph_run_options &o) : TextOutput(ES_TEXT, o.ess_prefix, o.ess_loci, "--ess-loci") {}
   static int validate(const gph_run_options &o)
   {
     if (!o.ess_prefix && o.ess_loci) { fprintf(stderr, "gphocs_hip: --ess-loci needs --ess PREFIX\n"); return GPH_EARG; }
     return GPH_OK;
   }
-  int select(Run &R) { return select_loci(R, spec, "--ess-loci", sel, widest); }
   int open(Run &R) override
   {
-    const int64_t none = 0;
-    /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
-    if (int rc = gph_engine_ess_enable(R.E, sel.empty() ? &none : sel.data(), (int64_t)sel.size(), 0)) {
-      if (rc == GPH_EFULL) snprintf(R.err, sizeof R.err, "the accumulators exceed 1 GiB: narrow --ess-loci");
-      return R.fail(rc, "gph_engine_ess_enable");
-    }
-    if (!(f = fopen(part_path(ES_PART, prefix, R.rank).c_str(), "w"))) {
-      snprintf(R.err, sizeof R.err, "Could not open %s", part_path(ES_PART, prefix, R.rank).c_str());
-      return R.fail(GPH_EARG, "opening the ess part file");
-    }
-    fputs("GPHES1\n", f);
+    if (int rc = enabled(R, gph_engine_ess_enable(R.E, loci(), (int64_t)sel.size(), 0), "gph_engine_ess_enable",
+                         "the accumulators exceed 1 GiB: narrow --ess-loci")) return rc;
+    if (int rc = open_part(R)) return rc;
     vals.assign((size_t)R.mc.numParameters + 4, 0.0);
     return GPH_OK;
   }
@@ -59,8 +41,7 @@ struct Ess : Output {
     double r5[5] = {0, 0, 0, 0, 0};
     { const double zero[64] = {0}; gph_ess_read(zero, S, -1, r5); }        /* (the level of S samples) */
     const int level = (int)r5[4];
-    long long rows = 0;
-    fprintf(f, "H\t%lld\t%d\t%d\n", (long long)S, level, (int)M);
+    fprintf(part.f, "H\t%lld\t%d\t%d\n", (long long)S, level, (int)M);
     if (R.lead) {
       const std::vector<std::string> names = R.trace_columns();
       const int ncol = R.mc.numParameters + 2;
@@ -72,13 +53,11 @@ struct Ess : Output {
         double o8[8] = {S > 0 ? col[0] : 0.0, 0, 0, 0, 0, 0, (double)level, 0};
         if (S >= 2)
           if (int rc = gph_ess(col.data(), S, 0, o8)) return R.fail(rc, "gph_ess");
-        fprintf(f, "P\t%s\t%lld\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\t%d\n", names[(size_t)i].c_str(), (long long)S, o8[0], o8[1], o8[3], o8[5], o8[4], (int)o8[7]);
-        rows++;
+        part.line("P\t%s\t%lld\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\t%d\n", names[(size_t)i].c_str(), (long long)S, o8[0], o8[1], o8[3], o8[5], o8[4], (int)o8[7]);
         if (o8[1] > 0.0 && (worst_at < 0 || o8[5] < worst)) { worst = o8[5]; worst_at = i; }      /* (a constant column has no ESS) */
       }
-      fprintf(f, "P\t# samples %lld level %d batch %lld minEssAcf %.10g (%s)\n", (long long)S, level, 1ll << level, worst,
-              worst_at < 0 ? "-" : names[(size_t)worst_at].c_str());
-      rows++;
+      part.line("P\t# samples %lld level %d batch %lld minEssAcf %.10g (%s)\n", (long long)S, level, 1ll << level, worst,
+                worst_at < 0 ? "-" : names[(size_t)worst_at].c_str());
     }
     for (size_t q = 0; q < sel.size(); q++) {
       const char *nm = gph_loci_name(R.LC, sel[q]);
@@ -89,15 +68,12 @@ struct Ess : Output {
         e[m] = r5[3];
         if (r5[1] > 0.0 && (!any || r5[3] < least)) { least = r5[3]; any = true; }
       }
-      fprintf(f, "L\t%a\t%lld\t%s\t%lld", least, (long long)sel[q], nm ? nm : "", (long long)S);
-      for (int m = 0; m < M; m++) fprintf(f, "\t%.10g", e[m]);
-      fprintf(f, "\t%u\t%.10g\n", (unsigned)changes[q], least);
-      rows++;
+      std::string series;
+      char num[64];
+      for (int m = 0; m < M; m++) { snprintf(num, sizeof num, "\t%.10g", e[m]); series += num; }
+      part.line("L\t%a\t%lld\t%s\t%lld%s\t%u\t%.10g\n", least, (long long)sel[q], nm ? nm : "", (long long)S, series.c_str(), (unsigned)changes[q], least);
     }
-    fprintf(f, "E\t%lld\n", rows);
-    const int rcc = ferror(f) | fclose(f);
-    f = nullptr;
-    return R.check(rcc ? GPH_EARG : GPH_OK, "writing the ess part file");
+    return close_part(R);
   }
   int write(int32_t ranks) override { return gph_ess_write(prefix, ranks); }
   void discard(int32_t ranks) override { gph_ess_discard(prefix, ranks); }

@@ -4,26 +4,16 @@
 // Included by gph_program.cpp inside its anonymous namespace, behind the other outputs.  k_predictive keeps the per-locus
 // accumulators and the per-sample rows on the device (gph_engine_predictive_*); the rows are fetched whenever their buffer is
 // full and at the end, the accumulators once, at the end.
-// Rank r's part PREFIX.predictive.part<r> is text, written once when the chain is done: a first line GPHPD1,
+// Rank r's text part PREFIX.predictive.part<r> (gph_textparts.h; PdJoin in gph_textjoin.h reads it):
 // "H\t<samples>\t<statistics>\t<seed>" + "\t<name>" per statistic, this rank's rows of PREFIX.predictive.tsv as
 // "L\t<minP, %a>\t" + row, its observed totals as "O" + "\t<u64>" per statistic, its per-sample rows as "R\t<iteration>" +
-// "\t<u64>" per statistic, and a last line "E\t<lines>".  gph_predictive_write concatenates the L rows in rank order and adds
-// the O and R lines of the ranks statistic by statistic.
-const PartFormat PD_PART = {{'G', 'P', 'H', 'P', 'D', '1', '\n', 0}, ".predictive.part", 0, nullptr, false, nullptr, nullptr, 0, true};
-const char *const PD_FILES[2] = {".predictive.tsv", ".predictive-genome.tsv"};
-
-struct Predictive : Output {
-  const char *prefix, *spec, *seed_text;
-  int32_t capacity;
+// "\t<u64>" per statistic.
+struct Predictive : RowsOutput {
+  const char *seed_text;
   uint64_t seed = 0;
-  std::vector<int64_t> sel;          /* this rank's selected loci (global indices) */
-  int64_t widest = 0;
   int32_t C = 0;
-  std::vector<uint64_t> rows, buf;   /* every row taken so far [sample][C]; one fetch */
-  std::vector<int32_t> iters, ibuf;
-  FILE *f = nullptr;
-  explicit Predictive(const gph_run_options &o) : prefix(o.predictive_prefix), spec(o.predictive_loci), seed_text(o.predictive_seed), capacity(o.predictive_rows) {}
-  ~Predictive() { if (f) fclose(f); }
+  uint64_t *observed = nullptr;      /* where the next fetch of rows leaves the data's totals, if anywhere */
+  explicit Predictive(const gph_run_options &o) : RowsOutput(PD_TEXT, o.predictive_prefix, o.predictive_loci, "--predictive-loci", o.predictive_rows), seed_text(o.predictive_seed) {}
   static int validate(const gph_run_options &o)
   {
     if (!o.predictive_prefix && (o.predictive_loci || o.predictive_seed || o.predictive_rows)) {
@@ -39,43 +29,18 @@ struct Predictive : Output {
     }
     return GPH_OK;
   }
-  int select(Run &R) { return select_loci(R, spec, "--predictive-loci", sel, widest); }
   int open(Run &R) override
   {
-    const int64_t none = 0;
     seed = seed_text ? (uint64_t)strtoull(seed_text, nullptr, 10) : (uint64_t)(int64_t)R.mc.seed;
-    C = 1 + R.cfg.Kc * (R.cfg.Kc + 1) / 2;
-    if (capacity <= 0) capacity = cs_default_rows(C);
-    /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
-    if (int rc = gph_engine_predictive_enable(R.E, seed, capacity, sel.empty() ? &none : sel.data(), (int64_t)sel.size(), 0)) {
-      if (rc == GPH_EFULL) snprintf(R.err, sizeof R.err, "accumulators and rows exceed 1 GiB: narrow --predictive-loci or --predictive-rows");
-      return R.fail(rc, "gph_engine_predictive_enable");
-    }
-    if (!(f = fopen(part_path(PD_PART, prefix, R.rank).c_str(), "w"))) {
-      snprintf(R.err, sizeof R.err, "Could not open %s", part_path(PD_PART, prefix, R.rank).c_str());
-      return R.fail(GPH_EARG, "opening the predictive part file");
-    }
-    fputs("GPHPD1\n", f);
-    buf.assign((size_t)capacity * C, 0);
-    ibuf.assign((size_t)capacity, 0);
-    return GPH_OK;
+    size_rows(C = 1 + R.cfg.Kc * (R.cfg.Kc + 1) / 2);
+    if (int rc = enabled(R, gph_engine_predictive_enable(R.E, seed, capacity, loci(), (int64_t)sel.size(), 0), "gph_engine_predictive_enable",
+                         "accumulators and rows exceed 1 GiB: narrow --predictive-loci or --predictive-rows")) return rc;
+    return open_part(R);
   }
-  int flush(Run &R, uint64_t *observed)
-  {
-    int32_t got = 0;
-    if (int rc = gph_engine_predictive_fetch_rows(R.E, ibuf.data(), buf.data(), observed, capacity, &got)) return R.fail(rc, "gph_engine_predictive_fetch_rows");
-    rows.insert(rows.end(), buf.begin(), buf.begin() + (size_t)got * C);
-    iters.insert(iters.end(), ibuf.begin(), ibuf.begin() + got);
-    return GPH_OK;
-  }
-  int sample(Run &R, int it) override
-  {
-    int32_t held = 0;
-    gph_engine_predictive_shape(R.E, nullptr, nullptr, nullptr, &held);
-    if (held >= capacity)
-      if (int rc = flush(R, nullptr)) return rc;
-    return R.check(gph_engine_predictive_sample(R.E, it), "gph_engine_predictive_sample");
-  }
+  int32_t held(Run &R) override { int32_t h = 0; gph_engine_predictive_shape(R.E, nullptr, nullptr, nullptr, &h); return h; }
+  /* (the one rows fetch without a leading dimension: its rows are C wide) */
+  int fetch(Run &R, int32_t *got) override { return R.check(gph_engine_predictive_fetch_rows(R.E, ibuf.data(), buf.data(), observed, capacity, got), "gph_engine_predictive_fetch_rows"); }
+  int take(Run &R, int it) override { return R.check(gph_engine_predictive_sample(R.E, it), "gph_engine_predictive_sample"); }
   std::string stat_name(Run &R, int c) const
   {
     if (c == 0) return "seg";
@@ -89,17 +54,17 @@ struct Predictive : Output {
   {
     int64_t S = 0;
     gph_engine_predictive_shape(R.E, nullptr, nullptr, &S, nullptr);
-    std::vector<uint64_t> observed((size_t)C, 0);
-    if (int rc = flush(R, observed.data())) return rc;
+    std::vector<uint64_t> totals((size_t)C, 0);
+    observed = totals.data();
+    if (int rc = flush(R)) return rc;
     std::vector<double> acc(sel.size() * (size_t)C * 5 + 1);
     std::vector<int64_t> sites(sel.size() + 1);
     if (int rc = gph_engine_predictive_fetch_loci(R.E, acc.data(), sites.data(), 0)) return R.fail(rc, "gph_engine_predictive_fetch_loci");
     std::vector<std::string> names;
     for (int c = 0; c < C; c++) names.push_back(stat_name(R, c));
-    long long lines = 0;
-    fprintf(f, "H\t%lld\t%d\t%llu", (long long)S, (int)C, (unsigned long long)seed);
-    for (const std::string &nm : names) fprintf(f, "\t%s", nm.c_str());
-    fputc('\n', f);
+    fprintf(part.f, "H\t%lld\t%d\t%llu", (long long)S, (int)C, (unsigned long long)seed);
+    for (const std::string &nm : names) fprintf(part.f, "\t%s", nm.c_str());
+    fputc('\n', part.f);
     const double n = (double)S;
     for (size_t q = 0; q < sel.size(); q++) {
       const char *nm = gph_loci_name(R.LC, sel[q]);
@@ -117,24 +82,12 @@ struct Predictive : Output {
         snprintf(num, sizeof num, "\t%.10g\t%.10g\t%.10g\t%.10g", a[0], mean, sqrt(var), p);
         row += num;
       }
-      fprintf(f, "L\t%a\t%lld\t%s\t%lld\t%lld%s\t%.10g\t%s\n", minp, (long long)sel[q], nm ? nm : "", (long long)S, (long long)sites[q], row.c_str(), minp,
-              names[(size_t)at].c_str());
-      lines++;
+      part.line("L\t%a\t%lld\t%s\t%lld\t%lld%s\t%.10g\t%s\n", minp, (long long)sel[q], nm ? nm : "", (long long)S, (long long)sites[q], row.c_str(), minp,
+                names[(size_t)at].c_str());
     }
-    fputc('O', f);
-    for (int c = 0; c < C; c++) fprintf(f, "\t%llu", (unsigned long long)observed[(size_t)c]);
-    fputc('\n', f);
-    lines++;
-    for (size_t r = 0; r < iters.size(); r++) {
-      fprintf(f, "R\t%d", (int)iters[r]);
-      for (int c = 0; c < C; c++) fprintf(f, "\t%llu", (unsigned long long)rows[r * (size_t)C + c]);
-      fputc('\n', f);
-      lines++;
-    }
-    fprintf(f, "E\t%lld\n", lines);
-    const int rcc = ferror(f) | fclose(f);
-    f = nullptr;
-    return R.check(rcc ? GPH_EARG : GPH_OK, "writing the predictive part file");
+    part.numbers("O", nullptr, totals.data(), (size_t)C);
+    write_rows();
+    return close_part(R);
   }
   int write(int32_t ranks) override { return gph_predictive_write(prefix, ranks); }
   void discard(int32_t ranks) override { gph_predictive_discard(prefix, ranks); }

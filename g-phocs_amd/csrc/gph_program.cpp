@@ -2,6 +2,7 @@
 // (GPhoCS.c:84-238, 1232-1330, 1763-1769) over the engine: same control file, same sequence
 // file, same trace file.  Everything per-locus runs on the MI355X engine; there is no CPU path.
 #include "../../include/gphocs_hip.h"
+#include "gph_textjoin.h"
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -85,7 +86,8 @@ static int write_locus_summary(const std::string &path, bool header, const gph_c
 // (magic, a few 32-bit integers, for coal stats the loci of all ranks as int64, the byte count of the names and the names,
 // NUL-separated), one record per sample and, written when the rank closes its part, a trailer: the number of records (and,
 // for ancestry, the number of bytes of text that sit between the records and the trailer).  A part without that trailer, or
-// whose size does not match it, is refused.
+// whose size does not match it, is refused.  (Clade tables, ESS, predictive checks and triplet weights travel as text
+// parts instead: gph_textparts.h has their form, gph_textjoin.h what gph_run_finish makes of them.)
 //   coal stats  PREFIX.coal.part<r>      n, K, doubles per row | L | n sample names as printed, K population names | row, logPrior
 //   time slices PREFIX.slices.part<r>    S, K, B, doubles per row | K population names, B "src->tgt" band names | row
 //   ancestry    PREFIX.ancestry.part<r>  n, B, integers per row | n sample names, B band names | iteration, row (32-bit integers)
@@ -746,60 +748,6 @@ extern "C" int gph_gene_trees_write(const char *prefix, int32_t ranks)
   return ok ? GPH_OK : GPH_EARG;
 }
 
-// ---- clade tables (`--clades PREFIX`).  Rank r's part PREFIX.clades.part<r> is text, written once when the chain is done:
-// a first line GPHCL1, the rank's rows of the two files -- "C\t" + a row of PREFIX.clades.tsv, "T\t" + a row of
-// PREFIX.consensus.tsv, locus by locus -- and a last line "E\t<rows>", written when the rank closes its part
-namespace {
-const PartFormat CL_PART = {{'G', 'P', 'H', 'C', 'L', '1', '\n', 0}, ".clades.part", 0, nullptr, false, nullptr, nullptr, 0, true};
-const char *const CL_FILES[2] = {".clades.tsv", ".consensus.tsv"};
-}   // namespace
-
-extern "C" int gph_clades_discard(const char *prefix, int32_t ranks)
-{
-  if (!prefix) return GPH_EARG;
-  remove_parts(CL_PART, prefix, ranks);
-  for (const char *sfx : CL_FILES) unlink((std::string(prefix) + sfx).c_str());     /* (files only: whatever else sits there is not ours) */
-  return GPH_OK;
-}
-
-extern "C" int gph_clades_write(const char *prefix, int32_t ranks)
-{
-  if (!prefix || ranks < 1) return GPH_EARG;
-  FILE *out[2] = {nullptr, nullptr};
-  bool ok = true;
-  for (int k = 0; k < 2 && ok; k++)
-    if (!(out[k] = fopen((std::string(prefix) + CL_FILES[k]).c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s%s\n", prefix, CL_FILES[k]); ok = false; }
-  if (ok) {
-    fprintf(out[0], "locus\tname\tsamples\tdropped\tsize\tsupport\tmeanAge\tmembers\n");
-    fprintf(out[1], "locus\tname\tsamples\tdistinct\tdropped\tresolved\ttree\n");
-  }
-  for (int r = 0; r < ranks && ok; r++) {
-    const std::string path = part_path(CL_PART, prefix, r);
-    FILE *in = fopen(path.c_str(), "r");
-    char *line = nullptr;
-    size_t cap = 0;
-    ssize_t len;
-    long long rows = 0, told = -1;
-    bool first = true;
-    while (in && ok && (len = getline(&line, &cap, in)) > 0) {
-      if (first) { ok = !strcmp(line, "GPHCL1\n"); first = false; continue; }
-      if (told >= 0) { ok = false; break; }                      /* something behind the last line */
-      if (line[0] == 'E' && line[1] == '\t') { told = atoll(line + 2); continue; }
-      ok = len > 2 && line[1] == '\t' && (line[0] == 'C' || line[0] == 'T') && line[len - 1] == '\n';
-      if (ok) { fputs(line + 2, out[line[0] == 'C' ? 0 : 1]); rows++; }
-    }
-    free(line);
-    if (in) fclose(in);
-    if (!in || !ok || first || told != rows) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); ok = false; }
-  }
-  for (int k = 0; k < 2; k++)
-    if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s%s failed\n", prefix, CL_FILES[k]); ok = false; }
-  remove_parts(CL_PART, prefix, ranks);
-  if (!ok)
-    for (int k = 0; k < 2; k++) if (out[k]) remove((std::string(prefix) + CL_FILES[k]).c_str());
-  return ok ? GPH_OK : GPH_EARG;
-}
-
 // the selection of `--gene-trees-loci SPEC`: a comma list of i, i-j (both ends included) or i-j:step over 0 .. L - 1, sorted;
 // an index named twice or beyond the loci is refused by name
 static int gt_parse_spec(const char *spec, int64_t L, std::vector<int64_t> &sel, bool &all, const char *opt = "--gene-trees-loci")
@@ -1075,7 +1023,12 @@ void Run::trace_kept(gph_mcmc *m, double *v, std::vector<double> &x, double &log
 
 // ---- the outputs.  open: enable on the engine, take the shape, size the host buffer, open this rank's part and write its
 // header; sample: at a trace line, and a flush when the buffer is full; close: the last flush, the trailer, the part closed;
-// write / discard: what becomes of the ranks' parts once the last rank is done (gph_run_finish)
+// write / discard: what becomes of the ranks' parts once the last rank is done (gph_run_finish).
+//   Part          this rank's binary part (coal stats, time slices, ancestry, gene trees)
+//   Selected      an output over `--<name>-loci SPEC`: this rank's share of the selection, how it is handed to the engine, the
+//                 message of an enable call that found the selection too large
+//   TextOutput    a Selected whose part is text (gph_textparts.h): clades, ess and, through RowsOutput, predictive, triplets
+//   RowsOutput    a TextOutput that also keeps per-sample rows: fetched when the device buffer is full, printed as R lines
 struct Output {
   virtual ~Output() {}
   virtual int open(Run &R) = 0;
@@ -1326,23 +1279,88 @@ static int select_loci(Run &R, const char *spec, const char *opt, std::vector<in
   return GPH_OK;
 }
 
-// sampled genealogies: the row buffer for this rank's selected loci; the part's samples each behind their iteration
-struct GeneTrees : Output {
-  const char *prefix, *spec;
-  int32_t capacity, held = 0, rb = 0;
-  Part part{"gene-trees"};
+struct Selected : Output {
+  const char *const prefix, *const spec, *const opt;   /* opt: "--<name>-loci", as the messages name the selection */
   std::vector<int64_t> sel;          /* this rank's selected loci (global indices) */
   int64_t widest = 0;                /* selected loci of the rank that holds most: every rank takes the same decisions */
+  Selected(const char *prefix_, const char *spec_, const char *opt_) : prefix(prefix_), spec(spec_), opt(opt_) {}
+  int select(Run &R) { return select_loci(R, spec, opt, sel, widest); }
+  /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
+  const int64_t *loci() const { static const int64_t none = 0; return sel.empty() ? &none : sel.data(); }
+  /* the return code of `call`, an enable call; advice: what to narrow when the engine's byte limit refused it */
+  int enabled(Run &R, int rc, const char *call, const char *advice)
+  {
+    if (rc == GPH_EFULL) snprintf(R.err, sizeof R.err, "%s", advice);
+    return R.check(rc, call);
+  }
+};
+
+struct TextOutput : Selected {
+  const TextPart &F;
+  TextWriter part;
+  TextOutput(const TextPart &F_, const char *prefix_, const char *spec_, const char *opt_) : Selected(prefix_, spec_, opt_), F(F_) {}
+  int open_part(Run &R)
+  {
+    if (part.open(F, prefix, R.rank)) return GPH_OK;
+    snprintf(R.err, sizeof R.err, "Could not open %s", text_part_path(F, prefix, R.rank).c_str());
+    return R.fail(GPH_EARG, ("opening the " + std::string(F.name) + " part file").c_str());
+  }
+  int close_part(Run &R) { return R.check(part.close() ? GPH_OK : GPH_EARG, ("writing the " + std::string(F.name) + " part file").c_str()); }
+};
+
+struct RowsOutput : TextOutput {
+  int32_t capacity, width = 0;       /* rows of the device buffer, numbers of a row */
+  std::vector<uint64_t> rows, buf;   /* every row taken so far [sample][width]; one fetch */
+  std::vector<int32_t> iters, ibuf;
+  RowsOutput(const TextPart &F_, const char *prefix_, const char *spec_, const char *opt_, int32_t rows_) : TextOutput(F_, prefix_, spec_, opt_), capacity(rows_) {}
+  virtual int32_t held(Run &R) = 0;                  /* rows in the device buffer */
+  virtual int fetch(Run &R, int32_t *got) = 0;       /* they into ibuf, buf */
+  virtual int take(Run &R, int it) = 0;              /* one sample on the engine */
+  /* the row width is known and the capacity settled: 0 asked for the default */
+  void size_rows(int32_t w)
+  {
+    width = w;
+    if (capacity <= 0) capacity = cs_default_rows(width);
+  }
+  int open_part(Run &R)
+  {
+    buf.assign((size_t)capacity * width, 0);
+    ibuf.assign((size_t)capacity, 0);
+    return TextOutput::open_part(R);
+  }
+  int flush(Run &R)
+  {
+    int32_t got = 0;
+    if (int rc = fetch(R, &got)) return rc;
+    rows.insert(rows.end(), buf.begin(), buf.begin() + (size_t)got * width);
+    iters.insert(iters.end(), ibuf.begin(), ibuf.begin() + got);
+    return GPH_OK;
+  }
+  int sample(Run &R, int it) override
+  {
+    if (held(R) >= capacity)
+      if (int rc = flush(R)) return rc;
+    return take(R, it);
+  }
+  void write_rows()
+  {
+    for (size_t r = 0; r < iters.size(); r++) part.numbers("R", &iters[r], rows.data() + r * (size_t)width, (size_t)width);
+  }
+};
+
+// sampled genealogies: the row buffer for this rank's selected loci; the part's samples each behind their iteration
+struct GeneTrees : Selected {
+  int32_t capacity, held = 0, rb = 0;
+  Part part{"gene-trees"};
   std::vector<char> rows;
   std::vector<int32_t> iters;
-  explicit GeneTrees(const gph_run_options &o) : prefix(o.gene_trees_prefix), spec(o.gene_trees_loci), capacity(o.gene_trees_rows) {}
+  explicit GeneTrees(const gph_run_options &o) : Selected(o.gene_trees_prefix, o.gene_trees_loci, "--gene-trees-loci"), capacity(o.gene_trees_rows) {}
   static int validate(const gph_run_options &o)
   {
     if (!o.gene_trees_prefix && (o.gene_trees_loci || o.gene_trees_rows != 0)) { fprintf(stderr, "gphocs_hip: a gene-trees selection or row count needs a gene-trees prefix\n"); return GPH_EARG; }
     return o.gene_trees_rows < 0 ? GPH_EARG : GPH_OK;
   }
   int check_names(Run &R) { return tree_names_ok(R, "--gene-trees"); }
-  int select(Run &R) { return select_loci(R, spec, "--gene-trees-loci", sel, widest); }
   int open(Run &R) override
   {
     /* the bytes of a record (the same on every rank) from an empty selection, then the rows that fit */
@@ -1358,8 +1376,7 @@ struct GeneTrees : Output {
     }
     const int64_t fit = row_bytes > 0 ? limit / row_bytes : limit;
     capacity = (int32_t)std::min<int64_t>(capacity > 0 ? capacity : 64, fit);
-    /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
-    if ((rc = gph_engine_gene_trees_enable(R.E, capacity, sel.empty() ? &none : sel.data(), (int64_t)sel.size(), 0))) return R.fail(rc, "gph_engine_gene_trees_enable");
+    if ((rc = gph_engine_gene_trees_enable(R.E, capacity, loci(), (int64_t)sel.size(), 0))) return R.fail(rc, "gph_engine_gene_trees_enable");
     int32_t hdr[GT_NH] = {R.cfg.n, R.cfg.K, R.cfg.B, rb};
     gph_engine_gene_trees_shape(R.E, nullptr, nullptr, nullptr, hdr + 4, nullptr);
     rows.resize((size_t)capacity * sel.size() * (size_t)rb);
@@ -1386,16 +1403,11 @@ struct GeneTrees : Output {
 };
 
 // clade tables: accumulated on the device over the whole run, fetched once; this rank's rows of the two files as its part
-struct Clades : Output {
-  const char *prefix, *spec;
+struct Clades : TextOutput {
   int32_t slots;
   double F;
-  std::vector<int64_t> sel;          /* this rank's selected loci (global indices) */
-  int64_t widest = 0;
-  FILE *f = nullptr;
-  explicit Clades(const gph_run_options &o) : prefix(o.clades_prefix), spec(o.clades_loci), slots(o.clades_slots),
+  explicit Clades(const gph_run_options &o) : TextOutput(CL_TEXT, o.clades_prefix, o.clades_loci, "--clades-loci"), slots(o.clades_slots),
                                               F(o.clades_min_support == 0.0 ? 0.5 : o.clades_min_support < 0.0 ? 0.0 : o.clades_min_support) {}
-  ~Clades() { if (f) fclose(f); }
   static int validate(const gph_run_options &o)
   {
     if (!o.clades_prefix && (o.clades_loci || o.clades_slots != 0 || o.clades_min_support != 0.0)) {
@@ -1410,21 +1422,11 @@ struct Clades : Output {
     return GPH_OK;
   }
   int check_names(Run &R) { return tree_names_ok(R, "--clades"); }
-  int select(Run &R) { return select_loci(R, spec, "--clades-loci", sel, widest); }
   int open(Run &R) override
   {
-    const int64_t none = 0;
-    /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
-    if (int rc = gph_engine_clades_enable(R.E, slots, sel.empty() ? &none : sel.data(), (int64_t)sel.size(), 0)) {
-      if (rc == GPH_EFULL) snprintf(R.err, sizeof R.err, "the tables exceed 1 GiB: narrow --clades-loci or lower --clades-slots");
-      return R.fail(rc, "gph_engine_clades_enable");
-    }
-    if (!(f = fopen(part_path(CL_PART, prefix, R.rank).c_str(), "w"))) {
-      snprintf(R.err, sizeof R.err, "Could not open %s", part_path(CL_PART, prefix, R.rank).c_str());
-      return R.fail(GPH_EARG, "opening the clades part file");
-    }
-    fputs("GPHCL1\n", f);
-    return GPH_OK;
+    if (int rc = enabled(R, gph_engine_clades_enable(R.E, slots, loci(), (int64_t)sel.size(), 0), "gph_engine_clades_enable",
+                         "the tables exceed 1 GiB: narrow --clades-loci or lower --clades-slots")) return rc;
+    return open_part(R);
   }
   int sample(Run &R, int) override { return R.check(gph_engine_clades_sample(R.E), "gph_engine_clades_sample"); }
   int close(Run &R) override
@@ -1440,9 +1442,8 @@ struct Clades : Output {
     std::vector<const char *> lab;
     for (int i = 0; i < n; i++) labels[(size_t)i] += "." + std::to_string(i);
     for (int i = 0; i < n; i++) lab.push_back(labels[(size_t)i].c_str());
-    long long rows = 0;
     std::vector<const uint64_t *> kept;
-    std::string tree;
+    std::string tree, members;
     for (size_t q = 0; q < sel.size(); q++) {
       const uint64_t *tab = ent.data() + q * (size_t)P * ew;
       const char *nm = gph_loci_name(R.LC, sel[q]);
@@ -1462,26 +1463,20 @@ struct Clades : Output {
       for (const uint64_t *en : kept) {
         double age;
         memcpy(&age, en + W + 1, 8);
-        fprintf(f, "C\t%lld\t%s\t%lld\t%u\t%d\t%.10g\t%.10g\t", (long long)sel[q], nm ? nm : "", (long long)S, (unsigned)dropped[q], size_of(en),
-                (double)en[W] / (double)S, age / (double)en[W]);
-        bool some = false;
+        members.clear();
         for (int i = 0; i < n; i++)
-          if ((en[i / 64] >> (i % 64)) & 1) { fprintf(f, "%s%s", some ? "," : "", lab[(size_t)i]); some = true; }
-        fputc('\n', f);
-        rows++;
+          if ((en[i / 64] >> (i % 64)) & 1) { if (!members.empty()) members += ","; members += lab[(size_t)i]; }
+        part.line("C\t%lld\t%s\t%lld\t%u\t%d\t%.10g\t%.10g\t%s\n", (long long)sel[q], nm ? nm : "", (long long)S, (unsigned)dropped[q], size_of(en),
+                  (double)en[W] / (double)S, age / (double)en[W], members.c_str());
       }
       size_t len = 0;
       int32_t resolved = 0;
       int rc = gph_clades_consensus(n, P, tab, S, lab.data(), nullptr, 0, &len, &resolved);
       if (!rc) { tree.assign(len + 1, '\0'); rc = gph_clades_consensus(n, P, tab, S, lab.data(), &tree[0], len + 1, &len, &resolved); }
       if (rc) { snprintf(R.err, sizeof R.err, "the table of locus %lld gives no consensus tree", (long long)sel[q]); return R.fail(rc, "gph_clades_consensus"); }
-      fprintf(f, "T\t%lld\t%s\t%lld\t%u\t%u\t%d\t%s\n", (long long)sel[q], nm ? nm : "", (long long)S, (unsigned)nkeys[q], (unsigned)dropped[q], (int)resolved, tree.c_str());
-      rows++;
+      part.line("T\t%lld\t%s\t%lld\t%u\t%u\t%d\t%s\n", (long long)sel[q], nm ? nm : "", (long long)S, (unsigned)nkeys[q], (unsigned)dropped[q], (int)resolved, tree.c_str());
     }
-    fprintf(f, "E\t%lld\n", rows);
-    const int rcc = ferror(f) | fclose(f);
-    f = nullptr;
-    return R.check(rcc ? GPH_EARG : GPH_OK, "writing the clades part file");
+    return close_part(R);
   }
   int write(int32_t ranks) override { return gph_clades_write(prefix, ranks); }
   void discard(int32_t ranks) override { gph_clades_discard(prefix, ranks); }
@@ -1871,352 +1866,6 @@ int run_chain(const gph_run_options &o)
   return ml && R.lead ? ml->write(R) : GPH_OK;
 }
 }   // namespace
-
-extern "C" int gph_ess_discard(const char *prefix, int32_t ranks)
-{
-  if (!prefix) return GPH_EARG;
-  remove_parts(ES_PART, prefix, ranks);
-  for (const char *sfx : ES_FILES) unlink((std::string(prefix) + sfx).c_str());     /* (files only: whatever else sits there is not ours) */
-  return GPH_OK;
-}
-
-extern "C" int gph_ess_write(const char *prefix, int32_t ranks)
-{
-  if (!prefix || ranks < 1) return GPH_EARG;
-  FILE *out[2] = {nullptr, nullptr};
-  bool ok = true;
-  for (int k = 0; k < 2 && ok; k++)
-    if (!(out[k] = fopen((std::string(prefix) + ES_FILES[k]).c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s%s\n", prefix, ES_FILES[k]); ok = false; }
-  long long S = -1, level = -1, M = -1;
-  std::vector<std::pair<double, long long>> least;      /* minEss and locus of every row */
-  std::string params;                                   /* the summary line of PREFIX.ess.tsv */
-  for (int r = 0; r < ranks && ok; r++) {
-    const std::string path = part_path(ES_PART, prefix, r);
-    FILE *in = fopen(path.c_str(), "r");
-    char *line = nullptr;
-    size_t cap = 0;
-    ssize_t len;
-    long long rows = 0, told = -1;
-    int at = 0;
-    while (in && ok && (len = getline(&line, &cap, in)) > 0) {
-      at++;
-      if (at == 1) { ok = !strcmp(line, "GPHES1\n"); continue; }
-      if (at == 2) {
-        long long s = 0, j = 0, m = 0;
-        ok = sscanf(line, "H\t%lld\t%lld\t%lld", &s, &j, &m) == 3 && (S < 0 || (s == S && j == level && m == M)) && m >= 5 && m <= 6;
-        if (ok && S < 0) {
-          S = s; level = j; M = m;
-          fprintf(out[0], "param\tsamples\tmean\tsd\tessBatch\tessAcf\ttauAcf\ttruncated\n");
-          fprintf(out[1], "locus\tname\tsamples");
-          for (int k = 0; k < M; k++) fprintf(out[1], "\t%s", ES_SERIES[k]);
-          fprintf(out[1], "\ttopoChanges\tminEss\n");
-        }
-        continue;
-      }
-      if (told >= 0) { ok = false; break; }                      /* something behind the last line */
-      if (line[0] == 'E' && line[1] == '\t') { told = atoll(line + 2); continue; }
-      ok = len > 2 && line[1] == '\t' && (line[0] == 'P' || line[0] == 'L') && line[len - 1] == '\n' && (line[0] == 'L' || r == 0);
-      if (!ok) break;
-      rows++;
-      if (line[0] == 'P') {
-        fputs(line + 2, out[0]);
-        if (line[2] == '#') params.assign(line + 4, (size_t)len - 5);
-        continue;
-      }
-      char *end = nullptr;
-      const double v = strtod(line + 2, &end);
-      ok = end && *end == '\t';
-      if (ok) { least.emplace_back(v, atoll(end + 1)); fputs(end + 1, out[1]); }
-    }
-    free(line);
-    if (in) fclose(in);
-    if (!in || !ok || at < 2 || told != rows) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); ok = false; }
-  }
-  if (ok) {
-    std::vector<double> v;
-    double lo = 0.0;
-    long long lo_at = -1;
-    for (const auto &p : least) { v.push_back(p.first); if (lo_at < 0 || p.first < lo) { lo = p.first; lo_at = p.second; } }
-    std::sort(v.begin(), v.end());
-    const size_t Q = v.size();
-    const double median = Q == 0 ? 0.0 : Q % 2 ? v[Q / 2] : (v[Q / 2 - 1] + v[Q / 2]) / 2.0;
-    char loci[256];
-    snprintf(loci, sizeof loci, "loci %lld level %lld batch %lld medianMinEss %.10g minMinEss %.10g (locus %lld)", (long long)Q, level, 1ll << level, median, lo, lo_at);
-    fprintf(out[1], "# %s\n", loci);
-    printf("ESS: %s; %s\n", params.c_str(), loci);
-    fflush(stdout);
-  }
-  for (int k = 0; k < 2; k++)
-    if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s%s failed\n", prefix, ES_FILES[k]); ok = false; }
-  remove_parts(ES_PART, prefix, ranks);
-  if (!ok)
-    for (int k = 0; k < 2; k++) if (out[k]) remove((std::string(prefix) + ES_FILES[k]).c_str());
-  return ok ? GPH_OK : GPH_EARG;
-}
-
-extern "C" int gph_predictive_discard(const char *prefix, int32_t ranks)
-{
-  if (!prefix) return GPH_EARG;
-  remove_parts(PD_PART, prefix, ranks);
-  for (const char *sfx : PD_FILES) unlink((std::string(prefix) + sfx).c_str());     /* (files only: whatever else sits there is not ours) */
-  return GPH_OK;
-}
-
-extern "C" int gph_predictive_write(const char *prefix, int32_t ranks)
-{
-  if (!prefix || ranks < 1) return GPH_EARG;
-  FILE *out[2] = {nullptr, nullptr};
-  bool ok = true;
-  for (int k = 0; k < 2 && ok; k++)
-    if (!(out[k] = fopen((std::string(prefix) + PD_FILES[k]).c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s%s\n", prefix, PD_FILES[k]); ok = false; }
-  long long S = -1, C = -1;
-  unsigned long long seed = 0;
-  std::vector<std::string> names;
-  std::vector<unsigned long long> observed, totals;     /* [C]; [sample][C] */
-  std::vector<long long> iters;
-  long long Q = 0, lo_at = -1;
-  double lo = 0.0;
-  auto numbers = [](char *at, long long count, unsigned long long *into, bool add) {      /* count tab-separated u64 behind `at` */
-    for (long long c = 0; c < count; c++) {
-      if (*at != '\t') return false;
-      char *end = nullptr;
-      const unsigned long long v = strtoull(at + 1, &end, 10);
-      if (end == at + 1) return false;
-      into[c] = add ? into[c] + v : v;
-      at = end;
-    }
-    return *at == '\n';
-  };
-  for (int r = 0; r < ranks && ok; r++) {
-    const std::string path = part_path(PD_PART, prefix, r);
-    FILE *in = fopen(path.c_str(), "r");
-    char *line = nullptr;
-    size_t cap = 0;
-    ssize_t len;
-    long long lines = 0, told = -1, sample = 0;
-    int at = 0;
-    while (in && ok && (len = getline(&line, &cap, in)) > 0) {
-      at++;
-      if (at == 1) { ok = !strcmp(line, "GPHPD1\n"); continue; }
-      if (at == 2) {
-        long long s = 0, c = 0;
-        unsigned long long sd = 0;
-        int used = 0;
-        ok = sscanf(line, "H\t%lld\t%lld\t%llu%n", &s, &c, &sd, &used) == 3 && (S < 0 || (s == S && c == C && sd == seed)) && c >= 1 && line[len - 1] == '\n';
-        if (ok && S < 0) {
-          S = s; C = c; seed = sd;
-          std::string rest(line + used, (size_t)len - used - 1);
-          size_t from = 0;
-          while (from < rest.size() && rest[from] == '\t') {
-            const size_t to = rest.find('\t', from + 1);
-            names.push_back(rest.substr(from + 1, to == std::string::npos ? std::string::npos : to - from - 1));
-            from = to == std::string::npos ? rest.size() : to;
-          }
-          ok = (long long)names.size() == C;
-          if (ok) {
-            observed.assign((size_t)C, 0);
-            totals.assign((size_t)(S * C), 0);
-            iters.assign((size_t)S, 0);
-            fprintf(out[0], "locus\tname\tsamples\tsites");
-            for (const std::string &nm : names) fprintf(out[0], "\tobs_%s\tmean_%s\tsd_%s\tp_%s", nm.c_str(), nm.c_str(), nm.c_str(), nm.c_str());
-            fprintf(out[0], "\tminP\tstat\n");
-          }
-        }
-        continue;
-      }
-      if (told >= 0) { ok = false; break; }                      /* something behind the last line */
-      if (line[0] == 'E' && line[1] == '\t') { told = atoll(line + 2); continue; }
-      ok = len > 2 && line[len - 1] == '\n';
-      if (!ok) break;
-      lines++;
-      if (line[0] == 'L' && line[1] == '\t') {
-        char *end = nullptr;
-        const double v = strtod(line + 2, &end);
-        ok = end && *end == '\t';
-        if (ok) {
-          if (lo_at < 0 || v < lo) { lo = v; lo_at = atoll(end + 1); }
-          Q++;
-          fputs(end + 1, out[0]);
-        }
-      } else if (line[0] == 'O') ok = numbers(line + 1, C, observed.data(), true);
-      else if (line[0] == 'R' && line[1] == '\t') {
-        char *end = nullptr;
-        const long long it = strtoll(line + 2, &end, 10);
-        ok = sample < S && end != line + 2 && (r == 0 || iters[(size_t)sample] == it) && numbers(end, C, totals.data() + (size_t)(sample * C), true);
-        if (ok) iters[(size_t)sample++] = it;
-      } else ok = false;
-    }
-    free(line);
-    if (in) fclose(in);
-    if (!in || !ok || at < 2 || told != lines || sample != S) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); ok = false; }
-  }
-  if (ok) {
-    fprintf(out[0], "# loci %lld samples %lld seed %llu minMinP %.10g (locus %lld)\n", Q, S, seed, lo, lo_at);
-    fprintf(out[1], "iter");
-    for (const std::string &nm : names) fprintf(out[1], "\t%s", nm.c_str());
-    fputc('\n', out[1]);
-    for (long long s = 0; s < S; s++) {
-      fprintf(out[1], "%7d", (int)iters[(size_t)s]);
-      for (long long c = 0; c < C; c++) fprintf(out[1], "\t%llu", totals[(size_t)(s * C + c)]);
-      fputc('\n', out[1]);
-    }
-    std::string obs = "# observed", mean = "# mean", pl = "# p";
-    char num[64];
-    for (long long c = 0; c < C; c++) {
-      unsigned long long sum = 0, gt = 0, eq = 0;
-      for (long long s = 0; s < S; s++) {
-        const unsigned long long t = totals[(size_t)(s * C + c)];
-        sum += t; gt += t > observed[(size_t)c]; eq += t == observed[(size_t)c];
-      }
-      snprintf(num, sizeof num, "\t%llu", observed[(size_t)c]); obs += num;
-      snprintf(num, sizeof num, "\t%.10g", S > 0 ? (double)sum / (double)S : 0.0); mean += num;
-      snprintf(num, sizeof num, "\t%.10g", S > 0 ? ((double)gt + (double)eq / 2) / (double)S : 0.0); pl += num;
-    }
-    fprintf(out[1], "%s\n%s\n%s\n# loci %lld samples %lld seed %llu\n", obs.c_str(), mean.c_str(), pl.c_str(), Q, S, seed);
-    printf("Predictive: %s\n", pl.c_str() + 2);
-    fflush(stdout);
-  }
-  for (int k = 0; k < 2; k++)
-    if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s%s failed\n", prefix, PD_FILES[k]); ok = false; }
-  remove_parts(PD_PART, prefix, ranks);
-  if (!ok)
-    for (int k = 0; k < 2; k++) if (out[k]) remove((std::string(prefix) + PD_FILES[k]).c_str());
-  return ok ? GPH_OK : GPH_EARG;
-}
-
-extern "C" int gph_triplets_discard(const char *prefix, int32_t ranks)
-{
-  if (!prefix) return GPH_EARG;
-  remove_parts(TR_PART, prefix, ranks);
-  for (const char *sfx : TR_FILES) unlink((std::string(prefix) + sfx).c_str());     /* (files only: whatever else sits there is not ours) */
-  return GPH_OK;
-}
-
-extern "C" int gph_triplets_write(const char *prefix, int32_t ranks)
-{
-  if (!prefix || ranks < 1) return GPH_EARG;
-  FILE *out[2] = {nullptr, nullptr};
-  bool ok = true;
-  for (int k = 0; k < 2 && ok; k++)
-    if (!(out[k] = fopen((std::string(prefix) + TR_FILES[k]).c_str(), "w"))) { fprintf(stderr, "gphocs_hip: cannot open %s%s\n", prefix, TR_FILES[k]); ok = false; }
-  long long S = -1, T = -1, rowsL = 0;
-  std::vector<std::string> names;                       /* [T][3] */
-  std::vector<unsigned long long> totals;               /* [sample][3 T] */
-  std::vector<long long> iters;
-  for (int r = 0; r < ranks && ok; r++) {
-    const std::string path = part_path(TR_PART, prefix, r);
-    FILE *in = fopen(path.c_str(), "r");
-    char *line = nullptr;
-    size_t cap = 0;
-    ssize_t len;
-    long long lines = 0, told = -1, sample = 0;
-    int at = 0;
-    while (in && ok && (len = getline(&line, &cap, in)) > 0) {
-      at++;
-      if (at == 1) { ok = !strcmp(line, "GPHTR1\n"); continue; }
-      if (at == 2) {
-        long long s = 0, t = 0;
-        int used = 0;
-        ok = sscanf(line, "H\t%lld\t%lld%n", &s, &t, &used) == 2 && (S < 0 || (s == S && t == T)) && t >= 1 && s >= 0 && line[len - 1] == '\n';
-        if (ok && S < 0) {
-          S = s; T = t;
-          std::string rest(line + used, (size_t)len - used - 1);
-          size_t from = 0;
-          while (from < rest.size() && rest[from] == '\t') {
-            const size_t to = std::min(rest.find('\t', from + 1), rest.size());
-            const std::string three = rest.substr(from + 1, to - from - 1);
-            const size_t c1 = three.find(','), c2 = c1 == std::string::npos ? c1 : three.find(',', c1 + 1);
-            if (c2 == std::string::npos) break;
-            names.push_back(three.substr(0, c1)); names.push_back(three.substr(c1 + 1, c2 - c1 - 1)); names.push_back(three.substr(c2 + 1));
-            from = to;
-          }
-          ok = (long long)names.size() == 3 * T;
-          if (ok) {
-            totals.assign((size_t)(S * 3 * T), 0);
-            iters.assign((size_t)S, 0);
-            fprintf(out[0], "locus\tname\tsamples\tP\tQ\tR\tw_PQ|R\tw_PR|Q\tw_QR|P\tage_PQ|R\tage_PR|Q\tage_QR|P\ttop\n");
-          }
-        }
-        continue;
-      }
-      if (told >= 0) { ok = false; break; }                      /* something behind the last line */
-      if (line[0] == 'E' && line[1] == '\t') { told = atoll(line + 2); continue; }
-      ok = len > 2 && line[len - 1] == '\n';
-      if (!ok) break;
-      lines++;
-      if (line[0] == 'L' && line[1] == '\t') { fputs(line + 2, out[0]); rowsL++; }
-      else if (line[0] == 'R' && line[1] == '\t') {
-        char *end = nullptr;
-        const long long it = strtoll(line + 2, &end, 10);
-        ok = sample < S && end != line + 2 && (r == 0 || iters[(size_t)sample] == it);
-        for (long long c = 0; c < 3 * T && ok; c++) {
-          char *from = end;
-          ok = *from == '\t';
-          if (!ok) break;
-          const unsigned long long v = strtoull(from + 1, &end, 10);
-          ok = end != from + 1;
-          totals[(size_t)(sample * 3 * T + c)] += v;
-        }
-        ok = ok && *end == '\n';
-        if (ok) iters[(size_t)sample++] = it;
-      } else ok = false;
-    }
-    free(line);
-    if (in) fclose(in);
-    if (!in || !ok || at < 2 || told != lines || sample != S) { fprintf(stderr, "gphocs_hip: %s is missing, damaged or incomplete\n", path.c_str()); ok = false; }
-  }
-  if (ok) {
-    fprintf(out[1], "iter");
-    for (long long k = 0; k < T; k++) {
-      const std::string m[3] = {names[(size_t)(3 * k)], names[(size_t)(3 * k + 1)], names[(size_t)(3 * k + 2)]};
-      for (int t = 0; t < 3; t++) fprintf(out[1], "\t%s", tr_label(m, t).c_str());
-    }
-    fputc('\n', out[1]);
-    for (long long s = 0; s < S; s++) {
-      fprintf(out[1], "%7d", (int)iters[(size_t)s]);
-      for (long long c = 0; c < 3 * T; c++) fprintf(out[1], "\t%llu", totals[(size_t)(s * 3 * T + c)]);
-      fputc('\n', out[1]);
-    }
-    std::string most;
-    double most_d = -1.0;
-    for (long long k = 0; k < T; k++) {
-      const std::string m[3] = {names[(size_t)(3 * k)], names[(size_t)(3 * k + 1)], names[(size_t)(3 * k + 2)]};
-      unsigned long long sum[3] = {0, 0, 0};
-      for (long long s = 0; s < S; s++)
-        for (int t = 0; t < 3; t++) sum[t] += totals[(size_t)(s * 3 * T + 3 * k + t)];
-      int major = 0;
-      for (int t = 1; t < 3; t++) if (sum[t] > sum[major]) major = t;
-      const int ma = major == 0 ? 1 : 0, mb = major == 2 ? 1 : 2;
-      const double all = (double)sum[0] + (double)sum[1] + (double)sum[2];
-      std::vector<double> D((size_t)S);
-      double mean = 0.0, ss = 0.0;
-      long long pos = 0;
-      for (long long s = 0; s < S; s++) {
-        const double a = (double)totals[(size_t)(s * 3 * T + 3 * k + ma)], b = (double)totals[(size_t)(s * 3 * T + 3 * k + mb)];
-        D[(size_t)s] = a + b > 0.0 ? (a - b) / (a + b) : 0.0;
-        mean = mean + D[(size_t)s];
-        pos += D[(size_t)s] > 0.0;
-      }
-      mean = S > 0 ? mean / (double)S : 0.0;
-      for (long long s = 0; s < S; s++) ss = ss + (D[(size_t)s] - mean) * (D[(size_t)s] - mean);
-      const double sd = S > 1 ? sqrt(ss / (double)(S - 1)) : 0.0;
-      char num[256];
-      snprintf(num, sizeof num, " wMajor %.10g D %.10g sd %.10g pPos %.10g", all > 0.0 ? (double)sum[major] / all : 0.0, mean, sd, S > 0 ? (double)pos / (double)S : 0.0);
-      const std::string text = m[0] + "," + m[1] + "," + m[2] + " major " + tr_label(m, major) + " minorA " + tr_label(m, ma) + " minorB " + tr_label(m, mb) + num;
-      fprintf(out[1], "# asym %s\n", text.c_str());
-      if (fabs(mean) > most_d) { most_d = fabs(mean); most = text; }
-    }
-    fprintf(out[1], "# loci %lld samples %lld triples %lld\n", T > 0 ? rowsL / T : 0, S, T);
-    printf("Triplets: %s\n", most.c_str());
-    fflush(stdout);
-  }
-  for (int k = 0; k < 2; k++)
-    if (out[k] && (ferror(out[k]) | fclose(out[k])) != 0) { fprintf(stderr, "gphocs_hip: writing %s%s failed\n", prefix, TR_FILES[k]); ok = false; }
-  remove_parts(TR_PART, prefix, ranks);
-  if (!ok)
-    for (int k = 0; k < 2; k++) if (out[k]) remove((std::string(prefix) + TR_FILES[k]).c_str());
-  return ok ? GPH_OK : GPH_EARG;
-}
 
 extern "C" int gph_run_finish(const gph_run_options *in, int32_t ranks, int32_t failed)
 {

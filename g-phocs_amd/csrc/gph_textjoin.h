@@ -1,0 +1,252 @@
+// gph_textjoin.h -- the four outputs that travel through text parts (gph_textparts.h): what each format's lines mean
+// once the last rank is done (gph_run_finish), and nothing else: its header line, which tag goes to which file, its summary
+// and its line on stdout.  The parts' writers are the outputs of a run (gph_program.cpp, gph_*_run.h).
+//
+// This header DEFINES the eight gph_<name>_write / _discard entry points: one translation unit of a program includes it
+// (gph_program.cpp in the library; a stand-alone program that wants the joiners without the engine includes it itself).
+#ifndef GPH_TEXTJOIN_H
+#define GPH_TEXTJOIN_H
+#include "gph_textparts.h"
+#include <algorithm>
+#include <cmath>
+
+namespace {
+// clade tables: "C\t" + a row of PREFIX.clades.tsv, "T\t" + a row of PREFIX.consensus.tsv, locus by locus; no H line
+struct ClJoin : TextJoin {
+  ClJoin() : TextJoin(false) {}
+  /* (the headers before any part is read; the formats with an H line print theirs when rank 0's has been read) */
+  void start() override
+  {
+    fprintf(out[0], "locus\tname\tsamples\tdropped\tsize\tsupport\tmeanAge\tmembers\n");
+    fprintf(out[1], "locus\tname\tsamples\tdistinct\tdropped\tresolved\ttree\n");
+  }
+  bool body(char *line, ssize_t, int) override
+  {
+    if (line[1] != '\t' || (line[0] != 'C' && line[0] != 'T')) return false;
+    fputs(line + 2, out[line[0] == 'C' ? 0 : 1]);
+    return true;
+  }
+};
+
+// effective sample sizes: "H\t<samples>\t<level>\t<series>", rank 0's rows of PREFIX.ess.tsv as "P\t" + row (its summary
+// line included), a rank's rows of PREFIX.locus-ess.tsv as "L\t<minEss, %a>\t" + row
+const char *const ES_SERIES[6] = {"essDataLnL", "essGenLnL", "essTmrca", "essNumMigs", "essTopo", "essRate"};
+struct EsJoin : TextJoin {
+  long long S = -1, level = -1, M = -1;
+  std::vector<std::pair<double, long long>> least;      /* minEss and locus of every row */
+  std::string params;                                   /* the summary line of PREFIX.ess.tsv */
+  EsJoin() : TextJoin(true) {}
+  bool header(char *line, ssize_t, int) override
+  {
+    long long s = 0, j = 0, m = 0;
+    if (!(sscanf(line, "H\t%lld\t%lld\t%lld", &s, &j, &m) == 3 && (S < 0 || (s == S && j == level && m == M)) && m >= 5 && m <= 6)) return false;
+    if (S >= 0) return true;
+    S = s; level = j; M = m;
+    fprintf(out[0], "param\tsamples\tmean\tsd\tessBatch\tessAcf\ttauAcf\ttruncated\n");
+    fprintf(out[1], "locus\tname\tsamples");
+    for (int k = 0; k < M; k++) fprintf(out[1], "\t%s", ES_SERIES[k]);
+    fprintf(out[1], "\ttopoChanges\tminEss\n");
+    return true;
+  }
+  bool body(char *line, ssize_t len, int r) override
+  {
+    if (line[1] != '\t' || !(line[0] == 'L' || (line[0] == 'P' && r == 0))) return false;
+    if (line[0] == 'P') {
+      fputs(line + 2, out[0]);
+      if (line[2] == '#') params.assign(line + 4, (size_t)len - 5);
+      return true;
+    }
+    char *end = nullptr;
+    const double v = strtod(line + 2, &end);
+    if (!end || *end != '\t') return false;
+    least.emplace_back(v, atoll(end + 1));
+    fputs(end + 1, out[1]);
+    return true;
+  }
+  void summary() override
+  {
+    std::vector<double> v;
+    double lo = 0.0;
+    long long lo_at = -1;
+    for (const auto &p : least) { v.push_back(p.first); if (lo_at < 0 || p.first < lo) { lo = p.first; lo_at = p.second; } }
+    std::sort(v.begin(), v.end());
+    const size_t Q = v.size();
+    const double median = Q == 0 ? 0.0 : Q % 2 ? v[Q / 2] : (v[Q / 2 - 1] + v[Q / 2]) / 2.0;
+    char loci[256];
+    snprintf(loci, sizeof loci, "loci %lld level %lld batch %lld medianMinEss %.10g minMinEss %.10g (locus %lld)", (long long)Q, level, 1ll << level, median, lo, lo_at);
+    fprintf(out[1], "# %s\n", loci);
+    printf("ESS: %s; %s\n", params.c_str(), loci);
+    fflush(stdout);
+  }
+};
+
+// the names behind the numbers of an H line: "\t<name>" each, to the end of the line
+std::vector<std::string> tab_fields(const char *from, size_t bytes)
+{
+  std::vector<std::string> v;
+  const std::string rest(from, bytes);
+  for (size_t at = 0; at < rest.size() && rest[at] == '\t';) {
+    const size_t to = std::min(rest.find('\t', at + 1), rest.size());
+    v.push_back(rest.substr(at + 1, to - at - 1));
+    at = to;
+  }
+  return v;
+}
+
+// predictive checks: "H\t<samples>\t<statistics>\t<seed>" + "\t<name>" per statistic, a rank's rows of PREFIX.predictive.tsv
+// as "L\t<minP, %a>\t" + row, its observed totals as "O" + "\t<u64>" per statistic, its per-sample rows as R lines; the L
+// rows are concatenated in rank order, the O and R lines added statistic by statistic
+struct PdJoin : TextJoin {
+  long long S = -1, C = -1, Q = 0, lo_at = -1;
+  unsigned long long seed = 0;
+  double lo = 0.0;
+  std::vector<std::string> names;
+  std::vector<unsigned long long> observed;             /* [C] */
+  TextRows rows;
+  PdJoin() : TextJoin(true) {}
+  bool header(char *line, ssize_t len, int) override
+  {
+    long long s = 0, c = 0;
+    unsigned long long sd = 0;
+    int used = 0;
+    if (!(sscanf(line, "H\t%lld\t%lld\t%llu%n", &s, &c, &sd, &used) == 3 && (S < 0 || (s == S && c == C && sd == seed)) && c >= 1 && line[len - 1] == '\n')) return false;
+    if (S >= 0) return true;
+    S = s; C = c; seed = sd;
+    names = tab_fields(line + used, (size_t)len - used - 1);
+    if ((long long)names.size() != C) return false;
+    observed.assign((size_t)C, 0);
+    rows.shape(S, C);
+    fprintf(out[0], "locus\tname\tsamples\tsites");
+    for (const std::string &nm : names) fprintf(out[0], "\tobs_%s\tmean_%s\tsd_%s\tp_%s", nm.c_str(), nm.c_str(), nm.c_str(), nm.c_str());
+    fprintf(out[0], "\tminP\tstat\n");
+    return true;
+  }
+  bool body(char *line, ssize_t, int r) override
+  {
+    if (line[0] == 'O') return TextRows::numbers(line + 1, C, observed.data());
+    if (line[1] != '\t') return false;
+    if (line[0] == 'R') return rows.row(line, r);
+    if (line[0] != 'L') return false;
+    char *end = nullptr;
+    const double v = strtod(line + 2, &end);
+    if (!end || *end != '\t') return false;
+    if (lo_at < 0 || v < lo) { lo = v; lo_at = atoll(end + 1); }
+    Q++;
+    fputs(end + 1, out[0]);
+    return true;
+  }
+  bool rank_done() override { return rows.rank_done(); }
+  void summary() override
+  {
+    fprintf(out[0], "# loci %lld samples %lld seed %llu minMinP %.10g (locus %lld)\n", Q, S, seed, lo, lo_at);
+    fprintf(out[1], "iter");
+    for (const std::string &nm : names) fprintf(out[1], "\t%s", nm.c_str());
+    fputc('\n', out[1]);
+    rows.print(out[1]);
+    std::string obs = "# observed", mean = "# mean", pl = "# p";
+    char num[64];
+    for (long long c = 0; c < C; c++) {
+      unsigned long long sum = 0, gt = 0, eq = 0;
+      for (long long s = 0; s < S; s++) {
+        const unsigned long long t = rows.totals[(size_t)(s * C + c)];
+        sum += t; gt += t > observed[(size_t)c]; eq += t == observed[(size_t)c];
+      }
+      snprintf(num, sizeof num, "\t%llu", observed[(size_t)c]); obs += num;
+      snprintf(num, sizeof num, "\t%.10g", S > 0 ? (double)sum / (double)S : 0.0); mean += num;
+      snprintf(num, sizeof num, "\t%.10g", S > 0 ? ((double)gt + (double)eq / 2) / (double)S : 0.0); pl += num;
+    }
+    fprintf(out[1], "%s\n%s\n%s\n# loci %lld samples %lld seed %llu\n", obs.c_str(), mean.c_str(), pl.c_str(), Q, S, seed);
+    printf("Predictive: %s\n", pl.c_str() + 2);
+    fflush(stdout);
+  }
+};
+
+// triplet weights: "H\t<samples>\t<triples>" + "\t<P>,<Q>,<R>" (names) per triple, a rank's rows of PREFIX.triplets.tsv as
+// "L\t" + row, its per-sample rows as R lines; the L rows are concatenated in rank order, the R lines added slot by slot
+struct TrJoin : TextJoin {
+  long long S = -1, T = -1, rowsL = 0;
+  std::vector<std::string> names;                       /* [T][3] */
+  TextRows rows;                                        /* [sample][3 T] */
+  TrJoin() : TextJoin(true) {}
+  bool header(char *line, ssize_t len, int) override
+  {
+    long long s = 0, t = 0;
+    int used = 0;
+    if (!(sscanf(line, "H\t%lld\t%lld%n", &s, &t, &used) == 2 && (S < 0 || (s == S && t == T)) && t >= 1 && s >= 0 && line[len - 1] == '\n')) return false;
+    if (S >= 0) return true;
+    S = s; T = t;
+    for (const std::string &three : tab_fields(line + used, (size_t)len - used - 1)) {
+      const size_t c1 = three.find(','), c2 = c1 == std::string::npos ? c1 : three.find(',', c1 + 1);
+      if (c2 == std::string::npos) break;
+      names.push_back(three.substr(0, c1)); names.push_back(three.substr(c1 + 1, c2 - c1 - 1)); names.push_back(three.substr(c2 + 1));
+    }
+    if ((long long)names.size() != 3 * T) return false;
+    rows.shape(S, 3 * T);
+    fprintf(out[0], "locus\tname\tsamples\tP\tQ\tR\tw_PQ|R\tw_PR|Q\tw_QR|P\tage_PQ|R\tage_PR|Q\tage_QR|P\ttop\n");
+    return true;
+  }
+  bool body(char *line, ssize_t, int r) override
+  {
+    if (line[1] != '\t') return false;
+    if (line[0] == 'R') return rows.row(line, r);
+    if (line[0] != 'L') return false;
+    fputs(line + 2, out[0]);
+    rowsL++;
+    return true;
+  }
+  bool rank_done() override { return rows.rank_done(); }
+  void summary() override
+  {
+    const std::vector<unsigned long long> &totals = rows.totals;
+    fprintf(out[1], "iter");
+    for (long long k = 0; k < T; k++) {
+      const std::string m[3] = {names[(size_t)(3 * k)], names[(size_t)(3 * k + 1)], names[(size_t)(3 * k + 2)]};
+      for (int t = 0; t < 3; t++) fprintf(out[1], "\t%s", tr_label(m, t).c_str());
+    }
+    fputc('\n', out[1]);
+    rows.print(out[1]);
+    std::string most;
+    double most_d = -1.0;
+    for (long long k = 0; k < T; k++) {
+      const std::string m[3] = {names[(size_t)(3 * k)], names[(size_t)(3 * k + 1)], names[(size_t)(3 * k + 2)]};
+      unsigned long long sum[3] = {0, 0, 0};
+      for (long long s = 0; s < S; s++)
+        for (int t = 0; t < 3; t++) sum[t] += totals[(size_t)(s * 3 * T + 3 * k + t)];
+      int major = 0;
+      for (int t = 1; t < 3; t++) if (sum[t] > sum[major]) major = t;
+      const int ma = major == 0 ? 1 : 0, mb = major == 2 ? 1 : 2;
+      const double all = (double)sum[0] + (double)sum[1] + (double)sum[2];
+      std::vector<double> D((size_t)S);
+      double mean = 0.0, ss = 0.0;
+      long long pos = 0;
+      for (long long s = 0; s < S; s++) {
+        const double a = (double)totals[(size_t)(s * 3 * T + 3 * k + ma)], b = (double)totals[(size_t)(s * 3 * T + 3 * k + mb)];
+        D[(size_t)s] = a + b > 0.0 ? (a - b) / (a + b) : 0.0;
+        mean = mean + D[(size_t)s];
+        pos += D[(size_t)s] > 0.0;
+      }
+      mean = S > 0 ? mean / (double)S : 0.0;
+      for (long long s = 0; s < S; s++) ss = ss + (D[(size_t)s] - mean) * (D[(size_t)s] - mean);
+      const double sd = S > 1 ? sqrt(ss / (double)(S - 1)) : 0.0;
+      char num[256];
+      snprintf(num, sizeof num, " wMajor %.10g D %.10g sd %.10g pPos %.10g", all > 0.0 ? (double)sum[major] / all : 0.0, mean, sd, S > 0 ? (double)pos / (double)S : 0.0);
+      const std::string text = m[0] + "," + m[1] + "," + m[2] + " major " + tr_label(m, major) + " minorA " + tr_label(m, ma) + " minorB " + tr_label(m, mb) + num;
+      fprintf(out[1], "# asym %s\n", text.c_str());
+      if (fabs(mean) > most_d) { most_d = fabs(mean); most = text; }
+    }
+    fprintf(out[1], "# loci %lld samples %lld triples %lld\n", T > 0 ? rowsL / T : 0, S, T);
+    printf("Triplets: %s\n", most.c_str());
+    fflush(stdout);
+  }
+};
+}   // namespace
+
+extern "C" int gph_clades_write(const char *prefix, int32_t ranks) { ClJoin J; return text_join(CL_TEXT, J, prefix, ranks); }
+extern "C" int gph_ess_write(const char *prefix, int32_t ranks) { EsJoin J; return text_join(ES_TEXT, J, prefix, ranks); }
+extern "C" int gph_predictive_write(const char *prefix, int32_t ranks) { PdJoin J; return text_join(PD_TEXT, J, prefix, ranks); }
+extern "C" int gph_triplets_write(const char *prefix, int32_t ranks) { TrJoin J; return text_join(TR_TEXT, J, prefix, ranks); }
+extern "C" int gph_clades_discard(const char *prefix, int32_t ranks) { return text_discard(CL_TEXT, prefix, ranks); }
+extern "C" int gph_ess_discard(const char *prefix, int32_t ranks) { return text_discard(ES_TEXT, prefix, ranks); }
+extern "C" int gph_predictive_discard(const char *prefix, int32_t ranks) { return text_discard(PD_TEXT, prefix, ranks); }
+extern "C" int gph_triplets_discard(const char *prefix, int32_t ranks) { return text_discard(TR_TEXT, prefix, ranks); }
+#endif

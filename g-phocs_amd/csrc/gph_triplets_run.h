@@ -4,32 +4,15 @@
 // Included by gph_program.cpp inside its anonymous namespace, behind the other outputs.  k_triplets keeps the per-locus
 // accumulators and the per-sample rows on the device (gph_engine_triplets_*); the rows are fetched whenever their buffer is
 // full and at the end, the accumulators once, at the end.
-// Rank r's part PREFIX.triplets.part<r> is text, written once when the chain is done: a first line GPHTR1,
+// Rank r's text part PREFIX.triplets.part<r> (gph_textparts.h; TrJoin in gph_textjoin.h reads it):
 // "H\t<samples>\t<triples>" + "\t<P>,<Q>,<R>" (names) per triple, this rank's rows of PREFIX.triplets.tsv as "L\t" + row, its
-// per-sample rows as "R\t<iteration>" + "\t<u64>" per slot, and a last line "E\t<lines>".  gph_triplets_write concatenates the L
-// rows in rank order and adds the R lines of the ranks slot by slot.
-const PartFormat TR_PART = {{'G', 'P', 'H', 'T', 'R', '1', '\n', 0}, ".triplets.part", 0, nullptr, false, nullptr, nullptr, 0, true};
-const char *const TR_FILES[2] = {".triplets.tsv", ".triplets-genome.tsv"};
-
-// the label of slot t of a triple of names: the sisters, then the third
-static std::string tr_label(const std::string m[3], int t)
-{
-  return m[t == 2 ? 1 : 0] + "," + m[t == 0 ? 1 : 2] + "|" + m[t == 0 ? 2 : t == 1 ? 1 : 0];
-}
-
-struct Triplets : Output {
-  const char *prefix, *pops, *spec;
-  int32_t capacity;
-  std::vector<int64_t> sel;          /* this rank's selected loci (global indices) */
-  int64_t widest = 0;
+// per-sample rows as "R\t<iteration>" + "\t<u64>" per slot.
+struct Triplets : RowsOutput {
+  const char *pops;
   std::vector<int32_t> named;        /* --triplets-pops: [triple][3] population indices as given; empty: all triples */
   std::vector<int32_t> tri;          /* the triples taken, members sorted: [T][3] */
   int32_t T = 0, slots = 0;
-  std::vector<uint64_t> rows, buf;   /* every row taken so far [sample][slots]; one fetch */
-  std::vector<int32_t> iters, ibuf;
-  FILE *f = nullptr;
-  explicit Triplets(const gph_run_options &o) : prefix(o.triplets_prefix), pops(o.triplets_pops), spec(o.triplets_loci), capacity(o.triplets_rows) {}
-  ~Triplets() { if (f) fclose(f); }
+  explicit Triplets(const gph_run_options &o) : RowsOutput(TR_TEXT, o.triplets_prefix, o.triplets_loci, "--triplets-loci", o.triplets_rows), pops(o.triplets_pops) {}
   static int validate(const gph_run_options &o)
   {
     if (!o.triplets_prefix && (o.triplets_pops || o.triplets_loci || o.triplets_rows)) {
@@ -88,10 +71,8 @@ struct Triplets : Output {
     }
     return GPH_OK;
   }
-  int select(Run &R) { return select_loci(R, spec, "--triplets-loci", sel, widest); }
   int open(Run &R) override
   {
-    const int64_t none = 0;
     const int Kc = R.cfg.Kc;
     if (named.empty()) {
       for (int P = 0; P < Kc; P++)
@@ -103,42 +84,17 @@ struct Triplets : Output {
       for (size_t k = 0; k < tri.size(); k += 3) std::sort(tri.begin() + (long)k, tri.begin() + (long)k + 3);
     }
     T = (int32_t)(tri.size() / 3);
-    slots = 3 * T;
-    if (capacity <= 0) capacity = cs_default_rows(slots);
-    /* (a rank without a selected locus hands over an empty list, not NULL, which would mean all its loci) */
-    if (int rc = gph_engine_triplets_enable(R.E, capacity, sel.empty() ? &none : sel.data(), (int64_t)sel.size(), named.empty() ? nullptr : named.data(),
-                                            (int32_t)(named.size() / 3), 0)) {
-      if (rc == GPH_EFULL) snprintf(R.err, sizeof R.err, "accumulators and rows exceed 1 GiB: narrow --triplets-loci, --triplets-pops or --triplets-rows");
-      return R.fail(rc, "gph_engine_triplets_enable");
-    }
+    size_rows(slots = 3 * T);
+    if (int rc = enabled(R, gph_engine_triplets_enable(R.E, capacity, loci(), (int64_t)sel.size(), named.empty() ? nullptr : named.data(), (int32_t)(named.size() / 3), 0),
+                         "gph_engine_triplets_enable", "accumulators and rows exceed 1 GiB: narrow --triplets-loci, --triplets-pops or --triplets-rows")) return rc;
     int32_t t = 0;
     gph_engine_triplets_shape(R.E, &t, nullptr, nullptr, nullptr, nullptr);
     if (t != T) return R.fail(GPH_ESTATE, "gph_engine_triplets_shape");
-    if (!(f = fopen(part_path(TR_PART, prefix, R.rank).c_str(), "w"))) {
-      snprintf(R.err, sizeof R.err, "Could not open %s", part_path(TR_PART, prefix, R.rank).c_str());
-      return R.fail(GPH_EARG, "opening the triplets part file");
-    }
-    fputs("GPHTR1\n", f);
-    buf.assign((size_t)capacity * slots, 0);
-    ibuf.assign((size_t)capacity, 0);
-    return GPH_OK;
+    return open_part(R);
   }
-  int flush(Run &R)
-  {
-    int32_t got = 0;
-    if (int rc = gph_engine_triplets_fetch_rows(R.E, ibuf.data(), buf.data(), slots, capacity, &got)) return R.fail(rc, "gph_engine_triplets_fetch_rows");
-    rows.insert(rows.end(), buf.begin(), buf.begin() + (size_t)got * slots);
-    iters.insert(iters.end(), ibuf.begin(), ibuf.begin() + got);
-    return GPH_OK;
-  }
-  int sample(Run &R, int it) override
-  {
-    int32_t held = 0;
-    gph_engine_triplets_shape(R.E, nullptr, nullptr, nullptr, nullptr, &held);
-    if (held >= capacity)
-      if (int rc = flush(R)) return rc;
-    return R.check(gph_engine_triplets_sample(R.E, it), "gph_engine_triplets_sample");
-  }
+  int32_t held(Run &R) override { int32_t h = 0; gph_engine_triplets_shape(R.E, nullptr, nullptr, nullptr, nullptr, &h); return h; }
+  int fetch(Run &R, int32_t *got) override { return R.check(gph_engine_triplets_fetch_rows(R.E, ibuf.data(), buf.data(), slots, capacity, got), "gph_engine_triplets_fetch_rows"); }
+  int take(Run &R, int it) override { return R.check(gph_engine_triplets_sample(R.E, it), "gph_engine_triplets_sample"); }
   int close(Run &R) override
   {
     int64_t S = 0;
@@ -148,10 +104,9 @@ struct Triplets : Output {
     std::vector<double> acc(sel.size() * w + 1);
     if (int rc = gph_engine_triplets_fetch_loci(R.E, acc.data(), (int64_t)w, 0)) return R.fail(rc, "gph_engine_triplets_fetch_loci");
     const std::vector<std::string> names = pop_names(R.C, R.cfg);
-    long long lines = 0;
-    fprintf(f, "H\t%lld\t%d", (long long)S, (int)T);
-    for (int k = 0; k < T; k++) fprintf(f, "\t%s,%s,%s", names[(size_t)tri[3 * k]].c_str(), names[(size_t)tri[3 * k + 1]].c_str(), names[(size_t)tri[3 * k + 2]].c_str());
-    fputc('\n', f);
+    fprintf(part.f, "H\t%lld\t%d", (long long)S, (int)T);
+    for (int k = 0; k < T; k++) fprintf(part.f, "\t%s,%s,%s", names[(size_t)tri[3 * k]].c_str(), names[(size_t)tri[3 * k + 1]].c_str(), names[(size_t)tri[3 * k + 2]].c_str());
+    fputc('\n', part.f);
     for (size_t q = 0; q < sel.size(); q++) {
       const char *nm = gph_loci_name(R.LC, sel[q]);
       for (int k = 0; k < T; k++) {
@@ -160,23 +115,13 @@ struct Triplets : Output {
         const double *W = acc.data() + q * w + 3 * k, *A = W + slots;
         int top = 0;
         for (int t = 1; t < 3; t++) if (W[t] > W[top]) top = t;
-        fprintf(f, "L\t%lld\t%s\t%lld\t%s\t%s\t%s", (long long)sel[q], nm ? nm : "", (long long)S, m[0].c_str(), m[1].c_str(), m[2].c_str());
-        for (int t = 0; t < 3; t++) fprintf(f, "\t%.10g", all > 0.0 ? W[t] / all : 0.0);
-        for (int t = 0; t < 3; t++) fprintf(f, "\t%.10g", W[t] > 0.0 ? A[t] / W[t] : 0.0);
-        fprintf(f, "\t%s\n", tr_label(m, top).c_str());
-        lines++;
+        part.line("L\t%lld\t%s\t%lld\t%s\t%s\t%s\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\t%s\n", (long long)sel[q], nm ? nm : "", (long long)S,
+                  m[0].c_str(), m[1].c_str(), m[2].c_str(), all > 0.0 ? W[0] / all : 0.0, all > 0.0 ? W[1] / all : 0.0, all > 0.0 ? W[2] / all : 0.0,
+                  W[0] > 0.0 ? A[0] / W[0] : 0.0, W[1] > 0.0 ? A[1] / W[1] : 0.0, W[2] > 0.0 ? A[2] / W[2] : 0.0, tr_label(m, top).c_str());
       }
     }
-    for (size_t r = 0; r < iters.size(); r++) {
-      fprintf(f, "R\t%d", (int)iters[r]);
-      for (int c = 0; c < slots; c++) fprintf(f, "\t%llu", (unsigned long long)rows[r * (size_t)slots + c]);
-      fputc('\n', f);
-      lines++;
-    }
-    fprintf(f, "E\t%lld\n", lines);
-    const int rcc = ferror(f) | fclose(f);
-    f = nullptr;
-    return R.check(rcc ? GPH_EARG : GPH_OK, "writing the triplets part file");
+    write_rows();
+    return close_part(R);
   }
   int write(int32_t ranks) override { return gph_triplets_write(prefix, ranks); }
   void discard(int32_t ranks) override { gph_triplets_discard(prefix, ranks); }
