@@ -280,7 +280,8 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("replicates", C.c_int32), ("replicates_prefix", C.c_char_p), ("replicates_min_freq", C.c_double),
                 ("replicates_every", C.c_int32), ("ess_prefix", C.c_char_p), ("ess_loci", C.c_char_p),
                 ("predictive_prefix", C.c_char_p), ("predictive_loci", C.c_char_p), ("predictive_seed", C.c_char_p), ("predictive_rows", C.c_int32),
-                ("triplets_prefix", C.c_char_p), ("triplets_pops", C.c_char_p), ("triplets_loci", C.c_char_p), ("triplets_rows", C.c_int32)]
+                ("triplets_prefix", C.c_char_p), ("triplets_pops", C.c_char_p), ("triplets_loci", C.c_char_p), ("triplets_rows", C.c_int32),
+                ("mutations_prefix", C.c_char_p), ("mutations_loci", C.c_char_p), ("mutations_rows", C.c_int32)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
@@ -290,7 +291,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                      mc3=0, mc3_heat=0.0, mc3_swap_every=0, mc3_report=None,
                      replicates=0, replicates_out=None, replicates_min_freq=None, replicates_every=0, ess=None, ess_loci=None,
                      predictive=None, predictive_loci=None, predictive_seed=None, predictive_rows=0,
-                     triplets=None, triplets_pops=None, triplets_loci=None, triplets_rows=0):
+                     triplets=None, triplets_pops=None, triplets_loci=None, triplets_rows=0,
+                     mutations=None, mutations_loci=None, mutations_rows=0):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
     marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
@@ -301,7 +303,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
     ess_loci: the loci of the second (a SPEC as gene_trees_loci; None: all).  predictive: the prefix of PREFIX.predictive.tsv /
     PREFIX.predictive-genome.tsv, predictive_loci a SPEC, predictive_seed None: the control file's random-seed, predictive_rows
     0: the default row buffer.  triplets: the prefix of PREFIX.triplets.tsv / PREFIX.triplets-genome.tsv, triplets_pops the triples
-    as "A,B,C;D,E,F" (None: all), triplets_loci a SPEC, triplets_rows 0: the default row buffer"""
+    as "A,B,C;D,E,F" (None: all), triplets_loci a SPEC, triplets_rows 0: the default row buffer.  mutations: the prefix of PREFIX.mutations.tsv /
+    PREFIX.mutations-genome.tsv, mutations_loci a SPEC, mutations_rows 0: the default row buffer"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -320,7 +323,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       replicates_every=replicates_every, ess_prefix=b(ess), ess_loci=b(ess_loci),
                       predictive_prefix=b(predictive), predictive_loci=b(predictive_loci),
                       predictive_seed=None if predictive_seed is None else str(predictive_seed).encode(), predictive_rows=predictive_rows,
-                      triplets_prefix=b(triplets), triplets_pops=b(triplets_pops), triplets_loci=b(triplets_loci), triplets_rows=triplets_rows)
+                      triplets_prefix=b(triplets), triplets_pops=b(triplets_pops), triplets_loci=b(triplets_loci), triplets_rows=triplets_rows,
+                      mutations_prefix=b(mutations), mutations_loci=b(mutations_loci), mutations_rows=mutations_rows)
     return lib.gph_run(C.byref(o))
 
 
@@ -373,6 +377,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_triplets_enable", "gph_engine_triplets_sample", "gph_engine_triplets_shape", "gph_engine_triplets_selected",
     "gph_engine_triplets_fetch_loci", "gph_engine_triplets_fetch_rows", "gph_engine_triplets_column_name",
     "gph_triplets_write", "gph_triplets_discard",
+    "gph_engine_mutations_enable", "gph_engine_mutations_sample", "gph_engine_mutations_shape", "gph_engine_mutations_selected",
+    "gph_engine_mutations_fetch_loci", "gph_engine_mutations_fetch_rows", "gph_engine_mutations_column_name",
+    "gph_mutations_write", "gph_mutations_discard",
 ]
 
 
@@ -576,6 +583,17 @@ def _load_library(path):
     lib.gph_engine_triplets_column_name.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_engine_triplets_column_name.restype = C.c_char_p
     lib.gph_triplets_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_mutations_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_mutations_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_engine_mutations_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int64]
+    lib.gph_engine_mutations_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_mutations_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int32)]
+    lib.gph_engine_mutations_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_mutations_fetch_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    lib.gph_engine_mutations_fetch_rows.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_mutations_column_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_mutations_column_name.restype = C.c_char_p
     lib.gph_triplets_discard.argtypes = [C.c_char_p, C.c_int32]
     return lib
 
@@ -1543,6 +1561,53 @@ class Sampler:
             raise RuntimeError("gphocs_hip: triplets_rows: not enabled (GPH_ESTATE)")
         its, rows = self._fetch_rows(self.lib.gph_engine_triplets_fetch_rows, held, slots, np.uint64, with_iters=True)
         return its.copy(), rows.copy()
+
+    # ---- expected substitutions per population branch and per sample (gph_engine_mutations_*): accumulated on the device
+    def mutations_enable(self, capacity, loci=None, max_bytes=0):
+        """per-locus accumulators of mut_p / exp_p (every population) and mutExt_i / expExt_i (every leaf) for the selected loci
+        (as enable_gene_trees; None: all loci of this rank) and a device buffer of `capacity` per-sample rows; capacity 0 switches
+        the feature off.  ValueError for a refused selection (stderr names the cause; the sampler is left as it was), MemoryError
+        when accumulators and rows would exceed max_bytes (0: 1 GiB)"""
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        self._enabled(self.lib.gph_engine_mutations_enable(self.engine, int(capacity), *sel, int(max_bytes)), "mutations_enable",
+                      "the mutations accumulators and rows exceed", "the capacity or the selection")
+
+    def mutations_sample(self, it):
+        """the expected substitutions of every selected locus under the current state, labelled iteration `it`; BufferError when
+        the row buffer is full"""
+        self._sample(self.lib.gph_engine_mutations_sample, "mutations row", "mutations_rows", int(it))
+
+    def _mutations_shape(self):
+        c, ch, q, S, held = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
+        self._chk(self.lib.gph_engine_mutations_shape(self.engine, C.byref(c), C.byref(ch), C.byref(q), C.byref(S), C.byref(held)), "mutations_shape")
+        return c.value, ch.value, q.value, S.value, held.value
+
+    def mutations_columns(self):
+        return [self.lib.gph_engine_mutations_column_name(self.engine, c).decode() for c in range(self._mutations_shape()[0])]
+
+    def mutations(self, reset=False):
+        """the accumulators of this rank's Q selected loci as the device holds them: a dict of loci[Q] (global indices), samples,
+        chunk (the selected loci a partial row sums), columns (the C names) and mut, exp (Q, K), mutExt, expExt (Q, n) float64: the
+        sums over the samples.  reset=True zeroes them afterwards and restarts the sample count"""
+        Cn, chunk, Q, S, _ = self._mutations_shape()
+        if Cn == 0:
+            raise RuntimeError("gphocs_hip: mutations: not enabled (GPH_ESTATE)")
+        loci = self._selected(self.lib.gph_engine_mutations_selected, Q)
+        acc = np.zeros((max(Q, 1), Cn), dtype=np.float64)
+        self._chk(self.lib.gph_engine_mutations_fetch_loci(self.engine, acc.ctypes.data, Cn, int(bool(reset))), "mutations_fetch_loci")
+        K, n = self.pack.K, self.pack.n
+        acc = acc[:Q]
+        return dict(loci=loci, samples=S, chunk=chunk, columns=self.mutations_columns(), mut=acc[:, :K].copy(), exp=acc[:, K:2 * K].copy(),
+                    mutExt=acc[:, 2 * K:2 * K + n].copy(), expExt=acc[:, 2 * K + n:].copy())
+
+    def mutations_rows(self):
+        """(iterations, rows): the per-sample rows taken since the last call, a float64 (samples, C) array of the columns summed over
+        THIS rank's selected loci, and their iterations; the device buffer is emptied"""
+        Cn, _, _, _, held = self._mutations_shape()
+        if Cn == 0:
+            raise RuntimeError("gphocs_hip: mutations_rows: not enabled (GPH_ESTATE)")
+        _, rows = self._fetch_rows(self.lib.gph_engine_mutations_fetch_rows, held, 1 + Cn)
+        return rows[:, 0].astype(np.int32), rows[:, 1:].copy()
 
     def hbm_bytes(self):
         b = C.c_double()

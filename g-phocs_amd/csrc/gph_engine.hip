@@ -33,6 +33,7 @@
 #include "gph_ess.h"
 #include "gph_predictive.h"
 #include "gph_triplets.h"
+#include "gph_mutations.h"
 #include "gph_cladecmp.h"
 #include "gph_comm.h"
 #include "../../include/gphocs_hip.h"
@@ -446,7 +447,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 24     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 25     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets, 24: k_mutations) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -572,8 +573,11 @@ struct gph_engine_state {
   // then A, of every slot), tri [T] packed triples, pop [n + Kc] bytes (leaf -> current population, then n_p) --, the per-sample
   // rows [cap][3 T] u64 with their iterations, the triples as the caller sees them
   struct : SmSelected { size_t o_tri = 0, o_pop = 0; GphTrShape shape = {}; std::vector<int32_t> tri; std::string name; } tr;
+  // expected substitutions of selected loci (gph_mutations.h): the block is acc [nsel][C] doubles in selection order; one partial
+  // row of 1 + C doubles per chunk of selected loci, folded into the per-sample rows [cap][1 + C] (column 0: the iteration)
+  struct : SmSelected { SmParts part; GphMuShape shape = {}; std::string name; } mu;
   // the samplers with accumulators over a selection, in the order gph_engine_init_genealogies zeroes them
-  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr}; }
+  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr, &mu}; }
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -978,7 +982,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   dev_free(e->gt.rows.d); dev_free(e->gt.sel.d_slot);
-  dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp);
+  dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp); dev_free(e->mu.part.d_part);
   for (SmSelected *s : e->selected()) { dev_free(s->d); dev_free(s->sel.d_slot); dev_free(s->rows.d); }
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
@@ -3438,6 +3442,126 @@ const char *gph_engine_triplets_column_name(gph_engine *e, int32_t col)
   const int x = t == 2 ? m[1] : m[0], y = t == 0 ? m[1] : m[2], z = t == 0 ? m[2] : t == 1 ? m[1] : m[0];
   e->tr.name = std::to_string(x) + "," + std::to_string(y) + "|" + std::to_string(z);
   return e->tr.name.c_str();
+}
+
+// ---- expected substitutions per population branch and per sample, of selected loci (gph_mutations.h)
+static int mutations_zero(gph_engine *e) { return acc_zero(e, e->mu.d, e->mu.bytes); }
+static void mutations_free(gph_engine *e) { selected_free(e->mu, {e->mu.part.d_part}); }
+static int mutations_refuse(const char *fmt, long long a, long long b)
+{
+  fprintf(stderr, "gphocs_hip: mutations: ");
+  fprintf(stderr, fmt, a, b);
+  fputc('\n', stderr);
+  return GPH_EARG;
+}
+
+int gph_engine_mutations_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity_rows < 0 || (loci && nloci < 0)) return GPH_EARG;
+  SETDEV(e);
+  if (capacity_rows == 0) { mutations_free(e); return 0; }
+  /* every refusal before anything is freed or allocated, as the triplet weights do: a refused call leaves the sampler as it was */
+  if (loci)
+    for (int64_t k = 0; k < nloci; k++) {
+      if (loci[k] < 0 || loci[k] >= e->cfg.L_total) return mutations_refuse("locus %lld is out of range (0 .. %lld)", loci[k], e->cfg.L_total - 1);
+      if (k > 0 && loci[k] == loci[k - 1]) return mutations_refuse("locus %lld is named twice", loci[k], 0);
+      if (k > 0 && loci[k] < loci[k - 1]) return mutations_refuse("locus %lld stands behind locus %lld: the selection is not increasing", loci[k], loci[k - 1]);
+    }
+  GphMuShape h;
+  gph_mu_shape(e->lay, h);
+  if (h.lds_bytes > GPH_MU_LDS_BUDGET) return mutations_refuse("%lld leaves need %lld bytes of LDS a workgroup for one row of a locus (40960 at most, the samplers' budget)", e->cfg.n, h.lds_bytes);
+  mutations_free(e);
+  int64_t nsel = 0;
+  if (!loci) nsel = e->L;
+  else for (int64_t k = 0; k < nloci; k++) nsel += loci[k] >= e->cfg.locus_begin && loci[k] < e->cfg.locus_begin + e->L;
+  const int rd = 1 + h.C, nchunks = (int)((nsel + h.chunk - 1) / h.chunk);
+  const size_t bytes = (size_t)nsel * h.C * 8, pbytes = (size_t)(nchunks > 0 ? nchunks : 1) * rd * 8;
+  const int64_t need = (int64_t)bytes + (int64_t)pbytes + (int64_t)capacity_rows * rd * 8;
+  /* (nothing to free behind this refusal: the sampler is off already) */
+  if (over_limit(need, max_bytes, "mutations: the accumulators and rows", "%lld loci x %d x 8 + (%d chunks + %d rows) x %d x 8",
+                 (long long)nsel, (int)h.C, nchunks > 0 ? nchunks : 1, (int)capacity_rows, rd)) return GPH_EFULL;
+  { int rcs = sel_alloc(e, e->mu.sel, loci, nloci); if (rcs) return rcs; }
+  if (dev_alloc((void **)&e->mu.d, bytes > 0 ? bytes : 8)) { dev_clear_error(); e->mu.d = nullptr; mutations_free(e); return GPH_EHIP; }
+  if (dev_alloc((void **)&e->mu.part.d_part, pbytes)) { dev_clear_error(); e->mu.part.d_part = nullptr; mutations_free(e); return GPH_EHIP; }
+  if (rows_alloc(e->mu.rows, sizeof(double), rd, capacity_rows)) { dev_clear_error(); mutations_free(e); return GPH_EHIP; }
+  e->mu.part.rd = rd; e->mu.part.chunk = h.chunk; e->mu.part.nchunks = nchunks;
+  e->mu.shape = h;
+  e->mu.bytes = bytes;
+  return selected_on(e, e->mu, mutations_zero);
+}
+
+// one sample of the current state into the accumulators and the next free row, queued on the engine's stream.  The settle level
+// is that of the time slices: the population ages and fathers are read from the chain state
+int gph_engine_mutations_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->mu.on) return GPH_ESTATE;
+  const GphMuShape &h = e->mu.shape;
+  const SmParts &p = e->mu.part;
+  const int nsel = (int)e->mu.sel.loci.size();
+  SmTaken t;
+  t.rows = &e->mu.rows;
+  t.samples = &e->mu.samples;
+  /* (a rank without a selected locus launches the fold alone: its row is the iteration and zeros) */
+  return sample_run(e, SETTLE_CHAIN, 24, p.nchunks > 0 ? 2 : 1, t, [&](void *row) {
+    if (p.nchunks > 0) {
+      launch_pre(e);
+      int rcl = launch_grid(e, GphGrid{p.nchunks, 1}, h.bd, (size_t)h.lds_bytes, k_mutations, e->ka, h, (const char *)e->dev.pages, (const char *)e->dev.cond,
+                            e->dev.cond_off, e->dev.seq, e->dev.seq_off, e->dev.P, (const int32_t *)e->mu.sel.d_slot, nsel, (int)e->L, (double *)e->mu.d, p.d_part);
+      if (rcl) return rcl;
+    }
+    return parts_fold(e, p, iteration, (double *)row);
+  });
+}
+
+int gph_engine_mutations_shape(gph_engine *e, int32_t *columns, int32_t *chunk, int64_t *selected, int64_t *samples, int32_t *rows_held)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->mu.on;
+  if (columns) *columns = on ? e->mu.shape.C : 0;
+  if (chunk) *chunk = on ? e->mu.shape.chunk : 0;
+  if (selected) *selected = on ? (int64_t)e->mu.sel.loci.size() : 0;
+  if (samples) *samples = on ? e->mu.samples : 0;
+  if (rows_held) *rows_held = on ? e->mu.rows.fill : 0;
+  return 0;
+}
+
+int gph_engine_mutations_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->mu : nullptr, out, max_loci, count); }
+
+// out [selected][ld] doubles, the C columns of gph_engine_mutations_column_name
+int gph_engine_mutations_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset)
+{
+  if (!e) return GPH_EARG;
+  if (!e->mu.on) return GPH_ESTATE;
+  const size_t nsel = e->mu.sel.loci.size(), w = (size_t)e->mu.shape.C;
+  if (nsel > 0 && (!out || ld < (int64_t)w)) return GPH_EARG;
+  SETDEV(e);
+  if (nsel > 0) {
+    std::vector<double> acc(nsel * w);
+    { int rc = pull_rows(e, acc.data(), e->mu.d, e->mu.bytes); if (rc) return rc; }
+    for (size_t q = 0; q < nsel; q++) memcpy(out + q * (size_t)ld, acc.data() + q * w, w * 8);
+  }
+  return reset ? selected_zero(e, e->mu) : 0;
+}
+
+// the rows taken since the last fetch, [rows][1 + C] doubles (column 0: the iteration); the row buffer is empty again
+int gph_engine_mutations_fetch_rows(gph_engine *e, double *out, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || (!out && max_rows > 0)) return GPH_EARG;
+  if (!e->mu.on) return GPH_ESTATE;
+  if (max_rows < e->mu.rows.fill) return GPH_EARG;
+  SETDEV(e);
+  return rows_fetch(e, e->mu.rows, out, rows);
+}
+
+// mut.<p>, exp.<p> for the K populations (model order), then mutExt.<i>, expExt.<i> for the n leaves
+const char *gph_engine_mutations_column_name(gph_engine *e, int32_t col)
+{
+  if (!e || !e->mu.on || col < 0 || col >= e->mu.shape.C) return nullptr;
+  const int K = e->cfg.K, n = e->cfg.n;
+  if (col < 2 * K) e->mu.name = std::string(col < K ? "mut." : "exp.") + std::to_string(col % K);
+  else e->mu.name = std::string(col - 2 * K < n ? "mutExt." : "expExt.") + std::to_string((col - 2 * K) % n);
+  return e->mu.name.c_str();
 }
 
 // ---- two engines exchange their chain states (Metropolis-coupled chains)

@@ -1,8 +1,8 @@
-// gph_textjoin.h -- the four outputs that travel through text parts (gph_textparts.h): what each format's lines mean
+// gph_textjoin.h -- the five outputs that travel through text parts (gph_textparts.h): what each format's lines mean
 // once the last rank is done (gph_run_finish), and nothing else: its header line, which tag goes to which file, its summary
 // and its line on stdout.  The parts' writers are the outputs of a run (gph_program.cpp, gph_*_run.h).
 //
-// This header DEFINES the eight gph_<name>_write / _discard entry points: one translation unit of a program includes it
+// This header DEFINES the ten gph_<name>_write / _discard entry points: one translation unit of a program includes it
 // (gph_program.cpp in the library; a stand-alone program that wants the joiners without the engine includes it itself).
 #ifndef GPH_TEXTJOIN_H
 #define GPH_TEXTJOIN_H
@@ -239,14 +239,115 @@ struct TrJoin : TextJoin {
     fflush(stdout);
   }
 };
+// expected substitutions: "H\t<samples>\t<K>\t<n>" + "\t<name>" per population, then per leaf; a rank's rows of
+// PREFIX.mutations.tsv as "L\t" + row; its per-sample rows as "R\t<iteration>" + "\t<u64>" per column: the bit pattern of the
+// double.  The L rows are concatenated in rank order, the R lines added column by column in rank order (fp64, from 0.0).  The summary lines are formed
+// from the values AS PRINTED ("%.10g" read back), so that they can be recomputed from the file's own rows
+struct MuJoin : TextJoin {
+  long long S = -1, K = -1, n = -1, C = 0, Q = 0, sample = 0;
+  std::vector<std::string> names;                       /* [K] populations, then [n] leaves */
+  std::vector<double> totals;                           /* [sample][C] */
+  std::vector<long long> iters;
+  MuJoin() : TextJoin(true) {}
+  bool header(char *line, ssize_t len, int) override
+  {
+    long long s = 0, k = 0, m = 0;
+    int used = 0;
+    if (!(sscanf(line, "H\t%lld\t%lld\t%lld%n", &s, &k, &m, &used) == 3 && (S < 0 || (s == S && k == K && m == n)) && k >= 1 && m >= 2 && s >= 0 && line[len - 1] == '\n')) return false;
+    if (S >= 0) return true;
+    S = s; K = k; n = m; C = 2 * (K + n);
+    names = tab_fields(line + used, (size_t)len - used - 1);
+    if ((long long)names.size() != K + n) return false;
+    totals.assign((size_t)(S * C), 0.0);
+    iters.assign((size_t)S, 0);
+    fprintf(out[0], "locus\tname\tsamples\tsites");
+    for (long long p = 0; p < K; p++) fprintf(out[0], "\tmut_%s\texp_%s", names[(size_t)p].c_str(), names[(size_t)p].c_str());
+    fprintf(out[0], "\trel\n");
+    return true;
+  }
+  bool body(char *line, ssize_t, int r) override
+  {
+    if (line[1] != '\t') return false;
+    if (line[0] == 'L') { fputs(line + 2, out[0]); Q++; return true; }
+    if (line[0] != 'R' || sample >= S) return false;
+    char *at = nullptr;
+    const long long it = strtoll(line + 2, &at, 10);
+    if (at == line + 2 || (r > 0 && iters[(size_t)sample] != it)) return false;
+    for (long long c = 0; c < C; c++) {
+      if (*at != '\t') return false;
+      char *end = nullptr;
+      const unsigned long long bits = strtoull(at + 1, &end, 10);
+      if (end == at + 1) return false;
+      double v;
+      memcpy(&v, &bits, 8);
+      double &t = totals[(size_t)(sample * C + c)];
+      t = t + v;
+      at = end;
+    }
+    if (*at != '\n') return false;
+    iters[(size_t)sample++] = it;
+    return true;
+  }
+  bool rank_done() override { const bool all = sample == S; sample = 0; return all; }
+  static double printed(double v) { char num[64]; snprintf(num, sizeof num, "%.10g", v); return strtod(num, nullptr); }
+  /* mean, sd and the share above 1 of mut / exp over the samples, columns cm and ce */
+  std::string ratio_stats(long long cm, long long ce, double &mean) const
+  {
+    std::vector<double> x((size_t)S);
+    double sum = 0.0, ss = 0.0;
+    long long high = 0;
+    for (long long s = 0; s < S; s++) {
+      const double m = printed(totals[(size_t)(s * C + cm)]), e = printed(totals[(size_t)(s * C + ce)]);
+      x[(size_t)s] = e != 0.0 ? m / e : 0.0;
+      sum = sum + x[(size_t)s];
+      high += x[(size_t)s] > 1.0;
+    }
+    mean = S > 0 ? sum / (double)S : 0.0;
+    for (long long s = 0; s < S; s++) ss = ss + (x[(size_t)s] - mean) * (x[(size_t)s] - mean);
+    char num[192];
+    snprintf(num, sizeof num, "mean %.10g sd %.10g pHigh %.10g", mean, S > 1 ? sqrt(ss / (double)(S - 1)) : 0.0, S > 0 ? (double)high / (double)S : 0.0);
+    return num;
+  }
+  void summary() override
+  {
+    fprintf(out[1], "iter");
+    for (int w = 0; w < 2; w++)
+      for (long long p = 0; p < K; p++) fprintf(out[1], "\t%s_%s", w ? "exp" : "mut", names[(size_t)p].c_str());
+    for (int w = 0; w < 2; w++)
+      for (long long i = 0; i < n; i++) fprintf(out[1], "\t%s_%s.%lld", w ? "expExt" : "mutExt", names[(size_t)(K + i)].c_str(), i);
+    fputc('\n', out[1]);
+    for (long long s = 0; s < S; s++) {
+      fprintf(out[1], "%7d", (int)iters[(size_t)s]);
+      for (long long c = 0; c < C; c++) fprintf(out[1], "\t%.10g", totals[(size_t)(s * C + c)]);
+      fputc('\n', out[1]);
+    }
+    std::string most = "none";
+    double most_d = -1.0;
+    for (long long p = 0; p < K; p++) {
+      double mean = 0.0;
+      const std::string text = names[(size_t)p] + " " + ratio_stats(p, K + p, mean);
+      fprintf(out[1], "# rel %s\n", text.c_str());
+      if (mean > 0.0 && fabs(log(mean)) > most_d) { most_d = fabs(log(mean)); most = text; }
+    }
+    for (long long i = 0; i < n; i++) {
+      double mean = 0.0;
+      fprintf(out[1], "# ext %s.%lld %s\n", names[(size_t)(K + i)].c_str(), i, ratio_stats(2 * K + i, 2 * K + n + i, mean).c_str());
+    }
+    fprintf(out[1], "# loci %lld samples %lld\n", Q, S);
+    printf("Mutations: %s\n", most.c_str());
+    fflush(stdout);
+  }
+};
 }   // namespace
 
 extern "C" int gph_clades_write(const char *prefix, int32_t ranks) { ClJoin J; return text_join(CL_TEXT, J, prefix, ranks); }
 extern "C" int gph_ess_write(const char *prefix, int32_t ranks) { EsJoin J; return text_join(ES_TEXT, J, prefix, ranks); }
 extern "C" int gph_predictive_write(const char *prefix, int32_t ranks) { PdJoin J; return text_join(PD_TEXT, J, prefix, ranks); }
 extern "C" int gph_triplets_write(const char *prefix, int32_t ranks) { TrJoin J; return text_join(TR_TEXT, J, prefix, ranks); }
+extern "C" int gph_mutations_write(const char *prefix, int32_t ranks) { MuJoin J; return text_join(MU_TEXT, J, prefix, ranks); }
 extern "C" int gph_clades_discard(const char *prefix, int32_t ranks) { return text_discard(CL_TEXT, prefix, ranks); }
 extern "C" int gph_ess_discard(const char *prefix, int32_t ranks) { return text_discard(ES_TEXT, prefix, ranks); }
 extern "C" int gph_predictive_discard(const char *prefix, int32_t ranks) { return text_discard(PD_TEXT, prefix, ranks); }
 extern "C" int gph_triplets_discard(const char *prefix, int32_t ranks) { return text_discard(TR_TEXT, prefix, ranks); }
+extern "C" int gph_mutations_discard(const char *prefix, int32_t ranks) { return text_discard(MU_TEXT, prefix, ranks); }
 #endif

@@ -246,7 +246,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * sweep's draws generated ahead of it (k_rng_ahead), 19 clade tables (gph_engine_clades_sample: k_clades), 20 the clade
  * tables of replicate chains compared (gph_engine_clades_compare: k_clades_compare, counted on engines[0]), 21 effective
  * sample sizes per locus (gph_engine_ess_sample: k_ess), 22 posterior predictive checks (gph_engine_predictive_sample:
- * k_predictive), 23 triplet topology weights (gph_engine_triplets_sample: k_triplets) */
+ * k_predictive), 23 triplet topology weights (gph_engine_triplets_sample: k_triplets), 24 expected substitutions
+ * (gph_engine_mutations_sample: k_mutations + k_rows_fold together) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -640,6 +641,70 @@ int gph_engine_triplets_selected(gph_engine *e, int64_t *out, int64_t max_loci, 
 int gph_engine_triplets_fetch_loci(gph_engine *e, double *out /* [selected][ld] */, int64_t ld, int32_t reset);
 int gph_engine_triplets_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *out /* [rows][ld] */, int64_t ld, int32_t max_rows, int32_t *rows);
 const char *gph_engine_triplets_column_name(gph_engine *e, int32_t col);
+
+/* EXPECTED SUBSTITUTIONS per population branch and per sample, of selected loci and genome-wide per sample (k_mutations:
+ * csrc/gph_mutations.h; timing class 24): where on the population tree the data put their mutations.  The model has one clock --
+ * one rate in every population, every locus scaled by its own factor; a lineage with another rate, or a sample whose private
+ * differences are errors, shows as a ratio mut / exp away from 1.  mut is the posterior expected number of substitutions given
+ * the data and the sampled genealogy (partial likelihoods from below AND from above), exp what the clock expects on the same
+ * exposure.  THE DEFINITION; all arithmetic is plain uncontracted fp64 in the order written, exp is gph_exp, a quotient is IEEE
+ * division.
+ *   locus        at one sample: n leaves, N = 2n - 1 nodes, rows 0 .. P - 1 of its sequence block.  A COLUMN is a row with a
+ *                non-zero phase word together with the ph - 1 rows behind it; it stands for `count` sites (as for the predictive
+ *                checks); sites = sum count; rate = FS_MUTRATE.  Node records, live migrations and log-likelihoods are the settled
+ *                ones a gene-tree record holds; population ages and fathers come from the chain state (settled as for time slices)
+ *   branch       above v != root with father f: t_v = age[f] - age[v], len = rate t_v, a = 4 len / 3.0,
+ *                u = len < 1e-100 ? 0 : 1 - exp(-4 len / 3.0), pe = u / 4.0, qe = 1 - 4.0 pe (edge_prob and the likelihood's qe),
+ *                    E_diff = (a qe) / u + 0.75 a          E_same = ((0.75 a) u) / (1 + 3 qe)
+ *                the expected number of real substitutions of a JC69 path whose ends differ / are equal: exact by uniformisation,
+ *                and the conditional density of substitutions along the branch is uniform, which allows splitting a branch by
+ *                time.  u == 0: the branch contributes nothing
+ *   per row      I_v(y) the inside conditional of v: an internal node's CURRENT half (IS_CBIT) of the conditional arrays, a leaf's
+ *                one-hot vector, all ones for code 4.  Top down: O_root(x) = 1.0; for a child c of v with sibling s
+ *                    U_c(x) = O_v(x) f_s(x)       f_s = child_factor of the sibling as the likelihood forms it (S >= 4 -> 1.0)
+ *                    SU = ((U_c(0) + U_c(1)) + U_c(2)) + U_c(3)        O_c(y) = pe_c SU + qe_c U_c(y)
+ *                with J_x = the sum of I_c(y) over y != x in increasing y
+ *                    D_c(row) = pe_c (((U_c(0) J_0 + U_c(1) J_1) + U_c(2) J_2) + U_c(3) J_3)
+ *                the posterior mass of "the ends of the branch differ" (every term positive: no cancellation);
+ *                R(row) = ((r0 + r1) + r2) + r3 of the root's conditionals
+ *   per column   j and branch: DD = sum D, RR = sum R over the column's rows in row order; d = DD / RR (0 where RR == 0);
+ *                Dv = sum_j (double)count_j d in column order; M_v = E_same (sites - Dv) + E_diff Dv.  A missing leaf needs no
+ *                special case: its all-ones vector gives the prior expectation
+ *   segments     of the branch above v: cur = npop[v], t = age[v]; the events are the live migrations whose branch is v by
+ *                increasing age (equal ages in `living` order), then age[f].  Before an event at age b: while cur has a father
+ *                population F with popAge[F] <= b, close (cur, popAge[F] - t), cur = F, t = popAge[F]; then close (cur, b - t),
+ *                t = b; at a migration cur = the band's source population (below the migration node the lineage is in the target
+ *                population, above it in the source).  Every loop is bounded: a record that does not fit still terminates.
+ *                Segment (p, dt): mut_p = mut_p + M_v (dt / t_v), exp_p = exp_p + (rate dt) sites; nodes in index order, then
+ *                segments in time order.  Leaf i: mutExt_i = M_i, expExt_i = (rate t_i) sites
+ *   columns      C = 2 (K + n): mut_p and exp_p of the K populations (model order), then mutExt_i and expExt_i of the n leaves
+ *   accumulators per selected locus C doubles, acc = acc + value, one plain fp64 add a sample in sample order
+ *   rows         per sample 1 + C doubles: the iteration, then the C columns summed over the rank's selected loci WITHOUT fp
+ *                atomics -- the loci of a chunk of `chunk` selected loci in selection order (from 0.0), the chunks in chunk order
+ *                (from 0.0; k_rows_fold): a row is rebuilt bit for bit for a given selection and rank count.  Ranks' rows add in
+ *                rank order
+ *   _enable      capacity_rows per-sample rows; 0 frees everything, the feature is off.  loci as gph_engine_triplets_enable, with
+ *                its refusals (GPH_EARG with a message that names the cause, nothing freed or allocated) and its limit: GPH_EFULL,
+ *                with the size in the message and the feature off, when accumulators, partial rows and rows exceed max_bytes
+ *                (<= 0: 1 GiB).  GPH_EARG with a message where one row of a locus no longer fits the samplers' 40 KB of LDS (more than
+ *                about 180 leaves).  GPH_ESTATE before the loci are loaded.  gph_engine_init_genealogies zeroes the accumulators,
+ *                the sample count and the rows held
+ *   _sample      k_mutations and the fold on the engine's stream, no host synchronisation; a rank without a selected locus
+ *                launches the fold alone.  GPH_EFULL when the row buffer is full; GPH_ESTATE when off or before
+ *                gph_engine_init_genealogies
+ *   _shape       C, the chunk size, selected loci of the rank, samples since the accumulators were zeroed, rows held (0 while off)
+ *   _fetch_loci  out[selected][ld], ld >= C; one copy and one host synchronisation; reset != 0 zeroes the accumulators and the
+ *                sample count afterwards
+ *   _fetch_rows  the rows taken since the last call, out[rows][1 + C]; the row buffer is empty again
+ *   _column_name column col of the C: "mut.<p>", "exp.<p>", "mutExt.<i>", "expExt.<i>"
+ * The kernel writes no page, draws no random number and touches no chain state. */
+int gph_engine_mutations_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int64_t max_bytes);
+int gph_engine_mutations_sample(gph_engine *e, int32_t iteration);
+int gph_engine_mutations_shape(gph_engine *e, int32_t *columns, int32_t *chunk, int64_t *selected, int64_t *samples, int32_t *rows_held);
+int gph_engine_mutations_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_mutations_fetch_loci(gph_engine *e, double *out /* [selected][ld] */, int64_t ld, int32_t reset);
+int gph_engine_mutations_fetch_rows(gph_engine *e, double *out /* [rows][1 + C] */, int32_t max_rows, int32_t *rows);
+const char *gph_engine_mutations_column_name(gph_engine *e, int32_t col);
 
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
@@ -1045,6 +1110,30 @@ typedef struct gph_run_options {
    * marginal_prefix they describe chain 0 and the run proper; every other output is the same bytes with and without. */
   const char *triplets_prefix, *triplets_pops, *triplets_loci;
   int32_t triplets_rows;
+  /* `--mutations PREFIX [--mutations-loci SPEC] [--mutations-rows N]`: expected substitutions per population branch and per
+   * sample (gph_engine_mutations_* above).  A sample is taken wherever a trace line is written.  mutations_loci as
+   * gene_trees_loci; mutations_rows: the rows of the device buffer (0: a default), fetched when it is full and at the end.  Either
+   * without mutations_prefix and negative rows are GPH_EARG with a message, before anything is read.  Rank r writes its part
+   * PREFIX.mutations.part<r> once, at the end; the part carries the per-sample rows as the doubles' 64-bit patterns, so the ranks' doubles add
+   * without loss.  gph_mutations_write makes of the parts (numbers "%.10g")
+   *   PREFIX.mutations.tsv         header locus name samples sites, then per population mut_<pop> exp_<pop>, then rel; one row per
+   *                                selected locus in sequence-file order (the ranks' rows concatenated); mut and exp are the means
+   *                                over the samples (accumulator / S), rel = (sum_p mut accumulators) / (sum_p exp accumulators),
+   *                                both sums in population order (0 where the second is 0)
+   *   PREFIX.mutations-genome.tsv  header iter, mut_<pop> and exp_<pop> of every population, mutExt_<sample>.<i> and
+   *                                expExt_<sample>.<i> of every leaf; one row per sample, "%7d" and "\t%.10g" per column: the
+   *                                sums over the selected loci (the ranks' rows added in rank order); then
+   *                                    # rel <pop> mean <v> sd <v> pHigh <v>            per population
+   *                                    # ext <sample>.<i> mean <v> sd <v> pHigh <v>     per leaf
+   *                                with, per sample, the ratio mut / exp of the row's values as printed (0 where exp is 0), mean
+   *                                and the sample sd (divisor S - 1; 0 for S = 1) over the samples in sample order, pHigh the
+   *                                share of samples with a ratio above 1; and a last line "# loci Q samples S"
+   * and prints "Mutations: " and the "# rel" values of the population with the largest |ln mean| (the first of equal ones) on
+   * stdout.  Both files are written once, on success only; a failed run leaves neither parts nor files.  With mc3_chains,
+   * replicates and marginal_prefix they describe chain 0 and the run proper; every other output is the same bytes with and
+   * without. */
+  const char *mutations_prefix, *mutations_loci;
+  int32_t mutations_rows;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
@@ -1070,6 +1159,8 @@ int gph_predictive_write(const char *prefix, int32_t ranks);
 int gph_predictive_discard(const char *prefix, int32_t ranks);
 int gph_triplets_write(const char *prefix, int32_t ranks);
 int gph_triplets_discard(const char *prefix, int32_t ranks);
+int gph_mutations_write(const char *prefix, int32_t ranks);
+int gph_mutations_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
  * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
  * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
