@@ -281,7 +281,9 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("replicates_every", C.c_int32), ("ess_prefix", C.c_char_p), ("ess_loci", C.c_char_p),
                 ("predictive_prefix", C.c_char_p), ("predictive_loci", C.c_char_p), ("predictive_seed", C.c_char_p), ("predictive_rows", C.c_int32),
                 ("triplets_prefix", C.c_char_p), ("triplets_pops", C.c_char_p), ("triplets_loci", C.c_char_p), ("triplets_rows", C.c_int32),
-                ("mutations_prefix", C.c_char_p), ("mutations_loci", C.c_char_p), ("mutations_rows", C.c_int32)]
+                ("mutations_prefix", C.c_char_p), ("mutations_loci", C.c_char_p), ("mutations_rows", C.c_int32),
+                ("simulate_prefix", C.c_char_p), ("simulate_loci", C.c_char_p), ("simulate_seed", C.c_char_p), ("simulate_rows", C.c_int32),
+                ("simulate_no_sites", C.c_int32)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
@@ -292,7 +294,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                      replicates=0, replicates_out=None, replicates_min_freq=None, replicates_every=0, ess=None, ess_loci=None,
                      predictive=None, predictive_loci=None, predictive_seed=None, predictive_rows=0,
                      triplets=None, triplets_pops=None, triplets_loci=None, triplets_rows=0,
-                     mutations=None, mutations_loci=None, mutations_rows=0):
+                     mutations=None, mutations_loci=None, mutations_rows=0,
+                     simulate=None, simulate_loci=None, simulate_seed=None, simulate_rows=0, simulate_no_sites=False):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
     marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
@@ -304,7 +307,9 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
     PREFIX.predictive-genome.tsv, predictive_loci a SPEC, predictive_seed None: the control file's random-seed, predictive_rows
     0: the default row buffer.  triplets: the prefix of PREFIX.triplets.tsv / PREFIX.triplets-genome.tsv, triplets_pops the triples
     as "A,B,C;D,E,F" (None: all), triplets_loci a SPEC, triplets_rows 0: the default row buffer.  mutations: the prefix of PREFIX.mutations.tsv /
-    PREFIX.mutations-genome.tsv, mutations_loci a SPEC, mutations_rows 0: the default row buffer"""
+    PREFIX.mutations-genome.tsv, mutations_loci a SPEC, mutations_rows 0: the default row buffer.  simulate: the prefix of
+    PREFIX.simulate.tsv / PREFIX.simulate-genome.tsv, simulate_loci a SPEC, simulate_seed None: the control file's random-seed,
+    simulate_rows 0: the default row buffer, simulate_no_sites: the genealogy level alone"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -324,7 +329,10 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       predictive_prefix=b(predictive), predictive_loci=b(predictive_loci),
                       predictive_seed=None if predictive_seed is None else str(predictive_seed).encode(), predictive_rows=predictive_rows,
                       triplets_prefix=b(triplets), triplets_pops=b(triplets_pops), triplets_loci=b(triplets_loci), triplets_rows=triplets_rows,
-                      mutations_prefix=b(mutations), mutations_loci=b(mutations_loci), mutations_rows=mutations_rows)
+                      mutations_prefix=b(mutations), mutations_loci=b(mutations_loci), mutations_rows=mutations_rows,
+                      simulate_prefix=b(simulate), simulate_loci=b(simulate_loci),
+                      simulate_seed=None if simulate_seed is None else str(simulate_seed).encode(), simulate_rows=simulate_rows,
+                      simulate_no_sites=int(bool(simulate_no_sites)))
     return lib.gph_run(C.byref(o))
 
 
@@ -380,6 +388,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_mutations_enable", "gph_engine_mutations_sample", "gph_engine_mutations_shape", "gph_engine_mutations_selected",
     "gph_engine_mutations_fetch_loci", "gph_engine_mutations_fetch_rows", "gph_engine_mutations_column_name",
     "gph_mutations_write", "gph_mutations_discard",
+    "gph_engine_simulate_enable", "gph_engine_simulate_sample", "gph_engine_simulate_shape", "gph_engine_simulate_selected",
+    "gph_engine_simulate_fetch_loci", "gph_engine_simulate_fetch_rows", "gph_engine_simulate_fetch_records", "gph_engine_simulate_column_name",
+    "gph_simulate_write", "gph_simulate_discard",
 ]
 
 
@@ -595,6 +606,18 @@ def _load_library(path):
     lib.gph_engine_mutations_column_name.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_engine_mutations_column_name.restype = C.c_char_p
     lib.gph_triplets_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_simulate_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_simulate_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_engine_simulate_enable.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int64]
+    lib.gph_engine_simulate_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_simulate_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gph_engine_simulate_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_simulate_fetch_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.gph_engine_simulate_fetch_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_simulate_fetch_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gph_engine_simulate_column_name.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.gph_engine_simulate_column_name.restype = C.c_char_p
     return lib
 
 
@@ -1608,6 +1631,85 @@ class Sampler:
             raise RuntimeError("gphocs_hip: mutations_rows: not enabled (GPH_ESTATE)")
         _, rows = self._fetch_rows(self.lib.gph_engine_mutations_fetch_rows, held, 1 + Cn)
         return rows[:, 0].astype(np.int32), rows[:, 1:].copy()
+
+    # ---- replicate genealogies simulated from the sampled parameters (gph_engine_simulate_*): simulated on the device
+    def simulate_enable(self, seed, capacity, loci=None, with_sites=True, max_bytes=0):
+        """per-locus accumulators of the replicate-against-sampled statistics for the selected loci (as enable_gene_trees; None:
+        all loci of this rank), the latest sample's replicate records and a device buffer of `capacity` per-sample rows; capacity
+        0 switches the feature off.  with_sites: the replicate alignment is drawn on the replicate genealogy as well.  The
+        replicates are a pure function of (seed, locus, sample) and the model.  ValueError for a refused selection or a locus
+        whose site statistics do not fit 32 bits, MemoryError when the buffers would exceed max_bytes (0: 1 GiB)"""
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        self._enabled(self.lib.gph_engine_simulate_enable(self.engine, int(seed) & 0xffffffffffffffff, int(capacity), *sel, int(bool(with_sites)),
+                                                          int(max_bytes)),
+                      "simulate_enable", "the simulate accumulators, records and rows exceed", "the capacity, the selection or a locus")
+
+    def simulate_sample(self, it):
+        """one replicate genealogy of every selected locus under the current parameters, labelled iteration `it`; BufferError
+        when the row buffer is full"""
+        self._sample(self.lib.gph_engine_simulate_sample, "simulate row", "simulate_rows", int(it))
+
+    def _simulate_shape(self):
+        q, m, c, rc, rb, S, held = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+        self._chk(self.lib.gph_engine_simulate_shape(self.engine, C.byref(q), C.byref(m), C.byref(c), C.byref(rc), C.byref(rb), C.byref(S), C.byref(held)),
+                  "simulate_shape")
+        return q.value, m.value, c.value, rc.value, rb.value, S.value, held.value
+
+    def simulate_columns(self, which=0):
+        """which 0: the genealogy statistics, 1: the columns of a per-sample row, 2: the site statistics"""
+        _, m, c, rc, _, _, _ = self._simulate_shape()
+        return [self.lib.gph_engine_simulate_column_name(self.engine, which, k).decode() for k in range((m, rc, c)[which])]
+
+    def simulate(self, reset=False):
+        """the accumulators of this rank's Q selected loci as the device holds them: a dict of loci[Q] (global indices), samples,
+        stats (the M names), acc (Q, M, 5) float64 -- gt, eq, sx, sy, sy2 --, failed[Q], and with sites site_stats (the C names),
+        sites[Q], site_acc (Q, C, 5) -- obs, gt, eq, s1, s2.  reset=True zeroes them afterwards and restarts the sample count"""
+        Q, M, Cn, _, _, S, _ = self._simulate_shape()
+        if M == 0:
+            raise RuntimeError("gphocs_hip: simulate: not enabled (GPH_ESTATE)")
+        loci = self._selected(self.lib.gph_engine_simulate_selected, Q)
+        names, snames = self.simulate_columns(0), self.simulate_columns(2)
+        acc = np.zeros((max(Q, 1), 5 * M + 1), dtype=np.float64)
+        sacc, sites = np.zeros((max(Q, 1), max(Cn, 1), 5), dtype=np.float64), np.zeros(max(Q, 1), dtype=np.int64)
+        self._chk(self.lib.gph_engine_simulate_fetch_loci(self.engine, acc.ctypes.data, sacc.ctypes.data if Cn else None, sites.ctypes.data,
+                                                          int(bool(reset))), "simulate_fetch_loci")
+        return dict(loci=loci, samples=S, stats=names, acc=acc[:Q, :5 * M].reshape(Q, M, 5).copy(), failed=acc[:Q, 5 * M].copy(),
+                    site_stats=snames, sites=sites[:Q].copy(), site_acc=sacc[:Q, :Cn].copy())
+
+    def simulate_rows(self):
+        """(iterations, rows, observed): the per-sample rows taken since the last call, a uint64 (samples, columns) array of the
+        totals over THIS rank's selected loci (simulate_columns(1)), their iterations, and the data's site totals observed[C];
+        the device buffer is emptied"""
+        _, M, Cn, rc, _, _, held = self._simulate_shape()
+        if M == 0:
+            raise RuntimeError("gphocs_hip: simulate_rows: not enabled (GPH_ESTATE)")
+        obs = np.zeros(max(Cn, 1), dtype=np.uint64)
+        its, rows = self._fetch_rows(self.lib.gph_engine_simulate_fetch_rows, held, rc, np.uint64, with_iters=True, ld=False, extra=(obs.ctypes.data,))
+        return its.copy(), rows.copy(), obs[:Cn]
+
+    def simulate_records(self, raw=False):
+        """the replicate genealogies of the latest sample, decoded as gene_trees() decodes a sample (arrays [Q, ...]); a failed
+        replicate has root -1.  raw=True adds records: uint8 [Q, record_bytes]"""
+        Q, M, _, _, rb, _, _ = self._simulate_shape()
+        if M == 0:
+            raise RuntimeError("gphocs_hip: simulate_records: not enabled (GPH_ESTATE)")
+        N, Mg = 2 * self.pack.n - 1, GT_MAX_MIGS
+        rec = np.zeros((max(Q, 1), max(rb, 1)), dtype=np.uint8)
+        off = (C.c_int32 * GT_OFFSETS)()
+        self._chk(self.lib.gph_engine_simulate_fetch_records(self.engine, rec.ctypes.data, off), "simulate_fetch_records")
+        rec = np.ascontiguousarray(rec[:Q])
+        out = dict(loci=self._selected(self.lib.gph_engine_simulate_selected, Q))
+        shapes = dict(age=((Q, N), np.float64), father=((Q, N), np.int32), left=((Q, N), np.int32), right=((Q, N), np.int32),
+                      npop=((Q, N), np.int32), root=((Q,), np.int32), num_migs=((Q,), np.int32), dataLnL=((Q,), np.float64),
+                      genLnL=((Q,), np.float64), mig_branch=((Q, Mg), np.int32), mig_band=((Q, Mg), np.int32),
+                      mig_spop=((Q, Mg), np.int32), mig_tpop=((Q, Mg), np.int32), mig_age=((Q, Mg), np.float64))
+        for k, (shp, dt) in shapes.items():
+            out[k] = np.zeros(shp, dtype=dt)
+        if Q:
+            self._chk(self.lib.gph_gene_trees_decode(rec.ctypes.data, Q, rb, off, N, *[out[k].ctypes.data for k in shapes]), "gene_trees_decode")
+        if raw:
+            out["records"] = rec
+        return out
 
     def hbm_bytes(self):
         b = C.c_double()

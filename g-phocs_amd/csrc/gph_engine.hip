@@ -32,6 +32,7 @@
 #include "gph_clades.h"
 #include "gph_ess.h"
 #include "gph_predictive.h"
+#include "gph_simulate.h"
 #include "gph_triplets.h"
 #include "gph_mutations.h"
 #include "gph_cladecmp.h"
@@ -447,7 +448,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 25     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets, 24: k_mutations) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 26     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets, 24: k_mutations, 25: k_simulate) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -576,8 +577,14 @@ struct gph_engine_state {
   // expected substitutions of selected loci (gph_mutations.h): the block is acc [nsel][C] doubles in selection order; one partial
   // row of 1 + C doubles per chunk of selected loci, folded into the per-sample rows [cap][1 + C] (column 0: the iteration)
   struct : SmSelected { SmParts part; GphMuShape shape = {}; std::string name; } mu;
+  // replicate genealogies of selected loci (gph_simulate.h): ONE buffer in selection order -- acc [nsel][W] doubles, then (with
+  // sites) sacc [nsel][C][5] doubles and sobs [C] u64 as the predictive checks keep them; behind them key [nsel] u64, skey [nsel]
+  // u64 (the site level's Kl), pop [n] bytes, recs [nsel][record]: the latest sample's replicates --, the per-sample rows
+  // [cap][RC + C] u64 with their iterations
+  struct : SmSelected { size_t o_sacc = 0, o_sobs = 0, o_key = 0, o_skey = 0, o_pop = 0, o_rec = 0; GphSiShape shape = {}; GphGtShape gshape = {};
+                        GphPdShape pshape = {}; int32_t C = 0; std::vector<int64_t> sites; std::string name; } si;
   // the samplers with accumulators over a selection, in the order gph_engine_init_genealogies zeroes them
-  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr, &mu}; }
+  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr, &mu, &si}; }
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -3176,7 +3183,8 @@ static int predictive_launch(gph_engine *e, int observed, uint64_t *row)
   launch_pre(e);
   return launch_grid(e, GphGrid{nsel, 1}, e->pd.shape.bd, (size_t)e->pd.shape.lds_bytes, k_predictive, e->ka, e->pd.shape, (const char *)e->dev.pages,
                      e->dev.seq, e->dev.seq_off, e->dev.P, (const int32_t *)e->pd.sel.d_slot, (const uint64_t *)(e->pd.d + e->pd.o_key),
-                     (const uint8_t *)(e->pd.d + e->pd.o_pop), nsel, (int)e->L, (long long)e->pd.samples, observed, (double *)e->pd.d, row);
+                     (const uint8_t *)(e->pd.d + e->pd.o_pop), nsel, (int)e->L, (long long)e->pd.samples, observed, (double *)e->pd.d, row,
+                     (const char *)nullptr, 0, 0, 0);
 }
 // the accumulators back to zero, t back to 0, and the data's statistics formed again (they live in the same words)
 static int predictive_zero(gph_engine *e)
@@ -3562,6 +3570,199 @@ const char *gph_engine_mutations_column_name(gph_engine *e, int32_t col)
   if (col < 2 * K) e->mu.name = std::string(col < K ? "mut." : "exp.") + std::to_string(col % K);
   else e->mu.name = std::string(col - 2 * K < n ? "mutExt." : "expExt.") + std::to_string((col - 2 * K) % n);
   return e->mu.name.c_str();
+}
+
+// ---- replicate genealogies of selected loci, simulated from the sampled parameters (gph_simulate.h)
+// the site level: k_predictive's site loop over the selection, on the data (observed) or on the replicate records of sample t
+static int simulate_sites_launch(gph_engine *e, int observed, uint64_t *row)
+{
+  const int nsel = (int)e->si.sel.loci.size();
+  const GphGtShape &g = e->si.gshape;
+  launch_pre(e);
+  return launch_grid(e, GphGrid{nsel, 1}, e->si.pshape.bd, (size_t)e->si.pshape.lds_bytes, k_predictive, e->ka, e->si.pshape, (const char *)e->dev.pages,
+                     e->dev.seq, e->dev.seq_off, e->dev.P, (const int32_t *)e->si.sel.d_slot, (const uint64_t *)(e->si.d + e->si.o_skey),
+                     (const uint8_t *)(e->si.d + e->si.o_pop), nsel, (int)e->L, (long long)e->si.samples, observed, (double *)(e->si.d + e->si.o_sacc), row,
+                     (const char *)(e->si.d + e->si.o_rec), (int)g.img.bytes, (int)g.off[GT_O_NODES], (int)g.off[GT_O_ROOT]);
+}
+// the accumulators back to zero, t back to 0, and (with sites) the data's statistics formed again
+static int simulate_zero(gph_engine *e)
+{
+  { int rcz = acc_zero(e, e->si.d, e->si.o_key); if (rcz) return rcz; }
+  if (e->si.C == 0 || e->si.sel.loci.empty()) return 0;
+  { int rcf = flush_pending(e); if (rcf) return rcf; }
+  { int rcl = simulate_sites_launch(e, 1, (uint64_t *)(e->si.d + e->si.o_sobs)); if (rcl) return rcl; }
+  flat_launched(e, -1, 1);
+  return 0;
+}
+static void simulate_free(gph_engine *e) { selected_free(e->si); }
+
+int gph_engine_simulate_enable(gph_engine *e, uint64_t seed, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int32_t with_sites, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity_rows < 0 || !sel_valid(loci, nloci)) return GPH_EARG;
+  SETDEV(e);
+  simulate_free(e);
+  if (capacity_rows == 0) return 0;
+  const int n = e->cfg.n, Kc = e->cfg.Kc;
+  GphSiShape h;
+  GphGtShape g;
+  GphPdShape ph;
+  gph_si_shape(e->lay, h);
+  gph_gt_shape(e->lay, g);
+  gph_pd_shape(e->lay, ph);
+  if (n > 255 || h.lds_bytes > 65536 || (with_sites && ph.lds_bytes > 65536)) {
+    fprintf(stderr, "gphocs_hip: simulate: %d leaves in %d populations need byte counts above 255 or %d bytes of LDS a workgroup (65536 at most)\n",
+            n, (int)e->cfg.K, (int)(h.lds_bytes > ph.lds_bytes ? h.lds_bytes : ph.lds_bytes));
+    return GPH_EARG;
+  }
+  { int rcs = sel_alloc(e, e->si.sel, loci, nloci); if (rcs) return rcs; }
+  const size_t nsel = e->si.sel.loci.size();
+  const int C = with_sites ? ph.C : 0;
+  int64_t maxpair = 1;
+  for (int p = 0; p < Kc; p++) if ((int64_t)e->samplesPerPop[p] * e->samplesPerPop[p] > maxpair) maxpair = (int64_t)e->samplesPerPop[p] * e->samplesPerPop[p];
+  for (size_t q = 0; q < nsel; q++) {
+    const int64_t gl = e->si.sel.loci[q], sites = e->h_sites[(size_t)(gl - e->cfg.locus_begin)];
+    if (with_sites && (sites >= ((int64_t)1 << 31) || sites * maxpair >= ((int64_t)1 << 32))) {
+      fprintf(stderr, "gphocs_hip: simulate: locus %lld: %lld sites x %lld sample pairs reach 2^32: its statistics do not fit 32 bits\n",
+              (long long)gl, (long long)sites, (long long)maxpair);
+      simulate_free(e);
+      return GPH_EARG;
+    }
+    e->si.sites.push_back(sites);
+  }
+  const size_t o_sacc = nsel * (size_t)h.W * 8, o_sobs = o_sacc + nsel * (size_t)C * GPH_PD_WORDS * 8, o_key = o_sobs + (size_t)C * 8, o_skey = o_key + nsel * 8,
+               o_pop = o_skey + nsel * 8, o_rec = (o_pop + (size_t)n + 15) & ~(size_t)15, bytes = o_rec + nsel * (size_t)g.img.bytes;
+  const int RC = h.RC + C;
+  const int64_t need = (int64_t)bytes + (int64_t)capacity_rows * RC * 8;
+  if (over_limit(need, max_bytes, "simulate: the accumulators, records and rows", "%lld loci x (%d doubles x 8 + %d statistics x 40 + 16 + %d bytes a record) + %d rows x %d x 8 + %d",
+                 (long long)nsel, (int)h.W, C, (int)g.img.bytes, (int)capacity_rows, RC, (int)(C * 8 + ((n + 15) & ~15)))) {
+    simulate_free(e);
+    return GPH_EFULL;
+  }
+  if (dev_alloc((void **)&e->si.d, bytes > 0 ? bytes : 16)) { dev_clear_error(); e->si.d = nullptr; simulate_free(e); return GPH_EHIP; }
+  if (rows_alloc(e->si.rows, sizeof(uint64_t), RC, capacity_rows)) { dev_clear_error(); simulate_free(e); return GPH_EHIP; }
+  std::vector<uint64_t> key(2 * nsel + 1);
+  for (size_t q = 0; q < nsel; q++) {
+    key[q] = gph_si_locus_key(seed, (uint64_t)e->si.sel.loci[q]);
+    key[nsel + q] = gph_si_locus_key(seed ^ GPH_SI_SITES, (uint64_t)e->si.sel.loci[q]);
+  }
+  const std::vector<uint8_t> pop = leaf_pops(e, false);
+  int rc = acc_zero(e, e->si.d, bytes);                /* (the records too: a fetch before the first sample reads zeros) */
+  if (!rc && nsel > 0) rc = h2d(e, e->si.d + o_key, key.data(), 2 * nsel * 8);
+  if (!rc) rc = h2d(e, e->si.d + o_pop, pop.data(), (size_t)n);
+  if (rc) { simulate_free(e); return rc; }
+  e->si.shape = h; e->si.gshape = g; e->si.pshape = ph; e->si.C = C;
+  e->si.o_sacc = o_sacc; e->si.o_sobs = o_sobs; e->si.o_key = o_key; e->si.o_skey = o_skey; e->si.o_pop = o_pop; e->si.o_rec = o_rec; e->si.bytes = bytes;
+  return selected_on(e, e->si, simulate_zero);
+}
+
+// one replicate of every selected locus under the current state, queued on the engine's stream: k_simulate, then (with sites)
+// the site loop on the replicate records.  The settle level is that of the time slices: the model is read from the chain state
+int gph_engine_simulate_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->si.on) return GPH_ESTATE;
+  const GphSiShape &h = e->si.shape;
+  const int nsel = (int)e->si.sel.loci.size(), groups = (nsel + h.bd - 1) / h.bd, k = groups > 0 ? (e->si.C > 0 ? 2 : 1) : 0;
+  /* (a rank without a selected locus launches nothing: its row stays 0) */
+  return sample_run(e, SETTLE_CHAIN, 25, k, SmTaken{&e->si.rows, true, &e->si.iters, iteration, &e->si.samples}, [&](void *row) {
+    launch_pre(e);
+    int rcl = launch_grid(e, GphGrid{groups, 1}, h.bd, (size_t)h.lds_bytes, k_simulate, e->ka, h, e->si.gshape, (const char *)e->dev.pages,
+                          (const int32_t *)e->si.sel.d_slot, (const uint64_t *)(e->si.d + e->si.o_key), (const uint8_t *)(e->si.d + e->si.o_pop), nsel, (int)e->L,
+                          (long long)e->si.samples, (double *)e->si.d, e->si.d + e->si.o_rec, (uint64_t *)row);
+    if (rcl || e->si.C == 0) return rcl;
+    return simulate_sites_launch(e, 0, (uint64_t *)row + h.RC);
+  });
+}
+
+int gph_engine_simulate_shape(gph_engine *e, int64_t *selected, int32_t *stats, int32_t *site_stats, int32_t *row_columns, int32_t *record_bytes,
+                              int64_t *samples, int32_t *rows_held)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->si.on;
+  if (selected) *selected = on ? (int64_t)e->si.sel.loci.size() : 0;
+  if (stats) *stats = on ? e->si.shape.M : 0;
+  if (site_stats) *site_stats = on ? e->si.C : 0;
+  if (row_columns) *row_columns = on ? e->si.shape.RC + e->si.C : 0;
+  if (record_bytes) *record_bytes = on ? e->si.gshape.img.bytes : 0;
+  if (samples) *samples = on ? e->si.samples : 0;
+  if (rows_held) *rows_held = on ? e->si.rows.fill : 0;
+  return 0;
+}
+
+int gph_engine_simulate_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->si : nullptr, out, max_loci, count); }
+
+// acc [selected][5 M + 1] (gt, eq, sx, sy, sy2 per statistic, then the failed replicates), site_acc [selected][C][5] (obs, gt, eq,
+// s1, s2; may be null), sites [selected] (may be null)
+int gph_engine_simulate_fetch_loci(gph_engine *e, double *acc, double *site_acc, int64_t *sites, int32_t reset)
+{
+  if (!e) return GPH_EARG;
+  if (!e->si.on) return GPH_ESTATE;
+  const size_t nsel = e->si.sel.loci.size();
+  if (nsel > 0 && !acc) return GPH_EARG;
+  SETDEV(e);
+  if (nsel > 0) { int rc = pull_rows(e, acc, e->si.d, e->si.o_sacc); if (rc) return rc; }
+  if (nsel > 0 && site_acc && e->si.C > 0) { int rc = d2h(e, site_acc, e->si.d + e->si.o_sacc, e->si.o_sobs - e->si.o_sacc); if (rc) return rc; }
+  if (sites) for (size_t q = 0; q < nsel; q++) sites[q] = e->si.sites[q];
+  return reset ? selected_zero(e, e->si) : 0;
+}
+
+// the rows taken since the last fetch ([rows][RC + C], with their iterations) and the data's totals (observed [C], may be null);
+// the row buffer is empty again
+int gph_engine_simulate_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *rows_out, uint64_t *observed, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || ((!rows_out || !iters) && max_rows > 0)) return GPH_EARG;
+  if (!e->si.on) return GPH_ESTATE;
+  SmRows &b = e->si.rows;
+  if (max_rows < b.fill) return GPH_EARG;
+  SETDEV(e);
+  if (observed && e->si.C > 0) { int rc = pull_rows(e, observed, e->si.d + e->si.o_sobs, (size_t)e->si.C * 8); if (rc) return rc; }
+  return rows_iters_fetch(e, b, e->si.iters, iters, rows_out, 0, true, rows);
+}
+
+// the replicate records of the latest sample, out [selected][record_bytes] in the layout of a gene-trees record; offsets as
+// gph_engine_gene_trees_shape hands them out (may be null)
+int gph_engine_simulate_fetch_records(gph_engine *e, void *out, int32_t *offsets)
+{
+  if (!e) return GPH_EARG;
+  if (!e->si.on) return GPH_ESTATE;
+  const size_t nsel = e->si.sel.loci.size();
+  if (nsel > 0 && !out) return GPH_EARG;
+  SETDEV(e);
+  if (offsets) for (int k = 0; k < GT_O_COUNT; k++) offsets[k] = e->si.gshape.off[k];
+  if (nsel > 0) return pull_rows(e, out, e->si.d + e->si.o_rec, nsel * (size_t)e->si.gshape.img.bytes);
+  return 0;
+}
+
+// which 0: the M statistics -- tmrca, length, genLnL, coal_<p>, mig_<b>; 1: the columns of a row -- s.coal_<p>, s.mig_<b>, r.coal_<p>,
+// r.mig_<b>, gt.tmrca, gt.length, gt.genLnL, failed, then r.<site statistic>; 2: the C site statistics (gph_engine_predictive_column_name)
+const char *gph_engine_simulate_column_name(gph_engine *e, int32_t which, int32_t col)
+{
+  if (!e || !e->si.on || col < 0) return nullptr;
+  const int K = e->cfg.K, B = e->cfg.B, Kc = e->cfg.Kc;
+  static const char *const fixed[SI_FIXED] = {"tmrca", "length", "genLnL"};
+  auto stat = [&](int c) { return c < SI_FIXED ? std::string(fixed[c]) : c < SI_FIXED + K ? "coal_" + std::to_string(c - SI_FIXED) : "mig_" + std::to_string(c - SI_FIXED - K); };
+  auto site = [&](int c) {
+    if (c == 0) return std::string("seg");
+    for (int p = 0; p < Kc; p++)
+      for (int q = p; q < Kc; q++)
+        if (gph_pd_pair(Kc, p, q) == c) return "diff_" + std::to_string(p) + "|" + std::to_string(q);
+    return std::string("?");
+  };
+  if (which == 0) {
+    if (col >= e->si.shape.M) return nullptr;
+    e->si.name = stat(col);
+  } else if (which == 1) {
+    if (col >= e->si.shape.RC + e->si.C) return nullptr;
+    const int KB = K + B;
+    if (col < 2 * KB) e->si.name = std::string(col < KB ? "s." : "r.") + stat(SI_FIXED + col % KB);
+    else if (col < 2 * KB + SI_FIXED) e->si.name = std::string("gt.") + fixed[col - 2 * KB];
+    else if (col == 2 * KB + SI_FIXED) e->si.name = "failed";
+    else e->si.name = "r." + site(col - e->si.shape.RC);
+  } else if (which == 2) {
+    if (col >= e->si.C) return nullptr;
+    e->si.name = site(col);
+  } else return nullptr;
+  return e->si.name.c_str();
 }
 
 // ---- two engines exchange their chain states (Metropolis-coupled chains)

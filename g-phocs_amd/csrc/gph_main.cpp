@@ -1,5 +1,5 @@
 // gph_main.cpp -- G-PhoCS-hip: the reference's command line (GPhoCS.c:84-238)
-//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--ess ess-prefix [--ess-loci SPEC]] [--predictive pp-prefix [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]] [--triplets tw-prefix [--triplets-pops "A,B,C;D,E,F"] [--triplets-loci SPEC] [--triplets-rows N]] [--mutations mutations-prefix [--mutations-loci SPEC] [--mutations-rows N]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] [--replicates R --replicates-out rep-prefix [--replicates-min-freq F] [--replicates-every k]] <control-file> [secondary-control-file]
+//   G-PhoCS-hip [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--ess ess-prefix [--ess-loci SPEC]] [--predictive pp-prefix [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]] [--triplets tw-prefix [--triplets-pops "A,B,C;D,E,F"] [--triplets-loci SPEC] [--triplets-rows N]] [--mutations mutations-prefix [--mutations-loci SPEC] [--mutations-rows N]] [--simulate sim-prefix [--simulate-loci SPEC] [--simulate-seed N] [--simulate-rows N] [--simulate-no-sites]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] [--replicates R --replicates-out rep-prefix [--replicates-min-freq F] [--replicates-every k]] <control-file> [secondary-control-file]
 // over libgphocs_hip.  The library comes in capacity variants (tighter LDS image = more
 // wavefronts per CU); the control file is read once with the default build to learn the model
 // dimensions, then the tightest variant that fits runs the chain.
@@ -36,6 +36,11 @@
 // --mutations PREFIX writes the posterior expected number of substitutions inside each population and on each sample's terminal
 // branch next to what the clock expects on the same exposure: per selected locus (--mutations-loci SPEC, default all) to
 // PREFIX.mutations.tsv, genome-wide per sample with the ratios' summary to PREFIX.mutations-genome.tsv (--mutations-rows N).
+// --simulate PREFIX confronts the demographic model itself: per sample and selected locus (--simulate-loci SPEC, default all) one
+// replicate genealogy is simulated on the device from the sampled parameters (the structured coalescent with migration), and,
+// unless --simulate-no-sites, a replicate alignment on it; the sampled genealogies' statistics against the replicates' and the
+// data's against the replicate alignments' go to PREFIX.simulate.tsv, the genome-wide totals per sample to
+// PREFIX.simulate-genome.tsv (--simulate-seed N, default the control file's random-seed; --simulate-rows N).
 // --beta B runs the whole chain on the power posterior p(D|G)^B p(G|Theta) p(Theta), B in [0, 64], 0 = the prior;
 // --marginal-likelihood PREFIX runs, behind the unchanged run, the ladder beta_k = (k/K)^(1/a) from 1 down to 0 (--ml-steps K,
 // default 32; --ml-alpha a, default 0.3; per rung --ml-burnin b discarded iterations, default the control file's burn-in or
@@ -162,6 +167,11 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--mutations") && i + 1 < argc) o.mutations_prefix = argv[++i];
     else if (!strcmp(argv[i], "--mutations-loci") && i + 1 < argc) o.mutations_loci = argv[++i];
     else if (!strcmp(argv[i], "--mutations-rows") && i + 1 < argc) { o.mutations_rows = atoi(argv[++i]); if (o.mutations_rows < 1) return usage(argv[0]); }
+    else if (!strcmp(argv[i], "--simulate") && i + 1 < argc) o.simulate_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--simulate-loci") && i + 1 < argc) o.simulate_loci = argv[++i];
+    else if (!strcmp(argv[i], "--simulate-seed") && i + 1 < argc) o.simulate_seed = argv[++i];
+    else if (!strcmp(argv[i], "--simulate-rows") && i + 1 < argc) { o.simulate_rows = atoi(argv[++i]); if (o.simulate_rows < 1) return usage(argv[0]); }
+    else if (!strcmp(argv[i], "--simulate-no-sites")) o.simulate_no_sites = 1;
     else if (!strcmp(argv[i], "--clades") && i + 1 < argc) o.clades_prefix = argv[++i];
     else if (!strcmp(argv[i], "--clades-loci") && i + 1 < argc) o.clades_loci = argv[++i];
     else if (!strcmp(argv[i], "--clades-slots") && i + 1 < argc) {
@@ -246,6 +256,10 @@ int main(int argc, char **argv)
   }
   if ((o.mutations_loci || o.mutations_rows) && !o.mutations_prefix) {
     fprintf(stderr, "%s: --mutations-loci and --mutations-rows need --mutations PREFIX\n", argv[0]);
+    return usage(argv[0]);
+  }
+  if ((o.simulate_loci || o.simulate_seed || o.simulate_rows || o.simulate_no_sites) && !o.simulate_prefix) {
+    fprintf(stderr, "%s: --simulate-loci, --simulate-seed, --simulate-rows and --simulate-no-sites need --simulate PREFIX\n", argv[0]);
     return usage(argv[0]);
   }
   if ((o.marginal_steps || o.marginal_burnin || o.marginal_samples || o.marginal_alpha != 0.0) && !o.marginal_prefix) {
@@ -375,7 +389,7 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(o.locus_summary_path); bad = 1; }
     if (bad && out) unlink(o.locus_summary_path);
   }
-  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.ess_prefix || o.predictive_prefix || o.triplets_prefix || o.mutations_prefix || o.marginal_prefix || o.mc3_report_prefix || o.replicates_prefix) {
+  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.ess_prefix || o.predictive_prefix || o.triplets_prefix || o.mutations_prefix || o.simulate_prefix || o.marginal_prefix || o.mc3_report_prefix || o.replicates_prefix) {
     /* the ranks' parts into the files, by the library that wrote them -- or, after a failure, removed */
     if (sym<decltype(&gph_run_finish)>(load_engine(dir, o.ctl, o.ctl2), "gph_run_finish")(&o, gpus, bad)) bad = 1;
   }

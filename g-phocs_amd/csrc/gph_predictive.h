@@ -200,18 +200,24 @@ GPH_SM_FN uint32_t gph_pd_row_sites(const char *blk, int q_phases, int q_count, 
 
 // workgroup bx = selected locus bx.  observed != 0: the data's statistics into acc[.][.][PD_OBS] and the observed row (no page
 // is read); else sample t.  P2: {phased, unphased} patterns per slot; key: Kl per selected locus; pop: leaf -> population;
-// acc [nsel][C][5]; row [C]
+// acc [nsel][C][5]; row [C].  The genealogy the sites are drawn on is handed over: recs == null, the sampled one (the node
+// records of the page); else the replicate genealogies of k_simulate (gph_simulate.h), recs [nsel][rec_bytes] with the node
+// records at rec_nodes and the root word at rec_root -- a replicate that failed (root < 0) is left out: no site, no word touched.
+// The rate is the locus's own either way.  One site loop for both.
 GPH_FLAT(k_predictive, GPH_PD_MAXTHREADS, GphKargs KA, GphPdShape h, const char *pages, const char *seq, const uint64_t *seq_off, const int32_t *P2,
-         const int32_t *sel_slot, const uint64_t *key, const uint8_t *pop, int nsel, int L, long long t, int observed, double *acc, uint64_t *row)
+         const int32_t *sel_slot, const uint64_t *key, const uint8_t *pop, int nsel, int L, long long t, int observed, double *acc, uint64_t *row,
+         const char *recs, int rec_bytes, int rec_nodes, int rec_root)
 {
   GPH_FLAT_BODY(GphNoLane);
   const GphLayout &y = KA.lay;
   const int n = y.n, N = y.N, NH = GPH_Q_NH(n), C = h.C, q = bx;
   if (q >= nsel) return;
+  if (recs && !observed && *(const int32_t *)(recs + (size_t)q * rec_bytes + rec_root) < 0) return;
   const int j = GPH_IX(sel_slot[GPH_IX(q, nsel)], L);
   const int P = P2[GPH_IX(2 * j, 2 * L)];
   const char *blk = seq + seq_off[GPH_IX(j, L + 1)];
   const char *pg = pages + (size_t)j * y.page_bytes;
+  const char *nodes = recs ? recs + (size_t)q * rec_bytes + rec_nodes : pg + y.o_nd;
   const int q_phases = GPH_Q_PHASES(P, n), q_count = GPH_Q_COUNT(P, n);
   GphPdLds s;
   gph_pd_carve(lds, h, s);
@@ -222,7 +228,7 @@ GPH_FLAT(k_predictive, GPH_PD_MAXTHREADS, GphKargs KA, GphPdShape h, const char 
     if (!observed)
       for (int v = tid; v < N; v += bd) {
         GphNode rec;
-        gph_copy16(&rec, pg + y.o_nd + (size_t)v * 16);
+        gph_copy16(&rec, nodes + (size_t)v * 16);
         s.age[GPH_IX(v, N)] = rec.age;
         s.up[GPH_IX(v, N)] = rec.father;
       }

@@ -1,8 +1,8 @@
-// gph_textjoin.h -- the five outputs that travel through text parts (gph_textparts.h): what each format's lines mean
+// gph_textjoin.h -- the six outputs that travel through text parts (gph_textparts.h): what each format's lines mean
 // once the last rank is done (gph_run_finish), and nothing else: its header line, which tag goes to which file, its summary
 // and its line on stdout.  The parts' writers are the outputs of a run (gph_program.cpp, gph_*_run.h).
 //
-// This header DEFINES the ten gph_<name>_write / _discard entry points: one translation unit of a program includes it
+// This header DEFINES the twelve gph_<name>_write / _discard entry points: one translation unit of a program includes it
 // (gph_program.cpp in the library; a stand-alone program that wants the joiners without the engine includes it itself).
 #ifndef GPH_TEXTJOIN_H
 #define GPH_TEXTJOIN_H
@@ -338,8 +338,96 @@ struct MuJoin : TextJoin {
     fflush(stdout);
   }
 };
+// replicate genealogies: "H\t<samples>\t<M>\t<C>\t<K>\t<B>\t<seed>" + "\t<name>" per genealogy statistic, then per site statistic; a
+// rank's rows of PREFIX.simulate.tsv as "L\t<minP, %a>\t<failed>\t" + row, its observed site totals as "O" + "\t<u64>", its
+// per-sample rows as R lines of 2 (K + B) + 4 + C numbers; the L rows are concatenated in rank order, the O and R lines added
+struct SiJoin : TextJoin {
+  long long S = -1, M = -1, C = -1, K = -1, B = -1, Q = 0, lo_at = -1, failed = 0;
+  unsigned long long seed = 0;
+  double lo = 0.0;
+  std::vector<std::string> names;                       /* [M + C] */
+  std::vector<unsigned long long> observed;             /* [C] */
+  TextRows rows;
+  SiJoin() : TextJoin(true) {}
+  bool header(char *line, ssize_t len, int) override
+  {
+    long long s = 0, m = 0, c = 0, k = 0, b = 0;
+    unsigned long long sd = 0;
+    int used = 0;
+    if (!(sscanf(line, "H\t%lld\t%lld\t%lld\t%lld\t%lld\t%llu%n", &s, &m, &c, &k, &b, &sd, &used) == 6 &&
+          (S < 0 || (s == S && m == M && c == C && k == K && b == B && sd == seed)) && k >= 1 && b >= 0 && c >= 0 && m == 3 + k + b && line[len - 1] == '\n')) return false;
+    if (S >= 0) return true;
+    S = s; M = m; C = c; K = k; B = b; seed = sd;
+    names = tab_fields(line + used, (size_t)len - used - 1);
+    if ((long long)names.size() != M + C) return false;
+    observed.assign((size_t)C + 1, 0);
+    rows.shape(S, 2 * (K + B) + 4 + C);
+    fprintf(out[0], "locus\tname\tsamples\tfailed\tsites");
+    for (long long i = 0; i < M + C; i++) {
+      const char *nm = names[(size_t)i].c_str();
+      fprintf(out[0], "\t%s_%s\tmean_%s\tsd_%s\tp_%s", i < M ? "s" : "obs", nm, nm, nm, nm);
+    }
+    fprintf(out[0], "\tminP\tstat\n");
+    return true;
+  }
+  bool body(char *line, ssize_t, int r) override
+  {
+    if (line[0] == 'O') return TextRows::numbers(line + 1, C, observed.data());
+    if (line[1] != '\t') return false;
+    if (line[0] == 'R') return rows.row(line, r);
+    if (line[0] != 'L') return false;
+    char *end = nullptr, *end2 = nullptr;
+    const double v = strtod(line + 2, &end);
+    if (!end || *end != '\t') return false;
+    const long long f = strtoll(end + 1, &end2, 10);
+    if (!end2 || end2 == end + 1 || *end2 != '\t') return false;
+    if (f < S && (lo_at < 0 || v < lo)) { lo = v; lo_at = atoll(end2 + 1); }     /* (a locus without a replicate has no p) */
+    failed += f;
+    Q++;
+    fputs(end2 + 1, out[0]);
+    return true;
+  }
+  bool rank_done() override { return rows.rank_done(); }
+  void summary() override
+  {
+    const long long KB = K + B, W = 2 * KB + 4 + C;
+    fprintf(out[0], "# loci %lld samples %lld seed %llu failed %lld minMinP %.10g (locus %lld)\n", Q, S, seed, failed, lo, lo_at);
+    fprintf(out[1], "iter");
+    for (int w = 0; w < 2; w++)
+      for (long long c = 0; c < KB; c++) fprintf(out[1], "\t%s.%s", w ? "r" : "s", names[(size_t)(3 + c)].c_str());
+    for (int c = 0; c < 3; c++) fprintf(out[1], "\tgt.%s", names[(size_t)c].c_str());
+    fprintf(out[1], "\tfailed");
+    for (long long c = 0; c < C; c++) fprintf(out[1], "\tr.%s", names[(size_t)(M + c)].c_str());
+    fputc('\n', out[1]);
+    rows.print(out[1]);
+    const std::vector<unsigned long long> &t = rows.totals;
+    unsigned long long live = 0;                          /* replicates that did not fail, over the samples */
+    for (long long s = 0; s < S; s++) live += (unsigned long long)Q - t[(size_t)(s * W + 2 * KB + 3)];
+    std::string obs = "# observed", mean = "# mean", pl = "# p";
+    char num[64];
+    for (long long c = 0; c < W; c++) {
+      unsigned long long sum = 0, gt = 0, eq = 0;
+      const bool site = c > 2 * KB + 3, rep = c >= KB && c < 2 * KB;
+      for (long long s = 0; s < S; s++) {
+        const unsigned long long v = t[(size_t)(s * W + c)], against = site ? observed[(size_t)(c - 2 * KB - 4)] : rep ? t[(size_t)(s * W + c - KB)] : 0;
+        sum += v; gt += v > against; eq += v == against;
+      }
+      if (site) { snprintf(num, sizeof num, "\t%llu", observed[(size_t)(c - 2 * KB - 4)]); obs += num; } else obs += "\t-";
+      snprintf(num, sizeof num, "\t%.10g", S > 0 ? (double)sum / (double)S : 0.0); mean += num;
+      if (site || rep) snprintf(num, sizeof num, "\t%.10g", S > 0 ? ((double)gt + (double)eq / 2) / (double)S : 0.0);
+      else if (c >= 2 * KB && c < 2 * KB + 3) snprintf(num, sizeof num, "\t%.10g", live > 0 ? (double)sum / (double)live : 0.0);
+      else snprintf(num, sizeof num, "\t-");
+      pl += num;
+    }
+    fprintf(out[1], "%s\n%s\n%s\n# loci %lld samples %lld seed %llu\n", obs.c_str(), mean.c_str(), pl.c_str(), Q, S, seed);
+    printf("Simulate: %s\n", pl.c_str() + 2);
+    fflush(stdout);
+  }
+};
 }   // namespace
 
+extern "C" int gph_simulate_write(const char *prefix, int32_t ranks) { SiJoin J; return text_join(SI_TEXT, J, prefix, ranks); }
+extern "C" int gph_simulate_discard(const char *prefix, int32_t ranks) { return text_discard(SI_TEXT, prefix, ranks); }
 extern "C" int gph_clades_write(const char *prefix, int32_t ranks) { ClJoin J; return text_join(CL_TEXT, J, prefix, ranks); }
 extern "C" int gph_ess_write(const char *prefix, int32_t ranks) { EsJoin J; return text_join(ES_TEXT, J, prefix, ranks); }
 extern "C" int gph_predictive_write(const char *prefix, int32_t ranks) { PdJoin J; return text_join(PD_TEXT, J, prefix, ranks); }

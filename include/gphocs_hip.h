@@ -706,6 +706,80 @@ int gph_engine_mutations_fetch_loci(gph_engine *e, double *out /* [selected][ld]
 int gph_engine_mutations_fetch_rows(gph_engine *e, double *out /* [rows][1 + C] */, int32_t max_rows, int32_t *rows);
 const char *gph_engine_mutations_column_name(gph_engine *e, int32_t col);
 
+/* REPLICATE GENEALOGIES simulated from the sampled parameters, of selected loci and genome-wide per sample (k_simulate:
+ * csrc/gph_simulate.h; timing class 25).  The predictive checks above redraw the data ON the sampled genealogy and so test the
+ * mutation process alone; here the replicate is drawn from the parameters, G_rep ~ p(G | Theta_s) by direct simulation of the
+ * structured coalescent with migration, and D_rep ~ p(D | G_rep) on it: the check of the demographic model against the data, the
+ * realized discrepancy T(G_s, Theta_s) against T(G_rep, Theta_s) of the sampled genealogies against their prior, and -- at beta 0,
+ * where G_s and G_rep are exchangeable -- a check of the sampler itself: every mid-p must centre on 0.5.
+ * THE DEFINITION; all arithmetic is plain uncontracted fp64 in the order written, log is the engine's own (glibc's log bit for bit), x / theta_p the
+ * correctly rounded quotient, every other quotient IEEE division.
+ *   model      theta, popAge, sampleAge, popFather, migRate, bandStart, bandEnd, bandSrc, bandTgt of the chain state (settled as for
+ *              the time slices); leaf i belongs to the current population whose samples hold it
+ *   generator  mix as for the predictive checks.  Kl = mix((seed ^ 0x53494D554C415445) ^ mix(g + 0x9E3779B97F4A7C15)), g the GLOBAL
+ *              locus index; Ks = mix(Kl + t), t = samples taken since _enable / a reset; Ka = mix(Ks + (a + 1) 0xD1B54A32D192ED03)
+ *              for attempt a = 0 .. 15; draw d = 0, 1, ... of the attempt: u_d = ((mix(Ka ^ d) >> 12) + 0.5) 2^-52, in (0, 1)
+ *   lineages   a list of (node, population).  enter(t): every current population p in index order that has not entered and has
+ *              sampleAge[p] <= t enters -- its leaves are appended in leaf order, each in p, leaf age sampleAge[p] --; then every
+ *              lineage in list order climbs: while its population has a father F with popAge[F] <= t it moves to F
+ *   start      t = 0; enter(0)
+ *   step       one lineage left and every population entered: the end; the root is node N - 1.  Else with c[p] = the lineages in p:
+ *              rates in this order -- p = 0 .. K - 1 with c[p] >= 2: r = (c (c - 1)) / theta_p; b = 0 .. B - 1 with bandStart[b] <= t
+ *              < bandEnd[b] and c[tgt b] >= 1: r = c[tgt b] migRate[b] --, R = R + r from 0.0 in that order.  nb = the smallest of
+ *              popAge[p] (p >= Kc), sampleAge[p] (p < Kc), bandStart[b], bandEnd[b] that is > t (none: infinity).  u = the next
+ *              draw (spent whatever follows); w = -log(u) / R.  If !(R > 0) or t + w >= nb: t' = nb (a BOUNDARY), else t' = t + w.
+ *              t' infinite: the attempt fails.  dt = t' - t; exposures: coal_p = coal_p + (c (c - 1)) dt for c[p] >= 2, mig_b =
+ *              mig_b + c[tgt b] dt for the bands live at t with c >= 1.  t = t'.  A boundary: enter(t), next step.  Else x = u' R
+ *              with the next draw u'; walking the non-zero rates in the same order, acc = acc + r from 0.0, the event is the first
+ *              with x < acc; the last non-zero rate takes the rounding residue
+ *   coalescence in p, c = c[p]: two further draws u, u': a = min(int(u c), c - 1), b = min(int(u' (c - 1)), c - 2), b += (b >= a);
+ *              the a-th and b-th lineages of p in list order.  Node v = n + (coalescences so far): age t, npop p, left = the one
+ *              earlier in the list, right = the later; v takes the earlier slot, the later slot is removed, the order is kept
+ *   migration  in b: with GPH_GT_MAX_MIGS migrations recorded already the attempt is ABANDONED and redrawn with the next a (the
+ *              chain's prior is truncated there, so the rejection is exact).  One further draw u: k = min(int(u c[tgt b]), c - 1);
+ *              the k-th lineage of tgt b in list order moves to bandSrc[b]; migration m = (migrations so far): branch = its node,
+ *              band b, spop = bandSrc[b], tpop = bandTgt[b], age t, living[m] = m
+ *   failed     after 16 attempts: the replicate of the locus at that sample is FAILED -- counted per locus and in the row's
+ *              `failed` column, left out of every statistic; its record is all zero with root -1
+ *   record     the layout of a gene-trees record (gph_engine_gene_trees_shape's offsets; gph_gene_trees_decode and
+ *              gph_gene_tree_newick read it unchanged); dataLnL = 0; genLnL as the engine's gtree_lnl forms it, every population
+ *              and band, no constant: lnL = 0.0; p = 0 .. K - 1: lnL += n_p log(2 / theta_p) - coal_p / theta_p; b = 0 .. B - 1 with
+ *              migRate[b] > 0: lnL += m_b log(migRate[b]) - mig_b migRate[b], n_p / m_b the replicate's coalescences / migrations
+ *   statistics M = 3 + K + B: tmrca (the root's age), length (the sum over the nodes v != root in node order of age[father v] -
+ *              age[v]), genLnL, coal_<p>, mig_<b>.  x on the sampled genealogy (settled node records, the page's counts and
+ *              genLnL), y on the replicate.  Per (selected locus, statistic) five doubles in sample order: gt += (y > x), eq +=
+ *              (y == x), sx = sx + x, sy = sy + y, sy2 = sy2 + y y; behind the 5 M one double: the failed replicates
+ *   sites      (with_sites) the replicate alignment is drawn on the replicate genealogy with the locus's rate and missing-data
+ *              pattern by the predictive checks' own site loop -- everything as defined there with K = mix(Kl' + t), Kl' =
+ *              mix((seed ^ 0x53494D554C415445 ^ 0x5349544553) ^ mix(g + 0x9E3779B97F4A7C15)) --: C statistics a locus, five
+ *              doubles obs, gt, eq, s1, s2 each.  A failed replicate adds nothing
+ *   rows       per sample the iteration and 2 (K + B) + 4 + C uint64 totals over the rank's selected loci (integer atomics; the
+ *              rows of the ranks add): the sampled coal_p, mig_b, the replicate's coal_p, mig_b, the loci with y > x for tmrca,
+ *              length, genLnL, `failed`, then the replicate's C site totals; the data's site totals once
+ *   _enable    capacity_rows per-sample rows; 0 frees everything, the feature is off.  The selection, the refusals and the limits
+ *              as for gph_engine_predictive_enable (the 2^32 bound only with_sites); GPH_EFULL above max_bytes (<= 0: 1 GiB)
+ *   _sample    k_simulate, then (with_sites) the site loop, on the engine's stream, no host synchronisation; a rank without a
+ *              selected locus launches nothing and still takes the (zero) row.  GPH_EFULL when the row buffer is full
+ *   _shape     selected loci of the rank, M, C (0 without sites), the columns of a row, the bytes of a record, samples since the
+ *              accumulators were zeroed, rows held (all 0 while off)
+ *   _fetch_loci   acc[selected][5 M + 1], site_acc[selected][C][5] (may be NULL), sites[selected] (may be NULL); reset != 0 zeroes
+ *              the accumulators afterwards and restarts t at 0
+ *   _fetch_rows   as gph_engine_predictive_fetch_rows, observed[C]
+ *   _fetch_records  the latest sample's replicates, out[selected][record bytes]; offsets[GPH_GT_O_COUNT] (may be NULL)
+ *   _column_name  which 0: statistic col; 1: row column col ("s.", "r." for sampled / replicate, "gt.", "failed"); 2: site statistic
+ * The kernels write no page and touch neither the chain state nor a locus generator. */
+int gph_engine_simulate_enable(gph_engine *e, uint64_t seed, int32_t capacity_rows, const int64_t *loci, int64_t nloci, int32_t with_sites,
+                               int64_t max_bytes);
+int gph_engine_simulate_sample(gph_engine *e, int32_t iteration);
+int gph_engine_simulate_shape(gph_engine *e, int64_t *selected, int32_t *stats, int32_t *site_stats, int32_t *row_columns, int32_t *record_bytes,
+                              int64_t *samples, int32_t *rows_held);
+int gph_engine_simulate_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_simulate_fetch_loci(gph_engine *e, double *acc /* [selected][5 M + 1] */, double *site_acc /* [selected][C][5] */, int64_t *sites,
+                                   int32_t reset);
+int gph_engine_simulate_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *rows_out, uint64_t *observed, int32_t max_rows, int32_t *rows);
+int gph_engine_simulate_fetch_records(gph_engine *e, void *out /* [selected][record bytes] */, int32_t *offsets);
+const char *gph_engine_simulate_column_name(gph_engine *e, int32_t which, int32_t col);
+
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
  * engine: general-slot RNG, priors, accept decisions of the global proposals
@@ -1134,6 +1208,34 @@ typedef struct gph_run_options {
    * without. */
   const char *mutations_prefix, *mutations_loci;
   int32_t mutations_rows;
+  /* `--simulate PREFIX [--simulate-loci SPEC] [--simulate-seed N] [--simulate-rows N] [--simulate-no-sites]`: replicate genealogies
+   * simulated from the sampled parameters (gph_engine_simulate_* above).  A sample is taken wherever a trace line is written.
+   * simulate_loci as gene_trees_loci; simulate_seed: an unsigned decimal number (NULL: the control file's random-seed);
+   * simulate_rows: the rows of the device buffer (0: a default); simulate_no_sites != 0: the genealogy level alone.  Any of them
+   * without simulate_prefix, a seed that is no number and negative rows are GPH_EARG with a message, before anything is read.
+   * Rank r writes its part PREFIX.simulate.part<r> once, at the end; gph_simulate_write makes of the parts (numbers "%.10g")
+   *   PREFIX.simulate.tsv         header locus name samples failed sites; per genealogy statistic -- tmrca, length, genLnL,
+   *                               coal_<pop>, mig_<src>-><tgt> -- s_<stat> mean_<stat> sd_<stat> p_<stat>: the sampled genealogies'
+   *                               mean sx / V, the replicates' mean sy / V and sd sqrt((sy2 - sy sy / V) / (V - 1)) (0 for V < 2
+   *                               or a negative radicand), the mid-p (gt + eq / 2) / V, V = samples - failed (all 0 for V = 0);
+   *                               with sites per site statistic obs_ mean_ sd_ p_ as PREFIX.predictive.tsv prints them, over V;
+   *                               then minP = the smallest 2 min(p, 1 - p) and the statistic that has it (the first of equal
+   *                               ones).  One row per selected locus, ranks in rank order; a last line
+   *                               "# loci Q samples S seed N failed F minMinP v (locus g)"
+   *   PREFIX.simulate-genome.tsv  header iter and the columns of a row (gph_engine_simulate_column_name, which 1, with the
+   *                               populations' and bands' names); one row per sample, the ranks' rows added; then
+   *                                   # observed   "-" per genealogy column, the data's total per site column
+   *                                   # mean       the column's mean over the samples
+   *                                   # p          "-" for s.* and failed; r.coal_* / r.mig_*: the mid-p of the replicates'
+   *                                                total against the sampled total of the same sample; gt.*: sum gt / sum (Q -
+   *                                                failed) over the samples; site columns: the mid-p against the observed total
+   *                               and a last line "# loci Q samples S seed N"
+   * and prints "Simulate: " and the p line on stdout.  Both files are written once, on success only; a failed run leaves
+   * neither parts nor files.  With mc3_chains, replicates and marginal_prefix they describe chain 0 and the run proper, with
+   * beta that chain.  Not built: a file of the replicate trees (gph_engine_simulate_fetch_records hands them out), replicates
+   * per heated or replicate chain, models other than the run's own. */
+  const char *simulate_prefix, *simulate_loci, *simulate_seed;
+  int32_t simulate_rows, simulate_no_sites;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
@@ -1161,6 +1263,8 @@ int gph_triplets_write(const char *prefix, int32_t ranks);
 int gph_triplets_discard(const char *prefix, int32_t ranks);
 int gph_mutations_write(const char *prefix, int32_t ranks);
 int gph_mutations_discard(const char *prefix, int32_t ranks);
+int gph_simulate_write(const char *prefix, int32_t ranks);
+int gph_simulate_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
  * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
  * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
