@@ -618,6 +618,9 @@ def _load_library(path):
     lib.gph_engine_simulate_fetch_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gph_engine_simulate_column_name.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.gph_engine_simulate_column_name.restype = C.c_char_p
+    # tests only, not in include/gphocs_hip.h (the trailing underscore): the cross-locus reduction on its own (csrc/gph_engine.hip)
+    lib.gph_debug_reduce_.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32]
     return lib
 
 

@@ -13,6 +13,9 @@
 
 // blocks of a flat launch (launch_grid): x, and y for the samplers that tile a chunk
 struct GphGrid { int x, y; };
+// what the reduction probe (debug_reduce, tests only) fills its buffers with before anything is folded: a quiet NaN with a
+// recognisable payload (info[8], info[9] of the probe: its low and high words)
+static const uint64_t GPH_RED_POISON = 0x7FF8DEADBEEF0BADull;
 
 // What a launch counts -- host_stats(), class_stats() and last_kernel_ms are asserted by tests, so the rules are kept as
 // they grew, and they are not the same in the two builds:
@@ -66,20 +69,46 @@ static int compare_order_after(gph_engine *const *, int) { return 0; }
 // a sampler's result -> the caller's buffer, with the call's one host synchronisation
 static int pull_rows(gph_engine *e, void *h, const void *d, size_t n) { memcpy(h, d, n); e->n_syncs++; return 0; }
 
-static int reduce_local(gph_engine *e, int sec, int ncols)
+// the serial fold of one section over L loci into `red` (that section of a reduced row): sum, minimum and maximum per column,
+// the loci in index order.  The engine (reduce_local) and the reduction probe (debug_reduce) both run this text
+static void reduce_serial(const double *out, const double *stats, int64_t L, int sec, int ncols, double *red)
 {
-  double *red = e->d_red + sec * GPH_RED_STRIDE;
   for (int c = 0; c < ncols; c++) {
     double s = 0, mn = 1e300, mx = -1e300;
-    for (int64_t g = 0; g < e->L; g++) {
+    for (int64_t g = 0; g < L; g++) {
       double v;
-      if (sec == 0) v = e->dev.out[(size_t)g * GPH_OUT_SLOTS + c];
-      else v = e->dev.stats[(size_t)g * ncols + c];
+      if (sec == 0) v = out[(size_t)g * GPH_OUT_SLOTS + c];
+      else v = stats[(size_t)g * ncols + c];
       s += v; mn = v < mn ? v : mn; mx = v > mx ? v : mx;
     }
     red[c] = s; red[GPH_RED_COLS + c] = mn; red[2 * GPH_RED_COLS + c] = mx;
   }
+}
+static int reduce_local(gph_engine *e, int sec, int ncols)
+{
+  double *red = e->d_red + sec * GPH_RED_STRIDE;
+  reduce_serial(e->dev.out, e->dev.stats, e->L, sec, ncols, red);
   red[3 * GPH_RED_COLS] = (double)*e->dev.err;
+  return 0;
+}
+// the reduction probe (gph_debug_reduce_ in gph_engine.hip): launch i folds input set i % nsets into row i with the engine's
+// serial loop; the error word goes where the device's final pass puts it (section 0's first trailing word)
+static int debug_reduce(const double *out0, const double *stats1, int64_t L, int nc0, int nc1, int nsets, int err_word, int launches,
+                        double *rows, int32_t *info, int)
+{
+  for (size_t i = 0; i < (size_t)launches * GPH_RED_ROW; i++) memcpy(rows + i, &GPH_RED_POISON, 8);
+  for (int i = 0; i < launches; i++) {
+    const size_t set = (size_t)(i % nsets);
+    double *red = rows + (size_t)i * GPH_RED_ROW;
+    if (nc0 > 0) reduce_serial(out0 + set * L * GPH_OUT_SLOTS, nullptr, L, 0, nc0, red);
+    if (nc1 > 0) reduce_serial(nullptr, stats1 + set * L * nc1, L, 1, nc1, red + GPH_RED_STRIDE);
+    red[3 * GPH_RED_COLS] = (double)err_word;
+  }
+  if (info) {     /* no tree here: no sub-sequences, no unroll, no ticket */
+    const int32_t v[10] = {GPH_RED_COLS, GPH_RED_STRIDE, GPH_RED_ROW, GPH_RED_BLOCKS, 0, 0, GPH_OUT_SLOTS, 0,
+                           (int32_t)(uint32_t)GPH_RED_POISON, (int32_t)(uint32_t)(GPH_RED_POISON >> 32)};
+    memcpy(info, v, sizeof v);
+  }
   return 0;
 }
 
@@ -584,6 +613,66 @@ static int debug_math(const double *x, const double *y, int n, double *out, int 
   { int rcl = launch_on(nullptr, GphGrid{(n + GPH_FLAT_THREADS - 1) / GPH_FLAT_THREADS, 1}, GPH_FLAT_THREADS, 0, which ? k_debug_accept : k_debug_math, ka, dx, dy, n, dout); if (rcl) return rcl; }
   HIPCHK(hipMemcpy(out, dout, sizeof(double) * (which ? 3 : 5) * n, hipMemcpyDeviceToHost));
   (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
+  return 0;
+}
+// the reduction probe (gph_debug_reduce_ in gph_engine.hip): k_reduce_stage itself, no engine.  `launches` launches back to
+// back on one stream of its own, no host synchronisation between them; launch i folds input set i % nsets into row i, all of
+// them through ONE partials buffer and ONE ticket sized as the engine's (gph_engine_load_loci, backend_open) -- what an
+// iteration's six reductions share.  The partials and the rows start as GPH_RED_POISON; no stage runs (do_stage = 0)
+struct GphRedProbe {
+  double *out = nullptr, *stats = nullptr, *part = nullptr, *rows = nullptr;
+  unsigned *ticket = nullptr;
+  int32_t *err = nullptr;
+  hipStream_t stream = nullptr;
+  ~GphRedProbe()
+  {
+    dev_free(out); dev_free(stats); dev_free(part); dev_free(rows); dev_free(ticket); dev_free(err);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+static int debug_reduce(const double *out0, const double *stats1, int64_t L, int nc0, int nc1, int nsets, int err_word, int launches,
+                        double *rows, int32_t *info, int device)
+{
+  HIPCHK(hipSetDevice(device));
+  GphRedProbe p;
+  const size_t n0 = nc0 > 0 ? (size_t)nsets * L * GPH_OUT_SLOTS : 0, n1 = nc1 > 0 ? (size_t)nsets * L * nc1 : 0;
+  const size_t npart = (size_t)2 * 3 * GPH_RED_BLOCKS * GPH_RED_COLS, nrows = (size_t)launches * GPH_RED_ROW;
+  std::vector<uint64_t> poison(npart > nrows ? npart : nrows, GPH_RED_POISON);
+  HIPCHK(hipStreamCreate(&p.stream));
+  if (n0) { HIPCHK(hipMalloc((void **)&p.out, sizeof(double) * n0)); HIPCHK(hipMemcpy(p.out, out0, sizeof(double) * n0, hipMemcpyHostToDevice)); }
+  if (n1) { HIPCHK(hipMalloc((void **)&p.stats, sizeof(double) * n1)); HIPCHK(hipMemcpy(p.stats, stats1, sizeof(double) * n1, hipMemcpyHostToDevice)); }
+  HIPCHK(hipMalloc((void **)&p.part, sizeof(double) * npart));
+  HIPCHK(hipMalloc((void **)&p.rows, sizeof(double) * nrows));
+  HIPCHK(hipMalloc((void **)&p.ticket, 64));
+  HIPCHK(hipMalloc((void **)&p.err, sizeof(int32_t)));
+  HIPCHK(hipMemcpy(p.part, poison.data(), sizeof(double) * npart, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(p.rows, poison.data(), sizeof(double) * nrows, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(p.ticket, 0, 64));
+  HIPCHK(hipMemcpy(p.err, &err_word, sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipDeviceSynchronize());
+  GphKargs ka;
+  memset(&ka, 0, sizeof ka);
+  GphDev dev;
+  memset(&dev, 0, sizeof dev);
+  dev.L = (int32_t)L;
+  dev.err = p.err;
+  const GphStageList none = {0, {0}, {0}};
+  for (int i = 0; i < launches; i++) {
+    const size_t set = (size_t)(i % nsets);
+    dev.out = n0 ? p.out + set * L * GPH_OUT_SLOTS : nullptr;
+    dev.stats = n1 ? p.stats + set * L * nc1 : nullptr;
+    { int rcl = launch_on(p.stream, GphGrid{GPH_RED_BLOCKS, 1}, GPH_RED_THREADS, 0, k_reduce_stage, ka, dev, nc0, nc1, p.part, p.ticket,
+                          p.rows + (size_t)i * GPH_RED_ROW, 0, none, 0); if (rcl) return rcl; }
+  }
+  HIPCHK(hipStreamSynchronize(p.stream));
+  unsigned ticket = 0;
+  HIPCHK(hipMemcpy(rows, p.rows, sizeof(double) * nrows, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&ticket, p.ticket, sizeof ticket, hipMemcpyDeviceToHost));
+  if (info) {
+    const int32_t v[10] = {GPH_RED_COLS, GPH_RED_STRIDE, GPH_RED_ROW, GPH_RED_BLOCKS, GPH_RED_SUBS, GPH_RED_UNROLL, GPH_OUT_SLOTS, (int32_t)ticket,
+                           (int32_t)(uint32_t)GPH_RED_POISON, (int32_t)(uint32_t)(GPH_RED_POISON >> 32)};
+    memcpy(info, v, sizeof v);
+  }
   return 0;
 }
 #endif

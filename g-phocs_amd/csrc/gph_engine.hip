@@ -191,7 +191,10 @@ __device__ __forceinline__ void reduce_run(const double *src, int stride, int co
   }
 }
 // cbase: first column of the window this call folds (at most 128 columns a call; the many-band build's statistics row is
-// folded window by window -- every column's additions are the same whatever the windows)
+// folded window by window).  A column's additions have the shape of ITS window's width, not of the row's: Q = 8 sub-sequences
+// in a full window of 128, and in the last window whatever its own width gives -- at 278 columns the first 256 are folded with
+// Q = 8 and the last 22 (a window of 22: cw = 32) with Q = 16.  Fixed for a given column count, so still the same run to run;
+// tests/reduce_util.py restates the shape and the probe gph_debug_reduce_ holds the kernel to it bit for bit
 __device__ void reduce_partial_body(const GphDev &D, int mode, int ncols, int cbase, int stride_cols, double *part, double (*sh)[GPH_RED_SUBS * 4][16])
 {
   /* a wavefront covers 64 / cw loci at a time (cw = columns rounded up to 16, 32 or 64): every lane has work */
@@ -1677,6 +1680,19 @@ int gph_debug_accept_(const double *x, const double *u, int32_t n, double *out, 
 {
   if (!x || !u || !out || n <= 0) return GPH_EARG;
   return debug_math(x, u, n, out, device, 1);
+}
+// tests only (not part of include/gphocs_hip.h): the cross-locus reduction on its own, no engine.  out0: [nsets][L][GPH_OUT_SLOTS]
+// (section 0, nc0 columns of it folded), stats1: [nsets][L][nc1] (section 1); launch i of `launches` folds set i % nsets into
+// rows[i][GPH_RED_ROW], back to back as the reductions of an iteration (gph_backend.h: debug_reduce); err_word: what the error
+// word holds.  rows start as the poison, so what a launch did not write reads as that.  info[10] (may be null): GPH_RED_COLS,
+// _STRIDE, _ROW, _BLOCKS, _SUBS, _UNROLL (the last two 0 in the host build: a serial loop), GPH_OUT_SLOTS, the ticket word after
+// the last launch, the poison's low and high words.  Refused before anything is allocated, launched or written: GPH_EARG
+int gph_debug_reduce_(const double *out0, const double *stats1, int64_t L, int32_t nc0, int32_t nc1, int32_t nsets, int32_t err_word,
+                      int32_t launches, double *rows, int32_t *info, int32_t device)
+{
+  if (L < 1 || L > INT32_MAX || nc0 < 0 || nc0 > GPH_OUT_SLOTS || nc1 < 0 || nc1 > GPH_RED_COLS || (nc0 == 0 && nc1 == 0)) return GPH_EARG;
+  if ((nc0 > 0 && !out0) || (nc1 > 0 && !stats1) || nsets < 1 || launches < 1 || !rows) return GPH_EARG;
+  return debug_reduce(out0, stats1, L, nc0, nc1, nsets, err_word, launches, rows, info, device);
 }
 
 // tests only (not part of include/gphocs_hip.h): the pass ahead of the sweep.  info[4] = on, M, C, bytes per locus;
