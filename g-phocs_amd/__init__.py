@@ -283,7 +283,9 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("triplets_prefix", C.c_char_p), ("triplets_pops", C.c_char_p), ("triplets_loci", C.c_char_p), ("triplets_rows", C.c_int32),
                 ("mutations_prefix", C.c_char_p), ("mutations_loci", C.c_char_p), ("mutations_rows", C.c_int32),
                 ("simulate_prefix", C.c_char_p), ("simulate_loci", C.c_char_p), ("simulate_seed", C.c_char_p), ("simulate_rows", C.c_int32),
-                ("simulate_no_sites", C.c_int32)]
+                ("simulate_no_sites", C.c_int32),
+                ("pair_times_prefix", C.c_char_p), ("pair_times_pops", C.c_char_p), ("pair_times_grid", C.c_char_p), ("pair_times_loci", C.c_char_p),
+                ("pair_times_rows", C.c_int32)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
@@ -295,7 +297,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                      predictive=None, predictive_loci=None, predictive_seed=None, predictive_rows=0,
                      triplets=None, triplets_pops=None, triplets_loci=None, triplets_rows=0,
                      mutations=None, mutations_loci=None, mutations_rows=0,
-                     simulate=None, simulate_loci=None, simulate_seed=None, simulate_rows=0, simulate_no_sites=False):
+                     simulate=None, simulate_loci=None, simulate_seed=None, simulate_rows=0, simulate_no_sites=False,
+                     pair_times=None, pair_times_pops=None, pair_times_grid=None, pair_times_loci=None, pair_times_rows=0):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
     marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
@@ -309,7 +312,9 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
     as "A,B,C;D,E,F" (None: all), triplets_loci a SPEC, triplets_rows 0: the default row buffer.  mutations: the prefix of PREFIX.mutations.tsv /
     PREFIX.mutations-genome.tsv, mutations_loci a SPEC, mutations_rows 0: the default row buffer.  simulate: the prefix of
     PREFIX.simulate.tsv / PREFIX.simulate-genome.tsv, simulate_loci a SPEC, simulate_seed None: the control file's random-seed,
-    simulate_rows 0: the default row buffer, simulate_no_sites: the genealogy level alone"""
+    simulate_rows 0: the default row buffer, simulate_no_sites: the genealogy level alone.  pair_times: the prefix of
+    PREFIX.pair-times.tsv / PREFIX.pair-times-genome.tsv, pair_times_pops the pairs as "A,B;A,A" (None: all), pair_times_grid
+    "LO,HI,B" (None: "1e-6,1e-2,34"), pair_times_loci a SPEC, pair_times_rows 0: the default row buffer"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -332,7 +337,9 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       mutations_prefix=b(mutations), mutations_loci=b(mutations_loci), mutations_rows=mutations_rows,
                       simulate_prefix=b(simulate), simulate_loci=b(simulate_loci),
                       simulate_seed=None if simulate_seed is None else str(simulate_seed).encode(), simulate_rows=simulate_rows,
-                      simulate_no_sites=int(bool(simulate_no_sites)))
+                      simulate_no_sites=int(bool(simulate_no_sites)),
+                      pair_times_prefix=b(pair_times), pair_times_pops=b(pair_times_pops), pair_times_grid=b(pair_times_grid),
+                      pair_times_loci=b(pair_times_loci), pair_times_rows=pair_times_rows)
     return lib.gph_run(C.byref(o))
 
 
@@ -391,6 +398,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_simulate_enable", "gph_engine_simulate_sample", "gph_engine_simulate_shape", "gph_engine_simulate_selected",
     "gph_engine_simulate_fetch_loci", "gph_engine_simulate_fetch_rows", "gph_engine_simulate_fetch_records", "gph_engine_simulate_column_name",
     "gph_simulate_write", "gph_simulate_discard",
+    "gph_engine_pair_times_enable", "gph_engine_pair_times_sample", "gph_engine_pair_times_shape", "gph_engine_pair_times_selected",
+    "gph_engine_pair_times_fetch_loci", "gph_engine_pair_times_fetch_rows", "gph_engine_pair_times_column_name",
+    "gph_pair_times_write", "gph_pair_times_discard",
 ]
 
 
@@ -594,6 +604,18 @@ def _load_library(path):
     lib.gph_engine_triplets_column_name.argtypes = [C.c_void_p, C.c_int32]
     lib.gph_engine_triplets_column_name.restype = C.c_char_p
     lib.gph_triplets_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_engine_pair_times_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.c_int32,
+                                                 C.POINTER(C.c_double), C.c_int32, C.c_int64]
+    lib.gph_engine_pair_times_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_pair_times_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]
+    lib.gph_engine_pair_times_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_pair_times_fetch_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    lib.gph_engine_pair_times_fetch_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_pair_times_column_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_pair_times_column_name.restype = C.c_char_p
+    lib.gph_pair_times_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_pair_times_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_mutations_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_mutations_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_engine_mutations_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int64]
@@ -1634,6 +1656,62 @@ class Sampler:
             raise RuntimeError("gphocs_hip: mutations_rows: not enabled (GPH_ESTATE)")
         _, rows = self._fetch_rows(self.lib.gph_engine_mutations_fetch_rows, held, 1 + Cn)
         return rows[:, 0].astype(np.int32), rows[:, 1:].copy()
+
+    # ---- pairwise coalescence-time distributions of selected loci (gph_engine_pair_times_*): accumulated on the device
+    def pair_times_enable(self, capacity, edges, loci=None, pairs=None, max_bytes=0):
+        """per-locus accumulators A, Y, X, M of every pair slot for the selected loci (as enable_gene_trees; None: all loci of this
+        rank) and a device buffer of `capacity` per-sample rows; capacity 0 switches the feature off.  edges: the E increasing,
+        finite, positive edges of the time grid (B = E + 1 bins).  pairs: None = every pair P <= Q of current populations with a
+        leaf pair, else a list of (P, Q) population indices in any order.  ValueError for a refused selection, pair list or grid
+        (stderr names the cause; the sampler is left as it was), MemoryError when accumulators and rows would exceed max_bytes
+        (0: 1 GiB)"""
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        pr = self._listed(None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2), C.c_int32)
+        ed = self._listed(np.ascontiguousarray(edges, dtype=np.float64).reshape(-1), C.c_double)
+        self._enabled(self.lib.gph_engine_pair_times_enable(self.engine, int(capacity), *sel, *pr, *ed, int(max_bytes)), "pair_times_enable",
+                      "the pair-times accumulators and rows exceed", "the capacity, the selection, the pairs or the grid")
+
+    def pair_times_sample(self, it):
+        """the distributions of every selected locus under the current state, labelled iteration `it`; BufferError when the row
+        buffer is full"""
+        self._sample(self.lib.gph_engine_pair_times_sample, "pair-times row", "pair_times_rows", int(it))
+
+    def _pair_times_shape(self):
+        """(NP, B, G, selected, samples, rows held)"""
+        a, b, g, q, S, held = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
+        self._chk(self.lib.gph_engine_pair_times_shape(self.engine, C.byref(a), C.byref(b), C.byref(g), C.byref(q), C.byref(S), C.byref(held), None),
+                  "pair_times_shape")
+        return a.value, b.value, g.value, q.value, S.value, held.value
+
+    def pair_times_columns(self):
+        NP, B = self._pair_times_shape()[:2]
+        return [self.lib.gph_engine_pair_times_column_name(self.engine, c).decode() for c in range(NP * (B + 2))]
+
+    def pair_times(self, reset=False):
+        """the accumulators of this rank's Q selected loci as the device holds them: a dict of loci[Q] (global indices), pairs
+        (NP, 2) population indices, edges[E] as given, samples, and A, Y, X, M (Q, NP) float64.  reset=True zeroes them afterwards
+        and restarts the sample count"""
+        NP, B, _, Q, S, _ = self._pair_times_shape()
+        if NP == 0:
+            raise RuntimeError("gphocs_hip: pair_times: not enabled (GPH_ESTATE)")
+        loci = self._selected(self.lib.gph_engine_pair_times_selected, Q)
+        edges = np.zeros(B - 1, dtype=np.float64)
+        self._chk(self.lib.gph_engine_pair_times_shape(self.engine, None, None, None, None, None, None, edges.ctypes.data), "pair_times_shape")
+        names = [self.lib.gph_engine_pair_times_column_name(self.engine, NP * B + k).decode() for k in range(NP)]
+        pairs = np.array([[int(x) for x in nm[len("below_"):].split("|")] for nm in names], dtype=np.int32).reshape(NP, 2)
+        acc = np.zeros((max(Q, 1), 4, NP), dtype=np.float64)
+        self._chk(self.lib.gph_engine_pair_times_fetch_loci(self.engine, acc.ctypes.data, 4 * NP, int(bool(reset))), "pair_times_fetch_loci")
+        return dict(loci=loci, pairs=pairs, edges=edges, samples=S, A=acc[:Q, 0].copy(), Y=acc[:Q, 1].copy(), X=acc[:Q, 2].copy(), M=acc[:Q, 3].copy())
+
+    def pair_times_rows(self):
+        """(iterations, rows): the per-sample rows taken since the last call, a uint64 (samples, NP (B + 2)) array over THIS rank's
+        selected loci -- per slot the B histogram totals, then per slot the pairs below the split, then per slot the loci with
+        one --, and their iterations; the device buffer is emptied"""
+        NP, B, _, _, _, held = self._pair_times_shape()
+        if NP == 0:
+            raise RuntimeError("gphocs_hip: pair_times_rows: not enabled (GPH_ESTATE)")
+        its, rows = self._fetch_rows(self.lib.gph_engine_pair_times_fetch_rows, held, NP * (B + 2), np.uint64, with_iters=True)
+        return its.copy(), rows.copy()
 
     # ---- replicate genealogies simulated from the sampled parameters (gph_engine_simulate_*): simulated on the device
     def simulate_enable(self, seed, capacity, loci=None, with_sites=True, max_bytes=0):

@@ -17,6 +17,7 @@
 #include <vector>
 #include <string>
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <set>
 #if defined(GPH_HOSTEMU) && defined(GPH_EMU64)
@@ -34,6 +35,7 @@
 #include "gph_predictive.h"
 #include "gph_simulate.h"
 #include "gph_triplets.h"
+#include "gph_pairtimes.h"
 #include "gph_mutations.h"
 #include "gph_cladecmp.h"
 #include "gph_comm.h"
@@ -451,7 +453,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 26     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets, 24: k_mutations, 25: k_simulate) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 27     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets, 24: k_mutations, 25: k_simulate, 26: k_pair_times) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -586,8 +588,12 @@ struct gph_engine_state {
   // [cap][RC + C] u64 with their iterations
   struct : SmSelected { size_t o_sacc = 0, o_sobs = 0, o_key = 0, o_skey = 0, o_pop = 0, o_rec = 0; GphSiShape shape = {}; GphGtShape gshape = {};
                         GphPdShape pshape = {}; int32_t C = 0; std::vector<int64_t> sites; std::string name; } si;
+  // pairwise coalescence-time distributions of selected loci (gph_pairtimes.h): ONE buffer in selection order -- acc [nsel][4][NP]
+  // doubles (A, Y, X, M of every slot), pair [NP] packed pairs, edges [E] doubles, pop [n + Kc] bytes --, the per-sample rows
+  // [cap][NP (B + 2)] u64 with their iterations, the pairs and edges as the caller sees them
+  struct : SmSelected { size_t o_pair = 0, o_edge = 0, o_pop = 0; GphPtShape shape = {}; std::vector<int32_t> pairs; std::vector<double> edges; std::string name; } pt;
   // the samplers with accumulators over a selection, in the order gph_engine_init_genealogies zeroes them
-  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr, &mu, &si}; }
+  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr, &mu, &si, &pt}; }
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -3586,6 +3592,166 @@ const char *gph_engine_mutations_column_name(gph_engine *e, int32_t col)
   if (col < 2 * K) e->mu.name = std::string(col < K ? "mut." : "exp.") + std::to_string(col % K);
   else e->mu.name = std::string(col - 2 * K < n ? "mutExt." : "expExt.") + std::to_string((col - 2 * K) % n);
   return e->mu.name.c_str();
+}
+
+// ---- pairwise coalescence-time distributions of selected loci (gph_pairtimes.h)
+// the accumulators back to zero, the sample count with them
+static int pair_times_zero(gph_engine *e) { return acc_zero(e, e->pt.d, e->pt.o_pair); }
+static void pair_times_free(gph_engine *e) { selected_free(e->pt); }
+static int pair_times_refuse(const char *fmt, long long a, long long b, long long c, long long d)
+{
+  fprintf(stderr, "gphocs_hip: pair times: ");
+  fprintf(stderr, fmt, a, b, c, d);
+  fputc('\n', stderr);
+  return GPH_EARG;
+}
+// the leaf pairs of slot (P, Q), P <= Q
+static int64_t pair_times_m(const gph_engine *e, int P, int Q)
+{
+  const int64_t a = e->samplesPerPop[P], b = e->samplesPerPop[Q];
+  return P == Q ? a * (a - 1) / 2 : a * b;
+}
+
+int gph_engine_pair_times_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, const int32_t *pairs, int32_t npairs,
+                                 const double *edges, int32_t nedges, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity_rows < 0 || (loci && nloci < 0) || (pairs && npairs < 0)) return GPH_EARG;
+  SETDEV(e);
+  if (capacity_rows == 0) { pair_times_free(e); return 0; }
+  const int n = e->cfg.n, Kc = e->cfg.Kc;
+  /* every refusal before anything is freed or allocated, as the triplet weights do: a refused call leaves the sampler as it was */
+  if (n > 255) return pair_times_refuse("%lld leaves: the byte counts of k_pair_times hold 255 at most", n, 0, 0, 0);
+  if (loci)
+    for (int64_t k = 0; k < nloci; k++) {
+      if (loci[k] < 0 || loci[k] >= e->cfg.L_total) return pair_times_refuse("locus %lld is out of range (0 .. %lld)", loci[k], e->cfg.L_total - 1, 0, 0);
+      if (k > 0 && loci[k] == loci[k - 1]) return pair_times_refuse("locus %lld is named twice", loci[k], 0, 0, 0);
+      if (k > 0 && loci[k] < loci[k - 1]) return pair_times_refuse("locus %lld stands behind locus %lld: the selection is not increasing", loci[k], loci[k - 1], 0, 0);
+    }
+  std::vector<int32_t> pr;
+  if (!pairs) {
+    for (int P = 0; P < Kc; P++)
+      for (int Q = P; Q < Kc; Q++)
+        if (pair_times_m(e, P, Q) >= 1) pr.push_back(gph_pt_pack(P, Q));
+  } else {
+    for (int32_t k = 0; k < npairs; k++) {
+      int m[2] = {pairs[2 * k], pairs[2 * k + 1]};
+      for (int a = 0; a < 2; a++)
+        if (m[a] < 0 || m[a] >= Kc) return pair_times_refuse("pair %lld names population %lld: the current populations are 0 .. %lld", k, m[a], Kc - 1, 0);
+      if (m[0] > m[1]) std::swap(m[0], m[1]);
+      if (m[0] == m[1] && e->samplesPerPop[m[0]] < 2) return pair_times_refuse("pair %lld: population %lld has fewer than two samples", k, m[0], 0, 0);
+      for (int a = 0; a < 2; a++)
+        if (e->samplesPerPop[m[a]] < 1) return pair_times_refuse("pair %lld names population %lld, which has no sample", k, m[a], 0, 0);
+      const int32_t word = gph_pt_pack(m[0], m[1]);
+      for (int32_t q = 0; q < k; q++)
+        if (pr[(size_t)q] == word) return pair_times_refuse("pair %lld (%lld, %lld) is named twice", k, m[0], m[1], 0);
+      pr.push_back(word);
+    }
+  }
+  if (pr.empty()) return pair_times_refuse("no pair of populations with a pair of samples", 0, 0, 0, 0);
+  if (nedges < 1 || nedges > GPH_PT_MAXEDGES || !edges) return pair_times_refuse("%lld edges: a grid has 1 .. %lld", edges ? nedges : 0, GPH_PT_MAXEDGES, 0, 0);
+  for (int32_t k = 0; k < nedges; k++) {
+    if (!std::isfinite(edges[k]) || !(edges[k] > 0.0)) return pair_times_refuse("edge %lld is not a finite positive number", k, 0, 0, 0);
+    if (k > 0 && !(edges[k] > edges[k - 1])) return pair_times_refuse("edge %lld does not lie above edge %lld", k, k - 1, 0, 0);
+  }
+  const int NP = (int)pr.size();
+  GphPtShape h;
+  gph_pt_shape(e->lay, NP, nedges, h);
+  if (h.tr.lds_bytes > 65536) return pair_times_refuse("%lld leaves in %lld current populations need %lld bytes of LDS a workgroup (65536 at most)", n, Kc, h.tr.lds_bytes, 0);
+  pair_times_free(e);
+  int64_t nsel = 0;
+  if (!loci) nsel = e->L;
+  else for (int64_t k = 0; k < nloci; k++) nsel += loci[k] >= e->cfg.locus_begin && loci[k] < e->cfg.locus_begin + e->L;
+  const std::vector<uint8_t> pop = leaf_pops(e, true);
+  const size_t o_pair = (size_t)nsel * 4 * NP * 8, o_edge = (o_pair + (size_t)NP * 4 + 15) & ~(size_t)15,
+               o_pop = (o_edge + (size_t)nedges * 8 + 15) & ~(size_t)15, bytes = o_pop + pop.size();
+  const int64_t need = (int64_t)bytes + (int64_t)capacity_rows * h.W * 8;
+  /* (nothing to free behind this refusal: the sampler is off already) */
+  if (over_limit(need, max_bytes, "pair times: the accumulators and rows", "%lld loci x %d pairs x 32 + %d rows x %d x 8 + %lld",
+                 (long long)nsel, NP, (int)capacity_rows, (int)h.W, (long long)(bytes - o_pair))) return GPH_EFULL;
+  { int rcs = sel_alloc(e, e->pt.sel, loci, nloci); if (rcs) return rcs; }
+  if (dev_alloc((void **)&e->pt.d, bytes)) { dev_clear_error(); e->pt.d = nullptr; pair_times_free(e); return GPH_EHIP; }
+  if (rows_alloc(e->pt.rows, sizeof(uint64_t), h.W, capacity_rows)) { dev_clear_error(); pair_times_free(e); return GPH_EHIP; }
+  int rc = h2d(e, e->pt.d + o_pair, pr.data(), (size_t)NP * 4);
+  if (!rc) rc = h2d(e, e->pt.d + o_edge, edges, (size_t)nedges * 8);
+  if (!rc) rc = h2d(e, e->pt.d + o_pop, pop.data(), pop.size());
+  if (rc) { pair_times_free(e); return rc; }
+  e->pt.shape = h;
+  e->pt.pairs = pr;
+  e->pt.edges.assign(edges, edges + nedges);
+  e->pt.o_pair = o_pair; e->pt.o_edge = o_edge; e->pt.o_pop = o_pop; e->pt.bytes = bytes;
+  return selected_on(e, e->pt, pair_times_zero);
+}
+
+// one sample of the current state, queued on the engine's stream.  The settle level is that of the time slices: the population
+// ages and fathers are read from the chain state
+int gph_engine_pair_times_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->pt.on) return GPH_ESTATE;
+  const GphPtShape &h = e->pt.shape;
+  const int nsel = (int)e->pt.sel.loci.size(), groups = (nsel + h.tr.G - 1) / h.tr.G;
+  /* (a rank without a selected locus launches nothing: its row stays 0) */
+  return sample_run(e, SETTLE_CHAIN, 26, groups > 0, SmTaken{&e->pt.rows, true, &e->pt.iters, iteration, &e->pt.samples}, [&](void *row) {
+    launch_pre(e);
+    return launch_grid(e, GphGrid{groups, 1}, h.tr.bd, (size_t)h.tr.lds_bytes, k_pair_times, e->ka, h, (const char *)e->dev.pages, (const int32_t *)e->pt.sel.d_slot,
+                       (const int32_t *)(e->pt.d + e->pt.o_pair), (const uint8_t *)(e->pt.d + e->pt.o_pop), (const double *)(e->pt.d + e->pt.o_edge), nsel,
+                       (int)e->L, (double *)e->pt.d, (uint64_t *)row);
+  });
+}
+
+// pairs: NP; bins: B; group: the loci a workgroup takes; edges_out [B - 1] (may be null): the grid as given
+int gph_engine_pair_times_shape(gph_engine *e, int32_t *pairs, int32_t *bins, int32_t *group, int64_t *selected, int64_t *samples, int32_t *rows_held, double *edges_out)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->pt.on;
+  if (pairs) *pairs = on ? e->pt.shape.NP : 0;
+  if (bins) *bins = on ? e->pt.shape.B : 0;
+  if (group) *group = on ? e->pt.shape.tr.G : 0;
+  if (selected) *selected = on ? (int64_t)e->pt.sel.loci.size() : 0;
+  if (samples) *samples = on ? e->pt.samples : 0;
+  if (rows_held) *rows_held = on ? e->pt.rows.fill : 0;
+  if (edges_out && on) for (size_t k = 0; k < e->pt.edges.size(); k++) edges_out[k] = e->pt.edges[k];
+  return 0;
+}
+
+int gph_engine_pair_times_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->pt : nullptr, out, max_loci, count); }
+
+// out [selected][ld], ld >= 4 NP: A of every slot, then Y, X, M
+int gph_engine_pair_times_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset)
+{
+  if (!e) return GPH_EARG;
+  if (!e->pt.on) return GPH_ESTATE;
+  const size_t nsel = e->pt.sel.loci.size(), w = 4 * (size_t)e->pt.shape.NP;
+  if ((nsel > 0 && !out) || ld < (int64_t)w) return GPH_EARG;
+  SETDEV(e);
+  if (nsel > 0) {
+    std::vector<double> acc(nsel * w);
+    { int rc = pull_rows(e, acc.data(), e->pt.d, e->pt.o_pair); if (rc) return rc; }
+    for (size_t q = 0; q < nsel; q++) memcpy(out + q * (size_t)ld, acc.data() + q * w, w * 8);
+  }
+  return reset ? selected_zero(e, e->pt) : 0;
+}
+
+// the rows taken since the last fetch (iters[rows], out[rows][ld], ld >= NP (B + 2)); the row buffer is empty again
+int gph_engine_pair_times_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *out, int64_t ld, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || ((!out || !iters) && max_rows > 0)) return GPH_EARG;
+  if (!e->pt.on) return GPH_ESTATE;
+  SmRows &b = e->pt.rows;
+  if (max_rows < b.fill || (b.fill > 0 && ld < b.n)) return GPH_EARG;
+  return rows_iters_fetch(e, b, e->pt.iters, iters, out, ld, true, rows);
+}
+
+// "<P>|<Q>:<k>" per slot and bin, then "below_<P>|<Q>" per slot, then "loci_<P>|<Q>" per slot, with the indices of the current populations
+const char *gph_engine_pair_times_column_name(gph_engine *e, int32_t col)
+{
+  if (!e || !e->pt.on || col < 0 || col >= e->pt.shape.W) return nullptr;
+  const int NP = e->pt.shape.NP, B = e->pt.shape.B;
+  const int sl = col < NP * B ? col / B : (col - NP * B) % NP;
+  const uint32_t word = (uint32_t)e->pt.pairs[(size_t)sl];
+  const std::string pq = std::to_string((int)(word & 255u)) + "|" + std::to_string((int)((word >> 8) & 255u));
+  e->pt.name = col < NP * B ? pq + ":" + std::to_string(col % B) : (col < NP * B + NP ? "below_" : "loci_") + pq;
+  return e->pt.name.c_str();
 }
 
 // ---- replicate genealogies of selected loci, simulated from the sampled parameters (gph_simulate.h)

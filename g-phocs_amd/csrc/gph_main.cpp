@@ -41,6 +41,11 @@
 // unless --simulate-no-sites, a replicate alignment on it; the sampled genealogies' statistics against the replicates' and the
 // data's against the replicate alignments' go to PREFIX.simulate.tsv, the genome-wide totals per sample to
 // PREFIX.simulate-genome.tsv (--simulate-seed N, default the control file's random-seed; --simulate-rows N).
+// --pair-times PREFIX writes the distribution of the coalescence time between the lineages of two current populations on an
+// absolute time axis: per selected locus (--pair-times-loci SPEC, default all) and pair (--pair-times-pops "A,B;A,A", default all
+// pairs) the mean and the youngest age and how often a coalescence lies below the populations' split to PREFIX.pair-times.tsv, and
+// per sample the genome-wide histograms over the grid (--pair-times-grid LO,HI,B, default 1e-6,1e-2,34: B bins, geometric edges)
+// with their cumulative curves to PREFIX.pair-times-genome.tsv (--pair-times-rows N: rows of the device buffer).
 // --beta B runs the whole chain on the power posterior p(D|G)^B p(G|Theta) p(Theta), B in [0, 64], 0 = the prior;
 // --marginal-likelihood PREFIX runs, behind the unchanged run, the ladder beta_k = (k/K)^(1/a) from 1 down to 0 (--ml-steps K,
 // default 32; --ml-alpha a, default 0.3; per rung --ml-burnin b discarded iterations, default the control file's burn-in or
@@ -132,7 +137,7 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--ess ess-prefix [--ess-loci SPEC]] [--predictive pp-prefix [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]] [--triplets tw-prefix [--triplets-pops \"A,B,C;D,E,F\"] [--triplets-loci SPEC] [--triplets-rows N]] [--mutations mutations-prefix [--mutations-loci SPEC] [--mutations-rows N]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] [--replicates R --replicates-out rep-prefix [--replicates-min-freq F] [--replicates-every k]] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--ess ess-prefix [--ess-loci SPEC]] [--predictive pp-prefix [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]] [--triplets tw-prefix [--triplets-pops \"A,B,C;D,E,F\"] [--triplets-loci SPEC] [--triplets-rows N]] [--mutations mutations-prefix [--mutations-loci SPEC] [--mutations-rows N]] [--pair-times pt-prefix [--pair-times-pops \"A,B;A,A\"] [--pair-times-grid LO,HI,B] [--pair-times-loci SPEC] [--pair-times-rows N]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] [--replicates R --replicates-out rep-prefix [--replicates-min-freq F] [--replicates-every k]] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
@@ -172,6 +177,11 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--simulate-seed") && i + 1 < argc) o.simulate_seed = argv[++i];
     else if (!strcmp(argv[i], "--simulate-rows") && i + 1 < argc) { o.simulate_rows = atoi(argv[++i]); if (o.simulate_rows < 1) return usage(argv[0]); }
     else if (!strcmp(argv[i], "--simulate-no-sites")) o.simulate_no_sites = 1;
+    else if (!strcmp(argv[i], "--pair-times") && i + 1 < argc) o.pair_times_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--pair-times-pops") && i + 1 < argc) o.pair_times_pops = argv[++i];
+    else if (!strcmp(argv[i], "--pair-times-grid") && i + 1 < argc) o.pair_times_grid = argv[++i];
+    else if (!strcmp(argv[i], "--pair-times-loci") && i + 1 < argc) o.pair_times_loci = argv[++i];
+    else if (!strcmp(argv[i], "--pair-times-rows") && i + 1 < argc) { o.pair_times_rows = atoi(argv[++i]); if (o.pair_times_rows < 1) return usage(argv[0]); }
     else if (!strcmp(argv[i], "--clades") && i + 1 < argc) o.clades_prefix = argv[++i];
     else if (!strcmp(argv[i], "--clades-loci") && i + 1 < argc) o.clades_loci = argv[++i];
     else if (!strcmp(argv[i], "--clades-slots") && i + 1 < argc) {
@@ -260,6 +270,10 @@ int main(int argc, char **argv)
   }
   if ((o.simulate_loci || o.simulate_seed || o.simulate_rows || o.simulate_no_sites) && !o.simulate_prefix) {
     fprintf(stderr, "%s: --simulate-loci, --simulate-seed, --simulate-rows and --simulate-no-sites need --simulate PREFIX\n", argv[0]);
+    return usage(argv[0]);
+  }
+  if ((o.pair_times_pops || o.pair_times_grid || o.pair_times_loci || o.pair_times_rows) && !o.pair_times_prefix) {
+    fprintf(stderr, "%s: --pair-times-pops, --pair-times-grid, --pair-times-loci and --pair-times-rows need --pair-times PREFIX\n", argv[0]);
     return usage(argv[0]);
   }
   if ((o.marginal_steps || o.marginal_burnin || o.marginal_samples || o.marginal_alpha != 0.0) && !o.marginal_prefix) {
@@ -389,7 +403,7 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(o.locus_summary_path); bad = 1; }
     if (bad && out) unlink(o.locus_summary_path);
   }
-  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.ess_prefix || o.predictive_prefix || o.triplets_prefix || o.mutations_prefix || o.simulate_prefix || o.marginal_prefix || o.mc3_report_prefix || o.replicates_prefix) {
+  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.ess_prefix || o.predictive_prefix || o.triplets_prefix || o.mutations_prefix || o.simulate_prefix || o.pair_times_prefix || o.marginal_prefix || o.mc3_report_prefix || o.replicates_prefix) {
     /* the ranks' parts into the files, by the library that wrote them -- or, after a failure, removed */
     if (sym<decltype(&gph_run_finish)>(load_engine(dir, o.ctl, o.ctl2), "gph_run_finish")(&o, gpus, bad)) bad = 1;
   }

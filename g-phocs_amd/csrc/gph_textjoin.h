@@ -1,8 +1,8 @@
-// gph_textjoin.h -- the six outputs that travel through text parts (gph_textparts.h): what each format's lines mean
+// gph_textjoin.h -- the seven outputs that travel through text parts (gph_textparts.h): what each format's lines mean
 // once the last rank is done (gph_run_finish), and nothing else: its header line, which tag goes to which file, its summary
 // and its line on stdout.  The parts' writers are the outputs of a run (gph_program.cpp, gph_*_run.h).
 //
-// This header DEFINES the twelve gph_<name>_write / _discard entry points: one translation unit of a program includes it
+// This header DEFINES the fourteen gph_<name>_write / _discard entry points: one translation unit of a program includes it
 // (gph_program.cpp in the library; a stand-alone program that wants the joiners without the engine includes it itself).
 #ifndef GPH_TEXTJOIN_H
 #define GPH_TEXTJOIN_H
@@ -424,8 +424,122 @@ struct SiJoin : TextJoin {
     fflush(stdout);
   }
 };
+// pair times: "H\t<samples>\t<pairs>\t<bins>" + "\t<P>,<Q>,<m>" (names, leaf pairs) per pair + "\t<u64>" per edge (the double's
+// 64-bit pattern); a rank's rows of PREFIX.pair-times.tsv as "L\t" + row, its per-sample rows as R lines of NP (B + 2) numbers;
+// the L rows are concatenated in rank order, the R lines added number by number
+struct PtJoin : TextJoin {
+  long long S = -1, NP = -1, B = -1, rowsL = 0;
+  std::vector<std::string> names;                       /* [NP][2] */
+  std::vector<long long> m;                             /* [NP] leaf pairs */
+  std::vector<double> edges;                            /* [B - 1] */
+  TextRows rows;                                        /* [sample][NP (B + 2)] */
+  PtJoin() : TextJoin(true) {}
+  std::string label(long long k) const { return names[(size_t)(2 * k)] + "|" + names[(size_t)(2 * k + 1)]; }
+  bool header(char *line, ssize_t len, int) override
+  {
+    long long s = 0, np = 0, b = 0;
+    int used = 0;
+    if (!(sscanf(line, "H\t%lld\t%lld\t%lld%n", &s, &np, &b, &used) == 3 && (S < 0 || (s == S && np == NP && b == B)) && np >= 1 && b >= 2 && b <= 128 && s >= 0 &&
+          line[len - 1] == '\n')) return false;
+    const std::vector<std::string> f = tab_fields(line + used, (size_t)len - used - 1);
+    if ((long long)f.size() != np + b - 1) return false;
+    std::vector<std::string> nm;
+    std::vector<long long> lp;
+    std::vector<double> ed;
+    for (long long k = 0; k < np; k++) {
+      const std::string &three = f[(size_t)k];
+      const size_t c1 = three.find(','), c2 = c1 == std::string::npos ? c1 : three.find(',', c1 + 1);
+      if (c2 == std::string::npos) return false;
+      nm.push_back(three.substr(0, c1)); nm.push_back(three.substr(c1 + 1, c2 - c1 - 1));
+      lp.push_back(atoll(three.c_str() + c2 + 1));
+      if (lp.back() < 1) return false;
+    }
+    for (long long k = 0; k < b - 1; k++) {
+      char *end = nullptr;
+      const unsigned long long bits = strtoull(f[(size_t)(np + k)].c_str(), &end, 10);
+      if (!end || *end != '\0' || end == f[(size_t)(np + k)].c_str()) return false;
+      double v;
+      memcpy(&v, &bits, 8);
+      ed.push_back(v);
+    }
+    if (S >= 0) return nm == names && lp == m && ed.size() == edges.size() && memcmp(ed.data(), edges.data(), ed.size() * 8) == 0;
+    S = s; NP = np; B = b; names = nm; m = lp; edges = ed;
+    rows.shape(S, NP * (B + 2));
+    fprintf(out[0], "locus\tname\tsamples\tP\tQ\tpairs\tmeanAge\tminAge\tpBelow\tfBelow\n");
+    return true;
+  }
+  bool body(char *line, ssize_t, int r) override
+  {
+    if (line[1] != '\t') return false;
+    if (line[0] == 'R') return rows.row(line, r);
+    if (line[0] != 'L') return false;
+    fputs(line + 2, out[0]);
+    rowsL++;
+    return true;
+  }
+  bool rank_done() override { return rows.rank_done(); }
+  /* mean and sample sd (divisor S - 1; 0 for S = 1) of v, sums in sample order from 0.0 */
+  static void mean_sd(const std::vector<double> &v, double &mean, double &sd)
+  {
+    const size_t n = v.size();
+    double sum = 0.0, ss = 0.0;
+    for (double x : v) sum = sum + x;
+    mean = n > 0 ? sum / (double)n : 0.0;
+    for (double x : v) ss = ss + (x - mean) * (x - mean);
+    sd = n > 1 ? sqrt(ss / (double)(n - 1)) : 0.0;
+  }
+  void summary() override
+  {
+    const std::vector<unsigned long long> &t = rows.totals;
+    const long long W = NP * (B + 2), Q = NP > 0 ? rowsL / NP : 0;
+    fprintf(out[0], "# loci %lld samples %lld pairs %lld bins %lld\n", Q, S, NP, B);
+    fprintf(out[1], "iter");
+    for (long long k = 0; k < NP; k++)
+      for (long long b = 0; b < B; b++) fprintf(out[1], "\t%s:%lld", label(k).c_str(), b);
+    for (long long k = 0; k < NP; k++) fprintf(out[1], "\tbelow_%s", label(k).c_str());
+    for (long long k = 0; k < NP; k++) fprintf(out[1], "\tloci_%s", label(k).c_str());
+    fputc('\n', out[1]);
+    rows.print(out[1]);
+    fprintf(out[1], "# edges");
+    for (double e : edges) fprintf(out[1], " %.17g", e);
+    fputc('\n', out[1]);
+    std::string most = "none";
+    double most_b = -1.0;
+    std::vector<double> v((size_t)S);
+    char num[256];
+    for (long long k = 0; k < NP; k++) {
+      const double all = (double)Q * (double)m[(size_t)k];
+      std::string cdf = "# cdf " + label(k), sds = "# sd " + label(k);
+      for (long long b = 0; b < B; b++) {
+        for (long long s = 0; s < S; s++) {
+          unsigned long long cum = 0;
+          for (long long j = 0; j <= b; j++) cum += t[(size_t)(s * W + k * B + j)];
+          v[(size_t)s] = all > 0.0 ? (double)cum / all : 0.0;
+        }
+        double mean, sd;
+        mean_sd(v, mean, sd);
+        snprintf(num, sizeof num, " %.10g", mean); cdf += num;
+        snprintf(num, sizeof num, " %.10g", sd); sds += num;
+      }
+      fprintf(out[1], "%s\n%s\n", cdf.c_str(), sds.c_str());
+      double bm, bs, lm, ls;
+      for (long long s = 0; s < S; s++) v[(size_t)s] = all > 0.0 ? (double)t[(size_t)(s * W + NP * B + k)] / all : 0.0;
+      mean_sd(v, bm, bs);
+      for (long long s = 0; s < S; s++) v[(size_t)s] = Q > 0 ? (double)t[(size_t)(s * W + NP * B + NP + k)] / (double)Q : 0.0;
+      mean_sd(v, lm, ls);
+      snprintf(num, sizeof num, " mean %.10g sd %.10g loci %.10g", bm, bs, lm);
+      const std::string text = label(k) + num;
+      fprintf(out[1], "# below %s\n", text.c_str());
+      if (names[(size_t)(2 * k)] != names[(size_t)(2 * k + 1)] && bm > most_b) { most_b = bm; most = text; }
+    }
+    printf("PairTimes: %s\n", most.c_str());
+    fflush(stdout);
+  }
+};
 }   // namespace
 
+extern "C" int gph_pair_times_write(const char *prefix, int32_t ranks) { PtJoin J; return text_join(PT_TEXT, J, prefix, ranks); }
+extern "C" int gph_pair_times_discard(const char *prefix, int32_t ranks) { return text_discard(PT_TEXT, prefix, ranks); }
 extern "C" int gph_simulate_write(const char *prefix, int32_t ranks) { SiJoin J; return text_join(SI_TEXT, J, prefix, ranks); }
 extern "C" int gph_simulate_discard(const char *prefix, int32_t ranks) { return text_discard(SI_TEXT, prefix, ranks); }
 extern "C" int gph_clades_write(const char *prefix, int32_t ranks) { ClJoin J; return text_join(CL_TEXT, J, prefix, ranks); }

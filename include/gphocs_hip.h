@@ -247,7 +247,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * tables of replicate chains compared (gph_engine_clades_compare: k_clades_compare, counted on engines[0]), 21 effective
  * sample sizes per locus (gph_engine_ess_sample: k_ess), 22 posterior predictive checks (gph_engine_predictive_sample:
  * k_predictive), 23 triplet topology weights (gph_engine_triplets_sample: k_triplets), 24 expected substitutions
- * (gph_engine_mutations_sample: k_mutations + k_rows_fold together) */
+ * (gph_engine_mutations_sample: k_mutations + k_rows_fold together), 25 replicate genealogies (gph_engine_simulate_sample),
+ * 26 pairwise coalescence-time distributions (gph_engine_pair_times_sample: k_pair_times) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -780,6 +781,64 @@ int gph_engine_simulate_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *rows
 int gph_engine_simulate_fetch_records(gph_engine *e, void *out /* [selected][record bytes] */, int32_t *offsets);
 const char *gph_engine_simulate_column_name(gph_engine *e, int32_t which, int32_t col);
 
+/* PAIRWISE COALESCENCE-TIME DISTRIBUTIONS per population pair, of selected loci and genome-wide per sample (k_pair_times:
+ * csrc/gph_pairtimes.h; timing class 26): the distribution of the coalescence time of a lineage from population P and a lineage
+ * from population Q on an ABSOLUTE time axis -- the curve set next to an MSMC or Relate cross-coalescence curve: it shows when two
+ * populations stopped exchanging lineages, whether the model has a band for it or not.  In a model without gene flow a P-Q
+ * coalescence cannot be younger than the split of P and Q, so "the youngest P-Q coalescence of this locus lies below the split"
+ * is a statement about the locus that needs no band index.
+ *   populations  the Kc CURRENT populations in model order; n_p = the leaves of p
+ *   pairs        (P, Q), P <= Q, with m_PQ >= 1 leaf pairs: m_PQ = n_P n_Q for P < Q, m_PP = n_P (n_P - 1) / 2; default all such
+ *                pairs in lexicographic order; pair number k is SLOT k, NP their number
+ *   grid         E = B - 1 EDGES e_0 < e_1 < ... < e_{E-1}, finite positive doubles in the genealogy's own units (as tmrca),
+ *                1 <= E <= 127; bin(a) = the number of edges e <= a: an age equal to an edge lies in the upper bin; bin 0 is
+ *                [0, e_0), bin B - 1 is [e_{E-1}, inf).  The engine takes the edges as given
+ *   per node     one locus at one sample, v an internal node with children l, r, c_x[p] = the leaves of p under x:
+ *                    w_v(P, Q) = c_l[P] c_r[Q] + c_r[P] c_l[Q]   (P < Q),      w_v(P, P) = c_l[P] c_r[P]
+ *                = the leaf pairs of the slot whose lca is v; an integer <= 200^2, never enumerated
+ *   split        from popAge and popFather of the chain state at the sample: P < Q the age of the youngest population that is an
+ *                ancestor of both; P = Q the age of P's father population, +inf when P has none
+ *   per sample   of a slot, all sums over the internal nodes in NODE-INDEX order, terms with w_v = 0 skipped, plain uncontracted
+ *                fp64 (a multiply, then an add):
+ *                    hist[k] = sum_{bin(age[v]) = k} w_v        a = sum age[v] (double)w_v        y = sum_{age[v] < split} w_v
+ *                    x = [y > 0]                                tmin = the smallest age[v] with w_v > 0
+ *   invariants   sum_k hist[k] = m_PQ and y <= m_PQ at every sample
+ *   accumulators per (selected locus, slot) four doubles: A += a, Y += y, X += x, M += tmin, one plain fp64 add a sample in sample
+ *                order; layout [locus][A | Y | X | M][slot]: 32 NP bytes a locus.  There are no per-locus histograms
+ *   rows         per sample the iteration and NP (B + 2) uint64 over the rank's selected loci: per slot the B hist totals, then per
+ *                slot the y total, then per slot the number of loci with x = 1 (integer atomics: order-free; the rows of the ranks add)
+ *   input        the settled node records a gene-tree record holds at that point of the chain, and the chain state's popAge
+ *   _enable      capacity_rows per-sample rows; 0 frees everything, the feature is off.  loci as gph_engine_triplets_enable.  pairs:
+ *                NULL = all, else npairs x 2 population indices in any order; the members are sorted, the pairs keep the caller's
+ *                order.  edges [nedges].  GPH_EARG with a message that names the cause, nothing freed or allocated: a locus index
+ *                out of range, named twice or out of order; a pair that names an index outside 0 .. Kc - 1, is named twice (after
+ *                sorting) or has no leaf pair ("population p has fewer than two samples" for P = Q); nedges outside 1 .. 127; an
+ *                edge that is non-finite, <= 0 or not above its predecessor, by index; more than 255 leaves; more than 64 KB of
+ *                LDS at one locus a workgroup.  GPH_EFULL, with the size in the message and the feature off, when accumulators and
+ *                rows exceed max_bytes (<= 0: 1 GiB).  GPH_ESTATE before the loci are loaded.  Enabling again frees and starts
+ *                over.  gph_engine_init_genealogies zeroes the accumulators, the sample count and the rows held
+ *   _sample      one kernel on the engine's stream, no host synchronisation; a rank without a selected locus launches nothing and
+ *                still takes the (zero) row.  GPH_EFULL when the row buffer is full; GPH_ESTATE when off or before
+ *                gph_engine_init_genealogies
+ *   _shape       NP, B, the loci a workgroup takes, selected loci of the rank, samples since the accumulators were zeroed, rows
+ *                held (all 0 while off); edges_out [B - 1] (may be NULL): the grid as given
+ *   _fetch_loci  out[selected][ld], ld >= 4 NP: A of the NP slots, then Y, X, M; one copy and one host synchronisation; reset != 0
+ *                zeroes the accumulators and the sample count afterwards
+ *   _fetch_rows  the rows taken since the last call (iters[rows], out[rows][ld], ld >= NP (B + 2)); the row buffer is empty again
+ *   _column_name column col of a row: "<P>|<Q>:<k>" per slot and bin, then "below_<P>|<Q>" per slot, then "loci_<P>|<Q>" per slot,
+ *                with the indices of the current populations
+ * The kernel writes no page, draws no random number and touches no chain state; there are no fp atomics.  Not built: coalescence
+ * rates / hazard estimates and a relative cross-coalescence ratio, per-locus histograms, pairs of ancestral populations. */
+int gph_engine_pair_times_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, const int32_t *pairs /* [npairs][2] */,
+                                 int32_t npairs, const double *edges, int32_t nedges, int64_t max_bytes);
+int gph_engine_pair_times_sample(gph_engine *e, int32_t iteration);
+int gph_engine_pair_times_shape(gph_engine *e, int32_t *pairs, int32_t *bins, int32_t *group, int64_t *selected, int64_t *samples, int32_t *rows_held,
+                                double *edges_out);
+int gph_engine_pair_times_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_pair_times_fetch_loci(gph_engine *e, double *out /* [selected][ld] */, int64_t ld, int32_t reset);
+int gph_engine_pair_times_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *out /* [rows][ld] */, int64_t ld, int32_t max_rows, int32_t *rows);
+const char *gph_engine_pair_times_column_name(gph_engine *e, int32_t col);
+
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
  * engine: general-slot RNG, priors, accept decisions of the global proposals
@@ -1236,6 +1295,37 @@ typedef struct gph_run_options {
    * per heated or replicate chain, models other than the run's own. */
   const char *simulate_prefix, *simulate_loci, *simulate_seed;
   int32_t simulate_rows, simulate_no_sites;
+  /* `--pair-times PREFIX [--pair-times-pops "A,B;A,A"] [--pair-times-grid LO,HI,B] [--pair-times-loci SPEC] [--pair-times-rows N]`:
+   * pairwise coalescence-time distributions (gph_engine_pair_times_* above).  A sample is taken wherever a trace line is written.
+   * pair_times_pops: the pairs as names of current populations of the control file, two a pair, pairs separated by ';' (NULL: all
+   * pairs with a leaf pair); pair_times_grid "LO,HI,B": B bins with E = B - 1 edges e_k = LO (HI / LO)^(k / (E - 1)), computed on
+   * the host as LO * pow(HI / LO, (double)k / (double)(E - 1)), e_0 = LO and e_{E-1} = HI exactly (NULL: "1e-6,1e-2,34");
+   * pair_times_loci as gene_trees_loci; pair_times_rows: the rows of the device buffer (0: a default).  Any of the four without
+   * pair_times_prefix and negative rows are GPH_EARG with a message, before anything is read; LO <= 0, HI <= LO, B outside 3 .. 128,
+   * an unknown population name, a pair named twice and a pair without a leaf pair are GPH_EARG with a message that names the
+   * option, once the control file is read and before the sequence file is.  Rank r writes its part PREFIX.pair-times.part<r>
+   * once, at the end; its H line carries every edge as used as its 64-bit pattern.  gph_pair_times_write makes of the parts
+   * (numbers "%.10g")
+   *   PREFIX.pair-times.tsv         header locus name samples P Q pairs meanAge minAge pBelow fBelow; one row per (selected locus,
+   *                                 pair) in sequence-file order, then slot order (the ranks' rows concatenated); P Q the
+   *                                 populations' names, pairs = m_PQ, meanAge = A / (S m), minAge = M / S, pBelow = X / S,
+   *                                 fBelow = Y / (S m); a last line "# loci Q samples S pairs NP bins B"
+   *   PREFIX.pair-times-genome.tsv  header iter, then "<P>|<Q>:<k>" per slot and bin, then "below_<P>|<Q>" per slot, then
+   *                                 "loci_<P>|<Q>" per slot (names); one row of integers per sample, "%7d" and "\t%llu" (the
+   *                                 ranks' rows added); then "# edges" and the E edges as "%.17g"; then per slot, with
+   *                                 F_s[k] = sum_{j <= k} hist_s[j] / (Q m) the sample's cumulative share (integer partial sums, one
+   *                                 division) and b_s = below_s / (Q m):
+   *                                     # cdf <P>|<Q> v_0 ... v_{B-1}        the means of F_s[k] over the samples
+   *                                     # sd <P>|<Q> v_0 ... v_{B-1}         their sample sd (divisor S - 1; 0 for S = 1)
+   *                                     # below <P>|<Q> mean <v> sd <v> loci <v>     mean and sd of b_s, mean of loci_s / Q
+   *                                 sums in sample order from 0.0, mean = sum / S, sd = sqrt(sum (v - mean)^2 / (S - 1))
+   * and prints "PairTimes: " and the "# below" values of the P < Q pair with the largest mean b (the first of equal ones; "none"
+   * without a P < Q pair) on stdout.  Both files are written once, on success only; a failed run leaves neither parts nor files.
+   * With mc3_chains, replicates and marginal_prefix they describe chain 0 and the run proper; every other output is the same bytes
+   * with and without.  Not built: coalescence rates / hazard estimates and a relative cross-coalescence ratio, per-locus
+   * histograms, pairs of ancestral populations, the output per heated or replicate chain, a control-file keyword. */
+  const char *pair_times_prefix, *pair_times_pops, *pair_times_grid, *pair_times_loci;
+  int32_t pair_times_rows;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
@@ -1265,6 +1355,8 @@ int gph_mutations_write(const char *prefix, int32_t ranks);
 int gph_mutations_discard(const char *prefix, int32_t ranks);
 int gph_simulate_write(const char *prefix, int32_t ranks);
 int gph_simulate_discard(const char *prefix, int32_t ranks);
+int gph_pair_times_write(const char *prefix, int32_t ranks);
+int gph_pair_times_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
  * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
  * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
