@@ -285,7 +285,8 @@ class GphRunOptions(C.Structure):   # gph_run_options: what each field switches 
                 ("simulate_prefix", C.c_char_p), ("simulate_loci", C.c_char_p), ("simulate_seed", C.c_char_p), ("simulate_rows", C.c_int32),
                 ("simulate_no_sites", C.c_int32),
                 ("pair_times_prefix", C.c_char_p), ("pair_times_pops", C.c_char_p), ("pair_times_grid", C.c_char_p), ("pair_times_loci", C.c_char_p),
-                ("pair_times_rows", C.c_int32)]
+                ("pair_times_rows", C.c_int32),
+                ("sfs_prefix", C.c_char_p), ("sfs_pairs", C.c_char_p), ("sfs_loci", C.c_char_p), ("sfs_rows", C.c_int32)]
 
 
 def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_summary=None, coal_stats=None, coal_stats_rows=0, time_slices=0,
@@ -298,7 +299,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                      triplets=None, triplets_pops=None, triplets_loci=None, triplets_rows=0,
                      mutations=None, mutations_loci=None, mutations_rows=0,
                      simulate=None, simulate_loci=None, simulate_seed=None, simulate_rows=0, simulate_no_sites=False,
-                     pair_times=None, pair_times_pops=None, pair_times_grid=None, pair_times_loci=None, pair_times_rows=0):
+                     pair_times=None, pair_times_pops=None, pair_times_grid=None, pair_times_loci=None, pair_times_rows=0,
+                     sfs=None, sfs_pairs=None, sfs_loci=None, sfs_rows=0):
     """gph_run: the program of the control file with the outputs that are named (paths and prefixes as str or bytes); the status.
     beta: the whole chain on the power posterior (None: the posterior, 0: the prior); marginal: the prefix of the
     marginal-likelihood ladder behind the run, marginal_steps / _samples / _alpha 0 and marginal_burnin None: the defaults.
@@ -314,7 +316,9 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
     PREFIX.simulate.tsv / PREFIX.simulate-genome.tsv, simulate_loci a SPEC, simulate_seed None: the control file's random-seed,
     simulate_rows 0: the default row buffer, simulate_no_sites: the genealogy level alone.  pair_times: the prefix of
     PREFIX.pair-times.tsv / PREFIX.pair-times-genome.tsv, pair_times_pops the pairs as "A,B;A,A" (None: all), pair_times_grid
-    "LO,HI,B" (None: "1e-6,1e-2,34"), pair_times_loci a SPEC, pair_times_rows 0: the default row buffer"""
+    "LO,HI,B" (None: "1e-6,1e-2,34"), pair_times_loci a SPEC, pair_times_rows 0: the default row buffer.  sfs: the prefix of
+    PREFIX.sfs.tsv / PREFIX.sfs-genome.tsv, sfs_pairs the pairs as "A,B;C,D" or "none" (None: all), sfs_loci a SPEC, sfs_rows 0: the
+    default row buffer"""
     def b(x):
         return os.fsencode(x) if x is not None else None
     o = GphRunOptions(size=C.sizeof(GphRunOptions), ctl=b(ctl), ctl2=b(ctl2), device=device, verbose=verbose, comm=comm,
@@ -339,7 +343,8 @@ def run_control_file(lib, ctl, ctl2=None, device=0, verbose=0, comm=None, locus_
                       simulate_seed=None if simulate_seed is None else str(simulate_seed).encode(), simulate_rows=simulate_rows,
                       simulate_no_sites=int(bool(simulate_no_sites)),
                       pair_times_prefix=b(pair_times), pair_times_pops=b(pair_times_pops), pair_times_grid=b(pair_times_grid),
-                      pair_times_loci=b(pair_times_loci), pair_times_rows=pair_times_rows)
+                      pair_times_loci=b(pair_times_loci), pair_times_rows=pair_times_rows,
+                      sfs_prefix=b(sfs), sfs_pairs=b(sfs_pairs), sfs_loci=b(sfs_loci), sfs_rows=sfs_rows)
     return lib.gph_run(C.byref(o))
 
 
@@ -401,6 +406,9 @@ EXPORTS = [  # every symbol include/gphocs_hip.h declares
     "gph_engine_pair_times_enable", "gph_engine_pair_times_sample", "gph_engine_pair_times_shape", "gph_engine_pair_times_selected",
     "gph_engine_pair_times_fetch_loci", "gph_engine_pair_times_fetch_rows", "gph_engine_pair_times_column_name",
     "gph_pair_times_write", "gph_pair_times_discard",
+    "gph_engine_sfs_enable", "gph_engine_sfs_sample", "gph_engine_sfs_shape", "gph_engine_sfs_selected", "gph_engine_sfs_slots",
+    "gph_engine_sfs_fetch_loci", "gph_engine_sfs_fetch_observed", "gph_engine_sfs_fetch_rows", "gph_engine_sfs_column_name",
+    "gph_sfs_write", "gph_sfs_discard",
 ]
 
 
@@ -616,6 +624,19 @@ def _load_library(path):
     lib.gph_engine_pair_times_column_name.restype = C.c_char_p
     lib.gph_pair_times_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_pair_times_discard.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_engine_sfs_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int64]
+    lib.gph_engine_sfs_sample.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_sfs_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.gph_engine_sfs_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+    lib.gph_engine_sfs_slots.argtypes = [C.c_void_p, C.c_void_p]
+    lib.gph_engine_sfs_fetch_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    lib.gph_engine_sfs_fetch_observed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.gph_engine_sfs_fetch_rows.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32)]
+    lib.gph_engine_sfs_column_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.gph_engine_sfs_column_name.restype = C.c_char_p
+    lib.gph_sfs_write.argtypes = [C.c_char_p, C.c_int32]
+    lib.gph_sfs_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_mutations_write.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_mutations_discard.argtypes = [C.c_char_p, C.c_int32]
     lib.gph_engine_mutations_enable.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int64]
@@ -1712,6 +1733,78 @@ class Sampler:
             raise RuntimeError("gphocs_hip: pair_times_rows: not enabled (GPH_ESTATE)")
         its, rows = self._fetch_rows(self.lib.gph_engine_pair_times_fetch_rows, held, NP * (B + 2), np.uint64, with_iters=True)
         return its.copy(), rows.copy()
+
+    # ---- site-frequency spectra, data against sampled genealogies (gph_engine_sfs_*): accumulated on the device
+    def sfs_enable(self, capacity, loci=None, pairs=None, max_bytes=0):
+        """per-locus accumulators E of every slot -- the folded spectrum bins of every current population with two leaves, then
+        privP, privQ, shared, fixed of every pair -- for the selected loci (as enable_gene_trees; None: all loci of this rank), the
+        data side (obs, use, sites: formed once, here) and a device buffer of `capacity` per-sample rows; capacity 0 switches the
+        feature off.  pairs: None = every pair P < Q of current populations with samples, [] = none, else a list of (P, Q)
+        population indices in any order.  ValueError for a refused selection or pair list (stderr names the cause; the sampler is
+        left as it was), MemoryError when accumulators and rows would exceed max_bytes (0: 1 GiB)"""
+        sel = self._listed(None if loci is None else np.ascontiguousarray(loci, dtype=np.int64))
+        pr = self._listed(None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2), C.c_int32)
+        self._enabled(self.lib.gph_engine_sfs_enable(self.engine, int(capacity), *sel, *pr, int(max_bytes)), "sfs_enable",
+                      "the sfs accumulators and rows exceed", "the capacity, the selection or the pairs")
+
+    def sfs_sample(self, it):
+        """the expected spectra of every selected locus under the current state, labelled iteration `it`; BufferError when the row
+        buffer is full"""
+        self._sample(self.lib.gph_engine_sfs_sample, "sfs row", "sfs_rows", int(it))
+
+    def _sfs_shape(self):
+        """(NS, NG, G, selected, samples, rows held)"""
+        a, b, g, q, S, held = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
+        self._chk(self.lib.gph_engine_sfs_shape(self.engine, C.byref(a), C.byref(b), C.byref(g), C.byref(q), C.byref(S), C.byref(held)), "sfs_shape")
+        return a.value, b.value, g.value, q.value, S.value, held.value
+
+    def sfs_columns(self):
+        """the NS slot names"""
+        return [self.lib.gph_engine_sfs_column_name(self.engine, c).decode() for c in range(self._sfs_shape()[0])]
+
+    def _sfs_tables(self):
+        NS, NG = self._sfs_shape()[:2]
+        if NS == 0:
+            raise RuntimeError("gphocs_hip: sfs: not enabled (GPH_ESTATE)")
+        slots = np.zeros((NS, 5), dtype=np.int32)
+        self._chk(self.lib.gph_engine_sfs_slots(self.engine, slots.ctypes.data), "sfs_slots")
+        groups = [self.lib.gph_engine_sfs_column_name(self.engine, NS + g).decode() for g in range(NG)]
+        return slots, groups
+
+    def sfs(self, reset=False):
+        """the accumulators of this rank's Q selected loci as the device holds them: a dict of loci[Q] (global indices), samples,
+        group (the selected loci a partial row sums), columns (the NS slot names), groups (the NG group names), slots (NS, 5) int32
+        (group, kind, P, Q, k) and E (Q, NS) float64.  reset=True zeroes E afterwards and restarts the sample count"""
+        NS, NG, G_, Q, S, _ = self._sfs_shape()
+        slots, groups = self._sfs_tables()
+        loci = self._selected(self.lib.gph_engine_sfs_selected, Q)
+        acc = np.zeros((max(Q, 1), NS), dtype=np.float64)
+        self._chk(self.lib.gph_engine_sfs_fetch_loci(self.engine, acc.ctypes.data, NS, int(bool(reset))), "sfs_fetch_loci")
+        return dict(loci=loci, samples=S, group=G_, columns=self.sfs_columns(), groups=groups, slots=slots, E=acc[:Q].copy())
+
+    def sfs_observed(self):
+        """the data side, formed once at enable: a dict of loci[Q], obs (Q, NS), use (Q, NG), sites (Q,) uint32 and their totals over
+        this rank's selected loci, obs_total (NS,), use_total (NG,), sites_total, uint64"""
+        NS, NG, _, Q, _, _ = self._sfs_shape()
+        if NS == 0:
+            raise RuntimeError("gphocs_hip: sfs_observed: not enabled (GPH_ESTATE)")
+        W = NS + NG + 1
+        out = np.zeros((max(Q, 1), W), dtype=np.uint32)
+        tot = np.zeros(W, dtype=np.uint64)
+        self._chk(self.lib.gph_engine_sfs_fetch_observed(self.engine, out.ctypes.data, W, tot.ctypes.data), "sfs_fetch_observed")
+        out = out[:Q]
+        return dict(loci=self._selected(self.lib.gph_engine_sfs_selected, Q), obs=out[:, :NS].copy(), use=out[:, NS:NS + NG].copy(), sites=out[:, NS + NG].copy(),
+                    obs_total=tot[:NS].copy(), use_total=tot[NS:NS + NG].copy(), sites_total=int(tot[NS + NG]))
+
+    def sfs_rows(self):
+        """(iterations, rows): the per-sample rows taken since the last call, a float64 (samples, NS) array -- per slot the expected
+        number of sites of the class among the usable ones, over THIS rank's selected loci -- and their iterations; the device
+        buffer is emptied"""
+        NS, _, _, _, _, held = self._sfs_shape()
+        if NS == 0:
+            raise RuntimeError("gphocs_hip: sfs_rows: not enabled (GPH_ESTATE)")
+        _, rows = self._fetch_rows(self.lib.gph_engine_sfs_fetch_rows, held, 1 + NS)
+        return rows[:, 0].astype(np.int32), rows[:, 1:].copy()
 
     # ---- replicate genealogies simulated from the sampled parameters (gph_engine_simulate_*): simulated on the device
     def simulate_enable(self, seed, capacity, loci=None, with_sites=True, max_bytes=0):

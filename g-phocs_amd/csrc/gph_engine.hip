@@ -36,6 +36,7 @@
 #include "gph_simulate.h"
 #include "gph_triplets.h"
 #include "gph_pairtimes.h"
+#include "gph_sfs.h"
 #include "gph_mutations.h"
 #include "gph_cladecmp.h"
 #include "gph_comm.h"
@@ -453,7 +454,7 @@ __global__ void __launch_bounds__(GPH_WAVE) k_rng_ahead(GphKargs KA, GphDev D)
 #endif
 
 // ---------------------------------------------------------------- engine object
-#define GPH_NCLS 27     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets, 24: k_mutations, 25: k_simulate, 26: k_pair_times) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
+#define GPH_NCLS 29     // (18: k_rng_ahead, 19: k_clades, 20: k_clades_compare, 21: k_ess, 22: k_predictive, 23: k_triplets, 24: k_mutations, 25: k_simulate, 26: k_pair_times, 27: k_sfs_tree, 28: k_sfs_data) kernel classes of gph_engine_last_kernel_ms (the chain state counts evaluations for the first 16)
 // the two buffers the statistics samplers keep on the device (alloc / free / fetch: sampler scaffold below)
 struct SmRows {      // the rows of the samples taken since the last fetch: [cap][n] elements of esz bytes, `fill` of them taken
   char *d = nullptr;
@@ -592,8 +593,14 @@ struct gph_engine_state {
   // doubles (A, Y, X, M of every slot), pair [NP] packed pairs, edges [E] doubles, pop [n + Kc] bytes --, the per-sample rows
   // [cap][NP (B + 2)] u64 with their iterations, the pairs and edges as the caller sees them
   struct : SmSelected { size_t o_pair = 0, o_edge = 0, o_pop = 0; GphPtShape shape = {}; std::vector<int32_t> pairs; std::vector<double> edges; std::string name; } pt;
+  // site-frequency spectra of selected loci (gph_sfs.h): ONE buffer in selection order -- acc [nsel][NS] doubles (E of every slot);
+  // behind it the data side, formed once at enable: obs [nsel][NS], use [nsel][NG], sites [nsel] u32, tot [NS + NG + 1] u64 (their
+  // totals over the selection); then the tables: slot [NS], sgrp [NS], gdef [NG], gbase [NG] i32, pop [n + Kc] bytes --, one partial
+  // row of 1 + NS doubles per workgroup of G selected loci, folded into the per-sample rows [cap][1 + NS] (column 0: the iteration)
+  struct : SmSelected { SmParts part; size_t o_obs = 0, o_use = 0, o_sites = 0, o_tot = 0, o_slot = 0, o_sgrp = 0, o_gdef = 0, o_gbase = 0, o_pop = 0;
+                        GphSfShape shape = {}; std::vector<int32_t> slot, sgrp, gdef, gbase; std::string name; } sf;
   // the samplers with accumulators over a selection, in the order gph_engine_init_genealogies zeroes them
-  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr, &mu, &si, &pt}; }
+  std::vector<SmSelected *> selected() { return {&cl, &es, &pd, &tr, &mu, &si, &pt, &sf}; }
   double last_ms[GPH_NCLS] = {0};
   // per kernel class: launches, summed HIP-event ms; evaluations / bytes / nodes live in the chain state
   double cls_launches[GPH_NCLS] = {0}, cls_ms[GPH_NCLS] = {0};
@@ -998,7 +1005,7 @@ void gph_engine_destroy(gph_engine *e)
   dev_free(e->ls.d); dev_free(e->cs.part.d_part); dev_free(e->cs.rows.d); dev_free(e->ts.part.d_part); dev_free(e->ts.rows.d);
   dev_free(e->an.d_acc); dev_free(e->an.rows.d);
   dev_free(e->gt.rows.d); dev_free(e->gt.sel.d_slot);
-  dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp); dev_free(e->mu.part.d_part);
+  dev_free(e->cl.d_hdr); dev_free(e->cl.d_cmp); dev_free(e->mu.part.d_part); dev_free(e->sf.part.d_part);
   for (SmSelected *s : e->selected()) { dev_free(s->d); dev_free(s->sel.d_slot); dev_free(s->rows.d); }
   dev_free((void *)e->dev.slog_map); dev_free(e->dev.slog); dev_free(e->dev.slog_n);
   if (e->d_gather != e->d_red) dev_free(e->d_gather);
@@ -3752,6 +3759,229 @@ const char *gph_engine_pair_times_column_name(gph_engine *e, int32_t col)
   const std::string pq = std::to_string((int)(word & 255u)) + "|" + std::to_string((int)((word >> 8) & 255u));
   e->pt.name = col < NP * B ? pq + ":" + std::to_string(col % B) : (col < NP * B + NP ? "below_" : "loci_") + pq;
   return e->pt.name.c_str();
+}
+
+// ---- site-frequency spectra of selected loci, data against sampled genealogies (gph_sfs.h)
+// the accumulators E back to zero, the sample count with them (the data side stays: it is formed once, at enable)
+static int sfs_zero(gph_engine *e) { return acc_zero(e, e->sf.d, e->sf.o_obs); }
+static void sfs_free(gph_engine *e) { selected_free(e->sf, {e->sf.part.d_part}); }
+static int sfs_refuse(const char *fmt, long long a, long long b, long long c)
+{
+  fprintf(stderr, "gphocs_hip: sfs: ");
+  fprintf(stderr, fmt, a, b, c);
+  fputc('\n', stderr);
+  return GPH_EARG;
+}
+
+int gph_engine_sfs_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, const int32_t *pairs, int32_t npairs, int64_t max_bytes)
+{
+  if (!e || !e->loaded) return GPH_ESTATE;
+  if (capacity_rows < 0 || (loci && nloci < 0) || (pairs && npairs < 0)) return GPH_EARG;
+  SETDEV(e);
+  if (capacity_rows == 0) { sfs_free(e); return 0; }
+  const int n = e->cfg.n, Kc = e->cfg.Kc;
+  /* every refusal before anything is freed or allocated, as the triplet weights do: a refused call leaves the sampler as it was */
+  if (n > 255) return sfs_refuse("%lld leaves: the byte counts of k_sfs_tree hold 255 at most", n, 0, 0);
+  int64_t nsel = 0;
+  for (int64_t k = 0; k < (loci ? nloci : e->L); k++) {
+    const int64_t g = loci ? loci[k] : e->cfg.locus_begin + k;
+    if (g < 0 || g >= e->cfg.L_total) return sfs_refuse("locus %lld is out of range (0 .. %lld)", g, e->cfg.L_total - 1, 0);
+    if (k > 0 && loci && g == loci[k - 1]) return sfs_refuse("locus %lld is named twice", g, 0, 0);
+    if (k > 0 && loci && g < loci[k - 1]) return sfs_refuse("locus %lld stands behind locus %lld: the selection is not increasing", g, loci[k - 1], 0);
+    if (g < e->cfg.locus_begin || g >= e->cfg.locus_begin + e->L) continue;
+    const int64_t sites = e->h_sites[(size_t)(g - e->cfg.locus_begin)];
+    if (sites >= ((int64_t)1 << 32)) return sfs_refuse("locus %lld: %lld sites reach 2^32: its counts do not fit 32 bits", g, sites, 0);
+    nsel++;
+  }
+  std::vector<int32_t> pr;                          /* [pair][2], P < Q */
+  if (!pairs) {
+    for (int P = 0; P < Kc; P++)
+      for (int Q = P + 1; Q < Kc; Q++)
+        if (e->samplesPerPop[P] >= 1 && e->samplesPerPop[Q] >= 1) { pr.push_back(P); pr.push_back(Q); }
+  } else {
+    for (int32_t k = 0; k < npairs; k++) {
+      int m[2] = {pairs[2 * k], pairs[2 * k + 1]};
+      for (int a = 0; a < 2; a++)
+        if (m[a] < 0 || m[a] >= Kc) return sfs_refuse("pair %lld names population %lld: the current populations are 0 .. %lld", k, m[a], Kc - 1);
+      if (m[0] == m[1]) return sfs_refuse("pair %lld names population %lld twice: a pair has two populations", k, m[0], 0);
+      if (m[0] > m[1]) std::swap(m[0], m[1]);
+      for (int a = 0; a < 2; a++)
+        if (e->samplesPerPop[m[a]] < 1) return sfs_refuse("pair %lld names population %lld, which has no sample", k, m[a], 0);
+      for (size_t q = 0; q < pr.size(); q += 2)
+        if (pr[q] == m[0] && pr[q + 1] == m[1]) return sfs_refuse("pair %lld (%lld, %lld) is named twice", k, m[0], m[1]);
+      pr.push_back(m[0]); pr.push_back(m[1]);
+    }
+  }
+  std::vector<int32_t> slot, sgrp, gdef, gbase;
+  for (int p = 0; p < Kc; p++) {
+    if (e->samplesPerPop[p] < 2) continue;
+    gdef.push_back(gph_sf_pack(0, p, p, 0)); gbase.push_back((int32_t)slot.size());
+    for (int k = 1; k <= e->samplesPerPop[p] / 2; k++) { slot.push_back(gph_sf_pack(SFS_BIN, p, p, k)); sgrp.push_back((int32_t)gdef.size() - 1); }
+  }
+  for (size_t q = 0; q < pr.size(); q += 2) {
+    gdef.push_back(gph_sf_pack(1, pr[q], pr[q + 1], 0)); gbase.push_back((int32_t)slot.size());
+    for (int c = SFS_PRIVP; c <= SFS_FIXED; c++) { slot.push_back(gph_sf_pack(c, pr[q], pr[q + 1], 0)); sgrp.push_back((int32_t)gdef.size() - 1); }
+  }
+  if (slot.empty()) return sfs_refuse("no population has two samples and no pair is taken: there is no slot", 0, 0, 0);
+  const int NS = (int)slot.size(), NG = (int)gdef.size(), W = NS + NG + 1;
+  GphSfShape h;
+  gph_sf_shape(e->lay, NS, NG, h);
+  if (h.tr.lds_bytes > 65536 || h.d_lds > 65536)
+    return sfs_refuse("%lld leaves in %lld current populations need %lld bytes of LDS a workgroup (65536 at most)", n, Kc, h.tr.lds_bytes > h.d_lds ? h.tr.lds_bytes : h.d_lds);
+  sfs_free(e);
+  const std::vector<uint8_t> pop = leaf_pops(e, true);
+  const int rd = 1 + NS, groups = (int)((nsel + h.tr.G - 1) / h.tr.G);
+  const size_t o_obs = (size_t)nsel * NS * 8, o_use = o_obs + (size_t)nsel * NS * 4, o_sites = o_use + (size_t)nsel * NG * 4,
+               o_tot = (o_sites + (size_t)nsel * 4 + 7) & ~(size_t)7, o_slot = o_tot + (size_t)W * 8, o_sgrp = o_slot + (size_t)NS * 4,
+               o_gdef = o_sgrp + (size_t)NS * 4, o_gbase = o_gdef + (size_t)NG * 4, o_pop = (o_gbase + (size_t)NG * 4 + 15) & ~(size_t)15,
+               bytes = o_pop + pop.size(), pbytes = (size_t)(groups > 0 ? groups : 1) * rd * 8;
+  const int64_t need = (int64_t)bytes + (int64_t)pbytes + (int64_t)capacity_rows * rd * 8;
+  /* (nothing to free behind this refusal: the sampler is off already) */
+  if (over_limit(need, max_bytes, "sfs: the accumulators and rows", "%lld loci x (%d slots x 12 + %d groups x 4 + 4) + (%d workgroups + %d rows) x %d x 8 + %lld",
+                 (long long)nsel, NS, NG, groups > 0 ? groups : 1, (int)capacity_rows, rd, (long long)(bytes - o_tot))) return GPH_EFULL;
+  { int rcs = sel_alloc(e, e->sf.sel, loci, nloci); if (rcs) return rcs; }
+  if (dev_alloc((void **)&e->sf.d, bytes)) { dev_clear_error(); e->sf.d = nullptr; sfs_free(e); return GPH_EHIP; }
+  if (dev_alloc((void **)&e->sf.part.d_part, pbytes)) { dev_clear_error(); e->sf.part.d_part = nullptr; sfs_free(e); return GPH_EHIP; }
+  if (rows_alloc(e->sf.rows, sizeof(double), rd, capacity_rows)) { dev_clear_error(); sfs_free(e); return GPH_EHIP; }
+  int rc = h2d(e, e->sf.d + o_slot, slot.data(), (size_t)NS * 4);
+  if (!rc) rc = h2d(e, e->sf.d + o_sgrp, sgrp.data(), (size_t)NS * 4);
+  if (!rc) rc = h2d(e, e->sf.d + o_gdef, gdef.data(), (size_t)NG * 4);
+  if (!rc) rc = h2d(e, e->sf.d + o_gbase, gbase.data(), (size_t)NG * 4);
+  if (!rc) rc = h2d(e, e->sf.d + o_pop, pop.data(), pop.size());
+  /* the data side, once: one workgroup a selected locus (a rank without one keeps the zeros) */
+  if (!rc) rc = acc_zero(e, e->sf.d + o_obs, o_slot - o_obs);
+  if (!rc && nsel > 0) {
+    int tms;
+    rc = sample_begin(e, 28, tms);
+    if (!rc) rc = launch_grid(e, GphGrid{(int)nsel, 1}, h.dbd, (size_t)h.d_lds, k_sfs_data, e->lay, h, e->dev.seq, e->dev.seq_off, e->dev.P,
+                              (const int32_t *)e->sf.sel.d_slot, (const int32_t *)(e->sf.d + o_gdef), (const int32_t *)(e->sf.d + o_gbase),
+                              (const uint8_t *)(e->sf.d + o_pop), (int)nsel, (int)e->L, (uint32_t *)(e->sf.d + o_obs), (uint32_t *)(e->sf.d + o_use),
+                              (uint32_t *)(e->sf.d + o_sites), (uint64_t *)(e->sf.d + o_tot));
+    if (!rc) sample_end(e, 28, 1, tms);
+  }
+  if (rc) { sfs_free(e); return rc; }
+  e->sf.part.rd = rd; e->sf.part.chunk = h.tr.G; e->sf.part.nchunks = groups;
+  e->sf.shape = h;
+  e->sf.slot = slot; e->sf.sgrp = sgrp; e->sf.gdef = gdef; e->sf.gbase = gbase;
+  e->sf.o_obs = o_obs; e->sf.o_use = o_use; e->sf.o_sites = o_sites; e->sf.o_tot = o_tot; e->sf.o_slot = o_slot; e->sf.o_sgrp = o_sgrp;
+  e->sf.o_gdef = o_gdef; e->sf.o_gbase = o_gbase; e->sf.o_pop = o_pop; e->sf.bytes = bytes;
+  return selected_on(e, e->sf, sfs_zero);
+}
+
+// one sample of the current state into the accumulators and the next free row, queued on the engine's stream: k_sfs_tree, then
+// the fold of its partial rows
+int gph_engine_sfs_sample(gph_engine *e, int32_t iteration)
+{
+  if (!e || !e->initialized || !e->sf.on) return GPH_ESTATE;
+  const GphSfShape &h = e->sf.shape;
+  const SmParts &p = e->sf.part;
+  const int nsel = (int)e->sf.sel.loci.size();
+  SmTaken t;
+  t.rows = &e->sf.rows;
+  t.samples = &e->sf.samples;
+  /* (a rank without a selected locus launches the fold alone: its row is the iteration and zeros) */
+  return sample_run(e, SETTLE_PAGES_AND_AGES, 27, p.nchunks > 0 ? 2 : 1, t, [&](void *row) {
+    if (p.nchunks > 0) {
+      int rcl = launch_grid(e, GphGrid{p.nchunks, 1}, h.tr.bd, (size_t)h.tr.lds_bytes, k_sfs_tree, e->lay, h, (const char *)e->dev.pages,
+                            (const int32_t *)e->sf.sel.d_slot, (const int32_t *)(e->sf.d + e->sf.o_slot), (const int32_t *)(e->sf.d + e->sf.o_sgrp),
+                            (const uint8_t *)(e->sf.d + e->sf.o_pop), (const uint32_t *)(e->sf.d + e->sf.o_use), nsel, (int)e->L, (double *)e->sf.d, p.d_part);
+      if (rcl) return rcl;
+    }
+    return parts_fold(e, p, iteration, (double *)row);
+  });
+}
+
+// slots: NS; groups: NG; group: the loci a workgroup takes (a partial row sums)
+int gph_engine_sfs_shape(gph_engine *e, int32_t *slots, int32_t *groups, int32_t *group, int64_t *selected, int64_t *samples, int32_t *rows_held)
+{
+  if (!e) return GPH_EARG;
+  const bool on = e->sf.on;
+  if (slots) *slots = on ? e->sf.shape.NS : 0;
+  if (groups) *groups = on ? e->sf.shape.NG : 0;
+  if (group) *group = on ? e->sf.shape.tr.G : 0;
+  if (selected) *selected = on ? (int64_t)e->sf.sel.loci.size() : 0;
+  if (samples) *samples = on ? e->sf.samples : 0;
+  if (rows_held) *rows_held = on ? e->sf.rows.fill : 0;
+  return 0;
+}
+
+int gph_engine_sfs_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count) { return selected_out(e, e ? &e->sf : nullptr, out, max_loci, count); }
+
+// out [NS][5]: the slot's group, its kind (0: a bin, 1 .. 4: privP, privQ, shared, fixed), P, Q (P again for a bin), k (0 for a class)
+int gph_engine_sfs_slots(gph_engine *e, int32_t *out)
+{
+  if (!e || !out) return GPH_EARG;
+  if (!e->sf.on) return GPH_ESTATE;
+  for (size_t s = 0; s < e->sf.slot.size(); s++) {
+    const uint32_t word = (uint32_t)e->sf.slot[s];
+    out[5 * s] = e->sf.sgrp[s]; out[5 * s + 1] = (int32_t)(word >> 24); out[5 * s + 2] = (int32_t)(word & 255u);
+    out[5 * s + 3] = (int32_t)((word >> 8) & 255u); out[5 * s + 4] = (int32_t)((word >> 16) & 255u);
+  }
+  return 0;
+}
+
+// out [selected][ld], ld >= NS: E of every slot
+int gph_engine_sfs_fetch_loci(gph_engine *e, double *out, int64_t ld, int32_t reset)
+{
+  if (!e) return GPH_EARG;
+  if (!e->sf.on) return GPH_ESTATE;
+  const size_t nsel = e->sf.sel.loci.size(), w = (size_t)e->sf.shape.NS;
+  if ((nsel > 0 && !out) || ld < (int64_t)w) return GPH_EARG;
+  SETDEV(e);
+  if (nsel > 0) {
+    std::vector<double> acc(nsel * w);
+    { int rc = pull_rows(e, acc.data(), e->sf.d, e->sf.o_obs); if (rc) return rc; }
+    for (size_t q = 0; q < nsel; q++) memcpy(out + q * (size_t)ld, acc.data() + q * w, w * 8);
+  }
+  return reset ? selected_zero(e, e->sf) : 0;
+}
+
+// the data side as k_sfs_data left it at enable: out [selected][ld], ld >= NS + NG + 1: obs of the NS slots, use of the NG groups,
+// sites; totals [NS + NG + 1] (may be null): the same over the selection.  One copy, one host synchronisation
+int gph_engine_sfs_fetch_observed(gph_engine *e, uint32_t *out, int64_t ld, uint64_t *totals)
+{
+  if (!e) return GPH_EARG;
+  if (!e->sf.on) return GPH_ESTATE;
+  const size_t nsel = e->sf.sel.loci.size(), NS = (size_t)e->sf.shape.NS, NG = (size_t)e->sf.shape.NG, W = NS + NG + 1;
+  if ((nsel > 0 && !out) || ld < (int64_t)W) return GPH_EARG;
+  SETDEV(e);
+  std::vector<char> all(e->sf.o_slot - e->sf.o_obs);
+  { int rc = pull_rows(e, all.data(), e->sf.d + e->sf.o_obs, all.size()); if (rc) return rc; }
+  const char *obs = all.data(), *use = all.data() + (e->sf.o_use - e->sf.o_obs), *sites = all.data() + (e->sf.o_sites - e->sf.o_obs);
+  for (size_t q = 0; q < nsel; q++) {
+    uint32_t *row = out + q * (size_t)ld;
+    memcpy(row, obs + q * NS * 4, NS * 4);
+    memcpy(row + NS, use + q * NG * 4, NG * 4);
+    memcpy(row + NS + NG, sites + q * 4, 4);
+  }
+  if (totals) memcpy(totals, all.data() + (e->sf.o_tot - e->sf.o_obs), W * 8);
+  return 0;
+}
+
+// the rows taken since the last fetch, [rows][1 + NS] doubles (column 0: the iteration); the row buffer is empty again
+int gph_engine_sfs_fetch_rows(gph_engine *e, double *out, int32_t max_rows, int32_t *rows)
+{
+  if (!e || !rows || max_rows < 0 || (!out && max_rows > 0)) return GPH_EARG;
+  if (!e->sf.on) return GPH_ESTATE;
+  if (max_rows < e->sf.rows.fill) return GPH_EARG;
+  SETDEV(e);
+  return rows_fetch(e, e->sf.rows, out, rows);
+}
+
+// the NS slots, "sfs_<p>:<k>" per bin and "privP_<P>|<Q>", "privQ_", "shared_", "fixed_" per pair, then the NG groups, "<p>" or
+// "<P>|<Q>", with the indices of the current populations
+const char *gph_engine_sfs_column_name(gph_engine *e, int32_t col)
+{
+  if (!e || !e->sf.on || col < 0 || col >= e->sf.shape.NS + e->sf.shape.NG) return nullptr;
+  static const char *const cls[5] = {"sfs_", "privP_", "privQ_", "shared_", "fixed_"};
+  const int NS = e->sf.shape.NS;
+  const uint32_t word = (uint32_t)(col < NS ? e->sf.slot[(size_t)col] : e->sf.gdef[(size_t)(col - NS)]);
+  const int kind = (int)(word >> 24);
+  const std::string P = std::to_string((int)(word & 255u)), Q = std::to_string((int)((word >> 8) & 255u));
+  if (col >= NS) e->sf.name = kind ? P + "|" + Q : P;
+  else if (kind == SFS_BIN) e->sf.name = cls[0] + P + ":" + std::to_string((int)((word >> 16) & 255u));
+  else e->sf.name = cls[kind] + P + "|" + Q;
+  return e->sf.name.c_str();
 }
 
 // ---- replicate genealogies of selected loci, simulated from the sampled parameters (gph_simulate.h)

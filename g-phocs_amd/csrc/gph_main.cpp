@@ -46,6 +46,10 @@
 // pairs) the mean and the youngest age and how often a coalescence lies below the populations' split to PREFIX.pair-times.tsv, and
 // per sample the genome-wide histograms over the grid (--pair-times-grid LO,HI,B, default 1e-6,1e-2,34: B bins, geometric edges)
 // with their cumulative curves to PREFIX.pair-times-genome.tsv (--pair-times-rows N: rows of the device buffer).
+// --sfs PREFIX writes the site-frequency spectrum of every current population and, per pair of populations (--sfs-pairs "A,B;C,D",
+// default all pairs, `none`: none), the private, shared and fixed variable sites, as the data show them next to what the sampled
+// genealogies expect: per selected locus (--sfs-loci SPEC, default all) to PREFIX.sfs.tsv, genome-wide per sample with the observed
+// totals, ratios and z scores to PREFIX.sfs-genome.tsv (--sfs-rows N: rows of the device buffer).
 // --beta B runs the whole chain on the power posterior p(D|G)^B p(G|Theta) p(Theta), B in [0, 64], 0 = the prior;
 // --marginal-likelihood PREFIX runs, behind the unchanged run, the ladder beta_k = (k/K)^(1/a) from 1 down to 0 (--ml-steps K,
 // default 32; --ml-alpha a, default 0.3; per rung --ml-burnin b discarded iterations, default the control file's burn-in or
@@ -137,7 +141,7 @@ static void forward_signal(int sig)
 
 static int usage(const char *a0)
 {
-  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--ess ess-prefix [--ess-loci SPEC]] [--predictive pp-prefix [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]] [--triplets tw-prefix [--triplets-pops \"A,B,C;D,E,F\"] [--triplets-loci SPEC] [--triplets-rows N]] [--mutations mutations-prefix [--mutations-loci SPEC] [--mutations-rows N]] [--pair-times pt-prefix [--pair-times-pops \"A,B;A,A\"] [--pair-times-grid LO,HI,B] [--pair-times-loci SPEC] [--pair-times-rows N]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] [--replicates R --replicates-out rep-prefix [--replicates-min-freq F] [--replicates-every k]] <control-file> [secondary-control-file]\n", a0);
+  fprintf(stderr, "usage: %s [-v] [-d device] [-g gpus] [-l locus-summary-file] [-s coal-stats-prefix [--coal-stats-rows N] [--time-slices S]] [--ancestry ancestry-prefix] [--gene-trees trees-prefix [--gene-trees-loci SPEC] [--gene-trees-rows N]] [--clades clades-prefix [--clades-loci SPEC] [--clades-slots P] [--clades-min-support F]] [--ess ess-prefix [--ess-loci SPEC]] [--predictive pp-prefix [--predictive-loci SPEC] [--predictive-seed N] [--predictive-rows N]] [--triplets tw-prefix [--triplets-pops \"A,B,C;D,E,F\"] [--triplets-loci SPEC] [--triplets-rows N]] [--mutations mutations-prefix [--mutations-loci SPEC] [--mutations-rows N]] [--pair-times pt-prefix [--pair-times-pops \"A,B;A,A\"] [--pair-times-grid LO,HI,B] [--pair-times-loci SPEC] [--pair-times-rows N]] [--sfs sfs-prefix [--sfs-pairs \"A,B;C,D\"|none] [--sfs-loci SPEC] [--sfs-rows N]] [--beta B] [--marginal-likelihood ml-prefix [--ml-steps K] [--ml-burnin b] [--ml-samples s] [--ml-alpha a]] [--mc3 C [--mc3-heat h] [--mc3-swap-every k] [--mc3-report mc3-prefix]] [--replicates R --replicates-out rep-prefix [--replicates-min-freq F] [--replicates-every k]] <control-file> [secondary-control-file]\n", a0);
   return 1;
 }
 
@@ -182,6 +186,10 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--pair-times-grid") && i + 1 < argc) o.pair_times_grid = argv[++i];
     else if (!strcmp(argv[i], "--pair-times-loci") && i + 1 < argc) o.pair_times_loci = argv[++i];
     else if (!strcmp(argv[i], "--pair-times-rows") && i + 1 < argc) { o.pair_times_rows = atoi(argv[++i]); if (o.pair_times_rows < 1) return usage(argv[0]); }
+    else if (!strcmp(argv[i], "--sfs") && i + 1 < argc) o.sfs_prefix = argv[++i];
+    else if (!strcmp(argv[i], "--sfs-pairs") && i + 1 < argc) o.sfs_pairs = argv[++i];
+    else if (!strcmp(argv[i], "--sfs-loci") && i + 1 < argc) o.sfs_loci = argv[++i];
+    else if (!strcmp(argv[i], "--sfs-rows") && i + 1 < argc) { o.sfs_rows = atoi(argv[++i]); if (o.sfs_rows < 1) return usage(argv[0]); }
     else if (!strcmp(argv[i], "--clades") && i + 1 < argc) o.clades_prefix = argv[++i];
     else if (!strcmp(argv[i], "--clades-loci") && i + 1 < argc) o.clades_loci = argv[++i];
     else if (!strcmp(argv[i], "--clades-slots") && i + 1 < argc) {
@@ -274,6 +282,10 @@ int main(int argc, char **argv)
   }
   if ((o.pair_times_pops || o.pair_times_grid || o.pair_times_loci || o.pair_times_rows) && !o.pair_times_prefix) {
     fprintf(stderr, "%s: --pair-times-pops, --pair-times-grid, --pair-times-loci and --pair-times-rows need --pair-times PREFIX\n", argv[0]);
+    return usage(argv[0]);
+  }
+  if ((o.sfs_pairs || o.sfs_loci || o.sfs_rows) && !o.sfs_prefix) {
+    fprintf(stderr, "%s: --sfs-pairs, --sfs-loci and --sfs-rows need --sfs PREFIX\n", argv[0]);
     return usage(argv[0]);
   }
   if ((o.marginal_steps || o.marginal_burnin || o.marginal_samples || o.marginal_alpha != 0.0) && !o.marginal_prefix) {
@@ -403,7 +415,7 @@ int main(int argc, char **argv)
     if (out && fclose(out) != 0) { perror(o.locus_summary_path); bad = 1; }
     if (bad && out) unlink(o.locus_summary_path);
   }
-  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.ess_prefix || o.predictive_prefix || o.triplets_prefix || o.mutations_prefix || o.simulate_prefix || o.pair_times_prefix || o.marginal_prefix || o.mc3_report_prefix || o.replicates_prefix) {
+  if (o.coal_stats_prefix || o.ancestry_prefix || o.gene_trees_prefix || o.clades_prefix || o.ess_prefix || o.predictive_prefix || o.triplets_prefix || o.mutations_prefix || o.simulate_prefix || o.pair_times_prefix || o.sfs_prefix || o.marginal_prefix || o.mc3_report_prefix || o.replicates_prefix) {
     /* the ranks' parts into the files, by the library that wrote them -- or, after a failure, removed */
     if (sym<decltype(&gph_run_finish)>(load_engine(dir, o.ctl, o.ctl2), "gph_run_finish")(&o, gpus, bad)) bad = 1;
   }

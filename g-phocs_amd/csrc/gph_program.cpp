@@ -1027,7 +1027,7 @@ void Run::trace_kept(gph_mcmc *m, double *v, std::vector<double> &x, double &log
 //   Part          this rank's binary part (coal stats, time slices, ancestry, gene trees)
 //   Selected      an output over `--<name>-loci SPEC`: this rank's share of the selection, how it is handed to the engine, the
 //                 message of an enable call that found the selection too large
-//   TextOutput    a Selected whose part is text (gph_textparts.h): clades, ess, mutations and, through RowsOutput, predictive, triplets, simulate, pair times
+//   TextOutput    a Selected whose part is text (gph_textparts.h): clades, ess, mutations and, through RowsOutput, predictive, triplets, simulate, pair times, sfs
 //   RowsOutput    a TextOutput that also keeps per-sample rows: fetched when the device buffer is full, printed as R lines
 struct Output {
   virtual ~Output() {}
@@ -1501,6 +1501,9 @@ struct Clades : TextOutput {
 // pairwise coalescence-time distributions
 #include "gph_pairtimes_run.h"
 
+// ---- `--sfs PREFIX [--sfs-pairs "A,B;C,D"|none] [--sfs-loci SPEC] [--sfs-rows N]`: site-frequency spectra, data against sampled genealogies
+#include "gph_sfs_run.h"
+
 // the enabled outputs in the order of their engine calls at a sample, which is also the order in which gph_run_finish writes
 // their files (the groups of fewer files first: should a later one fail, fewer are removed again).  A run closes them in the
 // opposite order, as it always did, and opens them in that order too: the summary is now enabled last, not first
@@ -1515,6 +1518,7 @@ struct Outputs {
   Mutations *mutations = nullptr;
   Simulate *simulate = nullptr;
   PairTimes *pair_times = nullptr;
+  Sfs *sfs = nullptr;
   explicit Outputs(const gph_run_options &o)
   {
     if (o.locus_summary_path) list.emplace_back(summary = new LocusSummary);
@@ -1524,6 +1528,7 @@ struct Outputs {
     if (o.mutations_prefix) list.emplace_back(mutations = new Mutations(o));
     if (o.simulate_prefix) list.emplace_back(simulate = new Simulate(o));
     if (o.pair_times_prefix) list.emplace_back(pair_times = new PairTimes(o));
+    if (o.sfs_prefix) list.emplace_back(sfs = new Sfs(o));
     if (o.clades_prefix) list.emplace_back(clades = new Clades(o));
     if (o.gene_trees_prefix) list.emplace_back(trees = new GeneTrees(o));
     if (o.ancestry_prefix) list.emplace_back(new Ancestry(o));
@@ -1799,6 +1804,7 @@ int run_chain(const gph_run_options &o)
   if (outs.clades && (rc = outs.clades->check_names(R))) return rc;
   if (outs.triplets && (rc = outs.triplets->check_pops(R))) return rc;
   if (outs.pair_times && (rc = outs.pair_times->check_pops(R))) return rc;
+  if (outs.sfs && (rc = outs.sfs->check_pops(R))) return rc;
   if ((rc = R.read_loci())) return rc;
   if (outs.trees && (rc = outs.trees->select(R))) return rc;
   if (outs.clades && (rc = outs.clades->select(R))) return rc;
@@ -1808,6 +1814,7 @@ int run_chain(const gph_run_options &o)
   if (outs.mutations && (rc = outs.mutations->select(R))) return rc;
   if (outs.simulate && (rc = outs.simulate->select(R))) return rc;
   if (outs.pair_times && (rc = outs.pair_times->select(R))) return rc;
+  if (outs.sfs && (rc = outs.sfs->select(R))) return rc;
   if ((rc = R.start_engine()) || (rc = R.open_trace())) return rc;
   if (o.beta != 0.0) {
     if ((rc = gph_mcmc_set_beta(R.M, option_beta(o)))) return R.fail(rc, "gph_mcmc_set_beta");
@@ -1878,7 +1885,7 @@ int run_chain(const gph_run_options &o)
   if (rcr) return rcr;
   if (checked && where != 0) {
     fprintf(stderr, "gphocs_hip: checked build: an index left its array at %d (source line + 100000 x file: 1 gph_locus.h, 2 gph_kernels.h, "
-                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h, 12 gph_ess.h, 13 gph_predictive.h, 14 gph_triplets.h, 15 gph_mutations.h, 16 gph_simulate.h, 17 gph_pairtimes.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
+                    "3 gph_summary.h, 4 gph_coalstats.h, 5 gph_timeslices.h, 6 gph_ancestry.h, 7 gph_sampler.h, 8 gph_genetrees.h, 10 gph_clades.h, 11 gph_cladecmp.h, 12 gph_ess.h, 13 gph_predictive.h, 14 gph_triplets.h, 15 gph_mutations.h, 16 gph_simulate.h, 17 gph_pairtimes.h, 18 gph_sfs.h; 8000xx / 9000xx: typed accessors of the image / the dynamic LDS)\n", (int)where);
     return GPH_EKERNEL;
   }
   if (outs.summary && (rc = outs.summary->write_table(R))) return rc;
@@ -1914,7 +1921,7 @@ extern "C" int gph_run(const gph_run_options *in)
   if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (o.world > 1 && !o.allreduce && !o.comm)) return GPH_EARG;
   /* the checks on the options alone, before anything is read */
   int rc;
-  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = Ess::validate(o)) || (rc = Predictive::validate(o)) || (rc = Triplets::validate(o)) || (rc = Mutations::validate(o)) || (rc = Simulate::validate(o)) || (rc = PairTimes::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
+  if ((rc = GeneTrees::validate(o)) || (rc = Clades::validate(o)) || (rc = Ess::validate(o)) || (rc = Predictive::validate(o)) || (rc = Triplets::validate(o)) || (rc = Mutations::validate(o)) || (rc = Simulate::validate(o)) || (rc = PairTimes::validate(o)) || (rc = Sfs::validate(o)) || (rc = CoalStats::validate(o)) || (rc = Marginal::validate(o)) || (rc = Mc3Run::validate(o)) ||
       (rc = Replicates::validate(o))) return rc;
   rc = run_chain(o);
   /* one rank: the statistics files now; several: the caller, once every rank's part is complete */

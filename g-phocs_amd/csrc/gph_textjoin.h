@@ -1,8 +1,8 @@
-// gph_textjoin.h -- the seven outputs that travel through text parts (gph_textparts.h): what each format's lines mean
+// gph_textjoin.h -- the eight outputs that travel through text parts (gph_textparts.h): what each format's lines mean
 // once the last rank is done (gph_run_finish), and nothing else: its header line, which tag goes to which file, its summary
 // and its line on stdout.  The parts' writers are the outputs of a run (gph_program.cpp, gph_*_run.h).
 //
-// This header DEFINES the fourteen gph_<name>_write / _discard entry points: one translation unit of a program includes it
+// This header DEFINES the sixteen gph_<name>_write / _discard entry points: one translation unit of a program includes it
 // (gph_program.cpp in the library; a stand-alone program that wants the joiners without the engine includes it itself).
 #ifndef GPH_TEXTJOIN_H
 #define GPH_TEXTJOIN_H
@@ -536,8 +536,103 @@ struct PtJoin : TextJoin {
     fflush(stdout);
   }
 };
+// site-frequency spectra: "H\t<samples>\t<slots>\t<groups>" + "\t<name>" per slot, then per group, + "\t<0|1>" per slot (1: a
+// spectrum slot); a rank's rows of PREFIX.sfs.tsv as "L\t" + row; its observed totals as "O" + "\t<u64>" per slot; its per-sample
+// rows as "R\t<iteration>" + "\t<u64>" per slot: the bit pattern of the double.  The L rows are concatenated in rank order, the O
+// lines added, the R lines added slot by slot in rank order (fp64, from 0.0)
+struct SfsJoin : TextJoin {
+  long long S = -1, NS = -1, NG = -1, Q = 0, sample = 0;
+  std::vector<std::string> names;                       /* [NS] slots, then [NG] groups, then [NS] flags */
+  std::vector<unsigned long long> observed;             /* [NS] */
+  std::vector<double> totals;                           /* [sample][NS] */
+  std::vector<long long> iters;
+  SfsJoin() : TextJoin(true) {}
+  bool header(char *line, ssize_t len, int) override
+  {
+    long long s = 0, ns = 0, ng = 0;
+    int used = 0;
+    if (!(sscanf(line, "H\t%lld\t%lld\t%lld%n", &s, &ns, &ng, &used) == 3 && (S < 0 || (s == S && ns == NS && ng == NG)) && ns >= 1 && ng >= 1 && s >= 0 &&
+          line[len - 1] == '\n')) return false;
+    const std::vector<std::string> f = tab_fields(line + used, (size_t)len - used - 1);
+    if ((long long)f.size() != 2 * ns + ng) return false;
+    if (S >= 0) return f == names;
+    S = s; NS = ns; NG = ng; names = f;
+    observed.assign((size_t)NS, 0);
+    totals.assign((size_t)(S * NS), 0.0);
+    iters.assign((size_t)S, 0);
+    fprintf(out[0], "locus\tname\tsamples\tsites");
+    for (long long g = 0; g < NG; g++) fprintf(out[0], "\tuse_%s", names[(size_t)(NS + g)].c_str());
+    for (long long k = 0; k < NS; k++) fprintf(out[0], "\tobs_%s\texp_%s", names[(size_t)k].c_str(), names[(size_t)k].c_str());
+    fprintf(out[0], "\trel\n");
+    return true;
+  }
+  bool body(char *line, ssize_t, int r) override
+  {
+    if (line[0] == 'O') return TextRows::numbers(line + 1, NS, observed.data());
+    if (line[1] != '\t') return false;
+    if (line[0] == 'L') { fputs(line + 2, out[0]); Q++; return true; }
+    if (line[0] != 'R' || sample >= S) return false;
+    char *at = nullptr;
+    const long long it = strtoll(line + 2, &at, 10);
+    if (at == line + 2 || (r > 0 && iters[(size_t)sample] != it)) return false;
+    for (long long c = 0; c < NS; c++) {
+      if (*at != '\t') return false;
+      char *end = nullptr;
+      const unsigned long long bits = strtoull(at + 1, &end, 10);
+      if (end == at + 1) return false;
+      double v;
+      memcpy(&v, &bits, 8);
+      double &t = totals[(size_t)(sample * NS + c)];
+      t = t + v;
+      at = end;
+    }
+    if (*at != '\n') return false;
+    iters[(size_t)sample++] = it;
+    return true;
+  }
+  bool rank_done() override { const bool all = sample == S; sample = 0; return all; }
+  void summary() override
+  {
+    fprintf(out[0], "# loci %lld samples %lld slots %lld\n", Q, S, NS);
+    fprintf(out[1], "iter");
+    for (long long k = 0; k < NS; k++) fprintf(out[1], "\t%s", names[(size_t)k].c_str());
+    fputc('\n', out[1]);
+    for (long long s = 0; s < S; s++) {
+      fprintf(out[1], "%7d", (int)iters[(size_t)s]);
+      for (long long c = 0; c < NS; c++) fprintf(out[1], "\t%.10g", totals[(size_t)(s * NS + c)]);
+      fputc('\n', out[1]);
+    }
+    std::string lines[5] = {"# observed", "# mean", "# sd", "# ratio", "# z"}, most = "none";
+    double most_z = -1.0;
+    char num[256];
+    for (long long k = 0; k < NS; k++) {
+      double sum = 0.0, ss = 0.0;
+      for (long long s = 0; s < S; s++) sum = sum + totals[(size_t)(s * NS + k)];
+      const double mean = S > 0 ? sum / (double)S : 0.0;
+      for (long long s = 0; s < S; s++) { const double d = totals[(size_t)(s * NS + k)] - mean; ss = ss + d * d; }
+      const double sd = S > 1 ? sqrt(ss / (double)(S - 1)) : 0.0, ob = (double)observed[(size_t)k];
+      const double ratio = mean != 0.0 ? ob / mean : 0.0, den = sqrt(mean + sd * sd), z = den != 0.0 ? (ob - mean) / den : 0.0;
+      snprintf(num, sizeof num, "\t%llu", observed[(size_t)k]); lines[0] += num;
+      snprintf(num, sizeof num, "\t%.10g", mean); lines[1] += num;
+      snprintf(num, sizeof num, "\t%.10g", sd); lines[2] += num;
+      snprintf(num, sizeof num, "\t%.10g", ratio); lines[3] += num;
+      snprintf(num, sizeof num, "\t%.10g", z); lines[4] += num;
+      if (fabs(z) > most_z) {
+        most_z = fabs(z);
+        snprintf(num, sizeof num, " observed %llu mean %.10g ratio %.10g z %.10g", observed[(size_t)k], mean, ratio, z);
+        most = names[(size_t)k] + num;
+      }
+    }
+    for (const std::string &ln : lines) fprintf(out[1], "%s\n", ln.c_str());
+    fprintf(out[1], "# loci %lld samples %lld\n", Q, S);
+    printf("SFS: %s\n", most.c_str());
+    fflush(stdout);
+  }
+};
 }   // namespace
 
+extern "C" int gph_sfs_write(const char *prefix, int32_t ranks) { SfsJoin J; return text_join(SF_TEXT, J, prefix, ranks); }
+extern "C" int gph_sfs_discard(const char *prefix, int32_t ranks) { return text_discard(SF_TEXT, prefix, ranks); }
 extern "C" int gph_pair_times_write(const char *prefix, int32_t ranks) { PtJoin J; return text_join(PT_TEXT, J, prefix, ranks); }
 extern "C" int gph_pair_times_discard(const char *prefix, int32_t ranks) { return text_discard(PT_TEXT, prefix, ranks); }
 extern "C" int gph_simulate_write(const char *prefix, int32_t ranks) { SiJoin J; return text_join(SI_TEXT, J, prefix, ranks); }

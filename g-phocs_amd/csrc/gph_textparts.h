@@ -1,6 +1,6 @@
 // gph_textparts.h -- the text part of a rank, in one place.  Host code that needs nothing of the engine or of a run.
 //
-// Clade tables, effective sample sizes, predictive checks, triplet weights, expected substitutions, replicate genealogies and pair times each write two files from the ranks' text
+// Clade tables, effective sample sizes, predictive checks, triplet weights, expected substitutions, replicate genealogies, pair times and site-frequency spectra each write two files from the ranks' text
 // parts.  Rank r's part PREFIX<suffix><r> is written once, when the chain is done: a first line with the format's magic
 // word, for most formats a line "H\t..." that every rank writes alike, lines "<tag>\t...", and a last line "E\t<lines>"
 // with the number of tagged lines, written when the rank closes its part.  A part without that last line, with anything
@@ -35,6 +35,7 @@ const TextPart TR_TEXT = {"GPHTR1", ".triplets.part", {".triplets.tsv", ".triple
 const TextPart MU_TEXT = {"GPHMU1", ".mutations.part", {".mutations.tsv", ".mutations-genome.tsv"}, "mutations"};
 const TextPart SI_TEXT = {"GPHSI1", ".simulate.part", {".simulate.tsv", ".simulate-genome.tsv"}, "simulate"};
 const TextPart PT_TEXT = {"GPHPT1", ".pair-times.part", {".pair-times.tsv", ".pair-times-genome.tsv"}, "pair-times"};
+const TextPart SF_TEXT = {"GPHSF1", ".sfs.part", {".sfs.tsv", ".sfs-genome.tsv"}, "sfs"};
 
 inline std::string text_part_path(const TextPart &F, const char *prefix, int r) { return std::string(prefix) + F.suffix + std::to_string(r); }
 inline void text_remove_parts(const TextPart &F, const char *prefix, int ranks) { for (int r = 0; r < ranks; r++) remove(text_part_path(F, prefix, r).c_str()); }

@@ -248,7 +248,8 @@ int gph_engine_unit(gph_engine *e, int32_t op, int32_t arg, double *out, int32_t
  * sample sizes per locus (gph_engine_ess_sample: k_ess), 22 posterior predictive checks (gph_engine_predictive_sample:
  * k_predictive), 23 triplet topology weights (gph_engine_triplets_sample: k_triplets), 24 expected substitutions
  * (gph_engine_mutations_sample: k_mutations + k_rows_fold together), 25 replicate genealogies (gph_engine_simulate_sample),
- * 26 pairwise coalescence-time distributions (gph_engine_pair_times_sample: k_pair_times) */
+ * 26 pairwise coalescence-time distributions (gph_engine_pair_times_sample: k_pair_times), 27 site-frequency spectra, the
+ * genealogy side (gph_engine_sfs_sample: k_sfs_tree + k_rows_fold together), 28 their data side (gph_engine_sfs_enable: k_sfs_data) */
 int gph_engine_last_kernel_ms(gph_engine *e, int32_t which, double *ms);
 /* classes whose launches are bracketed by HIP events (bit k = class k); default all */
 int gph_engine_set_timing(gph_engine *e, uint32_t class_mask);
@@ -839,6 +840,76 @@ int gph_engine_pair_times_fetch_loci(gph_engine *e, double *out /* [selected][ld
 int gph_engine_pair_times_fetch_rows(gph_engine *e, int32_t *iters, uint64_t *out /* [rows][ld] */, int64_t ld, int32_t max_rows, int32_t *rows);
 const char *gph_engine_pair_times_column_name(gph_engine *e, int32_t col);
 
+/* SITE-FREQUENCY SPECTRA, data against sampled genealogies, of selected loci and genome-wide per sample (k_sfs_tree, k_sfs_data:
+ * csrc/gph_sfs.h; timing classes 27 and 28): the folded site-frequency spectrum of every current population and the split of the
+ * variable sites of two populations into private, shared and fixed (Wakeley & Hey 1997) -- what the data show next to what the
+ * sampled genealogies expect (Fu 1995: the branch length under each frequency class).  Growth or a bottleneck on a branch, or a
+ * sample whose singletons are errors, changes the SHAPE of the spectrum far more than the mean pairwise difference.
+ *   populations  the Kc CURRENT populations in model order; n_p = the leaves of p
+ *   slots        NS of them.  For every p with n_p >= 2, in population order, the folded bins k = 1 .. n_p / 2 ("sfs_<p>:<k>");
+ *                then for every pair P < Q taken, four classes in this order: privP, privQ, shared, fixed.  Default: all pairs
+ *                with n_P, n_Q >= 1 in lexicographic order
+ *   groups       NG of them: what shares a denominator, one per population with bins, then one per pair
+ *   genealogy    one locus at one sample, from the settled node records a gene-tree record holds and the locus rate of the page:
+ *                every non-root node v in NODE-INDEX order, len_v = age[father v] - age[v] (leaf ages are the records': an
+ *                ancient sample's branch starts at its age), c_v[p] = the leaves of p under v (a leaf counts for its own
+ *                population whatever migrations lie on the branch).
+ *                    v is in sfs_p:k iff 0 < c_v[p] < n_p and min(c_v[p], n_p - c_v[p]) = k (c = n_p / 2 at even n_p: once)
+ *                    a = c_v[P], b = c_v[Q], "a inside" = 0 < a < n_P:
+ *                    privP iff a inside and b in {0, n_Q};  privQ iff b inside and a in {0, n_P};  shared iff both inside;
+ *                    fixed iff (a, b) = (n_P, 0) or (0, n_Q);  otherwise none of the four
+ *                per slot x = sum len_v over its nodes, plain uncontracted fp64 adds in node order from 0.0; e = rate x, one
+ *                multiply: the expected substitutions PER SITE that fall in the class
+ *   data         one locus, once at enable.  Its columns are the rows with a non-zero phase word, each standing for `count`
+ *                sites, as the predictive checks define them; the codes read are the column's own row (both haplotypes of a
+ *                diploid lie in one population, so a population's counts do not depend on the phase row read).
+ *                    p is USABLE at a column iff all n_p leaves have a code below 4 and show two distinct bases at most: the
+ *                    column adds count to use_p and, with k >= 1 carriers of the rarer base, to obs[sfs_p:k]
+ *                    a pair is usable iff all leaves of P and Q are non-missing and P u Q shows two bases at most: count to
+ *                    use_PQ and to one class at most: polymorphic in P only, in Q only, in both, or monomorphic in each with
+ *                    different bases
+ *                u32 per (selected locus, slot or group), and `sites`; a selected locus whose sites reach 2^32 is refused
+ *   accumulators per (selected locus, slot) one double, E = E + e: one plain add a sample, rebuilt bit for bit
+ *   rows         per sample 1 + NS doubles: the iteration, then per slot sum_loci (double)use_group(slot) e -- the expected
+ *                number of SITES of the class among the usable ones; the loci of a workgroup's G consecutive selected loci are
+ *                added in selection order from 0.0, the workgroups' partial rows then in workgroup order from 0.0 (no fp atomics)
+ *   observed     the totals of obs, use and sites over the rank's selected loci, uint64
+ *   meaning      under the model and infinite sites obs / expected is 1 per slot; JC69 multiple hits lower the observed counts by
+ *                a relative amount of the order of the tree's length in substitutions per site.  No exactness is claimed beyond
+ *                the definitions above
+ *   _enable      capacity_rows per-sample rows; 0 frees everything, the feature is off.  loci as gph_engine_triplets_enable.
+ *                pairs: NULL = all, else npairs x 2 population indices in any order (npairs 0 with a non-null pointer: none); the
+ *                members are sorted, the pairs keep the caller's order.  GPH_EARG with a message that names the cause, nothing
+ *                freed or allocated: a locus index out of range, named twice or out of order; a locus whose sites reach 2^32; a
+ *                pair that names an index outside 0 .. Kc - 1, one population twice, a population without a sample, or is named
+ *                twice (after sorting); no slot at all (no population has two samples and no pair is taken); more than 255
+ *                leaves; more than 64 KB of LDS at one locus a workgroup.  GPH_EFULL, with the size in the message and the
+ *                feature off, when accumulators, tables and rows exceed max_bytes (<= 0: 1 GiB).  GPH_ESTATE before the loci are
+ *                loaded.  Enabling again frees and starts over.  k_sfs_data runs here, once.  gph_engine_init_genealogies zeroes
+ *                E, the sample count and the rows held; the data side stays
+ *   _sample      k_sfs_tree and the fold on the engine's stream, no host synchronisation; a rank without a selected locus
+ *                launches the fold alone.  GPH_EFULL when the row buffer is full; GPH_ESTATE when off or before
+ *                gph_engine_init_genealogies
+ *   _shape       NS, NG, G, selected loci of the rank, samples since E was zeroed, rows held (all 0 while off)
+ *   _slots       out[NS][5]: group, kind (0 a bin, 1 .. 4 privP, privQ, shared, fixed), P, Q (P again for a bin), k (0 for a class)
+ *   _fetch_loci  out[selected][ld], ld >= NS: E; reset != 0 zeroes E and the sample count afterwards
+ *   _fetch_observed  out[selected][ld], ld >= NS + NG + 1: obs per slot, use per group, sites; totals[NS + NG + 1] (may be NULL)
+ *   _fetch_rows  the rows taken since the last call, [rows][1 + NS]; the row buffer is empty again
+ *   _column_name col < NS: "sfs_<p>:<k>" or "privP_<P>|<Q>", "privQ_", "shared_", "fixed_"; NS <= col < NS + NG: the group, "<p>"
+ *                or "<P>|<Q>"; with the indices of the current populations
+ * The kernels write no page, draw no random number and touch no chain state.  Not built: a replicate-based (exact, p-valued)
+ * spectrum check through k_predictive's generator, unfolded spectra, joint spectra beyond the four classes. */
+int gph_engine_sfs_enable(gph_engine *e, int32_t capacity_rows, const int64_t *loci, int64_t nloci, const int32_t *pairs /* [npairs][2] */, int32_t npairs,
+                          int64_t max_bytes);
+int gph_engine_sfs_sample(gph_engine *e, int32_t iteration);
+int gph_engine_sfs_shape(gph_engine *e, int32_t *slots, int32_t *groups, int32_t *group, int64_t *selected, int64_t *samples, int32_t *rows_held);
+int gph_engine_sfs_selected(gph_engine *e, int64_t *out, int64_t max_loci, int64_t *count);
+int gph_engine_sfs_slots(gph_engine *e, int32_t *out /* [NS][5] */);
+int gph_engine_sfs_fetch_loci(gph_engine *e, double *out /* [selected][ld] */, int64_t ld, int32_t reset);
+int gph_engine_sfs_fetch_observed(gph_engine *e, uint32_t *out /* [selected][ld] */, int64_t ld, uint64_t *totals);
+int gph_engine_sfs_fetch_rows(gph_engine *e, double *out /* [rows][1 + NS] */, int32_t max_rows, int32_t *rows);
+const char *gph_engine_sfs_column_name(gph_engine *e, int32_t col);
+
 /* ------------------------------------------------------------------------------------
  * host MCMC driver: the iteration body of performMCMC (GPhoCS.c:1476-1821) above the
  * engine: general-slot RNG, priors, accept decisions of the global proposals
@@ -1326,6 +1397,35 @@ typedef struct gph_run_options {
    * histograms, pairs of ancestral populations, the output per heated or replicate chain, a control-file keyword. */
   const char *pair_times_prefix, *pair_times_pops, *pair_times_grid, *pair_times_loci;
   int32_t pair_times_rows;
+  /* `--sfs PREFIX [--sfs-pairs "A,B;C,D"|none] [--sfs-loci SPEC] [--sfs-rows N]`: site-frequency spectra, data against sampled
+   * genealogies (gph_engine_sfs_* above).  A sample is taken wherever a trace line is written.  sfs_pairs: the pairs as names of
+   * current populations of the control file, two a pair, pairs separated by ';', in any order; "none": no pair (NULL: all pairs);
+   * sfs_loci as gene_trees_loci; sfs_rows: the rows of the device buffer (0: a default).  Any of the three without sfs_prefix and
+   * negative rows are GPH_EARG with a message, before anything is read; an unknown population name, a pair that names one
+   * population twice, a pair named twice, and a model in which no population has two samples and no pair is taken are GPH_EARG
+   * with a message that names the option, once the control file is read and before the sequence file is.  Rank r writes its part
+   * PREFIX.sfs.part<r> once, at the end.  gph_sfs_write makes of the parts (numbers "%.10g"; S the samples)
+   *   PREFIX.sfs.tsv         header locus name samples sites, then use_<g> per group, then obs_<slot> exp_<slot> per slot with
+   *                          exp = (double)use E / S (0 for S = 0), then rel = sum obs / sum exp over the SPECTRUM slots (sums
+   *                          in slot order from 0.0; 0 where the denominator is 0); one row per selected locus in sequence-file
+   *                          order (the ranks' rows concatenated); names: "sfs_<p>:<k>", "privP_<P>|<Q>", "privQ_", "shared_",
+   *                          "fixed_" and "<p>", "<P>|<Q>" with the populations' names; a last line "# loci Q samples S slots NS"
+   *   PREFIX.sfs-genome.tsv  header iter and the slot names; one row of expected counts per sample, "%7d" and "\t%.10g" (the
+   *                          ranks' rows added in rank order from their doubles' 64-bit patterns); then, per slot and over the
+   *                          samples' rows as added,
+   *                              # observed   the data's totals (integers, the ranks' added)
+   *                              # mean       sum / S, the sum in sample order from 0.0
+   *                              # sd         sqrt(sum (v - mean)^2 / (S - 1)), 0 for S = 1
+   *                              # ratio      observed / mean, 0 where mean is 0
+   *                              # z          (observed - mean) / sqrt(mean + sd^2), 0 where the denominator is 0
+   *                          then "# loci Q samples S"
+   * and prints "SFS: <slot> observed <v> mean <v> ratio <v> z <v>" for the slot with the largest |z| (the first of equal ones)
+   * on stdout.  Both files are written once, on success only; a failed run leaves neither parts nor files.  With mc3_chains,
+   * replicates and marginal_prefix they describe chain 0 and the run proper; every other output is the same bytes with and
+   * without.  Not built: a replicate-based (exact, p-valued) spectrum check through k_predictive's generator, unfolded spectra,
+   * the output per heated or replicate chain, a control-file keyword. */
+  const char *sfs_prefix, *sfs_pairs, *sfs_loci;
+  int32_t sfs_rows;
 } gph_run_options;
 int gph_run(const gph_run_options *o);
 int gph_run_finish(const gph_run_options *o, int32_t ranks, int32_t failed);
@@ -1357,6 +1457,8 @@ int gph_simulate_write(const char *prefix, int32_t ranks);
 int gph_simulate_discard(const char *prefix, int32_t ranks);
 int gph_pair_times_write(const char *prefix, int32_t ranks);
 int gph_pair_times_discard(const char *prefix, int32_t ranks);
+int gph_sfs_write(const char *prefix, int32_t ranks);
+int gph_sfs_discard(const char *prefix, int32_t ranks);
 /* records of gph_engine_gene_trees_fetch as plain arrays (host only; any output pointer may be NULL).  Record r of `count`,
  * record_bytes apart, with the offsets and N of _shape: age[r][N] (copied, the bit patterns intact), father / left / right /
  * npop[r][N], root / num_migs[r] (num_migs clamped to 0 .. GPH_GT_MAX_MIGS), dataLnL / genLnL[r], and per live migration
